@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py - adversarial images / second of the hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, config, final_loss).
+--full measures everything else as well: the per-kernel event timings and the roofline (probed iterations inside the timed region),
+the other BASELINE configs and the CPU baselines (N = 1), the per-phase device times (N > 1).  --dump-outputs DIR writes what the
+last timed step returned (and a fixed sample of the model state it left) as DIR/<name>.npy in float32, 64 MB at most.
 
 N > 1 without a torchrun environment: this process stays off the GPU and starts `python -m torch.distributed.run
 --nproc-per-node N bench.py ...` as a child (one rank per GPU over RCCL), relays its output and exits with its code.
@@ -15,7 +20,7 @@ train() loop (Tiny_ImageNet/experiments_tinyimagenet.py:234-306): PGD-10 attack 
 random start) + forward on the adversarial batch + cross-entropy + backward + SGD(momentum, wd) update
 (+ the gradient all-reduce over RCCL when N > 1).  value = N * B * K / time (weak scaling), fp32 throughout.
 
-Printed JSON also carries
+With --full the printed JSON also carries
   roofline     : the dominant hand-written kernel = the family with the largest (launches x mean duration) among those
                  timed: algorithmic bytes per launch / its mean duration measured with HIP events on the launch
                  stream inside the timed region (one PGD iteration per attack runs outside the HIP graph so
@@ -243,6 +248,37 @@ class Job:
             return "DistributedDataParallel, eager update (EEADV_GRAD_SYNC=ddp)"
         return "flat %.1f MB in %d pieces, %s" % (self.sync.flat.numel() * 4 / 1e6, len(self.sync.pieces), self.sync.describe())
 
+    def outputs(self, last):
+        """What the step `last` came from hands its caller, by name: the training steps return (loss, logits) and leave the updated
+        model (and, free-AT, the persistent perturbation) behind; one batch of validate() returns its two losses and four top-k counts."""
+        if self.eval_only:
+            return dict(zip(("loss_clean", "loss_adv", "prec1_clean", "prec5_clean", "prec1_adv", "prec5_adv"), last))
+        out = {"loss": last[0], "logits": last[1]}
+        if self.free_at:
+            out["noise"] = self.noise
+        state = [v.detach().reshape(-1).float() for _, v in sorted(self.model.state_dict().items()) if v.is_floating_point()]
+        out["model_state"] = torch.cat(state)  # every floating-point entry of the state_dict, in key order
+        return out
+
+
+DUMP_MAX_ELEMENTS = 1 << 22  # 16 MB of float32 per array: at most four such (model state, free-AT noise) + the small ones stay under 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """DIR/<name>.npy in float32.  An array of more than DUMP_MAX_ELEMENTS entries is replaced by a fixed sample: the flat positions
+    np.random.default_rng(0) draws (sorted, without repeats; they depend on the size only), saved as <name>_sample.npy."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, t in arrays.items():
+        a = t.detach().float()
+        if a.numel() > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.numel(), DUMP_MAX_ELEMENTS, replace=False))
+            a, name = a.reshape(-1)[torch.from_numpy(idx).to(a.device)], name + "_sample"
+        np.save(os.path.join(dirname, name + ".npy"), a.cpu().numpy().astype(np.float32))
+        written[name] = list(a.shape)
+    return written
+
 
 def fence(world):
     torch.cuda.synchronize()
@@ -416,21 +452,28 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="measure beyond the headline figure: per-kernel timings and roofline (probed iterations, --probe-iters / "
+                         "--probe-every), the other BASELINE configs and the CPU baselines at N = 1, per-phase device times at N > 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (and a fixed sample of the model state it left) as "
+                         "DIR/<name>.npy, float32")
     ap.add_argument("--workload", default="tiny_ee_at", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=None, help="per-rank batch (default: the reference config's)")
     ap.add_argument("--no-graph", action="store_true", help="run every PGD iteration eagerly (no HIP graph)")
     ap.add_argument("--probe-iters", type=int, default=1,
-                    help="PGD iterations per attack that run outside the HIP graph so their kernels can be event-timed")
+                    help="with --full: PGD iterations per attack that run outside the HIP graph so their kernels can be event-timed")
     ap.add_argument("--probe-every", type=int, default=10,
-                    help="steps between two probed attacks (the eager probe iteration costs ~1 %% of a step; its kernels are the "
-                         "roofline samples, so at least one step of the timed region is always probed)")
+                    help="with --full: steps between two probed attacks (the eager probe iteration costs ~1 %% of a step; its kernels "
+                         "are the roofline samples, so at least one step of the timed region is always probed)")
     ap.add_argument("--large-batch", action="store_true",
                     help="also time the section-8 kernels alone at 16x the batch (off by default: those launches would enter the "
                          "rocprofv3 per-kernel averages of this command, which must agree with `roofline.avg_launch_us`)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-workloads", action="store_true", help="time only the headline workload")
-    ap.add_argument("--other-steps", type=int, default=10, help="timed steps of each of the other BASELINE configs")
-    ap.add_argument("--extras-timeout", type=int, default=420, help="seconds after which the headline line is printed without the extra legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-other-workloads", action="store_true", help="with --full: time only the headline workload")
+    ap.add_argument("--other-steps", type=int, default=10, help="with --full: timed steps of each of the other BASELINE configs")
+    ap.add_argument("--extras-timeout", type=int, default=420,
+                    help="with --full: seconds after which the headline line is printed without the extra legs")
     ap.add_argument("--dry-launch", action="store_true", help="only prove that --gpus N starts N ranks (gloo, no GPU needed)")
     ap.add_argument("--channels-last", action="store_true")
     ap.add_argument("--no-miopen-db", action="store_true",
@@ -471,7 +514,8 @@ def main():
     global MIOPEN_DB
     MIOPEN_DB = None if a.no_miopen_db else runtime.use_shipped_miopen_db()  # before the first convolution
     os.environ["EEADV_GRAPH"] = "0" if a.no_graph else "1"
-    engine.PROBE_ITERS = 0 if a.no_graph else a.probe_iters
+    # a plain run times the steps alone; --full brackets kernels with HIP events (probed iterations) and phases (N > 1) as well
+    engine.PROBE_ITERS = 0 if a.no_graph or not a.full else a.probe_iters
     job = Job(a.workload, cfg, dev, world, rank, channels_last=a.channels_last)
     B = cfg["batch"]
     probe_iters = engine.PROBE_ITERS
@@ -483,23 +527,26 @@ def main():
             if trainer.PHASE_EVENTS is not None:
                 trainer.PHASE_EVENTS.start()
             last = job.step(i)
-            ops.prof_mark_empty()  # one empty event bracket per step: the bracket's own cost, measured live
+            if a.full:
+                ops.prof_mark_empty()  # one empty event bracket per step: the bracket's own cost, measured live
         return last
 
-    bracket_cost_us = calibrate_bracket(ops, N, cfg, dev)
+    bracket_cost_us = calibrate_bracket(ops, N, cfg, dev) if a.full else None
     run(SETUP_STEPS)  # one-off setup, not warm-up: MIOpen algorithm search and the two HIP-graph captures (the update graph is
     fence(world)      # captured on the third step of a configuration) must not land in the timed region when W < 3
     run(a.warmup)
     fence(world)
-    ops.prof_reset()
-    ops.prof_enable(True)
-    if world > 1:
-        trainer.PHASE_EVENTS = trainer.PhaseEvents()  # per-rank device time of attack / backward / all-reduce / SGD
+    if a.full:
+        ops.prof_reset()
+        ops.prof_enable(True)
+        if world > 1:
+            trainer.PHASE_EVENTS = trainer.PhaseEvents()  # per-rank device time of attack / backward / all-reduce / SGD
     t0 = time.perf_counter()
     last = run(a.steps)
     fence(world)
     dt = time.perf_counter() - t0
-    ops.prof_enable(False)
+    if a.full:
+        ops.prof_enable(False)
     phases = trainer.PHASE_EVENTS.summary() if trainer.PHASE_EVENTS is not None else None
     trainer.PHASE_EVENTS = None
     if world > 1:
@@ -509,6 +556,39 @@ def main():
     loss_val = float(last[0].item())
     workload_text, grad_sync_text = job.describe(), job.grad_sync()
     non_default_switches = runtime.non_default_switches()
+    dumped = dump_outputs(a.dump_outputs, job.outputs(last)) if a.dump_outputs and rank == 0 else None
+
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "adversarial images/sec (%s, %s)" % ("free-AT x%d" % cfg["steps"] if cfg["method"] == "free_AT" else "PGD-%d" % cfg["steps"], cfg["arch"]),
+            "value": round(world * B * a.steps / dt, 2), "unit": "adversarial images/s", "n_gpus": world, "steps": a.steps,
+            "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": workload_text,
+                "global_batch": world * B, "rccl_ranks": dist.get_world_size() if world > 1 else 1,
+                "backend": dist.get_backend() if world > 1 else None, "grad_sync": grad_sync_text,
+                "switches": non_default_switches,
+                "rank0_phase_ms": phases, "setup_steps": SETUP_STEPS, "hip_graph": not a.no_graph, "miopen_db": "recorded" if MIOPEN_DB else None, "miopen_db_matched": _db_matched(),
+                "fallback_layers": _fallback_layers(job.model), "full": a.full, "probe_iters": probe_iters, "probe_every": a.probe_every if probe_iters else None,
+                "device": (N.lib.ee_device_name() or b"?").decode()},
+            "final_loss": round(loss_val, 5),
+            "note": "throughput is bounded by the classifier's fp32 convolutions (hand-written MFMA kernels + MIOpen) and BatchNorm launches, "
+                    "not by the front-end / update / loss kernels (3 % of an iteration); reference log (unrecorded GPU): ~143 img/s for "
+                    "this config (BASELINE.md)",
+        }
+        if dumped is not None:
+            out["outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
+        if world == 1 and a.large_batch:
+            out["kernels_large_batch"] = large_batch_kernels(cfg, dev)
+
+    if not a.full:  # the headline line is all a plain run prints
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     if rank == 0:
         C, H, W = cfg["shape"]
@@ -603,27 +683,7 @@ def main():
         roofline = roofline_of(dom)
         # the largest HBM-bound family as well (the fused front end), when a matrix-core family dominates
         roofline_hbm = roofline_of(dom_hbm) if dom_hbm != dom else None
-        out = {
-            "metric": "adversarial images/sec (%s, %s)" % ("free-AT x%d" % cfg["steps"] if cfg["method"] == "free_AT" else "PGD-%d" % cfg["steps"], cfg["arch"]),
-            "value": round(world * B * a.steps / dt, 2), "unit": "adversarial images/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload_text,
-                "global_batch": world * B, "rccl_ranks": dist.get_world_size() if world > 1 else 1,
-                "backend": dist.get_backend() if world > 1 else None, "grad_sync": grad_sync_text,
-                "switches": non_default_switches,
-                "rank0_phase_ms": phases, "setup_steps": SETUP_STEPS, "hip_graph": not a.no_graph, "miopen_db": "recorded" if MIOPEN_DB else None, "miopen_db_matched": _db_matched(),
-                "fallback_layers": _fallback_layers(job.model), "probe_iters": probe_iters, "probe_every": a.probe_every,
-                "device": (N.lib.ee_device_name() or b"?").decode()},
-            "roofline": roofline, "roofline_front_end": roofline_hbm, "kernels": kernels, "final_loss": round(loss_val, 5),
-            "note": "throughput is bounded by the classifier's fp32 convolutions (hand-written MFMA kernels + MIOpen) and BatchNorm launches, "
-                    "not by the front-end / update / loss kernels (3 % of an iteration); reference log (unrecorded GPU): ~143 img/s for "
-                    "this config (BASELINE.md)",
-        }
-        if world == 1 and a.large_batch:
-            out["kernels_large_batch"] = large_batch_kernels(cfg, dev)
-    else:
-        out = None
+        out.update({"roofline": roofline, "roofline_front_end": roofline_hbm, "kernels": kernels})
 
     # ---- everything below is outside the timed region of the headline workload; the ONE JSON line is printed at the very end, or by
     # the watchdog if an extra leg does not come back (a collective of a config that has never run on this node must not cost the line)

@@ -6,7 +6,7 @@ mkdir -p gpurun_out/miopen_db
 TICK=$!
 export MIOPEN_USER_DB_PATH=$PWD/gpurun_out/miopen_db
 export MIOPEN_FIND_ENFORCE=${1:-3}
-timeout -k 10 ${2:-900} python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-200
+timeout -k 10 ${2:-900} python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline 2>&1 | tail -1 | cut -c1-200
 kill $TICK
 unset MIOPEN_FIND_ENFORCE
 echo "--- with the tuned db, normal find:"

@@ -6,6 +6,7 @@ What is exact and what is not is spelled out in tests/replay.py: the update, sta
 classifier runs on MIOpen, so a free-running attack is compared through predictions + the fraction of identical pixels,
 and the step-by-step replay bounds every possible divergence by the gradient magnitude at the step where it happened.
 """
+import copy
 import os
 
 import numpy as np
@@ -352,14 +353,35 @@ def test_free_at_repeat_vs_oracle(arch, B, size, K, batches):
             assert np.array_equal(got[agree], noise_c[:B].numpy()[agree]), what
             assert agree.mean() > 0.98, (what, agree.mean())
             # parameter gradients of the same backward (they persist until the next zero_grad), same budget against fp64
-            num_g = num_c = den = 0.0
+            moved = [None] * len(trained(cpu))
+            if arch.endswith("_EE"):
+                # the front end on its own: the GPU's output (what its CNN saw) within 1e-6 of the fp64 oracle's, and no further
+                # from it than 4 x the fp32 oracle's (measured: 9.5e-7 and 2.5e-7; an edge bit gone the other way would be 1)
+                in1 = (x + before[:B]).clamp(0, 1)
+                with torch.no_grad():
+                    xin_g = gpu.front(in1.to(DEV)).cpu().double()
+                    xin_64, xin_c = cpu64.front(in1.double()), cpu.front(in1).double()
+                dev_g, dev_c = float((xin_g - xin_64).abs().max()), float((xin_c - xin_64).abs().max())
+                assert dev_g <= 4 * dev_c + 1e-6, (what, dev_g, dev_c)
+                # how far the EXACT parameter gradient itself moves when its CNN sees the GPU's front-end output instead of the
+                # oracle's: at batch 4 a train-mode ResNet-18 moves 0.2 - 0.7 % of a BatchNorm gradient for input changes of 1e-6
+                # (ReLU and max-pool switches within that distance of a tie), the same order as the 1 % floor below.  The GPU
+                # cannot be asked to land closer to fp64 than fp64 lands to itself under the deviation just bounded
+                body = copy.deepcopy(cpu64.net)  # the weights of this repeat (lr 0), batch statistics (train mode)
+                body.zero_grad(set_to_none=True)
+                ce(body(xin_g), y).backward()
+                moved = [float((pb.grad - p64.grad).norm()) for pb, p64 in zip(body.parameters(), cpu64.net.parameters())]
+                assert len(moved) == len(trained(cpu))
+            num_g = num_c = den = num_m = 0.0
             assert len(trained(cpu)) == len(trained(gpu))
-            for (n_, pc), pg, p64 in zip(cpu.named_parameters(), trained(gpu), cpu64.parameters()):
+            for (n_, pc), pg, p64, m in zip(cpu.named_parameters(), trained(gpu), cpu64.parameters(), moved):
                 r = p64.grad
                 eg, ec = float((pg.grad.cpu().double() - r).norm()), float((pc.grad.double() - r).norm())
-                assert eg <= 4 * ec + (1e-2 if arch.endswith("_EE") else 1e-6) * float(r.norm()) + 1e-12, (what, n_, eg, ec)
-                num_g, num_c, den = num_g + eg ** 2, num_c + ec ** 2, den + float(r.norm()) ** 2
-            assert num_g ** 0.5 <= 2 * num_c ** 0.5 + (5e-3 if arch.endswith("_EE") else 1e-6) * den ** 0.5, (what, num_g, num_c, den)
+                m = 0.0 if m is None else m
+                assert eg <= 4 * ec + 2 * m + (1e-2 if arch.endswith("_EE") else 1e-6) * float(r.norm()) + 1e-12, (what, n_, eg, ec, m)
+                num_g, num_c, den, num_m = num_g + eg ** 2, num_c + ec ** 2, den + float(r.norm()) ** 2, num_m + m ** 2
+            assert num_g ** 0.5 <= 2 * num_c ** 0.5 + 2 * num_m ** 0.5 + (5e-3 if arch.endswith("_EE") else 1e-6) * den ** 0.5, (
+                what, num_g, num_c, num_m, den)
     last = "w2" if arch == "tinynet" else "fc.weight"
     assert not torch.equal(gpu.state_dict()[last].cpu(), _body_state(arch, state)[last])
 
