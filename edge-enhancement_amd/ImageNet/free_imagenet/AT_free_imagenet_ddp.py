@@ -159,6 +159,7 @@ def main(argv=None, parser=None, build=build_model, dirs_of=output_dirs, eval_at
     """`parser`, `build`, `dirs_of`, `eval_attack`, `log_args`: what AT_hfs_canny_free_imagenet_ddp.py (the same loop over the
     edge-enhanced models) changes."""
     args = (parser or make_parser()).parse_args(argv)
+    driver.data_source(args.data, {})  # synthetic only: a dataset directory is refused before the device is touched
     torch.cuda.set_device(ddp.local_rank())
     device = torch.device("cuda", ddp.local_rank())
     ddp.setup(device)

@@ -8,8 +8,11 @@ exact log.txt line formats that utils/read_log.py parses.  Fixed while keeping t
 `type_canny` / `step_size_3` keys are tolerated, `--evaluate` runs the PGD evaluations instead of calling an
 undefined function, DataParallel is replaced by one process per GPU (eeadv.ddp).
 
-Data: the benchmark and the tests use seeded synthetic NCHW batches generated on the device (`--data synthetic`,
-optionally `synthetic:<n_train_batches>:<n_val_batches>`); the torchvision loaders are out of scope.
+Data: `--data synthetic` (optionally `synthetic:<n_train_batches>:<n_val_batches>`, what the benchmark and most tests use) gives
+seeded NCHW batches generated on the device.  A dataset directory is read by eeadv.data in place of the reference's
+torchvision loaders (utils/data_loader.py) for the scripts whose SPEC names a "data" kind - Tiny-ImageNet and MNIST: each split
+decoded once, cached as uint8, held on the device, one HIP launch per batch.  The ImageNet driver and the free-AT scripts stay
+synthetic-only (RandomResizedCrop / Resize + CenterCrop over 1.28 M JPEGs is not implemented) and refuse a directory.
 """
 import argparse
 import os
@@ -58,11 +61,28 @@ class SyntheticLoader:
         return iter(self.batches)
 
 
-def make_loaders(args, spec, device, batch_size):
-    if not str(args.data).startswith("synthetic"):
+def data_source(data, spec):
+    """"synthetic", or the dataset kind of spec["data"] when `data` is a directory of that kind's layout (eeadv.data.LAYOUTS);
+    anything else raises before any work is done."""
+    if str(data).startswith("synthetic"):
+        return "synthetic"
+    kind = spec.get("data")
+    if kind is None:
         raise NotImplementedError(
-            "only --data synthetic[:train_batches[:val_batches]] is supported: the torchvision dataset loaders of the "
-            "reference (utils/data_loader.py) are outside the hot path and torchvision is not available offline")
+            "--data %s: this script supports only --data synthetic[:train_batches[:val_batches]]; real Tiny-ImageNet and MNIST "
+            "directories are read by experiments_tinyimagenet.py and experiments_mnist.py" % data)
+    from . import data as D
+    if not D.recognised(kind, data):
+        raise NotImplementedError("--data %s is neither synthetic[:train_batches[:val_batches]] nor a %s directory: expected %s"
+                                  % (data, kind, D.LAYOUTS[kind]))
+    return kind
+
+
+def make_loaders(args, spec, device, batch_size):
+    kind = data_source(args.data, spec)
+    if kind != "synthetic":
+        from . import data as D
+        return D.make_loaders(kind, args.data, spec, device, batch_size, args.seed)  # the same seed on every rank
     parts = str(args.data).split(":")
     n_train = int(parts[1]) if len(parts) > 1 else 4
     n_val = int(parts[2]) if len(parts) > 2 else 2
@@ -214,6 +234,7 @@ def run(spec, build_model, argv=None):
     """main() of the reference drivers (experiments_tinyimagenet.py:50-213)."""
     parser = make_parser(spec["description"], with_local_rank=spec.get("ddp", False))
     args = parse_config_file(parser.parse_args(argv))
+    data_source(args.data, spec)  # an unusable --data fails here, before a model is built
     for key, default in (("type_canny", None), ("step_size_3", args.get("step_size_2")), ("num_steps_3", args.get("num_steps_2")),
                          ("n_queries", 1), ("cize", spec["shape"][-1]), ("beta", 1.0)):
         if key not in args:
@@ -268,6 +289,8 @@ def run(spec, build_model, argv=None):
     if args.evaluate:
         if sync is not None:
             sync.broadcast_buffers()
+        if hasattr(val_loader, "set_epoch"):
+            val_loader.set_epoch(args.start_epoch)
         for k, s in ((args.num_steps_1, args.step_size_1), (args.num_steps_2, args.step_size_2), (args.num_steps_3, args.step_size_3)):
             print("=> evaluate.tar_num_step:{},step_size:{}".format(k, s))
             validate(val_loader, net, criterion, args, device, k, s, dirs["log"], spec)
@@ -280,6 +303,9 @@ def run(spec, build_model, argv=None):
             adjust_learning_rate(optimizer, epoch, args.lr)  # experiments_imagenet.py
         else:
             adjust_learning_rate_1(optimizer, epoch, args.lr, args.epochs)
+        for loader in (train_loader, val_loader):
+            if hasattr(loader, "set_epoch"):
+                loader.set_epoch(epoch)  # the epoch's order and flips (eeadv.data.DeviceLoader): --resume at epoch k replays epoch k's
         train(train_loader, net, criterion, optimizer, epoch, args, device, dirs["log"], spec, sync)
         if sync is not None:
             sync.broadcast_buffers()  # rank 0's BatchNorm statistics are the model's, as under DistributedDataParallel

@@ -1257,6 +1257,26 @@ def net2_conv_wrw(x, da2, a2, saved, da1, drop=None, keep=1.0):
     return out[n2:n2 + n1].view(32, 1, 5, 5), out[n2 + n1 + 64:], out[:n2].view(64, 32, 5, 5), out[n2 + n1:n2 + n1 + 64]
 
 
+# ---- batch assembly from a device-resident dataset split (eeadv.data) -----------------------------------------------------
+def batch_u8(data, labels, idx, flip, lut):
+    """data [N,H,W,C] u8, labels [N] i64, idx [B] i32 sample ids, flip [N] u8 or None, lut [256] f32 ->
+    (x [B,C,H,W] f32 = lut[data[idx]] mirrored where flip[idx], HWC -> NCHW;  y [B] i64 = labels[idx]).  One launch."""
+    if data.dim() != 4:
+        raise ValueError("data must be [N,H,W,C], got shape %s" % (tuple(data.shape),))
+    n, H, W, C = data.shape
+    B = idx.shape[0]
+    pd = _chk(data, torch.uint8, "data")
+    pl = _chk(labels, torch.int64, "labels", (n,))
+    pi = _chk(idx, torch.int32, "idx", (B,))
+    pf = _opt(flip, torch.uint8, "flip", (n,))
+    pt = _chk(lut, torch.float32, "lut", (256,))
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=data.device)
+    y = torch.empty((B,), dtype=torch.int64, device=data.device)
+    N.check(N.lib.ee_batch_u8_f32(pd, pl, pi, pf, pt, n, B, C, H, W, _chk(out, torch.float32, "out"), _chk(y, torch.int64, "labels_out"),
+                                  _stream()), "ee_batch_u8_f32")
+    return out, y
+
+
 # ---- timing hooks ------------------------------------------------------------------------------------------------------
 def prof_enable(on=True):
     N.check(N.lib.ee_prof_enable(1 if on else 0), "ee_prof_enable")

@@ -601,6 +601,22 @@ int ee_chain_bwd_f32(const float *g_in, const uint8_t *gate, const float *gx, co
                      float lo, float hi, int dir, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batch assembly from a device-resident dataset split   (utils/data_loader.py: ImageFolder / MNIST
+ * + RandomHorizontalFlip + ToTensor, one batch of a DataLoader)
+ * ------------------------------------------------------------------------------------------- */
+
+/* data [N,H,W,C] u8 (one split as decoded, HWC), labels [N], idx [B] = the batch's sample ids (a slice of the
+ * epoch's order, any order, repeats allowed), flip [N] = per-sample mirror flag of the epoch (nullable: no flip),
+ * lut [256] = float(v) / 255 built by the caller (bit-identical to ToTensor by construction):
+ *     out[b,c,h,w] = lut[data[idx[b], h, flip[idx[b]] ? W-1-w : w, c]]      out [B,C,H,W] f32
+ *     labels_out[b] = labels[idx[b]]                                         labels_out [B]
+ * One launch.  C in {1, 3} (EE_ERR_UNSUPPORTED otherwise); out 4-byte aligned (EE_ERR_ALIGN), 16-byte aligned with
+ * W % 4 == 0 for the vector path; B == 0 launches nothing.  Precondition: 0 <= idx[b] < N; an id outside that range
+ * is not read - its outputs are NaN and its label -1. */
+int ee_batch_u8_f32(const uint8_t *data, const int64_t *labels, const int32_t *idx, const uint8_t *flip, const float *lut,
+                    long long N, int B, int C, int H, int W, float *out, int64_t *labels_out, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Optional built-in timing of the last launch of each kernel family (HIP events on `stream`).
  * Off by default; bench.py switches it on outside graph capture to measure kernel durations live.
  * ------------------------------------------------------------------------------------------- */
