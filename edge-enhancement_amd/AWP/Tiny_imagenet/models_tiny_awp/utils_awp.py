@@ -4,7 +4,7 @@ AWP/Cifar100/models_cifar100_awp/; called from experiments_tiny_awp.py:256-286 a
 SURVEY 2.1 #11 / 8(f5): AWP is a weight-space method that only CALLS the path; what is kept here is its interface - `diff_in_weights`,
 `add_into_weights`, `AdvWeightPerturb(model, proxy, proxy_optim, gamma)` with `.calc_awp(inputs_adv, targets)`, `.perturb(diff)`,
 `.restore(diff)` - so that the reference's AWP train loop runs on top of utils.attacks.PGD unchanged.  The PreActResNet model zoo of
-that sub-project is out of scope (any model of eeadv.models works as `model` / `proxy`).
+that sub-project is eeadv.preact (re-exported by this package); any model of eeadv.models works as `model` / `proxy` too.
 
 Arithmetic as the reference's, tensor by tensor: for every state_dict entry with more than one dimension whose key contains 'weight',
 diff = ||w_model|| / (||w_proxy - w_model|| + 1e-20) * (w_proxy - w_model); perturb / restore add +-gamma * diff to the parameters of

@@ -250,12 +250,15 @@ __global__ __launch_bounds__(NT) void bn_bwd_kernel(const float *__restrict__ dy
 // statistics and the normalisation run on registers), which removes two of the three dependent L2 round trips -------------
 __device__ __forceinline__ float relu_nan(float r) { return r > 0.0f ? r : (r != r ? r : 0.0f); }
 
-template <int NT, int MAXV, bool RELU, bool RES>
+// SUM (ee_bn_sum_act_fwd_f32, the block boundary of a pre-activation network): the statistics and the normalisation are those of
+// s = x + res, so every part reads the residual for ALL its register slots; s goes to sum_out (nullable) for the part's own slots.
+// RES and SUM are never both set.
+template <int NT, int MAXV, bool RELU, bool RES, bool SUM = false>
 __global__ __launch_bounds__(NT) void bn_fwd_cached_kernel(const float *__restrict__ x, const float *__restrict__ res,
                                                            const float *__restrict__ gamma, const float *__restrict__ beta,
                                                            float *running_mean, float *running_var, float momentum, float eps, int training,
                                                            float *__restrict__ y, float *__restrict__ save_mean,
-                                                           float *__restrict__ save_invstd, BnShape s) {
+                                                           float *__restrict__ save_invstd, BnShape s, float *__restrict__ sum_out) {
     __shared__ float scratch[3 * (NT / 64)];
     const int c = blockIdx.x;
     // gridDim.y = P workgroups per channel (round 4; few-channel layers: 64 channels fill 64 of 256 CUs).  Every one of them reads the whole
@@ -267,7 +270,7 @@ __global__ __launch_bounds__(NT) void bn_fwd_cached_kernel(const float *__restri
     const float n = static_cast<float>(s.B) * static_cast<float>(s.HW);
     const float4 *x4 = reinterpret_cast<const float4 *>(x);
     const float4 *r4 = reinterpret_cast<const float4 *>(res);
-    float4 xv[MAXV], rv[RES ? MAXV : 1];
+    float4 xv[MAXV], rv[(RES || SUM) ? MAXV : 1];
     unsigned off[MAXV];
     float acc = 0.0f;
     // every load is issued unconditionally on a clamped (always valid) element and masked afterwards: a load under a
@@ -279,6 +282,12 @@ __global__ __launch_bounds__(NT) void bn_fwd_cached_kernel(const float *__restri
         const int b = e / per, q = e - b * per;
         off[j] = static_cast<unsigned>(b * s.C + c) * static_cast<unsigned>(per) + static_cast<unsigned>(q);
         xv[j] = x4[off[j]];
+    }
+    if (SUM) {
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j) rv[j] = r4[off[j]];
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j) xv[j] = add4(xv[j], rv[j]);  // one fp32 add per element, as the reference's `out += shortcut`
     }
     if (RES) {  // needed only by the last pass: its latency hides behind the statistics.  Slots of other parts: a load of this part's first slot
         const int jf = (part * MAXV + P - 1) / P;  // (smallest j with j * P / MAXV == part)
@@ -324,6 +333,7 @@ __global__ __launch_bounds__(NT) void bn_fwd_cached_kernel(const float *__restri
     for (int j = 0; j < MAXV; ++j)
         if (static_cast<int>(threadIdx.x) + j * NT < total && j * P / MAXV == part) {
             const float4 v = xv[j];
+            if (SUM && sum_out) reinterpret_cast<float4 *>(sum_out)[off[j]] = v;
             float4 r = make_float4((v.x - mean) * a + b0, (v.y - mean) * a + b0, (v.z - mean) * a + b0, (v.w - mean) * a + b0);
             if (RES) {
                 const float4 q = rv[j];
@@ -336,14 +346,16 @@ __global__ __launch_bounds__(NT) void bn_fwd_cached_kernel(const float *__restri
         }
 }
 
-template <int NT, int MAXV, bool RELU>
+// ADD (ee_bn_sum_act_bwd_f32): dx += dadd on store - the gradient that reaches the normalised sum through the next block's identity branch;
+// loaded only for the part's own slots, like the forward's residual
+template <int NT, int MAXV, bool RELU, bool ADD = false>
 __global__ __launch_bounds__(NT) void bn_bwd_cached_kernel(const float *__restrict__ dy, const float *__restrict__ dy2, const float *__restrict__ y,
                                                            const float *__restrict__ x, const float *__restrict__ beta,
                                                            const float *__restrict__ gamma, const float *__restrict__ save_mean,
                                                            const float *__restrict__ save_invstd, const float *__restrict__ running_mean,
                                                            const float *__restrict__ running_var, float eps, int training,
                                                            float *__restrict__ dx, float *__restrict__ dres, float *__restrict__ dgamma,
-                                                           float *__restrict__ dbeta, BnShape s) {
+                                                           float *__restrict__ dbeta, BnShape s, const float *__restrict__ dadd) {
     __shared__ float scratch[3 * (NT / 64)];
     const int c = blockIdx.x;
     const int P = static_cast<int>(gridDim.y), part = static_cast<int>(blockIdx.y);  // as in bn_fwd_cached_kernel: the sums by every part, the stores split
@@ -367,6 +379,16 @@ __global__ __launch_bounds__(NT) void bn_bwd_cached_kernel(const float *__restri
         gv[j] = dy4[off[j]];
         hv[j] = x4[off[j]];
         if (RELU && y4) yv[j] = y4[off[j]];
+    }
+    float4 av[ADD ? MAXV : 1];
+    if (ADD) {  // slots of other parts: a load of this part's first slot (see bn_fwd_cached_kernel's residual)
+        const float4 *da4 = reinterpret_cast<const float4 *>(dadd);
+        const int jf = (part * MAXV + P - 1) / P;
+        unsigned of = off[0];
+#pragma unroll
+        for (int j = 1; j < MAXV; ++j) of = j == jf ? off[j] : of;
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j) av[j] = da4[(j * P / MAXV == part) ? off[j] : of];
     }
     const MaskArgs mk = mask_args(y, gamma, beta, invstd, c);
     if (dy24) {
@@ -409,8 +431,11 @@ __global__ __launch_bounds__(NT) void bn_bwd_cached_kernel(const float *__restri
         if (static_cast<int>(threadIdx.x) + j * NT < total && j * P / MAXV == part) {
             const float4 g = gv[j], h = hv[j];
             if (dres) dr4[off[j]] = g;
-            if (dx) dx4[off[j]] = make_float4(w * ((g.x - m1) - h.x * m2), w * ((g.y - m1) - h.y * m2), w * ((g.z - m1) - h.z * m2),
-                                              w * ((g.w - m1) - h.w * m2));
+            if (dx) {
+                float4 d = make_float4(w * ((g.x - m1) - h.x * m2), w * ((g.y - m1) - h.y * m2), w * ((g.z - m1) - h.z * m2), w * ((g.w - m1) - h.w * m2));
+                if (ADD) d = add4(d, av[j]);
+                dx4[off[j]] = d;
+            }
         }
 }
 
@@ -590,13 +615,13 @@ void launch_fwd_cached(bool relu, bool has_res, hipStream_t st, const float *x, 
                        float *rv, float momentum, float eps, int training, float *y, float *sm, float *si, BnShape s) {
     const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
     if (relu && has_res)
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, true, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s);
+        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, true, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, nullptr);
     else if (relu)
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, true, false>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s);
+        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, true, false>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, nullptr);
     else if (has_res)
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, false, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s);
+        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, false, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, nullptr);
     else
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, false, false>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s);
+        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, false, false>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, nullptr);
 }
 
 template <int NT, int MAXV>
@@ -605,9 +630,35 @@ void launch_bwd_cached(bool relu, hipStream_t st, const float *dy, const float *
                        float *dbeta, BnShape s) {
     const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
     if (relu)
-        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, dres, dgamma, dbeta, s);
+        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, dres, dgamma, dbeta, s, nullptr);
     else
-        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, dres, dgamma, dbeta, s);
+        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, dres, dgamma, dbeta, s, nullptr);
+}
+
+template <int NT, int MAXV>
+void launch_sum_fwd_cached(bool relu, hipStream_t st, const float *x, const float *res, const float *gamma, const float *beta, float *rm, float *rv,
+                           float momentum, float eps, int training, float *sum_out, float *y, float *sm, float *si, BnShape s) {
+    const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
+    if (relu)
+        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, true, false, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, sum_out);
+    else
+        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, false, false, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, sum_out);
+}
+
+template <int NT, int MAXV>
+void launch_sum_bwd_cached(bool relu, hipStream_t st, const float *dy, const float *dy2, const float *y, const float *x, const float *beta, const float *gamma,
+                           const float *sm, const float *si, const float *rm, const float *rv, float eps, int training, const float *dadd, float *dx,
+                           float *dgamma, float *dbeta, BnShape s) {
+    const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
+    float *const none = nullptr;
+    if (relu && dadd)
+        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, true, true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, none, dgamma, dbeta, s, dadd);
+    else if (relu)
+        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, true, false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, none, dgamma, dbeta, s, dadd);
+    else if (dadd)
+        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, false, true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, none, dgamma, dbeta, s, dadd);
+    else
+        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, false, false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, none, dgamma, dbeta, s, dadd);
 }
 
 // which cached variant holds a channel of `quads` float4s: 0 = none
@@ -1409,6 +1460,50 @@ EE_API int ee_bn_act_bwd_f32(const float *dy, const float *y, const float *x, co
     if (relu && !y) return EE_ERR_NULL;
     return ee_bn_act_bwd2_f32(dy, nullptr, y, x, gamma, nullptr, save_mean, save_invstd, running_mean, running_var, eps, training, relu, dx, dresidual, dgamma,
                               dbeta, workspace, B, C, HW, stream);
+}
+
+// ---- the block boundary of a pre-activation network (AWP/Tiny_imagenet/models_tiny_awp/preactresnet.py:28-34): a block ends with a bare
+// `out += shortcut`, the next one begins with relu(bn1(out)) and takes the raw sum as its identity input.  One launch each way on the
+// register-cached kernels (SUM / ADD flags); shapes they cannot hold are EE_ERR_UNSUPPORTED - the caller adds and calls ee_bn_act_fwd_f32.
+EE_API int ee_bn_sum_act_fwd_f32(const float *x, const float *res, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                                 float momentum, float eps, int training, int relu, float *sum_out, float *y, float *save_mean, float *save_invstd,
+                                 int B, int C, int HW, void *stream) {
+    if (B < 0 || C < 1 || HW < 1) return EE_ERR_SHAPE;
+    if (static_cast<int64_t>(B) * HW > 0x7fffffffLL) return EE_ERR_SHAPE;
+    if (B == 0) return EE_OK;
+    if (!x || !res || !y) return EE_ERR_NULL;
+    if (training && (!save_mean || !save_invstd)) return EE_ERR_NULL;
+    if (!training && (!running_mean || !running_var)) return EE_ERR_NULL;
+    if (HW % 4 || !al16(x) || !al16(res) || !al16(y) || !al16(sum_out)) return EE_ERR_UNSUPPORTED;
+    const BnShape s{B, C, HW};
+    hipStream_t st = as_stream(stream);
+    const int cv = cached_variant(static_cast<int64_t>(B) * (HW / 4), static_cast<int64_t>(B) * C * HW);
+    if (cv == 1) launch_sum_fwd_cached<256, 2>(relu != 0, st, x, res, gamma, beta, running_mean, running_var, momentum, eps, training, sum_out, y, save_mean, save_invstd, s);
+    else if (cv == 2) launch_sum_fwd_cached<256, 7>(relu != 0, st, x, res, gamma, beta, running_mean, running_var, momentum, eps, training, sum_out, y, save_mean, save_invstd, s);
+    else if (cv == 3) launch_sum_fwd_cached<1024, 7>(relu != 0, st, x, res, gamma, beta, running_mean, running_var, momentum, eps, training, sum_out, y, save_mean, save_invstd, s);
+    else return EE_ERR_UNSUPPORTED;
+    return launch_status();
+}
+
+EE_API int ee_bn_sum_act_bwd_f32(const float *dy, const float *dy2, const float *y, const float *s, const float *gamma, const float *beta,
+                                 const float *save_mean, const float *save_invstd, const float *running_mean, const float *running_var, float eps,
+                                 int training, int relu, const float *ds_add, float *ds, float *dgamma, float *dbeta, int B, int C, int HW,
+                                 void *stream) {
+    if (B < 0 || C < 1 || HW < 1) return EE_ERR_SHAPE;
+    if (static_cast<int64_t>(B) * HW > 0x7fffffffLL) return EE_ERR_SHAPE;
+    if (B == 0) return EE_OK;
+    if (!dy || !s || !ds) return EE_ERR_NULL;  // y == NULL with relu: the mask is recomputed from s, gamma, beta (the forward's expression)
+    if (training && (!save_mean || !save_invstd)) return EE_ERR_NULL;
+    if (!training && (!running_mean || !running_var)) return EE_ERR_NULL;
+    if (HW % 4 || !al16(dy) || !al16(dy2) || !al16(y) || !al16(s) || !al16(ds_add) || !al16(ds)) return EE_ERR_UNSUPPORTED;
+    const BnShape sh{B, C, HW};
+    hipStream_t st = as_stream(stream);
+    const int cv = cached_variant(static_cast<int64_t>(B) * (HW / 4), static_cast<int64_t>(B) * C * HW);
+    if (cv == 1) launch_sum_bwd_cached<256, 2>(relu != 0, st, dy, dy2, y, s, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, ds_add, ds, dgamma, dbeta, sh);
+    else if (cv == 2) launch_sum_bwd_cached<256, 7>(relu != 0, st, dy, dy2, y, s, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, ds_add, ds, dgamma, dbeta, sh);
+    else if (cv == 3) launch_sum_bwd_cached<1024, 7>(relu != 0, st, dy, dy2, y, s, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, ds_add, ds, dgamma, dbeta, sh);
+    else return EE_ERR_UNSUPPORTED;
+    return launch_status();
 }
 
 // floats of workspace ee_bn_relu_pool_fwd/bwd_f32 want (statistics partials forward, gradient-sum partials backward); 0 = unsupported shape

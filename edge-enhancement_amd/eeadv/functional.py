@@ -255,6 +255,36 @@ class BnDualFn(torch.autograd.Function):
         return (dxa, dxb, keep(dga, 2), keep(dba, 3), None, None, None, None, keep(dgb, 8), keep(dbb, 9)) + none[10:]
 
 
+class BnSumActFn(torch.autograd.Function):
+    """a = [relu](bn(x + res)) - the boundary between two pre-activation blocks (AWP/Tiny_imagenet/models_tiny_awp/preactresnet.py:28-34:
+    `out += shortcut`, then the next block's relu(bn1(out))) in one launch each way (ee_bn.hip, ee_bn_sum_act_*).  want_sum: return
+    (a, s) - s = x + res is the next block's identity input; its gradient is added inside the backward launch.  The backward returns the
+    same ds for x and res (the gradient of a sum)."""
+
+    @staticmethod
+    def forward(ctx, x, res, gamma, beta, running_mean, running_var, momentum, eps, training, relu, want_sum=False):
+        a, s, sm, si = ops.bn_sum_act_fwd(x, res, gamma, beta, running_mean, running_var, momentum, eps, training, relu, want_sum=True)
+        # the ReLU mask is recomputed from s with the forward's expression: a is not kept
+        ctx.save_for_backward(s, gamma, beta, sm, si, None if training else running_mean, None if training else running_var)
+        ctx.cfg = (eps, training, relu)
+        ctx.set_materialize_grads(False)
+        return (a, s) if want_sum else a
+
+    @staticmethod
+    def backward(ctx, da, ds_add=None):
+        s, gamma, beta, sm, si, rm, rv = ctx.saved_tensors
+        eps, training, relu = ctx.cfg
+        need = ctx.needs_input_grad
+        want_params = (need[2] or need[3]) and not _INPUT_GRAD_ONLY
+        none = (None,) * 9
+        if da is None:
+            return (ds_add if need[0] else None, ds_add if need[1] else None) + none
+        ds, dg, db = ops.bn_sum_act_bwd(da.contiguous(), None, None, s, gamma, beta, sm, si, rm, rv, eps, training, relu,
+                                        None if ds_add is None else ds_add.contiguous(), want_params)
+        return (ds if need[0] else None, ds if need[1] else None, dg if want_params and need[2] else None,
+                db if want_params and need[3] else None) + none[2:]
+
+
 _POOL_XA = os.environ.get("EEADV_POOL_XA", "1") != "0"  # the stem's BatchNorm backward sums from pooled tensors (A/B switch)
 
 

@@ -151,11 +151,17 @@ def head(avgpool, fc, x):
 def s2_pair(block, x):
     """(conv1(x), downsample[0](x)) of a down-sampling BasicBlock as one launch each way (functional.Conv3x3S2PairFn, ee_s2.hip), or None:
     both convolutions read the block's input, and the shortcut's 1x1 / stride 2 filter sees exactly the 3x3's centre tap."""
-    ds, c3 = block.downsample, block.conv1
-    if ("conv3" in _STOCK or "conv" in _STOCK or "s2small" in _STOCK or "s2pair" in _STOCK or ds is None or not isinstance(ds, nn.Sequential) or len(ds) != 2
-            or type(ds[0]) is not nn.Conv2d or type(c3) is not nn.Conv2d or not _dense_f32(x) or x.shape[2] != x.shape[3] or x.shape[2] not in (4, 8, 16)):
+    ds = block.downsample
+    if ds is None or not isinstance(ds, nn.Sequential) or len(ds) != 2:
         return None
-    c1 = ds[0]
+    return conv_s2_pair(block.conv1, ds[0], x)
+
+
+def conv_s2_pair(c3, c1, x):
+    """(c3(x), c1(x)) for a 3x3 / stride 2 convolution and a 1x1 / stride 2 one that read the same x (s2_pair), or None"""
+    if ("conv3" in _STOCK or "conv" in _STOCK or "s2small" in _STOCK or "s2pair" in _STOCK or type(c1) is not nn.Conv2d
+            or type(c3) is not nn.Conv2d or not _dense_f32(x) or x.shape[2] != x.shape[3] or x.shape[2] not in (4, 8, 16)):
+        return None
     if (c3.kernel_size != (3, 3) or c3.stride != (2, 2) or c3.padding != (1, 1) or c3.dilation != (1, 1) or c3.groups != 1 or c3.bias is not None
             or c3.padding_mode != "zeros" or c1.kernel_size != (1, 1) or c1.stride != (2, 2) or c1.padding != (0, 0) or c1.groups != 1 or c1.bias is not None
             or c1.in_channels != c3.in_channels or c1.out_channels != c3.out_channels or c3.in_channels % 32 or c3.out_channels % 32
@@ -163,6 +169,18 @@ def s2_pair(block, x):
         return None
     _route(c3, "ee_s2.pair"), _route(c1, "ee_s2.pair")
     return Conv3x3S2PairFn.apply(x, c3.weight, c1.weight)
+
+
+def conv1x1s2(cv, x):
+    """cv(x) for a 1x1 / stride 2 shortcut convolution on ee_conv.hip (functional.Conv1x1S2Fn, route recorded) where the kernel takes the
+    shape, else None"""
+    if ("conv" not in _STOCK and type(cv) is nn.Conv2d and _dense_f32(x) and cv.kernel_size == (1, 1) and cv.stride == (2, 2)
+            and cv.padding == (0, 0) and cv.bias is None and cv.groups == 1 and cv.in_channels % 2 == 0 and cv.out_channels % 2 == 0
+            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.shape[3] <= _CONV1X1S2_MAXW and cv.in_channels <= _CONV1X1S2_MAXC
+            and cv.weight.is_contiguous()):
+        _route(cv, "ee_conv.1x1s2")
+        return Conv1x1S2Fn.apply(x, cv.weight)
+    return None
 
 
 def block_tail(block, bn, out, x, fork, sc=None):
@@ -181,12 +199,8 @@ def block_tail(block, bn, out, x, fork, sc=None):
     if ("bn" not in _STOCK and "bndual" not in _STOCK and ds is not None and isinstance(ds, nn.Sequential) and len(ds) == 2 and type(ds[0]) is nn.Conv2d
             and type(ds[1]) is BatchNorm2d and type(bn) is BatchNorm2d and _dense_f32(x) and _dense_f32(out) and bn.affine and ds[1].affine
             and bn.track_running_stats and ds[1].track_running_stats and bn.training == ds[1].training and ops.bn_dual_supported(out)):
-        cv = ds[0]
-        if ("conv" not in _STOCK and cv.kernel_size == (1, 1) and cv.stride == (2, 2) and cv.padding == (0, 0) and cv.bias is None and cv.groups == 1
-                and cv.in_channels % 2 == 0 and cv.out_channels % 2 == 0 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
-                and x.shape[3] <= _CONV1X1S2_MAXW and cv.in_channels <= _CONV1X1S2_MAXC and cv.weight.is_contiguous()):
-            _route(cv, "ee_conv.1x1s2")
-            sc = Conv1x1S2Fn.apply(x, cv.weight)
+        sc = conv1x1s2(ds[0], x)
+        if sc is not None:
             if sc.shape == out.shape:
                 b2 = ds[1]
                 return BnDualFn.apply(out, sc, bn.weight, bn.bias, bn.running_mean, bn.running_var, 0.0 if bn.momentum is None else bn.momentum, bn.eps,
@@ -201,13 +215,10 @@ def shortcut(block, x):
     ds = block.downsample
     if ds is None:
         return x
-    if ("conv" not in _STOCK and isinstance(ds, nn.Sequential) and len(ds) == 2 and type(ds[0]) is nn.Conv2d and _dense_f32(x)):
-        cv = ds[0]
-        if (cv.kernel_size == (1, 1) and cv.stride == (2, 2) and cv.padding == (0, 0) and cv.bias is None and cv.groups == 1
-                and cv.in_channels % 2 == 0 and cv.out_channels % 2 == 0 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
-                and x.shape[3] <= _CONV1X1S2_MAXW and cv.in_channels <= _CONV1X1S2_MAXC and cv.weight.is_contiguous()):
-            _route(cv, "ee_conv.1x1s2")
-            return bn_act(ds[1], Conv1x1S2Fn.apply(x, cv.weight), relu=False)
+    if isinstance(ds, nn.Sequential) and len(ds) == 2:
+        sc = conv1x1s2(ds[0], x)
+        if sc is not None:
+            return bn_act(ds[1], sc, relu=False)
     if isinstance(ds, nn.Sequential) and len(ds) and isinstance(ds[0], nn.Conv2d):
         _route(ds[0], "miopen")
     return ds(x)
@@ -527,29 +538,34 @@ def train_mid_bn(block, xm):
     training drivers runs in train mode): bn1's batch statistics cross the kernel boundary between the two convolutions instead of a
     BatchNorm launch (functional.TrainConvBnConvFn / TrainPairBnConvFn; EEADV_STOCK_GLUE=trainfuse switches it off).  Returns conv2's raw
     output (and the shortcut convolution's for a down-sampling block), or None where it does not apply."""
-    bn = block.bn1
-    if ("trainfuse" in _STOCK or "bn" in _STOCK or "conv3" in _STOCK or "wino" in _STOCK or not block.training or not _fn.attack_forward_active()
+    ds = block.downsample
+    if ds is not None and (not isinstance(ds, nn.Sequential) or len(ds) != 2):
+        return None
+    return train_conv_bn_conv(block.training, block.bn1, block.conv1, block.conv2, None if ds is None else ds[0], xm)
+
+
+def train_conv_bn_conv(training, bn, conv1, conv2, c1, xm):
+    """train_mid_bn on its pieces: conv2(relu(bn(conv1(xm)))) [and c1(xm), the 1x1 / stride 2 shortcut convolution, or None], or None"""
+    if ("trainfuse" in _STOCK or "bn" in _STOCK or "conv3" in _STOCK or "wino" in _STOCK or not training or not _fn.attack_forward_active()
             or not _dense_f32(xm) or xm.dim() != 4 or xm.shape[2] != xm.shape[3] or type(bn) is not BatchNorm2d or not bn.training or not bn.affine
-            or not bn.track_running_stats or bn.weight.dtype != torch.float32 or not _plain_conv3(block.conv2, 1) or block.conv2.in_channels > 256):
+            or not bn.track_running_stats or bn.weight.dtype != torch.float32 or not _plain_conv3(conv2, 1) or conv2.in_channels > 256):
         return None
-    ds, hw = block.downsample, xm.shape[2]
+    hw = xm.shape[2]
     mom = 0.0 if bn.momentum is None else bn.momentum
-    if (hw if ds is None else hw // 2) not in _TRAINFUSE_MAPS:  # the CONSUMER's map: conv2 runs behind the block's stride
+    if (hw if c1 is None else hw // 2) not in _TRAINFUSE_MAPS:  # the CONSUMER's map: conv2 runs behind the block's stride
         return None
-    if ds is None:
-        if hw not in (4, 8, 16) or not _plain_conv3(block.conv1, 1):
+    if c1 is None:
+        if hw not in (4, 8, 16) or not _plain_conv3(conv1, 1):
             return None
-        _route(block.conv1, "ee_wino+stats"), _route(block.conv2, "ee_wino+bn(train)")
-        return TrainConvBnConvFn.apply(xm, block.conv1.weight, block.conv2.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps), None
-    if ("s2pair" in _STOCK or "s2small" in _STOCK or hw not in (8, 16) or not _plain_conv3(block.conv1, 2) or not isinstance(ds, nn.Sequential) or len(ds) != 2
-            or type(ds[0]) is not nn.Conv2d):
+        _route(conv1, "ee_wino+stats"), _route(conv2, "ee_wino+bn(train)")
+        return TrainConvBnConvFn.apply(xm, conv1.weight, conv2.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps), None
+    if "s2pair" in _STOCK or "s2small" in _STOCK or hw not in (8, 16) or not _plain_conv3(conv1, 2) or type(c1) is not nn.Conv2d:
         return None
-    c1 = ds[0]
-    if (c1.kernel_size != (1, 1) or c1.stride != (2, 2) or c1.padding != (0, 0) or c1.groups != 1 or c1.bias is not None or c1.in_channels != block.conv1.in_channels
-            or c1.out_channels != block.conv1.out_channels or not c1.weight.is_contiguous()):
+    if (c1.kernel_size != (1, 1) or c1.stride != (2, 2) or c1.padding != (0, 0) or c1.groups != 1 or c1.bias is not None or c1.in_channels != conv1.in_channels
+            or c1.out_channels != conv1.out_channels or not c1.weight.is_contiguous()):
         return None
-    _route(block.conv1, "ee_s2.pair+stats"), _route(c1, "ee_s2.pair+stats"), _route(block.conv2, "ee_wino+bn(train)")
-    return TrainPairBnConvFn.apply(xm, block.conv1.weight, c1.weight, block.conv2.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps)
+    _route(conv1, "ee_s2.pair+stats"), _route(c1, "ee_s2.pair+stats"), _route(conv2, "ee_wino+bn(train)")
+    return TrainPairBnConvFn.apply(xm, conv1.weight, c1.weight, conv2.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, mom, bn.eps)
 
 
 class BasicBlock(nn.Module):

@@ -591,6 +591,58 @@ def bn_act_bwd(dy, y, x, gamma, save_mean, save_invstd, running_mean, running_va
     return dx, dres, dg, db
 
 
+# ---- the block boundary of a pre-activation ResNet: [relu](bn(x + res)), the sum kept for the identity branch ------------------------
+def bn_sum_act_supported(x):
+    """1 for the shapes ee_bn_sum_act_*_f32 take: the register-cached kernels hold a channel (ee_bn.hip cached_variant: B*H*W <= 7 * 1024
+    float4s, H*W % 4 == 0); the caller adds and calls bn_act_fwd otherwise."""
+    if x.dim() != 4 or x.shape[0] < 1:
+        return False
+    HW = x.shape[2] * x.shape[3]
+    return HW % 4 == 0 and x.shape[0] * (HW // 4) <= 7 * 1024 and x.numel() // 4 <= 0xffffffff
+
+
+def bn_sum_act_fwd(x, res, gamma, beta, running_mean, running_var, momentum, eps, training, relu, want_sum=True):
+    """s = x + res; y = [relu](bn(s)), one launch; returns (y, s, save_mean, save_invstd) (s None unless asked for, the saves None in
+    eval mode).  Running statistics as bn_act_fwd."""
+    B, C = x.shape[0], x.shape[1]
+    HW = x[0, 0].numel() if B else 1
+    px = _chk(x, torch.float32, "x")
+    pr = _chk(res, torch.float32, "res", x.shape)
+    ptr = lambda t, name: None if t is None else _chk(t, torch.float32, name, (C,))
+    y = torch.empty_like(x)
+    s = torch.empty_like(x) if want_sum else None
+    sm = si = None
+    if training:
+        sm = torch.empty(C, dtype=torch.float32, device=x.device)
+        si = torch.empty(C, dtype=torch.float32, device=x.device)
+    N.check(N.lib.ee_bn_sum_act_fwd_f32(px, pr, ptr(gamma, "gamma"), ptr(beta, "beta"), ptr(running_mean, "running_mean"),
+                                        ptr(running_var, "running_var"), float(momentum), float(eps), 1 if training else 0, 1 if relu else 0,
+                                        None if s is None else s.data_ptr(), y.data_ptr(), None if sm is None else sm.data_ptr(),
+                                        None if si is None else si.data_ptr(), B, C, HW, _stream()), "ee_bn_sum_act_fwd_f32")
+    return y, s, sm, si
+
+
+def bn_sum_act_bwd(dy, dy2, y, s, gamma, beta, save_mean, save_invstd, running_mean, running_var, eps, training, relu, ds_add=None,
+                   want_dparams=True):
+    """Backward of bn_sum_act_fwd: (ds, dgamma, dbeta) - ds is the gradient of both x and res, with ds_add (the sum's other consumer) added
+    on store; dy2 a second piece of y's gradient; y=None with relu: the mask is recomputed from s, gamma and `beta`."""
+    B, C = s.shape[0], s.shape[1]
+    HW = s[0, 0].numel() if B else 1
+    pdy = _chk(dy, torch.float32, "dy", s.shape)
+    pdy2 = _opt(dy2, torch.float32, "dy2", s.shape)
+    py = _opt(y, torch.float32, "y", s.shape)
+    ps = _chk(s, torch.float32, "s")
+    pad = _opt(ds_add, torch.float32, "ds_add", s.shape)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    ds = torch.empty_like(s)
+    dg = torch.empty(C, dtype=torch.float32, device=s.device) if want_dparams else None
+    db = torch.empty(C, dtype=torch.float32, device=s.device) if want_dparams else None
+    N.check(N.lib.ee_bn_sum_act_bwd_f32(pdy, pdy2, py, ps, ptr(gamma), ptr(beta), ptr(save_mean), ptr(save_invstd), ptr(running_mean),
+                                        ptr(running_var), float(eps), 1 if training else 0, 1 if relu else 0, pad, ds.data_ptr(), ptr(dg),
+                                        ptr(db), B, C, HW, _stream()), "ee_bn_sum_act_bwd_f32")
+    return ds, dg, db
+
+
 # ---- SyncBatchNorm: the local halves around the two exchanges (ee_bn.hip; the collectives live in eeadv/syncbn.py) --------------------
 def syncbn_supported(x):
     return x.dim() >= 3 and x.shape[0] > 0 and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and N.lib.ee_syncbn_workspace_floats(

@@ -324,6 +324,20 @@ int ee_bn_dual_bwd_f32(const float *dy, const float *dy2, const float *y, const 
                        const float *running_mean_b, const float *running_var_b, float eps_b, int training, float *dxa, float *dxb,
                        float *dgamma_a, float *dbeta_a, float *dgamma_b, float *dbeta_b, int B, int C, int HW, void *stream);
 
+/* The block boundary of a pre-activation ResNet (AWP/Tiny_imagenet/models_tiny_awp/preactresnet.py:28-34): s = x + res (one fp32 add per
+ * element, as `out += shortcut`), sum_out <- s (nullable), y = [relu](bn(s)) with batch or running statistics; running_* / save_* exactly as
+ * ee_bn_act_fwd_f32.  Backward: dz = [y > 0] * (dy [+ dy2]); ds = BN-backward(dz) [+ ds_add] - the gradient of BOTH x and res; dy2 (the
+ * second consumer of y), ds_add (what reaches s through the next block's identity branch), dgamma, dbeta nullable; y nullable with relu:
+ * the mask is then recomputed from s, gamma and beta with the forward's expression.  One launch each way on the register-cached kernels
+ * (B*HW <= 28672, H*W % 4 == 0, 16-byte aligned tensors); other shapes return EE_ERR_UNSUPPORTED before any launch. */
+int ee_bn_sum_act_fwd_f32(const float *x, const float *res, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                          float momentum, float eps, int training, int relu, float *sum_out, float *y, float *save_mean, float *save_invstd,
+                          int B, int C, int HW, void *stream);
+int ee_bn_sum_act_bwd_f32(const float *dy, const float *dy2, const float *y, const float *s, const float *gamma, const float *beta,
+                          const float *save_mean, const float *save_invstd, const float *running_mean, const float *running_var, float eps,
+                          int training, int relu, const float *ds_add, float *ds, float *dgamma, float *dbeta, int B, int C, int HW,
+                          void *stream);
+
 /* relu(batch_norm(x)) followed by MaxPool2d(3, stride 2, padding 1) - the ResNet stem (resnet.py:113-117 / :148-150) - without
  * the full-resolution activation: forward x [B,C,H,W] -> y_pool [B,C,OH,OW] + one-byte argmax codes (OH = (H-1)/2+1); backward
  * dy_pool (+ dy_pool2, nullable: the second piece of the gradient, see ee_bn_act_bwd2_f32) + codes + x -> dx [B,C,H,W] (nullable),

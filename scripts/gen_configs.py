@@ -11,7 +11,8 @@ E255 = {1: 0.003921568627451, 2: 0.007843137254902, 16: 0.062745098039216}
 ORDER = ["method_name", "arch", "start_epoch", "epochs", "batch_size", "lr", "momentum", "weight_decay", "workers", "pin_memory",
          "print_freq", "seed", "epsilon", "num_steps_1", "step_size_1", "num_steps_2", "step_size_2", "num_steps_3", "step_size_3",
          "random", "beta", "cize", "alpha", "sigma", "w", "r", "gf", "low", "high", "n_queries", "type_canny", "nGPU",
-         "prob_start_from_clean", "label_smooth"]
+         "prob_start_from_clean", "label_smooth", "l2", "l1", "lr_schedule", "attack_iters", "attack_iters_test", "restarts", "pgd_alpha", "norm",
+         "half", "width_factor", "cutout", "chkpt_iters", "awp_gamma", "awp_warmup"]
 
 
 def emit(path, header, d):
@@ -48,6 +49,16 @@ def tiny(method, arch, step1, **kw):
 
 def imagenet(method, arch, step1, **kw):
     d = tiny(method, arch, step1, epochs=90, batch_size=256, weight_decay=0.0001, print_freq=100, cize=224, nGPU=4)
+    d.update(kw)
+    return d
+
+
+def awp(method, arch, **kw):
+    """AWP/Tiny_imagenet/configs_tiny_awp/*.yml: the keys experiments_tiny_awp.py reads, and those of its files it does not (kept)"""
+    d = dict(method_name=method, arch=arch, start_epoch=0, epochs=200, batch_size=100, l2=0, l1=0, lr_schedule="piecewise", lr=0.1, workers=2,
+             pin_memory=True, attack_iters=10, attack_iters_test=20, restarts=1, pgd_alpha=2.0, norm="l_inf", seed=0, half=False, width_factor=10,
+             cutout=False, chkpt_iters=10, awp_gamma=0.005, awp_warmup=0, momentum=0.9, weight_decay=0.0005, random=True, epsilon=E255[16],
+             num_steps_1=10, step_size_1=E255[2], num_steps_2=20, print_freq=50, alpha=0, sigma=0, w=0, r=0, gf=False, low=0, high=0)
     d.update(kw)
     return d
 
@@ -93,6 +104,10 @@ FILES = {
                                                                            **EE_I),
     "ImageNet/configs_imagenet/targeted_ee_trick_training.yml": imagenet("tarEE_trick", "resnet18_EE", 1, type_canny="CannyFilter",
                                                                           prob_start_from_clean=0.2, label_smooth=0.1, **EE_I),
+    "AWP/Tiny_imagenet/configs_tiny_awp/at_awp.yml": awp("AT_AWP", "PreActResNet18"),
+    "AWP/Tiny_imagenet/configs_tiny_awp/ee_at_awp.yml": awp("EE_AT_AWP", "PreActResNet18_EE", cize=64, **EE_T),
+    "AWP/Tiny_imagenet/configs_tiny_awp/ee_bpda_at_awp.yml": awp("EE_AT_AWP", "PreActResNet18_EE_BPDA", cize=64, **EE_T),
+    "AWP/Tiny_imagenet/configs_tiny_awp/ee_bpda_3_at_awp.yml": awp("EE_AT_AWP", "PreActResNet18_EE_BPDA_3", cize=64, **EE_T),
 }
 
 if __name__ == "__main__":
