@@ -651,75 +651,8 @@ def test_full_canny_module_and_ee_at_model_UNPINNED(Cm, golden):
     assert np.abs(g[fin] - gr[fin]).max() < 2e-4 * np.abs(gr[fin]).max() + 1e-7
 
 
-_ALL_STOCK = frozenset(("bn", "pool", "head", "conv", "stem", "dense", "conv3", "conv3s2"))
-
-
-def _body_run(models, depth, x, dl, stock, dt=torch.float32, wrap=None):
-    """one forward + backward of make_resnet(depth, 'tiny') from seed 21 in train mode -> (names, logits, gradients of input and parameters, net)"""
-    models._STOCK = stock
-    torch.manual_seed(21)
-    net = models.make_resnet(depth, "tiny").to(DEV).to(dt).train()
-    xi = x.to(dt).requires_grad_(True)
-    logits = net(xi)
-    grads = torch.autograd.grad(logits, [xi] + list(net.parameters()), dl.to(dt))
-    return ["input"] + [n for n, _ in net.named_parameters()], logits.detach(), grads, net
-
-
-def replayed_body_gradients(monkeypatch, depth, B, seed, fp32_stock=frozenset(("bnpool",))):
-    """The fused ResNet body in fp32, and the stock modules in float64 ON THE SAME PIECEWISE-LINEAR BRANCH: every ReLU mask and the stem
-    max-pool's argmax of the float64 run are the ones the fp32 run took.
-
-    Why: the gradient of a ReLU network is discontinuous in its pre-activations.  Of the ~3 M of them in ResNet-18 at batch 16 about one
-    lies within fp32 rounding of zero, its mask differs between ANY two implementations (fp32 stock against float64 too), and one flipped
-    mask on a 2x2 map of layer 4 moves the whole gradient by 0.2 - 0.7 % of its norm (scripts/fused_vs_stock_diag.py: the fused path is off
-    by 2.4e-6 of the norm on inputs without a flip and by 1.5e-3 ... 3.9e-3 on the others; the all-MIOpen path the same, at random from run
-    to run).  Holding the branch fixed leaves the arithmetic of the kernels, which is what this compares.
-    The stem runs as its two kernels here (BatchNorm+ReLU, then the max-pool): their one-pass fusion never materialises the ReLU output
-    that carries the mask (tests/test_gpu_kernels.py::test_bn_relu_pool_fused_equals_the_two_kernels pins it bit for bit to the pair)."""
-    from eeadv import models
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    x, dl = torch.rand(B, 3, 64, 64, generator=g).to(DEV), torch.randn(B, 200, generator=g).to(DEV)
-    masks, nested = [], [0]
-    bn_act, block_tail, stem_pool = models.bn_act, models.block_tail, models.stem_pool
-    first = lambda t: t[0] if isinstance(t, tuple) else t
-
-    def rec_bn_act(bn, x, residual=None, relu=True, fork=False):
-        out = bn_act(bn, x, residual, relu, fork)
-        if relu and not nested[0]:
-            masks.append(first(out).detach().clone())
-        return out
-
-    def rec_tail(*a, **k):  # the last ReLU of a block, however block_tail gets there (BnDualFn, or bn_act around the shortcut)
-        nested[0] += 1
-        try:
-            out = block_tail(*a, **k)
-        finally:
-            nested[0] -= 1
-        masks.append(first(out).detach().clone())
-        return out
-    monkeypatch.setattr(models, "bn_act", rec_bn_act)
-    monkeypatch.setattr(models, "block_tail", rec_tail)
-    names, logits32, g32, _ = _body_run(models, depth, x, dl, fp32_stock)
-    n_relu = len(masks)
-    todo = list(masks)
-
-    def replay_bn_act(bn, x, residual=None, relu=True, fork=False):
-        out = bn(x)
-        if residual is not None:
-            out = out + residual
-        return out * (todo.pop(0) > 0).to(out.dtype) if relu else out
-
-    def replay_pool(pool, x64):  # ATen's first-maximum rule on the fp32 activations (ee_pool.hip is bit-identical to it), applied to the float64 ones
-        idx = F.max_pool2d(masks[0], 3, 2, 1, return_indices=True)[1]
-        return x64.flatten(2).gather(2, idx.flatten(2)).view(idx.shape)
-    monkeypatch.setattr(models, "bn_act", replay_bn_act)
-    monkeypatch.setattr(models, "block_tail", block_tail)
-    monkeypatch.setattr(models, "stem_pool", replay_pool)
-    _, logits64, g64, _ = _body_run(models, depth, x, dl, _ALL_STOCK, torch.float64)
-    assert not todo and n_relu == {18: 17, 50: 49}[depth]
-    monkeypatch.setattr(models, "bn_act", bn_act)
-    monkeypatch.setattr(models, "stem_pool", stem_pool)
-    return names, logits32, g32, logits64, g64
+# the fp32 body and the float64 stock modules on the same ReLU branch: tests/branch_replay.py (shared with test_gpu_attack_route.py)
+from branch_replay import ALL_STOCK as _ALL_STOCK, body_run as _body_run, replayed_body_gradients  # noqa: E402
 
 
 @pytest.mark.parametrize("depth,B", [(18, 16), (50, 8)])

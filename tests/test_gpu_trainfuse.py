@@ -140,7 +140,9 @@ def _grad_and_state(model, x, y):
 def test_train_mode_attack_gradient_with_and_without_the_boundary_exchange(monkeypatch):
     """the train-mode classifier inside the attack loop: input gradient and running statistics with bn1's statistics crossing the kernel
     boundary against the BatchNorm-launch path (EEADV_STOCK_GLUE=trainfuse).  The two differ by the summation order of the statistics; a ReLU
-    whose pre-activation sits within rounding of zero may flip between them (one flip moves the gradient by ~2e-3 of its norm)."""
+    whose pre-activation sits within rounding of zero may flip between them (one flip moves the gradient by ~2e-3 of its norm).
+    The 1e-2 below is therefore a statement about mask flips, not about the kernels' arithmetic: the precision claim for this route is carried by
+    tests/test_gpu_attack_route.py, which holds the ReLU branch fixed and compares with float64 (a few 1e-6 of the gradient's norm)."""
     import copy
     from eeadv import models as M
     monkeypatch.setattr(M, "_TRAINFUSE_MAPS", frozenset([16, 8, 4]))  # every block the kernels take, not only the default (16x16 maps)
