@@ -140,6 +140,8 @@ SIGNATURES = {
     "ee_ce_pool_linear_bwd_f32": [c_p, c_p, c_f, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     # data, labels, idx, flip, lut, N, B, C, H, W, out, labels_out, stream
     "ee_batch_u8_f32": [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
+    # pixels, nbytes, offsets, sizes, labels, idx, boxes, flip, lut, N, B, S, out, labels_out, stream
+    "ee_batch_rrc_u8_f32": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p],
     "ee_prof_enable": [c_i],
     "ee_prof_mark_empty": [c_p],
     "ee_prof_read": [c_i, c_p, c_p],

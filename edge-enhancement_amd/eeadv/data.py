@@ -1,6 +1,6 @@
-"""Real Tiny-ImageNet and MNIST for the drivers, held whole in device memory.
+"""Real Tiny-ImageNet, MNIST and ImageNet for the drivers, held whole in device memory.
 
-The reference (utils/data_loader.py) reads both with torchvision: ImageFolder + PIL + RandomHorizontalFlip (Tiny train) +
+The reference (utils/data_loader.py) reads the first two with torchvision: ImageFolder + PIL + RandomHorizontalFlip (Tiny train) +
 ToTensor in DataLoader workers, and datasets.MNIST + ToTensor.  Here each split is decoded once on the host into uint8
 [N,H,W,C] + int64 labels, cached on disk, uploaded to the device once, and every batch is assembled by ONE launch of
 ee_batch_u8_f32 (gather the epoch's sample ids, mirror the flagged ones, u8 -> f32 / 255 through a table built with torch's
@@ -18,7 +18,25 @@ Kept semantics
     drop_last (the last batch may be partial).  The reference's draws depend on DataLoader worker seeding and cannot be
     reproduced; the distribution is kept: a uniform permutation per epoch, each sample mirrored with probability 1/2 per epoch.
 
-Not kept: the images must already be H x W (the reference has no resize either; a different size is an error naming the file).
+Not kept: Tiny / MNIST images must already be H x W (the reference has no resize either; a different size is an error naming the file).
+
+ImageNet (utils/data_loader.py:98-120: ImageFolder + RandomResizedCrop(224) + RandomHorizontalFlip + ToTensor for train,
+Resize(256) + CenterCrop(224) + ToTensor for val)
+  - train: every file is decoded once (convert('RGB')) and kept at its own size in one ragged uint8 buffer (HWC images back to
+    back + byte offsets + (H, W) + labels), cached as one .npz and uploaded once.  A batch is ONE launch of ee_batch_rrc_u8_f32:
+    crop the epoch's box of each sample, resample it to S x S, mirror, u8 -> f32 through LUT, HWC -> NCHW.  torchvision resizes
+    PIL images, and PIL's 8-bit BILINEAR resample is integer fixed-point arithmetic (two passes, 22-bit coefficients formed in
+    double); `resample_u8` restates it in numpy and the kernel restates it again, so a batch is ToTensor(resize(crop(img)))
+    bit for bit.  `host_batch_rrc` is that restatement for a batch (and what --no-cuda runs).
+  - the boxes are RandomResizedCrop.get_params (scale (0.08, 1), ratio (3/4, 4/3), 10 tries, central fallback), drawn on the
+    host for the whole split per epoch from torch.Generator(seed + epoch) after the order and the flips, indexed by sample id
+    (so they do not depend on world size) and uploaded once per epoch.  As for the flips, the reference's own draws depend on
+    DataLoader worker seeding and cannot be reproduced; the distribution is kept.
+  - val: Resize + CenterCrop is deterministic, so it is applied once at decode by PIL itself and the split is cached as fixed
+    [N,S,S,3]; it is served by DeviceLoader / ee_batch_u8_f32 like Tiny's.
+  - the train split must fit in device memory next to the model (checked before the upload, DataError otherwise).  Departure
+    from the reference, off by default: EEADV_IMAGENET_SHORT=<pixels> shrinks, at decode, every train image whose shorter side
+    exceeds it to that shorter side (PIL BILINEAR, aspect ratio kept); the value is part of the cache key.
 """
 import gzip
 import hashlib
@@ -38,6 +56,7 @@ MNIST_FILES = {"train": ("train-images-idx3-ubyte", "train-labels-idx1-ubyte"), 
 LAYOUTS = {
     "tiny_imagenet": "<root>/train/<wnid>/**/*.JPEG and <root>/val/ (val/<wnid>/... or val/images/ + val/val_annotations.txt)",
     "mnist": "the IDX files {train,t10k}-{images-idx3,labels-idx1}-ubyte[.gz] in <root>/MNIST/raw/ or <root>/",
+    "imagenet": "<root>/train/<wnid>/**/*.JPEG and <root>/val/<wnid>/**/*.JPEG (the same class directories in both)",
 }
 _CHUNK = 512  # images per decode task
 
@@ -110,7 +129,7 @@ def recognised(kind, root):
     """Does `root` look like a `kind` dataset directory (LAYOUTS)?  Nothing is decoded."""
     if not os.path.isdir(root):
         return False
-    if kind == "tiny_imagenet":
+    if kind in ("tiny_imagenet", "imagenet"):
         return os.path.isdir(os.path.join(root, "train")) and os.path.isdir(os.path.join(root, "val"))
     if kind == "mnist":
         return all(_mnist_file(root, n) for pair in MNIST_FILES.values() for n in pair)
@@ -162,21 +181,21 @@ def cache_key(root, parts, files):
     return hashlib.sha256(blob.encode()).hexdigest()[:24]
 
 
-def cached(root, name, build):
-    """(images, labels) from <cache_dir(root)>/<name>, or build() them and publish the file atomically (temporary name +
+def cached(root, name, build, keys=("images", "labels")):
+    """The arrays `keys` from <cache_dir(root)>/<name>, or build() them and publish the file atomically (temporary name +
     os.replace: concurrent ranks at worst decode twice, none reads a half-written file).  An unwritable cache directory
     leaves the split decoded in memory only."""
     d = cache_dir(root)
     path = os.path.join(d, name)
     if os.path.isfile(path):
         with np.load(path) as z:
-            return z["images"], z["labels"]
-    images, labels = build()
+            return tuple(z[k] for k in keys)
+    arrays = tuple(build())
     tmp = "%s.%d.tmp" % (path, os.getpid())
     try:
         os.makedirs(d, exist_ok=True)
         with open(tmp, "wb") as f:
-            np.savez(f, images=images, labels=labels)
+            np.savez(f, **dict(zip(keys, arrays)))
         os.replace(tmp, path)
     except OSError as exc:
         print("eeadv.data: cache directory %s is not writable (%s): %s is decoded in memory only" % (d, exc.strerror or exc, name))
@@ -184,7 +203,7 @@ def cached(root, name, build):
             os.remove(tmp)
         except OSError:
             pass
-    return images, labels
+    return arrays
 
 
 def load_tiny_imagenet(root, split, shape=(3, 64, 64), num_classes=200):
@@ -241,6 +260,184 @@ def load_mnist(root, split, shape=(1, 28, 28), num_classes=10):
     return images.reshape(images.shape + (1,)).copy(), labels.astype(np.int64)
 
 
+# ---- ImageNet -----------------------------------------------------------------------------------------------------------------
+def imagenet_listing(root, split, num_classes):
+    """(classes, [(path, label)]) of ImageNet's `train` or `val` split: ImageFolder over <root>/<split>/<wnid>/**."""
+    train = os.path.join(root, "train")
+    if not os.path.isdir(train):
+        raise DataError("%s does not exist" % train)
+    classes = find_classes(train)
+    if len(classes) != num_classes:
+        raise DataError("%s holds %d class directories, expected %d" % (train, len(classes), num_classes))
+    if split == "train":
+        return classes, image_folder(train, classes)[1]
+    val = os.path.join(root, "val")
+    if not os.path.isdir(val):
+        raise DataError("%s does not exist" % val)
+    if find_classes(val) != classes:
+        raise DataError("the class directories of %s differ from those of %s" % (val, train))
+    return classes, image_folder(val, classes)[1]
+
+
+def imagenet_short():
+    """EEADV_IMAGENET_SHORT as an int (0 = off): the shorter side train images are shrunk to at decode."""
+    v = os.environ.get("EEADV_IMAGENET_SHORT", "").strip()
+    if not v:
+        return 0
+    if not v.isdigit() or int(v) < 1:
+        raise DataError("EEADV_IMAGENET_SHORT=%s: expected a number of pixels >= 1" % v)
+    return int(v)
+
+
+def resized_size(w, h, short):
+    """torchvision's Resize(short) on a w x h image: the shorter side becomes `short`, the longer int(short * long / short side)."""
+    if w <= h:
+        return short, int(short * h / w)
+    return int(short * w / h), short
+
+
+def _decode_ragged(job):
+    from PIL import Image
+    paths, short = job
+    out = []
+    for p in paths:
+        with open(p, "rb") as f:
+            img = Image.open(f).convert("RGB")
+        if short and min(img.size) > short:
+            img = img.resize(resized_size(img.size[0], img.size[1], short), Image.BILINEAR)
+        out.append(np.asarray(img, dtype=np.uint8).reshape(img.size[1], img.size[0], 3))
+    sizes = np.array([a.shape[:2] for a in out], dtype=np.int32).reshape(len(out), 2)
+    return np.concatenate([a.reshape(-1) for a in out]) if out else np.empty(0, np.uint8), sizes
+
+
+def _decode_val(job):
+    from PIL import Image
+    paths, S, resize = job
+    out = np.empty((len(paths), S, S, 3), dtype=np.uint8)
+    for i, p in enumerate(paths):
+        with open(p, "rb") as f:
+            img = Image.open(f).convert("RGB")
+        size = resized_size(img.size[0], img.size[1], resize)
+        if size != img.size:
+            img = img.resize(size, Image.BILINEAR)
+        top, left = int(round((size[1] - S) / 2.0)), int(round((size[0] - S) / 2.0))  # torchvision's center_crop
+        out[i] = np.asarray(img.crop((left, top, left + S, top + S)), dtype=np.uint8)
+    return out
+
+
+def _pool_map(fn, jobs):
+    """fn over jobs in order, by up to 16 forked processes (the CPUs this process may run on, not the machine's)."""
+    procs = min(16, len(os.sched_getaffinity(0)), len(jobs))
+    if procs <= 1:
+        return [fn(j) for j in jobs]
+    with multiprocessing.get_context("fork").Pool(procs) as pool:  # the workers only run PIL + numpy, never the device
+        return list(pool.imap(fn, jobs))
+
+
+def load_imagenet(root, split, shape=(3, 224, 224), num_classes=1000, resize=256):
+    """ImageNet `train` as the ragged (pixels uint8 [sum H*W*3], offsets int64 [N], sizes int32 [N,2] = (H, W), labels int64 [N]),
+    `val` as (uint8 [N,S,S,3], int64 [N]) after Resize(resize) + CenterCrop(S); decoded once, then read from the cache."""
+    C, S, S2 = shape
+    if C != 3 or S != S2 or resize < S:
+        raise DataError("ImageNet batches are 3 x S x S with S <= the resize size, got shape %s and resize %d" % (tuple(shape), resize))
+    classes, samples = imagenet_listing(root, split, num_classes)
+    if not samples:
+        raise DataError("no images in the %s split of %s" % (split, root))
+    paths = [p for p, _ in samples]
+    labels = np.array([lab for _, lab in samples], dtype=np.int64)
+    if split == "val":
+        key = cache_key(root, ["imagenet", "val", list(shape), resize, classes], paths)
+
+        def build_val():
+            print("eeadv.data: decoding %d images of %s/val" % (len(paths), root))
+            parts = _pool_map(_decode_val, [(paths[i:i + _CHUNK], S, resize) for i in range(0, len(paths), _CHUNK)])
+            return np.concatenate(parts), labels
+        return cached(root, "imagenet-val-%s.npz" % key, build_val)
+    short = imagenet_short()
+    key = cache_key(root, ["imagenet", "train", short, classes], paths)
+
+    def build():
+        print("eeadv.data: decoding %d images of %s/train%s" % (len(paths), root, " (shorter side <= %d)" % short if short else ""))
+        parts = _pool_map(_decode_ragged, [(paths[i:i + _CHUNK], short) for i in range(0, len(paths), _CHUNK)])
+        sizes = np.concatenate([s for _, s in parts])
+        nbytes = sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3
+        offsets = np.concatenate([np.zeros(1, np.int64), np.cumsum(nbytes)[:-1]])
+        return np.concatenate([p for p, _ in parts]), offsets, sizes, labels
+    return cached(root, "imagenet-train-%s.npz" % key, build, keys=("pixels", "offsets", "sizes", "labels"))
+
+
+# PIL's 8-bit resample (ImagingResample, BILINEAR): coefficients in double, then 22-bit fixed point
+_PRECISION_BITS = 22
+
+
+def resample_coeffs(n_in, n_out):
+    """(xmin int64 [n_out], n int64 [n_out], k int64 [n_out, ksize]) of one axis: result pixel xx is
+    clip8((2^21 + sum_{x < n[xx]} src[xmin[xx] + x] * k[xx, x]) >> 22); k is 0 at x >= n[xx]."""
+    scale = float(n_in) / float(n_out)
+    fs = max(scale, 1.0)
+    support = fs
+    ksize = int(np.ceil(support)) * 2 + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(0, np.trunc(center - support + 0.5).astype(np.int64))
+    n = np.minimum(n_in, np.trunc(center + support + 0.5).astype(np.int64)) - xmin
+    x = np.arange(ksize, dtype=np.int64)[None, :]
+    w = np.maximum(0.0, 1.0 - np.abs(((x + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) / fs))
+    w[x >= n[:, None]] = 0.0
+    ww = np.zeros(n_out, dtype=np.float64)
+    for j in range(ksize):  # the sum in ascending x, as PIL forms it
+        ww = ww + w[:, j]
+    w = w / ww[:, None]
+    return xmin, n, np.trunc(0.5 + w * float(1 << _PRECISION_BITS)).astype(np.int64)
+
+
+def _resample_axis1(a, n_out):
+    """a uint8 [R, n_in, C] -> uint8 [R, n_out, C] along axis 1."""
+    xmin, _, k = resample_coeffs(a.shape[1], n_out)
+    acc = np.full((a.shape[0], n_out, a.shape[2]), 1 << (_PRECISION_BITS - 1), dtype=np.int64)
+    for j in range(k.shape[1]):
+        acc += a[:, np.minimum(xmin + j, a.shape[1] - 1), :].astype(np.int64) * k[None, :, j, None]
+    return np.clip(acc >> _PRECISION_BITS, 0, 255).astype(np.uint8)
+
+
+def resample_u8(img, out_h, out_w):
+    """PIL's Image.resize((out_w, out_h), BILINEAR) of a uint8 [H,W,C] array, byte for byte: the horizontal pass to uint8, then
+    the vertical pass over that.
+
+    The one exception, stated here for the kernel and the documents too: Image.resize takes the vertical pass first when the image
+    (here: the crop) has H > 100 W and out_h < H.  At W = 1 the horizontal pass copies its single pixel (one coefficient, 2^22), so
+    the order cannot change a byte; at W >= 2 some bytes then differ by one.  So the bytes are PIL's except for H > 100 W with
+    W >= 2 and out_h < H.  RandomResizedCrop's ratio range [3/4, 4/3] never draws such a crop, and the kernel keeps this order."""
+    tmp = _resample_axis1(np.ascontiguousarray(img), out_w)
+    return _resample_axis1(tmp.transpose(1, 0, 2), out_h).transpose(1, 0, 2)
+
+
+def rrc_boxes(sizes, generator, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """torchvision's RandomResizedCrop.get_params for every image of `sizes` [N,2] = (H, W) at once -> int32 [N,4] = (top, left,
+    h, w): up to 10 tries of area * U(scale) and exp(U(log ratio)), w = round(sqrt(a * r)), h = round(sqrt(a / r)), the first
+    try with 0 < w <= W and 0 < h <= H at a uniform integer position; otherwise the central crop with the ratio clamped."""
+    sizes = torch.as_tensor(np.asarray(sizes)).to(torch.int64).reshape(-1, 2)
+    n = sizes.shape[0]
+    H, W = sizes[:, 0], sizes[:, 1]
+    area = (H * W).double()[:, None]
+    target = area * (scale[0] + (scale[1] - scale[0]) * torch.rand(n, 10, dtype=torch.float64, generator=generator))
+    lo, hi = np.log(ratio[0]), np.log(ratio[1])
+    aspect = torch.exp(lo + (hi - lo) * torch.rand(n, 10, dtype=torch.float64, generator=generator))
+    w = torch.round(torch.sqrt(target * aspect)).to(torch.int64)  # round half to even, as Python's round()
+    h = torch.round(torch.sqrt(target / aspect)).to(torch.int64)
+    ok = (w > 0) & (w <= W[:, None]) & (h > 0) & (h <= H[:, None])
+    first = torch.argmax(ok.to(torch.int8), dim=1, keepdim=True)
+    found = ok.any(dim=1)
+    w, h = w.gather(1, first)[:, 0], h.gather(1, first)[:, 0]
+    u = torch.rand(n, 2, dtype=torch.float64, generator=generator)
+    top = torch.minimum((u[:, 0] * (H - h + 1).double()).to(torch.int64), H - h)
+    left = torch.minimum((u[:, 1] * (W - w + 1).double()).to(torch.int64), W - w)
+    in_ratio = W.double() / H.double()
+    fw = torch.where(in_ratio > ratio[1], torch.round(H.double() * ratio[1]).to(torch.int64), W)
+    fh = torch.where(in_ratio < ratio[0], torch.round(W.double() / ratio[0]).to(torch.int64), H)
+    box = torch.where(found[:, None], torch.stack([top, left, h, w], 1), torch.stack([(H - fh) // 2, (W - fw) // 2, fh, fw], 1))
+    return box.to(torch.int32)
+
+
 # ---- batches ------------------------------------------------------------------------------------------------------------------
 def host_batch(images, labels, ids, flip):
     """The batch on the host with torch ops: what ee_batch_u8_f32 computes (and --no-cuda runs)."""
@@ -248,6 +445,22 @@ def host_batch(images, labels, ids, flip):
     if flip is not None:
         f = flip[ids].bool()
         x[f] = x[f].flip(-1)
+    return x, labels[ids]
+
+
+def host_batch_rrc(pixels, offsets, sizes, labels, ids, boxes, flip, S):
+    """The ImageNet train batch on the host: what ee_batch_rrc_u8_f32 computes (and --no-cuda runs).  pixels uint8 [bytes],
+    offsets int64 [N], sizes int32 [N,2], labels int64 [N], ids int64 [B], boxes int32 [N,4], flip bool / uint8 [N] or None."""
+    pix = pixels.numpy()
+    x = torch.empty((len(ids), 3, S, S), dtype=torch.float32)
+    for b, s in enumerate(ids.tolist()):
+        H, W = sizes[s].tolist()
+        top, left, h, w = boxes[s].tolist()
+        img = pix[int(offsets[s]):int(offsets[s]) + H * W * 3].reshape(H, W, 3)
+        r = torch.from_numpy(resample_u8(img[top:top + h, left:left + w], S, S))
+        if flip is not None and bool(flip[s]):
+            r = r.flip(1)
+        x[b] = r.permute(2, 0, 1).float().div(255)
     return x, labels[ids]
 
 
@@ -309,8 +522,64 @@ class DeviceLoader:
             yield ops.batch_u8(images, labels, ids[k:k + B], flip, self.lut)
 
 
+HBM_RESERVE = 16 << 30  # bytes of device memory left to the model, its activations and the attack next to a resident split
+
+
+def check_hbm(nbytes, device, what):
+    """DataError when `nbytes` of `what` do not fit in the free memory of `device` minus HBM_RESERVE."""
+    free, total = torch.cuda.mem_get_info(device)
+    if nbytes > free - HBM_RESERVE:
+        raise DataError("%s is %.1f GB as uint8; the device has %.1f of %.1f GB free and %.1f GB are kept for the model: set "
+                        "EEADV_IMAGENET_SHORT=<pixels> (e.g. 160) to shrink the images at decode, so that the split fits"
+                        % (what, nbytes / 1e9, free / 1e9, total / 1e9, HBM_RESERVE / 1e9))
+
+
+class RaggedDeviceLoader(DeviceLoader):
+    """DeviceLoader over a split of images of different sizes (ImageNet train): `load()` -> (pixels, offsets, sizes, labels),
+    every batch is RandomResizedCrop(S) + flip by ONE launch of ee_batch_rrc_u8_f32.  The boxes are drawn per epoch for the whole
+    split after the order and the flips, from the same generator, indexed by sample id like the flips."""
+
+    def __init__(self, load, S, batch_size, device, seed, rank=None, world=None, what="the train split"):
+        super().__init__(load, batch_size, device, seed, shuffle=True, flip=True, rank=rank, world=world)
+        self.S, self.what = int(S), what
+
+    def _ready(self):
+        if self._split is None:
+            split = [torch.from_numpy(np.ascontiguousarray(a)) for a in self._load()]
+            self.n = split[1].shape[0]
+            self.positions = torch.tensor(ddp.shard_indices(self.n, self.rank, self.world), dtype=torch.int64)
+            self.sizes_host = split[2]
+            if self.device.type == "cuda":
+                check_hbm(split[0].numel(), self.device, self.what)
+                split, self.lut = [a.to(self.device) for a in split], LUT.to(self.device)
+            self._split = tuple(split)
+        return self._split
+
+    def epoch_draws(self):
+        """(sample ids of this rank in batch order, flip flags [N] bool, boxes int32 [N,4]) of this epoch, on the host."""
+        self._ready()
+        g = torch.Generator().manual_seed(self.seed + self.epoch)
+        perm = torch.randperm(self.n, generator=g)
+        flip = torch.rand(self.n, generator=g) < 0.5
+        return perm[self.positions], flip, rrc_boxes(self.sizes_host, g)
+
+    def __iter__(self):
+        pixels, offsets, sizes, labels = self._ready()
+        ids, flip, boxes = self.epoch_draws()
+        B = self.batch_size
+        if self.device.type != "cuda":
+            for k in range(0, ids.numel(), B):
+                yield host_batch_rrc(pixels, offsets, sizes, labels, ids[k:k + B], boxes, flip, self.S)
+            return
+        from . import ops
+        ids = ids.to(torch.int32).to(self.device)  # the epoch's only host -> device copies
+        flip, boxes = flip.to(torch.uint8).to(self.device), boxes.to(self.device)
+        for k in range(0, ids.numel(), B):
+            yield ops.batch_rrc(pixels, offsets, sizes, labels, ids[k:k + B], boxes, flip, self.lut, self.S)
+
+
 def make_loaders(kind, root, spec, device, batch_size, seed):
-    """(train, val) DeviceLoaders of a `kind` directory, with the reference's shuffle / flip per split."""
+    """(train, val) loaders of a `kind` directory, with the reference's shuffle / flip (/ crop) per split."""
     root = os.path.abspath(root)
     shape, k = tuple(spec["shape"]), spec["num_classes"]
     if kind == "tiny_imagenet":
@@ -319,4 +588,9 @@ def make_loaders(kind, root, spec, device, batch_size, seed):
     if kind == "mnist":
         return (DeviceLoader(lambda: load_mnist(root, "train", shape, k), batch_size, device, seed, shuffle=True, flip=False),
                 DeviceLoader(lambda: load_mnist(root, "test", shape, k), batch_size, device, seed, shuffle=True, flip=False))
+    if kind == "imagenet":
+        resize = int(spec.get("resize", 256))
+        return (RaggedDeviceLoader(lambda: load_imagenet(root, "train", shape, k, resize), shape[-1], batch_size, device, seed,
+                                   what="the train split of %s" % root),
+                DeviceLoader(lambda: load_imagenet(root, "val", shape, k, resize), batch_size, device, seed, shuffle=False, flip=False))
     raise ValueError("unknown dataset kind %r" % (kind,))

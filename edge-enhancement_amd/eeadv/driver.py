@@ -10,9 +10,13 @@ undefined function, DataParallel is replaced by one process per GPU (eeadv.ddp).
 
 Data: `--data synthetic` (optionally `synthetic:<n_train_batches>:<n_val_batches>`, what the benchmark and most tests use) gives
 seeded NCHW batches generated on the device.  A dataset directory is read by eeadv.data in place of the reference's
-torchvision loaders (utils/data_loader.py) for the scripts whose SPEC names a "data" kind - Tiny-ImageNet and MNIST: each split
-decoded once, cached as uint8, held on the device, one HIP launch per batch.  The ImageNet driver and the free-AT scripts stay
-synthetic-only (RandomResizedCrop / Resize + CenterCrop over 1.28 M JPEGs is not implemented) and refuse a directory.
+torchvision loaders (utils/data_loader.py) for the scripts whose SPEC names a "data" kind - Tiny-ImageNet, MNIST and ImageNet: each
+split decoded once, cached as uint8, held on the device, one HIP launch per batch (ImageNet train: images of their own sizes,
+RandomResizedCrop + flip in that launch; ImageNet val: Resize + CenterCrop applied once at decode).  The free-AT scripts stay
+synthetic-only and refuse a directory.
+
+A SPEC may list YAML keys that resize its problem under "yaml_sizes" (the ImageNet driver: num_classes, crop_size, resize_size;
+absent keys keep the reference's 1000 / 224 / 256) - see `sized`.
 """
 import argparse
 import os
@@ -76,6 +80,20 @@ def data_source(data, spec):
         raise NotImplementedError("--data %s is neither synthetic[:train_batches[:val_batches]] nor a %s directory: expected %s"
                                   % (data, kind, D.LAYOUTS[kind]))
     return kind
+
+
+def sized(spec, args):
+    """`spec` with the keys it lists under "yaml_sizes" taken from the YAML when present: num_classes, crop_size (the side of the
+    batches, spec["shape"]) and resize_size (the val split's Resize before its CenterCrop, spec["resize"])."""
+    spec = dict(spec)
+    allowed = spec.get("yaml_sizes", ())
+    if "num_classes" in allowed and args.get("num_classes") is not None:
+        spec["num_classes"] = int(args.num_classes)
+    if "crop_size" in allowed and args.get("crop_size") is not None:
+        spec["shape"] = (spec["shape"][0], int(args.crop_size), int(args.crop_size))
+    if "resize_size" in allowed and args.get("resize_size") is not None:
+        spec["resize"] = int(args.resize_size)
+    return spec
 
 
 def make_loaders(args, spec, device, batch_size):
@@ -234,12 +252,14 @@ def run(spec, build_model, argv=None):
     """main() of the reference drivers (experiments_tinyimagenet.py:50-213)."""
     parser = make_parser(spec["description"], with_local_rank=spec.get("ddp", False))
     args = parse_config_file(parser.parse_args(argv))
+    spec = sized(spec, args)
     data_source(args.data, spec)  # an unusable --data fails here, before a model is built
     for key, default in (("type_canny", None), ("step_size_3", args.get("step_size_2")), ("num_steps_3", args.get("num_steps_2")),
                          ("n_queries", 1), ("cize", spec["shape"][-1]), ("beta", 1.0)):
         if key not in args:
             args[key] = default  # keys the reference reads unconditionally but several of its YAMLs omit (SURVEY 4)
     args.num_classes = spec["num_classes"]
+    args.crop_size = spec["shape"][-1]
     use_cuda = not args.no_cuda and torch.cuda.is_available()
     if use_cuda:
         torch.cuda.set_device(ddp.local_rank())

@@ -1329,6 +1329,28 @@ def batch_u8(data, labels, idx, flip, lut):
     return out, y
 
 
+def batch_rrc(pixels, offsets, sizes, labels, idx, boxes, flip, lut, S):
+    """pixels [bytes] u8 (images HWC, C = 3, back to back), offsets [N] i64, sizes [N,2] i32 = (H, W), labels [N] i64, idx [B] i32
+    sample ids, boxes [N,4] i32 = (top, left, h, w), flip [N] u8 or None, lut [256] f32 ->
+    (x [B,3,S,S] f32 = lut[PIL-BILINEAR resize of each sample's crop to S x S] mirrored where flip[idx];  y [B] i64).  One launch."""
+    n, B, S = offsets.shape[0], idx.shape[0], int(S)
+    if pixels.dim() != 1:
+        raise ValueError("pixels must be one flat buffer, got shape %s" % (tuple(pixels.shape),))
+    pp = _chk(pixels, torch.uint8, "pixels")
+    po = _chk(offsets, torch.int64, "offsets", (n,))
+    ps = _chk(sizes, torch.int32, "sizes", (n, 2))
+    pl = _chk(labels, torch.int64, "labels", (n,))
+    pi = _chk(idx, torch.int32, "idx", (B,))
+    pb = _chk(boxes, torch.int32, "boxes", (n, 4))
+    pf = _opt(flip, torch.uint8, "flip", (n,))
+    pt = _chk(lut, torch.float32, "lut", (256,))
+    out = torch.empty((B, 3, S, S), dtype=torch.float32, device=pixels.device)
+    y = torch.empty((B,), dtype=torch.int64, device=pixels.device)
+    N.check(N.lib.ee_batch_rrc_u8_f32(pp, pixels.numel(), po, ps, pl, pi, pb, pf, pt, n, B, S, _chk(out, torch.float32, "out"),
+                                      _chk(y, torch.int64, "labels_out"), _stream()), "ee_batch_rrc_u8_f32")
+    return out, y
+
+
 # ---- timing hooks ------------------------------------------------------------------------------------------------------
 def prof_enable(on=True):
     N.check(N.lib.ee_prof_enable(1 if on else 0), "ee_prof_enable")

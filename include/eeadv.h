@@ -630,6 +630,24 @@ int ee_chain_bwd_f32(const float *g_in, const uint8_t *gate, const float *gx, co
 int ee_batch_u8_f32(const uint8_t *data, const int64_t *labels, const int32_t *idx, const uint8_t *flip, const float *lut,
                     long long N, int B, int C, int H, int W, float *out, int64_t *labels_out, void *stream);
 
+/* The same for a split of images of different sizes, each batch sample cropped and resized to S x S (utils/data_loader.py:
+ * ImageFolder + RandomResizedCrop(S) + RandomHorizontalFlip + ToTensor).  pixels [nbytes] u8 = the split as one ragged buffer,
+ * image n HWC with C = 3 at byte offsets[n], sizes [N,2] = (H_n, W_n), boxes [N,4] = (top, left, h, w) of every sample for this
+ * epoch (drawn by the caller), idx / flip / lut / labels as above:
+ *     out[b] = lut[ resize(crop(image idx[b], boxes[idx[b]]), S x S) ], mirrored along w when flip[idx[b]]     out [B,3,S,S] f32
+ *     labels_out[b] = labels[idx[b]]
+ * resize = PIL's 8-bit BILINEAR resample restated: per axis the coefficients of precompute_coeffs in double, rounded to 22-bit
+ * fixed point, a horizontal pass over the crop's rows to uint8, then a vertical pass over that to uint8 - the bytes of
+ * PIL.Image.crop(box).resize((S, S), BILINEAR), except for a crop with h > 100 w, w >= 2 and S < h, where PIL takes the vertical
+ * pass first and some bytes differ by one (eeadv.data.resample_u8 states the condition; RandomResizedCrop never draws one).
+ * One launch, one workgroup per (sample, 16 result rows); S <= 4096 (EE_ERR_UNSUPPORTED beyond); out 4-byte aligned
+ * (EE_ERR_ALIGN), 16-byte aligned with S % 4 == 0 for the 16-byte stores; B == 0 launches nothing.  Preconditions: 0 <= idx[b] < N,
+ * h, w >= 1, the box inside its image and the image inside pixels; a sample that breaks one is not read - its outputs are NaN
+ * and its label -1. */
+int ee_batch_rrc_u8_f32(const uint8_t *pixels, long long nbytes, const int64_t *offsets, const int32_t *sizes, const int64_t *labels,
+                        const int32_t *idx, const int32_t *boxes, const uint8_t *flip, const float *lut, long long N, int B, int S,
+                        float *out, int64_t *labels_out, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Optional built-in timing of the last launch of each kernel family (HIP events on `stream`).
  * Off by default; bench.py switches it on outside graph capture to measure kernel durations live.
