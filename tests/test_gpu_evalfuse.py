@@ -30,9 +30,12 @@ def _same(a, b, what):
     assert bool(ok.all()), "%s: %d of %d elements differ, max |d| = %g" % (what, int((~ok).sum()), ok.numel(), float((a - b)[~ok].abs().max()))
 
 
-def _bn(C, gen):
+def _bn(C, gen, affine="rand", roll=0):
     g = (torch.rand(C, generator=gen) + 0.5).to(DEV)
     b = (torch.randn(C, generator=gen) * 0.3).to(DEV)
+    if affine == "hard":  # gamma of both signs and zero, beta of both signs and zero (tests/bn_reference.py)
+        from bn_reference import hard_affine
+        g, b = (t.to(DEV) for t in hard_affine(C, roll))
     rm = (torch.randn(C, generator=gen) * 0.2).to(DEV)
     rv = (torch.rand(C, generator=gen) + 0.3).to(DEV)
     return g, b, rm, rv, 1e-5
@@ -44,13 +47,13 @@ def _wino_sets(w):
 
 
 @pytest.mark.parametrize("B,C,H", [(5, 64, 16), (3, 128, 8), (2, 128, 8), (7, 256, 4), (4, 256, 4), (1, 32, 16), (9, 64, 8)])
-@pytest.mark.parametrize("with_res", [False, True])
-def test_wino_bn_eval_forward_equals_the_two_kernels(ops, B, C, H, with_res):
+@pytest.mark.parametrize("with_res,affine", [(False, "rand"), (True, "rand"), (False, "hard"), (True, "hard")], ids=["False", "True", "False-hard", "True-hard"])
+def test_wino_bn_eval_forward_equals_the_two_kernels(ops, B, C, H, with_res, affine):
     gen = torch.Generator().manual_seed(B * 1000 + C + H)
     x = torch.randn(B, C, H, H, generator=gen).to(DEV)
     w = (torch.randn(C, C, 3, 3, generator=gen) * (2.0 / (9 * C)) ** 0.5).to(DEV)
     res = torch.randn(B, C, H, H, generator=gen).to(DEV) if with_res else None
-    g, b, rm, rv, eps = _bn(C, gen)
+    g, b, rm, rv, eps = _bn(C, gen, affine)
     u = _wino_sets(w)[0]
     want, _, _ = ops.bn_act_fwd(ops.wino3x3(x, u), res, g, b, rm, rv, 0.1, eps, False, True)
     got = ops.wino3x3_bn_eval_fwd(x, u, (rm, rv, g, b, eps), res, True)
@@ -61,16 +64,20 @@ def test_wino_bn_eval_forward_equals_the_two_kernels(ops, B, C, H, with_res):
     _same(ops.wino3x3_bn_eval_fwd(x, u, (rm, rv, None, None, eps), res, False), want2, "fused forward, no affine parameters, no ReLU")
 
 
+_BWD_FORMS = [(1, False, False), (2, True, False), (1, True, True), (2, False, True), (2, True, True)]
+
+
 @pytest.mark.parametrize("B,C,H", [(5, 64, 16), (3, 128, 8), (2, 128, 8), (7, 256, 4), (4, 256, 4), (1, 32, 16)])
-@pytest.mark.parametrize("pieces,want_dres,with_add", [(1, False, False), (2, True, False), (1, True, True), (2, False, True), (2, True, True)])
-def test_wino_bn_eval_backward_equals_the_two_kernels(ops, B, C, H, pieces, want_dres, with_add):
+@pytest.mark.parametrize("pieces,want_dres,with_add,affine", [f + ("rand",) for f in _BWD_FORMS] + [f + ("hard",) for f in _BWD_FORMS],
+                         ids=["%d-%s-%s" % f for f in _BWD_FORMS] + ["%d-%s-%s-hard" % f for f in _BWD_FORMS])
+def test_wino_bn_eval_backward_equals_the_two_kernels(ops, B, C, H, pieces, want_dres, with_add, affine):
     gen = torch.Generator().manual_seed(B * 1000 + C + H + pieces)
     y = torch.relu(torch.randn(B, C, H, H, generator=gen)).to(DEV)  # the forward's output: its sign pattern is the ReLU mask
     dy = torch.randn(B, C, H, H, generator=gen).to(DEV)
     dy2 = torch.randn(B, C, H, H, generator=gen).to(DEV) if pieces == 2 else None
     dx_add = torch.randn(B, C, H, H, generator=gen).to(DEV) if with_add else None
     w = (torch.randn(C, C, 3, 3, generator=gen) * (2.0 / (9 * C)) ** 0.5).to(DEV)
-    g, b, rm, rv, eps = _bn(C, gen)
+    g, b, rm, rv, eps = _bn(C, gen, affine)
     ub = _wino_sets(w)[1]
     # the unfused sequence: BatchNorm + ReLU backward in eval mode (x only enters through xhat * 0), then the backward-data convolution
     xdummy = torch.randn(B, C, H, H, generator=gen).to(DEV)
@@ -87,16 +94,17 @@ def test_wino_bn_eval_backward_equals_the_two_kernels(ops, B, C, H, pieces, want
 
 
 @pytest.mark.parametrize("B,Cin,Cout,H", [(5, 64, 128, 16), (3, 128, 256, 8), (9, 256, 512, 4), (2, 32, 64, 8)])
-@pytest.mark.parametrize("mt", ["222111", "111222"])
-def test_s2_pair_bn_eval_equals_the_unfused_kernels(ops, B, Cin, Cout, H, mt, monkeypatch):
+@pytest.mark.parametrize("mt,affine", [("222111", "rand"), ("111222", "rand"), ("222111", "hard"), ("111222", "hard")],
+                         ids=["222111", "111222", "222111-hard", "111222-hard"])
+def test_s2_pair_bn_eval_equals_the_unfused_kernels(ops, B, Cin, Cout, H, mt, affine, monkeypatch):
     from eeadv import functional as Fn
     monkeypatch.setenv("EEADV_S2_MT", mt)
     gen = torch.Generator().manual_seed(B + Cin + H)
     x = torch.randn(B, Cin, H, H, generator=gen).to(DEV)
     w3 = (torch.randn(Cout, Cin, 3, 3, generator=gen) * (2.0 / (9 * Cin)) ** 0.5).to(DEV)
     w1 = (torch.randn(Cout, Cin, 1, 1, generator=gen) * (2.0 / Cin) ** 0.5).to(DEV)
-    g3, b3, rm3, rv3, eps = _bn(Cout, gen)
-    g1, b1, rm1, rv1, _ = _bn(Cout, gen)
+    g3, b3, rm3, rv3, eps = _bn(Cout, gen, affine)
+    g1, b1, rm1, rv1, _ = _bn(Cout, gen, affine, roll=3)
     w10f, w10b = Fn._dense_weight(w3, "s2p_f", w1), Fn._dense_weight(w3, "s2p_b", w1)
     y3, y1 = ops.conv3x3s2_pair_fwd(x, w10f, Cout)
     want3, _, _ = ops.bn_act_fwd(y3, None, g3, b3, rm3, rv3, 0.1, eps, False, True)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from bn_reference import hard_affine
 from oracle import ee_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -442,8 +443,9 @@ def test_bn_act_matches_torch(ops, shape, relu, res, training):
 
 
 @pytest.mark.parametrize("shape", [(100, 64, 16, 16), (100, 128, 8, 8), (100, 256, 4, 4), (100, 64, 32, 32), (7, 5, 3, 3), (3, 4, 1, 1)])
-@pytest.mark.parametrize("relu,res", [(True, True), (True, False), (False, True)])
-def test_bn_act_forked_output_adds_the_two_gradients_on_load(ops, shape, relu, res):
+@pytest.mark.parametrize("relu,res,affine", [(True, True, "rand"), (True, False, "rand"), (False, True, "rand"), (True, True, "hard"), (True, False, "hard"),
+                                             (False, True, "hard")], ids=["True-True", "True-False", "False-True", "True-True-hard", "True-False-hard", "False-True-hard"])
+def test_bn_act_forked_output_adds_the_two_gradients_on_load(ops, shape, relu, res, affine):
     """BnActFn(fork=True) hands its output out twice (next block's convolution + identity branch, resnet.py:44-59); the two gradients
     reach the backward kernel separately and are added on load (every kernel variant: cached <256,2> / <256,7> / <1024,7>, split, generic):
     bit-identical to the unforked function fed with their sum (the same fp32 add autograd's own accumulation performs)."""
@@ -454,6 +456,8 @@ def test_bn_act_forked_output_adds_the_two_gradients_on_load(ops, shape, relu, r
     r = torch.randn(shape, generator=g).to(DEV).requires_grad_(True) if res else None
     w = (torch.rand(C, generator=g) + 0.5).to(DEV).requires_grad_(True)
     b = torch.randn(C, generator=g).to(DEV).requires_grad_(True)
+    if affine == "hard":  # gamma of both signs and zero, beta of both signs and zero (tests/bn_reference.py)
+        w, b = (t.to(DEV).requires_grad_(True) for t in hard_affine(C))
     d1, d2 = torch.randn(shape, generator=g).to(DEV), torch.randn(shape, generator=g).to(DEV)
     ins = [x, w, b] + ([r] if res else [])
     stats = lambda: (torch.zeros(C, device=DEV), torch.ones(C, device=DEV))
@@ -471,8 +475,8 @@ def test_bn_act_forked_output_adds_the_two_gradients_on_load(ops, shape, relu, r
 
 
 @pytest.mark.parametrize("shape", [(100, 64, 16, 16), (100, 128, 8, 8), (100, 256, 4, 4), (100, 64, 32, 32), (7, 5, 3, 3), (2, 3, 5, 7)])
-@pytest.mark.parametrize("training", [True, False])
-def test_bn_act_backward_relu_mask_recomputed_from_x(ops, shape, training):
+@pytest.mark.parametrize("training,affine", [(True, "rand"), (False, "rand"), (True, "hard"), (False, "hard")], ids=["True", "False", "True-hard", "False-hard"])
+def test_bn_act_backward_relu_mask_recomputed_from_x(ops, shape, training, affine):
     """Without a residual branch the backward's ReLU mask (y > 0) is recomputed from x, gamma, beta with the forward's expression
     instead of reading y (ee_bn_act_bwd2_f32 with y = NULL): every kernel variant returns the same bits as with y, also where
     the pre-activation is exactly 0, tiny, or NaN."""
@@ -484,6 +488,8 @@ def test_bn_act_backward_relu_mask_recomputed_from_x(ops, shape, training):
     b = torch.randn(C, generator=g)
     if C > 2:
         b[2] = 0.0
+    if affine == "hard":
+        w, b = hard_affine(C)
     rm, rv = torch.randn(C, generator=g), torch.rand(C, generator=g) + 0.5
     if not training and x.numel() > 60:
         x[0, 0].view(-1)[:3] = torch.tensor([float("nan"), float("inf"), float("-inf")])[:x[0, 0].numel()][:3] if x[0, 0].numel() >= 3 else x[0, 0].view(-1)[:3]
@@ -500,8 +506,8 @@ def test_bn_act_backward_relu_mask_recomputed_from_x(ops, shape, training):
 
 
 @pytest.mark.parametrize("shape", [(100, 128, 8, 8), (100, 256, 4, 4), (100, 512, 2, 2), (3, 6, 2, 2), (9, 4, 4, 8)])
-@pytest.mark.parametrize("training", [True, False])
-def test_bn_dual_equals_the_two_batchnorm_calls(ops, shape, training):
+@pytest.mark.parametrize("training,affine", [(True, "rand"), (False, "rand"), (True, "hard"), (False, "hard")], ids=["True", "False", "True-hard", "False-hard"])
+def test_bn_dual_equals_the_two_batchnorm_calls(ops, shape, training, affine):
     """relu(bn2(conv2 out) + bn_ds(conv1x1 out)) - the end of a block with a down-sampling shortcut (resnet.py:54-59, :137-142) - in one
     launch each way: output, running statistics and every gradient bit-identical to BnActFn(xb, relu=False) -> BnActFn(xa, residual,
     relu=True), one gradient piece or two (forked output)."""
@@ -513,6 +519,8 @@ def test_bn_dual_equals_the_two_batchnorm_calls(ops, shape, training):
     xa, xb = mk(), mk()
     pr = lambda: ((torch.rand(C, generator=g) + 0.5).to(DEV).requires_grad_(True), torch.randn(C, generator=g).to(DEV).requires_grad_(True))
     (ga, ba), (gb, bb) = pr(), pr()
+    if affine == "hard":  # the two sides on different points of the cycle
+        (ga, ba), (gb, bb) = ((t.to(DEV).requires_grad_(True) for t in hard_affine(C, roll)) for roll in (0, 3))
     st0 = [torch.randn(C, generator=g).to(DEV), (torch.rand(C, generator=g) + 0.5).to(DEV), torch.randn(C, generator=g).to(DEV), (torch.rand(C, generator=g) + 0.5).to(DEV)]
     ins = [xa, xb, ga, ba, gb, bb]
     d1, d2 = torch.randn(shape, generator=g).to(DEV), torch.randn(shape, generator=g).to(DEV)

@@ -26,14 +26,38 @@ def _close(a, b, rel, what):
     assert err <= rel * scale, "%s: max |d| = %.3e of max |ref| = %.3e (allowed %.1e relative)" % (what, err, scale, rel)
 
 
-@pytest.mark.parametrize("B,C,H", [(100, 64, 16), (5, 64, 16), (7, 128, 8), (2, 128, 8), (9, 256, 4), (4, 256, 4), (3, 32, 16)])
-def test_conv_bn_relu_conv_across_the_kernel_boundary(ops, B, C, H):
+def _close_per_channel(a, b, rel, what, scale=None):
+    """_close for the [C]-shaped quantities, channel by channel: every channel against its OWN scale - by default the reference entry's
+    magnitude; for a mean, whose rounding error grows with the spread of what was averaged, the caller passes |mean| + std"""
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    scale = b.abs() if scale is None else scale.detach().double().cpu()
+    err = (a - b).abs()
+    bad = (err > rel * (scale + 1e-30)).nonzero().flatten().tolist()
+    assert not bad, "%s: channels %s: |d| = %s of scale %s (allowed %.1e relative)" % (what, bad[:8], err[bad][:8].tolist(), scale[bad][:8].tolist(), rel)
+
+
+def _affine(C, gen, affine):
+    gamma, beta = (torch.rand(C, generator=gen) + 0.5).to(DEV), (torch.randn(C, generator=gen) * 0.2).to(DEV)
+    if affine == "hard":  # gamma of both signs and zero, beta of both signs and zero (tests/bn_reference.py)
+        from bn_reference import hard_affine
+        gamma, beta = (t.to(DEV) for t in hard_affine(C))
+    return gamma, beta
+
+
+def _with_hard(cases):
+    """every case with the suite's gamma = rand + 0.5 (its id unchanged) and again with bn_reference.hard_affine"""
+    ids = ["-".join(str(v) for v in c) for c in cases]
+    return dict(argvalues=[c + ("rand",) for c in cases] + [c + ("hard",) for c in cases], ids=ids + [i + "-hard" for i in ids])
+
+
+@pytest.mark.parametrize("B,C,H,affine", **_with_hard([(100, 64, 16), (5, 64, 16), (7, 128, 8), (2, 128, 8), (9, 256, 4), (4, 256, 4), (3, 32, 16)]))
+def test_conv_bn_relu_conv_across_the_kernel_boundary(ops, B, C, H, affine):
     from eeadv import functional as Fn
     gen = torch.Generator().manual_seed(B + C + H)
     x = torch.relu(torch.randn(B, C, H, H, generator=gen)).to(DEV)
     w1 = (torch.randn(C, C, 3, 3, generator=gen) * (2.0 / (9 * C)) ** 0.5).to(DEV)
     w2 = (torch.randn(C, C, 3, 3, generator=gen) * (2.0 / (9 * C)) ** 0.5).to(DEV)
-    gamma, beta = (torch.rand(C, generator=gen) + 0.5).to(DEV), (torch.randn(C, generator=gen) * 0.2).to(DEV)
+    gamma, beta = _affine(C, gen, affine)
     u1, u2 = Fn.wino_sets(w1)[0], Fn.wino_sets(w2)[0]
     rm_a, rv_a = torch.full((C,), 0.1, device=DEV), torch.full((C,), 0.9, device=DEV)
     rm_b, rv_b = rm_a.clone(), rv_a.clone()
@@ -53,6 +77,10 @@ def test_conv_bn_relu_conv_across_the_kernel_boundary(ops, B, C, H):
     _close(sib, si, 2e-6, "save_invstd")
     _close(rm_b, rm_a, 2e-6, "running_mean")
     _close(rv_b, rv_a, 2e-6, "running_var")
+    _close_per_channel(smb, sm, 2e-6, "save_mean, per channel", sm.abs() + 1.0 / si)
+    _close_per_channel(sib, si, 2e-6, "save_invstd, per channel")
+    _close_per_channel(rm_b, rm_a, 2e-6, "running_mean, per channel", rm_a.abs() + 0.1 / si)
+    _close_per_channel(rv_b, rv_a, 2e-6, "running_var, per channel")
     _close(got, want, 2e-5, "conv2(relu(bn1(conv1 x)))")
     # bit-reproducible
     rm_c, rv_c = torch.full((C,), 0.1, device=DEV), torch.full((C,), 0.9, device=DEV)
@@ -63,8 +91,8 @@ def test_conv_bn_relu_conv_across_the_kernel_boundary(ops, B, C, H):
     ops.wino3x3_bn_train_pre(c1b, stats, H * H, None, None, 1e-5, 0.1, None, None, u2)
 
 
-@pytest.mark.parametrize("B,C", [(100, 64), (5, 64), (3, 32), (9, 128)])
-def test_batchnorm_backward_across_the_kernel_boundary(ops, B, C):
+@pytest.mark.parametrize("B,C,affine", **_with_hard([(100, 64), (5, 64), (3, 32), (9, 128)]))
+def test_batchnorm_backward_across_the_kernel_boundary(ops, B, C, affine):
     """conv2^T -> BatchNorm / ReLU backward (train mode, mask from x) -> conv1^T on 16x16 maps: the sums epilogue + merge / apply prologue
     against ee_wino3x3_f32 | ee_bn_act_bwd2_f32(training = 1) | ee_wino3x3_f32 - the convolutions' raw outputs bit-equal, the rest within
     rounding (the batch sums are taken in another order), bit-reproducible."""
@@ -75,7 +103,7 @@ def test_batchnorm_backward_across_the_kernel_boundary(ops, B, C):
     dc2 = torch.randn(B, C, H, H, generator=gen).to(DEV)  # the gradient of conv2's output
     w1 = (torch.randn(C, C, 3, 3, generator=gen) * (2.0 / (9 * C)) ** 0.5).to(DEV)
     w2 = (torch.randn(C, C, 3, 3, generator=gen) * (2.0 / (9 * C)) ** 0.5).to(DEV)
-    gamma, beta = (torch.rand(C, generator=gen) + 0.5).to(DEV), (torch.randn(C, generator=gen) * 0.2).to(DEV)
+    gamma, beta = _affine(C, gen, affine)
     sm = c1.mean((0, 2, 3)).contiguous()
     si = (1.0 / torch.sqrt(c1.var((0, 2, 3), unbiased=False) + 1e-5)).contiguous()
     u1b, u2b = Fn.wino_sets(w1)[1], Fn.wino_sets(w2)[1]
@@ -96,8 +124,9 @@ def test_batchnorm_backward_across_the_kernel_boundary(ops, B, C):
 
 
 @pytest.mark.parametrize("B,Cin,Cout,H", [(100, 64, 128, 16), (5, 64, 128, 16), (7, 128, 256, 8), (2, 128, 256, 8)])
-@pytest.mark.parametrize("mt", ["222111", "111222"])
-def test_pair_statistics_feed_the_consumer(ops, B, Cin, Cout, H, mt, monkeypatch):
+@pytest.mark.parametrize("mt,affine", [("222111", "rand"), ("111222", "rand"), ("222111", "hard"), ("111222", "hard")],
+                         ids=["222111", "111222", "222111-hard", "111222-hard"])
+def test_pair_statistics_feed_the_consumer(ops, B, Cin, Cout, H, mt, affine, monkeypatch):
     from eeadv import functional as Fn
     monkeypatch.setenv("EEADV_S2_MT", mt)
     gen = torch.Generator().manual_seed(B + Cin + H)
@@ -105,7 +134,7 @@ def test_pair_statistics_feed_the_consumer(ops, B, Cin, Cout, H, mt, monkeypatch
     w3 = (torch.randn(Cout, Cin, 3, 3, generator=gen) * (2.0 / (9 * Cin)) ** 0.5).to(DEV)
     wd = (torch.randn(Cout, Cin, 1, 1, generator=gen) * (2.0 / Cin) ** 0.5).to(DEV)
     w2 = (torch.randn(Cout, Cout, 3, 3, generator=gen) * (2.0 / (9 * Cout)) ** 0.5).to(DEV)
-    gamma, beta = (torch.rand(Cout, generator=gen) + 0.5).to(DEV), (torch.randn(Cout, generator=gen) * 0.2).to(DEV)
+    gamma, beta = _affine(Cout, gen, affine)
     w10 = Fn._dense_weight(w3, "s2p_f", wd)
     y3, y1 = ops.conv3x3s2_pair_fwd(x, w10, Cout)
     y3b, y1b, stats, cnt = ops.conv3x3s2_pair_stats_fwd(x, w10, Cout)
@@ -120,6 +149,10 @@ def test_pair_statistics_feed_the_consumer(ops, B, Cin, Cout, H, mt, monkeypatch
     _close(smb, sm, 2e-6, "save_mean")
     _close(sib, si, 2e-6, "save_invstd")
     _close(rv_b, rv_a, 2e-6, "running_var")
+    _close_per_channel(smb, sm, 2e-6, "save_mean, per channel", sm.abs() + 1.0 / si)
+    _close_per_channel(sib, si, 2e-6, "save_invstd, per channel")
+    _close_per_channel(rm_b, rm_a, 2e-6, "running_mean, per channel", rm_a.abs() + 0.1 / si)
+    _close_per_channel(rv_b, rv_a, 2e-6, "running_var, per channel")
     _close(got, want, 2e-5, "conv2(relu(bn1(pair conv x)))")
 
 
