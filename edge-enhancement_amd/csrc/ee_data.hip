@@ -303,6 +303,71 @@ __global__ __launch_bounds__(kBlock) void batch_rrc_kernel(const uint8_t *__rest
     }
 }
 
+// ---- crop from the zero-padded image + mirror + NEAREST rotation (RandomCrop + RandomHorizontalFlip + RandomRotation) -----------
+// Thread t owns output float4 t (VEC: W % 4 == 0) or float t of out [B,C,H,W].  Output pixel (x, y) of sample b reads pixel
+// (xin, yin) = ((a2 + x a0 + y a1) >> 16, (a5 + x a3 + y a4) >> 16) of the rotation's source, the mirrored crop; outside its W x H
+// frame it is the fill.  Column xin of the mirrored crop is column W-1-xin of the crop, and crop pixel (xs, yin) is image pixel
+// (xs + left - pad, yin + top - pad), 0 outside the image.  64-bit products: no (H, W, coefficient) can overflow them.
+template <bool VEC>
+__global__ __launch_bounds__(kBlock) void batch_aug_kernel(const uint8_t *__restrict__ data, const int64_t *__restrict__ labels,
+                                                           const int32_t *__restrict__ idx, const int32_t *__restrict__ offs,
+                                                           const uint8_t *__restrict__ flip, const int32_t *__restrict__ coef,
+                                                           const float *__restrict__ lut, int64_t N, int B, int C, int H, int W, int pad,
+                                                           float *__restrict__ out, int64_t *__restrict__ labels_out) {
+    __shared__ float s_lut[256];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) s_lut[i] = lut[i];
+    __syncthreads();
+
+    const int64_t tid0 = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    for (int64_t b = tid0; b < B; b += stride) {
+        const int64_t s = idx[b];
+        const int top = offs[2 * b], left = offs[2 * b + 1];
+        labels_out[b] = (s >= 0 && s < N && top >= 0 && top <= 2 * pad && left >= 0 && left <= 2 * pad) ? labels[s] : -1;
+    }
+    constexpr int K = VEC ? 4 : 1;
+    const int Wg = W / K;  // work items per output row
+    const int64_t total = static_cast<int64_t>(B) * C * H * Wg;
+    for (int64_t t = tid0; t < total; t += stride) {
+        int64_t r = t;
+        const int q = static_cast<int>(r % Wg);
+        r /= Wg;
+        const int y = static_cast<int>(r % H);
+        r /= H;
+        const int c = static_cast<int>(r % C);
+        const int b = static_cast<int>(r / C);
+        const int64_t s = idx[b];
+        const int top = offs[2 * b], left = offs[2 * b + 1];
+        float o[K];
+        if (s < 0 || s >= N || top < 0 || top > 2 * pad || left < 0 || left > 2 * pad) {
+            // outside the documented precondition: never read out of bounds, make the batch visibly wrong
+#pragma unroll
+            for (int k = 0; k < K; ++k) o[k] = nanf_();
+        } else {
+            const bool f = flip != nullptr && flip[b] != 0;
+            const int32_t *const a = coef + 6 * static_cast<int64_t>(b);
+            const int64_t a0 = a[0], a3 = a[3];
+            const int64_t xr = a[2] + static_cast<int64_t>(y) * a[1], yr = a[5] + static_cast<int64_t>(y) * a[4];
+            const uint8_t *const img = data + s * H * static_cast<int64_t>(W) * C + c;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int x = K * q + k;
+                const int64_t xin = (xr + x * a0) >> 16, yin = (yr + x * a3) >> 16;
+                uint32_t v = 0;  // the fill; lut[0] = 0.0f
+                if (xin >= 0 && xin < W && yin >= 0 && yin < H) {
+                    const int64_t xs = (f ? W - 1 - xin : xin) + left - pad, ys = yin + top - pad;
+                    if (xs >= 0 && xs < W && ys >= 0 && ys < H) v = img[(ys * W + xs) * C];
+                }
+                o[k] = s_lut[v];
+            }
+        }
+        if (VEC)
+            reinterpret_cast<float4 *>(out)[t] = make_float4(o[0], o[K > 1 ? 1 : 0], o[K > 2 ? 2 : 0], o[K > 3 ? 3 : 0]);
+        else
+            out[t] = o[0];
+    }
+}
+
 }  // namespace
 
 EE_API int ee_batch_u8_f32(const uint8_t *data, const int64_t *labels, const int32_t *idx, const uint8_t *flip, const float *lut,
@@ -341,5 +406,34 @@ EE_API int ee_batch_rrc_u8_f32(const uint8_t *pixels, long long nbytes, const in
     else
         EE_LAUNCH((batch_rrc_kernel<false>), grid, dim3(kBlock), 0, as_stream(stream), pixels, static_cast<int64_t>(nbytes), offsets, sizes, labels,
                   idx, boxes, flip, lut, static_cast<int64_t>(N), S, nbands, out, labels_out);
+    return launch_status();
+}
+
+EE_API int ee_batch_aug_u8_f32(const uint8_t *data, const int64_t *labels, const int32_t *idx, const int32_t *offs, const uint8_t *flip,
+                               const int32_t *coef, const float *lut, const int32_t *idx_host, const int32_t *offs_host, long long N, int B, int C,
+                               int H, int W, int pad, float *out, int64_t *labels_out, void *stream) {
+    if (B < 0 || N <= 0 || C <= 0 || H <= 0 || W <= 0 || pad < 0) return EE_ERR_SHAPE;
+    if (pad > (1 << 20) || static_cast<int64_t>(H) * W > (int64_t(1) << 40) / C) return EE_ERR_UNSUPPORTED;
+    if (B == 0) return EE_OK;
+    if (!data || !labels || !idx || !offs || !coef || !lut || !idx_host || !offs_host || !out || !labels_out) return EE_ERR_NULL;
+    if (!aligned4(out) || !aligned4(lut) || !aligned4(idx) || !aligned4(offs) || !aligned4(coef) || !aligned4(idx_host) || !aligned4(offs_host) ||
+        (reinterpret_cast<uintptr_t>(labels) & 7u) || (reinterpret_cast<uintptr_t>(labels_out) & 7u))
+        return EE_ERR_ALIGN;
+    for (int b = 0; b < B; ++b) {  // the host's copy of the draws: nothing is launched on a sample or a crop outside its range
+        if (idx_host[b] < 0 || idx_host[b] >= N) return EE_ERR_SHAPE;
+        if (offs_host[2 * b] < 0 || offs_host[2 * b] > 2 * pad || offs_host[2 * b + 1] < 0 || offs_host[2 * b + 1] > 2 * pad) return EE_ERR_SHAPE;
+    }
+    const bool vec = W % 4 == 0 && aligned16(out);
+    const int64_t work = static_cast<int64_t>(B) * C * H * (vec ? W / 4 : W);
+    int64_t blocks = (work + kBlock - 1) / kBlock;
+    if (blocks > kMaxGrid) blocks = kMaxGrid;
+    const dim3 grid(static_cast<unsigned>(blocks));
+    ProfScope prof(EE_K_BATCH_AUG, as_stream(stream));
+    if (vec)
+        EE_LAUNCH((batch_aug_kernel<true>), grid, dim3(kBlock), 0, as_stream(stream), data, labels, idx, offs, flip, coef, lut, static_cast<int64_t>(N),
+                  B, C, H, W, pad, out, labels_out);
+    else
+        EE_LAUNCH((batch_aug_kernel<false>), grid, dim3(kBlock), 0, as_stream(stream), data, labels, idx, offs, flip, coef, lut,
+                  static_cast<int64_t>(N), B, C, H, W, pad, out, labels_out);
     return launch_status();
 }

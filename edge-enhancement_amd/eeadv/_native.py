@@ -142,6 +142,8 @@ SIGNATURES = {
     "ee_batch_u8_f32": [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
     # pixels, nbytes, offsets, sizes, labels, idx, boxes, flip, lut, N, B, S, out, labels_out, stream
     "ee_batch_rrc_u8_f32": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p],
+    # data, labels, idx, offs, flip, coef, lut, idx_host, offs_host, N, B, C, H, W, pad, out, labels_out, stream
+    "ee_batch_aug_u8_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
     "ee_prof_enable": [c_i],
     "ee_prof_mark_empty": [c_p],
     "ee_prof_read": [c_i, c_p, c_p],
@@ -154,6 +156,7 @@ _RESTYPE = {"ee_strerror": ctypes.c_char_p, "ee_device_name": ctypes.c_char_p, "
 (K_PGD_STEP, K_FRONTEND_FWD, K_FRONTEND_BWD, K_EDGE_FWD, K_EDGE_BWD, K_CE, K_PGD_STEP_BCAST, K_EMPTY, K_HFS, K_CHAIN_FWD, K_CHAIN_BWD,
  K_HFS_SQ_FWD, K_HFS_SQ_BWD, K_SQUARE_DRAW) = range(14)
 K_WINO, K_CONV3S2_FWD, K_CONV3S2_BWD, K_WINO_FUSED = 18, 19, 20, 21  # 14 - 17: the direct 3x3 kernels removed in round 3
+K_BATCH_AUG = 22
 
 
 class EEError(RuntimeError):

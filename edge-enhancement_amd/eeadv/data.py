@@ -37,10 +37,21 @@ Resize(256) + CenterCrop(224) + ToTensor for val)
   - the train split must fit in device memory next to the model (checked before the upload, DataError otherwise).  Departure
     from the reference, off by default: EEADV_IMAGENET_SHORT=<pixels> shrinks, at decode, every train image whose shorter side
     exceeds it to that shorter side (PIL BILINEAR, aspect ratio kept); the value is part of the cache key.
+
+CIFAR-100 (utils/data_loader.py:27-60: datasets.CIFAR100 + RandomCrop(32, padding=4) + RandomHorizontalFlip + RandomRotation(15) +
+ToTensor for train, ToTensor for test)
+  - the two python pickles are read once (`data` [N,3072] planar CHW -> HWC, `fine_labels`), cached and uploaded like Tiny's.
+  - train: a batch is ONE launch of ee_batch_aug_u8_f32.  torchvision rotates PIL images with Image.rotate(angle, NEAREST, fillcolor
+    = 0): the inverse matrix formed in Python floats (rotate_matrix), walked in 16.16 fixed point by PIL's C code (aug_coeffs).  The
+    crop from the zero-padded image, the mirror and that walk are integer arithmetic, restated in `host_batch_aug` (numpy; what
+    --no-cuda runs) and in the kernel, so a batch is ToTensor(rotate(flip(crop(pad(img))))) bit for bit.  The draws are per epoch on
+    the host, as above; the distribution is the reference's (offsets uniform in [0, 8], angles uniform in [-15, 15]).
+  - test: in file order through DeviceLoader / ee_batch_u8_f32.
 """
 import gzip
 import hashlib
 import json
+import math
 import multiprocessing
 import os
 import struct
@@ -57,6 +68,7 @@ LAYOUTS = {
     "tiny_imagenet": "<root>/train/<wnid>/**/*.JPEG and <root>/val/ (val/<wnid>/... or val/images/ + val/val_annotations.txt)",
     "mnist": "the IDX files {train,t10k}-{images-idx3,labels-idx1}-ubyte[.gz] in <root>/MNIST/raw/ or <root>/",
     "imagenet": "<root>/train/<wnid>/**/*.JPEG and <root>/val/<wnid>/**/*.JPEG (the same class directories in both)",
+    "cifar100": "the python pickles <root>/cifar-100-python/train and <root>/cifar-100-python/test (or <root>/train and <root>/test)",
 }
 _CHUNK = 512  # images per decode task
 
@@ -133,6 +145,8 @@ def recognised(kind, root):
         return os.path.isdir(os.path.join(root, "train")) and os.path.isdir(os.path.join(root, "val"))
     if kind == "mnist":
         return all(_mnist_file(root, n) for pair in MNIST_FILES.values() for n in pair)
+    if kind == "cifar100":
+        return all(os.path.isfile(os.path.join(_cifar_dir(root), n)) for n in ("train", "test"))
     return False
 
 
@@ -258,6 +272,86 @@ def load_mnist(root, split, shape=(1, 28, 28), num_classes=10):
     if labels.size and int(labels.max()) >= num_classes:
         raise DataError("%s: label %d, expected < %d" % (fl, int(labels.max()), num_classes))
     return images.reshape(images.shape + (1,)).copy(), labels.astype(np.int64)
+
+
+# ---- CIFAR-100 ----------------------------------------------------------------------------------------------------------------
+def _cifar_dir(root):
+    """<root>/cifar-100-python (torchvision's layout, what the archive unpacks to) when it exists, else <root> itself"""
+    d = os.path.join(root, "cifar-100-python")
+    return d if os.path.isdir(d) else root
+
+
+def load_cifar100(root, split, shape=(3, 32, 32), num_classes=100):
+    """CIFAR-100 `train` / `test` as (uint8 [N,32,32,3], int64 [N]) from the python pickle (torchvision's CIFAR100: encoding
+    latin1, `data` [N,3072] planar CHW, `fine_labels`); transposed to HWC once, then read from the cache."""
+    C, H, W = shape
+    path = os.path.join(_cifar_dir(root), split)
+    if not os.path.isfile(path):
+        raise DataError("%s does not exist (expected %s)" % (path, LAYOUTS["cifar100"]))
+    key = cache_key(root, ["cifar100", split, list(shape), num_classes], [path])
+
+    def build():
+        import pickle
+        with open(path, "rb") as f:
+            try:
+                entry = pickle.load(f, encoding="latin1")
+            except Exception as exc:
+                raise DataError("%s is not a CIFAR-100 python pickle (%s)" % (path, exc))
+        if not isinstance(entry, dict) or "data" not in entry or "fine_labels" not in entry:
+            raise DataError("%s holds no `data` / `fine_labels` entries" % path)
+        data, labels = np.asarray(entry["data"], dtype=np.uint8), np.asarray(entry["fine_labels"], dtype=np.int64)
+        if data.ndim != 2 or data.shape[1] != C * H * W:
+            raise DataError("%s: data is %s, expected [N,%d]" % (path, "x".join(str(d) for d in data.shape), C * H * W))
+        if data.shape[0] != labels.shape[0]:
+            raise DataError("%s holds %d images and %d fine labels" % (path, data.shape[0], labels.shape[0]))
+        if not data.shape[0]:
+            raise DataError("no images in %s" % path)
+        if int(labels.min()) < 0 or int(labels.max()) >= num_classes:
+            raise DataError("%s: fine label %d, expected 0 <= label < %d" % (path, int(labels.max() if labels.min() >= 0 else labels.min()), num_classes))
+        return np.ascontiguousarray(data.reshape(-1, C, H, W).transpose(0, 2, 3, 1)), labels
+    return cached(root, "cifar100-%s-%s.npz" % (split, key), build)
+
+
+# RandomCrop(32, padding=4) + RandomHorizontalFlip() + RandomRotation(15) (utils/data_loader.py:30-36).  torchvision's rotate of a PIL
+# image ends in img.rotate(angle, resample=NEAREST, expand=False, fillcolor=0): PIL/Image.py::rotate forms the inverse matrix in Python
+# floats, and ImagingTransformAffine (Geometry.c, affine_fixed) walks it in 16.16 fixed point.  Both are restated here; the inner
+# arithmetic is integer, so a batch is the PIL pipeline bit for bit.
+AUG_IDENTITY = (65536, 0, 32768, 0, 65536, 32768)
+
+
+def rotate_matrix(angle, w, h):
+    """PIL's Image.rotate(angle) matrix (destination -> source) of a w x h image as six Python floats, or None where rotate()
+    returns a copy (angle % 360 == 0)."""
+    angle = float(angle) % 360.0
+    if angle == 0:
+        return None
+    cx, cy = w / 2, h / 2
+    angle = -math.radians(angle)
+    m = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0, round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+    x, y = -cx, -cy
+    m[2], m[5] = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def _fix(v):
+    """Geometry.c's FIX: 16.16 fixed point, rounded half away from zero"""
+    return int(v * 65536.0 + (-0.5 if v < 0 else 0.5))
+
+
+def aug_coeffs(angles, H, W):
+    """int32 [n,6]: the 16.16 fixed-point inverse map of Image.rotate(angle) on a W x H image for every angle (degrees), with the
+    half-pixel offset of the pixel centres folded into the constant terms as affine_fixed does: output pixel (x, y) reads source
+    pixel ((a2 + x a0 + y a1) >> 16, (a5 + x a3 + y a4) >> 16), or the fill where that lies outside the image."""
+    out = np.empty((len(angles), 6), dtype=np.int32)
+    for k, angle in enumerate(np.asarray(angles, dtype=np.float64).tolist()):
+        m = rotate_matrix(angle, W, H)
+        if m is None:
+            out[k] = AUG_IDENTITY
+        else:
+            out[k] = (_fix(m[0]), _fix(m[1]), _fix(m[2] + m[0] * 0.5 + m[1] * 0.5), _fix(m[3]), _fix(m[4]), _fix(m[5] + m[3] * 0.5 + m[4] * 0.5))
+    return out
 
 
 # ---- ImageNet -----------------------------------------------------------------------------------------------------------------
@@ -464,6 +558,32 @@ def host_batch_rrc(pixels, offsets, sizes, labels, ids, boxes, flip, S):
     return x, labels[ids]
 
 
+def host_batch_aug(images, labels, ids, offs, flip, coef, pad):
+    """The CIFAR train batch on the host: what ee_batch_aug_u8_f32 computes (and --no-cuda runs).  images uint8 [N,H,W,C], labels
+    int64 [N]; per batch position: ids int64 [B], offs int32 [B,2] = the crop's (top, left) in the image zero-padded by `pad`, flip
+    bool / uint8 [B], coef int32 [B,6] (aug_coeffs).  The inverse maps are composed in the transform order crop, flip, rotate: output
+    pixel -> rotation source in the crop's frame -> un-mirrored column -> image pixel = crop offset - pad; outside the rotated frame
+    or outside the image gives 0."""
+    img = images.numpy()
+    N, H, W, C = img.shape
+    B = len(ids)
+    idn, o, f, a = np.asarray(ids, dtype=np.int64), np.asarray(offs, dtype=np.int64).reshape(B, 2), np.asarray(flip).astype(bool).reshape(B), \
+        np.asarray(coef, dtype=np.int64).reshape(B, 6)
+    if B and (idn.min() < 0 or idn.max() >= N or o.min() < 0 or o.max() > 2 * pad):
+        raise ValueError("host_batch_aug: a sample id outside [0, %d) or a crop offset outside [0, %d]" % (N, 2 * pad))
+    y, x = np.arange(H, dtype=np.int64)[None, :, None], np.arange(W, dtype=np.int64)[None, None, :]
+    a = a[:, :, None, None]
+    xin = (a[:, 2] + x * a[:, 0] + y * a[:, 1]) >> 16
+    yin = (a[:, 5] + x * a[:, 3] + y * a[:, 4]) >> 16
+    ok = (xin >= 0) & (xin < W) & (yin >= 0) & (yin < H)
+    xs = np.where(f[:, None, None], W - 1 - xin, xin) + o[:, 1, None, None] - pad
+    ys = yin + o[:, 0, None, None] - pad
+    ok &= (xs >= 0) & (xs < W) & (ys >= 0) & (ys < H)
+    u8 = img[idn[:, None, None], np.clip(ys, 0, H - 1), np.clip(xs, 0, W - 1)] * ok[..., None].astype(np.uint8)  # [B,H,W,C]
+    xb = torch.from_numpy(u8).permute(0, 3, 1, 2).float().div(255).clone(memory_format=torch.contiguous_format)
+    return xb, labels[torch.as_tensor(idn)]
+
+
 class DeviceLoader:
     """One split held on `device`; len() batches of `batch_size` (the last one may be partial), iterating yields (x f32
     [B,C,H,W], y int64 [B]) already on the device - as driver.SyntheticLoader.
@@ -578,6 +698,48 @@ class RaggedDeviceLoader(DeviceLoader):
             yield ops.batch_rrc(pixels, offsets, sizes, labels, ids[k:k + B], boxes, flip, self.lut, self.S)
 
 
+class AugDeviceLoader(DeviceLoader):
+    """DeviceLoader whose every batch is RandomCrop(H, padding=pad) + RandomHorizontalFlip + RandomRotation(degrees) by ONE launch of
+    ee_batch_aug_u8_f32 (CIFAR-100 train).  Per epoch the order, the flips, the crop offsets (uniform integers in [0, 2 pad], as
+    RandomCrop.get_params) and the angles (uniform in [-degrees, degrees], as RandomRotation.get_params) are drawn on the host for
+    the whole split from torch.Generator(seed + epoch), indexed by sample id like the flips; the angles become the 16.16 fixed-point
+    matrices of aug_coeffs there, and this rank's draws go to the device once, in batch order."""
+
+    def __init__(self, load, batch_size, device, seed, pad=4, degrees=15.0, rank=None, world=None):
+        super().__init__(load, batch_size, device, seed, shuffle=True, flip=True, rank=rank, world=world)
+        self.pad, self.degrees = int(pad), float(degrees)
+
+    def epoch_draws(self):
+        """(sample ids of this rank in batch order int64, flip flags [N] bool, crop offsets int32 [N,2] = (top, left), angles float64
+        [N] in degrees) of this epoch, on the host."""
+        self._ready()
+        g = torch.Generator().manual_seed(self.seed + self.epoch)
+        perm = torch.randperm(self.n, generator=g)
+        flip = torch.rand(self.n, generator=g) < 0.5
+        offs = torch.randint(0, 2 * self.pad + 1, (self.n, 2), generator=g, dtype=torch.int32)
+        angles = (torch.rand(self.n, dtype=torch.float64, generator=g) * 2.0 - 1.0) * self.degrees
+        return perm[self.positions], flip, offs, angles
+
+    def __iter__(self):
+        images, labels = self._ready()
+        ids, flip, offs, angles = self.epoch_draws()
+        H, W = images.shape[1], images.shape[2]
+        # this rank's draws in batch order
+        offs, flip = offs[ids].contiguous(), flip[ids].to(torch.uint8)
+        coef = torch.from_numpy(aug_coeffs(angles[ids].numpy(), H, W))
+        B = self.batch_size
+        if self.device.type != "cuda":
+            for k in range(0, ids.numel(), B):
+                yield host_batch_aug(images, labels, ids[k:k + B], offs[k:k + B], flip[k:k + B], coef[k:k + B], self.pad)
+            return
+        from . import ops
+        ids = ids.to(torch.int32)
+        d_ids, d_offs, d_flip, d_coef = (t.to(self.device) for t in (ids, offs, flip, coef))  # the epoch's only host -> device copies
+        for k in range(0, ids.numel(), B):
+            yield ops.batch_aug(images, labels, d_ids[k:k + B], d_offs[k:k + B], d_flip[k:k + B], d_coef[k:k + B], self.lut,
+                                ids[k:k + B], offs[k:k + B], self.pad)
+
+
 def make_loaders(kind, root, spec, device, batch_size, seed):
     """(train, val) loaders of a `kind` directory, with the reference's shuffle / flip (/ crop) per split."""
     root = os.path.abspath(root)
@@ -593,4 +755,8 @@ def make_loaders(kind, root, spec, device, batch_size, seed):
         return (RaggedDeviceLoader(lambda: load_imagenet(root, "train", shape, k, resize), shape[-1], batch_size, device, seed,
                                    what="the train split of %s" % root),
                 DeviceLoader(lambda: load_imagenet(root, "val", shape, k, resize), batch_size, device, seed, shuffle=False, flip=False))
+    if kind == "cifar100":
+        return (AugDeviceLoader(lambda: load_cifar100(root, "train", shape, k), batch_size, device, seed, pad=int(spec.get("pad", 4)),
+                                degrees=float(spec.get("degrees", 15.0))),
+                DeviceLoader(lambda: load_cifar100(root, "test", shape, k), batch_size, device, seed, shuffle=False, flip=False))
     raise ValueError("unknown dataset kind %r" % (kind,))

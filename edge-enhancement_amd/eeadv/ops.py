@@ -1351,6 +1351,33 @@ def batch_rrc(pixels, offsets, sizes, labels, idx, boxes, flip, lut, S):
     return out, y
 
 
+def batch_aug(data, labels, idx, offs, flip, coef, lut, idx_host, offs_host, pad):
+    """data [N,H,W,C] u8, labels [N] i64, lut [256] f32; per batch position idx [B] i32 sample ids, offs [B,2] i32 = (top, left) of the
+    crop in the image zero-padded by `pad`, flip [B] u8 or None, coef [B,6] i32 (eeadv.data.aug_coeffs); idx_host / offs_host = the
+    HOST tensors idx and offs were uploaded from, which the library checks before it launches ->
+    (x [B,C,H,W] f32 = lut[rotate(flip(crop(pad(data[idx]))))], HWC -> NCHW;  y [B] i64 = labels[idx]).  One launch."""
+    if data.dim() != 4:
+        raise ValueError("data must be [N,H,W,C], got shape %s" % (tuple(data.shape),))
+    n, H, W, C = data.shape
+    B = idx.shape[0]
+    pd = _chk(data, torch.uint8, "data")
+    pl = _chk(labels, torch.int64, "labels", (n,))
+    pi = _chk(idx, torch.int32, "idx", (B,))
+    po = _chk(offs, torch.int32, "offs", (B, 2))
+    pf = _opt(flip, torch.uint8, "flip", (B,))
+    pc = _chk(coef, torch.int32, "coef", (B, 6))
+    pt = _chk(lut, torch.float32, "lut", (256,))
+    for t, name, shape in ((idx_host, "idx_host", (B,)), (offs_host, "offs_host", (B, 2))):
+        if not isinstance(t, torch.Tensor) or t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError("%s must be a contiguous int32 host tensor of shape %s" % (name, shape))
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=data.device)
+    y = torch.empty((B,), dtype=torch.int64, device=data.device)
+    N.check(N.lib.ee_batch_aug_u8_f32(pd, pl, pi, po, pf, pc, pt, ctypes.c_void_p(idx_host.data_ptr()), ctypes.c_void_p(offs_host.data_ptr()),
+                                      n, B, C, H, W, int(pad), _chk(out, torch.float32, "out"), _chk(y, torch.int64, "labels_out"), _stream()),
+            "ee_batch_aug_u8_f32")
+    return out, y
+
+
 # ---- timing hooks ------------------------------------------------------------------------------------------------------
 def prof_enable(on=True):
     N.check(N.lib.ee_prof_enable(1 if on else 0), "ee_prof_enable")

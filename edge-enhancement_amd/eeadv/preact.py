@@ -4,8 +4,14 @@
   PreActResNet_EE (+ _BPDA, _BPDA_3)             : preactresnet_EE.py:70-187 (the same with CannyFilter_BPDA / CannyFilter_step125_1)
 
 State-dict keys, construction order and initialisation (PyTorch's defaults: the reference's init loop is commented out) are the
-reference's, so a seed gives the same weights and checkpoints load both ways.  Only dataset="Tiny-ImageNet" is built (7x7 / 2 stem +
-BatchNorm + ReLU + max-pool, then 16x16, 8x8, 4x4 and 2x2 maps at 64x64 inputs - exactly the map sizes of eeadv.models.ResNet).
+reference's, so a seed gives the same weights and checkpoints load both ways.  PreActResNet builds only dataset="Tiny-ImageNet" (7x7 / 2
+stem + BatchNorm + ReLU + max-pool, then 16x16, 8x8, 4x4 and 2x2 maps at 64x64 inputs - exactly the map sizes of eeadv.models.ResNet).
+
+  PreActResNetCifar : AWP/Cifar100/models_cifar100_awp/preactresnet.py:67-154 with dataset "CIFAR10" / "CIFAR100" (make_preact_cifar)
+The CIFAR stem is a bare 3x3 / 1 convolution into layer1 and the head is AvgPool2d(4, stride=1) + `linear`.  At 32x32 inputs the stem and
+layer1 work on 32x32 maps, which no kernel of csrc/ takes: those convolutions are MIOpen's (models.conv3 routes them), and the glue
+around them is fused wherever its own predicate accepts the shape.  layer2 - layer4 see 16x16, 8x8 and 4x4 maps and run as the Tiny model's
+layers 1 - 3 do; the final 4x4 map makes the pool global, so the head is ee_head.hip's.
 
 A pre-activation block ends with a bare `out += shortcut`; the next block begins with relu(bn1(out)) and takes the raw sum as its identity
 input.  Here a block hands its output on UN-ADDED, as the pending pair (conv2 output, shortcut), and whoever consumes it - the next
@@ -134,6 +140,8 @@ class PreActBottleneck(nn.Module):
 
 
 class PreActResNet(nn.Module):
+    _linear = "fc"  # the attribute name of the final nn.Linear (a state-dict key of the reference)
+
     def __init__(self, block, num_blocks, num_classes=10, dataset="Tiny-ImageNet"):
         super(PreActResNet, self).__init__()
         self._build_cnn(block, num_blocks, dataset)
@@ -179,21 +187,55 @@ class PreActResNet(nn.Module):
         return feat
 
     def head_from_pre(self, feat):
-        return head(self.avgpool, self.fc, feat)
+        return head(self.avgpool, getattr(self, self._linear), feat)
 
     def head_grad(self, feat, labels, reduction):
         """d CrossEntropyLoss(head(feat), labels) / d feat through ee_head.hip (models.ResNet.head_grad), or None"""
-        if not _HEAD_CE or not _head_is_fused(self.avgpool, self.fc, feat):
+        fc = getattr(self, self._linear)
+        if not _HEAD_CE or not _head_is_fused(self.avgpool, fc, feat):
             return None
         feat = feat.contiguous()
-        logits, _ = ops.pool_linear_fwd(feat, self.fc.weight.detach(), None if self.fc.bias is None else self.fc.bias.detach())
-        return ops.ce_pool_linear_bwd(logits, labels, self.fc.weight.detach(), tuple(feat.shape), reduction)
+        logits, _ = ops.pool_linear_fwd(feat, fc.weight.detach(), None if fc.bias is None else fc.bias.detach())
+        return ops.ce_pool_linear_bwd(logits, labels, fc.weight.detach(), tuple(feat.shape), reduction)
 
     def body(self, x):
         return self.head_from_pre(self.body_pre(x))
 
     def forward(self, x):
         return self.body(x)
+
+
+class PreActResNetCifar(PreActResNet):
+    """The reference's PreActResNet with dataset "CIFAR10" / "CIFAR100" (AWP/Cifar100/models_cifar100_awp/preactresnet.py:74-81, 103-105,
+    128-149): conv1 3x3 / 1 straight into layer1 (no bn1, relu, maxpool), AvgPool2d(4, stride=1), `linear` with 10 / 100 outputs."""
+    _linear = "linear"
+    _CLASSES = {"CIFAR10": 10, "CIFAR100": 100}
+
+    def _build_cnn(self, block, num_blocks, dataset):
+        if dataset not in self._CLASSES:
+            raise NotImplementedError("dataset=%r: the CIFAR PreActResNets take CIFAR10 or CIFAR100 (Tiny-ImageNet: make_preact)" % (dataset,))
+        self.in_planes = 64
+        self.dataset = dataset
+        self.conv1 = nn.Conv2d(3, 64, kernel_size=3, stride=1, padding=1, bias=False)
+
+        self.layer1 = self._make_layer(block, 64, num_blocks[0], stride=1)
+        self.layer2 = self._make_layer(block, 128, num_blocks[1], stride=2)
+        self.layer3 = self._make_layer(block, 256, num_blocks[2], stride=2)
+        self.layer4 = self._make_layer(block, 512, num_blocks[3], stride=2)
+        self.bn = BatchNorm2d(512 * block.expansion)
+
+        self.avgpool = nn.AvgPool2d(4, stride=1)
+        self.linear = nn.Linear(512 * block.expansion, self._CLASSES[dataset])
+
+    def body_pre(self, x):
+        """relu(self.bn(layer4 output)); the stem's output is layer1's block input as it is (a plain tensor: resolve's third case)"""
+        p = conv3(self.conv1, x)
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in layer:
+                p = blk.pending(p)
+        feat, _ = resolve(self.bn, p, want_sum=False)
+        _bump_bn_counters(self)
+        return feat
 
 
 class PreActResNet_EE(_EEFrontMixin, PreActResNet):
@@ -232,6 +274,12 @@ _BLOCKS = {18: (PreActBlock, [2, 2, 2, 2]), 34: (PreActBlock, [3, 4, 6, 3]), 50:
 def make_preact(depth, dataset="CIFAR10"):
     block, layers = _BLOCKS[depth]
     return PreActResNet(block, layers, dataset=dataset)
+
+
+def make_preact_cifar(depth, dataset="CIFAR10"):
+    """the CIFAR models have a door of their own: make_preact keeps refusing every dataset but Tiny-ImageNet"""
+    block, layers = _BLOCKS[depth]
+    return PreActResNetCifar(block, layers, dataset=dataset)
 
 
 def make_preact_ee(depth, variant, dataset="CIFAR10", **kwargs):

@@ -648,6 +648,25 @@ int ee_batch_rrc_u8_f32(const uint8_t *pixels, long long nbytes, const int64_t *
                         const int32_t *idx, const int32_t *boxes, const uint8_t *flip, const float *lut, long long N, int B, int S,
                         float *out, int64_t *labels_out, void *stream);
 
+/* The CIFAR-100 train transform on a split of equal-sized images (utils/data_loader.py:30-36: RandomCrop(32, padding=4) +
+ * RandomHorizontalFlip() + RandomRotation(15) + ToTensor; the rotation ends in PIL's Image.rotate(angle, NEAREST, fillcolor=0)).
+ * data / labels / lut as for ee_batch_u8_f32; per batch position b, drawn by the caller: idx [B] = the sample id, offs [B,2] = (top,
+ * left) of the crop in the image zero-padded by `pad` on every side (0 <= top, left <= 2 pad), flip [B] (nullable: no flip) and
+ * coef [B,6] = (a0 .. a5), PIL's inverse rotation matrix in 16.16 fixed point with the half-pixel offset folded into a2 and a5
+ * (Geometry.c affine_fixed; eeadv.data.aug_coeffs forms it, (65536, 0, 32768, 0, 65536, 32768) is the identity).  Per output pixel:
+ *     xin = (a2 + x a0 + y a1) >> 16,  yin = (a5 + x a3 + y a4) >> 16          source pixel in the mirrored crop, 64-bit integers
+ *     xs = (flip[b] ? W-1-xin : xin) + left - pad,  ys = yin + top - pad      the same pixel in the image
+ *     out[b,c,y,x] = lut[data[idx[b], ys, xs, c]], or 0 when (xin, yin) or (xs, ys) lies outside [0, W) x [0, H)     out [B,C,H,W] f32
+ *     labels_out[b] = labels[idx[b]]
+ * which is ToTensor(rotate(flip(crop(pad(image))))) bit for bit.  One launch; any C >= 1; out 4-byte aligned (EE_ERR_ALIGN), 16-byte
+ * aligned with W % 4 == 0 for the 16-byte stores; B == 0 launches nothing.  idx_host [B] and offs_host [B,2] are HOST copies of idx
+ * and offs (the caller drew them on the host): a sample id outside [0, N) or an offset outside [0, 2 pad] in them returns EE_ERR_SHAPE
+ * before any launch.  The kernel checks the device arrays again; a sample that breaks a bound there is not read - its outputs are
+ * NaN and its label -1. */
+int ee_batch_aug_u8_f32(const uint8_t *data, const int64_t *labels, const int32_t *idx, const int32_t *offs, const uint8_t *flip,
+                        const int32_t *coef, const float *lut, const int32_t *idx_host, const int32_t *offs_host, long long N, int B, int C,
+                        int H, int W, int pad, float *out, int64_t *labels_out, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Optional built-in timing of the last launch of each kernel family (HIP events on `stream`).
  * Off by default; bench.py switches it on outside graph capture to measure kernel durations live.
@@ -672,7 +691,8 @@ int ee_batch_rrc_u8_f32(const uint8_t *pixels, long long nbytes, const int64_t *
 #define EE_K_CONV3S2_BWD 20 /* ee_conv3x3s2_small_bwd_data_f32 */
 #define EE_K_WINO_FUSED 21  /* ee_wino3x3_bn_eval_*, ee_wino3x3_stats_f32, ee_wino3x3_bn_train_*, ee_wino3x3_bwd_sums_f32: the same products with the
                              * BatchNorm work of the layer folded into the staging / output stage; work = the convolution's flops only */
-#define EE_K_COUNT 22
+#define EE_K_BATCH_AUG 22  /* ee_batch_aug_u8_f32 */
+#define EE_K_COUNT 23
 int ee_prof_enable(int on);
 /* records one empty start/stop bracket on `stream` (family EE_K_EMPTY): callers subtract its mean from the other
  * families' means, because a HIP event pair costs ~4-5 us on gfx950 - comparable to the kernels being timed */

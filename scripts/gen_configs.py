@@ -6,7 +6,7 @@ Keys the reference drivers read but some of its files omit (type_canny, step_siz
 import os
 
 ROOT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "edge-enhancement_amd")
-E255 = {1: 0.003921568627451, 2: 0.007843137254902, 16: 0.062745098039216}
+E255 = {1: 0.003921568627451, 2: 0.007843137254902, 8: 0.03137254901960784, 16: 0.062745098039216}
 
 ORDER = ["method_name", "arch", "start_epoch", "epochs", "batch_size", "lr", "momentum", "weight_decay", "workers", "pin_memory",
          "print_freq", "seed", "epsilon", "num_steps_1", "step_size_1", "num_steps_2", "step_size_2", "num_steps_3", "step_size_3",
@@ -108,6 +108,9 @@ FILES = {
     "AWP/Tiny_imagenet/configs_tiny_awp/ee_at_awp.yml": awp("EE_AT_AWP", "PreActResNet18_EE", cize=64, **EE_T),
     "AWP/Tiny_imagenet/configs_tiny_awp/ee_bpda_at_awp.yml": awp("EE_AT_AWP", "PreActResNet18_EE_BPDA", cize=64, **EE_T),
     "AWP/Tiny_imagenet/configs_tiny_awp/ee_bpda_3_at_awp.yml": awp("EE_AT_AWP", "PreActResNet18_EE_BPDA_3", cize=64, **EE_T),
+    # the keys experiments_cifar100_awp.py reads; step_size_2 / num_steps_3 / step_size_3 (its -e path) are written out here
+    "AWP/Cifar100/configs_cifar100_awp/at_awp.yml": awp("AT_AWP", "PreActResNet18", batch_size=128, awp_gamma=0.01, weight_decay=0.0002,
+                                                        epsilon=E255[8], step_size_2=E255[2], num_steps_3=100, step_size_3=E255[2]),
 }
 
 if __name__ == "__main__":
