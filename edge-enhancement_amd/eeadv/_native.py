@@ -54,6 +54,14 @@ SIGNATURES = {
     "ee_mse_num_partials": [c_l],
     "ee_reduce_rows_f64": [c_p, c_l, c_d, c_p, c_p],
     "ee_topk_i64": [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p],
+    # x, x_old, g, x0, step, counter, B, per_sample, eps, stream
+    "ee_apgd_step_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_f, c_p],
+    # logits, labels, targets, B, K, kind, row_loss, dlogits, pred, stream
+    "ee_apgd_loss_f32": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    # loss, pred, fstate, istate, counter, sched, n_iter, B, stream
+    "ee_apgd_book_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
+    # x, g, x_best, g_best, x_best_adv, flags, counter, B, per_sample, stream
+    "ee_apgd_select_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_p],
     "ee_add_square_fwd_f32": [c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_add_square_bwd_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_square_draw_f32": [c_p, c_l, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],

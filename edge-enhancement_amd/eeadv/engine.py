@@ -221,3 +221,179 @@ def pgd_loop(model, x0, x_init, spec, num_steps, step_size, eps, direction=1, lo
         attack_step_(model, x, x0, spec, step_size, eps, direction, lo, hi)
         x = x.detach()
     return x.requires_grad_(False)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# APGD (Croce & Hein 2020; Linf, one run, no EOT): APGD-CE and, on the targeted DLR loss, the runs of APGD-T
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def apgd_schedule(n_iter):
+    """sched[i] = the window length k when a checkpoint closes iteration i (0-based), else 0.  k starts at max(int(0.22 n), 1) and
+    shrinks by max(int(0.03 n), 1) per checkpoint down to max(int(0.06 n), 1): n = 100 puts checkpoints after iterations 22, 41, 57, 70, 80,
+    87, 93, 99 (counted from 1)."""
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("APGD needs n_iter >= 1")
+    k, n_min, dec = max(int(0.22 * n_iter), 1), max(int(0.06 * n_iter), 1), max(int(0.03 * n_iter), 1)
+    sched, since = [0] * n_iter, 0
+    for i in range(n_iter):
+        since += 1
+        if since == k:
+            sched[i], since, k = k, 0, max(k - dec, n_min)
+    return sched
+
+
+class _ApgdSpec:
+    """The loss-gradient step of `_body_input_grad` for an APGD run: the row losses, their logit gradient and `pred` in one launch, then -
+    once the run is past its start point - the per-sample bookkeeping in a second one.  The kind is none of the CE kinds, so the route is the
+    generic one (logits -> this -> autograd): the fused head launches produce no row losses."""
+
+    def __init__(self, run):
+        self.kind, self.payload, self.run = "apgd_" + run.loss, run.y, run
+
+    def dlogits(self, logits):
+        r = self.run
+        r.loss_rows, d, r.pred = ops.apgd_loss(logits.detach(), r.y, r.loss, r.t)
+        if r.started:
+            ops.apgd_book_(r.loss_rows, r.pred, r.fstate, r.istate, r.counter, r.sched)
+        return d
+
+
+class _ApgdRun:
+    """The device state of one APGD run (include/eeadv.h, "APGD") and its two pieces: `start` (the forward/backward at the start point and the
+    initial state: a handful of small launches, once per attack) and `iteration` (step, forward, loss, bookkeeping, backward, copies: what
+    a captured graph replays).  No host read anywhere."""
+
+    def __init__(self, x0, y, n_iter, eps, loss):
+        B, dev = x0.shape[0], x0.device
+        self.loss, self.eps, self.n_iter = loss, float(eps), int(n_iter)
+        self.x = torch.empty_like(x0).requires_grad_(True)
+        self.x0, self.x_old, self.g = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
+        self.x_best, self.g_best, self.x_best_adv = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
+        self.y = torch.empty(B, dtype=torch.int64, device=dev)
+        self.t = torch.empty(B, dtype=torch.int64, device=dev) if loss == "dlr_t" else None
+        self.fstate = torch.empty((4, B), dtype=torch.float32, device=dev)
+        self.istate = torch.empty((4, B), dtype=torch.int32, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.sched = torch.tensor(apgd_schedule(n_iter), dtype=torch.int32).to(dev)
+        self.loss0 = torch.empty(B, dtype=torch.float32, device=dev)
+        self.loss_rows = self.pred = None
+        self.started = False
+        self.spec = _ApgdSpec(self)
+
+    def load(self, x_init, x0, y, targets):
+        with torch.no_grad():
+            self.x.detach().copy_(x_init)
+            self.x0.copy_(x0)
+            self.y.copy_(y)
+            if self.t is not None:
+                self.t.copy_(targets)
+
+    def start(self, model):
+        self.started = False
+        g = input_gradient(model, self.x, self.spec)
+        self.started = True
+        with torch.no_grad():
+            x = self.x.detach()
+            for t in (self.x_old, self.x_best, self.x_best_adv):
+                t.copy_(x)
+            self.g.copy_(g)
+            self.g_best.copy_(g)
+            self.loss0.copy_(self.loss_rows)
+            self.fstate[ops.APGD_F_STEP].fill_(2.0 * self.eps)
+            self.fstate[ops.APGD_F_LOSS_BEST:].copy_(self.loss_rows.expand(3, -1))
+            self.istate.zero_()
+            self.istate[ops.APGD_I_REDUCED_LAST].fill_(1)
+            self.istate[ops.APGD_I_ROBUST].copy_(self.pred)
+            self.counter.zero_()
+
+    def iteration(self, model, g):
+        """One iteration from the gradient `g` of the current iterate; returns the gradient of the next one (a fresh tensor, restored in
+        place for the samples a checkpoint sent back)."""
+        ops.apgd_step_(self.x.detach(), self.x_old, g, self.x0, self.fstate[ops.APGD_F_STEP], self.counter, self.eps)
+        g_new = input_gradient(model, self.x, self.spec).contiguous()
+        ops.apgd_select_(self.x.detach(), g_new, self.x_best, self.g_best, self.x_best_adv, self.istate[ops.APGD_I_FLAGS], self.counter)
+        return g_new
+
+    def result(self):
+        with torch.no_grad():
+            robust = self.istate[ops.APGD_I_ROBUST] != 0
+            keep = robust.view(-1, *([1] * (self.x0.dim() - 1)))
+            return torch.where(keep, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
+
+
+class _GraphedApgd:
+    """`iters` consecutive APGD iterations captured into one graph over the static buffers of an _ApgdRun.  The gradient enters through
+    run.g and leaves through it (one copy per replay): inside the graph each iteration reads the autograd result of the one before."""
+
+    def __init__(self, model, run, iters):
+        self.run, self.iters, self.model, self.graph = run, iters, weakref.ref(model), None
+
+    def _body(self, model):
+        g = self.run.g
+        for _ in range(self.iters):
+            g = self.run.iteration(model, g)
+        self.run.g.copy_(g)
+
+    def capture(self, model):
+        runtime.draw_state(self.run.x0.device)
+        self.run.start(model)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):  # warm-up outside capture, as _GraphedStep.capture; the state it advances is rebuilt by the next start()
+                self._body(model)
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        from .models import deferred_bn_counters
+        with torch.cuda.graph(self.graph, capture_error_mode=runtime.capture_mode()):
+            with deferred_bn_counters():
+                self._body(model)
+
+
+def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None):
+    """One APGD run of n_iter iterations from x_init inside the eps-ball around x0, on loss 'ce', 'dlr' or 'dlr_t' (which takes `targets`).
+    Returns (x_adv, robust, loss_best): x0 with the rows that were fooled at any point replaced by a fooling point, robust [B] bool,
+    the best row loss seen [B].  The model's mode is left as the caller set it.  Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a
+    captured graph of up to MAX_ITERS_PER_GRAPH iterations; both give the same bits."""
+    if loss not in ops.APGD_KINDS:
+        raise ValueError("APGD loss must be one of %s, got %r" % (sorted(ops.APGD_KINDS), loss))
+    if loss == "dlr_t" and targets is None:
+        raise ValueError("the targeted DLR loss needs targets")
+    model = _unwrap(model)
+    x0 = x0.detach().contiguous()
+    x_init = x_init.detach().contiguous()
+    n_iter = int(n_iter)
+    if use_graph is None:
+        use_graph = graphs_enabled()
+    if not use_graph:
+        run = _ApgdRun(x0, y, n_iter, eps, loss)
+        run.load(x_init, x0, y, targets)
+        run.start(model)
+        g = run.g
+        for _ in range(n_iter):
+            g = run.iteration(model, g)
+        return run.result()
+    chunk = max(c for c in range(1, min(n_iter, MAX_ITERS_PER_GRAPH) + 1) if n_iter % c == 0)
+    key = ("apgd", id(model), model.training, tuple(x0.shape), loss, n_iter, float(eps), x0.device.index, chunk)
+    gs = _GRAPHS.get(key)
+    if gs is not None and gs.model() is not model:
+        gs = None
+    if gs is None:
+        run = _ApgdRun(x0, y, n_iter, eps, loss)
+        run.load(x_init, x0, y, targets)
+        gs = _GraphedApgd(model, run, chunk)
+        saved = {}
+        if model.training:  # as pgd_loop: the start point and warm-up passes before the capture are extra train-mode forwards
+            saved = {k: v.clone() for k, v in model.state_dict().items() if "running_" in k or "num_batches" in k}
+        gs.capture(model)
+        if saved:
+            live = model.state_dict()
+            for k, v in saved.items():
+                live[k].data.copy_(v)
+        _GRAPHS[key] = gs
+    gs.run.load(x_init, x0, y, targets)
+    refresh_dense_weights()
+    gs.run.start(model)
+    for _ in range(n_iter // chunk):
+        gs.graph.replay()
+    return gs.run.result()

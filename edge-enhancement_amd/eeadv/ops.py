@@ -411,6 +411,62 @@ def topk(logits, labels, k):
     return idx, correct
 
 
+# ---- APGD (ee_apgd.hip) ----------------------------------------------------------------------------------------------
+APGD_KINDS = {"ce": 0, "dlr": 1, "dlr_t": 2}  # EE_APGD_CE / _DLR / _DLR_T
+APGD_F_STEP, APGD_F_LOSS_BEST, APGD_F_PREV, APGD_F_LOSS_BEST_LAST = range(4)  # rows of fstate
+APGD_I_INC, APGD_I_REDUCED_LAST, APGD_I_ROBUST, APGD_I_FLAGS = range(4)  # rows of istate
+APGD_IMPROVED, APGD_FOOLED, APGD_REDUCED = 1, 2, 4  # bits of the flags row
+
+
+def apgd_step_(x, x_old, g, x0, step, counter, eps):
+    """The momentum step in place on x and x_old [B, ...]; step [B] float32, counter [1] int32 (0: the first iteration, a = 1)."""
+    B = x.shape[0]
+    px = _chk(x, torch.float32, "x")
+    po = _chk(x_old, torch.float32, "x_old", x.shape)
+    pg = _chk(g, torch.float32, "g", x.shape)
+    p0 = _chk(x0, torch.float32, "x0", x.shape)
+    ps = _chk(step, torch.float32, "step", (B,))
+    pc = _chk(counter, torch.int32, "counter", (1,))
+    N.check(N.lib.ee_apgd_step_f32(px, po, pg, p0, ps, pc, B, x.numel() // B if B else 0, eps, _stream()), "ee_apgd_step_f32")
+    return x
+
+
+def apgd_loss(logits, labels, kind, targets=None):
+    """(row losses [B] float32, dlogits [B,K] of their sum, pred [B] int32) for kind 'ce', 'dlr' or 'dlr_t' (which reads targets)."""
+    B, K = logits.shape
+    pz = _chk(logits, torch.float32, "logits")
+    py = _chk(labels, torch.int64, "labels", (B,))
+    if kind == "dlr_t" and targets is None:
+        raise ValueError("the targeted DLR loss needs targets")
+    pt = _chk(targets, torch.int64, "targets", (B,)) if kind == "dlr_t" else None
+    loss = torch.empty(B, dtype=torch.float32, device=logits.device)
+    d = torch.empty_like(logits)
+    pred = torch.empty(B, dtype=torch.int32, device=logits.device)
+    N.check(N.lib.ee_apgd_loss_f32(pz, py, pt, B, K, APGD_KINDS[kind], _chk(loss, torch.float32, "loss"), _chk(d, torch.float32, "d"),
+                                   _chk(pred, torch.int32, "pred"), _stream()), "ee_apgd_loss_f32")
+    return loss, d, pred
+
+
+def apgd_book_(loss, pred, fstate, istate, counter, sched):
+    """One iteration's per-sample bookkeeping in place on fstate [4,B] float32 / istate [4,B] int32 (its flags row is the result)."""
+    B = loss.shape[0]
+    N.check(N.lib.ee_apgd_book_f32(_chk(loss, torch.float32, "loss", (B,)), _chk(pred, torch.int32, "pred", (B,)),
+                                   _chk(fstate, torch.float32, "fstate", (4, B)), _chk(istate, torch.int32, "istate", (4, B)),
+                                   _chk(counter, torch.int32, "counter", (1,)), _chk(sched, torch.int32, "sched"), sched.numel(), B, _stream()),
+            "ee_apgd_book_f32")
+    return istate[APGD_I_FLAGS]
+
+
+def apgd_select_(x, g, x_best, g_best, x_best_adv, flags, counter):
+    """The copies the flags [B] ask for, in place, then counter += 1."""
+    B = x.shape[0]
+    px = _chk(x, torch.float32, "x")
+    ptrs = [_chk(t, torch.float32, n, x.shape) for t, n in ((g, "g"), (x_best, "x_best"), (g_best, "g_best"), (x_best_adv, "x_best_adv"))]
+    N.check(N.lib.ee_apgd_select_f32(px, *ptrs, _chk(flags, torch.int32, "flags", (B,)), _chk(counter, torch.int32, "counter", (1,)), B,
+                                     x.numel() // B if B else 0, _stream()), "ee_apgd_select_f32")
+    return x
+
+
 # ---- Add_Square ------------------------------------------------------------------------------------------------------
 def add_square_fwd(x, eps, stripe, sq_sign, sq_pos, sq_size):
     B, C, H, W = x.shape

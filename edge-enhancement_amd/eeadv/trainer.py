@@ -682,7 +682,24 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             tl = torch.fmod(target + off, n_class)
         return A.CWLinfAttack(x=input, y=target, model=model, magnitude=args.epsilon, previous_p=None, max_eps=args.epsilon,
                               max_iters=20, target=tl, n_class=n_class, cur_device=device)[0]
+    if args.attack_method in APGD_METHODS:
+        # not in the reference's drivers (they call the `autoattack` package): APGD-CE, APGD-T on the DLR loss, or CE then T with the
+        # flags ANDed and the first fooling point kept.  num_steps iterations per run; the step size is APGD's own.
+        if targeted:
+            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+        x_adv, robust = None, None
+        if args.attack_method in ('APGD-CE', 'APGD'):
+            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce')
+        if args.attack_method in ('APGD-T', 'APGD'):
+            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class)
+            if x_adv is None:
+                return xt
+            x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
+        return x_adv
     raise NotImplementedError
+
+
+APGD_METHODS = ('APGD-CE', 'APGD-T', 'APGD')
 
 
 def validate_batch(model, criterion, args, input, target, device, num_steps, step_size, n_class):

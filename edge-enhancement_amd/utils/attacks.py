@@ -113,6 +113,132 @@ def targeted_PGD_trick(model, args, inputs, labels, num_steps, step_size, nclass
     return x, target_labels
 
 
+# ---------------------------------------------------------------------------------------------------------
+# APGD-CE and APGD-T (Croce & Hein 2020): the two gradient attacks of AutoAttack's `standard` version.  Not in the
+# reference's utils/attacks.py - its drivers call the `autoattack` package for them.  FAB-T and Square, the `rand` / EOT
+# versions, the L2 / L1 norms and restarts are NOT here, so the result is not an AutoAttack number.
+# ---------------------------------------------------------------------------------------------------------
+def _apgd_row_losses(z, y, loss, t=None):
+    """Row losses [B] of logits [B,K] in z's dtype; classes ordered by value descending, ties to the lower index."""
+    rows = torch.arange(z.shape[0], device=z.device)
+    zy = z[rows, y]
+    if loss == 'ce':
+        return torch.logsumexp(z, dim=1) - zy
+    K = z.shape[1]
+    if K < (3 if loss == 'dlr' else 4):
+        raise ValueError("the %s loss needs at least %d classes" % (loss, 3 if loss == 'dlr' else 4))
+    zs, order = torch.sort(z, dim=1, descending=True, stable=True)
+    tiny = torch.tensor(1e-12, dtype=torch.float32).to(z.dtype)  # the constant is a float32 one in every dtype
+    if loss == 'dlr':
+        o = torch.where(order[:, 0] == y, order[:, 1], order[:, 0])
+        return -(zy - z[rows, o]) / ((zs[:, 0] - zs[:, 2]) + tiny)
+    if loss == 'dlr_t':
+        return -(zy - z[rows, t]) / ((zs[:, 0] - (zs[:, 2] + zs[:, 3]) * 0.5) + tiny)
+    raise ValueError("APGD loss must be 'ce', 'dlr' or 'dlr_t', got %r" % (loss,))
+
+
+def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None):
+    """Plumbing path for CPU tensors (opt-in), the counterpart of _host_loop: the iteration of engine.apgd_loop in plain torch ops, in the
+    input's dtype.  `trace`, a list, receives one dict of clones per iteration (the start point first)."""
+    def grad_at(xc):
+        xc = xc.detach().requires_grad_()
+        with torch.enable_grad():
+            z = model(xc)
+            rows = _apgd_row_losses(z, y, loss, t)
+        g = torch.autograd.grad(rows.sum(), [xc])[0]
+        zd = z.detach()
+        first = torch.sort(zd, dim=1, descending=True, stable=True)[1][:, 0]
+        return rows.detach(), g.detach(), first == y
+
+    def proj(v):
+        return torch.clamp(torch.min(torch.max(v, x0 - eps), x0 + eps), 0, 1)
+
+    shape = (-1,) + (1,) * (x0.dim() - 1)
+    sched = engine.apgd_schedule(n_iter)
+    x = x.detach()
+    l, g, pred = grad_at(x)
+    step = torch.full_like(l, 2.0 * eps)
+    loss_best, f_prev, loss_best_last = l.clone(), l.clone(), l.clone()
+    x_best, x_best_adv, x_old, g_best = x.clone(), x.clone(), x.clone(), g.clone()
+    reduced_last = torch.ones_like(pred)
+    inc = torch.zeros_like(y)
+    robust = pred.clone()
+
+    def note(**kw):
+        if trace is not None:
+            kw.update(x=x, x_old=x_old, g=g, loss=l, pred=pred, step=step, loss_best=loss_best, f_prev=f_prev, loss_best_last=loss_best_last,
+                      inc=inc, reduced_last=reduced_last, robust=robust, x_best=x_best, g_best=g_best, x_best_adv=x_best_adv)
+            trace.append({k: v.clone() for k, v in kw.items()})
+    note()
+    for i in range(n_iter):
+        a = 1.0 if i == 0 else 0.75
+        z = proj(x + step.view(shape) * torch.sign(g))
+        x_new = proj((x + (z - x) * a) + (x - x_old) * (1.0 - a))
+        x_old, x = x, x_new
+        l, g, pred = grad_at(x)
+        fooled = ~pred
+        robust = robust & pred
+        x_best_adv = torch.where(fooled.view(shape), x, x_best_adv)
+        inc = inc + (l > f_prev).to(inc.dtype)
+        f_prev = l.clone()
+        improved = l > loss_best
+        loss_best = torch.where(improved, l, loss_best)
+        x_best = torch.where(improved.view(shape), x, x_best)
+        g_best = torch.where(improved.view(shape), g, g_best)
+        reduced = torch.zeros_like(pred)
+        k = sched[i]
+        if k:
+            osc = 4 * inc <= 3 * k
+            noimp = ~reduced_last & (loss_best_last >= loss_best)
+            reduced = osc | noimp
+            reduced_last, loss_best_last, inc = reduced.clone(), loss_best.clone(), torch.zeros_like(inc)
+            step = torch.where(reduced, step / 2, step)
+            x = torch.where(reduced.view(shape), x_best, x)
+            g = torch.where(reduced.view(shape), g_best, g)
+        note(improved=improved, fooled=fooled, reduced=reduced)
+    return torch.where(robust.view(shape), x0, x_best_adv), robust, loss_best
+
+
+def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None):
+    """One APGD run (Linf, eps = args.epsilon, num_steps iterations) on loss 'ce', 'dlr' or 'dlr_t' (targeted at `y_target`).  Returns
+    (x_adv, robust): the inputs, with every sample that some iterate fooled replaced by such an iterate, and the [B] bool flags of the samples
+    that stayed correctly classified throughout.  The start point is the project's uniform start, clamp(x0 + U(-eps, eps), 0, 1) (`noise=`
+    injects the draw); the public implementation rescales each sample's draw to the full radius first - that normalisation is deliberately
+    left out.  The model runs in the mode the caller left it in.  On the device the targeted DLR denominator is formed as the mean of
+    z_p1 - z_p3 and z_p1 - z_p4 (csrc/ee_apgd.hip: no cancellation against a rounded sum); the host path below keeps
+    z_p1 - (z_p3 + z_p4)/2, so an fp32 host run and a device run differ in the last bits of the `dlr_t` loss."""
+    x0 = inputs.detach()
+    eps = float(args.epsilon)
+    x = _uniform_start(x0, eps, noise)
+    if runtime.require_device(x0, "APGD"):
+        x_adv, robust, _ = engine.apgd_loop(model, x0, x, targets, num_steps, eps, loss, y_target)
+    else:
+        x_adv, robust, _ = _apgd_host(model, x0, x, targets, num_steps, eps, loss, y_target)
+    return x_adv, robust
+
+
+def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None):
+    """Targeted APGD on the DLR loss: one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most
+    nclass - 1 of them), each on the whole batch - samples fooled by an earlier target are carried along, which keeps one shape (one captured
+    graph) for all runs.  Returns (x_adv, robust) with the flags ANDed over the runs and, per sample, the first fooling point."""
+    x0 = inputs.detach()
+    n_t = min(int(n_target_classes), int(nclass) - 1)
+    with torch.no_grad():
+        z = model(x0)
+    if runtime.require_device(x0, "APGD_T"):
+        order = ops.topk(z.detach().float().contiguous(), None, n_t + 1)[0]
+    else:
+        order = torch.sort(z, dim=1, descending=True, stable=True)[1][:, :n_t + 1]
+    x_adv = x0.clone()
+    robust = torch.ones(x0.shape[0], dtype=torch.bool, device=x0.device)
+    shape = (-1,) + (1,) * (x0.dim() - 1)
+    for j in range(1, n_t + 1):
+        xa, rb = APGD(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise)
+        x_adv = torch.where((robust & ~rb).view(shape), xa, x_adv)
+        robust = robust & rb
+    return x_adv, robust
+
+
 class LabelSmoothLoss(torch.nn.Module):
     """attacks.py:89-99."""
 

@@ -209,6 +209,60 @@ int ee_reduce_rows_f64(const double *rows, int64_t n, double scale, double *out,
 int ee_topk_i64(const float *logits, const int64_t *labels, int B, int K, int k, int64_t *idx, int64_t *correct,
                 void *stream);
 
+/* ---- APGD (Croce & Hein 2020, Linf, one run, no EOT): the per-iteration work around the classifier, ee_apgd.hip ----
+ * State of one attack on B samples of per_sample elements each, all in device memory:
+ *   x, x_old, x0, g, x_best, g_best, x_best_adv   float [B, per_sample]
+ *   fstate  float [4, B]: rows EE_APGD_F_*  (step size, best loss, previous loss, best loss at the last checkpoint)
+ *   istate  int   [4, B]: rows EE_APGD_I_*  (loss increases in the window, reduced at the last checkpoint, still robust, flags)
+ *   counter int   [1]   : index of the iteration in flight (0-based); ee_apgd_select_f32 advances it
+ *   sched   int   [n_iter]: sched[i] = the window length k if a checkpoint closes iteration i, else 0
+ * An iteration is step -> classifier forward -> loss -> book -> classifier backward -> select.  No argument changes from one
+ * iteration to the next, so a captured graph of one iteration replays for all of them. */
+#define EE_APGD_CE 0    /* lse(z) - z_y                                   dlogits = softmax(z) - onehot(y) */
+#define EE_APGD_DLR 1   /* -(z_y - z_o) / (z_p1 - z_p3 + 1e-12), o = p2 if p1 == y else p1           (K >= 3) */
+#define EE_APGD_DLR_T 2 /* -(z_y - z_t) / (z_p1 - (z_p3 + z_p4)/2 + 1e-12)                           (K >= 4) */
+#define EE_APGD_F_STEP 0
+#define EE_APGD_F_LOSS_BEST 1
+#define EE_APGD_F_PREV 2
+#define EE_APGD_F_LOSS_BEST_LAST 3
+#define EE_APGD_I_INC 0
+#define EE_APGD_I_REDUCED_LAST 1
+#define EE_APGD_I_ROBUST 2
+#define EE_APGD_I_FLAGS 3
+#define EE_APGD_IMPROVED 1 /* flags: the loss beat loss_best -> x_best, g_best take the iterate */
+#define EE_APGD_FOOLED 2   /*        the iterate is misclassified -> x_best_adv takes it */
+#define EE_APGD_REDUCED 4  /*        the step was halved at a checkpoint -> x, g return to x_best, g_best */
+
+/* The momentum step, in place on x and x_old, with P(v) = clamp(min(max(v, x0 - eps), x0 + eps), 0, 1) and a = 1 when
+ * counter[0] == 0, else 0.75:
+ *     z = P(x + step[b]*sign(g));  x_new = P((x + (z - x)*a) + (x - x_old)*(1 - a));  x_old = x;  x = x_new
+ * b = element / per_sample; sign(NaN) = sign(0) = 0 as in ee_pgd_step_f32.  32 B of HBM traffic per element. */
+int ee_apgd_step_f32(float *x, float *x_old, const float *g, const float *x0, const float *step, const int *counter, int64_t B,
+                     int64_t per_sample, float eps, void *stream);
+
+/* Per row of logits [B,K]: row_loss[B] (fp32), dlogits[B,K] = d sum_b loss_b / d logits, pred[B] = (p1 == y), where p1, p2, ...
+ * are the classes by value descending, ties to the lower index (the order of ee_topk_i64).  kind = EE_APGD_CE / _DLR / _DLR_T;
+ * targets [B] is read for EE_APGD_DLR_T only.  K below the kind's minimum: EE_ERR_UNSUPPORTED.  The targeted denominator is formed
+ * as ((z_p1 - z_p3) + (z_p1 - z_p4))/2 + 1e-12: the same number without the cancellation of subtracting a rounded sum (the
+ * host path of utils/attacks.py keeps z_p1 - (z_p3 + z_p4)/2, so its fp32 loss differs from this one in the last bits).  A label or target outside
+ * [0, K) gives that row a NaN loss, a zero gradient and pred = 0. */
+int ee_apgd_loss_f32(const float *logits, const int64_t *labels, const int64_t *targets, int B, int K, int kind, float *row_loss,
+                     float *dlogits, int *pred, void *stream);
+
+/* The per-sample bookkeeping of one iteration from its losses and pred, one thread per sample, with k = sched[counter[0]]:
+ *     robust &= pred;  fooled = !pred;  inc += (loss > f_prev);  f_prev = loss;  improved = loss > loss_best -> loss_best = loss
+ *     if k > 0:  reduced = (4*inc <= 3*k) || (!reduced_last && loss_best_last >= loss_best);  reduced_last = reduced;
+ *                loss_best_last = loss_best;  inc = 0;  if reduced: step /= 2
+ * and writes the three decisions to the flags row of istate.  A counter outside [0, n_iter) is no checkpoint. */
+int ee_apgd_book_f32(const float *loss, const int *pred, float *fstate, int *istate, const int *counter, const int *sched, int n_iter,
+                     int B, void *stream);
+
+/* The tensor copies the flags [B] ask for, then counter[0] += 1.  Per sample: fooled: x_best_adv = x;  improved: x_best = x,
+ * g_best = g;  reduced: x = x_best, g = g_best (x_old stays).  A sample with no flag costs the read of its flag.  B == 0 or
+ * per_sample == 0 is no attack: nothing is launched and the counter stays. */
+int ee_apgd_select_f32(float *x, float *g, float *x_best, float *g_best, float *x_best_adv, const int *flags, int *counter, int B,
+                       int64_t per_sample, void *stream);
+
 /* CannyFilter_BPDA (utils/core.py:386-505; AWP configs): no alpha mask, NMS by multiplication, thresholds through
  * To_compare (core.py:329-358), hysteresis through To_eq (core.py:361-382).  thresholds given, hysteresis=True.
  *   forward: edge, thin (the thinned magnitude), t2 (the {0, .5, 1} threshold map) [B,1,H,W]; thin / t2 feed the backward.
