@@ -6,16 +6,27 @@
 // and two (backward) launches per layer of pure HBM-bound element-wise work.  Fused: one launch each way, the
 // normalised tensor is written once, and the ReLU mask is taken from the output instead of a saved copy.
 //
-// Three families, chosen per shape by the launcher: (1) "cached": one workgroup per channel, the channel held in registers
-// (one read pass, all loads of a lane in flight together) - every layer but the stem at the reference batch; (2) "split":
-// a channel too large for that is cut into slices, one workgroup each, partial statistics through a small workspace and a
-// second launch (the 64-channel stem); (3) the generic three-pass loop (any shape, also unaligned).  Training mode: mean,
-// then centred variance (two-pass, fp32, fixed-order wave / workgroup reductions -> bit-reproducible), then normalise +
-// add + ReLU.  Running statistics are updated in the kernel exactly as nn.BatchNorm2d does (momentum, unbiased
-// variance).  NCHW fp32; 16-B accesses when H*W % 4 == 0 (every ResNet stage: 1024, 256, 64, 16, 4).
+// Seven kernel families.  The first three serve ee_bn_act_fwd/bwd_f32, which picks per shape:
+//   cached   HW % 4 == 0, 16-B aligned, B * HW / 4 <= 7168 (cached_variant): one workgroup per channel - up to four on few-channel
+//            layers (cached_parts) - holds the channel in registers: one read pass, all loads of a lane in flight together.
+//            Every layer but the stem at the reference batch.
+//   split    aligned channels too large for that, given a workspace: cut into slices (split_slices), one workgroup each; partial
+//            statistics through the workspace, a second launch recombines and applies.  The 64-channel stem.
+//   generic  everything else (no workspace, unaligned, HW % 4 != 0): one workgroup per channel, three passes over memory.
+// The other four have entry points of their own, on the machinery of the first three:
+//   dual     ee_bn_dual_*: relu(bn_a(xa) + bn_b(xb)), the end of a block with a down-sampling shortcut, cached <256, *> only.
+//   sum      ee_bn_sum_act_*: the block boundary of a pre-activation network, bn(x + res); the cached kernels' SUM / ADD flags.
+//   pool     ee_bn_relu_pool_*: the stem's relu(bn(x)) -> MaxPool2d(3, 2, 1) without the full-resolution activation.
+//   sync     ee_syncbn_*: SyncBatchNorm's local halves around the two collectives, on the split kernels.
+// Training mode: mean, then centred variance (two-pass, fp32, fixed-order wave / workgroup reductions -> bit-reproducible), then
+// normalise + add + ReLU.  Running statistics are updated in the kernel exactly as nn.BatchNorm2d does (momentum, unbiased
+// variance).  NCHW fp32.  Every per-element and per-channel expression is one of ee_bn_math.hpp's, which is what makes the
+// families (and the convolutions of ee_fuse.hpp) agree bit for bit.
 //
 // This is CNN-body glue, not one of SURVEY.md section 8's rows: parity is "logits within 1e-4" through the model tests.
-#include "ee_common.hpp"
+#include "ee_bn_math.hpp"
+
+#include <type_traits>
 
 namespace {
 
@@ -62,26 +73,24 @@ struct BnShape {
     int B, C, HW;
 };
 
-// the gradient may arrive in two pieces (the block output feeds the next block's convolution AND its identity branch; autograd
-// would add them in a separate launch): dy + dy2, the same fp32 add, on load
-__device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-// The ReLU mask of the backward is y > 0.  Without a residual branch y = relu((x - mean) * a + b0), so the mask can be recomputed
-// from x - which the backward reads anyway - with the forward's expression (the same bits) instead of reading y (one tensor less:
-// the layer-1 kernels run one workgroup per channel on 64 CUs and are bound by what a CU can pull).  MaskArgs.on selects it.
-struct MaskArgs {
-    int on;
-    float a, b0;  // invstd * gamma, beta
-};
-__device__ __forceinline__ float4 pre4(float4 v, float mean, const MaskArgs &m) {
-    return make_float4((v.x - mean) * m.a + m.b0, (v.y - mean) * m.a + m.b0, (v.z - mean) * m.a + m.b0, (v.w - mean) * m.a + m.b0);
+template <int NT>
+__device__ __forceinline__ void block_sum_pair(float &a, float &b, float *scratch) {
+    float two[2] = {a, b};
+    block_sums<NT, 2>(two, scratch);
+    a = two[0], b = two[1];
 }
-__device__ __forceinline__ MaskArgs mask_args(const float *y, const float *gamma, const float *beta, float invstd, int c) {
-    MaskArgs m;
-    m.on = y == nullptr;
-    m.a = invstd * (gamma ? gamma[c] : 1.0f);
-    m.b0 = (beta && m.on) ? beta[c] : 0.0f;
-    return m;
+
+// y = [relu]((v - mean) * a + b0 [+ q])
+template <bool RELU, bool RES>
+__device__ __forceinline__ float4 bn_out4(float4 v, float4 q, float mean, float a, float b0) {
+    float4 r = bn_affine4(v, mean, a, b0);
+    if (RES) r = add4(r, q);
+    return RELU ? relu_nan4(r) : r;
+}
+
+__device__ __forceinline__ void put_param_grads(float *dgamma, float *dbeta, int c, float sdz, float sdzx) {
+    if (dgamma) dgamma[c] = sdzx;
+    if (dbeta) dbeta[c] = sdz;
 }
 
 // element e (0 .. B*HW) of channel c lives at ((b*C + c)*HW + p), b = e / HW, p = e % HW; VEC = 4 walks float4s (HW % 4 == 0)
@@ -107,60 +116,35 @@ __global__ __launch_bounds__(NT) void bn_fwd_kernel(const float *__restrict__ x,
     if (training) {
         float acc = 0.0f;
         for_channel<NT, VEC>(s, c, [&](size_t o) {
-            if (VEC == 4) {
-                const float4 v = *reinterpret_cast<const float4 *>(x + o);
-                acc += (v.x + v.y) + (v.z + v.w);
-            } else {
-                acc += x[o];
-            }
+            if (VEC == 4) acc += quad_sum(*reinterpret_cast<const float4 *>(x + o));
+            else acc += x[o];
         });
         mean = block_sum<NT>(acc, scratch) / n;
         float var = 0.0f;
         for_channel<NT, VEC>(s, c, [&](size_t o) {
             if (VEC == 4) {
-                const float4 v = *reinterpret_cast<const float4 *>(x + o);
-                const float a = v.x - mean, b = v.y - mean, cc = v.z - mean, d = v.w - mean;
-                var += (a * a + b * b) + (cc * cc + d * d);
+                var += quad_sqdev(*reinterpret_cast<const float4 *>(x + o), mean);
             } else {
                 const float a = x[o] - mean;
                 var += a * a;
             }
         });
         var = block_sum<NT>(var, scratch) / n;
-        invstd = 1.0f / sqrtf(var + eps);
-        if (threadIdx.x == 0) {
-            save_mean[c] = mean;
-            save_invstd[c] = invstd;
-            if (running_mean) {
-                const float unbiased = (n > 1.0f) ? var * (n / (n - 1.0f)) : var;
-                running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mean;
-                running_var[c] = (1.0f - momentum) * running_var[c] + momentum * unbiased;
-            }
-        }
+        invstd = bn_invstd(var, eps);
+        if (threadIdx.x == 0) bn_commit_stats(c, mean, var, invstd, n, momentum, save_mean, save_invstd, running_mean, running_var);
     } else {
-        mean = running_mean[c];
-        invstd = 1.0f / sqrtf(running_var[c] + eps);
+        const BnStats st = bn_known_stats(0, save_mean, save_invstd, running_mean, running_var, eps, c);
+        mean = st.mean, invstd = st.invstd;
     }
-    const float a = invstd * (gamma ? gamma[c] : 1.0f), b0 = beta ? beta[c] : 0.0f;
+    const float a = bn_gain(invstd, gamma, c), b0 = bn_shift(beta, c);
     for_channel<NT, VEC>(s, c, [&](size_t o) {
         if (VEC == 4) {
-            const float4 v = *reinterpret_cast<const float4 *>(x + o);
-            float4 r = make_float4((v.x - mean) * a + b0, (v.y - mean) * a + b0, (v.z - mean) * a + b0, (v.w - mean) * a + b0);
-            if (RES) {
-                const float4 q = *reinterpret_cast<const float4 *>(res + o);
-                r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-            }
-            if (RELU) {
-                r.x = r.x > 0.0f ? r.x : (r.x != r.x ? r.x : 0.0f);
-                r.y = r.y > 0.0f ? r.y : (r.y != r.y ? r.y : 0.0f);
-                r.z = r.z > 0.0f ? r.z : (r.z != r.z ? r.z : 0.0f);
-                r.w = r.w > 0.0f ? r.w : (r.w != r.w ? r.w : 0.0f);
-            }
-            *reinterpret_cast<float4 *>(y + o) = r;
+            const float4 q = RES ? *reinterpret_cast<const float4 *>(res + o) : zero4();
+            *reinterpret_cast<float4 *>(y + o) = bn_out4<RELU, RES>(*reinterpret_cast<const float4 *>(x + o), q, mean, a, b0);
         } else {
-            float r = (x[o] - mean) * a + b0;
+            float r = bn_affine(x[o], mean, a, b0);
             if (RES) r += res[o];
-            if (RELU) r = r > 0.0f ? r : (r != r ? r : 0.0f);
+            if (RELU) r = relu_nan(r);
             y[o] = r;
         }
     });
@@ -168,6 +152,8 @@ __global__ __launch_bounds__(NT) void bn_fwd_kernel(const float *__restrict__ x,
 
 // backward.  dz = RELU ? dy * (y > 0) : dy  (threshold_backward); dres = dz (the residual branch's gradient);
 // training: dx = gamma*invstd * (dz - mean(dz) - xhat * mean(dz*xhat));  eval: dx = gamma*invstd_running * dz.
+// The gradient may arrive in two pieces (the block output feeds the next block's convolution AND its identity branch; autograd
+// would add them in a separate launch): dy + dy2, the same fp32 add, on load.
 template <int NT, int VEC, bool RELU>
 __global__ __launch_bounds__(NT) void bn_bwd_kernel(const float *__restrict__ dy, const float *__restrict__ dy2, const float *__restrict__ y,
                                                     const float *__restrict__ x, const float *__restrict__ beta,
@@ -178,24 +164,18 @@ __global__ __launch_bounds__(NT) void bn_bwd_kernel(const float *__restrict__ dy
     __shared__ float scratch[3 * (NT / 64)];
     const int c = blockIdx.x;
     const float n = static_cast<float>(s.B) * static_cast<float>(s.HW);
-    const float mean = training ? save_mean[c] : running_mean[c];
-    const float invstd = training ? save_invstd[c] : 1.0f / sqrtf(running_var[c] + eps);
+    const BnStats st = bn_known_stats(training, save_mean, save_invstd, running_mean, running_var, eps, c);
+    const float mean = st.mean, invstd = st.invstd;
     const MaskArgs mk = mask_args(y, gamma, beta, invstd, c);
     auto masked4 = [&](size_t o, float4 v) {
         float4 g = *reinterpret_cast<const float4 *>(dy + o);
         if (dy2) g = add4(g, *reinterpret_cast<const float4 *>(dy2 + o));
-        if (RELU) {
-            const float4 yy = mk.on ? pre4(v, mean, mk) : *reinterpret_cast<const float4 *>(y + o);
-            g.x = yy.x > 0.0f ? g.x : 0.0f;
-            g.y = yy.y > 0.0f ? g.y : 0.0f;
-            g.z = yy.z > 0.0f ? g.z : 0.0f;
-            g.w = yy.w > 0.0f ? g.w : 0.0f;
-        }
+        if (RELU) g = mask4(g, mk.on ? bn_affine4(v, mean, mk.a, mk.b0) : *reinterpret_cast<const float4 *>(y + o));
         return g;
     };
     auto masked1 = [&](size_t o, float v) {
         float g = dy2 ? dy[o] + dy2[o] : dy[o];
-        if (RELU) g = (mk.on ? (v - mean) * mk.a + mk.b0 : y[o]) > 0.0f ? g : 0.0f;
+        if (RELU) g = mask1(g, mk.on ? bn_affine(v, mean, mk.a, mk.b0) : y[o]);
         return g;
     };
     float sdz = 0.0f, sdzx = 0.0f;
@@ -203,52 +183,104 @@ __global__ __launch_bounds__(NT) void bn_bwd_kernel(const float *__restrict__ dy
         if (VEC == 4) {
             const float4 v = *reinterpret_cast<const float4 *>(x + o);
             const float4 g = masked4(o, v);
-            sdz += (g.x + g.y) + (g.z + g.w);
-            sdzx += (g.x * ((v.x - mean) * invstd) + g.y * ((v.y - mean) * invstd)) + (g.z * ((v.z - mean) * invstd) + g.w * ((v.w - mean) * invstd));
+            sdz += quad_sum(g);
+            sdzx += quad_dot(g, bn_xhat4(v, mean, invstd));
         } else {
             const float v = x[o];
             const float g = masked1(o, v);
             sdz += g;
-            sdzx += g * ((v - mean) * invstd);
+            sdzx += g * bn_xhat(v, mean, invstd);
         }
     });
-    {
-        float two[2] = {sdz, sdzx};
-        block_sums<NT, 2>(two, scratch);
-        sdz = two[0], sdzx = two[1];
-    }
-    if (threadIdx.x == 0) {
-        if (dgamma) dgamma[c] = sdzx;
-        if (dbeta) dbeta[c] = sdz;
-    }
-    const float w = (gamma ? gamma[c] : 1.0f) * invstd;
+    block_sum_pair<NT>(sdz, sdzx, scratch);
+    if (threadIdx.x == 0) put_param_grads(dgamma, dbeta, c, sdz, sdzx);
+    const float w = bn_gain(invstd, gamma, c);
     const float m1 = training ? sdz / n : 0.0f, m2 = training ? sdzx / n : 0.0f;
     for_channel<NT, VEC>(s, c, [&](size_t o) {
         if (VEC == 4) {
             const float4 v = *reinterpret_cast<const float4 *>(x + o);
             const float4 g = masked4(o, v);
             if (dres) *reinterpret_cast<float4 *>(dres + o) = g;
-            if (dx) {
-                float4 r;
-                r.x = w * ((g.x - m1) - ((v.x - mean) * invstd) * m2);
-                r.y = w * ((g.y - m1) - ((v.y - mean) * invstd) * m2);
-                r.z = w * ((g.z - m1) - ((v.z - mean) * invstd) * m2);
-                r.w = w * ((g.w - m1) - ((v.w - mean) * invstd) * m2);
-                *reinterpret_cast<float4 *>(dx + o) = r;
-            }
+            if (dx) *reinterpret_cast<float4 *>(dx + o) = bn_dx4(w, g, m1, bn_xhat4(v, mean, invstd), m2);
         } else {
             const float v = x[o];
             const float g = masked1(o, v);
             if (dres) dres[o] = g;
-            if (dx) dx[o] = w * ((g - m1) - ((v - mean) * invstd) * m2);
+            if (dx) dx[o] = bn_dx(w, g, m1, bn_xhat(v, mean, invstd), m2);
         }
     });
 }
 
-
 // ---- register-cached variants: a channel that fits MAXV float4s per lane is read from memory ONCE (the two-pass
 // statistics and the normalisation run on registers), which removes two of the three dependent L2 round trips -------------
-__device__ __forceinline__ float relu_nan(float r) { return r > 0.0f ? r : (r != r ? r : 0.0f); }
+
+// float4 offsets of a lane's MAXV register slots in channel c; load(j) then reads slot j.  A slot past the channel's end gets the
+// offset of the channel's last element, so every slot is loaded unconditionally - MAXV loads in flight - and masked afterwards
+// (slot_valid): a load under a predicate becomes a branch with its own s_waitcnt, i.e. MAXV serialised memory round trips.
+template <int NT, int MAXV, class L>
+__device__ __forceinline__ void load_channel(const BnShape s, int c, unsigned (&off)[MAXV], L load) {
+    const int per = s.HW / 4, total = s.B * per;
+#pragma unroll
+    for (int j = 0; j < MAXV; ++j) {
+        const int e0 = threadIdx.x + j * NT;
+        const int e = e0 < total ? e0 : total - 1;
+        const int b = e / per, q = e - b * per;
+        off[j] = static_cast<unsigned>(b * s.C + c) * static_cast<unsigned>(per) + static_cast<unsigned>(q);
+        load(j);
+    }
+}
+template <int NT>
+__device__ __forceinline__ bool slot_valid(int j, int total) {
+    return static_cast<int>(threadIdx.x) + j * NT < total;
+}
+
+// gridDim.y = P workgroups per channel (few-channel layers: 64 channels fill 64 of 256 CUs).  Every one of them reads the whole
+// channel and forms the SAME sums in the same order (the same bits); part p then finishes and stores only the register slots it owns -
+// a quarter of the stores per CU - and part 0 owns the per-channel side effects.
+template <int MAXV>
+__device__ __forceinline__ bool owns_slot(int j, int P, int part) {
+    return j * P / MAXV == part;
+}
+// a tensor that only the last pass needs (the forward's residual, the backward's dadd), so only for the slots the part owns; the slots
+// of other parts load this part's first own slot again - unconditional, and no traffic
+template <int MAXV>
+__device__ __forceinline__ void load_own_slots(const float4 *p, const unsigned (&off)[MAXV], int P, int part, float4 (&v)[MAXV]) {
+    const int jf = (part * MAXV + P - 1) / P;  // (smallest j with j * P / MAXV == part)
+    unsigned of = off[0];
+#pragma unroll
+    for (int j = 1; j < MAXV; ++j) of = j == jf ? off[j] : of;
+#pragma unroll
+    for (int j = 0; j < MAXV; ++j) v[j] = p[owns_slot<MAXV>(j, P, part) ? off[j] : of];
+}
+
+struct BnParams {
+    const float *gamma, *beta;
+    float *running_mean, *running_var;
+    float momentum, eps;
+    float *save_mean, *save_invstd;
+};
+
+// mean and invstd of the channel held in xv (lanes past the end hold zeros); in training mode the workgroup with `writer` commits them
+template <int NT, int MAXV>
+__device__ __forceinline__ void cached_stats(const float4 (&xv)[MAXV], int total, float n, const BnParams &p, int training, int c, float *scratch,
+                                             bool writer, float &mean, float &invstd) {
+    if (training) {
+        float acc = 0.0f;
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j) acc += quad_sum(xv[j]);
+        mean = block_sum<NT>(acc, scratch) / n;
+        float var = 0.0f;
+#pragma unroll
+        for (int j = 0; j < MAXV; ++j)
+            if (slot_valid<NT>(j, total)) var += quad_sqdev(xv[j], mean);
+        var = block_sum<NT>(var, scratch) / n;
+        invstd = bn_invstd(var, p.eps);
+        if (threadIdx.x == 0 && writer) bn_commit_stats(c, mean, var, invstd, n, p.momentum, p.save_mean, p.save_invstd, p.running_mean, p.running_var);
+    } else {
+        const BnStats st = bn_known_stats(0, p.save_mean, p.save_invstd, p.running_mean, p.running_var, p.eps, c);
+        mean = st.mean, invstd = st.invstd;
+    }
+}
 
 // SUM (ee_bn_sum_act_fwd_f32, the block boundary of a pre-activation network): the statistics and the normalisation are those of
 // s = x + res, so every part reads the residual for ALL its register slots; s goes to sum_out (nullable) for the part's own slots.
@@ -261,93 +293,37 @@ __global__ __launch_bounds__(NT) void bn_fwd_cached_kernel(const float *__restri
                                                            float *__restrict__ save_invstd, BnShape s, float *__restrict__ sum_out) {
     __shared__ float scratch[3 * (NT / 64)];
     const int c = blockIdx.x;
-    // gridDim.y = P workgroups per channel (round 4; few-channel layers: 64 channels fill 64 of 256 CUs).  Every one of them reads the whole
-    // channel and forms the SAME statistics in the same order (the same bits); part p then normalises, adds the residual for and stores only
-    // the register slots j with j * P / MAXV == p - a quarter of the residual reads and of the stores per CU; part 0 owns the statistics' side
-    // effects
     const int P = static_cast<int>(gridDim.y), part = static_cast<int>(blockIdx.y);
-    const int per = s.HW / 4, total = s.B * per;
+    const int total = s.B * (s.HW / 4);
     const float n = static_cast<float>(s.B) * static_cast<float>(s.HW);
-    const float4 *x4 = reinterpret_cast<const float4 *>(x);
-    const float4 *r4 = reinterpret_cast<const float4 *>(res);
+    const float4 *x4 = reinterpret_cast<const float4 *>(x), *r4 = reinterpret_cast<const float4 *>(res);
     float4 xv[MAXV], rv[(RES || SUM) ? MAXV : 1];
     unsigned off[MAXV];
-    float acc = 0.0f;
-    // every load is issued unconditionally on a clamped (always valid) element and masked afterwards: a load under a
-    // predicate becomes a branch with its own s_waitcnt, i.e. MAXV serialised memory round trips instead of MAXV in flight
-#pragma unroll
-    for (int j = 0; j < MAXV; ++j) {
-        const int e0 = threadIdx.x + j * NT;
-        const int e = e0 < total ? e0 : total - 1;
-        const int b = e / per, q = e - b * per;
-        off[j] = static_cast<unsigned>(b * s.C + c) * static_cast<unsigned>(per) + static_cast<unsigned>(q);
-        xv[j] = x4[off[j]];
-    }
-    if (SUM) {
+    load_channel<NT, MAXV>(s, c, off, [&](int j) { xv[j] = x4[off[j]]; });
+    if constexpr (SUM) {
 #pragma unroll
         for (int j = 0; j < MAXV; ++j) rv[j] = r4[off[j]];
 #pragma unroll
         for (int j = 0; j < MAXV; ++j) xv[j] = add4(xv[j], rv[j]);  // one fp32 add per element, as the reference's `out += shortcut`
     }
-    if (RES) {  // needed only by the last pass: its latency hides behind the statistics.  Slots of other parts: a load of this part's first slot
-        const int jf = (part * MAXV + P - 1) / P;  // (smallest j with j * P / MAXV == part)
-        unsigned of = off[0];
+    if constexpr (RES) load_own_slots(r4, off, P, part, rv);  // its latency hides behind the statistics
 #pragma unroll
-        for (int j = 1; j < MAXV; ++j) of = j == jf ? off[j] : of;
-#pragma unroll
-        for (int j = 0; j < MAXV; ++j) rv[j] = r4[(j * P / MAXV == part) ? off[j] : of];
-    }
-#pragma unroll
-    for (int j = 0; j < MAXV; ++j) {
-        if (static_cast<int>(threadIdx.x) + j * NT >= total) xv[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        acc += (xv[j].x + xv[j].y) + (xv[j].z + xv[j].w);
-    }
+    for (int j = 0; j < MAXV; ++j)
+        if (!slot_valid<NT>(j, total)) xv[j] = zero4();
     float mean, invstd;
-    if (training) {
-        mean = block_sum<NT>(acc, scratch) / n;
-        float var = 0.0f;
-#pragma unroll
-        for (int j = 0; j < MAXV; ++j)
-            if (static_cast<int>(threadIdx.x) + j * NT < total) {
-                const float a = xv[j].x - mean, b = xv[j].y - mean, cc = xv[j].z - mean, d = xv[j].w - mean;
-                var += (a * a + b * b) + (cc * cc + d * d);
-            }
-        var = block_sum<NT>(var, scratch) / n;
-        invstd = 1.0f / sqrtf(var + eps);
-        if (threadIdx.x == 0 && part == 0) {
-            save_mean[c] = mean;
-            save_invstd[c] = invstd;
-            if (running_mean) {
-                const float unbiased = (n > 1.0f) ? var * (n / (n - 1.0f)) : var;
-                running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mean;
-                running_var[c] = (1.0f - momentum) * running_var[c] + momentum * unbiased;
-            }
-        }
-    } else {
-        mean = running_mean[c];
-        invstd = 1.0f / sqrtf(running_var[c] + eps);
-    }
-    const float a = invstd * (gamma ? gamma[c] : 1.0f), b0 = beta ? beta[c] : 0.0f;
+    cached_stats<NT, MAXV>(xv, total, n, BnParams{gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd}, training, c, scratch,
+                           part == 0, mean, invstd);
+    const float a = bn_gain(invstd, gamma, c), b0 = bn_shift(beta, c);
     float4 *y4 = reinterpret_cast<float4 *>(y);
 #pragma unroll
     for (int j = 0; j < MAXV; ++j)
-        if (static_cast<int>(threadIdx.x) + j * NT < total && j * P / MAXV == part) {
-            const float4 v = xv[j];
-            if (SUM && sum_out) reinterpret_cast<float4 *>(sum_out)[off[j]] = v;
-            float4 r = make_float4((v.x - mean) * a + b0, (v.y - mean) * a + b0, (v.z - mean) * a + b0, (v.w - mean) * a + b0);
-            if (RES) {
-                const float4 q = rv[j];
-                r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-            }
-            if (RELU) {
-                r.x = relu_nan(r.x); r.y = relu_nan(r.y); r.z = relu_nan(r.z); r.w = relu_nan(r.w);
-            }
-            y4[off[j]] = r;
+        if (slot_valid<NT>(j, total) && owns_slot<MAXV>(j, P, part)) {
+            if (SUM && sum_out) reinterpret_cast<float4 *>(sum_out)[off[j]] = xv[j];
+            y4[off[j]] = bn_out4<RELU, RES>(xv[j], rv[RES ? j : 0], mean, a, b0);
         }
 }
 
-// ADD (ee_bn_sum_act_bwd_f32): dx += dadd on store - the gradient that reaches the normalised sum through the next block's identity branch;
-// loaded only for the part's own slots, like the forward's residual
+// ADD (ee_bn_sum_act_bwd_f32): dx += dadd on store - the gradient that reaches the normalised sum through the next block's identity branch
 template <int NT, int MAXV, bool RELU, bool ADD = false>
 __global__ __launch_bounds__(NT) void bn_bwd_cached_kernel(const float *__restrict__ dy, const float *__restrict__ dy2, const float *__restrict__ y,
                                                            const float *__restrict__ x, const float *__restrict__ beta,
@@ -358,81 +334,50 @@ __global__ __launch_bounds__(NT) void bn_bwd_cached_kernel(const float *__restri
                                                            float *__restrict__ dbeta, BnShape s, const float *__restrict__ dadd) {
     __shared__ float scratch[3 * (NT / 64)];
     const int c = blockIdx.x;
-    const int P = static_cast<int>(gridDim.y), part = static_cast<int>(blockIdx.y);  // as in bn_fwd_cached_kernel: the sums by every part, the stores split
-    const int per = s.HW / 4, total = s.B * per;
+    const int P = static_cast<int>(gridDim.y), part = static_cast<int>(blockIdx.y);
+    const int total = s.B * (s.HW / 4);
     const float n = static_cast<float>(s.B) * static_cast<float>(s.HW);
-    const float mean = training ? save_mean[c] : running_mean[c];
-    const float invstd = training ? save_invstd[c] : 1.0f / sqrtf(running_var[c] + eps);
+    const BnStats st = bn_known_stats(training, save_mean, save_invstd, running_mean, running_var, eps, c);
+    const float mean = st.mean, invstd = st.invstd;
     const float4 *dy4 = reinterpret_cast<const float4 *>(dy), *y4 = reinterpret_cast<const float4 *>(y), *x4 = reinterpret_cast<const float4 *>(x);
     const float4 *dy24 = reinterpret_cast<const float4 *>(dy2);
-    float4 gv[MAXV], hv[MAXV];  // masked gradient dz and xhat
+    float4 gv[MAXV], hv[MAXV], yv[RELU ? MAXV : 1], av[ADD ? MAXV : 1];  // masked gradient dz, xhat, y, dadd
     unsigned off[MAXV];
-    float sdz = 0.0f, sdzx = 0.0f;
-    // unconditional clamped loads first (all in flight together), masking second - see bn_fwd_cached_kernel
-    float4 yv[RELU ? MAXV : 1];
-#pragma unroll
-    for (int j = 0; j < MAXV; ++j) {
-        const int e0 = threadIdx.x + j * NT;
-        const int e = e0 < total ? e0 : total - 1;
-        const int b = e / per, q = e - b * per;
-        off[j] = static_cast<unsigned>(b * s.C + c) * static_cast<unsigned>(per) + static_cast<unsigned>(q);
+    load_channel<NT, MAXV>(s, c, off, [&](int j) {
         gv[j] = dy4[off[j]];
         hv[j] = x4[off[j]];
         if (RELU && y4) yv[j] = y4[off[j]];
-    }
-    float4 av[ADD ? MAXV : 1];
-    if (ADD) {  // slots of other parts: a load of this part's first slot (see bn_fwd_cached_kernel's residual)
-        const float4 *da4 = reinterpret_cast<const float4 *>(dadd);
-        const int jf = (part * MAXV + P - 1) / P;
-        unsigned of = off[0];
-#pragma unroll
-        for (int j = 1; j < MAXV; ++j) of = j == jf ? off[j] : of;
-#pragma unroll
-        for (int j = 0; j < MAXV; ++j) av[j] = da4[(j * P / MAXV == part) ? off[j] : of];
-    }
+    });
+    if constexpr (ADD) load_own_slots(reinterpret_cast<const float4 *>(dadd), off, P, part, av);
     const MaskArgs mk = mask_args(y, gamma, beta, invstd, c);
     if (dy24) {
 #pragma unroll
         for (int j = 0; j < MAXV; ++j) gv[j] = add4(gv[j], dy24[off[j]]);
     }
+    float sdz = 0.0f, sdzx = 0.0f;
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {
-        const bool in = static_cast<int>(threadIdx.x) + j * NT < total;
         float4 g = gv[j];
         const float4 v = hv[j];
-        if (RELU) {
-            const float4 yy = mk.on ? pre4(v, mean, mk) : yv[j];
-            g.x = yy.x > 0.0f ? g.x : 0.0f;
-            g.y = yy.y > 0.0f ? g.y : 0.0f;
-            g.z = yy.z > 0.0f ? g.z : 0.0f;
-            g.w = yy.w > 0.0f ? g.w : 0.0f;
-        }
-        float4 h = make_float4((v.x - mean) * invstd, (v.y - mean) * invstd, (v.z - mean) * invstd, (v.w - mean) * invstd);
-        if (!in) g = h = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        sdz += (g.x + g.y) + (g.z + g.w);
-        sdzx += (g.x * h.x + g.y * h.y) + (g.z * h.z + g.w * h.w);
+        if (RELU) g = mask4(g, mk.on ? bn_affine4(v, mean, mk.a, mk.b0) : yv[j]);
+        float4 h = bn_xhat4(v, mean, invstd);
+        if (!slot_valid<NT>(j, total)) g = h = zero4();
+        sdz += quad_sum(g);
+        sdzx += quad_dot(g, h);
         gv[j] = g;
         hv[j] = h;
     }
-    {
-        float two[2] = {sdz, sdzx};
-        block_sums<NT, 2>(two, scratch);
-        sdz = two[0], sdzx = two[1];
-    }
-    if (threadIdx.x == 0 && part == 0) {
-        if (dgamma) dgamma[c] = sdzx;
-        if (dbeta) dbeta[c] = sdz;
-    }
-    const float w = (gamma ? gamma[c] : 1.0f) * invstd;
+    block_sum_pair<NT>(sdz, sdzx, scratch);
+    if (threadIdx.x == 0 && part == 0) put_param_grads(dgamma, dbeta, c, sdz, sdzx);
+    const float w = bn_gain(invstd, gamma, c);
     const float m1 = training ? sdz / n : 0.0f, m2 = training ? sdzx / n : 0.0f;
     float4 *dx4 = reinterpret_cast<float4 *>(dx), *dr4 = reinterpret_cast<float4 *>(dres);
 #pragma unroll
     for (int j = 0; j < MAXV; ++j)
-        if (static_cast<int>(threadIdx.x) + j * NT < total && j * P / MAXV == part) {
-            const float4 g = gv[j], h = hv[j];
-            if (dres) dr4[off[j]] = g;
+        if (slot_valid<NT>(j, total) && owns_slot<MAXV>(j, P, part)) {
+            if (dres) dr4[off[j]] = gv[j];
             if (dx) {
-                float4 d = make_float4(w * ((g.x - m1) - h.x * m2), w * ((g.y - m1) - h.y * m2), w * ((g.z - m1) - h.z * m2), w * ((g.w - m1) - h.w * m2));
+                float4 d = bn_dx4(w, gv[j], m1, hv[j], m2);
                 if (ADD) d = add4(d, av[j]);
                 dx4[off[j]] = d;
             }
@@ -443,44 +388,6 @@ __global__ __launch_bounds__(NT) void bn_bwd_cached_kernel(const float *__restri
 // :137-142).  Both are per-channel, so one workgroup does both for its channel - one launch each way instead of two (at these sizes
 // a BatchNorm launch is 5-6 us of launch floor).  Same statistics, same expressions, same order as bn_fwd/bwd_cached_kernel run one
 // after the other: bit-identical results. ---------------------------------------------------------------------------------------------
-struct BnParams {
-    const float *gamma, *beta;
-    float *running_mean, *running_var;
-    float momentum, eps;
-    float *save_mean, *save_invstd;
-};
-
-template <int NT, int MAXV>
-__device__ __forceinline__ void cached_stats(const float4 (&xv)[MAXV], int total, float n, const BnParams &p, int training, int c, float *scratch,
-                                             float &mean, float &invstd) {
-    if (training) {
-        float acc = 0.0f;
-#pragma unroll
-        for (int j = 0; j < MAXV; ++j) acc += (xv[j].x + xv[j].y) + (xv[j].z + xv[j].w);  // lanes past the end hold zeros
-        mean = block_sum<NT>(acc, scratch) / n;
-        float var = 0.0f;
-#pragma unroll
-        for (int j = 0; j < MAXV; ++j)
-            if (static_cast<int>(threadIdx.x) + j * NT < total) {
-                const float a = xv[j].x - mean, b = xv[j].y - mean, cc = xv[j].z - mean, d = xv[j].w - mean;
-                var += (a * a + b * b) + (cc * cc + d * d);
-            }
-        var = block_sum<NT>(var, scratch) / n;
-        invstd = 1.0f / sqrtf(var + p.eps);
-        if (threadIdx.x == 0) {
-            p.save_mean[c] = mean;
-            p.save_invstd[c] = invstd;
-            if (p.running_mean) {
-                const float unbiased = (n > 1.0f) ? var * (n / (n - 1.0f)) : var;
-                p.running_mean[c] = (1.0f - p.momentum) * p.running_mean[c] + p.momentum * mean;
-                p.running_var[c] = (1.0f - p.momentum) * p.running_var[c] + p.momentum * unbiased;
-            }
-        }
-    } else {
-        mean = p.running_mean[c];
-        invstd = 1.0f / sqrtf(p.running_var[c] + p.eps);
-    }
-}
 
 // y = relu( bn_a(xa) + bn_b(xb) ): bn_b first (it is the `residual` of the unfused call), then bn_a with the residual added
 template <int NT, int MAXV>
@@ -488,38 +395,24 @@ __global__ __launch_bounds__(NT) void bn_dual_fwd_cached_kernel(const float *__r
                                                                 int training, float *__restrict__ y, BnShape s) {
     __shared__ float scratch[3 * (NT / 64)];
     const int c = blockIdx.x;
-    const int per = s.HW / 4, total = s.B * per;
+    const int total = s.B * (s.HW / 4);
     const float n = static_cast<float>(s.B) * static_cast<float>(s.HW);
     const float4 *a4 = reinterpret_cast<const float4 *>(xa), *b4 = reinterpret_cast<const float4 *>(xb);
     float4 av[MAXV], bv[MAXV];
     unsigned off[MAXV];
-#pragma unroll
-    for (int j = 0; j < MAXV; ++j) {
-        const int e0 = threadIdx.x + j * NT;
-        const int e = e0 < total ? e0 : total - 1;
-        const int b = e / per, q = e - b * per;
-        off[j] = static_cast<unsigned>(b * s.C + c) * static_cast<unsigned>(per) + static_cast<unsigned>(q);
-        av[j] = a4[off[j]];
-        bv[j] = b4[off[j]];
-    }
+    load_channel<NT, MAXV>(s, c, off, [&](int j) { av[j] = a4[off[j]], bv[j] = b4[off[j]]; });
 #pragma unroll
     for (int j = 0; j < MAXV; ++j)
-        if (static_cast<int>(threadIdx.x) + j * NT >= total) av[j] = bv[j] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (!slot_valid<NT>(j, total)) av[j] = bv[j] = zero4();
     float mean_b, inv_b, mean_a, inv_a;
-    cached_stats<NT, MAXV>(bv, total, n, pb, training, c, scratch, mean_b, inv_b);
-    cached_stats<NT, MAXV>(av, total, n, pa, training, c, scratch, mean_a, inv_a);
-    const float sb = inv_b * (pb.gamma ? pb.gamma[c] : 1.0f), tb = pb.beta ? pb.beta[c] : 0.0f;
-    const float sa = inv_a * (pa.gamma ? pa.gamma[c] : 1.0f), ta = pa.beta ? pa.beta[c] : 0.0f;
+    cached_stats<NT, MAXV>(bv, total, n, pb, training, c, scratch, true, mean_b, inv_b);
+    cached_stats<NT, MAXV>(av, total, n, pa, training, c, scratch, true, mean_a, inv_a);
+    const float sb = bn_gain(inv_b, pb.gamma, c), tb = bn_shift(pb.beta, c);
+    const float sa = bn_gain(inv_a, pa.gamma, c), ta = bn_shift(pa.beta, c);
     float4 *y4 = reinterpret_cast<float4 *>(y);
 #pragma unroll
     for (int j = 0; j < MAXV; ++j)
-        if (static_cast<int>(threadIdx.x) + j * NT < total) {
-            const float4 u = bv[j], v = av[j];
-            const float4 q = make_float4((u.x - mean_b) * sb + tb, (u.y - mean_b) * sb + tb, (u.z - mean_b) * sb + tb, (u.w - mean_b) * sb + tb);
-            float4 r = make_float4((v.x - mean_a) * sa + ta, (v.y - mean_a) * sa + ta, (v.z - mean_a) * sa + ta, (v.w - mean_a) * sa + ta);
-            r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-            y4[off[j]] = make_float4(relu_nan(r.x), relu_nan(r.y), relu_nan(r.z), relu_nan(r.w));
-        }
+        if (slot_valid<NT>(j, total)) y4[off[j]] = bn_out4<true, true>(av[j], bn_affine4(bv[j], mean_b, sb, tb), mean_a, sa, ta);
 }
 
 // dz = (y > 0) * (dy + dy2); bn_a's backward on dz -> dxa, then bn_b's (no ReLU of its own) on the same dz -> dxb
@@ -531,26 +424,20 @@ __global__ __launch_bounds__(NT) void bn_dual_bwd_cached_kernel(const float *__r
                                                                 float *__restrict__ dgamma_b, float *__restrict__ dbeta_b, BnShape s) {
     __shared__ float scratch[3 * (NT / 64)];
     const int c = blockIdx.x;
-    const int per = s.HW / 4, total = s.B * per;
+    const int total = s.B * (s.HW / 4);
     const float n = static_cast<float>(s.B) * static_cast<float>(s.HW);
-    const float mean_a = training ? pa.save_mean[c] : pa.running_mean[c], mean_b = training ? pb.save_mean[c] : pb.running_mean[c];
-    const float inv_a = training ? pa.save_invstd[c] : 1.0f / sqrtf(pa.running_var[c] + pa.eps);
-    const float inv_b = training ? pb.save_invstd[c] : 1.0f / sqrtf(pb.running_var[c] + pb.eps);
+    const BnStats a = bn_known_stats(training, pa.save_mean, pa.save_invstd, pa.running_mean, pa.running_var, pa.eps, c);
+    const BnStats b = bn_known_stats(training, pb.save_mean, pb.save_invstd, pb.running_mean, pb.running_var, pb.eps, c);
     const float4 *dy4 = reinterpret_cast<const float4 *>(dy), *dy24 = reinterpret_cast<const float4 *>(dy2), *y4 = reinterpret_cast<const float4 *>(y);
     const float4 *a4 = reinterpret_cast<const float4 *>(xa), *b4 = reinterpret_cast<const float4 *>(xb);
     float4 gv[MAXV], ha[MAXV], hb[MAXV], yv[MAXV];
     unsigned off[MAXV];
-#pragma unroll
-    for (int j = 0; j < MAXV; ++j) {
-        const int e0 = threadIdx.x + j * NT;
-        const int e = e0 < total ? e0 : total - 1;
-        const int b = e / per, q = e - b * per;
-        off[j] = static_cast<unsigned>(b * s.C + c) * static_cast<unsigned>(per) + static_cast<unsigned>(q);
+    load_channel<NT, MAXV>(s, c, off, [&](int j) {
         gv[j] = dy4[off[j]];
         ha[j] = a4[off[j]];
         hb[j] = b4[off[j]];
         yv[j] = y4[off[j]];
-    }
+    });
     if (dy24) {
 #pragma unroll
         for (int j = 0; j < MAXV; ++j) gv[j] = add4(gv[j], dy24[off[j]]);
@@ -558,20 +445,12 @@ __global__ __launch_bounds__(NT) void bn_dual_bwd_cached_kernel(const float *__r
     float sdz = 0.0f, sa = 0.0f, sb = 0.0f;
 #pragma unroll
     for (int j = 0; j < MAXV; ++j) {
-        const bool in = static_cast<int>(threadIdx.x) + j * NT < total;
-        float4 g = gv[j];
-        const float4 yy = yv[j];
-        g.x = yy.x > 0.0f ? g.x : 0.0f;
-        g.y = yy.y > 0.0f ? g.y : 0.0f;
-        g.z = yy.z > 0.0f ? g.z : 0.0f;
-        g.w = yy.w > 0.0f ? g.w : 0.0f;
-        const float4 va = ha[j], vb = hb[j];
-        float4 xa_ = make_float4((va.x - mean_a) * inv_a, (va.y - mean_a) * inv_a, (va.z - mean_a) * inv_a, (va.w - mean_a) * inv_a);
-        float4 xb_ = make_float4((vb.x - mean_b) * inv_b, (vb.y - mean_b) * inv_b, (vb.z - mean_b) * inv_b, (vb.w - mean_b) * inv_b);
-        if (!in) g = xa_ = xb_ = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        sdz += (g.x + g.y) + (g.z + g.w);
-        sa += (g.x * xa_.x + g.y * xa_.y) + (g.z * xa_.z + g.w * xa_.w);
-        sb += (g.x * xb_.x + g.y * xb_.y) + (g.z * xb_.z + g.w * xb_.w);
+        float4 g = mask4(gv[j], yv[j]);
+        float4 xa_ = bn_xhat4(ha[j], a.mean, a.invstd), xb_ = bn_xhat4(hb[j], b.mean, b.invstd);
+        if (!slot_valid<NT>(j, total)) g = xa_ = xb_ = zero4();
+        sdz += quad_sum(g);
+        sa += quad_dot(g, xa_);
+        sb += quad_dot(g, xb_);
         gv[j] = g;
         ha[j] = xa_;
         hb[j] = xb_;
@@ -582,20 +461,17 @@ __global__ __launch_bounds__(NT) void bn_dual_bwd_cached_kernel(const float *__r
         sdz = three[0], sa = three[1], sb = three[2];
     }
     if (threadIdx.x == 0) {
-        if (dgamma_a) dgamma_a[c] = sa;
-        if (dbeta_a) dbeta_a[c] = sdz;
-        if (dgamma_b) dgamma_b[c] = sb;
-        if (dbeta_b) dbeta_b[c] = sdz;
+        put_param_grads(dgamma_a, dbeta_a, c, sdz, sa);
+        put_param_grads(dgamma_b, dbeta_b, c, sdz, sb);
     }
-    const float wa = (pa.gamma ? pa.gamma[c] : 1.0f) * inv_a, wb = (pb.gamma ? pb.gamma[c] : 1.0f) * inv_b;
+    const float wa = bn_gain(a.invstd, pa.gamma, c), wb = bn_gain(b.invstd, pb.gamma, c);
     const float m1 = training ? sdz / n : 0.0f, ma = training ? sa / n : 0.0f, mb = training ? sb / n : 0.0f;
     float4 *da4 = reinterpret_cast<float4 *>(dxa), *db4 = reinterpret_cast<float4 *>(dxb);
 #pragma unroll
     for (int j = 0; j < MAXV; ++j)
-        if (static_cast<int>(threadIdx.x) + j * NT < total) {
-            const float4 g = gv[j], p = ha[j], q = hb[j];
-            if (dxa) da4[off[j]] = make_float4(wa * ((g.x - m1) - p.x * ma), wa * ((g.y - m1) - p.y * ma), wa * ((g.z - m1) - p.z * ma), wa * ((g.w - m1) - p.w * ma));
-            if (dxb) db4[off[j]] = make_float4(wb * ((g.x - m1) - q.x * mb), wb * ((g.y - m1) - q.y * mb), wb * ((g.z - m1) - q.z * mb), wb * ((g.w - m1) - q.w * mb));
+        if (slot_valid<NT>(j, total)) {
+            if (dxa) da4[off[j]] = bn_dx4(wa, gv[j], m1, ha[j], ma);
+            if (dxb) db4[off[j]] = bn_dx4(wb, gv[j], m1, hb[j], mb);
         }
 }
 
@@ -610,57 +486,6 @@ inline int cached_parts(int C, int maxv) {
     return p < 1 ? 1 : p;
 }
 
-template <int NT, int MAXV>
-void launch_fwd_cached(bool relu, bool has_res, hipStream_t st, const float *x, const float *res, const float *gamma, const float *beta, float *rm,
-                       float *rv, float momentum, float eps, int training, float *y, float *sm, float *si, BnShape s) {
-    const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
-    if (relu && has_res)
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, true, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, nullptr);
-    else if (relu)
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, true, false>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, nullptr);
-    else if (has_res)
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, false, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, nullptr);
-    else
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, false, false>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, nullptr);
-}
-
-template <int NT, int MAXV>
-void launch_bwd_cached(bool relu, hipStream_t st, const float *dy, const float *dy2, const float *y, const float *x, const float *beta, const float *gamma, const float *sm,
-                       const float *si, const float *rm, const float *rv, float eps, int training, float *dx, float *dres, float *dgamma,
-                       float *dbeta, BnShape s) {
-    const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
-    if (relu)
-        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, dres, dgamma, dbeta, s, nullptr);
-    else
-        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, dres, dgamma, dbeta, s, nullptr);
-}
-
-template <int NT, int MAXV>
-void launch_sum_fwd_cached(bool relu, hipStream_t st, const float *x, const float *res, const float *gamma, const float *beta, float *rm, float *rv,
-                           float momentum, float eps, int training, float *sum_out, float *y, float *sm, float *si, BnShape s) {
-    const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
-    if (relu)
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, true, false, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, sum_out);
-    else
-        EE_LAUNCH((bn_fwd_cached_kernel<NT, MAXV, false, false, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s, sum_out);
-}
-
-template <int NT, int MAXV>
-void launch_sum_bwd_cached(bool relu, hipStream_t st, const float *dy, const float *dy2, const float *y, const float *x, const float *beta, const float *gamma,
-                           const float *sm, const float *si, const float *rm, const float *rv, float eps, int training, const float *dadd, float *dx,
-                           float *dgamma, float *dbeta, BnShape s) {
-    const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
-    float *const none = nullptr;
-    if (relu && dadd)
-        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, true, true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, none, dgamma, dbeta, s, dadd);
-    else if (relu)
-        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, true, false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, none, dgamma, dbeta, s, dadd);
-    else if (dadd)
-        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, false, true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, none, dgamma, dbeta, s, dadd);
-    else
-        EE_LAUNCH((bn_bwd_cached_kernel<NT, MAXV, false, false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, none, dgamma, dbeta, s, dadd);
-}
-
 // which cached variant holds a channel of `quads` float4s: 0 = none
 inline int cached_variant(int64_t quads, int64_t numel) {
     if (numel / 4 > 0xffffffffLL) return 0;  // 32-bit float4 offsets
@@ -668,6 +493,79 @@ inline int cached_variant(int64_t quads, int64_t numel) {
     if (quads <= 7 * 256) return 2;          // <256, 7>
     if (quads <= 7 * 1024) return 3;         // <1024, 7>
     return 0;
+}
+
+// ---- host side: from run-time flags to template arguments ------------------------------------------------------------------------------
+// dispatch(flag, f) calls f(std::true_type{}) or f(std::false_type{}); with two flags, f(A, B)
+template <class F>
+void dispatch(bool a, F f) {
+    if (a) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+void dispatch(bool a, bool b, F f) {
+    dispatch(a, [&](auto A) { dispatch(b, [&](auto B) { f(A, B); }); });
+}
+
+// cached_variant's number as the cached kernels' <NT, MAXV>: f(CachedCfg<NT, MAXV>{}); false: cv names no cached variant
+template <int NT_, int MAXV_>
+struct CachedCfg {
+    static constexpr int NT = NT_, MAXV = MAXV_;
+};
+template <class F>
+bool with_cached_cfg(int cv, F f) {
+    if (cv == 1) f(CachedCfg<256, 2>{});
+    else if (cv == 2) f(CachedCfg<256, 7>{});
+    else if (cv == 3) f(CachedCfg<1024, 7>{});
+    else return false;
+    return true;
+}
+
+// the arguments that the generic, cached and split kernels of a direction share, in the kernels' order; `tail`: what follows them
+struct FwdArgs {
+    const float *x, *res, *gamma, *beta;
+    float *running_mean, *running_var;
+    float momentum, eps;
+    int training;
+    float *y, *save_mean, *save_invstd;
+};
+struct BwdArgs {
+    const float *dy, *dy2, *y, *x, *beta, *gamma, *save_mean, *save_invstd, *running_mean, *running_var;
+    float eps;
+    int training;
+    float *dx, *dres, *dgamma, *dbeta;
+};
+template <class K, class... Tail>
+void launch_fwd_args(K kernel, dim3 grid, dim3 block, hipStream_t st, const FwdArgs &a, Tail... tail) {
+    EE_LAUNCH(kernel, grid, block, 0, st, a.x, a.res, a.gamma, a.beta, a.running_mean, a.running_var, a.momentum, a.eps, a.training, a.y, a.save_mean,
+              a.save_invstd, tail...);
+}
+template <class K, class... Tail>
+void launch_bwd_args(K kernel, dim3 grid, dim3 block, hipStream_t st, const BwdArgs &a, Tail... tail) {
+    EE_LAUNCH(kernel, grid, block, 0, st, a.dy, a.dy2, a.y, a.x, a.beta, a.gamma, a.save_mean, a.save_invstd, a.running_mean, a.running_var, a.eps,
+              a.training, a.dx, a.dres, a.dgamma, a.dbeta, tail...);
+}
+
+// sum_out: the SUM form (ee_bn_sum_act_fwd_f32: a.res is added BEFORE the statistics; never together with RES); `sum` says so, as
+// sum_out itself may be null
+template <int NT, int MAXV>
+void launch_fwd_cached(bool relu, bool sum, hipStream_t st, const FwdArgs &a, BnShape s, float *sum_out) {
+    const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
+    if (sum)
+        dispatch(relu, [&](auto R) { launch_fwd_args(bn_fwd_cached_kernel<NT, MAXV, decltype(R)::value, false, true>, grid, block, st, a, s, sum_out); });
+    else
+        dispatch(relu, a.res != nullptr, [&](auto R, auto Q) {
+            launch_fwd_args(bn_fwd_cached_kernel<NT, MAXV, decltype(R)::value, decltype(Q)::value>, grid, block, st, a, s, sum_out);
+        });
+}
+
+// dadd: ee_bn_sum_act_bwd_f32's gradient from the identity branch, or null
+template <int NT, int MAXV>
+void launch_bwd_cached(bool relu, hipStream_t st, const BwdArgs &a, BnShape s, const float *dadd) {
+    const dim3 grid(static_cast<unsigned>(s.C), static_cast<unsigned>(cached_parts(s.C, MAXV))), block(NT);
+    dispatch(relu, dadd != nullptr, [&](auto R, auto A) {
+        launch_bwd_args(bn_bwd_cached_kernel<NT, MAXV, decltype(R)::value, decltype(A)::value>, grid, block, st, a, s, dadd);
+    });
 }
 
 
@@ -716,26 +614,47 @@ __device__ __forceinline__ void for_slice(const BnShape s, int c, Slice sl, L lo
     }
 }
 
-// Chan's recombination of the S per-slice (sum, M2) partials of bn_split_stats_kernel, in slice order (as bn_split_apply_kernel).
-// The partials come through LDS in ONE parallel load: a loop of dependent global loads (S up to 64) cost 10 us per workgroup.
-__device__ __forceinline__ void combine_slices(const float *__restrict__ ws, int c, int S, int total, float n, float *sh, float &mean, float &var) {
-    for (int i = threadIdx.x; i < 2 * S; i += SPLIT_NT) sh[i] = ws[static_cast<size_t>(c) * S * 2 + i];
-    __syncthreads();
+// Chan's recombination of the S per-slice partials p[2 i + {0, 1}] = (sum, M2 about the slice's own mean) of bn_split_stats_kernel, in
+// slice order: the channel's mean and M2.  The one routine behind every workgroup's statistics and SyncBatchNorm's per-rank moments.
+__device__ __forceinline__ void combine_moments(const float *p, int S, int total, float n, float &mean, float &m2) {
     float sum = 0.0f;
 #pragma unroll 4
-    for (int i = 0; i < S; ++i) sum += sh[2 * i];
+    for (int i = 0; i < S; ++i) sum += p[2 * i];
     mean = sum / n;
-    float m2 = 0.0f;
+    m2 = 0.0f;
 #pragma unroll 4
     for (int i = 0; i < S; ++i) {
         const Slice sl = my_slice(total, S, i);
         const float cnt = 4.0f * static_cast<float>(sl.end - sl.begin);
         if (cnt > 0.0f) {
-            const float d = sh[2 * i] / cnt - mean;
-            m2 += sh[2 * i + 1] + cnt * (d * d);
+            const float d = p[2 * i] / cnt - mean;
+            m2 += p[2 * i + 1] + cnt * (d * d);
         }
     }
+}
+
+// channel c's S pairs of a [C][S][2] workspace through LDS in ONE parallel load: a loop of dependent global loads (S up to 64) cost
+// 10 us per workgroup
+__device__ __forceinline__ void stage_partials(const float *__restrict__ ws, int c, int S, float *sh) {
+    for (int i = threadIdx.x; i < 2 * S; i += SPLIT_NT) sh[i] = ws[static_cast<size_t>(c) * S * 2 + i];
+    __syncthreads();
+}
+// every lane recombines the S partials itself, in slice order: identical in all workgroups
+__device__ __forceinline__ void combine_slices(const float *__restrict__ ws, int c, int S, int total, float n, float *sh, float &mean, float &var) {
+    stage_partials(ws, c, S, sh);
+    float m2;
+    combine_moments(sh, S, total, n, mean, m2);
     var = m2 / n;
+}
+// the backward's partials (sum dz, sum dz * xhat), summed by every lane in index order
+__device__ __forceinline__ void sum_partials(const float *__restrict__ ws, int c, int S, float *sh, float &sdz, float &sdzx) {
+    stage_partials(ws, c, S, sh);
+    sdz = 0.0f, sdzx = 0.0f;
+#pragma unroll 4
+    for (int i = 0; i < S; ++i) {
+        sdz += sh[2 * i];
+        sdzx += sh[2 * i + 1];
+    }
 }
 
 // ws[(c*S + s)*2 + {0,1}] = (sum, M2 about the slice's own mean)
@@ -745,20 +664,30 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_split_stats_kernel(const float *_
     const Slice sl = my_slice(s.B * (s.HW / 4), S, sl_i);
     const float4 *x4 = reinterpret_cast<const float4 *>(x);
     float acc = 0.0f;
-    for_slice(s, c, sl, [&](size_t o) { return x4[o]; }, [&](float4 v, size_t) { acc += (v.x + v.y) + (v.z + v.w); });
+    for_slice(s, c, sl, [&](size_t o) { return x4[o]; }, [&](float4 v, size_t) { acc += quad_sum(v); });
     const float sum = block_sum<SPLIT_NT>(acc, scratch);
     const float cnt = 4.0f * static_cast<float>(sl.end - sl.begin);
     const float mean = cnt > 0.0f ? sum / cnt : 0.0f;
     float m2 = 0.0f;
-    for_slice(s, c, sl, [&](size_t o) { return x4[o]; }, [&](float4 v, size_t) {
-        const float a = v.x - mean, b = v.y - mean, cc = v.z - mean, d = v.w - mean;
-        m2 += (a * a + b * b) + (cc * cc + d * d);
-    });
+    for_slice(s, c, sl, [&](size_t o) { return x4[o]; }, [&](float4 v, size_t) { m2 += quad_sqdev(v, mean); });
     m2 = block_sum<SPLIT_NT>(m2, scratch);
     if (threadIdx.x == 0) {
         ws[(static_cast<size_t>(c) * S + sl_i) * 2 + 0] = sum;
         ws[(static_cast<size_t>(c) * S + sl_i) * 2 + 1] = m2;
     }
+}
+
+// the forward over one slice, once the channel's statistics are known (bn_split_apply_kernel, bn_sync_apply_kernel)
+template <bool RELU, bool RES>
+__device__ __forceinline__ void slice_fwd_apply(const float *__restrict__ x, const float *__restrict__ res, float *__restrict__ y, BnShape s, int c,
+                                                Slice sl, float mean, float a, float b0) {
+    const float4 *x4 = reinterpret_cast<const float4 *>(x), *r4 = reinterpret_cast<const float4 *>(res);
+    float4 *y4 = reinterpret_cast<float4 *>(y);
+    struct XR {
+        float4 x, r;
+    };
+    for_slice(s, c, sl, [&](size_t o) { return XR{x4[o], RES ? r4[o] : zero4()}; },
+              [&](XR in, size_t o) { y4[o] = bn_out4<RELU, RES>(in.x, in.r, mean, a, b0); });
 }
 
 template <bool RELU, bool RES>
@@ -771,43 +700,17 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_split_apply_kernel(const float *_
     const int total = s.B * (s.HW / 4);
     const float n = static_cast<float>(s.B) * static_cast<float>(s.HW);
     float mean, invstd;
-    if (training) {  // every lane recombines the S partials itself, in slice order: identical in all workgroups
+    if (training) {
         __shared__ float parts[2 * SPLIT_MAX];
         float var;
         combine_slices(ws, c, S, total, n, parts, mean, var);
-        invstd = 1.0f / sqrtf(var + eps);
-        if (sl_i == 0 && threadIdx.x == 0) {
-            save_mean[c] = mean;
-            save_invstd[c] = invstd;
-            if (running_mean) {
-                const float unbiased = (n > 1.0f) ? var * (n / (n - 1.0f)) : var;
-                running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mean;
-                running_var[c] = (1.0f - momentum) * running_var[c] + momentum * unbiased;
-            }
-        }
+        invstd = bn_invstd(var, eps);
+        if (sl_i == 0 && threadIdx.x == 0) bn_commit_stats(c, mean, var, invstd, n, momentum, save_mean, save_invstd, running_mean, running_var);
     } else {
-        mean = running_mean[c];
-        invstd = 1.0f / sqrtf(running_var[c] + eps);
+        const BnStats st = bn_known_stats(0, save_mean, save_invstd, running_mean, running_var, eps, c);
+        mean = st.mean, invstd = st.invstd;
     }
-    const float a = invstd * (gamma ? gamma[c] : 1.0f), b0 = beta ? beta[c] : 0.0f;
-    const float4 *x4 = reinterpret_cast<const float4 *>(x), *r4 = reinterpret_cast<const float4 *>(res);
-    float4 *y4 = reinterpret_cast<float4 *>(y);
-    struct XR {
-        float4 x, r;
-    };
-    for_slice(s, c, my_slice(total, S, sl_i), [&](size_t o) { return XR{x4[o], RES ? r4[o] : make_float4(0.0f, 0.0f, 0.0f, 0.0f)}; },
-              [&](XR in, size_t o) {
-        const float4 v = in.x;
-        float4 r = make_float4((v.x - mean) * a + b0, (v.y - mean) * a + b0, (v.z - mean) * a + b0, (v.w - mean) * a + b0);
-        if (RES) {
-            const float4 q = in.r;
-            r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-        }
-        if (RELU) {
-            r.x = relu_nan(r.x); r.y = relu_nan(r.y); r.z = relu_nan(r.z); r.w = relu_nan(r.w);
-        }
-        y4[o] = r;
-    });
+    slice_fwd_apply<RELU, RES>(x, res, y, s, c, my_slice(total, S, sl_i), mean, bn_gain(invstd, gamma, c), bn_shift(beta, c));
 }
 
 struct BwdIn {
@@ -815,20 +718,10 @@ struct BwdIn {
 };
 __device__ __forceinline__ BwdIn bwd_load(const float4 *dy4, const float4 *dy24, const float4 *y4, const float4 *x4, size_t o, bool relu, bool want_x,
                                           float mean, const MaskArgs &mk) {
-    const float4 z = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    const float4 xv = (want_x || (relu && mk.on)) ? x4[o] : z;
-    return BwdIn{dy24 ? add4(dy4[o], dy24[o]) : dy4[o], relu ? (mk.on ? pre4(xv, mean, mk) : y4[o]) : z, xv};
+    const float4 xv = (want_x || (relu && mk.on)) ? x4[o] : zero4();
+    return BwdIn{dy24 ? add4(dy4[o], dy24[o]) : dy4[o], relu ? (mk.on ? bn_affine4(xv, mean, mk.a, mk.b0) : y4[o]) : zero4(), xv};
 }
-__device__ __forceinline__ float4 masked_dz(const BwdIn &in, bool relu) {
-    float4 g = in.dy;
-    if (relu) {
-        g.x = in.y.x > 0.0f ? g.x : 0.0f;
-        g.y = in.y.y > 0.0f ? g.y : 0.0f;
-        g.z = in.y.z > 0.0f ? g.z : 0.0f;
-        g.w = in.y.w > 0.0f ? g.w : 0.0f;
-    }
-    return g;
-}
+__device__ __forceinline__ float4 masked_dz(const BwdIn &in, bool relu) { return relu ? mask4(in.dy, in.y) : in.dy; }
 
 // ws[(c*S + s)*2 + {0,1}] = (sum dz, sum dz*xhat) of the slice
 template <bool RELU>
@@ -841,26 +734,39 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_split_bwd_partial_kernel(const fl
                                                                         float *__restrict__ ws, BnShape s, int S) {
     __shared__ float scratch[3 * (SPLIT_NT / 64)];
     const int c = blockIdx.x, sl_i = blockIdx.y;
-    const float mean = training ? save_mean[c] : running_mean[c];
-    const float invstd = training ? save_invstd[c] : 1.0f / sqrtf(running_var[c] + eps);
+    const BnStats st = bn_known_stats(training, save_mean, save_invstd, running_mean, running_var, eps, c);
+    const float mean = st.mean, invstd = st.invstd;
     const float4 *dy4 = reinterpret_cast<const float4 *>(dy), *y4 = reinterpret_cast<const float4 *>(y), *x4 = reinterpret_cast<const float4 *>(x);
     const MaskArgs mk = mask_args(y, gamma, beta, invstd, c);
     float sdz = 0.0f, sdzx = 0.0f;
     for_slice(s, c, my_slice(s.B * (s.HW / 4), S, sl_i), [&](size_t o) { return bwd_load(dy4, reinterpret_cast<const float4 *>(dy2), y4, x4, o, RELU, true, mean, mk); }, [&](BwdIn in, size_t) {
         const float4 g = masked_dz(in, RELU);
-        const float4 v = in.x;
-        sdz += (g.x + g.y) + (g.z + g.w);
-        sdzx += (g.x * ((v.x - mean) * invstd) + g.y * ((v.y - mean) * invstd)) + (g.z * ((v.z - mean) * invstd) + g.w * ((v.w - mean) * invstd));
+        sdz += quad_sum(g);
+        sdzx += quad_dot(g, bn_xhat4(in.x, mean, invstd));
     });
-    {
-        float two[2] = {sdz, sdzx};
-        block_sums<SPLIT_NT, 2>(two, scratch);
-        sdz = two[0], sdzx = two[1];
-    }
+    block_sum_pair<SPLIT_NT>(sdz, sdzx, scratch);
     if (threadIdx.x == 0) {
         ws[(static_cast<size_t>(c) * S + sl_i) * 2 + 0] = sdz;
         ws[(static_cast<size_t>(c) * S + sl_i) * 2 + 1] = sdzx;
     }
+}
+
+// the backward over one slice, once m1 = mean(dz) and m2 = mean(dz * xhat) are known (bn_split_bwd_apply_kernel, bn_sync_bwd_apply_kernel)
+template <bool RELU>
+__device__ __forceinline__ void slice_bwd_apply(const float *__restrict__ dy, const float *__restrict__ dy2, const float *__restrict__ y,
+                                                const float *__restrict__ x, const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                float *__restrict__ dx, float *__restrict__ dres, BnShape s, int c, Slice sl, float mean, float invstd,
+                                                float m1, float m2) {
+    const float w = bn_gain(invstd, gamma, c);
+    const float4 *dy4 = reinterpret_cast<const float4 *>(dy), *y4 = reinterpret_cast<const float4 *>(y), *x4 = reinterpret_cast<const float4 *>(x);
+    float4 *dx4 = reinterpret_cast<float4 *>(dx), *dr4 = reinterpret_cast<float4 *>(dres);
+    const bool want_x = dx != nullptr;
+    const MaskArgs mk = mask_args(y, gamma, beta, invstd, c);
+    for_slice(s, c, sl, [&](size_t o) { return bwd_load(dy4, reinterpret_cast<const float4 *>(dy2), y4, x4, o, RELU, want_x, mean, mk); }, [&](BwdIn in, size_t o) {
+        const float4 g = masked_dz(in, RELU);
+        if (dres) dr4[o] = g;
+        if (dx) dx4[o] = bn_dx4(w, g, m1, bn_xhat4(in.x, mean, invstd), m2);
+    });
 }
 
 template <bool RELU>
@@ -873,37 +779,14 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_split_bwd_apply_kernel(const floa
                                                                       float *__restrict__ dbeta, const float *__restrict__ ws, BnShape s, int S) {
     const int c = blockIdx.x, sl_i = blockIdx.y;
     const float n = static_cast<float>(s.B) * static_cast<float>(s.HW);
-    const float mean = training ? save_mean[c] : running_mean[c];
-    const float invstd = training ? save_invstd[c] : 1.0f / sqrtf(running_var[c] + eps);
+    const BnStats st = bn_known_stats(training, save_mean, save_invstd, running_mean, running_var, eps, c);
     __shared__ float parts[2 * SPLIT_MAX];
-    for (int i = threadIdx.x; i < 2 * S; i += SPLIT_NT) parts[i] = ws[static_cast<size_t>(c) * S * 2 + i];
-    __syncthreads();
-    float sdz = 0.0f, sdzx = 0.0f;
-#pragma unroll 4
-    for (int i = 0; i < S; ++i) {
-        sdz += parts[2 * i];
-        sdzx += parts[2 * i + 1];
-    }
-    if (sl_i == 0 && threadIdx.x == 0) {
-        if (dgamma) dgamma[c] = sdzx;
-        if (dbeta) dbeta[c] = sdz;
-    }
+    float sdz, sdzx;
+    sum_partials(ws, c, S, parts, sdz, sdzx);
+    if (sl_i == 0 && threadIdx.x == 0) put_param_grads(dgamma, dbeta, c, sdz, sdzx);
     if (!dx && !dres) return;
-    const float w = (gamma ? gamma[c] : 1.0f) * invstd;
-    const float m1 = training ? sdz / n : 0.0f, m2 = training ? sdzx / n : 0.0f;
-    const float4 *dy4 = reinterpret_cast<const float4 *>(dy), *y4 = reinterpret_cast<const float4 *>(y), *x4 = reinterpret_cast<const float4 *>(x);
-    float4 *dx4 = reinterpret_cast<float4 *>(dx), *dr4 = reinterpret_cast<float4 *>(dres);
-    const bool want_x = dx != nullptr;
-    const MaskArgs mk = mask_args(y, gamma, beta, invstd, c);
-    for_slice(s, c, my_slice(s.B * (s.HW / 4), S, sl_i), [&](size_t o) { return bwd_load(dy4, reinterpret_cast<const float4 *>(dy2), y4, x4, o, RELU, want_x, mean, mk); }, [&](BwdIn in, size_t o) {
-        const float4 g = masked_dz(in, RELU);
-        if (dres) dr4[o] = g;
-        if (dx) {
-            const float4 v = in.x;
-            dx4[o] = make_float4(w * ((g.x - m1) - ((v.x - mean) * invstd) * m2), w * ((g.y - m1) - ((v.y - mean) * invstd) * m2),
-                                 w * ((g.z - m1) - ((v.z - mean) * invstd) * m2), w * ((g.w - m1) - ((v.w - mean) * invstd) * m2));
-        }
-    });
+    slice_bwd_apply<RELU>(dy, dy2, y, x, gamma, beta, dx, dres, s, c, my_slice(s.B * (s.HW / 4), S, sl_i), st.mean, st.invstd,
+                          training ? sdz / n : 0.0f, training ? sdzx / n : 0.0f);
 }
 
 // ---- the stem: relu(bn(x)) followed by MaxPool2d(3, 2, 1) (resnet.py:113-117) without the full-resolution activation -----------------
@@ -956,13 +839,7 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_stats_finalize_kernel(const float
 #pragma unroll
         for (int w = 1; w < SPLIT_NT / 64; ++w) t = merge(t, sh[w]);
         const float var = t.n > 0.0f ? t.m2 / t.n : 0.0f;
-        save_mean[c] = t.mean;
-        save_invstd[c] = 1.0f / sqrtf(var + eps);
-        if (running_mean) {
-            const float unbiased = (t.n > 1.0f) ? var * (t.n / (t.n - 1.0f)) : var;
-            running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * t.mean;
-            running_var[c] = (1.0f - momentum) * running_var[c] + momentum * unbiased;
-        }
+        bn_commit_stats(c, t.mean, var, bn_invstd(var, eps), t.n, momentum, save_mean, save_invstd, running_mean, running_var);
     }
 }
 
@@ -1011,42 +888,24 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_pool_fwd_kernel(const float *__re
         __syncthreads();  // (the scratch of the first pair of sums is read)
         m2 = block_sum<SPLIT_NT>(m2, parts);
         const float var = cnt > 0.0f ? m2 / cnt : 0.0f;
-        invstd = 1.0f / sqrtf(var + eps);
-        if (g == 0 && threadIdx.x == 0) {
-            save_mean[c] = mean;
-            save_invstd[c] = invstd;
-            if (running_mean) {
-                const float unbiased = (cnt > 1.0f) ? var * (cnt / (cnt - 1.0f)) : var;
-                running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mean;
-                running_var[c] = (1.0f - momentum) * running_var[c] + momentum * unbiased;
-            }
-        }
+        invstd = bn_invstd(var, eps);
+        if (g == 0 && threadIdx.x == 0) bn_commit_stats(c, mean, var, invstd, cnt, momentum, save_mean, save_invstd, running_mean, running_var);
     } else if (training) {
         float var;
         combine_slices(ws, c, S, p.B * HWq, n, parts, mean, var);
-        invstd = 1.0f / sqrtf(var + eps);
-        if (g == 0 && threadIdx.x == 0) {
-            save_mean[c] = mean;
-            save_invstd[c] = invstd;
-            if (running_mean) {
-                const float unbiased = (n > 1.0f) ? var * (n / (n - 1.0f)) : var;
-                running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mean;
-                running_var[c] = (1.0f - momentum) * running_var[c] + momentum * unbiased;
-            }
-        }
+        invstd = bn_invstd(var, eps);
+        if (g == 0 && threadIdx.x == 0) bn_commit_stats(c, mean, var, invstd, n, momentum, save_mean, save_invstd, running_mean, running_var);
     } else {
-        mean = running_mean[c];
-        invstd = 1.0f / sqrtf(running_var[c] + eps);
+        const BnStats st = bn_known_stats(0, save_mean, save_invstd, running_mean, running_var, eps, c);
+        mean = st.mean, invstd = st.invstd;
     }
-    const float a = invstd * (gamma ? gamma[c] : 1.0f), b0 = beta ? beta[c] : 0.0f;
+    const float a = bn_gain(invstd, gamma, c), b0 = bn_shift(beta, c);
     const int b_end = (g + 1) * p.IPW < p.B ? (g + 1) * p.IPW : p.B;
     for (int b = g * p.IPW; b < b_end; ++b) {
         const size_t pl = static_cast<size_t>(b) * p.C + c;
         const float4 *x4 = reinterpret_cast<const float4 *>(x) + pl * HWq;
         for (int q = threadIdx.x; q < HWq; q += SPLIT_NT) {
-            const float4 v = x4[q];
-            reinterpret_cast<float4 *>(plane)[q] = make_float4(relu_nan((v.x - mean) * a + b0), relu_nan((v.y - mean) * a + b0),
-                                                               relu_nan((v.z - mean) * a + b0), relu_nan((v.w - mean) * a + b0));
+            reinterpret_cast<float4 *>(plane)[q] = relu_nan4(bn_affine4(x4[q], mean, a, b0));
         }
         __syncthreads();
         for (int o = threadIdx.x; o < OHW; o += SPLIT_NT) {
@@ -1085,7 +944,7 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_pool_bwd_sums_pooled_kernel(const
     const int c = blockIdx.x, g = blockIdx.y;
     const int OHW = p.OH * p.OW;
     const float mean = save_mean[c], invstd = save_invstd[c];
-    const float a = invstd * (gamma ? gamma[c] : 1.0f), b0 = beta ? beta[c] : 0.0f;
+    const float a = bn_gain(invstd, gamma, c), b0 = bn_shift(beta, c);
     const int b_end = (g + 1) * p.IPW < p.B ? (g + 1) * p.IPW : p.B;
     float sdz = 0.0f, sdzx = 0.0f;
     for (int b = g * p.IPW; b < b_end; ++b) {
@@ -1103,10 +962,9 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_pool_bwd_sums_pooled_kernel(const
             for (int u = 0; u < 4; ++u)
                 if (o0 + u * SPLIT_NT < OHW) {
                     const float gg = dyp2 ? gv[u] + g2[u] : gv[u];
-                    const float pre = (xv[u] - mean) * a + b0;
-                    const float dz = pre > 0.0f ? gg : 0.0f;
+                    const float dz = mask1(gg, bn_affine(xv[u], mean, a, b0));
                     sdz += dz;
-                    sdzx += dz * ((xv[u] - mean) * invstd);
+                    sdzx += dz * bn_xhat(xv[u], mean, invstd);
                 }
         }
     }
@@ -1133,24 +991,15 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_pool_bwd_kernel(const float *__re
     const int HW = p.H * p.W, HWq = HW / 4, OHW = p.OH * p.OW, Wq = p.W / 4;
     float *gp = lds;                                            // pooled gradient of one plane
     uint8_t *cd = reinterpret_cast<uint8_t *>(lds + OHW);       // its argmax codes
-    const float mean = training ? save_mean[c] : running_mean[c];
-    const float invstd = training ? save_invstd[c] : 1.0f / sqrtf(running_var[c] + eps);
-    const float a = invstd * (gamma ? gamma[c] : 1.0f), b0 = beta ? beta[c] : 0.0f;
+    const BnStats st = bn_known_stats(training, save_mean, save_invstd, running_mean, running_var, eps, c);
+    const float mean = st.mean, invstd = st.invstd;
+    const float a = bn_gain(invstd, gamma, c), b0 = bn_shift(beta, c);
     float m1 = 0.0f, m2 = 0.0f;
     if (APPLY && !p.nosums) {
-        __shared__ float parts[2 * SPLIT_MAX];  // the G partial sums, one parallel load (a loop of dependent global loads cost 8 us)
-        for (int i = threadIdx.x; i < 2 * p.G; i += SPLIT_NT) parts[i] = ws[static_cast<size_t>(c) * p.G * 2 + i];
-        __syncthreads();
-        float sdz = 0.0f, sdzx = 0.0f;
-#pragma unroll 4
-        for (int i = 0; i < p.G; ++i) {
-            sdz += parts[2 * i];
-            sdzx += parts[2 * i + 1];
-        }
-        if (g == 0 && threadIdx.x == 0) {
-            if (dgamma) dgamma[c] = sdzx;
-            if (dbeta) dbeta[c] = sdz;
-        }
+        __shared__ float parts[2 * SPLIT_MAX];
+        float sdz, sdzx;
+        sum_partials(ws, c, p.G, parts, sdz, sdzx);
+        if (g == 0 && threadIdx.x == 0) put_param_grads(dgamma, dbeta, c, sdz, sdzx);
         if (!dx) return;
         const float n = static_cast<float>(p.B) * static_cast<float>(HW);
         m1 = training ? sdz / n : 0.0f;
@@ -1198,14 +1047,13 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_pool_bwd_kernel(const float *__re
                         const int want = (h - ((oh0 + r) * 2 - 1)) * 3 + (w - ((ow0 + k) * 2 - 1));
                         if (cv[r][k] == want) acc += gv[r][k];
                     }
-                const float pre = (xv[v] - mean) * a + b0;  // the forward's expression: the same bits, hence the same mask as y > 0
-                const float dz = pre > 0.0f ? acc : 0.0f;
-                const float xhat = (xv[v] - mean) * invstd;
+                const float dz = mask1(acc, bn_affine(xv[v], mean, a, b0));  // the forward's expression: the same mask as y > 0
+                const float xhat = bn_xhat(xv[v], mean, invstd);
                 if (!APPLY) {
                     sdz += dz;
                     sdzx += dz * xhat;
                 } else {
-                    out[v] = a * ((dz - m1) - xhat * m2);
+                    out[v] = bn_dx(a, dz, m1, xhat, m2);
                 }
             }
             if (APPLY) reinterpret_cast<float4 *>(dx)[pl * HWq + q] = make_float4(out[0], out[1], out[2], out[3]);
@@ -1213,11 +1061,7 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_pool_bwd_kernel(const float *__re
         __syncthreads();
     }
     if (!APPLY) {
-        {
-            float two[2] = {sdz, sdzx};
-            block_sums<SPLIT_NT, 2>(two, scratch);
-            sdz = two[0], sdzx = two[1];
-        }
+        block_sum_pair<SPLIT_NT>(sdz, sdzx, scratch);
         if (threadIdx.x == 0) {
             ws[(static_cast<size_t>(c) * p.G + g) * 2 + 0] = sdz;
             ws[(static_cast<size_t>(c) * p.G + g) * 2 + 1] = sdzx;
@@ -1234,27 +1078,15 @@ inline bool pool_shape(int B, int C, int H, int W, PoolShape &p) {
 }
 
 template <int NT, int VEC>
-void launch_fwd(bool relu, bool has_res, hipStream_t st, const float *x, const float *res, const float *gamma, const float *beta, float *rm,
-                float *rv, float momentum, float eps, int training, float *y, float *sm, float *si, BnShape s) {
-    const dim3 grid(static_cast<unsigned>(s.C)), block(NT);
-    if (relu && has_res)
-        EE_LAUNCH((bn_fwd_kernel<NT, VEC, true, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s);
-    else if (relu)
-        EE_LAUNCH((bn_fwd_kernel<NT, VEC, true, false>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s);
-    else if (has_res)
-        EE_LAUNCH((bn_fwd_kernel<NT, VEC, false, true>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s);
-    else
-        EE_LAUNCH((bn_fwd_kernel<NT, VEC, false, false>), grid, block, 0, st, x, res, gamma, beta, rm, rv, momentum, eps, training, y, sm, si, s);
+void launch_fwd(bool relu, hipStream_t st, const FwdArgs &a, BnShape s) {
+    dispatch(relu, a.res != nullptr, [&](auto R, auto Q) {
+        launch_fwd_args(bn_fwd_kernel<NT, VEC, decltype(R)::value, decltype(Q)::value>, dim3(static_cast<unsigned>(s.C)), dim3(NT), st, a, s);
+    });
 }
 
 template <int NT, int VEC>
-void launch_bwd(bool relu, hipStream_t st, const float *dy, const float *dy2, const float *y, const float *x, const float *beta, const float *gamma, const float *sm, const float *si,
-                const float *rm, const float *rv, float eps, int training, float *dx, float *dres, float *dgamma, float *dbeta, BnShape s) {
-    const dim3 grid(static_cast<unsigned>(s.C)), block(NT);
-    if (relu)
-        EE_LAUNCH((bn_bwd_kernel<NT, VEC, true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, dres, dgamma, dbeta, s);
-    else
-        EE_LAUNCH((bn_bwd_kernel<NT, VEC, false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, sm, si, rm, rv, eps, training, dx, dres, dgamma, dbeta, s);
+void launch_bwd(bool relu, hipStream_t st, const BwdArgs &a, BnShape s) {
+    dispatch(relu, [&](auto R) { launch_bwd_args(bn_bwd_kernel<NT, VEC, decltype(R)::value>, dim3(static_cast<unsigned>(s.C)), dim3(NT), st, a, s); });
 }
 
 
@@ -1272,20 +1104,9 @@ void launch_bwd(bool relu, hipStream_t st, const float *dy, const float *dy2, co
 __global__ __launch_bounds__(64) void bn_moments_kernel(const float *__restrict__ ws, float *__restrict__ moments, BnShape s, int S) {
     const int c = blockIdx.x * 64 + threadIdx.x;
     if (c >= s.C) return;
-    const int total = s.B * (s.HW / 4);
     const float n = static_cast<float>(s.B) * static_cast<float>(s.HW);
-    float sum = 0.0f;
-    for (int i = 0; i < S; ++i) sum += ws[(static_cast<size_t>(c) * S + i) * 2];
-    const float mean = sum / n;
-    float m2 = 0.0f;
-    for (int i = 0; i < S; ++i) {  // the same recombination, in the same order, as combine_slices
-        const Slice sl = my_slice(total, S, i);
-        const float cnt = 4.0f * static_cast<float>(sl.end - sl.begin);
-        if (cnt > 0.0f) {
-            const float d = ws[(static_cast<size_t>(c) * S + i) * 2] / cnt - mean;
-            m2 += ws[(static_cast<size_t>(c) * S + i) * 2 + 1] + cnt * (d * d);
-        }
-    }
+    float mean, m2;
+    combine_moments(ws + static_cast<size_t>(c) * S * 2, S, s.B * (s.HW / 4), n, mean, m2);
     moments[3 * c + 0] = mean;
     moments[3 * c + 1] = m2;
     moments[3 * c + 2] = n;
@@ -1316,35 +1137,9 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_sync_apply_kernel(const float *__
         t = merge(t, Moments{m[2], m[0], m[1]});
     }
     const float var = t.n > 0.0f ? t.m2 / t.n : 0.0f;
-    const float mean = t.mean, invstd = 1.0f / sqrtf(var + eps);
-    if (sl_i == 0 && threadIdx.x == 0) {
-        save_mean[c] = mean;
-        save_invstd[c] = invstd;
-        if (running_mean) {
-            const float unbiased = (t.n > 1.0f) ? var * (t.n / (t.n - 1.0f)) : var;
-            running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * mean;
-            running_var[c] = (1.0f - momentum) * running_var[c] + momentum * unbiased;
-        }
-    }
-    const float a = invstd * (gamma ? gamma[c] : 1.0f), b0 = beta ? beta[c] : 0.0f;
-    const float4 *x4 = reinterpret_cast<const float4 *>(x), *r4 = reinterpret_cast<const float4 *>(res);
-    float4 *y4 = reinterpret_cast<float4 *>(y);
-    struct XR {
-        float4 x, r;
-    };
-    for_slice(s, c, my_slice(s.B * (s.HW / 4), S, sl_i), [&](size_t o) { return XR{x4[o], RES ? r4[o] : make_float4(0.0f, 0.0f, 0.0f, 0.0f)}; },
-              [&](XR in, size_t o) {
-        const float4 v = in.x;
-        float4 r = make_float4((v.x - mean) * a + b0, (v.y - mean) * a + b0, (v.z - mean) * a + b0, (v.w - mean) * a + b0);
-        if (RES) {
-            const float4 q = in.r;
-            r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
-        }
-        if (RELU) {
-            r.x = relu_nan(r.x); r.y = relu_nan(r.y); r.z = relu_nan(r.z); r.w = relu_nan(r.w);
-        }
-        y4[o] = r;
-    });
+    const float mean = t.mean, invstd = bn_invstd(var, eps);
+    if (sl_i == 0 && threadIdx.x == 0) bn_commit_stats(c, mean, var, invstd, t.n, momentum, save_mean, save_invstd, running_mean, running_var);
+    slice_fwd_apply<RELU, RES>(x, res, y, s, c, my_slice(s.B * (s.HW / 4), S, sl_i), mean, bn_gain(invstd, gamma, c), bn_shift(beta, c));
 }
 
 template <bool RELU>
@@ -1354,25 +1149,29 @@ __global__ __launch_bounds__(SPLIT_NT) void bn_sync_bwd_apply_kernel(const float
                                                                      const float *__restrict__ global_sums, float n_global, float *__restrict__ dx,
                                                                      float *__restrict__ dres, BnShape s, int S) {
     const int c = blockIdx.x, sl_i = blockIdx.y;
-    const float mean = save_mean[c], invstd = save_invstd[c];
-    const float w = (gamma ? gamma[c] : 1.0f) * invstd;
-    const float m1 = global_sums[2 * c] / n_global, m2 = global_sums[2 * c + 1] / n_global;
-    const float4 *dy4 = reinterpret_cast<const float4 *>(dy), *y4 = reinterpret_cast<const float4 *>(y), *x4 = reinterpret_cast<const float4 *>(x);
-    float4 *dx4 = reinterpret_cast<float4 *>(dx), *dr4 = reinterpret_cast<float4 *>(dres);
-    const bool want_x = dx != nullptr;
-    const MaskArgs mk = mask_args(y, gamma, beta, invstd, c);
-    for_slice(s, c, my_slice(s.B * (s.HW / 4), S, sl_i), [&](size_t o) { return bwd_load(dy4, reinterpret_cast<const float4 *>(dy2), y4, x4, o, RELU, want_x, mean, mk); }, [&](BwdIn in, size_t o) {
-        const float4 g = masked_dz(in, RELU);
-        if (dres) dr4[o] = g;
-        if (dx) {
-            const float4 v = in.x;
-            dx4[o] = make_float4(w * ((g.x - m1) - ((v.x - mean) * invstd) * m2), w * ((g.y - m1) - ((v.y - mean) * invstd) * m2),
-                                 w * ((g.z - m1) - ((v.z - mean) * invstd) * m2), w * ((g.w - m1) - ((v.w - mean) * invstd) * m2));
-        }
-    });
+    slice_bwd_apply<RELU>(dy, dy2, y, x, gamma, beta, dx, dres, s, c, my_slice(s.B * (s.HW / 4), S, sl_i), save_mean[c], save_invstd[c],
+                          global_sums[2 * c] / n_global, global_sums[2 * c + 1] / n_global);
 }
 
 inline bool al16(const void *q) { return !q || aligned16(q); }
+
+// training mode writes the batch statistics (forward) or reads them (backward); eval mode reads the running ones
+inline bool stats_ptrs_ok(int training, const float *save_mean, const float *save_invstd, const float *running_mean, const float *running_var) {
+    return training ? (save_mean && save_invstd) : (running_mean && running_var);
+}
+
+// The prologue of the ee_bn_act_* / ee_bn_sum_act_* entry points.  true: return `status` now (an error, or EE_OK for an empty batch).
+// tensors: the entry point's required tensor pointers are all there.
+inline bool bn_args_settled(int B, int C, int HW, bool tensors, int training, const float *save_mean, const float *save_invstd, const float *running_mean,
+                            const float *running_var, int &status) {
+    status = EE_OK;
+    if (B < 0 || C < 1 || HW < 1 || static_cast<int64_t>(B) * HW > 0x7fffffffLL) status = EE_ERR_SHAPE;
+    else if (B == 0) return true;
+    else if (!tensors || !stats_ptrs_ok(training, save_mean, save_invstd, running_mean, running_var)) status = EE_ERR_NULL;
+    return status != EE_OK;
+}
+
+inline dim3 split_grid(int C, int S) { return dim3(static_cast<unsigned>(C), static_cast<unsigned>(S)); }
 
 }  // namespace
 
@@ -1387,70 +1186,56 @@ EE_API int ee_bn_workspace_floats(int B, int C, int HW) {
 EE_API int ee_bn_act_fwd_f32(const float *x, const float *residual, const float *gamma, const float *beta, float *running_mean,
                              float *running_var, float momentum, float eps, int training, int relu, float *y, float *save_mean,
                              float *save_invstd, float *workspace, int B, int C, int HW, void *stream) {
-    if (B < 0 || C < 1 || HW < 1) return EE_ERR_SHAPE;
-    if (static_cast<int64_t>(B) * HW > 0x7fffffffLL) return EE_ERR_SHAPE;
-    if (B == 0) return EE_OK;
-    if (!x || !y) return EE_ERR_NULL;
-    if (training && (!save_mean || !save_invstd)) return EE_ERR_NULL;
-    if (!training && (!running_mean || !running_var)) return EE_ERR_NULL;
+    int status;
+    if (bn_args_settled(B, C, HW, x && y, training, save_mean, save_invstd, running_mean, running_var, status)) return status;
     const BnShape s{B, C, HW};
+    const FwdArgs a{x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd};
     const bool vec = (HW % 4 == 0) && al16(x) && al16(y) && al16(residual);
     const bool big = static_cast<int64_t>(B) * HW >= 16384;
+    const int64_t quads = static_cast<int64_t>(B) * (HW / 4), numel = static_cast<int64_t>(B) * C * HW;
     hipStream_t st = as_stream(stream);
-    const int cv = vec ? cached_variant(static_cast<int64_t>(B) * (HW / 4), static_cast<int64_t>(B) * C * HW) : 0;
-    if (cv == 1) launch_fwd_cached<256, 2>(relu != 0, residual != nullptr, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, s);
-    else if (cv == 2) launch_fwd_cached<256, 7>(relu != 0, residual != nullptr, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, s);
-    else if (cv == 3) launch_fwd_cached<1024, 7>(relu != 0, residual != nullptr, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, s);
-    else if (vec && workspace && static_cast<int64_t>(B) * C * HW / 4 <= 0x7fffffffLL) {
-        const int S = split_slices(static_cast<int64_t>(B) * (HW / 4));
-        const dim3 grid(static_cast<unsigned>(C), static_cast<unsigned>(S)), block(SPLIT_NT);
-        if (training) EE_LAUNCH(bn_split_stats_kernel, grid, block, 0, st, x, workspace, s, S);
-        if (relu && residual)
-            EE_LAUNCH((bn_split_apply_kernel<true, true>), grid, block, 0, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, workspace, s, S);
-        else if (relu)
-            EE_LAUNCH((bn_split_apply_kernel<true, false>), grid, block, 0, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, workspace, s, S);
-        else if (residual)
-            EE_LAUNCH((bn_split_apply_kernel<false, true>), grid, block, 0, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, workspace, s, S);
-        else
-            EE_LAUNCH((bn_split_apply_kernel<false, false>), grid, block, 0, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, workspace, s, S);
-    } else if (vec && big) launch_fwd<1024, 4>(relu != 0, residual != nullptr, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, s);
-    else if (vec) launch_fwd<256, 4>(relu != 0, residual != nullptr, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, s);
-    else if (big) launch_fwd<1024, 1>(relu != 0, residual != nullptr, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, s);
-    else launch_fwd<256, 1>(relu != 0, residual != nullptr, st, x, residual, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd, s);
+    const bool cached = with_cached_cfg(vec ? cached_variant(quads, numel) : 0, [&](auto cfg) {
+        launch_fwd_cached<decltype(cfg)::NT, decltype(cfg)::MAXV>(relu != 0, false, st, a, s, nullptr);
+    });
+    if (cached) {
+    } else if (vec && workspace && numel / 4 <= 0x7fffffffLL) {
+        const int S = split_slices(quads);
+        if (training) EE_LAUNCH(bn_split_stats_kernel, split_grid(C, S), dim3(SPLIT_NT), 0, st, x, workspace, s, S);
+        dispatch(relu != 0, residual != nullptr, [&](auto R, auto Q) {
+            launch_fwd_args(bn_split_apply_kernel<decltype(R)::value, decltype(Q)::value>, split_grid(C, S), dim3(SPLIT_NT), st, a,
+                            static_cast<const float *>(workspace), s, S);
+        });
+    } else {
+        dispatch(vec, big, [&](auto V, auto G) { launch_fwd<decltype(G)::value ? 1024 : 256, decltype(V)::value ? 4 : 1>(relu != 0, st, a, s); });
+    }
     return launch_status();
 }
 
 EE_API int ee_bn_act_bwd2_f32(const float *dy, const float *dy2, const float *y, const float *x, const float *gamma, const float *beta, const float *save_mean,
                              const float *save_invstd, const float *running_mean, const float *running_var, float eps, int training, int relu,
                              float *dx, float *dresidual, float *dgamma, float *dbeta, float *workspace, int B, int C, int HW, void *stream) {
-    if (B < 0 || C < 1 || HW < 1) return EE_ERR_SHAPE;
-    if (static_cast<int64_t>(B) * HW > 0x7fffffffLL) return EE_ERR_SHAPE;
-    if (B == 0) return EE_OK;
-    if (!dy || !x) return EE_ERR_NULL;  // y == NULL with relu: the mask is recomputed from x, gamma, beta (no residual branch: the caller's promise)
-    if (training && (!save_mean || !save_invstd)) return EE_ERR_NULL;
-    if (!training && (!running_mean || !running_var)) return EE_ERR_NULL;
+    int status;  // y == NULL with relu: the mask is recomputed from x, gamma, beta (no residual branch: the caller's promise)
+    if (bn_args_settled(B, C, HW, dy && x, training, save_mean, save_invstd, running_mean, running_var, status)) return status;
     const BnShape s{B, C, HW};
+    const BwdArgs a{dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta};
     const bool vec = (HW % 4 == 0) && al16(dy) && al16(dy2) && al16(y) && al16(x) && al16(dx) && al16(dresidual);
     const bool big = static_cast<int64_t>(B) * HW >= 16384;
+    const int64_t quads = static_cast<int64_t>(B) * (HW / 4), numel = static_cast<int64_t>(B) * C * HW;
     hipStream_t st = as_stream(stream);
-    const int cv = vec ? cached_variant(static_cast<int64_t>(B) * (HW / 4), static_cast<int64_t>(B) * C * HW) : 0;
-    if (cv == 1) launch_bwd_cached<256, 2>(relu != 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta, s);
-    else if (cv == 2) launch_bwd_cached<256, 7>(relu != 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta, s);
-    else if (cv == 3) launch_bwd_cached<1024, 7>(relu != 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta, s);
-    else if (vec && workspace && static_cast<int64_t>(B) * C * HW / 4 <= 0x7fffffffLL) {
-        const int S = split_slices(static_cast<int64_t>(B) * (HW / 4));
-        const dim3 grid(static_cast<unsigned>(C), static_cast<unsigned>(S)), block(SPLIT_NT);
-        if (relu) {
-            EE_LAUNCH((bn_split_bwd_partial_kernel<true>), grid, block, 0, st, dy, dy2, y, x, gamma, beta, save_mean, save_invstd, running_mean, running_var, eps, training, workspace, s, S);
-            EE_LAUNCH((bn_split_bwd_apply_kernel<true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta, workspace, s, S);
-        } else {
-            EE_LAUNCH((bn_split_bwd_partial_kernel<false>), grid, block, 0, st, dy, dy2, y, x, gamma, beta, save_mean, save_invstd, running_mean, running_var, eps, training, workspace, s, S);
-            EE_LAUNCH((bn_split_bwd_apply_kernel<false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta, workspace, s, S);
-        }
-    } else if (vec && big) launch_bwd<1024, 4>(relu != 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta, s);
-    else if (vec) launch_bwd<256, 4>(relu != 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta, s);
-    else if (big) launch_bwd<1024, 1>(relu != 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta, s);
-    else launch_bwd<256, 1>(relu != 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, dx, dresidual, dgamma, dbeta, s);
+    const bool cached = with_cached_cfg(vec ? cached_variant(quads, numel) : 0, [&](auto cfg) {
+        launch_bwd_cached<decltype(cfg)::NT, decltype(cfg)::MAXV>(relu != 0, st, a, s, nullptr);
+    });
+    if (cached) {
+    } else if (vec && workspace && numel / 4 <= 0x7fffffffLL) {
+        const int S = split_slices(quads);
+        dispatch(relu != 0, [&](auto R) {
+            EE_LAUNCH(bn_split_bwd_partial_kernel<decltype(R)::value>, split_grid(C, S), dim3(SPLIT_NT), 0, st, dy, dy2, y, x, gamma, beta, save_mean,
+                      save_invstd, running_mean, running_var, eps, training, workspace, s, S);
+            launch_bwd_args(bn_split_bwd_apply_kernel<decltype(R)::value>, split_grid(C, S), dim3(SPLIT_NT), st, a, static_cast<const float *>(workspace), s, S);
+        });
+    } else {
+        dispatch(vec, big, [&](auto V, auto G) { launch_bwd<decltype(G)::value ? 1024 : 256, decltype(V)::value ? 4 : 1>(relu != 0, st, a, s); });
+    }
     return launch_status();
 }
 
@@ -1468,20 +1253,16 @@ EE_API int ee_bn_act_bwd_f32(const float *dy, const float *y, const float *x, co
 EE_API int ee_bn_sum_act_fwd_f32(const float *x, const float *res, const float *gamma, const float *beta, float *running_mean, float *running_var,
                                  float momentum, float eps, int training, int relu, float *sum_out, float *y, float *save_mean, float *save_invstd,
                                  int B, int C, int HW, void *stream) {
-    if (B < 0 || C < 1 || HW < 1) return EE_ERR_SHAPE;
-    if (static_cast<int64_t>(B) * HW > 0x7fffffffLL) return EE_ERR_SHAPE;
-    if (B == 0) return EE_OK;
-    if (!x || !res || !y) return EE_ERR_NULL;
-    if (training && (!save_mean || !save_invstd)) return EE_ERR_NULL;
-    if (!training && (!running_mean || !running_var)) return EE_ERR_NULL;
+    int status;
+    if (bn_args_settled(B, C, HW, x && res && y, training, save_mean, save_invstd, running_mean, running_var, status)) return status;
     if (HW % 4 || !al16(x) || !al16(res) || !al16(y) || !al16(sum_out)) return EE_ERR_UNSUPPORTED;
     const BnShape s{B, C, HW};
+    const FwdArgs a{x, res, gamma, beta, running_mean, running_var, momentum, eps, training, y, save_mean, save_invstd};
     hipStream_t st = as_stream(stream);
-    const int cv = cached_variant(static_cast<int64_t>(B) * (HW / 4), static_cast<int64_t>(B) * C * HW);
-    if (cv == 1) launch_sum_fwd_cached<256, 2>(relu != 0, st, x, res, gamma, beta, running_mean, running_var, momentum, eps, training, sum_out, y, save_mean, save_invstd, s);
-    else if (cv == 2) launch_sum_fwd_cached<256, 7>(relu != 0, st, x, res, gamma, beta, running_mean, running_var, momentum, eps, training, sum_out, y, save_mean, save_invstd, s);
-    else if (cv == 3) launch_sum_fwd_cached<1024, 7>(relu != 0, st, x, res, gamma, beta, running_mean, running_var, momentum, eps, training, sum_out, y, save_mean, save_invstd, s);
-    else return EE_ERR_UNSUPPORTED;
+    if (!with_cached_cfg(cached_variant(static_cast<int64_t>(B) * (HW / 4), static_cast<int64_t>(B) * C * HW), [&](auto cfg) {
+            launch_fwd_cached<decltype(cfg)::NT, decltype(cfg)::MAXV>(relu != 0, true, st, a, s, sum_out);
+        }))
+        return EE_ERR_UNSUPPORTED;
     return launch_status();
 }
 
@@ -1489,20 +1270,16 @@ EE_API int ee_bn_sum_act_bwd_f32(const float *dy, const float *dy2, const float 
                                  const float *save_mean, const float *save_invstd, const float *running_mean, const float *running_var, float eps,
                                  int training, int relu, const float *ds_add, float *ds, float *dgamma, float *dbeta, int B, int C, int HW,
                                  void *stream) {
-    if (B < 0 || C < 1 || HW < 1) return EE_ERR_SHAPE;
-    if (static_cast<int64_t>(B) * HW > 0x7fffffffLL) return EE_ERR_SHAPE;
-    if (B == 0) return EE_OK;
-    if (!dy || !s || !ds) return EE_ERR_NULL;  // y == NULL with relu: the mask is recomputed from s, gamma, beta (the forward's expression)
-    if (training && (!save_mean || !save_invstd)) return EE_ERR_NULL;
-    if (!training && (!running_mean || !running_var)) return EE_ERR_NULL;
+    int status;  // y == NULL with relu: the mask is recomputed from s, gamma, beta (the forward's expression)
+    if (bn_args_settled(B, C, HW, dy && s && ds, training, save_mean, save_invstd, running_mean, running_var, status)) return status;
     if (HW % 4 || !al16(dy) || !al16(dy2) || !al16(y) || !al16(s) || !al16(ds_add) || !al16(ds)) return EE_ERR_UNSUPPORTED;
     const BnShape sh{B, C, HW};
+    const BwdArgs a{dy, dy2, y, s, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, ds, nullptr, dgamma, dbeta};
     hipStream_t st = as_stream(stream);
-    const int cv = cached_variant(static_cast<int64_t>(B) * (HW / 4), static_cast<int64_t>(B) * C * HW);
-    if (cv == 1) launch_sum_bwd_cached<256, 2>(relu != 0, st, dy, dy2, y, s, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, ds_add, ds, dgamma, dbeta, sh);
-    else if (cv == 2) launch_sum_bwd_cached<256, 7>(relu != 0, st, dy, dy2, y, s, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, ds_add, ds, dgamma, dbeta, sh);
-    else if (cv == 3) launch_sum_bwd_cached<1024, 7>(relu != 0, st, dy, dy2, y, s, beta, gamma, save_mean, save_invstd, running_mean, running_var, eps, training, ds_add, ds, dgamma, dbeta, sh);
-    else return EE_ERR_UNSUPPORTED;
+    if (!with_cached_cfg(cached_variant(static_cast<int64_t>(B) * (HW / 4), static_cast<int64_t>(B) * C * HW), [&](auto cfg) {
+            launch_bwd_cached<decltype(cfg)::NT, decltype(cfg)::MAXV>(relu != 0, st, a, sh, ds_add);
+        }))
+        return EE_ERR_UNSUPPORTED;
     return launch_status();
 }
 
@@ -1522,8 +1299,7 @@ static int bn_relu_pool_fwd_impl(const float *x, const float *gamma, const float
     PoolShape p;
     if (!pool_shape(B, C, H, W, p)) return EE_ERR_UNSUPPORTED;
     if (!x || !y_pool || !code || !workspace) return EE_ERR_NULL;
-    if (training && (!save_mean || !save_invstd)) return EE_ERR_NULL;
-    if (!training && (!running_mean || !running_var)) return EE_ERR_NULL;
+    if (!stats_ptrs_ok(training, save_mean, save_invstd, running_mean, running_var)) return EE_ERR_NULL;
     if (!aligned16(x)) return EE_ERR_ALIGN;
     hipStream_t st = as_stream(stream);
     const BnShape s{B, C, H * W};
@@ -1573,8 +1349,7 @@ static int bn_relu_pool_bwd_impl(const float *dy_pool, const float *dy_pool2, co
     PoolShape p;
     if (!pool_shape(B, C, H, W, p)) return EE_ERR_UNSUPPORTED;
     if (!dy_pool || !code || !x || !workspace) return EE_ERR_NULL;
-    if (training && (!save_mean || !save_invstd)) return EE_ERR_NULL;
-    if (!training && (!running_mean || !running_var)) return EE_ERR_NULL;
+    if (!stats_ptrs_ok(training, save_mean, save_invstd, running_mean, running_var)) return EE_ERR_NULL;
     if (!aligned16(x) || (dx && !aligned16(dx))) return EE_ERR_ALIGN;
     hipStream_t st = as_stream(stream);
     const dim3 grid(static_cast<unsigned>(C), static_cast<unsigned>(p.G)), block(SPLIT_NT);
@@ -1686,7 +1461,7 @@ EE_API int ee_syncbn_stats_f32(const float *x, float *workspace, float *moments,
     const BnShape s{B, C, HW};
     const int S = split_slices(static_cast<int64_t>(B) * (HW / 4));
     hipStream_t st = as_stream(stream);
-    EE_LAUNCH(bn_split_stats_kernel, dim3(static_cast<unsigned>(C), static_cast<unsigned>(S)), dim3(SPLIT_NT), 0, st, x, workspace, s, S);
+    EE_LAUNCH(bn_split_stats_kernel, split_grid(C, S), dim3(SPLIT_NT), 0, st, x, workspace, s, S);
     EE_LAUNCH(bn_moments_kernel, dim3(static_cast<unsigned>((C + 63) / 64)), dim3(64), 0, st, workspace, moments, s, S);
     return launch_status();
 }
@@ -1702,16 +1477,11 @@ EE_API int ee_syncbn_apply_f32(const float *x, const float *residual, const floa
     if (!aligned16(x) || !aligned16(y) || !al16(residual)) return EE_ERR_ALIGN;
     const BnShape s{B, C, HW};
     const int S = split_slices(static_cast<int64_t>(B) * (HW / 4));
-    const dim3 grid(static_cast<unsigned>(C), static_cast<unsigned>(S)), block(SPLIT_NT);
     hipStream_t st = as_stream(stream);
-    if (relu && residual)
-        EE_LAUNCH((bn_sync_apply_kernel<true, true>), grid, block, 0, st, x, residual, gamma, beta, all_moments, W, running_mean, running_var, momentum, eps, y, save_mean, save_invstd, s, S);
-    else if (relu)
-        EE_LAUNCH((bn_sync_apply_kernel<true, false>), grid, block, 0, st, x, residual, gamma, beta, all_moments, W, running_mean, running_var, momentum, eps, y, save_mean, save_invstd, s, S);
-    else if (residual)
-        EE_LAUNCH((bn_sync_apply_kernel<false, true>), grid, block, 0, st, x, residual, gamma, beta, all_moments, W, running_mean, running_var, momentum, eps, y, save_mean, save_invstd, s, S);
-    else
-        EE_LAUNCH((bn_sync_apply_kernel<false, false>), grid, block, 0, st, x, residual, gamma, beta, all_moments, W, running_mean, running_var, momentum, eps, y, save_mean, save_invstd, s, S);
+    dispatch(relu != 0, residual != nullptr, [&](auto R, auto Q) {
+        EE_LAUNCH((bn_sync_apply_kernel<decltype(R)::value, decltype(Q)::value>), split_grid(C, S), dim3(SPLIT_NT), 0, st, x, residual, gamma, beta, all_moments,
+                  W, running_mean, running_var, momentum, eps, y, save_mean, save_invstd, s, S);
+    });
     return launch_status();
 }
 
@@ -1724,12 +1494,11 @@ EE_API int ee_syncbn_bwd_sums_f32(const float *dy, const float *dy2, const float
     if (!aligned16(dy) || !aligned16(x) || !al16(dy2) || !al16(y)) return EE_ERR_ALIGN;
     const BnShape s{B, C, HW};
     const int S = split_slices(static_cast<int64_t>(B) * (HW / 4));
-    const dim3 grid(static_cast<unsigned>(C), static_cast<unsigned>(S)), block(SPLIT_NT);
     hipStream_t st = as_stream(stream);
-    if (relu)
-        EE_LAUNCH((bn_split_bwd_partial_kernel<true>), grid, block, 0, st, dy, dy2, y, x, gamma, beta, save_mean, save_invstd, nullptr, nullptr, 0.0f, 1, workspace, s, S);
-    else
-        EE_LAUNCH((bn_split_bwd_partial_kernel<false>), grid, block, 0, st, dy, dy2, y, x, gamma, beta, save_mean, save_invstd, nullptr, nullptr, 0.0f, 1, workspace, s, S);
+    dispatch(relu != 0, [&](auto R) {
+        EE_LAUNCH(bn_split_bwd_partial_kernel<decltype(R)::value>, split_grid(C, S), dim3(SPLIT_NT), 0, st, dy, dy2, y, x, gamma, beta, save_mean, save_invstd,
+                  nullptr, nullptr, 0.0f, 1, workspace, s, S);
+    });
     EE_LAUNCH(bn_sums_kernel, dim3(static_cast<unsigned>((C + 63) / 64)), dim3(64), 0, st, workspace, sums, C, S);
     return launch_status();
 }
@@ -1745,11 +1514,10 @@ EE_API int ee_syncbn_bwd_apply_f32(const float *dy, const float *dy2, const floa
     if (!dx && !dresidual) return EE_OK;
     const BnShape s{B, C, HW};
     const int S = split_slices(static_cast<int64_t>(B) * (HW / 4));
-    const dim3 grid(static_cast<unsigned>(C), static_cast<unsigned>(S)), block(SPLIT_NT);
     hipStream_t st = as_stream(stream);
-    if (relu)
-        EE_LAUNCH((bn_sync_bwd_apply_kernel<true>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, global_sums, static_cast<float>(n_global), dx, dresidual, s, S);
-    else
-        EE_LAUNCH((bn_sync_bwd_apply_kernel<false>), grid, block, 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd, global_sums, static_cast<float>(n_global), dx, dresidual, s, S);
+    dispatch(relu != 0, [&](auto R) {
+        EE_LAUNCH(bn_sync_bwd_apply_kernel<decltype(R)::value>, split_grid(C, S), dim3(SPLIT_NT), 0, st, dy, dy2, y, x, beta, gamma, save_mean, save_invstd,
+                  global_sums, static_cast<float>(n_global), dx, dresidual, s, S);
+    });
     return launch_status();
 }

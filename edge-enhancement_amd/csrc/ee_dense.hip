@@ -107,7 +107,7 @@ __global__ __launch_bounds__(DN_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         if constexpr (PRE) {                                                                   \
             const size_t ko_ = static_cast<size_t>(round_) * DN_KU;                            \
             /* two gradient pieces: rare, fetched here */                                      \
-            if (pre.add) v_ = sum4(v_, *reinterpret_cast<const float4 *>(pre.add + ao[J] + ko_)); \
+            if (pre.add) v_ = add4(v_, *reinterpret_cast<const float4 *>(pre.add + ao[J] + ko_)); \
             v_ = mask4(v_, RM##AS##_##J);                                                      \
             if (ast[J]) *reinterpret_cast<float4 *>(pre.store + ao[J] + ko_) = v_;             \
             v_ = scale4(wtab[((round_) * DN_KU + 4 * af) >> 2], v_);                           \
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(DN_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                     const float4 q = *reinterpret_cast<const float4 *>(post.res + o);
                     s.x += q.x, s.y += q.y, s.z += q.z, s.w += q.w;
                 }
-                if (post.relu) s.x = relu_keep_nan(s.x), s.y = relu_keep_nan(s.y), s.z = relu_keep_nan(s.z), s.w = relu_keep_nan(s.w);
+                if (post.relu) s.x = relu_nan(s.x), s.y = relu_nan(s.y), s.z = relu_nan(s.z), s.w = relu_nan(s.w);
             }
             *reinterpret_cast<float4 *>(c + o) = s;
         }

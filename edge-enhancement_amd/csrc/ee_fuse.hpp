@@ -6,12 +6,12 @@
 //   forward   the convolution's output transform applies it, adds the block's residual and the ReLU (FusePost) before the only store;
 //   backward  the backward-data convolution applies dz = (y > 0) * (dy [+ dy2]),  x = gamma * invstd * dz  while it stages its input
 //             (FusePre), and one workgroup per image writes dz out as the residual branch's gradient.
-// The expressions and their order are those of ee_bn.hip's kernels in eval mode (bn_fwd_cached_kernel / bn_bwd_cached_kernel with
-// training = 0; -ffp-contract=off), so the fused path gives the bits of the unfused one.
+// The expressions are ee_bn_math.hpp's, the ones ee_bn.hip's kernels evaluate in eval mode, so the fused path gives the bits of the
+// unfused one.
 //
 // CNN-body glue, not a row of SURVEY.md section 8.
 #pragma once
-#include "ee_common.hpp"
+#include "ee_bn_math.hpp"
 
 namespace ee {
 
@@ -33,37 +33,24 @@ struct FusePost {
     int relu;
 };
 
-// invstd exactly as ee_bn.hip computes it in eval mode
-__device__ __forceinline__ float bn_invstd(float var, float eps) { return 1.0f / sqrtf(var + eps); }
-// bn_fwd_cached_kernel: a = invstd * gamma;  bn_bwd_cached_kernel: w = gamma * invstd - one product, commutative: the same bits
-__device__ __forceinline__ float bn_scale(const float *var, const float *gamma, float eps, int c) {
-    return bn_invstd(var[c], eps) * (gamma ? gamma[c] : 1.0f);
-}
-// ReLU that keeps NaN (ee_bn.hip: relu_nan)
-__device__ __forceinline__ float relu_keep_nan(float r) { return r > 0.0f ? r : (r != r ? r : 0.0f); }
+__device__ __forceinline__ float bn_scale(const float *var, const float *gamma, float eps, int c) { return bn_gain(bn_invstd(var[c], eps), gamma, c); }
 
 struct PostConst {  // a lane's constants for its result channel
     float mean, a, b;
 };
 __device__ __forceinline__ PostConst post_const(const FusePost &p, int c) {
     if (!p.mean) return PostConst{0.0f, 1.0f, 0.0f};
-    return PostConst{p.mean[c], bn_scale(p.var, p.gamma, p.eps, c), p.beta ? p.beta[c] : 0.0f};
+    return PostConst{p.mean[c], bn_scale(p.var, p.gamma, p.eps, c), bn_shift(p.beta, c)};
 }
-__device__ __forceinline__ float post_apply(float c, const PostConst &k) { return (c - k.mean) * k.a + k.b; }
-
-__device__ __forceinline__ float4 mask4(float4 v, float4 m) {
-    return make_float4(m.x > 0.0f ? v.x : 0.0f, m.y > 0.0f ? v.y : 0.0f, m.z > 0.0f ? v.z : 0.0f, m.w > 0.0f ? v.w : 0.0f);
-}
-__device__ __forceinline__ float4 sum4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ float4 scale4(float w, float4 v) { return make_float4(w * v.x, w * v.y, w * v.z, w * v.w); }
+__device__ __forceinline__ float post_apply(float c, const PostConst &k) { return bn_affine(c, k.mean, k.a, k.b); }
 
 // ---- TRAIN-mode BatchNorm across the kernel boundary (round 4) ------------------------------------------------------------------------
 // The convolution in front of a mid-block BatchNorm (resnet.py:44-49: conv1 -> bn1 -> relu -> conv2) writes, next to its raw output, the
 // moments of what each workgroup holds: stats_out [channels][S][2] = (mean, M2) of `cnt` values each (equal counts).  The convolution
 // behind it merges the S partials of every reduction channel in its prologue - each of 16 lanes its share in index order, then a fixed
 // butterfly: mean = sum mean_s / S, M2 = sum (M2_s + cnt * (mean_s - mean)^2), no division inside the sums, the same bits in every
-// workgroup and every run - and stages relu((x - mean) * invstd * gamma + beta).  Workgroup 0 also writes save_mean / save_invstd (the
-// backward pass reads them) and moves the running statistics exactly as ee_bn.hip's forward does.
+// workgroup and every run - and stages relu((x - mean) * invstd * gamma + beta).  Workgroup 0 also commits the statistics
+// (bn_commit_stats).
 struct TrainBn {
     float *stats_out;            // producer: [result channels][S][2]; null: no statistics epilogue
     const float *part;           // consumer: the producer's stats_out, [reduction channels][S][2]
@@ -97,17 +84,9 @@ __device__ __forceinline__ void train_bn_merge(const TrainBn &tb, int KC, float 
         if (j == 0) {
             const float var = s2 / n, invstd = bn_invstd(var, tb.eps);
             table[3 * c] = mean;
-            table[3 * c + 1] = invstd * (tb.gamma ? tb.gamma[c] : 1.0f);
-            table[3 * c + 2] = tb.beta ? tb.beta[c] : 0.0f;
-            if (writer) {
-                tb.save_mean[c] = mean;
-                tb.save_invstd[c] = invstd;
-                if (tb.running_mean) {  // ee_bn.hip: bn_fwd_cached_kernel
-                    const float unbiased = (n > 1.0f) ? var * (n / (n - 1.0f)) : var;
-                    tb.running_mean[c] = (1.0f - tb.momentum) * tb.running_mean[c] + tb.momentum * mean;
-                    tb.running_var[c] = (1.0f - tb.momentum) * tb.running_var[c] + tb.momentum * unbiased;
-                }
-            }
+            table[3 * c + 1] = bn_gain(invstd, tb.gamma, c);
+            table[3 * c + 2] = bn_shift(tb.beta, c);
+            if (writer) bn_commit_stats(c, mean, var, invstd, n, tb.momentum, tb.save_mean, tb.save_invstd, tb.running_mean, tb.running_var);
         }
     }
 }
@@ -130,22 +109,21 @@ __device__ __forceinline__ void train_bn_bwd_merge(const TrainBn &tb, int KC, fl
 #pragma unroll
         for (int off = 1; off < 16; off <<= 1) s1 += __shfl_xor(s1, off, 16), s2 += __shfl_xor(s2, off, 16);
         if (j == 0) {
-            const float invstd = tb.save_invstd[c], g = tb.gamma ? tb.gamma[c] : 1.0f;
+            const float invstd = tb.save_invstd[c], w = bn_gain(invstd, tb.gamma, c);
             float *t = table + 7 * c;
-            t[0] = tb.save_mean[c], t[1] = invstd, t[2] = invstd * g, t[3] = tb.beta ? tb.beta[c] : 0.0f, t[4] = g * invstd, t[5] = s1 / n, t[6] = s2 / n;
+            t[0] = tb.save_mean[c], t[1] = invstd, t[2] = w, t[3] = bn_shift(tb.beta, c), t[4] = w, t[5] = s1 / n, t[6] = s2 / n;
         }
     }
 }
-// ee_bn.hip: bn_bwd_cached_kernel with the mask recomputed from x (MaskArgs.on) - the same expressions
+// the mask is recomputed from x (ee_bn_math.hpp: MaskArgs.on)
 __device__ __forceinline__ float train_bn_bwd_apply(float d, float x, const float *t) {
-    const float dz = ((x - t[0]) * t[2] + t[3]) > 0.0f ? d : 0.0f;
-    return t[4] * ((dz - t[5]) - ((x - t[0]) * t[1]) * t[6]);
+    return bn_dx(t[4], mask1(d, bn_affine(x, t[0], t[2], t[3])), t[5], bn_xhat(x, t[0], t[1]), t[6]);
 }
 __device__ __forceinline__ float4 train_bn_bwd_apply4(float4 d, float4 x, const float *t) {
     return make_float4(train_bn_bwd_apply(d.x, x.x, t), train_bn_bwd_apply(d.y, x.y, t), train_bn_bwd_apply(d.z, x.z, t), train_bn_bwd_apply(d.w, x.w, t));
 }
 
-__device__ __forceinline__ float train_bn_apply(float v, const float *t) { return relu_keep_nan((v - t[0]) * t[1] + t[2]); }
+__device__ __forceinline__ float train_bn_apply(float v, const float *t) { return relu_nan(bn_affine(v, t[0], t[1], t[2])); }
 __device__ __forceinline__ float4 train_bn_apply4(float4 v, const float *t) {
     return make_float4(train_bn_apply(v.x, t), train_bn_apply(v.y, t), train_bn_apply(v.z, t), train_bn_apply(v.w, t));
 }

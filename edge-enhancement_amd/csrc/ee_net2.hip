@@ -11,7 +11,7 @@
 // runs through those; the parameter gradients of a training step: net2_conv*_wrw_kernel below (round 3).
 //
 // CNN-body glue, not a row of SURVEY.md section 8.
-#include "ee_common.hpp"
+#include "ee_bn_math.hpp"
 
 #include <math.h>
 #include <stdlib.h>
@@ -22,8 +22,6 @@ using namespace ee;
 
 constexpr int N2_NT = 256;
 constexpr int N2_H0 = 28, N2_C1 = 32, N2_H1 = 12, N2_C2 = 64, N2_H2 = 4;
-
-__device__ __forceinline__ float relu_keep_nan(float v) { return v > 0.0f ? v : (v != v ? v : 0.0f); }
 
 // max over a 2x2 window in ATen's order (0,0) (0,1) (1,0) (1,1); code = index of the winner
 __device__ __forceinline__ float pool4(const float v[4], int &code) {
@@ -78,7 +76,7 @@ __global__ __launch_bounds__(N2_NT) void net2_conv1_fwd_kernel(const float *__re
         int code;
         const float best = pool4(v, code);
         const size_t dst = (static_cast<size_t>(b) * N2_C1 + c0 + c) * (N2_H1 * N2_H1) + r;
-        a1[dst] = relu_keep_nan(best);
+        a1[dst] = relu_nan(best);
         code1[dst] = static_cast<uint8_t>(code);
     }
 }
@@ -180,7 +178,7 @@ __global__ __launch_bounds__(N2_NT) void net2_conv2_fwd_kernel(const float *__re
         int code;
         const float best = pool4(v, code);
         const size_t dst = (static_cast<size_t>(b) * N2_C2 + c0 + co) * (N2_H2 * N2_H2) + p;
-        a2[dst] = relu_keep_nan(best);
+        a2[dst] = relu_nan(best);
         code2[dst] = static_cast<uint8_t>(code);
     }
 }
@@ -281,7 +279,7 @@ __global__ __launch_bounds__(N2_NT) void net2_conv2_fwd_mfma_kernel(const float 
             int code;
             const float best = pool4(v, code);
             const size_t dst = (static_cast<size_t>(b) * N2_C2 + co) * (N2_H2 * N2_H2) + wave * N2_H2 + (l15 >> 1);
-            a2[dst] = relu_keep_nan(best);
+            a2[dst] = relu_nan(best);
             code2[dst] = static_cast<uint8_t>(code);
         }
     }

@@ -298,7 +298,7 @@ __global__ __launch_bounds__(S2_NT, 4) void conv3s2_fwd_mfma_kernel(const float 
                     const PostConst k = post_const(pp, co0 + co);
                     s.x = post_apply(s.x, k), s.y = post_apply(s.y, k), s.z = post_apply(s.z, k), s.w = post_apply(s.w, k);
                 }
-                if (pp.relu) s.x = relu_keep_nan(s.x), s.y = relu_keep_nan(s.y), s.z = relu_keep_nan(s.z), s.w = relu_keep_nan(s.w);
+                if (pp.relu) s.x = relu_nan(s.x), s.y = relu_nan(s.y), s.z = relu_nan(s.z), s.w = relu_nan(s.w);
             }
             if (b0 + img < d.B) *reinterpret_cast<float4 *>((set == 0 ? y : y1) + dst) = s;
             if constexpr (STATS) {

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(W4_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         if constexpr (PRE == 3) {
             own = train_bn_apply4(own, wtab + 3 * ((round_ < rounds ? round_ : rounds - 1) * WN_CK + ci_x));
         } else {
-            if constexpr (PRE == 2) own = sum4(own, y0);
+            if constexpr (PRE == 2) own = add4(own, y0);
             own = mask4(own, m0);
             if (pre_store && round_ < rounds) *reinterpret_cast<float4 *>((pre.store + round_ * xstep) + xq) = own;
             own = scale4(wtab[(round_ < rounds ? round_ : rounds - 1) * WN_CK + ci_x], own);
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(W4_NT) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                     const float2 q0 = *reinterpret_cast<const float2 *>(post.res + oo), q1 = *reinterpret_cast<const float2 *>(post.res + oo + 4);
                     r0.x += q0.x, r0.y += q0.y, r1.x += q1.x, r1.y += q1.y;
                 }
-                if (post.relu) r0.x = relu_keep_nan(r0.x), r0.y = relu_keep_nan(r0.y), r1.x = relu_keep_nan(r1.x), r1.y = relu_keep_nan(r1.y);
+                if (post.relu) r0.x = relu_nan(r0.x), r0.y = relu_nan(r0.y), r1.x = relu_nan(r1.x), r1.y = relu_nan(r1.y);
             }
             *reinterpret_cast<float2 *>(y + oo) = r0;
             *reinterpret_cast<float2 *>(y + oo + 4) = r1;
@@ -465,7 +465,7 @@ __global__ __launch_bounds__(PcGeo<MAP>::NT) __attribute__((amdgpu_waves_per_eu(
             return train_bn_apply4(v, wtab + 3 * ((round_ < rounds ? round_ : rounds - 1) * G::CK + ci_p));
         if constexpr (PRE == 4)  // train-mode BatchNorm + ReLU BACKWARD: v = dy, m = the BatchNorm's input
             return train_bn_bwd_apply4(v, m, wtab + 7 * ((round_ < rounds ? round_ : rounds - 1) * G::CK + ci_p));
-        if constexpr (PRE == 2) v = sum4(v, a);
+        if constexpr (PRE == 2) v = add4(v, a);
         v = mask4(v, m);
         if (pre_store && round_ < rounds) *reinterpret_cast<float4 *>((pre.store + round_ * xstep) + xo) = v;
         return scale4(wtab[(round_ < rounds ? round_ : rounds - 1) * G::CK + ci_p], v);
@@ -697,7 +697,7 @@ __global__ __launch_bounds__(PcGeo<MAP>::NT) __attribute__((amdgpu_waves_per_eu(
                 if constexpr (POST) {
                     if (post.mean) r0.x = post_apply(r0.x, pk), r0.y = post_apply(r0.y, pk), r1.x = post_apply(r1.x, pk), r1.y = post_apply(r1.y, pk);
                     if (post.res) r0.x += q0[nb].x, r0.y += q0[nb].y, r1.x += q1[nb].x, r1.y += q1[nb].y;
-                    if (post.relu) r0.x = relu_keep_nan(r0.x), r0.y = relu_keep_nan(r0.y), r1.x = relu_keep_nan(r1.x), r1.y = relu_keep_nan(r1.y);
+                    if (post.relu) r0.x = relu_nan(r0.x), r0.y = relu_nan(r0.y), r1.x = relu_nan(r1.x), r1.y = relu_nan(r1.y);
                 }
                 *reinterpret_cast<float2 *>(y + oo) = r0;
                 *reinterpret_cast<float2 *>(y + oo + MAP) = r1;
