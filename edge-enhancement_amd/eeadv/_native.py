@@ -62,6 +62,12 @@ SIGNATURES = {
     "ee_apgd_book_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
     # x, g, x_best, g_best, x_best_adv, flags, counter, B, per_sample, stream
     "ee_apgd_select_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_p],
+    # x_best, x_new, x0, seed, B, C, H, W, eps, stream
+    "ee_sqatk_init_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
+    # logits, labels, B, K, margin_out, margin_min, queries, flags, counter, stream
+    "ee_sqatk_margin_f32": [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    # x_best, x_new, x0, flags, margin_min, counter, sizes, n_sizes, seed, B, C, H, W, eps, stream
+    "ee_sqatk_step_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
     "ee_add_square_fwd_f32": [c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_add_square_bwd_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_square_draw_f32": [c_p, c_l, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],
@@ -165,6 +171,7 @@ _RESTYPE = {"ee_strerror": ctypes.c_char_p, "ee_device_name": ctypes.c_char_p, "
  K_HFS_SQ_FWD, K_HFS_SQ_BWD, K_SQUARE_DRAW) = range(14)
 K_WINO, K_CONV3S2_FWD, K_CONV3S2_BWD, K_WINO_FUSED = 18, 19, 20, 21  # 14 - 17: the direct 3x3 kernels removed in round 3
 K_BATCH_AUG = 22
+K_SQATK_INIT, K_SQATK_MARGIN, K_SQATK_STEP = 23, 24, 25
 
 
 class EEError(RuntimeError):

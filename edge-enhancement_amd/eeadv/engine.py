@@ -15,7 +15,7 @@ import weakref
 
 import torch
 
-from . import ops, runtime
+from . import ops, runtime, sqatk
 from .functional import attack_forward, input_grad_only, refresh_dense_weights
 
 CE_SUM, CE_MEAN, KL, SOFTCE = "ce_sum", "ce_mean", "kl", "softce"
@@ -397,3 +397,173 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
     for _ in range(n_iter // chunk):
         gs.graph.replay()
     return gs.run.result()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Square attack (Andriushchenko et al. 2020; Linf, margin loss, p_init = 0.8 with the rescaled schedule, one run, no EOT): DESIGN.md section 12
+# ---------------------------------------------------------------------------------------------------------------------------------------
+SQUARE_CHECK_EVERY = 64  # iterations between two host reads of "is any sample still active" (the only host read of the attack)
+
+
+def square_schedule(n_queries, H, W):
+    """sizes[i] = the window edge of proposal i (0-based; n_queries - 1 proposals, the start being the first query):
+    clamp(int(round(sqrt(p(i) * H * W))), 1, min(H, W)) with Add_Square's p table at p_init = 0.8, i rescaled to a run of 10000."""
+    return sqatk.square_schedule(n_queries, H, W)
+
+
+def _signed64(seed):
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return seed - (1 << 64) if seed >= (1 << 63) else seed
+
+
+class _SquareRun:
+    """The device state of one Square attack (include/eeadv.h, "Square attack") and its pieces: `start` (the striped start and its forward,
+    once per attack), `iteration` (step, eval forward under no_grad, margin: what a captured graph replays) and `finish` (the commit of the
+    last accepted proposal).  No host read anywhere."""
+
+    def __init__(self, x0, y, n_queries, eps):
+        if x0.dim() != 4:
+            raise ValueError("the Square attack takes image batches [B,C,H,W], got shape %s" % (tuple(x0.shape),))
+        B, dev = x0.shape[0], x0.device
+        self.eps, self.n_queries = float(eps), int(n_queries)
+        self.x0, self.x_best, self.x_new = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
+        self.y = torch.empty(B, dtype=torch.int64, device=dev)
+        self.margin_out = torch.empty(B, dtype=torch.float32, device=dev)
+        self.margin_min = torch.empty(B, dtype=torch.float32, device=dev)
+        self.queries = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.flags = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.sizes = torch.tensor(square_schedule(n_queries, x0.shape[2], x0.shape[3]), dtype=torch.int32).to(dev)
+        self.trace = None
+
+    def load(self, x0, y, seed):
+        with torch.no_grad():
+            self.x0.copy_(x0)
+            self.y.copy_(y)
+            self.seed.copy_(torch.tensor([_signed64(seed)], dtype=torch.int64))  # in place: a captured graph holds this tensor's address
+
+    def _query(self, model):
+        with torch.no_grad():
+            z = model(self.x_new)
+        ops.sqatk_margin_(z.detach().float().contiguous(), self.y, self.margin_out, self.margin_min, self.queries, self.flags, self.counter)
+        if self.trace is not None:
+            self.trace.append({"margin": self.margin_out.clone(), "flags": self.flags.clone()})
+
+    def start(self, model):
+        with torch.no_grad():
+            self.margin_min.fill_(float("inf"))
+            self.queries.zero_()
+            self.flags.zero_()
+            self.counter.fill_(-1)  # the start's margin launch brings it to proposal 0
+        ops.sqatk_init_(self.x_best, self.x_new, self.x0, self.seed, self.eps)
+        self._query(model)
+
+    def iteration(self, model):
+        ops.sqatk_step_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, self.sizes, self.seed, self.eps)
+        self._query(model)
+
+    def finish(self):
+        """The flags of the last margin launch are still to be committed: a step without a table commits and proposes nothing."""
+        ops.sqatk_step_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, None, self.seed, self.eps)
+
+    def any_active(self):
+        return bool((~(self.margin_min <= 0)).any().item())
+
+    def result(self):
+        with torch.no_grad():
+            robust = self.margin_min > 0
+            keep = robust.view(-1, 1, 1, 1)
+            return torch.where(keep, self.x0, self.x_best), robust, self.queries.clone()
+
+
+class _GraphedSquare:
+    """`iters` consecutive Square iterations captured into one graph over the static buffers of a _SquareRun."""
+
+    def __init__(self, model, run, iters):
+        self.run, self.iters, self.model, self.graph = run, iters, weakref.ref(model), None
+
+    def _body(self, model):
+        for _ in range(self.iters):
+            self.run.iteration(model)
+
+    def capture(self, model):
+        runtime.draw_state(self.run.x0.device)
+        self.run.start(model)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):  # warm-up outside capture, as _GraphedStep.capture; the state it advances is rebuilt by the next start()
+                self._body(model)
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        from .models import deferred_bn_counters
+        with torch.cuda.graph(self.graph, capture_error_mode=runtime.capture_mode()):
+            with deferred_bn_counters():
+                self._body(model)
+
+
+def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=None, early_exit=True):
+    """One Square attack of at most n_queries forwards per sample inside the eps-ball around x0 [B,C,H,W].  Returns (x_adv, robust,
+    queries): x0 with the fooled rows (margin_min <= 0) replaced by their fooling point, robust [B] bool (margin_min > 0), and the number
+    of forwards each sample was active for (int32 [B]).  `seed` keys the draws (None: a ticket from torch's generator of the device, so
+    torch.manual_seed governs it).  The model's mode is left as the caller set it.  Eager, or - under EEADV_GRAPH=1 / use_graph - replayed
+    from a captured graph of MAX_ITERS_PER_GRAPH iterations, the remainder running eagerly; both give the same bits.  early_exit: the
+    host reads "is any sample still active" once per SQUARE_CHECK_EVERY iterations and stops when none is - fooled samples are frozen, so
+    the result is the same bits either way.  `trace` (a list, eager only) receives {"margin", "flags"} of every forward, the start's
+    first."""
+    model = _unwrap(model)
+    x0 = x0.detach().contiguous()
+    n_queries = int(n_queries)
+    if n_queries < 1:
+        raise ValueError("Square needs n_queries >= 1")
+    if use_graph is None:
+        use_graph = graphs_enabled() and trace is None
+    if use_graph and trace is not None:
+        raise ValueError("the Square trace is recorded by eager runs only")
+    if seed is None:
+        # the generator's seed is the same for every attack of a process, its offset is what the ticket advances: both go into the key
+        s, off = runtime.philox_ticket(x0.device, 4)
+        seed = (s + (off + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    n_prop = n_queries - 1
+    chunk = min(n_prop, MAX_ITERS_PER_GRAPH)
+    if x0.shape[0] == 0:
+        return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=torch.int32, device=x0.device)
+    if not use_graph or chunk == 0:
+        run, gs = _SquareRun(x0, y, n_queries, eps), None
+    else:
+        key = ("square", id(model), model.training, tuple(x0.shape), n_queries, float(eps), x0.device.index, chunk)
+        gs = _GRAPHS.get(key)
+        if gs is not None and gs.model() is not model:
+            gs = None
+        if gs is None:
+            run = _SquareRun(x0, y, n_queries, eps)
+            run.load(x0, y, seed)
+            gs = _GraphedSquare(model, run, chunk)
+            saved = {}
+            if model.training:  # as pgd_loop: the start and warm-up passes before the capture are extra train-mode forwards
+                saved = {k: v.clone() for k, v in model.state_dict().items() if "running_" in k or "num_batches" in k}
+            gs.capture(model)
+            if saved:
+                live = model.state_dict()
+                for k, v in saved.items():
+                    live[k].data.copy_(v)
+            _GRAPHS[key] = gs
+        run = gs.run
+        refresh_dense_weights()
+    run.trace = trace
+    run.load(x0, y, seed)
+    run.start(model)
+    done = 0
+    while done < n_prop:
+        if early_exit and done and done % SQUARE_CHECK_EVERY == 0 and not run.any_active():
+            break
+        if gs is not None and n_prop - done >= chunk:
+            gs.graph.replay()
+            done += chunk
+        else:
+            run.iteration(model)
+            done += 1
+    run.finish()
+    run.trace = None
+    return run.result()

@@ -467,6 +467,43 @@ def apgd_select_(x, g, x_best, g_best, x_best_adv, flags, counter):
     return x
 
 
+# ---- Square attack (ee_sqatk.hip) ------------------------------------------------------------------------------------
+def _sqatk_images(x_best, x_new, x0):
+    if x_best.dim() != 4:
+        raise ValueError("the Square attack takes image batches [B,C,H,W], got shape %s" % (tuple(x_best.shape),))
+    return (_chk(x_best, torch.float32, "x_best"), _chk(x_new, torch.float32, "x_new", x_best.shape), _chk(x0, torch.float32, "x0", x_best.shape))
+
+
+def sqatk_init_(x_best, x_new, x0, seed, eps):
+    """The striped start into x_best and x_new [B,C,H,W]; seed int64 [1] on the device."""
+    B, C, H, W = x_best.shape
+    pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
+    N.check(N.lib.ee_sqatk_init_f32(pb, pn, p0, _chk(seed, torch.int64, "seed", (1,)), B, C, H, W, eps, _stream()), "ee_sqatk_init_f32")
+    return x_best
+
+
+def sqatk_margin_(logits, labels, margin_out, margin_min, queries, flags, counter):
+    """margin_out <- z_y - max_{j != y} z_j of logits [B,K]; margin_min, queries [B] updated in place, flags [B] <- accept; counter += 1."""
+    B, K = logits.shape
+    N.check(N.lib.ee_sqatk_margin_f32(_chk(logits, torch.float32, "logits"), _chk(labels, torch.int64, "labels", (B,)), B, K,
+                                      _chk(margin_out, torch.float32, "margin_out", (B,)), _chk(margin_min, torch.float32, "margin_min", (B,)),
+                                      _chk(queries, torch.int32, "queries", (B,)), _chk(flags, torch.int32, "flags", (B,)),
+                                      _chk(counter, torch.int32, "counter", (1,)), _stream()), "ee_sqatk_margin_f32")
+    return flags
+
+
+def sqatk_step_(x_best, x_new, x0, flags, margin_min, counter, sizes, seed, eps):
+    """Commit under flags [B], then proposal counter[0] with the window edge sizes[counter[0]] (sizes None or empty: commit only)."""
+    B, C, H, W = x_best.shape
+    pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
+    n_sizes = 0 if sizes is None else int(sizes.numel())
+    ps = _chk(sizes, torch.int32, "sizes", (n_sizes,)) if n_sizes else None
+    N.check(N.lib.ee_sqatk_step_f32(pb, pn, p0, _chk(flags, torch.int32, "flags", (B,)), _chk(margin_min, torch.float32, "margin_min", (B,)),
+                                    _chk(counter, torch.int32, "counter", (1,)), ps, n_sizes, _chk(seed, torch.int64, "seed", (1,)), B, C, H, W,
+                                    eps, _stream()), "ee_sqatk_step_f32")
+    return x_new
+
+
 # ---- Add_Square ------------------------------------------------------------------------------------------------------
 def add_square_fwd(x, eps, stripe, sq_sign, sq_pos, sq_size):
     B, C, H, W = x.shape

@@ -696,10 +696,27 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
                 return xt
             x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
         return x_adv
+    if args.attack_method in SQUARE_METHODS:
+        # Square (black-box, args.square_queries forwards per sample at most), alone or after APGD-CE and APGD-T: flags ANDed, the first
+        # fooling point kept
+        if targeted:
+            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+        shape = (-1,) + (1,) * (input.dim() - 1)
+        x_adv, robust = None, None
+        if args.attack_method == 'APGD+Square':
+            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce')
+            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class)
+            x_adv = torch.where((robust & ~rt).view(shape), xt, x_adv)
+            robust = robust & rt
+        xs, rs, _ = A.Square(model, args, input, target, int(getattr(args, 'square_queries', 5000)))
+        if x_adv is None:
+            return xs
+        return torch.where((robust & ~rs).view(shape), xs, x_adv)
     raise NotImplementedError
 
 
 APGD_METHODS = ('APGD-CE', 'APGD-T', 'APGD')
+SQUARE_METHODS = ('Square', 'APGD+Square')
 
 
 def validate_batch(model, criterion, args, input, target, device, num_steps, step_size, n_class):

@@ -10,6 +10,7 @@ deliberate and documented in DESIGN.md:
   * random starts are drawn on the device (Philox inside the init kernel) unless `noise=` is injected -
     device and host generators differ anyway, parity tests inject the noise;
   * CWLinfAttack(target=None) works (the reference raises TypeError at :152, SURVEY a17);
+  * APGD / APGD_T and Square are additions: the reference runs them through the `autoattack` package (DESIGN.md sections 11, 12);
   * CPU tensors are refused unless eeadv.runtime.allow_cpu_plumbing(True) was called (--no-cuda drivers).
 """
 import numpy as np
@@ -115,8 +116,8 @@ def targeted_PGD_trick(model, args, inputs, labels, num_steps, step_size, nclass
 
 # ---------------------------------------------------------------------------------------------------------
 # APGD-CE and APGD-T (Croce & Hein 2020): the two gradient attacks of AutoAttack's `standard` version.  Not in the
-# reference's utils/attacks.py - its drivers call the `autoattack` package for them.  FAB-T and Square, the `rand` / EOT
-# versions, the L2 / L1 norms and restarts are NOT here, so the result is not an AutoAttack number.
+# reference's utils/attacks.py - its drivers call the `autoattack` package for them.  Square, the black-box member, follows below; FAB-T,
+# the `rand` / EOT versions, the L2 / L1 norms and restarts are NOT here, so the result is not an AutoAttack number.
 # ---------------------------------------------------------------------------------------------------------
 def _apgd_row_losses(z, y, loss, t=None):
     """Row losses [B] of logits [B,K] in z's dtype; classes ordered by value descending, ties to the lower index."""
@@ -237,6 +238,80 @@ def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, 
         x_adv = torch.where((robust & ~rb).view(shape), xa, x_adv)
         robust = robust & rb
     return x_adv, robust
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Square (Andriushchenko et al. 2020, Linf): the black-box member of AutoAttack's `standard` version - score-based random search on the
+# margin loss, p_init = 0.8 with the rescaled schedule, one run, no EOT.  Built from the published description;
+# every sample draws a window of its own (the paper's form), so a sample's trajectory does not depend on who shares its batch.
+# ---------------------------------------------------------------------------------------------------------
+def _square_margin(z, y):
+    """margin [B] = z_y - max_{j != y} z_j in z's dtype; NaN for a row with a NaN logit or a label outside [0, K)."""
+    K = z.shape[1]
+    valid = (y >= 0) & (y < K)
+    yc = y.clamp(0, K - 1)
+    zy = z.gather(1, yc.view(-1, 1)).squeeze(1)
+    other = z.masked_fill(F.one_hot(yc, K).bool(), -_INF).max(dim=1)[0]
+    bad = torch.isnan(z).any(dim=1) | ~valid
+    return torch.where(bad, torch.full_like(zy, float("nan")), zy - other)
+
+
+def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early_exit=True):
+    """Plumbing path for CPU tensors (opt-in): the iteration of engine.square_loop in plain torch ops, in the input's dtype, with the
+    kernels' draws (eeadv.sqatk: the same Philox key, counters and stream ids).  `ids` [B]: the batch index each sample draws under
+    (default 0 .. B-1).  Returns (x_best, margin_min, queries); `trace`, a list, receives {"margin", "flags"} of every forward."""
+    from eeadv import sqatk
+    B, C, H, W = x0.shape
+    ids = np.arange(B) if ids is None else np.asarray(ids)
+    sizes = engine.square_schedule(n_queries, H, W)
+    inf = torch.full((B,), _INF, dtype=x0.dtype, device=x0.device)
+    state = {"margin_min": inf, "queries": torch.zeros(B, dtype=torch.int32, device=x0.device)}
+
+    def query(x_new, x_best):
+        with torch.no_grad():
+            m = _square_margin(model(x_new), y)
+        active = ~(state["margin_min"] <= 0)
+        accept = active & (m < state["margin_min"])
+        state["margin_min"] = torch.where(accept, m, state["margin_min"])
+        state["queries"] = state["queries"] + active.to(torch.int32)
+        if trace is not None:
+            trace.append({"margin": m.clone(), "flags": accept.clone()})
+        return torch.where(accept.view(-1, 1, 1, 1), x_new, x_best)
+
+    stripe = torch.from_numpy(sqatk.stripes(seed, ids, C, W)).to(x0.dtype).to(x0.device)
+    x_best = torch.clamp(x0 + eps * stripe.view(B, C, 1, W), 0, 1)
+    x_best = query(x_best, x_best)
+    hh, ww, cc = torch.arange(H).view(1, H), torch.arange(W).view(1, W), torch.arange(C).view(1, C)
+    for i, s in enumerate(sizes):
+        active = ~(state["margin_min"] <= 0)
+        if early_exit and not bool(active.any()):
+            break
+        vh, vw, bits = (torch.from_numpy(a).view(B, 1) for a in sqatk.windows(seed, i, ids, H, W, s))
+        inside = ((hh >= vh) & (hh < vh + s)).view(B, 1, H, 1) & ((ww >= vw) & (ww < vw + s)).view(B, 1, 1, W)
+        up = torch.tensor(2.0 * eps, dtype=x0.dtype)  # a 0-dim tensor of the input's dtype: two Python scalars would make float32 of it
+        sign = torch.where(((bits >> cc) & 1).bool(), up, -up).view(B, C, 1, 1)
+        delta = torch.where(inside, sign, torch.zeros((), dtype=x0.dtype)).to(x0.device)
+        prop = torch.clamp(torch.min(torch.max(x_best + delta, x0 - eps), x0 + eps), 0, 1)
+        x_new = torch.where(active.view(-1, 1, 1, 1), prop, x_best)
+        x_best = query(x_new, x_best)
+    return x_best, state["margin_min"], state["queries"]
+
+
+def Square(model, args, inputs, targets, n_queries=5000, seed=None):
+    """One Square attack (Linf, eps = args.epsilon, at most n_queries forwards per sample).  Returns (x_adv, robust, queries): the inputs
+    with every fooled sample (margin z_y - max_{j != y} z_j <= 0 at some query) replaced by its fooling point, the [B] bool flags of the
+    samples whose margin stayed positive, and the number of forwards each sample was active for.  `seed` keys the counter-based draws;
+    None takes it from torch's generator (torch.manual_seed governs it).  The model runs in the mode the caller left it in; a defence that
+    redraws at every forward (Add_Square) makes the margins noisy, and a lucky low margin sticks - what the non-EOT version does."""
+    x0 = inputs.detach()
+    eps = float(args.epsilon)
+    if runtime.require_device(x0, "Square"):
+        return engine.square_loop(model, x0, targets, n_queries, eps, seed)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    x_best, margin_min, queries = _square_host(model, x0, targets, n_queries, eps, seed)
+    robust = margin_min > 0
+    return torch.where(robust.view(-1, 1, 1, 1), x0, x_best), robust, queries
 
 
 class LabelSmoothLoss(torch.nn.Module):

@@ -17,7 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from eeadv import _native  # noqa: F401  (fails loudly at import when libeeadv.so is missing)
-from eeadv import functional as EF, hfs as _hfs, ops, runtime
+from eeadv import functional as EF, hfs as _hfs, ops, runtime, sqatk
 
 
 # function to suppress high freqency components (core.py:15-55)
@@ -309,30 +309,8 @@ class Add_Square(nn.Module):
         return t.long()
 
     def p_selection(self, it):
-        """ schedule to decrease the parameter p (core.py:607-634)"""
-        if self.rescale_schedule:
-            it = int(it / self.n_queries * 10000)
-        if 10 < it <= 50:
-            p = self.p_init / 2
-        elif 50 < it <= 200:
-            p = self.p_init / 4
-        elif 200 < it <= 500:
-            p = self.p_init / 8
-        elif 500 < it <= 1000:
-            p = self.p_init / 16
-        elif 1000 < it <= 2000:
-            p = self.p_init / 32
-        elif 2000 < it <= 4000:
-            p = self.p_init / 64
-        elif 4000 < it <= 6000:
-            p = self.p_init / 128
-        elif 6000 < it <= 8000:
-            p = self.p_init / 256
-        elif 8000 < it:
-            p = self.p_init / 512
-        else:
-            p = self.p_init
-        return p
+        """ schedule to decrease the parameter p (core.py:607-634); the table is eeadv.sqatk.p_selection, shared with the Square attack"""
+        return sqatk.p_selection(it, self.p_init, self.n_queries if self.rescale_schedule else None)
 
     def square_sizes(self, device):
         """s of core.py:644 for every query: deterministic, built once per device."""

@@ -263,6 +263,40 @@ int ee_apgd_book_f32(const float *loss, const int *pred, float *fstate, int *ist
 int ee_apgd_select_f32(float *x, float *g, float *x_best, float *g_best, float *x_best_adv, const int *flags, int *counter, int B,
                        int64_t per_sample, void *stream);
 
+/* ---- Square attack (Andriushchenko et al. 2020, Linf, score-based; the schedule of AutoAttack's `standard` version), ee_sqatk.hip ----
+ * The ATTACK - not the Add_Square defence (ee_add_square_*, ee_square_draw_f32).  State of one attack on B images [C,H,W], all in
+ * device memory:
+ *   x0, x_best, x_new  float [B,C,H,W]   the clean images, the best point so far, the proposal the classifier sees
+ *   margin_out float [B]  z_y - max_{j != y} z_j of the last forward      margin_min float [B]  the smallest accepted margin (+inf at first)
+ *   queries    int   [B]  forwards the sample was active for              flags      int   [B]  1: the last proposal was accepted
+ *   counter    int   [1]  index of the next proposal (0-based)            sizes      int   [n_sizes]  window edge of every proposal
+ *   seed       int64 [1]  the Philox key of this attack
+ * A sample is fooled once margin_min <= 0 and is frozen from then on.  A query is step -> classifier forward on x_new -> margin; no
+ * argument changes from one query to the next, so a captured graph of one query replays for all of them.  Randomness is
+ * counter-based: r = Philox4x32-10(seed)(ctr, stream_id) with stream_id 11 for windows, ctr = (proposal << 32) | b, and stream_id 12 for
+ * the start's stripes, ctr = ((b*C + c) << 32) | (w >> 7): bit (w & 127) of the 128-bit r (x = bits 0..31, y, z, w follow). */
+
+/* The striped start: x_best = x_new = clamp(x0 + (bit ? eps : -eps), 0, 1), one bit per (b, c, w).  C > 32: EE_ERR_UNSUPPORTED. */
+int ee_sqatk_init_f32(float *x_best, float *x_new, const float *x0, const int64_t *seed, int B, int C, int H, int W, float eps,
+                      void *stream);
+
+/* Per row of logits [B,K], K >= 2, one wavefront per row: margin_out[b] = z_y - max_{j != y} z_j (one fp32 difference: exact); NaN when
+ * any logit of the row is NaN or the label is outside [0, K).  If the sample is not fooled (not margin_min <= 0): queries += 1 and the
+ * proposal is accepted iff margin < margin_min (never for NaN): margin_min = margin, flags = 1; otherwise flags = 0.  Then counter[0] += 1
+ * (this launch never reads it).  B == 0 launches nothing and leaves the counter. */
+int ee_sqatk_margin_f32(const float *logits, const int64_t *labels, int B, int K, float *margin_out, float *margin_min, int *queries,
+                        int *flags, int *counter, void *stream);
+
+/* Commit and propose, in place.  Per sample: flags[b]: x_best = x_new.  Then, if the sample is not fooled and i = counter[0] is inside
+ * [0, n_sizes): with s = sizes[i] (1 <= s <= min(H, W), else no proposal), r = the window draw, vh = umulhi(r.x, H - s + 1),
+ * vw = umulhi(r.y, W - s + 1), delta = +-2 eps by bit c of r.z inside rows vh .. vh+s-1, columns vw .. vw+s-1 and 0 outside,
+ *     x_new = clamp(min(max(x_best + delta, x0 - eps), x0 + eps), 0, 1).
+ * A fooled sample keeps x_new = x_best (after its commit nothing of it is touched again); a counter outside the table (or n_sizes = 0,
+ * sizes then nullable) commits only.  128-bit accesses when the three tensors are 16-byte aligned; W and C*H*W need not be multiples
+ * of 4.  12 B of HBM traffic per element of a sample whose last proposal was rejected.  C > 32: EE_ERR_UNSUPPORTED. */
+int ee_sqatk_step_f32(float *x_best, float *x_new, const float *x0, const int *flags, const float *margin_min, const int *counter,
+                      const int *sizes, int n_sizes, const int64_t *seed, int B, int C, int H, int W, float eps, void *stream);
+
 /* CannyFilter_BPDA (utils/core.py:386-505; AWP configs): no alpha mask, NMS by multiplication, thresholds through
  * To_compare (core.py:329-358), hysteresis through To_eq (core.py:361-382).  thresholds given, hysteresis=True.
  *   forward: edge, thin (the thinned magnitude), t2 (the {0, .5, 1} threshold map) [B,1,H,W]; thin / t2 feed the backward.
@@ -746,7 +780,10 @@ int ee_batch_aug_u8_f32(const uint8_t *data, const int64_t *labels, const int32_
 #define EE_K_WINO_FUSED 21  /* ee_wino3x3_bn_eval_*, ee_wino3x3_stats_f32, ee_wino3x3_bn_train_*, ee_wino3x3_bwd_sums_f32: the same products with the
                              * BatchNorm work of the layer folded into the staging / output stage; work = the convolution's flops only */
 #define EE_K_BATCH_AUG 22  /* ee_batch_aug_u8_f32 */
-#define EE_K_COUNT 23
+#define EE_K_SQATK_INIT 23   /* ee_sqatk_init_f32 */
+#define EE_K_SQATK_MARGIN 24 /* ee_sqatk_margin_f32 */
+#define EE_K_SQATK_STEP 25   /* ee_sqatk_step_f32 */
+#define EE_K_COUNT 26
 int ee_prof_enable(int on);
 /* records one empty start/stop bracket on `stream` (family EE_K_EMPTY): callers subtract its mean from the other
  * families' means, because a HIP event pair costs ~4-5 us on gfx950 - comparable to the kernels being timed */
