@@ -128,9 +128,9 @@ def validate(val_loader, model, criterion, args, device, num_steps, step_size, l
 def main(argv=None):
     """experiments_tiny_awp.py:60-223"""
     args = parse_config_file(make_parser().parse_args(argv))
-    if args.attack_method != 'PGD' and args.attack_method not in trainer.APGD_METHODS + trainer.SQUARE_METHODS:
+    if args.attack_method != 'PGD' and args.attack_method not in trainer.APGD_METHODS + trainer.SQUARE_METHODS + trainer.FAB_METHODS:
         raise SystemExit("--attack_method %s: %s; validation runs PGD" % (args.attack_method, AA_UNAVAILABLE) if args.attack_method == 'AA'
-                         else "--attack_method %s: the AWP driver validates with PGD, APGD-CE, APGD-T, APGD, Square or APGD+Square" % args.attack_method)
+                         else "--attack_method %s: the AWP driver validates with PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T or APGD+FAB+Square" % args.attack_method)
     driver.data_source(args.data, SPEC)  # an unusable --data fails here, before a model is built
     args.setdefault("cize", 64)
     args.num_classes = SPEC["num_classes"]

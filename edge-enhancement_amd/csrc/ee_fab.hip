@@ -1,0 +1,458 @@
+// ee_fab.hip - the hot path of FAB-T (Croce & Hein 2020, "Minimally distorted adversarial examples with a fast adaptive boundary attack";
+// Linf, targeted, the constants of AutoAttack's "standard" version: eta = 1.05, beta = 0.9, alpha_max = 0.1, one run, no random start).
+// One iteration is four launches around two forwards and one backward of the classifier:
+//     ee_fab_diff_f32       logits -> df = z_t - z_y, its logit gradient, pred        (one wavefront per row, as ee_apgd_loss_f32)
+//     ee_fab_proj_linf_f32  (x, x0, w, df) -> lambda, sign, ||delta||_inf of the two box-constrained Linf projections of a sample
+//                           (one workgroup per problem, 2B problems; scalars only - the two deltas never reach memory)
+//     ee_fab_step_f32       rebuilds delta1 / delta2 per element from those scalars, mixes, writes the new x   (element-wise, 128-bit accesses)
+//     ee_fab_commit_f32     after the second forward: argmax, ||x - x0||_inf, adv / res update, the shrink step, counter += 1
+//                           (one workgroup per sample)
+// Nothing here depends on a host value that changes from iteration to iteration, so one captured graph serves every iteration.  No launch
+// writes a per-sample scalar that another workgroup of the same launch reads: a projection problem and a commit sample each belong to one
+// workgroup, step only reads the scalars, and commit is the one place that advances the counter (nothing reads it there).
+//
+// The projection.  For v = s w (s the sign of c), c' = |c| and rooms r_i (the distance of p_i to the bound v_i pushes it to),
+// g(lambda) = sum_i |v_i| min(lambda, r_i) is continuous, piecewise linear and non-decreasing; lambda is the smallest value with
+// g(lambda) = c'.  The kernel finds T, the largest float with g(T) < c', by 31 steps over the bit pattern of non-negative floats (one
+// workgroup-wide sum each), and then solves the segment that contains lambda in closed form: lambda = (c' - sum_{r_i <= T} |v_i| r_i) /
+// sum_{r_i > T} |v_i|.  No breakpoint lies strictly between T and lambda, so this IS the segment solve of the sort-based formulation - not a
+// bisection stopped at a tolerance - and every loop has a trip count fixed by D and the launch shape.  All sums are double (products of two
+// floats are exact there) in one fixed order - thread t takes the float4 groups t, t + 512, ... in turn, wavefronts are reduced by
+// xor-shuffles, the eight partial sums are added in index order - which the resident path (a problem's |w_i| and r_i stay in registers across
+// all passes, D <= 12288) and the streaming path (re-read through L2) share, so the two return the same bits.
+#include <math.h>
+
+#include "ee_common.hpp"
+
+namespace {
+
+using namespace ee;
+
+constexpr int kRowsPerBlock = kBlock / kWave;
+constexpr int kNone = 0x7fffffff;
+constexpr float kEta = 1.05f, kBeta = 0.9f, kAlphaMax = 0.1f;
+
+constexpr int kProjBlock = 512;                               // 8 wavefronts per problem
+constexpr int kProjWaves = kProjBlock / kWave;
+constexpr int kProjVecs = 6;                                  // float4 groups per thread the resident path keeps
+constexpr int kProjResident = kProjBlock * kProjVecs * 4;     // 12288 = 3*64*64
+constexpr int kCommitBlock = 512;
+constexpr int kCommitWaves = kCommitBlock / kWave;
+
+// the order of ee_topk_i64: by value descending, ties to the lower index, NaN above everything
+__device__ __forceinline__ bool better(float va, int ia, float vb, int ib) {
+    const bool na = va != va, nb = vb != vb;
+    if (na != nb) return na;
+    if (!na && va != vb) return va > vb;
+    return ia < ib;
+}
+
+// the first class of one row in that order (every lane of the wavefront gets it); nan: the row holds a NaN
+__device__ __forceinline__ int row_first(const float *__restrict__ z, int K, int lane, bool &nan) {
+    float bv = 0.0f;
+    int bi = kNone, any = 0;
+    for (int c = lane; c < K; c += kWave) {
+        const float v = z[c];
+        any |= (v != v);
+        if (bi == kNone || better(v, c, bv, bi)) {
+            bv = v;
+            bi = c;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        any |= __shfl_xor(any, off);
+        if (oi != kNone && (bi == kNone || better(ov, oi, bv, bi))) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    nan = any != 0;
+    return bi;
+}
+
+// the room of a coordinate at p that v pushes down (v > 0: to 0) or up (v < 0: to 1); 0 where v is 0 or NaN.  Never negative.
+__device__ __forceinline__ float room(float v, float p) { return fmaxf(v > 0.0f ? p : (v < 0.0f ? 1.0f - p : 0.0f), 0.0f); }
+
+// ---- df, its logit gradient, pred ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kBlock) void diff_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels,
+                                                      const int64_t *__restrict__ targets, int B, int K, float *__restrict__ df,
+                                                      float *__restrict__ dlogits, int *__restrict__ pred) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int row = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
+    if (row >= B) return;
+    const float *z = logits + static_cast<size_t>(row) * K;
+    float *d = dlogits + static_cast<size_t>(row) * K;
+    const int64_t y = labels[row], t = targets[row];
+    const bool valid = y >= 0 && y < K && t >= 0 && t < K;  // a label or target outside the row is never dereferenced
+    bool nan;
+    const int first = row_first(z, K, lane, nan);
+    for (int k = lane; k < K; k += kWave) d[k] = valid ? (k == t ? 1.0f : 0.0f) - (k == y ? 1.0f : 0.0f) : 0.0f;
+    if (lane == 0) {
+        df[row] = valid ? z[t] - z[y] : NAN;
+        pred[row] = first;
+    }
+}
+
+// ---- the projection ------------------------------------------------------------------------------------------------------------------
+struct Reducer {
+    double *sh;  // [2][kProjWaves]: consecutive reductions alternate halves, so one barrier per reduction is enough
+    int phase;
+    __device__ __forceinline__ double finish(double v) {
+        double *buf = sh + phase * kProjWaves;
+        phase ^= 1;
+        if ((threadIdx.x & (kWave - 1)) == 0) buf[threadIdx.x >> 6] = v;
+        __syncthreads();
+        double r = buf[0];
+#pragma unroll
+        for (int i = 1; i < kProjWaves; ++i) r += buf[i];
+        return r;
+    }
+    __device__ __forceinline__ double sum(double v) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        return finish(v);
+    }
+    __device__ __forceinline__ double max(double v) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+        double *buf = sh + phase * kProjWaves;
+        phase ^= 1;
+        if ((threadIdx.x & (kWave - 1)) == 0) buf[threadIdx.x >> 6] = v;
+        __syncthreads();
+        double r = buf[0];
+#pragma unroll
+        for (int i = 1; i < kProjWaves; ++i) r = fmax(r, buf[i]);
+        return r;
+    }
+};
+
+// four consecutive elements of a row from element e on; elements at or past D read as 0
+template <bool VEC>
+__device__ __forceinline__ void load4(const float *__restrict__ row, int64_t e, int64_t D, float (&o)[4]) {
+    if (VEC && e + 3 < D) {
+        const float4 v = *reinterpret_cast<const float4 *>(row + e);
+        o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = e + j < D ? row[e + j] : 0.0f;
+    }
+}
+
+// RES: groups 0 .. kProjVecs-1 of this thread live in a[] / r[] (zeros past D); otherwise every pass re-reads w and p.
+// The body sees (|w|, room) of every element of the thread in the same order on both paths.
+template <bool RES, bool VEC, class F>
+__device__ __forceinline__ void each_element(const float *__restrict__ w, const float *__restrict__ p, int64_t D, int groups, float s,
+                                             const float (&a)[kProjVecs * 4], const float (&r)[kProjVecs * 4], F body) {
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kProjVecs * 4; ++k) body(a[k], r[k]);
+    } else {
+        for (int g = 0; g < groups; ++g) {
+            const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+            float wv[4], pv[4];
+            load4<VEC>(w, e, D, wv);
+            load4<VEC>(p, e, D, pv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) body(fabsf(wv[j]), room(s * wv[j], pv[j]));
+        }
+    }
+}
+
+template <bool RES, bool VEC>
+__global__ __launch_bounds__(kProjBlock) void proj_kernel(const float *__restrict__ x, const float *__restrict__ x0, const float *__restrict__ w,
+                                                          const float *__restrict__ df, int B, int64_t D, float *__restrict__ out) {
+    __shared__ double sh[2 * kProjWaves];
+    Reducer red{sh, 0};
+    const int q = blockIdx.x, b = q < B ? q : q - B;
+    const bool second = q >= B;  // problem B + b projects x0, problem b projects x
+    const float *xr = x + static_cast<int64_t>(b) * D, *x0r = x0 + static_cast<int64_t>(b) * D, *wr = w + static_cast<int64_t>(b) * D;
+    const float *pr = second ? x0r : xr;
+    const int groups = static_cast<int>((D + 4 * kProjBlock - 1) / (4 * kProjBlock));  // float4 groups per thread; <= kProjVecs when RES
+    float *lam_out = out + q, *sgn_out = out + 2 * static_cast<int64_t>(B) + q, *nrm_out = out + 4 * static_cast<int64_t>(B) + q;
+
+    // pass 1: sum |w_i| and sum w_i (x0_i - x_i); the resident path keeps w in a[] and the point in r[]
+    float a[kProjVecs * 4], r[kProjVecs * 4];
+    double sabs = 0.0, dot = 0.0;
+    if (RES) {
+#pragma unroll
+        for (int g = 0; g < kProjVecs; ++g) {
+            const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+            float wv[4], xv[4], ov[4];
+            load4<VEC>(wr, e, D, wv);
+            load4<VEC>(xr, e, D, xv);
+            load4<VEC>(x0r, e, D, ov);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                sabs += static_cast<double>(fabsf(wv[j]));
+                dot = fma(static_cast<double>(wv[j]), static_cast<double>(ov[j] - xv[j]), dot);
+                a[g * 4 + j] = wv[j];
+                r[g * 4 + j] = second ? ov[j] : xv[j];
+            }
+        }
+    } else {
+        for (int g = 0; g < groups; ++g) {
+            const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+            float wv[4], xv[4], ov[4];
+            load4<VEC>(wr, e, D, wv);
+            load4<VEC>(xr, e, D, xv);
+            load4<VEC>(x0r, e, D, ov);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                sabs += static_cast<double>(fabsf(wv[j]));
+                dot = fma(static_cast<double>(wv[j]), static_cast<double>(ov[j] - xv[j]), dot);
+            }
+        }
+    }
+    sabs = red.sum(sabs);
+    dot = red.sum(dot);
+    const float d = df[b];
+    // every decision below is taken on values all threads of the workgroup hold alike: the early exits are uniform
+    if (!(isfinite(d) && d != 0.0f && isfinite(sabs) && sabs > 0.0)) {  // no hyperplane to project onto: both problems of the sample rest
+        if (threadIdx.x == 0) *lam_out = 0.0f, *sgn_out = 0.0f, *nrm_out = 0.0f;
+        return;
+    }
+    const float c = second ? static_cast<float>(static_cast<double>(d) + dot) : d;
+    const float s = c >= 0.0f ? 1.0f : -1.0f;  // NaN cannot come here: d and dot are finite
+    const float cp = fabsf(c);
+    if (!isfinite(c) || cp == 0.0f) {  // c = 0: the point lies on the hyperplane
+        if (threadIdx.x == 0) *lam_out = 0.0f, *sgn_out = 1.0f, *nrm_out = 0.0f;
+        return;
+    }
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kProjVecs * 4; ++k) {
+            const float wv = a[k];
+            r[k] = room(s * wv, r[k]);
+            a[k] = fabsf(wv);
+        }
+    }
+    // g(inf) and the largest room among the coordinates that move
+    double ginf = 0.0, rm = 0.0;
+    each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
+        ginf = fma(static_cast<double>(av), static_cast<double>(rv), ginf);
+        if (av != 0.0f) rm = fmax(rm, static_cast<double>(rv));
+    });
+    ginf = red.sum(ginf);
+    const float rmax = static_cast<float>(red.max(rm));
+    const double cpd = static_cast<double>(cp);
+    if (cpd >= ginf) {  // infeasible inside the box: every coordinate that can move goes to its bound
+        if (threadIdx.x == 0) *lam_out = INFINITY, *sgn_out = s, *nrm_out = rmax;
+        return;
+    }
+    // T: the largest non-negative float with g(T) < c' (g(0) = 0 < c' holds, g(inf) < c' does not)
+    uint32_t T = 0u;
+    for (int bit = 30; bit >= 0; --bit) {
+        const uint32_t cand = T | (1u << bit);
+        const float tf = __uint_as_float(cand);
+        double part = 0.0;
+        each_element<RES, VEC>(wr, pr, D, groups, s, a, r,
+                               [&](float av, float rv) { part = fma(static_cast<double>(av), static_cast<double>(fminf(tf, rv)), part); });
+        if (red.sum(part) < cpd) T = cand;
+    }
+    // the segment (T, next breakpoint]: g(lambda) = S + lambda A there
+    const float tl = __uint_as_float(T);
+    double S = 0.0, A = 0.0;
+    each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
+        if (rv <= tl)
+            S = fma(static_cast<double>(av), static_cast<double>(rv), S);
+        else
+            A += static_cast<double>(av);
+    });
+    S = red.sum(S);
+    A = red.sum(A);
+    const float lam = A > 0.0 ? static_cast<float>((cpd - S) / A) : INFINITY;
+    if (threadIdx.x == 0) *lam_out = lam, *sgn_out = s, *nrm_out = fminf(lam, rmax);
+}
+
+// ---- the step ------------------------------------------------------------------------------------------------------------------------
+struct StepSample {
+    float l1, s1, l2, s2, alpha;
+};
+
+__device__ __forceinline__ StepSample step_sample(const float *__restrict__ scal, int64_t B, int64_t b) {
+    StepSample r;
+    r.l1 = scal[b], r.l2 = scal[B + b];
+    r.s1 = scal[2 * B + b], r.s2 = scal[3 * B + b];
+    const float a1 = fmaxf(scal[4 * B + b], 1e-8f), a2 = fmaxf(scal[5 * B + b], 1e-8f);
+    r.alpha = fminf(a1 / (a1 + a2), kAlphaMax);
+    return r;
+}
+
+__device__ __forceinline__ float step_op(float x, float x0, float w, const StepSample &sm) {
+    if (sm.s1 == 0.0f) return x;  // a sample without a hyperplane stays where it is
+    const float v1 = sm.s1 * w, v2 = sm.s2 * w;
+    const float d1 = -sgn(v1) * fminf(sm.l1, room(v1, x));
+    const float d2 = -sgn(v2) * fminf(sm.l2, room(v2, x0));
+    return tclamp((x + kEta * d1) * (1.0f - sm.alpha) + (x0 + kEta * d2) * sm.alpha, 0.0f, 1.0f);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void step_kernel(float *x, const float *__restrict__ x0, const float *__restrict__ w,
+                                                      const float *__restrict__ scal, int64_t B, int64_t per_sample) {
+    const int64_t n = B * per_sample;
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int64_t nv = VEC == 4 ? (n >> 2) : 0;
+    for (int64_t v = i; v < nv; v += stride) {
+        const float4 vx = reinterpret_cast<const float4 *>(x)[v];
+        const float4 v0 = reinterpret_cast<const float4 *>(x0)[v];
+        const float4 vw = reinterpret_cast<const float4 *>(w)[v];
+        const int64_t base = v << 2;
+        const int64_t b = base / per_sample;
+        const float xi[4] = {vx.x, vx.y, vx.z, vx.w}, oi[4] = {v0.x, v0.y, v0.z, v0.w}, wi[4] = {vw.x, vw.y, vw.z, vw.w};
+        float out[4];
+        if (base - b * per_sample + 4 <= per_sample) {  // the four elements belong to one sample
+            const StepSample sm = step_sample(scal, B, b);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) out[k] = step_op(xi[k], oi[k], wi[k], sm);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) out[k] = step_op(xi[k], oi[k], wi[k], step_sample(scal, B, (base + k) / per_sample));  // base + k < n
+        }
+        reinterpret_cast<float4 *>(x)[v] = make_float4(out[0], out[1], out[2], out[3]);
+    }
+    for (int64_t e = (nv << 2) + i; e < n; e += stride) x[e] = step_op(x[e], x0[e], w[e], step_sample(scal, B, e / per_sample));
+}
+
+// ---- the check after the second forward ------------------------------------------------------------------------------------------------
+template <int VEC>
+__global__ __launch_bounds__(kCommitBlock) void commit_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels, int K, float *x,
+                                                              const float *__restrict__ x0, float *adv, float *res, int *__restrict__ pred,
+                                                              int *__restrict__ flags, int *counter, int64_t per_sample) {
+    __shared__ float sh_max[kCommitWaves];
+    __shared__ int sh_first, sh_nan;
+    const int b = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    if (b == 0 && threadIdx.x == 0) counter[0] = counter[0] + 1;  // nobody reads the counter in this launch
+    const float best = res[b];  // read by every thread before the barrier below, written by thread 0 after it
+    if (wave == 0) {
+        bool nan;
+        const int first = row_first(logits + static_cast<size_t>(b) * K, K, lane, nan);
+        if (lane == 0) sh_first = first, sh_nan = nan ? 1 : 0;
+    }
+    const int64_t off = static_cast<int64_t>(b) * per_sample;
+    float m = 0.0f;
+    if (VEC == 4) {  // per_sample % 4 == 0 and 16-byte bases: a sample is a whole number of aligned vectors
+        const float4 *vx = reinterpret_cast<const float4 *>(x + off), *v0 = reinterpret_cast<const float4 *>(x0 + off);
+        for (int64_t v = threadIdx.x; v < (per_sample >> 2); v += kCommitBlock) {
+            const float4 p = vx[v], o = v0[v];
+            m = fmaxf(m, fmaxf(fmaxf(fabsf(p.x - o.x), fabsf(p.y - o.y)), fmaxf(fabsf(p.z - o.z), fabsf(p.w - o.w))));
+        }
+    } else {
+        for (int64_t k = threadIdx.x; k < per_sample; k += kCommitBlock) m = fmaxf(m, fabsf(x[off + k] - x0[off + k]));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if (lane == 0) sh_max[wave] = m;
+    __syncthreads();
+    m = sh_max[0];
+#pragma unroll
+    for (int i = 1; i < kCommitWaves; ++i) m = fmaxf(m, sh_max[i]);
+    const int64_t y = labels[b];
+    const int first = sh_first;
+    const bool is_adv = !sh_nan && y >= 0 && y < K && first != y;  // a row with a NaN logit is never adversarial
+    const bool improve = is_adv && m < best;
+    if (threadIdx.x == 0) {
+        pred[b] = first;
+        flags[b] = (is_adv ? EE_FAB_ADV : 0) | (improve ? EE_FAB_IMPROVED : 0);
+        if (improve) res[b] = m;
+    }
+    if (!is_adv) return;
+    if (VEC == 4) {
+        float4 *vx = reinterpret_cast<float4 *>(x + off), *va = reinterpret_cast<float4 *>(adv + off);
+        const float4 *v0 = reinterpret_cast<const float4 *>(x0 + off);
+        for (int64_t v = threadIdx.x; v < (per_sample >> 2); v += kCommitBlock) {
+            const float4 p = vx[v], o = v0[v];
+            if (improve) va[v] = p;
+            vx[v] = make_float4(o.x + kBeta * (p.x - o.x), o.y + kBeta * (p.y - o.y), o.z + kBeta * (p.z - o.z), o.w + kBeta * (p.w - o.w));
+        }
+    } else {
+        for (int64_t k = threadIdx.x; k < per_sample; k += kCommitBlock) {
+            const float p = x[off + k], o = x0[off + k];
+            if (improve) adv[off + k] = p;
+            x[off + k] = o + kBeta * (p - o);
+        }
+    }
+}
+
+bool bad_shape(int64_t B, int64_t per_sample) {
+    return B < 0 || per_sample < 0 || B > INT32_MAX / 2 || per_sample > INT32_MAX || (per_sample > 0 && B > INT64_MAX / per_sample);
+}
+
+}  // namespace
+
+EE_API int ee_fab_diff_f32(const float *logits, const int64_t *labels, const int64_t *targets, int B, int K, float *df, float *dlogits, int *pred,
+                           void *stream) {
+    if (B < 0 || K < 2 || K > 65536) return EE_ERR_SHAPE;
+    if (B == 0) return EE_OK;
+    if (!logits || !labels || !targets || !df || !dlogits || !pred) return EE_ERR_NULL;
+    if (!aligned4(logits) || !aligned4(df) || !aligned4(dlogits) || !aligned4(pred) || (reinterpret_cast<uintptr_t>(labels) & 7u) ||
+        (reinterpret_cast<uintptr_t>(targets) & 7u))
+        return EE_ERR_ALIGN;
+    ProfScope prof(EE_K_FAB_DIFF, as_stream(stream));
+    EE_LAUNCH(diff_kernel, dim3(static_cast<unsigned>((B + kRowsPerBlock - 1) / kRowsPerBlock)), dim3(kBlock), 0, as_stream(stream), logits, labels,
+              targets, B, K, df, dlogits, pred);
+    return launch_status();
+}
+
+EE_API int ee_fab_proj_linf_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path,
+                                float *out, void *stream) {
+    if (bad_shape(B, per_sample) || per_sample < 1 || path < EE_FAB_PATH_AUTO || path > EE_FAB_PATH_STREAMING) return EE_ERR_SHAPE;
+    if (path == EE_FAB_PATH_RESIDENT && per_sample > kProjResident) return EE_ERR_UNSUPPORTED;
+    if (B == 0) return EE_OK;
+    if (!x || !x0 || !w || !df || !out) return EE_ERR_NULL;
+    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(df) || !aligned4(out)) return EE_ERR_ALIGN;
+    const bool res = path == EE_FAB_PATH_RESIDENT || (path == EE_FAB_PATH_AUTO && per_sample <= kProjResident);
+    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x0) && aligned16(w);  // every row then starts 16-byte aligned
+    const dim3 grid(static_cast<unsigned>(2 * B)), block(kProjBlock);
+    const int nb = static_cast<int>(B);
+    ProfScope prof(EE_K_FAB_PROJ, as_stream(stream));
+    if (res && vec)
+        EE_LAUNCH((proj_kernel<true, true>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+    else if (res)
+        EE_LAUNCH((proj_kernel<true, false>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+    else if (vec)
+        EE_LAUNCH((proj_kernel<false, true>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+    else
+        EE_LAUNCH((proj_kernel<false, false>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+    return launch_status();
+}
+
+EE_API int ee_fab_step_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
+    if (bad_shape(B, per_sample)) return EE_ERR_SHAPE;
+    const int64_t n = B * per_sample;
+    if (n == 0) return EE_OK;
+    if (!x || !x0 || !w || !scal) return EE_ERR_NULL;
+    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(scal)) return EE_ERR_ALIGN;
+    const bool vec = aligned16(x) && aligned16(x0) && aligned16(w);
+    const int64_t work = vec ? (n + 3) / 4 : n;
+    int64_t blocks = (work + kBlock - 1) / kBlock;
+    if (blocks > kMaxGrid) blocks = kMaxGrid;
+    ProfScope prof(EE_K_FAB_STEP, as_stream(stream));
+    if (vec)
+        EE_LAUNCH(step_kernel<4>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+    else
+        EE_LAUNCH(step_kernel<1>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+    return launch_status();
+}
+
+EE_API int ee_fab_commit_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res, int *pred,
+                             int *flags, int *counter, int64_t per_sample, void *stream) {
+    if (B < 0 || K < 2 || K > 65536 || bad_shape(B, per_sample)) return EE_ERR_SHAPE;
+    if (B == 0 || per_sample == 0) return EE_OK;  // an empty batch is no attack: nothing is launched, the counter stays
+    if (!logits || !labels || !x || !x0 || !adv || !res || !pred || !flags || !counter) return EE_ERR_NULL;
+    if (!aligned4(logits) || !aligned4(x) || !aligned4(x0) || !aligned4(adv) || !aligned4(res) || !aligned4(pred) || !aligned4(flags) ||
+        !aligned4(counter) || (reinterpret_cast<uintptr_t>(labels) & 7u))
+        return EE_ERR_ALIGN;
+    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x0) && aligned16(adv);
+    ProfScope prof(EE_K_FAB_COMMIT, as_stream(stream));
+    if (vec)
+        EE_LAUNCH(commit_kernel<4>, dim3(static_cast<unsigned>(B)), dim3(kCommitBlock), 0, as_stream(stream), logits, labels, K, x, x0, adv, res,
+                  pred, flags, counter, per_sample);
+    else
+        EE_LAUNCH(commit_kernel<1>, dim3(static_cast<unsigned>(B)), dim3(kCommitBlock), 0, as_stream(stream), logits, labels, K, x, x0, adv, res,
+                  pred, flags, counter, per_sample);
+    return launch_status();
+}

@@ -68,6 +68,14 @@ SIGNATURES = {
     "ee_sqatk_margin_f32": [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     # x_best, x_new, x0, flags, margin_min, counter, sizes, n_sizes, seed, B, C, H, W, eps, stream
     "ee_sqatk_step_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
+    # logits, labels, targets, B, K, df, dlogits, pred, stream
+    "ee_fab_diff_f32": [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
+    # x, x0, w, df, B, per_sample, path, out, stream
+    "ee_fab_proj_linf_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_i, c_p, c_p],
+    # x, x0, w, scal, B, per_sample, stream
+    "ee_fab_step_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_p],
+    # logits, labels, B, K, x, x0, adv, res, pred, flags, counter, per_sample, stream
+    "ee_fab_commit_f32": [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p],
     "ee_add_square_fwd_f32": [c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_add_square_bwd_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_square_draw_f32": [c_p, c_l, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],
@@ -172,6 +180,7 @@ _RESTYPE = {"ee_strerror": ctypes.c_char_p, "ee_device_name": ctypes.c_char_p, "
 K_WINO, K_CONV3S2_FWD, K_CONV3S2_BWD, K_WINO_FUSED = 18, 19, 20, 21  # 14 - 17: the direct 3x3 kernels removed in round 3
 K_BATCH_AUG = 22
 K_SQATK_INIT, K_SQATK_MARGIN, K_SQATK_STEP = 23, 24, 25
+K_FAB_DIFF, K_FAB_PROJ, K_FAB_STEP, K_FAB_COMMIT = 26, 27, 28, 29
 
 
 class EEError(RuntimeError):

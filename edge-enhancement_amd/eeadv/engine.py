@@ -567,3 +567,145 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
     run.finish()
     run.trace = None
     return run.result()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# FAB-T (Croce & Hein 2020; Linf, targeted, eta = 1.05, beta = 0.9, alpha_max = 0.1, one run from x0, no EOT): DESIGN.md section 13
+# ---------------------------------------------------------------------------------------------------------------------------------------
+class _FabSpec:
+    """The loss-gradient step of `_body_input_grad` for a FAB run: df = z_t - z_y, its logit gradient and `pred` in one launch.  The kind is
+    none of the CE kinds, so the route is the generic one (logits -> this -> autograd), through the whole model for edge-enhanced ones."""
+
+    def __init__(self, run):
+        self.kind, self.payload, self.run = "fab_t", run.y, run
+
+    def dlogits(self, logits):
+        r = self.run
+        r.df, d, r.pred_at_x = ops.fab_diff(logits.detach().float().contiguous(), r.y, r.t)
+        return d
+
+
+class _FabRun:
+    """The device state of one FAB-T run (include/eeadv.h, "FAB-T") and its two pieces: `start` (the initial state: a few fills, once per
+    run) and `iteration` (forward, diff, backward, projection, step, forward, commit: what a captured graph replays).  No host read anywhere."""
+
+    def __init__(self, x0, y, n_iter, path="auto"):
+        B, dev = x0.shape[0], x0.device
+        self.n_iter, self.path = int(n_iter), path
+        self.x = torch.empty_like(x0).requires_grad_(True)
+        self.x0, self.adv = torch.empty_like(x0), torch.empty_like(x0)
+        self.y = torch.empty(B, dtype=torch.int64, device=dev)
+        self.t = torch.empty(B, dtype=torch.int64, device=dev)
+        self.res = torch.empty(B, dtype=torch.float32, device=dev)
+        self.scal = torch.zeros((3, 2 * B), dtype=torch.float32, device=dev)
+        self.pred = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.flags = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.df = self.pred_at_x = None
+        self.spec = _FabSpec(self)
+
+    def load(self, x0, y, targets):
+        with torch.no_grad():
+            self.x0.copy_(x0)
+            self.y.copy_(y)
+            self.t.copy_(targets)
+
+    def start(self):
+        with torch.no_grad():
+            self.x.detach().copy_(self.x0)
+            self.adv.copy_(self.x0)
+            self.res.fill_(float("inf"))
+            self.flags.zero_()
+            self.counter.zero_()
+
+    def iteration(self, model):
+        w = input_gradient(model, self.x, self.spec).contiguous()
+        x = self.x.detach()
+        ops.fab_proj_linf(x, self.x0, w, self.df, self.path, self.scal)
+        ops.fab_step_(x, self.x0, w, self.scal)
+        with torch.no_grad():
+            z = model(self.x)
+        ops.fab_commit_(z.detach().float().contiguous(), self.y, x, self.x0, self.adv, self.res, self.pred, self.flags, self.counter)
+
+    def result(self, eps):
+        with torch.no_grad():
+            robust = ~(self.res <= eps)
+            keep = robust.view(-1, *([1] * (self.x0.dim() - 1)))
+            return torch.where(keep, self.x0, self.adv), robust, self.res.clone()
+
+
+class _GraphedFab:
+    """`iters` consecutive FAB-T iterations captured into one graph over the static buffers of a _FabRun."""
+
+    def __init__(self, model, run, iters):
+        self.run, self.iters, self.model, self.graph = run, iters, weakref.ref(model), None
+
+    def _body(self, model):
+        for _ in range(self.iters):
+            self.run.iteration(model)
+
+    def capture(self, model):
+        runtime.draw_state(self.run.x0.device)
+        self.run.start()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):  # warm-up outside capture, as _GraphedStep.capture; the state it advances is rebuilt by the next start()
+                self._body(model)
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        from .models import deferred_bn_counters
+        with torch.cuda.graph(self.graph, capture_error_mode=runtime.capture_mode()):
+            with deferred_bn_counters():
+                self._body(model)
+
+
+def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto"):
+    """One FAB-T run (Linf) of n_iter iterations from x0 towards the classes `targets` [B].  Returns (x_adv, robust, norm): norm [B] is the
+    smallest ||adv - x0||_inf over the adversarial iterates (+inf if there was none), robust = not (norm <= eps), and x_adv is x0 with the
+    non-robust rows replaced by that closest adversarial point.  The search itself is not confined to the eps-ball: FAB looks for the
+    minimum norm and eps only thresholds its result.  Deterministic - no random start, no draws of its own.  The model's mode is left as the
+    caller set it.  Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of up to MAX_ITERS_PER_GRAPH iterations; both
+    give the same bits.  `path` picks the projection kernel's path ('auto', 'resident', 'streaming'; the same bits)."""
+    model = _unwrap(model)
+    x0 = x0.detach().contiguous()
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("FAB needs n_iter >= 1")
+    if path not in ops.FAB_PATHS:
+        raise ValueError("FAB projection path must be one of %s, got %r" % (sorted(ops.FAB_PATHS), path))
+    if x0.shape[0] == 0:
+        return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=torch.float32, device=x0.device)
+    if use_graph is None:
+        use_graph = graphs_enabled()
+    if not use_graph:
+        run = _FabRun(x0, y, n_iter, path)
+        run.load(x0, y, targets)
+        run.start()
+        for _ in range(n_iter):
+            run.iteration(model)
+        return run.result(float(eps))
+    chunk = max(c for c in range(1, min(n_iter, MAX_ITERS_PER_GRAPH) + 1) if n_iter % c == 0)
+    key = ("fab", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk)
+    gs = _GRAPHS.get(key)
+    if gs is not None and gs.model() is not model:
+        gs = None
+    if gs is None:
+        run = _FabRun(x0, y, n_iter, path)
+        run.load(x0, y, targets)
+        gs = _GraphedFab(model, run, chunk)
+        saved = {}
+        if model.training:  # as pgd_loop: the warm-up passes before the capture are extra train-mode forwards
+            saved = {k: v.clone() for k, v in model.state_dict().items() if "running_" in k or "num_batches" in k}
+        gs.capture(model)
+        if saved:
+            live = model.state_dict()
+            for k, v in saved.items():
+                live[k].data.copy_(v)
+        _GRAPHS[key] = gs
+    gs.run.load(x0, y, targets)
+    refresh_dense_weights()
+    gs.run.start()
+    for _ in range(n_iter // chunk):
+        gs.graph.replay()
+    return gs.run.result(float(eps))

@@ -504,6 +504,59 @@ def sqatk_step_(x_best, x_new, x0, flags, margin_min, counter, sizes, seed, eps)
     return x_new
 
 
+# ---- FAB-T (ee_fab.hip) ----------------------------------------------------------------------------------------------
+FAB_ADV, FAB_IMPROVED = 1, 2  # bits of the flags of fab_commit_ (EE_FAB_*)
+FAB_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_FAB_PATH_*
+FAB_LAMBDA, FAB_SIGN, FAB_NORM = range(3)  # rows of the projection scalars [3, 2B]
+
+
+def fab_diff(logits, labels, targets):
+    """(df [B] = z_t - z_y, dlogits [B,K] of its batch sum, pred [B] int32: the first class in the order of topk)."""
+    B, K = logits.shape
+    df = torch.empty(B, dtype=torch.float32, device=logits.device)
+    d = torch.empty_like(logits)
+    pred = torch.empty(B, dtype=torch.int32, device=logits.device)
+    N.check(N.lib.ee_fab_diff_f32(_chk(logits, torch.float32, "logits"), _chk(labels, torch.int64, "labels", (B,)),
+                                  _chk(targets, torch.int64, "targets", (B,)), B, K, _chk(df, torch.float32, "df"), _chk(d, torch.float32, "d"),
+                                  _chk(pred, torch.int32, "pred"), _stream()), "ee_fab_diff_f32")
+    return df, d, pred
+
+
+def fab_proj_linf(x, x0, w, df, path="auto", out=None):
+    """The scalars [3, 2B] (rows lambda, sign, ||delta||_inf) of the two projections of every sample: column b projects x[b] with c = df[b],
+    column B + b projects x0[b] with c = df[b] + <w[b], x0[b] - x[b]>.  path: 'auto', 'resident' (per-sample size <= 12288) or 'streaming'."""
+    B = x.shape[0]
+    px = _chk(x, torch.float32, "x")
+    p0 = _chk(x0, torch.float32, "x0", x.shape)
+    pw = _chk(w, torch.float32, "w", x.shape)
+    pd = _chk(df, torch.float32, "df", (B,))
+    out = torch.empty((3, 2 * B), dtype=torch.float32, device=x.device) if out is None else out
+    po = _chk(out, torch.float32, "out", (3, 2 * B))
+    if B:
+        N.check(N.lib.ee_fab_proj_linf_f32(px, p0, pw, pd, B, x.numel() // B, FAB_PATHS[path], po, _stream()), "ee_fab_proj_linf_f32")
+    return out
+
+
+def fab_step_(x, x0, w, scal):
+    """The FAB step in place on x [B, ...] from the projection scalars [3, 2B]."""
+    B = x.shape[0]
+    px = _chk(x, torch.float32, "x")
+    N.check(N.lib.ee_fab_step_f32(px, _chk(x0, torch.float32, "x0", x.shape), _chk(w, torch.float32, "w", x.shape),
+                                  _chk(scal, torch.float32, "scal", (3, 2 * B)), B, x.numel() // B if B else 0, _stream()), "ee_fab_step_f32")
+    return x
+
+
+def fab_commit_(logits, labels, x, x0, adv, res, pred, flags, counter):
+    """The check after the second forward, in place on x, adv [B, ...], res [B]; pred, flags [B] int32 are written; counter += 1."""
+    B, K = logits.shape
+    N.check(N.lib.ee_fab_commit_f32(_chk(logits, torch.float32, "logits", (x.shape[0], K)), _chk(labels, torch.int64, "labels", (B,)), B, K,
+                                    _chk(x, torch.float32, "x"), _chk(x0, torch.float32, "x0", x.shape), _chk(adv, torch.float32, "adv", x.shape),
+                                    _chk(res, torch.float32, "res", (B,)), _chk(pred, torch.int32, "pred", (B,)),
+                                    _chk(flags, torch.int32, "flags", (B,)), _chk(counter, torch.int32, "counter", (1,)),
+                                    x.numel() // B if B else 0, _stream()), "ee_fab_commit_f32")
+    return flags
+
+
 # ---- Add_Square ------------------------------------------------------------------------------------------------------
 def add_square_fwd(x, eps, stripe, sq_sign, sq_pos, sq_size):
     B, C, H, W = x.shape

@@ -712,11 +712,30 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         if x_adv is None:
             return xs
         return torch.where((robust & ~rs).view(shape), xs, x_adv)
+    if args.attack_method in FAB_METHODS:
+        # FAB-T (minimum-norm, args.fab_iters iterations per target class, thresholded at args.epsilon), alone or between APGD-T and Square -
+        # the order of AutoAttack's `standard` version: flags ANDed, the first fooling point kept
+        if targeted:
+            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+        shape = (-1,) + (1,) * (input.dim() - 1)
+        fab_iters = int(getattr(args, 'fab_iters', 100))
+        if args.attack_method == 'FAB-T':
+            return A.FAB_T(model, args, input, target, n_class, fab_iters)[0]
+        x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce')
+        xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class)
+        x_adv = torch.where((robust & ~rt).view(shape), xt, x_adv)
+        robust = robust & rt
+        xf, rf, _ = A.FAB_T(model, args, input, target, n_class, fab_iters)
+        x_adv = torch.where((robust & ~rf).view(shape), xf, x_adv)
+        robust = robust & rf
+        xs, rs, _ = A.Square(model, args, input, target, int(getattr(args, 'square_queries', 5000)))
+        return torch.where((robust & ~rs).view(shape), xs, x_adv)
     raise NotImplementedError
 
 
 APGD_METHODS = ('APGD-CE', 'APGD-T', 'APGD')
 SQUARE_METHODS = ('Square', 'APGD+Square')
+FAB_METHODS = ('FAB-T', 'APGD+FAB+Square')
 
 
 def validate_batch(model, criterion, args, input, target, device, num_steps, step_size, n_class):

@@ -10,7 +10,7 @@ deliberate and documented in DESIGN.md:
   * random starts are drawn on the device (Philox inside the init kernel) unless `noise=` is injected -
     device and host generators differ anyway, parity tests inject the noise;
   * CWLinfAttack(target=None) works (the reference raises TypeError at :152, SURVEY a17);
-  * APGD / APGD_T and Square are additions: the reference runs them through the `autoattack` package (DESIGN.md sections 11, 12);
+  * APGD / APGD_T, Square and FAB_T are additions: the reference runs them through the `autoattack` package (DESIGN.md sections 11 - 13);
   * CPU tensors are refused unless eeadv.runtime.allow_cpu_plumbing(True) was called (--no-cuda drivers).
 """
 import numpy as np
@@ -116,7 +116,7 @@ def targeted_PGD_trick(model, args, inputs, labels, num_steps, step_size, nclass
 
 # ---------------------------------------------------------------------------------------------------------
 # APGD-CE and APGD-T (Croce & Hein 2020): the two gradient attacks of AutoAttack's `standard` version.  Not in the
-# reference's utils/attacks.py - its drivers call the `autoattack` package for them.  Square, the black-box member, follows below; FAB-T,
+# reference's utils/attacks.py - its drivers call the `autoattack` package for them.  Square, the black-box member, and FAB-T follow below;
 # the `rand` / EOT versions, the L2 / L1 norms and restarts are NOT here, so the result is not an AutoAttack number.
 # ---------------------------------------------------------------------------------------------------------
 def _apgd_row_losses(z, y, loss, t=None):
@@ -312,6 +312,134 @@ def Square(model, args, inputs, targets, n_queries=5000, seed=None):
     x_best, margin_min, queries = _square_host(model, x0, targets, n_queries, eps, seed)
     robust = margin_min > 0
     return torch.where(robust.view(-1, 1, 1, 1), x0, x_best), robust, queries
+
+
+# ---------------------------------------------------------------------------------------------------------
+# FAB-T (Croce & Hein 2020, Linf, targeted): the minimum-norm member of AutoAttack's `standard` version - it walks along linearised
+# decision boundaries instead of ascending a loss.  Built from the published algorithm with the constants `standard`
+# runs it with (eta = 1.05, beta = 0.9, alpha_max = 0.1, 9 target classes, one run from the clean point: deterministic).  Untargeted FAB,
+# L2 / L1, restarts with the random start, the final line search and EOT are NOT here.
+# ---------------------------------------------------------------------------------------------------------
+_FAB_ETA, _FAB_BETA, _FAB_ALPHA_MAX = 1.05, 0.9, 0.1
+
+
+def _fab_projection(p, w, c):
+    """The box-constrained Linf projection of the rows of p [B,D] (in [0,1]) onto <w, .> = const at signed distance c [B]: (lambda, s,
+    ||delta||_inf) per row, delta_i = -sign(s w_i) min(lambda, r_i).  Sort, cumulative sums (the sums above a breakpoint taken from the top,
+    so nothing cancels) and the closed form on the segment that holds lambda.  c = 0: lambda = 0; c' >= g(inf): lambda = inf."""
+    s = torch.where(c >= 0, torch.ones_like(c), -torch.ones_like(c))
+    v = s.view(-1, 1) * w
+    a = v.abs()
+    r = torch.where(v > 0, p, torch.where(v < 0, 1 - p, torch.zeros_like(p))).clamp_min(0)
+    cp = c.abs()
+    rs, order = torch.sort(r, dim=1)
+    a_s = a.gather(1, order)
+    below = torch.cumsum(a_s * rs, dim=1)  # sum_{j <= k} a_j r_j
+    above = torch.flip(torch.cumsum(torch.flip(a_s, [1]), dim=1), [1]) - a_s  # sum_{j > k} a_j
+    g = below + rs * above  # g at breakpoint k
+    zero = torch.zeros_like(cp).view(-1, 1)
+    k = (g < cp.view(-1, 1)).sum(dim=1, keepdim=True)  # breakpoints strictly below the solution
+    S = torch.cat([zero, below], dim=1).gather(1, k).squeeze(1)
+    A = torch.cat([a_s.sum(dim=1, keepdim=True), above], dim=1).gather(1, k).squeeze(1)
+    lam = (cp - S) / A
+    lam = torch.where(cp >= below[:, -1], torch.full_like(lam, _INF), lam)
+    lam = torch.where(cp == 0, torch.zeros_like(lam), lam)
+    rmax = torch.where(a != 0, r, torch.zeros_like(r)).max(dim=1)[0]
+    return lam, s, torch.minimum(lam, rmax)
+
+
+def _fab_delta(p, w, lam, s):
+    v = s.view(-1, 1) * w
+    r = torch.where(v > 0, p, torch.where(v < 0, 1 - p, torch.zeros_like(p))).clamp_min(0)
+    return -torch.sign(v) * torch.minimum(lam.view(-1, 1), r)
+
+
+def _fab_host_iteration(model, x, x0, y, t, adv, res):
+    """One FAB-T iteration in plain torch ops, in the input's dtype: (x, adv, res) -> (x, adv, res, info).  `info` holds every
+    intermediate quantity (df, w, the projection scalars, alpha, the stepped point, pred, the flags)."""
+    B = x0.shape[0]
+    rows = torch.arange(B, device=x0.device)
+    xc = x.detach().clone().requires_grad_()
+    with torch.enable_grad():
+        z = model(xc)
+        diff = z[rows, t] - z[rows, y]
+    w = torch.autograd.grad(diff.sum(), [xc])[0].detach().reshape(B, -1)
+    df = diff.detach()
+    xf, x0f = x.detach().reshape(B, -1), x0.reshape(B, -1)
+    sabs = w.abs().sum(dim=1)
+    on = torch.isfinite(df) & (df != 0) & torch.isfinite(sabs) & (sabs > 0)
+    safe_w = torch.where(on.view(-1, 1), w, torch.ones_like(w))  # rows without a hyperplane are computed on stand-ins and masked below
+    c1 = torch.where(on, df, torch.ones_like(df))
+    c2 = torch.where(on, df + (safe_w * (x0f - xf)).sum(dim=1), torch.ones_like(df))  # a sum of differences: <w, x0> - <w, x> would cancel
+    l1, s1, n1 = _fab_projection(xf, safe_w, c1)
+    l2, s2, n2 = _fab_projection(x0f, safe_w, c2)
+    zero = torch.zeros_like(df)
+    l1, s1, n1, l2, s2, n2 = (torch.where(on, q, zero) for q in (l1, s1, n1, l2, s2, n2))
+    d1, d2 = _fab_delta(xf, safe_w, l1, s1), _fab_delta(x0f, safe_w, l2, s2)
+    a1, a2 = n1.clamp_min(1e-8), n2.clamp_min(1e-8)
+    alpha = torch.minimum(a1 / (a1 + a2), torch.full_like(a1, _FAB_ALPHA_MAX))
+    al = alpha.view(-1, 1)
+    x_step = torch.clamp((xf + _FAB_ETA * d1) * (1 - al) + (x0f + _FAB_ETA * d2) * al, 0, 1)
+    x_step = torch.where(on.view(-1, 1), x_step, xf)
+    with torch.no_grad():
+        z2 = model(x_step.view(x0.shape))
+    pred = torch.sort(z2, dim=1, descending=True, stable=True)[1][:, 0]
+    is_adv = (pred != y) & ~torch.isnan(z2).any(dim=1)
+    nrm = (x_step - x0f).abs().max(dim=1)[0]
+    improved = is_adv & (nrm < res)
+    adv = torch.where(improved.view(-1, 1), x_step, adv.reshape(B, -1)).view(x0.shape)
+    res = torch.where(improved, nrm, res)
+    x_new = torch.where(is_adv.view(-1, 1), x0f + _FAB_BETA * (x_step - x0f), x_step).view(x0.shape)
+    info = dict(df=df, w=w, lam1=l1, s1=s1, n1=n1, lam2=l2, s2=s2, n2=n2, alpha=alpha, x_step=x_step.view(x0.shape), pred=pred, is_adv=is_adv,
+                improved=improved, nrm=nrm, enabled=on)
+    return x_new, adv, res, info
+
+
+def _fab_host(model, x0, y, t, n_iter, trace=None):
+    """Plumbing path for CPU tensors (opt-in), the counterpart of _host_loop: the iteration of engine.fab_loop in plain torch ops, in the
+    input's dtype.  Returns (adv, res).  `trace`, a list, receives one dict of clones per iteration."""
+    x, adv = x0.clone(), x0.clone()
+    res = torch.full((x0.shape[0],), _INF, dtype=x0.dtype, device=x0.device)
+    for _ in range(int(n_iter)):
+        x, adv, res, info = _fab_host_iteration(model, x, x0, y, t, adv, res)
+        if trace is not None:
+            info.update(x=x, adv=adv, res=res)
+            trace.append({k: v.clone() for k, v in info.items()})
+    return adv, res
+
+
+def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9):
+    """Targeted FAB (Linf): one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most nclass - 1 of
+    them, taken as APGD_T takes them), each on the whole batch from the clean point.  Returns (x_adv, robust, norm): norm [B] is the smallest
+    ||adv - x0||_inf over all runs (+inf if no run found an adversarial point, 0 for a sample the clean forward already misclassifies),
+    robust = not (norm <= args.epsilon), and x_adv is the inputs with every non-robust sample replaced by the point that attains its norm
+    (the first one, among equals).  eps only thresholds the result - the search is not confined to the ball.  Deterministic.  The model runs in
+    the mode the caller left it in.  On the device c2 = df + sum w_i (x0_i - x_i) is summed in double (csrc/ee_fab.hip); the host path
+    below forms the same sum of differences in the input's dtype - the public code's <w, x0> - (<w, x> - df) cancels in fp32."""
+    x0 = inputs.detach()
+    eps = float(args.epsilon)
+    n_t = min(int(n_target_classes), int(nclass) - 1)
+    on_dev = runtime.require_device(x0, "FAB_T")
+    with torch.no_grad():
+        z = model(x0)
+    if on_dev:
+        order = ops.topk(z.detach().float().contiguous(), None, n_t + 1)[0]
+    else:
+        order = torch.sort(z, dim=1, descending=True, stable=True)[1][:, :n_t + 1]
+    shape = (-1,) + (1,) * (x0.dim() - 1)
+    x_adv = x0.clone()
+    inf = torch.full((x0.shape[0],), _INF, dtype=torch.float32 if on_dev else x0.dtype, device=x0.device)
+    norm = torch.where(order[:, 0] != targets, torch.zeros_like(inf), inf)
+    for j in range(1, n_t + 1):
+        t = order[:, j].contiguous()
+        if on_dev:
+            xa, _, nj = engine.fab_loop(model, x0, targets, t, n_iter, eps)
+        else:
+            xa, nj = _fab_host(model, x0, targets, t, n_iter)
+        closer = (nj < norm) & (nj <= eps)
+        x_adv = torch.where(closer.view(shape), xa, x_adv)
+        norm = torch.minimum(norm, nj)
+    return x_adv, ~(norm <= eps), norm
 
 
 class LabelSmoothLoss(torch.nn.Module):

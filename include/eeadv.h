@@ -297,6 +297,53 @@ int ee_sqatk_margin_f32(const float *logits, const int64_t *labels, int B, int K
 int ee_sqatk_step_f32(float *x_best, float *x_new, const float *x0, const int *flags, const float *margin_min, const int *counter,
                       const int *sizes, int n_sizes, const int64_t *seed, int B, int C, int H, int W, float eps, void *stream);
 
+/* ---- FAB-T (Croce & Hein 2020, "Minimally distorted adversarial examples with a fast adaptive boundary attack"; Linf, targeted, one run,
+ * eta = 1.05, beta = 0.9, alpha_max = 0.1 - the constants of AutoAttack's `standard` version), ee_fab.hip ----
+ * State of one run on B samples of per_sample elements each, all in device memory:
+ *   x, x0, adv  float [B, per_sample]   the iterate, the clean input, the closest adversarial point so far
+ *   res   float [B]      ||adv - x0||_inf, +inf while none was found      df   float [B]   z_t - z_y at the iterate
+ *   scal  float [3, 2B]  rows lambda, sign, ||delta||_inf of the 2B projection problems: problem b projects x[b], problem B + b projects x0[b]
+ *   pred  int [B]  the first class of the last logits     flags int [B]  EE_FAB_*     counter int [1]  iterations done
+ * An iteration is classifier forward -> diff -> classifier backward (w = d(z_t - z_y)/dx) -> proj -> step -> classifier forward ->
+ * commit.  No argument changes from one iteration to the next, so a captured graph of one iteration replays for all of them. */
+#define EE_FAB_ADV 1      /* flags: the iterate is misclassified (and no logit of its row is NaN) */
+#define EE_FAB_IMPROVED 2 /*        ... and closer to x0 than adv was: adv took it */
+#define EE_FAB_PATH_AUTO 0      /* resident when per_sample <= 12288, else streaming */
+#define EE_FAB_PATH_RESIDENT 1  /* a problem's (|w_i|, r_i) stay in registers across all passes; per_sample > 12288: EE_ERR_UNSUPPORTED */
+#define EE_FAB_PATH_STREAMING 2 /* every pass re-reads w and the point; any per_sample */
+
+/* Per row of logits [B,K], K >= 2, one wavefront per row: df[b] = z_t - z_y (one fp32 difference), dlogits[b] = +1 at t, -1 at y (0 at
+ * both when t == y), pred[b] = the first class by value descending, ties to the lower index, NaN above everything (the order of
+ * ee_topk_i64).  A label or target outside [0, K) gives the row df = NaN and a zero gradient. */
+int ee_fab_diff_f32(const float *logits, const int64_t *labels, const int64_t *targets, int B, int K, float *df, float *dlogits, int *pred,
+                    void *stream);
+
+/* The box-constrained Linf projection onto the hyperplane <w, .> + b = 0, per problem q of 2B, one workgroup each; scalars only.
+ * Problem b: point p = x[b], c = df[b].  Problem B + b: p = x0[b], c = df[b] + sum_i w_i (x0_i - x_i) (a sum of differences, in double).
+ * With s = +1 if c >= 0 else -1, v = s w, c' = |c|, room r_i = p_i if v_i > 0, 1 - p_i if v_i < 0, 0 otherwise (never negative) and
+ * g(l) = sum_i |v_i| min(l, r_i):  c' >= g(inf): lambda = +inf (infeasible: every moving coordinate goes to its bound);  otherwise lambda =
+ * the smallest l with g(l) = c', as the exact solve of the segment of g that contains it ((c' - sum_{r_i <= T} |v_i| r_i) / sum_{r_i > T} |v_i|
+ * with T the largest float with g(T) < c', found in 31 steps over the bit pattern; sums in double, one fixed order on both paths: the
+ * two paths return the same bits).  out[0][q] = lambda, out[1][q] = s, out[2][q] = min(lambda, max_{v_i != 0} r_i) = ||delta||_inf of
+ * delta_i = -sign(v_i) min(lambda, r_i).  A sample whose df or sum |w_i| is not finite or is 0 gets lambda = 0, s = 0, norm = 0 in both
+ * problems; c = 0 or not finite in problem B + b alone: lambda = 0, s = +1.  The points are taken to lie in [0,1].  per_sample >= 1, any
+ * remainder modulo 4; 128-bit loads when per_sample % 4 == 0 and the tensors are 16-byte aligned. */
+int ee_fab_proj_linf_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path, float *out,
+                         void *stream);
+
+/* The step, in place on x, from the scalars of ee_fab_proj_linf_f32: with delta1_i = -sign(s1 w_i) min(lambda1, r_i(x)), delta2_i =
+ * -sign(s2 w_i) min(lambda2, r_i(x0)) (the rooms as above), a_k = max(norm_k, 1e-8), alpha = min(a1 / (a1 + a2), 0.1):
+ *     x = clamp((x + 1.05 delta1) * (1 - alpha) + (x0 + 1.05 delta2) * alpha, 0, 1)
+ * in that order, every operation rounded once.  A sample with s1 = 0 (no hyperplane) keeps its x.  16 B of HBM traffic per element. */
+int ee_fab_step_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream);
+
+/* The check after the second forward, one workgroup per sample: pred[b] = the first class of logits[b] (order as above); adversarial =
+ * pred != y and no logit of the row is NaN (a label outside [0, K) is never adversarial).  If adversarial: n = ||x - x0||_inf; if
+ * n < res[b]: adv = x, res[b] = n; then x = x0 + 0.9 (x - x0).  flags[b] = EE_FAB_ADV | EE_FAB_IMPROVED as they apply.  Then
+ * counter[0] += 1 (this launch never reads it).  B == 0 or per_sample == 0 launches nothing and leaves the counter. */
+int ee_fab_commit_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res, int *pred,
+                      int *flags, int *counter, int64_t per_sample, void *stream);
+
 /* CannyFilter_BPDA (utils/core.py:386-505; AWP configs): no alpha mask, NMS by multiplication, thresholds through
  * To_compare (core.py:329-358), hysteresis through To_eq (core.py:361-382).  thresholds given, hysteresis=True.
  *   forward: edge, thin (the thinned magnitude), t2 (the {0, .5, 1} threshold map) [B,1,H,W]; thin / t2 feed the backward.
@@ -783,7 +830,11 @@ int ee_batch_aug_u8_f32(const uint8_t *data, const int64_t *labels, const int32_
 #define EE_K_SQATK_INIT 23   /* ee_sqatk_init_f32 */
 #define EE_K_SQATK_MARGIN 24 /* ee_sqatk_margin_f32 */
 #define EE_K_SQATK_STEP 25   /* ee_sqatk_step_f32 */
-#define EE_K_COUNT 26
+#define EE_K_FAB_DIFF 26     /* ee_fab_diff_f32 */
+#define EE_K_FAB_PROJ 27     /* ee_fab_proj_linf_f32 */
+#define EE_K_FAB_STEP 28     /* ee_fab_step_f32 */
+#define EE_K_FAB_COMMIT 29   /* ee_fab_commit_f32 */
+#define EE_K_COUNT 30
 int ee_prof_enable(int on);
 /* records one empty start/stop bracket on `stream` (family EE_K_EMPTY): callers subtract its mean from the other
  * families' means, because a HIP event pair costs ~4-5 us on gfx950 - comparable to the kernels being timed */

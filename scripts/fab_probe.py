@@ -1,0 +1,117 @@
+#!/usr/bin/env python3
+"""What a FAB-T iteration costs next to the work it shares with the attacks that exist: one PGD iteration (forward + backward) plus one
+eval forward.
+
+Eval mode, batch 100 of synthetic 3x64x64 images, 200 classes, graph replay (EEADV_GRAPH=1), on `resnet18` and `resnet18_EE_square`
+(the Tiny-ImageNet models).  Per-iteration time: CUDA events around whole runs of 100 and of 20 iterations, alternating PGD and FAB-T
+(one target: the second class of the clean logits), median of `reps`; (t100 - t20) / 80 leaves out what a run pays once.  The eval
+forward: a captured graph of 16 forwards under no_grad, per forward.  The projection launch alone (2 x 100 problems of 12288 coordinates,
+on a gradient and an iterate taken from a real run): CUDA events around 50 launches, per launch, on both paths.  The networks are
+untrained: labels are their own clean predictions.
+
+    python scripts/fab_probe.py [reps]      -> a few text lines, then one JSON line per model
+"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "edge-enhancement_amd")
+
+
+def main():
+    os.environ["EEADV_GRAPH"] = "1"
+    sys.path[:0] = [PKG]
+    import torch
+    import utils.attacks as A
+    from eeadv import engine, models as M, ops, runtime
+
+    if not torch.cuda.is_available():
+        raise SystemExit("fab_probe: needs a ROCm device (a time taken on the host says nothing)")
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
+    dev = torch.device("cuda", 0)
+    eps = 16 / 255
+
+    class Args:
+        random, epsilon = True, eps
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b)
+
+    def median(v):
+        return sorted(v)[len(v) // 2]
+
+    for name in ("resnet18", "resnet18_EE_square"):
+        torch.manual_seed(0)
+        if name == "resnet18":
+            m = M.make_resnet(18, "tiny")
+        else:
+            m = M.make_resnet_ee(18, "tiny", True, cize=64, r=8, w=1.0, with_gf=False, low=38.0, high=76.0, alpha=0.0, sigma=1.0,
+                                 type_canny="CannyFilter_step125_1", epsilon=eps, n_queries=1)
+        m = m.to(dev).eval()
+        g = torch.Generator().manual_seed(1)
+        x = torch.rand(100, 3, 64, 64, generator=g).to(dev)
+        with torch.no_grad():
+            order = ops.topk(m(x).float().contiguous(), None, 2)[0]
+        y, t = order[:, 0].contiguous(), order[:, 1].contiguous()
+        runs = {"pgd": lambda k: A.PGD(m, Args, x, y, k, 2 / 255), "fab_t": lambda k: engine.fab_loop(m, x, y, t, k, eps)}
+        for fn in runs.values():  # captures and warm-up of both lengths
+            for k in (100, 20, 100, 20):
+                fn(k)
+        torch.cuda.synchronize()
+        ms = {(n, k): [] for n in runs for k in (100, 20)}
+        for _ in range(reps):
+            for k in (100, 20):
+                for n, fn in runs.items():
+                    ms[(n, k)].append(timed(lambda: fn(k)))
+        out = {"model": name, "batch": 100, "reps": reps}
+        for n in runs:
+            t100, t20 = median(ms[(n, 100)]), median(ms[(n, 20)])
+            out[n + "_ms_100"], out[n + "_ms_20"] = round(t100, 3), round(t20, 3)
+            out[n + "_iter_ms"] = round((t100 - t20) / 80, 4)
+        # the eval forward, replayed from a graph of 16
+        runtime.draw_state(dev)
+        xs = x.clone()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side), torch.no_grad():
+            m(xs)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode=runtime.capture_mode()), torch.no_grad():
+            for _ in range(16):
+                m(xs)
+        graph.replay()
+        torch.cuda.synchronize()
+        out["eval_fwd_ms"] = round(median([timed(graph.replay) for _ in range(reps)]) / 16, 4)
+        shared = out["pgd_iter_ms"] + out["eval_fwd_ms"]
+        out["fab_over_shared"] = round(out["fab_t_iter_ms"] / shared, 4)
+        out["fab_extra_us_per_iter"] = round(1e3 * (out["fab_t_iter_ms"] - shared), 1)
+        # the projection launch alone, on the state of a real run's third iteration
+        run = engine._FabRun(x, y, 3)
+        run.load(x, y, t)
+        run.start()
+        for _ in range(2):
+            run.iteration(m)
+        w = engine.input_gradient(m, run.x, run.spec).contiguous()
+        xi = run.x.detach()
+        for path in ("resident", "streaming"):
+            launch = lambda: [ops.fab_proj_linf(xi, run.x0, w, run.df, path, run.scal) for _ in range(50)]
+            launch()
+            torch.cuda.synchronize()
+            out["proj_%s_us" % path] = round(1e3 * median([timed(launch) for _ in range(reps)]) / 50, 2)
+        res = engine.fab_loop(m, x, y, t, 100, eps)
+        out["fab_t_non_robust_after_one_target"] = round(1.0 - float(res[1].float().mean()), 3)
+        print("%s: PGD %.4f ms/iter + eval forward %.4f ms = %.4f ms; FAB-T %.4f ms/iter (x%.3f, +%.1f us); projection launch %.1f us resident, "
+              "%.1f us streaming" % (name, out["pgd_iter_ms"], out["eval_fwd_ms"], shared, out["fab_t_iter_ms"], out["fab_over_shared"],
+                                     out["fab_extra_us_per_iter"], out["proj_resident_us"], out["proj_streaming_us"]), flush=True)
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
