@@ -3,7 +3,7 @@
 //
 // One iteration is four launches around the classifier:
 //     ee_apgd_step_f32    x, x_old <- momentum step            (element-wise, 128-bit accesses, reads step[b] and the iteration counter)
-//     ee_apgd_loss_f32    logits -> row loss, dlogits, pred    (one wavefront per row, as ee_loss.hip)
+//     ee_apgd_loss_f32    logits -> row loss, dlogits, pred    (one wavefront per row, ee_rows.hpp)
 //     ee_apgd_book_f32    per-sample scalars -> flags          (one thread per sample; the checkpoint comes from sched[counter])
 //     ee_apgd_select_f32  copies under the flags, counter += 1 (element-wise; a sample without a flag costs the flag read)
 // Nothing here depends on a host value that changes from iteration to iteration, so one captured graph serves every iteration.
@@ -11,75 +11,19 @@
 // thread b alone and only reads the counter; select only reads the flags and is the one place that advances the counter.
 #include <math.h>
 
-#include "ee_common.hpp"
+#include "ee_rows.hpp"
 
 namespace {
 
 using namespace ee;
 
-constexpr int kRowsPerBlock = kBlock / kWave;
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// the order of ee_topk_i64: by value descending, ties to the lower index, NaN above everything
-__device__ __forceinline__ bool better(float va, int ia, float vb, int ib) {
-    const bool na = va != va, nb = vb != vb;
-    if (na != nb) return na;
-    if (!na && va != vb) return va > vb;
-    return ia < ib;
-}
-
-constexpr int kNone = 0x7fffffff;
-
-// the first M classes of one row in that order (every lane gets all of them); M <= K
-template <int M>
-__device__ __forceinline__ void row_top(const float *__restrict__ z, int K, int lane, int (&idx)[M], float (&val)[M]) {
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-        float bv = 0.0f;
-        int bi = kNone;
-        for (int c = lane; c < K; c += kWave) {
-            bool taken = false;
-#pragma unroll
-            for (int jj = 0; jj < M; ++jj) taken |= (jj < j && idx[jj] == c);
-            if (taken) continue;
-            const float v = z[c];
-            if (bi == kNone || better(v, c, bv, bi)) {
-                bv = v;
-                bi = c;
-            }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float ov = __shfl_xor(bv, off);
-            const int oi = __shfl_xor(bi, off);
-            if (oi != kNone && (bi == kNone || better(ov, oi, bv, bi))) {
-                bv = ov;
-                bi = oi;
-            }
-        }
-        idx[j] = bi;
-        val[j] = bv;
-    }
-}
-
 // ---- step ----------------------------------------------------------------------------------------------------------------------------
 struct StepOp {
     float a, eps;
-    __device__ __forceinline__ float proj(float v, float x0) const { return tclamp(tmin(tmax(v, x0 - eps), x0 + eps), 0.0f, 1.0f); }
     // returns x_new; the caller stores x as the new x_old
     __device__ __forceinline__ float operator()(float x, float xo, float g, float x0, float step) const {
-        const float z = proj(x + step * sgn(g), x0);
-        return proj((x + (z - x) * a) + (x - xo) * (1.0f - a), x0);
+        const float z = proj_linf(x + step * sgn(g), x0, eps);
+        return proj_linf((x + (z - x) * a) + (x - xo) * (1.0f - a), x0, eps);
     }
 };
 
@@ -158,14 +102,9 @@ __global__ __launch_bounds__(kBlock) void loss_kernel(const float *__restrict__ 
         int pi[1];
         float pv[1];
         row_top<1>(z, K, lane, pi, pv);
-        // ee_ce_f32's arithmetic: fp32 exponentials summed in double, lse = log(float(sum)), loss = lse - (z_y - max)
-        float m = -INFINITY;
-        for (int k = lane; k < K; k += kWave) m = fmaxf(m, z[k]);
-        const float mx = wave_max(m);
-        double s = 0.0;
-        for (int k = lane; k < K; k += kWave) s += static_cast<double>(expf(z[k] - mx));
-        const float lse = logf(static_cast<float>(wave_sum(s)));
-        for (int k = lane; k < K; k += kWave) d[k] = expf((z[k] - mx) - lse) - (k == y ? 1.0f : 0.0f);
+        float mx, lse;  // ee_ce_f32's loss and gradient: loss = lse - (z_y - max)
+        row_stats(z, K, lane, mx, lse);
+        for (int k = lane; k < K; k += kWave) d[k] = ce_grad(z[k], mx, lse, k == y, 1.0f);
         if (lane == 0) {
             row_loss[row] = lse - (z[y] - mx);
             pred[row] = pi[0] == y;
@@ -333,14 +272,12 @@ EE_API int ee_apgd_step_f32(float *x, float *x_old, const float *g, const float 
     if (!x || !x_old || !g || !x0 || !step || !counter) return EE_ERR_NULL;
     if (!aligned4(x) || !aligned4(x_old) || !aligned4(g) || !aligned4(x0) || !aligned4(step) || !aligned4(counter)) return EE_ERR_ALIGN;
     const bool vec = aligned16(x) && aligned16(x_old) && aligned16(g) && aligned16(x0);
-    const int64_t work = vec ? (n + 3) / 4 : n;
-    int64_t blocks = (work + kBlock - 1) / kBlock;
-    if (blocks > kMaxGrid) blocks = kMaxGrid;
+    const unsigned blocks = grid_for(vec ? (n + 3) / 4 : n);
     if (vec)
-        EE_LAUNCH(step_kernel<4>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, as_stream(stream), x, x_old, g, x0, step, counter, n,
+        EE_LAUNCH(step_kernel<4>, dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x_old, g, x0, step, counter, n,
                   per_sample, eps);
     else
-        EE_LAUNCH(step_kernel<1>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, as_stream(stream), x, x_old, g, x0, step, counter, n,
+        EE_LAUNCH(step_kernel<1>, dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x_old, g, x0, step, counter, n,
                   per_sample, eps);
     return launch_status();
 }
@@ -351,7 +288,7 @@ EE_API int ee_apgd_loss_f32(const float *logits, const int64_t *labels, const in
     if ((kind == EE_APGD_DLR && K < 3) || (kind == EE_APGD_DLR_T && K < 4)) return EE_ERR_UNSUPPORTED;
     if (B == 0) return EE_OK;
     if (!logits || !labels || !row_loss || !dlogits || !pred || (kind == EE_APGD_DLR_T && !targets)) return EE_ERR_NULL;
-    EE_LAUNCH(loss_kernel, dim3(static_cast<unsigned>((B + kRowsPerBlock - 1) / kRowsPerBlock)), dim3(kBlock), 0, as_stream(stream), logits,
+    EE_LAUNCH(loss_kernel, dim3(row_grid(B)), dim3(kBlock), 0, as_stream(stream), logits,
               labels, targets, B, K, kind, row_loss, dlogits, pred);
     return launch_status();
 }

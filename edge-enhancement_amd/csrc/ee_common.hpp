@@ -15,6 +15,12 @@ constexpr int kMaxGrid = 256 * 8; // 256 CUs x 8 workgroups: cap, then grid-stri
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
+// workgroups of kBlock threads for `work` items of a grid-stride kernel: at least one, at most kMaxGrid
+static inline unsigned grid_for(int64_t work) {
+    const int64_t blocks = (work + kBlock - 1) / kBlock;
+    return static_cast<unsigned>(blocks > kMaxGrid ? kMaxGrid : (blocks < 1 ? 1 : blocks));
+}
+
 // ---- XCD-aware workgroup numbering for kernels whose workgroups are (image group, result-channel block) pairs ------------------------
 // The 8 XCDs of a gfx950 take the workgroups of a 1-D grid round-robin, and each has an L2 of its own: what two workgroups share is fetched
 // once only if they sit on the same XCD.  weights_local: the channel block runs fastest (an XCD sees the filter slabs of the blocks
@@ -85,6 +91,10 @@ __device__ __forceinline__ float tclamp(float v, float lo, float hi) {
     float r = v < lo ? lo : v;
     r = r > hi ? hi : r;
     return (v != v) ? v : r;
+}
+// the eps-ball around x0, then the box: clamp(min(max(v, x0 - eps), x0 + eps), lo, hi) (attacks.py:26-27)
+__device__ __forceinline__ float proj_linf(float v, float x0, float eps, float lo = 0.0f, float hi = 1.0f) {
+    return tclamp(tmin(tmax(v, x0 - eps), x0 + eps), lo, hi);
 }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

@@ -14,10 +14,7 @@ using namespace ee;
 struct PgdStepOp {
     float a, eps, lo, hi;
     __device__ __forceinline__ float operator()(float x, float g, float x0) const {
-        float t = x + a * sgn(g);
-        t = tmax(t, x0 - eps);
-        t = tmin(t, x0 + eps);
-        return tclamp(t, lo, hi);
+        return proj_linf(x + a * sgn(g), x0, eps, lo, hi);
     }
 };
 
@@ -51,13 +48,10 @@ template <class Op>
 int launch_map3(float *out, const float *a, const float *b, const float *c, int64_t n, Op op, hipStream_t s) {
     if (n == 0) return EE_OK;
     const bool vec = aligned16(out) && aligned16(a) && aligned16(b) && (!c || aligned16(c));
-    const int64_t work = vec ? (n + 3) / 4 : n;
-    int64_t blocks = (work + kBlock - 1) / kBlock;
-    if (blocks > kMaxGrid) blocks = kMaxGrid;
     if (vec)
-        EE_LAUNCH((map3_kernel<4, Op>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, out, a, b, c, n, op);
+        EE_LAUNCH((map3_kernel<4, Op>), dim3(grid_for((n + 3) / 4)), dim3(kBlock), 0, s, out, a, b, c, n, op);
     else
-        EE_LAUNCH((map3_kernel<1, Op>), dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, s, out, a, b, c, n, op);
+        EE_LAUNCH((map3_kernel<1, Op>), dim3(grid_for(n)), dim3(kBlock), 0, s, out, a, b, c, n, op);
     return launch_status();
 }
 
@@ -234,11 +228,6 @@ __global__ __launch_bounds__(kL2Block) void l2_step_kernel(float *x, const float
     }
 }
 
-int grid_for(int64_t n) {
-    int64_t blocks = (n + kBlock - 1) / kBlock;
-    return static_cast<int>(blocks > kMaxGrid ? kMaxGrid : (blocks < 1 ? 1 : blocks));
-}
-
 }  // namespace
 
 EE_API int ee_pgd_init_f32(float *x, const float *x0, const float *noise, int64_t n, float lo, float hi, void *stream) {
@@ -254,7 +243,7 @@ EE_API int ee_pgd_init_rng_f32(float *x, const float *x0, int64_t n, float scale
     if (n < 0 || dist < 0 || dist > 1) return EE_ERR_SHAPE;
     if (n == 0) return EE_OK;
     if (!x || !x0) return EE_ERR_NULL;
-    const int g = grid_for((n + 3) / 4);
+    const unsigned g = grid_for((n + 3) / 4);
     if (dist == 0)
         EE_LAUNCH(init_rng_kernel<0>, dim3(g), dim3(kBlock), 0, as_stream(stream), x, x0, n, scale, seed, offset, lo, hi);
     else

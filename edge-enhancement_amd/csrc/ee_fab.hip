@@ -22,14 +22,12 @@
 // all passes, D <= 12288) and the streaming path (re-read through L2) share, so the two return the same bits.
 #include <math.h>
 
-#include "ee_common.hpp"
+#include "ee_rows.hpp"
 
 namespace {
 
 using namespace ee;
 
-constexpr int kRowsPerBlock = kBlock / kWave;
-constexpr int kNone = 0x7fffffff;
 constexpr float kEta = 1.05f, kBeta = 0.9f, kAlphaMax = 0.1f;
 
 constexpr int kProjBlock = 512;                               // 8 wavefronts per problem
@@ -38,40 +36,6 @@ constexpr int kProjVecs = 6;                                  // float4 groups p
 constexpr int kProjResident = kProjBlock * kProjVecs * 4;     // 12288 = 3*64*64
 constexpr int kCommitBlock = 512;
 constexpr int kCommitWaves = kCommitBlock / kWave;
-
-// the order of ee_topk_i64: by value descending, ties to the lower index, NaN above everything
-__device__ __forceinline__ bool better(float va, int ia, float vb, int ib) {
-    const bool na = va != va, nb = vb != vb;
-    if (na != nb) return na;
-    if (!na && va != vb) return va > vb;
-    return ia < ib;
-}
-
-// the first class of one row in that order (every lane of the wavefront gets it); nan: the row holds a NaN
-__device__ __forceinline__ int row_first(const float *__restrict__ z, int K, int lane, bool &nan) {
-    float bv = 0.0f;
-    int bi = kNone, any = 0;
-    for (int c = lane; c < K; c += kWave) {
-        const float v = z[c];
-        any |= (v != v);
-        if (bi == kNone || better(v, c, bv, bi)) {
-            bv = v;
-            bi = c;
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const float ov = __shfl_xor(bv, off);
-        const int oi = __shfl_xor(bi, off);
-        any |= __shfl_xor(any, off);
-        if (oi != kNone && (bi == kNone || better(ov, oi, bv, bi))) {
-            bv = ov;
-            bi = oi;
-        }
-    }
-    nan = any != 0;
-    return bi;
-}
 
 // the room of a coordinate at p that v pushes down (v > 0: to 0) or up (v < 0: to 1); 0 where v is 0 or NaN.  Never negative.
 __device__ __forceinline__ float room(float v, float p) { return fmaxf(v > 0.0f ? p : (v < 0.0f ? 1.0f - p : 0.0f), 0.0f); }
@@ -110,14 +74,9 @@ struct Reducer {
         for (int i = 1; i < kProjWaves; ++i) r += buf[i];
         return r;
     }
-    __device__ __forceinline__ double sum(double v) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-        return finish(v);
-    }
+    __device__ __forceinline__ double sum(double v) { return finish(wave_sum(v)); }
     __device__ __forceinline__ double max(double v) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+        v = wave_max(v);
         double *buf = sh + phase * kProjWaves;
         phase ^= 1;
         if ((threadIdx.x & (kWave - 1)) == 0) buf[threadIdx.x >> 6] = v;
@@ -343,8 +302,7 @@ __global__ __launch_bounds__(kCommitBlock) void commit_kernel(const float *__res
     } else {
         for (int64_t k = threadIdx.x; k < per_sample; k += kCommitBlock) m = fmaxf(m, fabsf(x[off + k] - x0[off + k]));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = wave_max(m);
     if (lane == 0) sh_max[wave] = m;
     __syncthreads();
     m = sh_max[0];
@@ -392,7 +350,7 @@ EE_API int ee_fab_diff_f32(const float *logits, const int64_t *labels, const int
         (reinterpret_cast<uintptr_t>(targets) & 7u))
         return EE_ERR_ALIGN;
     ProfScope prof(EE_K_FAB_DIFF, as_stream(stream));
-    EE_LAUNCH(diff_kernel, dim3(static_cast<unsigned>((B + kRowsPerBlock - 1) / kRowsPerBlock)), dim3(kBlock), 0, as_stream(stream), logits, labels,
+    EE_LAUNCH(diff_kernel, dim3(row_grid(B)), dim3(kBlock), 0, as_stream(stream), logits, labels,
               targets, B, K, df, dlogits, pred);
     return launch_status();
 }
@@ -427,14 +385,12 @@ EE_API int ee_fab_step_f32(float *x, const float *x0, const float *w, const floa
     if (!x || !x0 || !w || !scal) return EE_ERR_NULL;
     if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(scal)) return EE_ERR_ALIGN;
     const bool vec = aligned16(x) && aligned16(x0) && aligned16(w);
-    const int64_t work = vec ? (n + 3) / 4 : n;
-    int64_t blocks = (work + kBlock - 1) / kBlock;
-    if (blocks > kMaxGrid) blocks = kMaxGrid;
+    const unsigned blocks = grid_for(vec ? (n + 3) / 4 : n);
     ProfScope prof(EE_K_FAB_STEP, as_stream(stream));
     if (vec)
-        EE_LAUNCH(step_kernel<4>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+        EE_LAUNCH(step_kernel<4>, dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
     else
-        EE_LAUNCH(step_kernel<1>, dim3(static_cast<unsigned>(blocks)), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+        EE_LAUNCH(step_kernel<1>, dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
     return launch_status();
 }
 

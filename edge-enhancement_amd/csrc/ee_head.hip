@@ -6,7 +6,7 @@
 // time with coalesced 256-B reads (a first version with one row in flight was latency-bound at 150 us).  The weight / bias gradients are needed once per training step only and stay on the BLAS.
 //
 // CNN-body glue, not a row of SURVEY.md section 8: parity is "logits within 1e-4" through the model tests.
-#include "ee_common.hpp"
+#include "ee_rows.hpp"
 
 namespace {
 
@@ -112,13 +112,9 @@ __global__ __launch_bounds__(HEAD_NT) void pool_linear_fwd_kernel(const float *_
     }
 }
 
-// dfeat[b,c,:] = (sum_k dlogits[b,k] * W[k,c]) / HW        grid (B, ceil(C / 256)), one lane per channel
-__global__ __launch_bounds__(HEAD_NT) void pool_linear_bwd_kernel(const float *__restrict__ dlogits, const float *__restrict__ w,
-                                                                  float *__restrict__ dfeat, int C, int HW, int K) {
-    extern __shared__ float dl[];
-    const int b = blockIdx.x;
-    for (int k = threadIdx.x; k < K; k += HEAD_NT) dl[k] = dlogits[static_cast<size_t>(b) * K + k];
-    __syncthreads();
+// dfeat[b,c,:] = (sum_k dl[k] * W[k,c]) / HW for this thread's channel of image b, dl the image's logit gradient in LDS: the way back
+// through fc and the pooling that the two backward kernels share
+__device__ __forceinline__ void dlogits_to_dfeat(const float *dl, const float *__restrict__ w, float *__restrict__ dfeat, int b, int C, int HW, int K) {
     const int c = blockIdx.y * HEAD_NT + threadIdx.x;
     if (c >= C) return;
     const float inv = 1.0f / static_cast<float>(HW);
@@ -137,10 +133,19 @@ __global__ __launch_bounds__(HEAD_NT) void pool_linear_bwd_kernel(const float *_
     for (int i = 0; i < HW; ++i) d[i] = acc;
 }
 
+// dfeat[b,c,:] = (sum_k dlogits[b,k] * W[k,c]) / HW        grid (B, ceil(C / 256)), one lane per channel
+__global__ __launch_bounds__(HEAD_NT) void pool_linear_bwd_kernel(const float *__restrict__ dlogits, const float *__restrict__ w,
+                                                                  float *__restrict__ dfeat, int C, int HW, int K) {
+    extern __shared__ float dl[];
+    const int b = blockIdx.x;
+    for (int k = threadIdx.x; k < K; k += HEAD_NT) dl[k] = dlogits[static_cast<size_t>(b) * K + k];
+    __syncthreads();
+    dlogits_to_dfeat(dl, w, dfeat, b, C, HW, K);
+}
+
 // The cross-entropy gradient AND the head's backward in one launch (round 4): d CrossEntropyLoss(logits, labels) / d feat.  Every workgroup of
-// an image (ceil(C / 256) of them) forms the row's softmax itself - wavefront 0 with ee_loss.hip's row_stats expressions (row maximum, the
-// exponentials' sum carried in float64 through the same butterfly, its logarithm), then dl[k] = (exp((z_k - mx) - lse) - [k == y]) * gscale as
-// ce_kernel writes it - and goes on as pool_linear_bwd_kernel does: the same bits as the two launches, one launch (5 us) less per iteration.
+// an image (ceil(C / 256) of them) forms the row's softmax itself - wavefront 0 calls row_stats, then every thread ce_grad (ee_rows.hpp, as
+// ce_kernel does) - and goes on as pool_linear_bwd_kernel does: the same bits as the two launches, one launch (5 us) less per iteration.
 __global__ __launch_bounds__(HEAD_NT) void ce_pool_linear_bwd_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels, float gscale,
                                                                      const float *__restrict__ w, float *__restrict__ dfeat, int C, int HW, int K) {
     extern __shared__ float dl[];
@@ -148,37 +153,16 @@ __global__ __launch_bounds__(HEAD_NT) void ce_pool_linear_bwd_kernel(const float
     const int b = blockIdx.x, lane = threadIdx.x & 63;
     const float *z = logits + static_cast<size_t>(b) * K;
     if (threadIdx.x < 64) {
-        float m = -INFINITY;
-        for (int k = lane; k < K; k += 64) m = fmaxf(m, z[k]);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-        double sum = 0.0;
-        for (int k = lane; k < K; k += 64) sum += static_cast<double>(expf(z[k] - m));
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-        if (lane == 0) stats[0] = m, stats[1] = logf(static_cast<float>(sum));
+        float m, l;
+        row_stats(z, K, lane, m, l);
+        if (lane == 0) stats[0] = m, stats[1] = l;
     }
     __syncthreads();
     const float mx = stats[0], lse = stats[1];
     const int y = static_cast<int>(labels[b]);
-    for (int k = threadIdx.x; k < K; k += HEAD_NT) dl[k] = (expf((z[k] - mx) - lse) - (k == y ? 1.0f : 0.0f)) * gscale;
+    for (int k = threadIdx.x; k < K; k += HEAD_NT) dl[k] = ce_grad(z[k], mx, lse, k == y, gscale);
     __syncthreads();
-    const int c = blockIdx.y * HEAD_NT + threadIdx.x;
-    if (c >= C) return;
-    const float inv = 1.0f / static_cast<float>(HW);
-    float acc = 0.0f;
-    int k = 0;
-    for (; k + 8 <= K; k += 8) {
-        float wv[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wv[i] = w[static_cast<size_t>(k + i) * C + c];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) acc = fmaf(dl[k + i], wv[i], acc);
-    }
-    for (; k < K; ++k) acc = fmaf(dl[k], w[static_cast<size_t>(k) * C + c], acc);
-    acc *= inv;
-    float *d = dfeat + (static_cast<size_t>(b) * C + c) * HW;
-    for (int i = 0; i < HW; ++i) d[i] = acc;
+    dlogits_to_dfeat(dl, w, dfeat, b, C, HW, K);
 }
 
 }  // namespace

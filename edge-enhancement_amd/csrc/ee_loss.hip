@@ -7,35 +7,11 @@
 // every scalar bit-reproducible run to run.  These kernels are latency-bound (B*K*4 B <= 400 KB).
 #include <math.h>
 
-#include "ee_common.hpp"
+#include "ee_rows.hpp"
 
 namespace {
 
 using namespace ee;
-
-constexpr int kRowsPerBlock = kBlock / kWave;
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// max and log-sum-exp of one row, as log_softmax needs them:  logp_k = (z_k - mx) - lse
-__device__ __forceinline__ void row_stats(const float *__restrict__ z, int K, int lane, float &mx, float &lse) {
-    float m = -INFINITY;
-    for (int k = lane; k < K; k += kWave) m = fmaxf(m, z[k]);
-    mx = wave_max(m);
-    double s = 0.0;
-    for (int k = lane; k < K; k += kWave) s += static_cast<double>(expf(z[k] - mx));
-    s = wave_sum(s);
-    lse = logf(static_cast<float>(s));
-}
 
 __global__ __launch_bounds__(kBlock) void ce_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels, int B,
                                                     int K, float smoothing, float gscale, double *__restrict__ row_loss,
@@ -65,9 +41,8 @@ __global__ __launch_bounds__(kBlock) void ce_kernel(const float *__restrict__ lo
     if (dlogits) {
         float *d = dlogits + static_cast<size_t>(row) * K;
         for (int k = lane; k < K; k += kWave) {
-            const float pk = expf((z[k] - mx) - lse);
             const float wk = (smoothing == 0.0f) ? (k == y ? 1.0f : 0.0f) : (k == y ? w_on : w_off);
-            d[k] = (pk - wk) * gscale;
+            d[k] = ce_grad_soft(z[k], mx, lse, wk, gscale);
         }
     }
 }
@@ -158,14 +133,7 @@ __global__ __launch_bounds__(kBlock) void reduce_rows_kernel(const double *__res
     if (threadIdx.x == 0) out[0] = scale * (((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
 }
 
-// top-k by repeated wave arg-max; ties -> lower index; NaN ranks above everything (as torch.topk)
-__device__ __forceinline__ bool better(float va, int ia, float vb, int ib) {
-    const bool na = va != va, nb = vb != vb;
-    if (na != nb) return na;
-    if (!na && va != vb) return va > vb;
-    return ia < ib;
-}
-
+// top-k by repeated wave arg-max in ee_rows.hpp's order
 constexpr int kMaxTopK = 16;
 __global__ __launch_bounds__(kBlock) void topk_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels, int B,
                                                       int K, int k, int64_t *__restrict__ idx,
@@ -182,15 +150,19 @@ __global__ __launch_bounds__(kBlock) void topk_kernel(const float *__restrict__ 
 #pragma unroll
     for (int j = 0; j < kMaxTopK; ++j) {
         if (j < k) {
+            // row_next(z, K, lane, chosen, j, bv) written out: through the shared function this kernel's control flow comes out
+            // differently and it measured slower at [100, 200], k = 5 - 13.98 and 14.10 us in two sessions against 13.58 .. 13.71 us over
+            // four sessions of this form (50 launches per replay, medians of 9 replays; within a session +-0.1 us).  The order itself is
+            // ee_rows.hpp's better(), and tests/test_gpu_shared_rows.py holds this loop to row_next's picks.
             float bv = 0.0f;
-            int bi = 0x7fffffff;
+            int bi = kNone;
             for (int c = lane; c < K; c += kWave) {
                 bool taken = false;
 #pragma unroll
                 for (int jj = 0; jj < kMaxTopK; ++jj) taken |= (jj < j && chosen[jj] == c);
                 if (taken) continue;
                 const float v = z[c];
-                if (bi == 0x7fffffff || better(v, c, bv, bi)) {
+                if (bi == kNone || better(v, c, bv, bi)) {
                     bv = v;
                     bi = c;
                 }
@@ -199,7 +171,7 @@ __global__ __launch_bounds__(kBlock) void topk_kernel(const float *__restrict__ 
             for (int off = 32; off > 0; off >>= 1) {
                 const float ov = __shfl_xor(bv, off);
                 const int oi = __shfl_xor(bi, off);
-                if (oi != 0x7fffffff && (bi == 0x7fffffff || better(ov, oi, bv, bi))) {
+                if (oi != kNone && (bi == kNone || better(ov, oi, bv, bi))) {
                     bv = ov;
                     bi = oi;
                 }
@@ -212,8 +184,6 @@ __global__ __launch_bounds__(kBlock) void topk_kernel(const float *__restrict__ 
     if (lane == 0 && correct && hit >= 0)
         for (int j = hit; j < k; ++j) atomicAdd(&correct[j], 1ULL);
 }
-
-inline unsigned row_grid(int B) { return static_cast<unsigned>((B + kRowsPerBlock - 1) / kRowsPerBlock); }
 
 // ---- the last two layers of a LeNet-style classifier and the cross-entropy behind them, gradient only ----------------------------------
 // `return self.fc2(F.relu(self.fc1(x)))` (MNIST/models_mnist/Net2.py:27-28) followed by CrossEntropyLoss (attacks.py:23): given the
@@ -237,7 +207,7 @@ __global__ __launch_bounds__(kBlock) void fc_ce_grad_kernel(const float *__restr
         const float *wr = w2 + static_cast<size_t>(k) * Hd;
         float acc = 0.0f;
         for (int j = lane; j < Hd; j += kWave) acc = fmaf(wr[j], h[j], acc);
-        acc = wave_sum(acc);
+        acc = static_cast<float>(wave_sum(static_cast<double>(acc)));  // the double butterfly, rounded once
         if (lane == 0) lg[k] = acc + (b2 ? b2[k] : 0.0f);
     }
     __syncthreads();
@@ -246,7 +216,7 @@ __global__ __launch_bounds__(kBlock) void fc_ce_grad_kernel(const float *__restr
         row_stats(lg, K, lane, mx, lse);
         const int y = static_cast<int>(labels[row]);
         for (int k = lane; k < K; k += kWave) {
-            dl[k] = (expf((lg[k] - mx) - lse) - (k == y ? 1.0f : 0.0f)) * gscale;
+            dl[k] = ce_grad(lg[k], mx, lse, k == y, gscale);
             if (logits_out) logits_out[static_cast<size_t>(row) * K + k] = lg[k];
         }
     }
@@ -291,7 +261,7 @@ __global__ __launch_bounds__(kBlock) void fc_ce_grad_small_kernel(const float *_
         float acc = 0.0f;
 #pragma unroll
         for (int i = 0; i < JP; ++i) acc = fmaf(in[i] ? w[k][i] : 0.0f, hv[i], acc);
-        acc = wave_sum(acc);
+        acc = static_cast<float>(wave_sum(static_cast<double>(acc)));
         if (lane == 0) part[wave][k] = acc;
     }
     __syncthreads();
@@ -302,7 +272,7 @@ __global__ __launch_bounds__(kBlock) void fc_ce_grad_small_kernel(const float *_
         float mx, lse;
         row_stats(lg, K, lane, mx, lse);
         const int y = static_cast<int>(labels[row]);
-        if (lane < KM) dl[lane] = lane < K ? (expf((lg[lane] - mx) - lse) - (lane == y ? 1.0f : 0.0f)) * gscale : 0.0f;
+        if (lane < KM) dl[lane] = lane < K ? ce_grad(lg[lane], mx, lse, lane == y, gscale) : 0.0f;
         if (logits_out && lane < K) logits_out[static_cast<size_t>(row) * K + lane] = lg[lane];
     }
     __syncthreads();

@@ -9,17 +9,14 @@
 // it advances.
 #include <math.h>
 
-#include "ee_common.hpp"
+#include "ee_rows.hpp"
 
 namespace {
 
 using namespace ee;
 
-constexpr int kRowsPerBlock = kBlock / kWave;
 constexpr uint32_t kStreamWindow = 11u;  // Philox stream ids; 0 (the default) and 7 (ee_net2.hip) are taken
 constexpr uint32_t kStreamStripe = 12u;
-
-__device__ __forceinline__ float proj(float v, float x0, float eps) { return tclamp(tmin(tmax(v, x0 - eps), x0 + eps), 0.0f, 1.0f); }
 
 // ---- start ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void init_kernel(float *__restrict__ x_best, float *__restrict__ x_new, const float *__restrict__ x0,
@@ -102,7 +99,7 @@ __device__ __forceinline__ Sample sample_of(int64_t b, const int *__restrict__ f
 __device__ __forceinline__ float propose(float xb, float x0, const Sample &sm, int c, int h, int w, int s, float eps) {
     const bool in = h >= sm.vh && h < sm.vh + s && w >= sm.vw && w < sm.vw + s;
     const float delta = in ? (((sm.bits >> c) & 1u) ? 2.0f * eps : -2.0f * eps) : 0.0f;
-    return proj(xb + delta, x0, eps);
+    return proj_linf(xb + delta, x0, eps);
 }
 
 template <int VEC>
@@ -193,12 +190,6 @@ int check_shape(int B, int C, int H, int W) {
     return EE_OK;
 }
 
-unsigned grid_for(int64_t work) {
-    int64_t blocks = (work + kBlock - 1) / kBlock;
-    if (blocks > kMaxGrid) blocks = kMaxGrid;
-    return static_cast<unsigned>(blocks);
-}
-
 }  // namespace
 
 EE_API int ee_sqatk_init_f32(float *x_best, float *x_new, const float *x0, const int64_t *seed, int B, int C, int H, int W, float eps,
@@ -223,7 +214,7 @@ EE_API int ee_sqatk_margin_f32(const float *logits, const int64_t *labels, int B
         (reinterpret_cast<uintptr_t>(labels) & 7u))
         return EE_ERR_ALIGN;
     ProfScope prof(EE_K_SQATK_MARGIN, as_stream(stream));
-    EE_LAUNCH(margin_kernel, dim3(static_cast<unsigned>((B + kRowsPerBlock - 1) / kRowsPerBlock)), dim3(kBlock), 0, as_stream(stream), logits,
+    EE_LAUNCH(margin_kernel, dim3(row_grid(B)), dim3(kBlock), 0, as_stream(stream), logits,
               labels, B, K, margin_out, margin_min, queries, flags, counter);
     return launch_status();
 }

@@ -113,40 +113,52 @@ def attack_step_(model, x, x0, spec, step_size, eps, direction, lo, hi):
     ops.pgd_step_(x.detach(), g.contiguous(), x0, step_size, eps, lo, hi, direction)
 
 
-class _GraphedStep:
-    """`iters` consecutive PGD steps captured into one graph, bound to static buffers (one replay per attack: consecutive
-    replays of a one-step graph leave a ~12 us bubble between them)."""
+class _Captured:
+    """`iters` consecutive iterations of one attack captured into one graph (one replay covers them all: consecutive replays of a
+    one-iteration graph leave a ~12 us bubble between them).  `run` holds the static buffers the graph is bound to."""
 
-    def __init__(self, model, x0, spec, step_size, eps, direction, lo, hi, iters=1):
-        self.iters = iters
+    def __init__(self, model, device, iters, run=None):
+        self.model, self.device, self.iters, self.run, self.graph = weakref.ref(model), device, iters, run, None
+
+    def capture(self, model, body, start=None, warmup=None):
+        """Captures body(model).  start() sets the run up first; the state that the two warm-up executions (warmup(model), by default the
+        body) advance is rebuilt by the caller's own start / load before the first replay."""
+        runtime.draw_state(self.device)  # the device-side draws of a captured iteration (Add_Square, Net_2's dropout) need their state to exist
+        if start is not None:
+            start()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):  # warm-up outside capture: MIOpen algorithm search, allocator, autograd
+                (warmup or body)(model)
+        torch.cuda.current_stream().wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        from .models import deferred_bn_counters
+        with torch.cuda.graph(self.graph, capture_error_mode=runtime.capture_mode()):
+            with deferred_bn_counters():  # the BatchNorm counters of the captured forwards: one launch at the end of the graph
+                body(model)
+        return self
+
+
+def _times(n, step):
+    def body(model):
+        for _ in range(n):
+            step(model)
+    return body
+
+
+class _PgdBuffers:
+    """The static buffers of a captured PGD loop and its step on them."""
+
+    def __init__(self, x0, spec, step_size, eps, direction, lo, hi):
         self.x = torch.empty_like(x0).requires_grad_(True)
         self.x0 = torch.empty_like(x0)
         self.payload = torch.empty_like(spec.payload)
         self.spec = LossSpec(spec.kind, self.payload)
         self.cfg = (step_size, eps, direction, lo, hi)
-        self.model = weakref.ref(model)
-        self.graph = None
 
-    def _body(self, model):
-        step_size, eps, direction, lo, hi = self.cfg
-        attack_step_(model, self.x, self.x0, self.spec, step_size, eps, direction, lo, hi)
-
-    def capture(self, model, x_init, x0, payload):
-        runtime.draw_state(x0.device)  # the device-side draws of a captured iteration (Add_Square, Net_2's dropout) need their state to exist
-        self.load(x_init, x0, payload)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):  # warm-up outside capture: MIOpen algorithm search, allocator, autograd
-                self._body(model)
-        torch.cuda.current_stream().wait_stream(side)
-        self.load(x_init, x0, payload)
-        self.graph = torch.cuda.CUDAGraph()
-        from .models import deferred_bn_counters
-        with torch.cuda.graph(self.graph, capture_error_mode=runtime.capture_mode()):
-            with deferred_bn_counters():  # the BatchNorm counters of the `iters` forwards: one launch at the end of the graph
-                for _ in range(self.iters):
-                    self._body(model)
+    def step(self, model):
+        attack_step_(model, self.x, self.x0, self.spec, *self.cfg)
 
     def load(self, x_init, x0, payload):
         with torch.no_grad():
@@ -172,6 +184,35 @@ def clear_graphs():
     _GRAPHS.clear()
 
 
+def _chunk(n):
+    """Iterations per replay: the largest divisor of n not above MAX_ITERS_PER_GRAPH."""
+    return max(c for c in range(1, min(n, MAX_ITERS_PER_GRAPH) + 1) if n % c == 0)
+
+
+def _cached(key, model, build):
+    """The captured loop under `key`: the cached one if it was captured on this very model (ids are reused), else build()'s."""
+    gs = _GRAPHS.get(key)
+    if gs is not None and gs.model() is model:
+        return gs
+    # what runs before and around a capture (a start point, the two warm-up executions) are extra train-mode forwards: shield the
+    # BatchNorm statistics from them.  Restored through .data so that autograd graphs the caller still holds (TRADES / ALP keep
+    # `preds = model(x)` alive across the attack) do not see a version bump on the saved running statistics.
+    saved = {}
+    if model.training:
+        saved = {k: v.clone() for k, v in model.state_dict().items() if "running_" in k or "num_batches" in k}
+    gs = _GRAPHS[key] = build()
+    if saved:
+        live = model.state_dict()
+        for k, v in saved.items():
+            live[k].data.copy_(v)
+    return gs
+
+
+def _adv_where_fooled(robust, x0, x_adv):
+    """x0 where the sample is robust, else its adversarial point."""
+    return torch.where(robust.view(-1, *([1] * (x0.dim() - 1))), x0, x_adv)
+
+
 def pgd_loop(model, x0, x_init, spec, num_steps, step_size, eps, direction=1, lo=0.0, hi=1.0, use_graph=None):
     """Runs num_steps updates starting from x_init (a fresh tensor the loop may update in place); returns a
     detached tensor.  attacks.py:19-27: x = clamp(min(max(x + dir*alpha*sign(g), x0-eps), x0+eps), 0, 1)."""
@@ -182,31 +223,21 @@ def pgd_loop(model, x0, x_init, spec, num_steps, step_size, eps, direction=1, lo
     if use_graph and num_steps > min(PROBE_ITERS, num_steps):
         probe = min(PROBE_ITERS, num_steps)
         n_graph = num_steps - probe
-        chunk = max(c for c in range(1, min(n_graph, MAX_ITERS_PER_GRAPH) + 1) if n_graph % c == 0)  # iterations per replay
-        key = (id(model), model.training, tuple(x0.shape), spec.kind, tuple(spec.payload.shape), spec.payload.dtype,
+        chunk = _chunk(n_graph)
+        key = ("pgd", id(model), model.training, tuple(x0.shape), spec.kind, tuple(spec.payload.shape), spec.payload.dtype,
                float(step_size), float(eps), direction, lo, hi, x0.device.index, chunk)
-        gs = _GRAPHS.get(key)
-        if gs is not None and gs.model() is not model:
-            gs = None
-        if gs is None:
-            gs = _GraphedStep(model, x0, spec, step_size, eps, direction, lo, hi, iters=chunk)
-            # the two warm-up executions before capture are extra train-mode forwards: shield the BatchNorm statistics
-            # from them.  Restored through .data so that autograd graphs the caller still holds (TRADES / ALP keep
-            # `preds = model(x)` alive across the attack) do not see a version bump on the saved running statistics.
-            saved = {}
-            if model.training:
-                saved = {k: v.clone() for k, v in model.state_dict().items() if "running_" in k or "num_batches" in k}
-            gs.capture(model, x_init, x0, spec.payload)
-            if saved:
-                live = model.state_dict()
-                for k, v in saved.items():
-                    live[k].data.copy_(v)
-            _GRAPHS[key] = gs
-        gs.load(x_init.detach().contiguous(), x0, spec.payload)
+
+        def build():
+            bufs = _PgdBuffers(x0, spec, step_size, eps, direction, lo, hi)
+            bufs.load(x_init, x0, spec.payload)
+            return _Captured(model, x0.device, chunk, bufs).capture(model, _times(chunk, bufs.step), warmup=bufs.step)
+
+        gs = _cached(key, model, build)
+        gs.run.load(x_init.detach().contiguous(), x0, spec.payload)
         refresh_dense_weights()  # weight-derived buffers the captured kernels read (functional.Conv3x3Map2Fn)
-        for _ in range(n_graph // chunk):
+        for _ in range(n_graph // gs.iters):
             gs.graph.replay()
-        x = gs.x.detach().clone()
+        x = gs.run.x.detach().clone()
         if probe:
             # the probed iterations come LAST: their first kernel then follows an iteration's last one, caches as warm as inside the
             # graph (as the attack's first iteration, right behind the parameter update, the front-end kernel read its tables cold and
@@ -317,37 +348,7 @@ class _ApgdRun:
     def result(self):
         with torch.no_grad():
             robust = self.istate[ops.APGD_I_ROBUST] != 0
-            keep = robust.view(-1, *([1] * (self.x0.dim() - 1)))
-            return torch.where(keep, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
-
-
-class _GraphedApgd:
-    """`iters` consecutive APGD iterations captured into one graph over the static buffers of an _ApgdRun.  The gradient enters through
-    run.g and leaves through it (one copy per replay): inside the graph each iteration reads the autograd result of the one before."""
-
-    def __init__(self, model, run, iters):
-        self.run, self.iters, self.model, self.graph = run, iters, weakref.ref(model), None
-
-    def _body(self, model):
-        g = self.run.g
-        for _ in range(self.iters):
-            g = self.run.iteration(model, g)
-        self.run.g.copy_(g)
-
-    def capture(self, model):
-        runtime.draw_state(self.run.x0.device)
-        self.run.start(model)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):  # warm-up outside capture, as _GraphedStep.capture; the state it advances is rebuilt by the next start()
-                self._body(model)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        from .models import deferred_bn_counters
-        with torch.cuda.graph(self.graph, capture_error_mode=runtime.capture_mode()):
-            with deferred_bn_counters():
-                self._body(model)
+            return _adv_where_fooled(robust, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
 
 
 def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None):
@@ -373,28 +374,26 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
         for _ in range(n_iter):
             g = run.iteration(model, g)
         return run.result()
-    chunk = max(c for c in range(1, min(n_iter, MAX_ITERS_PER_GRAPH) + 1) if n_iter % c == 0)
+    chunk = _chunk(n_iter)
     key = ("apgd", id(model), model.training, tuple(x0.shape), loss, n_iter, float(eps), x0.device.index, chunk)
-    gs = _GRAPHS.get(key)
-    if gs is not None and gs.model() is not model:
-        gs = None
-    if gs is None:
+
+    def build():
         run = _ApgdRun(x0, y, n_iter, eps, loss)
         run.load(x_init, x0, y, targets)
-        gs = _GraphedApgd(model, run, chunk)
-        saved = {}
-        if model.training:  # as pgd_loop: the start point and warm-up passes before the capture are extra train-mode forwards
-            saved = {k: v.clone() for k, v in model.state_dict().items() if "running_" in k or "num_batches" in k}
-        gs.capture(model)
-        if saved:
-            live = model.state_dict()
-            for k, v in saved.items():
-                live[k].data.copy_(v)
-        _GRAPHS[key] = gs
+
+        def body(model):  # the gradient enters through run.g and leaves through it (one copy per replay): inside the graph each
+            g = run.g     # iteration reads the autograd result of the one before
+            for _ in range(chunk):
+                g = run.iteration(model, g)
+            run.g.copy_(g)
+
+        return _Captured(model, x0.device, chunk, run).capture(model, body, start=lambda: run.start(model))
+
+    gs = _cached(key, model, build)
     gs.run.load(x_init, x0, y, targets)
     refresh_dense_weights()
     gs.run.start(model)
-    for _ in range(n_iter // chunk):
+    for _ in range(n_iter // gs.iters):
         gs.graph.replay()
     return gs.run.result()
 
@@ -473,34 +472,7 @@ class _SquareRun:
     def result(self):
         with torch.no_grad():
             robust = self.margin_min > 0
-            keep = robust.view(-1, 1, 1, 1)
-            return torch.where(keep, self.x0, self.x_best), robust, self.queries.clone()
-
-
-class _GraphedSquare:
-    """`iters` consecutive Square iterations captured into one graph over the static buffers of a _SquareRun."""
-
-    def __init__(self, model, run, iters):
-        self.run, self.iters, self.model, self.graph = run, iters, weakref.ref(model), None
-
-    def _body(self, model):
-        for _ in range(self.iters):
-            self.run.iteration(model)
-
-    def capture(self, model):
-        runtime.draw_state(self.run.x0.device)
-        self.run.start(model)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):  # warm-up outside capture, as _GraphedStep.capture; the state it advances is rebuilt by the next start()
-                self._body(model)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        from .models import deferred_bn_counters
-        with torch.cuda.graph(self.graph, capture_error_mode=runtime.capture_mode()):
-            with deferred_bn_counters():
-                self._body(model)
+            return _adv_where_fooled(robust, self.x0, self.x_best), robust, self.queries.clone()
 
 
 def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=None, early_exit=True):
@@ -533,22 +505,13 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
         run, gs = _SquareRun(x0, y, n_queries, eps), None
     else:
         key = ("square", id(model), model.training, tuple(x0.shape), n_queries, float(eps), x0.device.index, chunk)
-        gs = _GRAPHS.get(key)
-        if gs is not None and gs.model() is not model:
-            gs = None
-        if gs is None:
+
+        def build():
             run = _SquareRun(x0, y, n_queries, eps)
             run.load(x0, y, seed)
-            gs = _GraphedSquare(model, run, chunk)
-            saved = {}
-            if model.training:  # as pgd_loop: the start and warm-up passes before the capture are extra train-mode forwards
-                saved = {k: v.clone() for k, v in model.state_dict().items() if "running_" in k or "num_batches" in k}
-            gs.capture(model)
-            if saved:
-                live = model.state_dict()
-                for k, v in saved.items():
-                    live[k].data.copy_(v)
-            _GRAPHS[key] = gs
+            return _Captured(model, x0.device, chunk, run).capture(model, _times(chunk, run.iteration), start=lambda: run.start(model))
+
+        gs = _cached(key, model, build)
         run = gs.run
         refresh_dense_weights()
     run.trace = trace
@@ -558,9 +521,9 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
     while done < n_prop:
         if early_exit and done and done % SQUARE_CHECK_EVERY == 0 and not run.any_active():
             break
-        if gs is not None and n_prop - done >= chunk:
+        if gs is not None and n_prop - done >= gs.iters:
             gs.graph.replay()
-            done += chunk
+            done += gs.iters
         else:
             run.iteration(model)
             done += 1
@@ -630,34 +593,7 @@ class _FabRun:
     def result(self, eps):
         with torch.no_grad():
             robust = ~(self.res <= eps)
-            keep = robust.view(-1, *([1] * (self.x0.dim() - 1)))
-            return torch.where(keep, self.x0, self.adv), robust, self.res.clone()
-
-
-class _GraphedFab:
-    """`iters` consecutive FAB-T iterations captured into one graph over the static buffers of a _FabRun."""
-
-    def __init__(self, model, run, iters):
-        self.run, self.iters, self.model, self.graph = run, iters, weakref.ref(model), None
-
-    def _body(self, model):
-        for _ in range(self.iters):
-            self.run.iteration(model)
-
-    def capture(self, model):
-        runtime.draw_state(self.run.x0.device)
-        self.run.start()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(2):  # warm-up outside capture, as _GraphedStep.capture; the state it advances is rebuilt by the next start()
-                self._body(model)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        from .models import deferred_bn_counters
-        with torch.cuda.graph(self.graph, capture_error_mode=runtime.capture_mode()):
-            with deferred_bn_counters():
-                self._body(model)
+            return _adv_where_fooled(robust, self.x0, self.adv), robust, self.res.clone()
 
 
 def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto"):
@@ -685,27 +621,18 @@ def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto"):
         for _ in range(n_iter):
             run.iteration(model)
         return run.result(float(eps))
-    chunk = max(c for c in range(1, min(n_iter, MAX_ITERS_PER_GRAPH) + 1) if n_iter % c == 0)
+    chunk = _chunk(n_iter)
     key = ("fab", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk)
-    gs = _GRAPHS.get(key)
-    if gs is not None and gs.model() is not model:
-        gs = None
-    if gs is None:
+
+    def build():
         run = _FabRun(x0, y, n_iter, path)
         run.load(x0, y, targets)
-        gs = _GraphedFab(model, run, chunk)
-        saved = {}
-        if model.training:  # as pgd_loop: the warm-up passes before the capture are extra train-mode forwards
-            saved = {k: v.clone() for k, v in model.state_dict().items() if "running_" in k or "num_batches" in k}
-        gs.capture(model)
-        if saved:
-            live = model.state_dict()
-            for k, v in saved.items():
-                live[k].data.copy_(v)
-        _GRAPHS[key] = gs
+        return _Captured(model, x0.device, chunk, run).capture(model, _times(chunk, run.iteration), start=run.start)
+
+    gs = _cached(key, model, build)
     gs.run.load(x0, y, targets)
     refresh_dense_weights()
     gs.run.start()
-    for _ in range(n_iter // chunk):
+    for _ in range(n_iter // gs.iters):
         gs.graph.replay()
     return gs.run.result(float(eps))

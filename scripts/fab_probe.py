@@ -24,7 +24,7 @@ def main():
     sys.path[:0] = [PKG]
     import torch
     import utils.attacks as A
-    from eeadv import engine, models as M, ops, runtime
+    from eeadv import engine, models as M, ops
 
     if not torch.cuda.is_available():
         raise SystemExit("fab_probe: needs a ROCm device (a time taken on the host says nothing)")
@@ -75,17 +75,13 @@ def main():
             out[n + "_ms_100"], out[n + "_ms_20"] = round(t100, 3), round(t20, 3)
             out[n + "_iter_ms"] = round((t100 - t20) / 80, 4)
         # the eval forward, replayed from a graph of 16
-        runtime.draw_state(dev)
         xs = x.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():
-            m(xs)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode=runtime.capture_mode()), torch.no_grad():
-            for _ in range(16):
-                m(xs)
+
+        def forward(model):
+            with torch.no_grad():
+                model(xs)
+
+        graph = engine._Captured(m, dev, 16).capture(m, engine._times(16, forward), warmup=forward).graph
         graph.replay()
         torch.cuda.synchronize()
         out["eval_fwd_ms"] = round(median([timed(graph.replay) for _ in range(reps)]) / 16, 4)

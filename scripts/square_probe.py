@@ -21,7 +21,7 @@ PKG = os.path.join(ROOT, "edge-enhancement_amd")
 def main():
     sys.path[:0] = [PKG]
     import torch
-    from eeadv import engine, models as M, runtime
+    from eeadv import engine, models as M
 
     if not torch.cuda.is_available():
         raise SystemExit("square_probe: needs a ROCm device (a time taken on the host says nothing)")
@@ -53,25 +53,15 @@ def main():
         # (b) the attack's own graph
         run = engine._SquareRun(x, y, n_queries, eps)
         run.load(x, y, 1)
-        gs = engine._GraphedSquare(m, run, iters)
-        gs.capture(m)
+        gs = engine._Captured(m, dev, iters, run).capture(m, engine._times(iters, run.iteration), start=lambda: run.start(m))
         # (a) the forward alone, captured the same way
-        runtime.draw_state(dev)
         xs = x.clone()
 
-        def forwards():
+        def forward(model):
             with torch.no_grad():
-                for _ in range(iters):
-                    m(xs)
+                model(xs)
 
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            forwards()
-        torch.cuda.current_stream().wait_stream(side)
-        fg = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(fg, capture_error_mode=runtime.capture_mode()):
-            forwards()
+        fg = engine._Captured(m, dev, iters).capture(m, engine._times(iters, forward)).graph
 
         def window(graph):
             for _ in range(replays):
