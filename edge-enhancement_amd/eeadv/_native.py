@@ -166,6 +166,12 @@ SIGNATURES = {
     "ee_batch_rrc_u8_f32": [c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_p, c_p, c_p],
     # data, labels, idx, offs, flip, coef, lut, idx_host, offs_host, N, B, C, H, W, pad, out, labels_out, stream
     "ee_batch_aug_u8_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
+    # x, y, id, order, keep, B, D, K, pool_x, pool_y, pool_id, pool_order, count, cap, stream
+    "ee_pool_append_f32": [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_l, c_p],
+    # pool_x, pool_y, pool_id, pool_order, count, cap, B, D, K, x, y, id, order, stream
+    "ee_pool_pop_f32": [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_l, c_i, c_p, c_p, c_p, c_p, c_p],
+    # robust, id, x_adv, B, n_valid, D, stage, N, robust_out, stage_out, adv_out, keep, stream
+    "ee_cascade_resolve_f32": [c_p, c_p, c_p, c_i, c_i, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_p],
     "ee_prof_enable": [c_i],
     "ee_prof_mark_empty": [c_p],
     "ee_prof_read": [c_i, c_p, c_p],

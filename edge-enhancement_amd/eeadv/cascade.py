@@ -1,0 +1,240 @@
+"""Survivor-only attack cascade over a whole validation split: clean -> APGD-CE -> APGD-T -> FAB-T -> Square.
+
+A sample enters a stage only if it is still correctly classified after every stage before it.  The attack loops replay captured graphs of
+ONE batch shape, so "only the survivors" is not a boolean index per batch: the survivors of several validation batches are regrouped into
+full batches of the captured shape.  Every stage has a pool of rows (image, label, global sample id, clean-logit class order) in HBM;
+whenever a pool holds a full batch it is popped, attacked by the stage's unchanged loop (utils.attacks.APGD / APGD_T / FAB_T / Square),
+what the stage broke is recorded by sample id and its survivors are appended to the next stage's pool.  After the last incoming batch the
+pools are flushed in stage order; a flushed batch is padded with copies of the pool's first row, which never reach the result.  The
+classifier runs in eval mode, so a sample's trajectory does not depend on who shares its batch (sections 11, 12) - except through the
+random draws, which stay what each attack draws today, per popped batch (nothing is keyed by the global id).
+
+Host reads: the host decides when to pop, so it reads a pool's count once per append - 4 bytes; nothing is added inside the attack loops.
+
+compaction="hip" (the default on a ROCm device) runs the pools as HIP kernels (csrc/ee_cascade.hip); compaction="torch" (the default for
+CPU tensors, what --no-cuda takes) states the same staging with index_select, and feeds identical batches to identical loops.
+"""
+import types
+
+import torch
+
+import utils.attacks as A
+
+from . import ops, runtime
+
+STAGES = ("APGD-CE", "APGD-T", "FAB-T", "Square")
+
+
+def default_stages(args, num_steps, n_class, n_target_classes=9):
+    """[(name, fn)] of AutoAttack's `standard` order; fn(model, args, x, y, order) -> (x_adv, robust) runs one stage on one full batch, `order`
+    being the class order of the clean logits [B, n_t + 1] (the targets of APGD-T and FAB-T: no clean forward of their own)."""
+    fab_iters = int(getattr(args, "fab_iters", 100))
+    queries = int(getattr(args, "square_queries", 5000))
+    return [
+        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce")),
+        ("APGD-T", lambda model, a, x, y, order: A.APGD_T(model, a, x, y, num_steps, n_class, n_target_classes, order=order)),
+        ("FAB-T", lambda model, a, x, y, order: A.FAB_T(model, a, x, y, n_class, fab_iters, n_target_classes, order=order)[:2]),
+        ("Square", lambda model, a, x, y, order: A.Square(model, a, x, y, queries)[:2]),
+    ]
+
+
+class _Rows:
+    """x [n, D], y [n], ids [n], order [n, K]: the fields of n pool rows (a pool's store, or the batch a pop fills)."""
+
+    def __init__(self, n, D, K, dtype, device):
+        self.x = torch.zeros((n, D), dtype=dtype, device=device)
+        self.y = torch.zeros(n, dtype=torch.int64, device=device)
+        self.ids = torch.zeros(n, dtype=torch.int64, device=device)
+        self.order = torch.zeros((n, K), dtype=torch.int64, device=device)
+
+    def fields(self):
+        return self.x, self.y, self.ids, self.order
+
+
+class _HipPool:
+    """cap = 2 B rows in HBM and their count on the device (csrc/ee_cascade.hip); `count` is the host's copy of it."""
+
+    def __init__(self, B, D, K, dtype, device):
+        if dtype != torch.float32:
+            raise TypeError("the device pools hold float32 images, got %s" % dtype)
+        self.B, self.rows, self.count = B, _Rows(2 * B, D, K, dtype, device), 0
+        self.count_dev = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def append(self, x, y, ids, order, keep):
+        ops.pool_append_(x, y, ids, order, keep, *self.rows.fields(), self.count_dev)
+        self.count = int(self.count_dev.item())  # THE host read of the cascade: 4 bytes per append, to decide when to pop
+        return self.count
+
+    def pop(self, batch):
+        ops.pool_pop_(*self.rows.fields(), self.count_dev, *batch.fields())
+        self.count = max(self.count - self.B, 0)  # what the count launch computes: no read
+
+
+class _TorchPool:
+    """The same pool in torch ops (index_select): the host path, and the statement the device pools are tested against."""
+
+    def __init__(self, B, D, K, dtype, device):
+        self.B, self.rows, self.count = B, _Rows(2 * B, D, K, dtype, device), 0
+
+    def append(self, x, y, ids, order, keep):
+        idx = torch.nonzero(keep.view(-1).to(torch.bool)).view(-1)
+        k = int(idx.numel())  # the same read: the number of kept rows
+        for dst, src in zip(self.rows.fields(), (x, y, ids, order)):
+            dst[self.count:self.count + k] = src.index_select(0, idx)
+        self.count += k
+        return self.count
+
+    def pop(self, batch):
+        B, c = self.B, self.count
+        idx = torch.arange(B, device=self.rows.x.device)
+        idx = torch.where(idx < c, idx, torch.zeros_like(idx))  # padding: the pool's row 0
+        for dst, src in zip(batch.fields(), self.rows.fields()):
+            dst.copy_(src.index_select(0, idx))
+            if c > B:
+                src[:c - B] = src[B:c].clone()
+        self.count = max(c - B, 0)
+
+
+def _resolve_torch(robust, ids, x_adv, n_valid, stage, robust_out, stage_out, adv_out, keep):
+    valid = torch.arange(robust.shape[0], device=robust.device) < n_valid
+    broken = ids[valid & ~robust]
+    robust_out[broken] = False
+    stage_out[broken] = stage
+    if adv_out is not None:
+        adv_out[broken] = x_adv[valid & ~robust]
+    keep.copy_(valid & robust)
+    return keep
+
+
+def _free_bytes(device):
+    """Bytes a new tensor on `device` could take: what the driver reports free plus what torch's allocator holds unused.  None on the host."""
+    if device.type != "cuda":
+        return None
+    free, _ = torch.cuda.mem_get_info(device)
+    return free + torch.cuda.memory_reserved(device) - torch.cuda.memory_allocated(device)
+
+
+def _count_samples(batches):
+    return sum(int(y.shape[0]) for _, y in batches)
+
+
+class _Run:
+    """One cascade: the pools, the one batch a pop fills, and the result arrays - everything sized by the first batch."""
+
+    def __init__(self, model, args, stages, x, N, K, keep_adv, compaction, batch_size=None):
+        self.model, self.args, self.stages = model, args, stages
+        self.on_dev = runtime.require_device(x, "cascade")
+        mode = compaction or ("hip" if self.on_dev else "torch")
+        if mode not in ("hip", "torch"):
+            raise ValueError("compaction must be 'hip' or 'torch', got %r" % (compaction,))
+        if mode == "hip" and not self.on_dev:
+            raise RuntimeError("compaction='hip' needs the batches on a ROCm device; the host path is compaction='torch'")
+        B, D, dev, S = int(batch_size or x.shape[0]), x[0].numel(), x.device, len(stages)
+        if not 1 <= B <= 4096:
+            raise ValueError("the cascade takes batches of 1 .. 4096 samples, got %d" % B)
+        if keep_adv:
+            free, need = _free_bytes(dev), (N + S * 2 * B + B) * D * x.element_size()
+            if free is not None and need > free:
+                raise MemoryError("keep_adv needs %.1f GiB on %s for the adversarial points of %d samples of %d values next to the pools, "
+                                  "%.1f GiB are free alongside the model: evaluate without keep_adv, or over a smaller split"
+                                  % (need / 2 ** 30, dev, N, D, free / 2 ** 30))
+        self.B, self.D, self.K, self.N, self.shape, self.dev = B, D, K, N, tuple(x.shape[1:]), dev
+        pool_cls = _HipPool if mode == "hip" else _TorchPool
+        self.resolve = ops.cascade_resolve_ if mode == "hip" else _resolve_torch
+        self.pools = [pool_cls(B, D, K, x.dtype, dev) for _ in range(S)]
+        self.batch = _Rows(B, D, K, x.dtype, dev)
+        self.robust = torch.ones(N, dtype=torch.bool, device=dev)
+        self.stage = torch.full((N,), S + 1, dtype=torch.int32, device=dev)
+        self.adv = torch.zeros((N, D), dtype=x.dtype, device=dev) if keep_adv else None
+        self.keep = torch.zeros(B, dtype=torch.bool, device=dev)
+        self.rows, self.runs, self.seen = [0] * S, [0] * S, 0
+
+    def clean(self, x, y):
+        """The clean stage of one incoming batch: one forward, the class order once, the correct rows into the first pool."""
+        b = int(x.shape[0])
+        if b > self.B or tuple(x.shape[1:]) != self.shape:
+            raise ValueError("batch of shape %s after a first batch of %s: the cascade runs one batch shape"
+                             % (tuple(x.shape), (self.B,) + self.shape))
+        if self.seen + b > self.N:
+            raise ValueError("more samples than n = %d" % self.N)
+        with torch.no_grad():
+            z = self.model(x)
+        if self.on_dev:
+            order = ops.topk(z.detach().float().contiguous(), None, self.K)[0]
+        else:
+            order = torch.sort(z, dim=1, descending=True, stable=True)[1][:, :self.K].contiguous()
+        y = y.contiguous()
+        ids = torch.arange(self.seen, self.seen + b, dtype=torch.int64, device=self.dev)
+        x2 = x.reshape(b, self.D).contiguous()
+        keep = torch.zeros(b, dtype=torch.bool, device=self.dev)
+        self.resolve((order[:, 0] == y).contiguous(), ids, x2, b, 0, self.robust, self.stage, None, keep)
+        if self.adv is not None:
+            self.adv[self.seen:self.seen + b] = x2
+        self.seen += b
+        if self.pools:
+            self.pools[0].append(x2, y, ids, order, keep)
+            self.drain(0)
+
+    def run_stage(self, s):
+        pool, batch, B = self.pools[s], self.batch, self.B
+        n_valid = min(pool.count, B)
+        pool.pop(batch)
+        x_adv, robust = self.stages[s][1](self.model, self.args, batch.x.view((B,) + self.shape), batch.y, batch.order)
+        self.resolve(robust.contiguous(), batch.ids, x_adv.detach().reshape(B, self.D).contiguous(), n_valid, s + 1, self.robust, self.stage,
+                     self.adv, self.keep)
+        self.rows[s] += n_valid
+        self.runs[s] += 1
+        if s + 1 < len(self.pools):
+            self.pools[s + 1].append(*batch.fields(), self.keep)  # the CLEAN rows: every stage starts from the sample itself
+            self.drain(s + 1)
+
+    def drain(self, s, flush=False):
+        while self.pools[s].count >= self.B or (flush and self.pools[s].count > 0):
+            self.run_stage(s)
+
+
+def evaluate(model, args, batches, n_class, keep_adv=False, compaction=None, stages=None, num_steps=None, n=None, device=None, batch_size=None):
+    """Runs the cascade over `batches`, a re-iterable of (x [b, ...], y [b] int64) with b <= B = `batch_size` (default: the size of the first
+    batch), the one shape the attack loops capture; the model is expected in eval mode.  `n`: the number of samples if known (else the batches are counted
+    in a pass of their own); `device`: where the batches are moved to (default: where they are); `num_steps`: APGD's iterations
+    (default args.num_steps_1); args.epsilon, args.fab_iters, args.square_queries and args.n_target_classes (default 9) as for the
+    attacks.  `stages`, a list of (name, fn) as default_stages gives, replaces the attacks (tests script them).
+
+    Returns a namespace: n, clean_correct, robust [n] bool and stage [n] int32 indexed by global sample id (the position in the
+    iteration order; stage 0 = misclassified clean, k = broken by stage k, len(stages) + 1 = survived), stage_names,
+    robust_after [per stage: samples still robust after it], rows_attacked [per stage: rows it ran on, padding excluded],
+    batches_attacked [per stage] and adv [n, ...] (keep_adv: the clean sample where robust or misclassified clean, else the point that
+    broke it; None otherwise)."""
+    if iter(batches) is batches:
+        batches = list(batches)
+    N = int(n) if n is not None else _count_samples(batches)
+    if N < 1:
+        raise ValueError("the cascade needs at least one sample")
+    n_t = min(int(getattr(args, "n_target_classes", 9)), int(n_class) - 1)
+    if stages is None:
+        if num_steps is None:
+            num_steps = args.num_steps_1
+        stages = default_stages(args, int(num_steps), n_class, n_t)
+    S = len(stages)
+    run = None
+    for x, y in batches:
+        if device is not None:
+            x, y = x.to(device), y.to(device)
+        x = x.detach()
+        if run is None:
+            run = _Run(model, args, stages, x, N, n_t + 1, keep_adv, compaction, batch_size)
+        run.clean(x, y)
+    if run.seen != N:
+        raise ValueError("%d samples came, n = %d" % (run.seen, N))
+    for s in range(S):
+        run.drain(s, flush=True)
+
+    counts = torch.bincount(run.stage.to(torch.int64), minlength=S + 2).tolist()  # one read at the end
+    clean_correct = N - counts[0]
+    robust_after, left = [], clean_correct
+    for s in range(S):
+        left -= counts[s + 1]
+        robust_after.append(left)
+    return types.SimpleNamespace(n=N, clean_correct=clean_correct, robust=run.robust, stage=run.stage, stage_names=[name for name, _ in stages],
+                                 robust_after=robust_after, rows_attacked=run.rows, batches_attacked=run.runs,
+                                 adv=None if run.adv is None else run.adv.view((N,) + run.shape))

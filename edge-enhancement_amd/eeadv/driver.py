@@ -38,7 +38,7 @@ def make_parser(description, default_data="synthetic", with_local_rank=False):
     parser.add_argument('--pretrained', dest='pretrained', action='store_true', help='use pre-trained model')
     parser.add_argument('--resume', default='', type=str, metavar='PATH', help='path to latest checkpoint, (default: None)')
     parser.add_argument('-e', '--evaluate', dest='evaluate', action='store_true', help='evaluate model on validation set')
-    parser.add_argument('--attack_method', default='PGD', type=str, metavar='PATH', help='attack method in validation: PGD, FGSM, CW, APGD-CE, APGD-T, APGD (CE then T), Square, APGD+Square (CE, T, then Square), FAB-T or APGD+FAB+Square (CE, T, FAB-T, then Square), (default: PGD)')
+    parser.add_argument('--attack_method', default='PGD', type=str, metavar='PATH', help='attack method in validation: PGD, FGSM, CW, APGD-CE, APGD-T, APGD (CE then T), Square, APGD+Square (CE, T, then Square), FAB-T, APGD+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch) or Cascade (the same four, each on the samples still robust, over the whole split), (default: PGD)')
     parser.add_argument('--square_queries', default=5000, type=int, help='forwards per sample of the Square attack at most (default: 5000); not the defence\'s n_queries')
     parser.add_argument('--fab_iters', default=100, type=int, help='iterations of FAB-T per target class (default: 100)')
     parser.add_argument('--no-cuda', action='store_true', default=False, help='disables CUDA training')
@@ -214,9 +214,31 @@ def with_module_prefix(state):
     return {("module." + k if not k.startswith("module.") else k): v for k, v in state.items()}
 
 
+def validate_cascade(val_loader, model, args, device, num_steps, n_class, log):
+    """--attack_method Cascade: eeadv.cascade.evaluate over the whole loader in place of the per-batch loop.  log(line) receives the clean
+    accuracy and one `robust accuracy after <stage>` line per stage (percent of this rank's samples).  Returns the final robust accuracy
+    twice, in the place of validate's (adv top-1, adv top-5), averaged over ranks."""
+    from . import cascade
+    if "tar" in args.method_name:
+        raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+    model.eval()
+    start = time.time()
+    res = cascade.evaluate(model, args, val_loader, n_class, num_steps=num_steps, device=device)
+    log(' * Cascade: {0} samples, {1} attacked rows per stage {2}, {3:.1f} s'.format(
+        res.n, '/'.join(res.stage_names), '/'.join(str(r) for r in res.rows_attacked), time.time() - start))
+    log(' * Cascade clean accuracy {0:.3f}'.format(100.0 * res.clean_correct / res.n))
+    for name, left in zip(res.stage_names, res.robust_after):
+        log(' * Cascade robust accuracy after {0} {1:.3f}'.format(name, 100.0 * left / res.n))
+    last = 100.0 * (res.robust_after[-1] if res.robust_after else res.clean_correct) / res.n
+    a1, = ddp.gather_mean(last)
+    return a1, a1
+
+
 def validate(val_loader, model, criterion, args, device, num_steps, step_size, log_dir, spec, local_result=False):
     """experiments_tinyimagenet.py:326-432.  Returns (adv top-1, adv top-5) averaged over ranks (the free-AT script returns
     its rank-local averages, AT_free_imagenet_ddp.py:403: local_result=True)."""
+    if args.attack_method == trainer.CASCADE_METHOD:
+        return validate_cascade(val_loader, model, args, device, num_steps, spec["num_classes"], lambda line: _log(line, log_dir))
     batch_time = AverageMeter()
     meters = _DeviceMeters(6, device)
     model.eval()

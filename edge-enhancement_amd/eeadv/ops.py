@@ -557,6 +557,58 @@ def fab_commit_(logits, labels, x, x0, adv, res, pred, flags, counter):
     return flags
 
 
+# ---- sample pools of the attack cascade (ee_cascade.hip) -------------------------------------------------------------
+def _u8(t, name, shape):
+    """A bool or uint8 flag vector as the uint8 pointer the kernels read (the same bytes: a view, no copy)."""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    return _chk(t, torch.uint8, name, shape)
+
+
+def _pool_ptrs(pool_x, pool_y, pool_id, pool_order, count):
+    cap, D = pool_x.shape
+    K = pool_order.shape[1]
+    ptrs = (_chk(pool_x, torch.float32, "pool_x"), _chk(pool_y, torch.int64, "pool_y", (cap,)), _chk(pool_id, torch.int64, "pool_id", (cap,)),
+            _chk(pool_order, torch.int64, "pool_order", (cap, K)), _chk(count, torch.int32, "count", (1,)))
+    return ptrs, cap, D, K
+
+
+def pool_append_(x, y, ids, order, keep, pool_x, pool_y, pool_id, pool_order, count):
+    """The rows of the batch (x [B,D] f32, y, ids [B] i64, order [B,K] i64) with keep [B] (bool / uint8) set go behind the count [1] int32
+    rows already in the pool (pool_x [cap,D], pool_y, pool_id [cap], pool_order [cap,K]), in source order; then count += kept.  The caller
+    keeps count + kept <= cap."""
+    ptrs, cap, D, K = _pool_ptrs(pool_x, pool_y, pool_id, pool_order, count)
+    B = x.shape[0]
+    N.check(N.lib.ee_pool_append_f32(_chk(x, torch.float32, "x", (B, D)), _chk(y, torch.int64, "y", (B,)), _chk(ids, torch.int64, "ids", (B,)),
+                                     _chk(order, torch.int64, "order", (B, K)), _u8(keep, "keep", (B,)), B, D, K, *ptrs, cap, _stream()),
+            "ee_pool_append_f32")
+    return count
+
+
+def pool_pop_(pool_x, pool_y, pool_id, pool_order, count, x, y, ids, order):
+    """The first B pool rows into the batch buffers (x [B,D], y, ids [B], order [B,K]; a pool with fewer than B rows pads with its row 0), the
+    remaining rows to the front, count = max(count - B, 0).  The caller pops at count < 2 B <= cap."""
+    ptrs, cap, D, K = _pool_ptrs(pool_x, pool_y, pool_id, pool_order, count)
+    B = x.shape[0]
+    N.check(N.lib.ee_pool_pop_f32(*ptrs, cap, B, D, K, _chk(x, torch.float32, "x", (B, D)), _chk(y, torch.int64, "y", (B,)),
+                                  _chk(ids, torch.int64, "ids", (B,)), _chk(order, torch.int64, "order", (B, K)), _stream()), "ee_pool_pop_f32")
+    return x
+
+
+def cascade_resolve_(robust, ids, x_adv, n_valid, stage, robust_out, stage_out, adv_out, keep):
+    """Rows b < n_valid of a stage's batch: keep[b] = robust[b]; a broken one writes robust_out[ids[b]] = 0, stage_out[ids[b]] = stage and
+    - adv_out [N,D] given - adv_out[ids[b]] = x_adv[b].  Every other row: keep[b] = 0.  robust, keep [B] and robust_out [N] are bool / uint8,
+    stage_out [N] int32."""
+    B = robust.shape[0]
+    n = robust_out.shape[0]
+    D = x_adv.numel() // B
+    N.check(N.lib.ee_cascade_resolve_f32(_u8(robust, "robust", (B,)), _chk(ids, torch.int64, "ids", (B,)), _chk(x_adv, torch.float32, "x_adv"), B,
+                                         int(n_valid), D, int(stage), n, _u8(robust_out, "robust_out", (n,)),
+                                         _chk(stage_out, torch.int32, "stage_out", (n,)), _opt(adv_out, torch.float32, "adv_out", (n, D)),
+                                         _u8(keep, "keep", (B,)), _stream()), "ee_cascade_resolve_f32")
+    return keep
+
+
 # ---- Add_Square ------------------------------------------------------------------------------------------------------
 def add_square_fwd(x, eps, stripe, sq_sign, sq_pos, sq_size):
     B, C, H, W = x.shape

@@ -730,12 +730,16 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         robust = robust & rf
         xs, rs, _ = A.Square(model, args, input, target, int(getattr(args, 'square_queries', 5000)))
         return torch.where((robust & ~rs).view(shape), xs, x_adv)
+    if args.attack_method == CASCADE_METHOD:
+        raise NotImplementedError("--attack_method Cascade regroups the survivors of a whole split: it runs as eeadv.cascade.evaluate over the "
+                                  "loader (driver.validate_cascade), not batch by batch")
     raise NotImplementedError
 
 
 APGD_METHODS = ('APGD-CE', 'APGD-T', 'APGD')
 SQUARE_METHODS = ('Square', 'APGD+Square')
 FAB_METHODS = ('FAB-T', 'APGD+FAB+Square')
+CASCADE_METHOD = 'Cascade'  # the same four attacks, each on the samples the ones before it left standing (eeadv.cascade)
 
 
 def validate_batch(model, criterion, args, input, target, device, num_steps, step_size, n_class):

@@ -218,18 +218,29 @@ def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, nois
     return x_adv, robust
 
 
-def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None):
-    """Targeted APGD on the DLR loss: one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most
-    nclass - 1 of them), each on the whole batch - samples fooled by an earlier target are carried along, which keeps one shape (one captured
-    graph) for all runs.  Returns (x_adv, robust) with the flags ANDed over the runs and, per sample, the first fooling point."""
-    x0 = inputs.detach()
-    n_t = min(int(n_target_classes), int(nclass) - 1)
+def _class_order(model, x0, n_t, what, order=None):
+    """The first n_t + 1 classes of the clean logits [B, n_t + 1] int64, by value descending, ties to the lower index; `order`, the same thing
+    computed by the caller (the cascade takes it from its own clean forward), is checked and returned without a forward."""
+    on_dev = runtime.require_device(x0, what)
+    if order is not None:
+        if tuple(order.shape) != (x0.shape[0], n_t + 1) or order.dtype != torch.int64:
+            raise ValueError("%s: order must be int64 of shape %s, got %s %s" % (what, (x0.shape[0], n_t + 1), order.dtype, tuple(order.shape)))
+        return order
     with torch.no_grad():
         z = model(x0)
-    if runtime.require_device(x0, "APGD_T"):
-        order = ops.topk(z.detach().float().contiguous(), None, n_t + 1)[0]
-    else:
-        order = torch.sort(z, dim=1, descending=True, stable=True)[1][:, :n_t + 1]
+    if on_dev:
+        return ops.topk(z.detach().float().contiguous(), None, n_t + 1)[0]
+    return torch.sort(z, dim=1, descending=True, stable=True)[1][:, :n_t + 1]
+
+
+def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None, order=None):
+    """Targeted APGD on the DLR loss: one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most
+    nclass - 1 of them), each on the whole batch - samples fooled by an earlier target are carried along, which keeps one shape (one captured
+    graph) for all runs.  Returns (x_adv, robust) with the flags ANDed over the runs and, per sample, the first fooling point.  `order`
+    [B, n_t + 1]: the class order of the clean logits if the caller has it already - the clean forward is then skipped."""
+    x0 = inputs.detach()
+    n_t = min(int(n_target_classes), int(nclass) - 1)
+    order = _class_order(model, x0, n_t, "APGD_T", order)
     x_adv = x0.clone()
     robust = torch.ones(x0.shape[0], dtype=torch.bool, device=x0.device)
     shape = (-1,) + (1,) * (x0.dim() - 1)
@@ -408,24 +419,20 @@ def _fab_host(model, x0, y, t, n_iter, trace=None):
     return adv, res
 
 
-def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9):
+def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, order=None):
     """Targeted FAB (Linf): one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most nclass - 1 of
     them, taken as APGD_T takes them), each on the whole batch from the clean point.  Returns (x_adv, robust, norm): norm [B] is the smallest
     ||adv - x0||_inf over all runs (+inf if no run found an adversarial point, 0 for a sample the clean forward already misclassifies),
     robust = not (norm <= args.epsilon), and x_adv is the inputs with every non-robust sample replaced by the point that attains its norm
     (the first one, among equals).  eps only thresholds the result - the search is not confined to the ball.  Deterministic.  The model runs in
     the mode the caller left it in.  On the device c2 = df + sum w_i (x0_i - x_i) is summed in double (csrc/ee_fab.hip); the host path
-    below forms the same sum of differences in the input's dtype - the public code's <w, x0> - (<w, x> - df) cancels in fp32."""
+    below forms the same sum of differences in the input's dtype - the public code's <w, x0> - (<w, x> - df) cancels in fp32.  `order`
+    [B, n_t + 1]: the class order of the clean logits if the caller has it already - the clean forward is then skipped."""
     x0 = inputs.detach()
     eps = float(args.epsilon)
     n_t = min(int(n_target_classes), int(nclass) - 1)
     on_dev = runtime.require_device(x0, "FAB_T")
-    with torch.no_grad():
-        z = model(x0)
-    if on_dev:
-        order = ops.topk(z.detach().float().contiguous(), None, n_t + 1)[0]
-    else:
-        order = torch.sort(z, dim=1, descending=True, stable=True)[1][:, :n_t + 1]
+    order = _class_order(model, x0, n_t, "FAB_T", order)
     shape = (-1,) + (1,) * (x0.dim() - 1)
     x_adv = x0.clone()
     inf = torch.full((x0.shape[0],), _INF, dtype=torch.float32 if on_dev else x0.dtype, device=x0.device)

@@ -803,6 +803,36 @@ int ee_batch_aug_u8_f32(const uint8_t *data, const int64_t *labels, const int32_
                         int H, int W, int pad, float *out, int64_t *labels_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sample pools of the survivor-only attack cascade (ee_cascade.hip).
+ * A pool is a row store of fixed capacity `cap` on the device: pool_x [cap, D] f32, pool_y [cap] i64 (labels), pool_id [cap] i64
+ * (global sample ids), pool_order [cap, K] i64 (the clean-logit class order: the targets of APGD-T and FAB-T) and count [1] i32, the
+ * number of rows held.  Rows are copied as bits (NaN payloads survive), with 16-byte accesses where both row starts are 16-byte
+ * aligned - decided per row - and word by word otherwise.  Any D >= 1, K >= 1, 1 <= B <= 4096 (EE_ERR_UNSUPPORTED beyond);
+ * f32 pointers 4-byte, i64 pointers 8-byte aligned (EE_ERR_ALIGN).  A count outside [0, cap] is read as the nearest bound.  Every
+ * loop's trip count follows from the launch shape and D.  The count is read by the copying launches and advanced by a launch of
+ * its own after them.
+ * ------------------------------------------------------------------------------------------- */
+/* Rows b of the batch (x [B,D], y, id [B], order [B,K]) with keep[b] != 0 go behind the count rows already in the pool, in source
+ * order: row b lands at count + #{i < b : keep[i] != 0}, counted inside the row's own workgroups; a destination >= cap is not
+ * written (the caller keeps count + kept <= cap).  Then count <- min(count + kept, cap).  Two launches. */
+int ee_pool_append_f32(const float *x, const int64_t *y, const int64_t *id, const int64_t *order, const uint8_t *keep, int B, long long D,
+                       int K, float *pool_x, int64_t *pool_y, int64_t *pool_id, int64_t *pool_order, int32_t *count, long long cap,
+                       void *stream);
+/* The first B pool rows go to the batch buffers (x [B,D], y, id [B], order [B,K]); a pool holding fewer than B rows fills the rest
+ * of the batch with copies of its row 0 (the caller ignores them).  Then rows [B, count) move to the front - the caller pops at
+ * count < 2 B, so source and destination rows of that launch are disjoint; cap >= 2 B (EE_ERR_SHAPE) - and
+ * count <- min(max(count - B, 0), B).  Three launches. */
+int ee_pool_pop_f32(float *pool_x, int64_t *pool_y, int64_t *pool_id, int64_t *pool_order, int32_t *count, long long cap, int B,
+                    long long D, int K, float *x, int64_t *y, int64_t *id, int64_t *order, void *stream);
+/* After a stage's run on a popped batch: robust [B] (u8, != 0: the stage left the sample correctly classified), id [B], x_adv [B,D]
+ * (the stage's result).  For b < n_valid (the rows that are no padding) with 0 <= id[b] < N:
+ *     keep[b] = robust[b] != 0;   a broken row writes robust_out[id[b]] = 0, stage_out[id[b]] = stage and, when adv_out [N,D]
+ *     is given, adv_out[id[b]] = x_adv[b] (bits).
+ * Every other row: keep[b] = 0, nothing else written.  keep [B] u8 is the flag vector of the append into the next pool.  One launch. */
+int ee_cascade_resolve_f32(const uint8_t *robust, const int64_t *id, const float *x_adv, int B, int n_valid, long long D, int stage,
+                           long long N, uint8_t *robust_out, int32_t *stage_out, float *adv_out, uint8_t *keep, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Optional built-in timing of the last launch of each kernel family (HIP events on `stream`).
  * Off by default; bench.py switches it on outside graph capture to measure kernel durations live.
  * ------------------------------------------------------------------------------------------- */
