@@ -95,7 +95,7 @@ def train(train_loader, model, awp_adversary, criterion, optimizer, epoch, args,
 
 def validate(val_loader, model, criterion, args, device, num_steps, step_size, log_dir):
     """experiments_cifar100_awp.py:353-435: PGD-`num_steps` in eval mode; lines to log/log.txt.  Returns (adv top-1, adv top-5)."""
-    if args.attack_method == trainer.CASCADE_METHOD:
+    if args.attack_method in trainer.CASCADE_METHODS:
         return driver.validate_cascade(val_loader, model, args, device, num_steps, SPEC["num_classes"], lambda line: _log(line, log_dir + 'log.txt'))
     batch_time = AverageMeter()
     meters = driver._DeviceMeters(6, device)
@@ -122,9 +122,10 @@ def validate(val_loader, model, criterion, args, device, num_steps, step_size, l
 def main(argv=None):
     """experiments_cifar100_awp.py:138-269"""
     args = parse_config_file(make_parser().parse_args(argv))
-    if args.attack_method != 'PGD' and args.attack_method not in trainer.APGD_METHODS + trainer.SQUARE_METHODS + trainer.FAB_METHODS + (trainer.CASCADE_METHOD,):
-        raise NotImplementedError("--attack_method %s: validation runs PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T, APGD+FAB+Square or Cascade" % args.attack_method)  # experiments_cifar100_awp.py:374-380
+    if args.attack_method != 'PGD' and args.attack_method not in trainer.EVAL_METHODS:
+        raise NotImplementedError("--attack_method %s: validation runs PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T, APGD+FAB+Square, Cascade, APGD-DLR, Rand or Cascade-Rand" % args.attack_method)  # experiments_cifar100_awp.py:374-380
     driver.data_source(args.data, SPEC)  # an unusable --data fails here, before a model is built
+    trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
     for key, default in (("step_size_2", args.get("step_size_1")), ("num_steps_3", args.get("num_steps_2"))):
         args.setdefault(key, default)
     args.setdefault("step_size_3", args.step_size_2)

@@ -103,7 +103,7 @@ def train(train_loader, model, awp_adversary, criterion, optimizer, epoch, args,
 
 def validate(val_loader, model, criterion, args, device, num_steps, step_size, log_dir):
     """experiments_tiny_awp.py:307-376: PGD-`num_steps` in eval mode; lines to log/log_pgd.txt.  Returns (adv top-1, adv top-5)."""
-    if args.attack_method == trainer.CASCADE_METHOD:
+    if args.attack_method in trainer.CASCADE_METHODS:
         return driver.validate_cascade(val_loader, model, args, device, num_steps, SPEC["num_classes"], lambda line: _log(line, log_dir + 'log_pgd.txt'))
     batch_time = AverageMeter()
     meters = driver._DeviceMeters(6, device)
@@ -130,10 +130,11 @@ def validate(val_loader, model, criterion, args, device, num_steps, step_size, l
 def main(argv=None):
     """experiments_tiny_awp.py:60-223"""
     args = parse_config_file(make_parser().parse_args(argv))
-    if args.attack_method != 'PGD' and args.attack_method not in trainer.APGD_METHODS + trainer.SQUARE_METHODS + trainer.FAB_METHODS + (trainer.CASCADE_METHOD,):
+    if args.attack_method != 'PGD' and args.attack_method not in trainer.EVAL_METHODS:
         raise SystemExit("--attack_method %s: %s; validation runs PGD" % (args.attack_method, AA_UNAVAILABLE) if args.attack_method == 'AA'
-                         else "--attack_method %s: the AWP driver validates with PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T, APGD+FAB+Square or Cascade" % args.attack_method)
+                         else "--attack_method %s: the AWP driver validates with PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T, APGD+FAB+Square, Cascade, APGD-DLR, Rand or Cascade-Rand" % args.attack_method)
     driver.data_source(args.data, SPEC)  # an unusable --data fails here, before a model is built
+    trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
     args.setdefault("cize", 64)
     args.num_classes = SPEC["num_classes"]
     use_cuda = not args.no_cuda and torch.cuda.is_available()

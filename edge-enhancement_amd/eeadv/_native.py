@@ -62,6 +62,8 @@ SIGNATURES = {
     "ee_apgd_book_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p],
     # x, g, x_best, g_best, x_best_adv, flags, counter, B, per_sample, stream
     "ee_apgd_select_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_p],
+    # g_acc, g, loss_acc, loss, loss_mean, k, E, B, per_sample, stream
+    "ee_apgd_eot_acc_f32": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_l, c_p],
     # x_best, x_new, x0, seed, B, C, H, W, eps, stream
     "ee_sqatk_init_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
     # logits, labels, B, K, margin_out, margin_min, queries, flags, counter, stream

@@ -38,6 +38,19 @@ def default_stages(args, num_steps, n_class, n_target_classes=9):
     ]
 
 
+def rand_stages(args, num_steps, eot_iter=None):
+    """[(name, fn)] of the public ensemble's `rand` order for randomised defences: APGD-CE, then APGD-DLR on its survivors, every gradient
+    averaged over eot_iter forwards (default args.eot_iter, else 20)."""
+    E = eot_iter if eot_iter is not None else getattr(args, "eot_iter", None)
+    E = 20 if E is None else int(E)
+    if E < 1:
+        raise ValueError("the rand stages need eot_iter >= 1, got %d" % E)
+    return [
+        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", eot_iter=E)),
+        ("APGD-DLR", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "dlr", eot_iter=E)),
+    ]
+
+
 class _Rows:
     """x [n, D], y [n], ids [n], order [n, K]: the fields of n pool rows (a pool's store, or the batch a pop fills)."""
 

@@ -38,7 +38,8 @@ def make_parser(description, default_data="synthetic", with_local_rank=False):
     parser.add_argument('--pretrained', dest='pretrained', action='store_true', help='use pre-trained model')
     parser.add_argument('--resume', default='', type=str, metavar='PATH', help='path to latest checkpoint, (default: None)')
     parser.add_argument('-e', '--evaluate', dest='evaluate', action='store_true', help='evaluate model on validation set')
-    parser.add_argument('--attack_method', default='PGD', type=str, metavar='PATH', help='attack method in validation: PGD, FGSM, CW, APGD-CE, APGD-T, APGD (CE then T), Square, APGD+Square (CE, T, then Square), FAB-T, APGD+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch) or Cascade (the same four, each on the samples still robust, over the whole split), (default: PGD)')
+    parser.add_argument('--attack_method', default='PGD', type=str, metavar='PATH', help='attack method in validation: PGD, FGSM, CW, APGD-CE, APGD-T, APGD (CE then T), Square, APGD+Square (CE, T, then Square), FAB-T, APGD+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch) Cascade (the same four, each on the samples still robust, over the whole split), APGD-DLR, Rand (APGD-CE then APGD-DLR, every gradient averaged over --eot_iter forwards: for defences that redraw at every forward) or Cascade-Rand (the same two, APGD-DLR on the survivors only), (default: PGD)')
+    parser.add_argument('--eot_iter', default=None, type=int, help='forwards every APGD gradient is averaged over (EOT); default: 20 for Rand and Cascade-Rand, 1 for APGD-CE and APGD-DLR; the other attacks have no EOT and refuse a value above 1')
     parser.add_argument('--square_queries', default=5000, type=int, help='forwards per sample of the Square attack at most (default: 5000); not the defence\'s n_queries')
     parser.add_argument('--fab_iters', default=100, type=int, help='iterations of FAB-T per target class (default: 100)')
     parser.add_argument('--no-cuda', action='store_true', default=False, help='disables CUDA training')
@@ -215,7 +216,7 @@ def with_module_prefix(state):
 
 
 def validate_cascade(val_loader, model, args, device, num_steps, n_class, log):
-    """--attack_method Cascade: eeadv.cascade.evaluate over the whole loader in place of the per-batch loop.  log(line) receives the clean
+    """--attack_method Cascade / Cascade-Rand: eeadv.cascade.evaluate over the whole loader in place of the per-batch loop.  log(line) receives the clean
     accuracy and one `robust accuracy after <stage>` line per stage (percent of this rank's samples).  Returns the final robust accuracy
     twice, in the place of validate's (adv top-1, adv top-5), averaged over ranks."""
     from . import cascade
@@ -223,7 +224,12 @@ def validate_cascade(val_loader, model, args, device, num_steps, n_class, log):
         raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
     model.eval()
     start = time.time()
-    res = cascade.evaluate(model, args, val_loader, n_class, num_steps=num_steps, device=device)
+    eot_iter, stages = trainer.eot_iter_for(args), None
+    if args.attack_method == trainer.CASCADE_RAND_METHOD:
+        if n_class < 3:
+            raise ValueError("--attack_method Cascade-Rand runs APGD-DLR, which needs at least 3 classes, not %d" % n_class)
+        stages = cascade.rand_stages(args, int(num_steps), eot_iter)
+    res = cascade.evaluate(model, args, val_loader, n_class, num_steps=num_steps, device=device, stages=stages)
     log(' * Cascade: {0} samples, {1} attacked rows per stage {2}, {3:.1f} s'.format(
         res.n, '/'.join(res.stage_names), '/'.join(str(r) for r in res.rows_attacked), time.time() - start))
     log(' * Cascade clean accuracy {0:.3f}'.format(100.0 * res.clean_correct / res.n))
@@ -237,7 +243,7 @@ def validate_cascade(val_loader, model, args, device, num_steps, n_class, log):
 def validate(val_loader, model, criterion, args, device, num_steps, step_size, log_dir, spec, local_result=False):
     """experiments_tinyimagenet.py:326-432.  Returns (adv top-1, adv top-5) averaged over ranks (the free-AT script returns
     its rank-local averages, AT_free_imagenet_ddp.py:403: local_result=True)."""
-    if args.attack_method == trainer.CASCADE_METHOD:
+    if args.attack_method in trainer.CASCADE_METHODS:
         return validate_cascade(val_loader, model, args, device, num_steps, spec["num_classes"], lambda line: _log(line, log_dir))
     batch_time = AverageMeter()
     meters = _DeviceMeters(6, device)
@@ -278,6 +284,7 @@ def run(spec, build_model, argv=None):
     args = parse_config_file(parser.parse_args(argv))
     spec = sized(spec, args)
     data_source(args.data, spec)  # an unusable --data fails here, before a model is built
+    trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
     for key, default in (("type_canny", None), ("step_size_3", args.get("step_size_2")), ("num_steps_3", args.get("num_steps_2")),
                          ("n_queries", 1), ("cize", spec["shape"][-1]), ("beta", 1.0)):
         if key not in args:

@@ -189,6 +189,14 @@ def _chunk(n):
     return max(c for c in range(1, min(n, MAX_ITERS_PER_GRAPH) + 1) if n % c == 0)
 
 
+def _eot_chunk(n, eot_iter):
+    """Iterations per replay of a loop whose iteration holds eot_iter forward/backward pairs: the largest divisor of n not above
+    max(1, MAX_ITERS_PER_GRAPH // eot_iter) - the graph keeps about the node count of MAX_ITERS_PER_GRAPH plain iterations (E = 20: one
+    iteration per graph; E = 1: _chunk(n))."""
+    cap = max(1, MAX_ITERS_PER_GRAPH // int(eot_iter))
+    return max(c for c in range(1, min(n, cap) + 1) if n % c == 0)
+
+
 def _cached(key, model, build):
     """The captured loop under `key`: the cached one if it was captured on this very model (ids are reused), else build()'s."""
     gs = _GRAPHS.get(key)
@@ -255,7 +263,8 @@ def pgd_loop(model, x0, x_init, spec, num_steps, step_size, eps, direction=1, lo
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# APGD (Croce & Hein 2020; Linf, one run, no EOT): APGD-CE and, on the targeted DLR loss, the runs of APGD-T
+# APGD (Croce & Hein 2020; Linf, one run): APGD-CE, APGD-DLR and, on the targeted DLR loss, the runs of APGD-T; eot_iter > 1 averages every
+# gradient over that many forwards of a randomised defence
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def apgd_schedule(n_iter):
     """sched[i] = the window length k when a checkpoint closes iteration i (0-based), else 0.  k starts at max(int(0.22 n), 1) and
@@ -276,7 +285,8 @@ def apgd_schedule(n_iter):
 class _ApgdSpec:
     """The loss-gradient step of `_body_input_grad` for an APGD run: the row losses, their logit gradient and `pred` in one launch, then -
     once the run is past its start point - the per-sample bookkeeping in a second one.  The kind is none of the CE kinds, so the route is the
-    generic one (logits -> this -> autograd): the fused head launches produce no row losses."""
+    generic one (logits -> this -> autograd): the fused head launches produce no row losses.  In an EOT run (eot_iter > 1) the bookkeeping
+    is not launched here: it runs once per iterate, after the last draw (_ApgdRun.gradient)."""
 
     def __init__(self, run):
         self.kind, self.payload, self.run = "apgd_" + run.loss, run.y, run
@@ -284,7 +294,7 @@ class _ApgdSpec:
     def dlogits(self, logits):
         r = self.run
         r.loss_rows, d, r.pred = ops.apgd_loss(logits.detach(), r.y, r.loss, r.t)
-        if r.started:
+        if r.started and r.eot_iter == 1:
             ops.apgd_book_(r.loss_rows, r.pred, r.fstate, r.istate, r.counter, r.sched)
         return d
 
@@ -292,11 +302,17 @@ class _ApgdSpec:
 class _ApgdRun:
     """The device state of one APGD run (include/eeadv.h, "APGD") and its two pieces: `start` (the forward/backward at the start point and the
     initial state: a handful of small launches, once per attack) and `iteration` (step, forward, loss, bookkeeping, backward, copies: what
-    a captured graph replays).  No host read anywhere."""
+    a captured graph replays).  No host read anywhere.  eot_iter = E > 1: every gradient is the mean over E forward/backward pairs, summed
+    into `g` by ee_apgd_eot_acc_f32 (so `g` is the one gradient buffer of the run), and the bookkeeping runs once per iterate on the mean
+    of the E row losses and the last draw's pred.  `trace` (a list, eager runs only) receives one dict per gradient evaluation."""
 
-    def __init__(self, x0, y, n_iter, eps, loss):
+    def __init__(self, x0, y, n_iter, eps, loss, eot_iter=1):
         B, dev = x0.shape[0], x0.device
-        self.loss, self.eps, self.n_iter = loss, float(eps), int(n_iter)
+        self.loss, self.eps, self.n_iter, self.eot_iter = loss, float(eps), int(n_iter), int(eot_iter)
+        self.trace = None
+        if self.eot_iter > 1:
+            self.loss_acc = torch.empty(B, dtype=torch.float64, device=dev)
+            self.loss_mean = torch.empty(B, dtype=torch.float32, device=dev)
         self.x = torch.empty_like(x0).requires_grad_(True)
         self.x0, self.x_old, self.g = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
         self.x_best, self.g_best, self.x_best_adv = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
@@ -319,19 +335,52 @@ class _ApgdRun:
             if self.t is not None:
                 self.t.copy_(targets)
 
+    def gradient(self, model):
+        """The gradient of the current iterate and, past the start point, its bookkeeping.  E = 1: one forward/backward, the bookkeeping
+        inside it (_ApgdSpec), a fresh tensor.  E > 1: E of them, each followed by the accumulate launch, then the bookkeeping on
+        (loss_mean, the last draw's pred); the result is self.g."""
+        E = self.eot_iter
+        if E == 1:
+            # .contiguous() launches nothing for the dense tensor autograd returns here: the start point, which did without it before
+            # EOT existed, and the iterations launch what they always launched
+            g = input_gradient(model, self.x, self.spec).contiguous()
+            if self.trace is not None:
+                self._note([dict(loss=self.loss_rows.clone(), pred=self.pred.clone(), g=g.clone())], self.loss_rows, g)
+            return g
+        draws = []
+        for k in range(E):
+            g = input_gradient(model, self.x, self.spec).contiguous()
+            ops.apgd_eot_acc_(self.g, g, self.loss_acc, self.loss_rows, self.loss_mean, k, E)
+            if self.trace is not None:
+                draws.append(dict(loss=self.loss_rows.clone(), pred=self.pred.clone(), g=g.clone()))
+        if self.started:
+            ops.apgd_book_(self.loss_mean, self.pred, self.fstate, self.istate, self.counter, self.sched)
+        if self.trace is not None:
+            self._note(draws, self.loss_mean, self.g)
+        return self.g
+
+    def _note(self, draws, loss, g):
+        """One trace entry: the draws, what the bookkeeping received (the start point has none: its flags are None) and the gradient
+        before the copies of `select`."""
+        self.trace.append(dict(draws=draws, book_loss=loss.clone(), book_pred=self.pred.clone(), g_mean=g.clone(),
+                               counter=int(self.counter.item()) if self.started else None,
+                               flags=self.istate[ops.APGD_I_FLAGS].clone() if self.started else None))
+
     def start(self, model):
         self.started = False
-        g = input_gradient(model, self.x, self.spec)
+        g = self.gradient(model)
         self.started = True
+        loss = self.loss_rows if self.eot_iter == 1 else self.loss_mean
         with torch.no_grad():
             x = self.x.detach()
             for t in (self.x_old, self.x_best, self.x_best_adv):
                 t.copy_(x)
-            self.g.copy_(g)
+            if g is not self.g:
+                self.g.copy_(g)
             self.g_best.copy_(g)
-            self.loss0.copy_(self.loss_rows)
+            self.loss0.copy_(loss)
             self.fstate[ops.APGD_F_STEP].fill_(2.0 * self.eps)
-            self.fstate[ops.APGD_F_LOSS_BEST:].copy_(self.loss_rows.expand(3, -1))
+            self.fstate[ops.APGD_F_LOSS_BEST:].copy_(loss.expand(3, -1))
             self.istate.zero_()
             self.istate[ops.APGD_I_REDUCED_LAST].fill_(1)
             self.istate[ops.APGD_I_ROBUST].copy_(self.pred)
@@ -340,8 +389,10 @@ class _ApgdRun:
     def iteration(self, model, g):
         """One iteration from the gradient `g` of the current iterate; returns the gradient of the next one (a fresh tensor, restored in
         place for the samples a checkpoint sent back)."""
+        if self.trace is not None:
+            self.trace.append(dict(step_g=g.clone()))
         ops.apgd_step_(self.x.detach(), self.x_old, g, self.x0, self.fstate[ops.APGD_F_STEP], self.counter, self.eps)
-        g_new = input_gradient(model, self.x, self.spec).contiguous()
+        g_new = self.gradient(model)
         ops.apgd_select_(self.x.detach(), g_new, self.x_best, self.g_best, self.x_best_adv, self.istate[ops.APGD_I_FLAGS], self.counter)
         return g_new
 
@@ -351,41 +402,55 @@ class _ApgdRun:
             return _adv_where_fooled(robust, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
 
 
-def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None):
+def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, eot_iter=1, trace=None):
     """One APGD run of n_iter iterations from x_init inside the eps-ball around x0, on loss 'ce', 'dlr' or 'dlr_t' (which takes `targets`).
     Returns (x_adv, robust, loss_best): x0 with the rows that were fooled at any point replaced by a fooling point, robust [B] bool,
     the best row loss seen [B].  The model's mode is left as the caller set it.  Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a
-    captured graph of up to MAX_ITERS_PER_GRAPH iterations; both give the same bits."""
+    captured graph of up to MAX_ITERS_PER_GRAPH iterations; both give the same bits.
+
+    eot_iter = E > 1 (expectation over transformation, for a defence that redraws at every forward): every gradient evaluation, the start
+    point's included, is E forward/backward pairs whose input gradients are averaged (ee_apgd_eot_acc_f32); the bookkeeping runs once per
+    iterate on the mean of the E row losses (summed in double) and on the LAST draw's pred.  A replay then covers _eot_chunk(n_iter, E)
+    iterations.  E = 1 launches exactly what the loop launched before EOT existed.  `trace` (a list, eager only) receives, per gradient
+    evaluation (the start's first), {"draws": [{"loss", "pred", "g"} per draw], "book_loss", "book_pred", "g_mean", "counter", "flags"}
+    (the last two None at the start point) and, before each step, {"step_g"}: the gradient that step reads."""
     if loss not in ops.APGD_KINDS:
         raise ValueError("APGD loss must be one of %s, got %r" % (sorted(ops.APGD_KINDS), loss))
     if loss == "dlr_t" and targets is None:
         raise ValueError("the targeted DLR loss needs targets")
+    eot_iter = int(eot_iter)
+    if eot_iter < 1:
+        raise ValueError("APGD needs eot_iter >= 1, got %d" % eot_iter)
     model = _unwrap(model)
     x0 = x0.detach().contiguous()
     x_init = x_init.detach().contiguous()
     n_iter = int(n_iter)
     if use_graph is None:
-        use_graph = graphs_enabled()
+        use_graph = graphs_enabled() and trace is None
+    if use_graph and trace is not None:
+        raise ValueError("the APGD trace is recorded by eager runs only")
     if not use_graph:
-        run = _ApgdRun(x0, y, n_iter, eps, loss)
+        run = _ApgdRun(x0, y, n_iter, eps, loss, eot_iter)
+        run.trace = trace
         run.load(x_init, x0, y, targets)
         run.start(model)
         g = run.g
         for _ in range(n_iter):
             g = run.iteration(model, g)
         return run.result()
-    chunk = _chunk(n_iter)
-    key = ("apgd", id(model), model.training, tuple(x0.shape), loss, n_iter, float(eps), x0.device.index, chunk)
+    chunk = _eot_chunk(n_iter, eot_iter)
+    key = ("apgd", id(model), model.training, tuple(x0.shape), loss, n_iter, float(eps), x0.device.index, chunk, eot_iter)
 
     def build():
-        run = _ApgdRun(x0, y, n_iter, eps, loss)
+        run = _ApgdRun(x0, y, n_iter, eps, loss, eot_iter)
         run.load(x_init, x0, y, targets)
 
         def body(model):  # the gradient enters through run.g and leaves through it (one copy per replay): inside the graph each
-            g = run.g     # iteration reads the autograd result of the one before
+            g = run.g     # iteration reads the autograd result of the one before (an EOT run sums into run.g itself: no copy)
             for _ in range(chunk):
                 g = run.iteration(model, g)
-            run.g.copy_(g)
+            if g is not run.g:
+                run.g.copy_(g)
 
         return _Captured(model, x0.device, chunk, run).capture(model, body, start=lambda: run.start(model))
 

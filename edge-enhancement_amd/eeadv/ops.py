@@ -467,6 +467,19 @@ def apgd_select_(x, g, x_best, g_best, x_best_adv, flags, counter):
     return x
 
 
+# ---- EOT for APGD (ee_eot.hip) ---------------------------------------------------------------------------------------
+def apgd_eot_acc_(g_acc, g, loss_acc, loss, loss_mean, k, E):
+    """Draw k of E in place: g_acc [B, ...] takes g (k == 0) or g_acc + g, and * (1/E) after the last draw; loss_acc [B] float64 takes the
+    row losses [B] the same way, and loss_mean [B] = loss_acc / E after the last draw."""
+    B = g_acc.shape[0]
+    pa = _chk(g_acc, torch.float32, "g_acc")
+    pg = _chk(g, torch.float32, "g", g_acc.shape)
+    N.check(N.lib.ee_apgd_eot_acc_f32(pa, pg, _chk(loss_acc, torch.float64, "loss_acc", (B,)), _chk(loss, torch.float32, "loss", (B,)),
+                                      _chk(loss_mean, torch.float32, "loss_mean", (B,)), int(k), int(E), B, g_acc.numel() // B if B else 0,
+                                      _stream()), "ee_apgd_eot_acc_f32")
+    return g_acc
+
+
 # ---- Square attack (ee_sqatk.hip) ------------------------------------------------------------------------------------
 def _sqatk_images(x_best, x_new, x0):
     if x_best.dim() != 4:

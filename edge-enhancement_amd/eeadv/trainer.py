@@ -663,9 +663,26 @@ class FreeAtStep:
         return self.loss.clone(), self.output.clone()
 
 
+def eot_iter_for(args):
+    """The EOT count of args.attack_method from args.eot_iter (--eot_iter; None / absent: 20 for Rand and Cascade-Rand, 1 for APGD-CE and
+    APGD-DLR, which honour an explicit value).  Every other method has no EOT: a value above 1 stops here instead of being ignored."""
+    e = getattr(args, 'eot_iter', None)
+    if e is not None and int(e) < 1:
+        raise ValueError("--eot_iter must be at least 1, got %d" % int(e))
+    if args.attack_method in ('Rand', CASCADE_RAND_METHOD):
+        return 20 if e is None else int(e)
+    if args.attack_method in ('APGD-CE', 'APGD-DLR'):
+        return 1 if e is None else int(e)
+    if e is not None and int(e) > 1:
+        raise NotImplementedError("--eot_iter %d with --attack_method %s: EOT is built for APGD-CE, APGD-DLR, Rand and Cascade-Rand only - not for "
+                                  "APGD-T, FAB-T, Square, their composites, Cascade or the reference's own attacks" % (int(e), args.attack_method))
+    return 1
+
+
 def attack_for_validation(model, args, input, target, device, num_steps, step_size, n_class):
     """experiments_tinyimagenet.py:354-374."""
     targeted = "tar" in args.method_name
+    eot_iter = eot_iter_for(args)
     if args.attack_method == 'PGD':
         if targeted:
             return A.targeted_PGD(model, args, input, target, num_steps, step_size, n_class, device)[0]
@@ -689,7 +706,7 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
         x_adv, robust = None, None
         if args.attack_method in ('APGD-CE', 'APGD'):
-            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce')
+            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', eot_iter=eot_iter)
         if args.attack_method in ('APGD-T', 'APGD'):
             xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class)
             if x_adv is None:
@@ -730,6 +747,17 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         robust = robust & rf
         xs, rs, _ = A.Square(model, args, input, target, int(getattr(args, 'square_queries', 5000)))
         return torch.where((robust & ~rs).view(shape), xs, x_adv)
+    if args.attack_method in RAND_METHODS:
+        # APGD on the untargeted DLR loss, or the `rand` order for randomised defences: APGD-CE then APGD-DLR, every gradient averaged over
+        # eot_iter forwards
+        if targeted:
+            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+        if args.attack_method == 'APGD-DLR':
+            return A.APGD(model, args, input, target, num_steps, 'dlr', eot_iter=eot_iter)[0]
+        return A.APGD_Rand(model, args, input, target, num_steps, eot_iter, n_class)[0]
+    if args.attack_method == CASCADE_RAND_METHOD:
+        raise NotImplementedError("--attack_method Cascade-Rand regroups the survivors of a whole split: it runs as eeadv.cascade.evaluate over the "
+                                  "loader (driver.validate_cascade), not batch by batch")
     if args.attack_method == CASCADE_METHOD:
         raise NotImplementedError("--attack_method Cascade regroups the survivors of a whole split: it runs as eeadv.cascade.evaluate over the "
                                   "loader (driver.validate_cascade), not batch by batch")
@@ -739,7 +767,12 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
 APGD_METHODS = ('APGD-CE', 'APGD-T', 'APGD')
 SQUARE_METHODS = ('Square', 'APGD+Square')
 FAB_METHODS = ('FAB-T', 'APGD+FAB+Square')
+RAND_METHODS = ('APGD-DLR', 'Rand')  # Rand: APGD-CE then APGD-DLR with EOT, the `rand` order for randomised defences
+CASCADE_RAND_METHOD = 'Cascade-Rand'  # the same two, APGD-DLR on the survivors of APGD-CE only, over the whole split
 CASCADE_METHOD = 'Cascade'  # the same four attacks, each on the samples the ones before it left standing (eeadv.cascade)
+CASCADE_METHODS = (CASCADE_METHOD, CASCADE_RAND_METHOD)
+# what the AWP drivers validate with next to PGD
+EVAL_METHODS = APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS
 
 
 def validate_batch(model, criterion, args, input, target, device, num_steps, step_size, n_class):

@@ -10,7 +10,8 @@ deliberate and documented in DESIGN.md:
   * random starts are drawn on the device (Philox inside the init kernel) unless `noise=` is injected -
     device and host generators differ anyway, parity tests inject the noise;
   * CWLinfAttack(target=None) works (the reference raises TypeError at :152, SURVEY a17);
-  * APGD / APGD_T, Square and FAB_T are additions: the reference runs them through the `autoattack` package (DESIGN.md sections 11 - 13);
+  * APGD / APGD_T, Square, FAB_T and APGD_Rand are additions: the reference runs them through the `autoattack` package (DESIGN.md
+    sections 11 - 13 and 15);
   * CPU tensors are refused unless eeadv.runtime.allow_cpu_plumbing(True) was called (--no-cuda drivers).
 """
 import numpy as np
@@ -117,7 +118,9 @@ def targeted_PGD_trick(model, args, inputs, labels, num_steps, step_size, nclass
 # ---------------------------------------------------------------------------------------------------------
 # APGD-CE and APGD-T (Croce & Hein 2020): the two gradient attacks of AutoAttack's `standard` version.  Not in the
 # reference's utils/attacks.py - its drivers call the `autoattack` package for them.  Square, the black-box member, and FAB-T follow below;
-# the `rand` / EOT versions, the L2 / L1 norms and restarts are NOT here, so the result is not an AutoAttack number.
+# `eot_iter` averages every gradient over that many forwards (EOT), and APGD_Rand is the `rand` version's order, APGD-CE then APGD-DLR with
+# EOT.  EOT for APGD-T, Square and FAB-T, the L2 / L1 norms and restarts are NOT here, so the result is not an
+# AutoAttack number.
 # ---------------------------------------------------------------------------------------------------------
 def _apgd_row_losses(z, y, loss, t=None):
     """Row losses [B] of logits [B,K] in z's dtype; classes ordered by value descending, ties to the lower index."""
@@ -138,10 +141,29 @@ def _apgd_row_losses(z, y, loss, t=None):
     raise ValueError("APGD loss must be 'ce', 'dlr' or 'dlr_t', got %r" % (loss,))
 
 
-def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None):
+def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=1):
     """Plumbing path for CPU tensors (opt-in), the counterpart of _host_loop: the iteration of engine.apgd_loop in plain torch ops, in the
-    input's dtype.  `trace`, a list, receives one dict of clones per iteration (the start point first)."""
+    input's dtype.  `trace`, a list, receives one dict of clones per iteration (the start point first).  eot_iter = E > 1: every gradient
+    is the sum of E draws' gradients in draw order times 1/E (formed in the input's dtype), the loss the mean of their row losses summed
+    in float64, pred the last draw's; the trace then also holds draw_loss / draw_g / draw_pred, stacked over the draws."""
+    E = int(eot_iter)
+    if E < 1:
+        raise ValueError("APGD needs eot_iter >= 1, got %d" % E)
+    last = {}
+
     def grad_at(xc):
+        if E == 1:
+            return grad_once(xc)
+        draws = [grad_once(xc) for _ in range(E)]
+        acc, lacc = draws[0][1], draws[0][0].to(torch.float64)
+        for l_k, g_k, _ in draws[1:]:
+            acc = acc + g_k
+            lacc = lacc + l_k.to(torch.float64)
+        last.update(draw_loss=torch.stack([d[0] for d in draws]), draw_g=torch.stack([d[1] for d in draws]),
+                    draw_pred=torch.stack([d[2] for d in draws]))
+        return (lacc / E).to(draws[0][0].dtype), acc * (torch.ones((), dtype=acc.dtype) / E), draws[-1][2]
+
+    def grad_once(xc):
         xc = xc.detach().requires_grad_()
         with torch.enable_grad():
             z = model(xc)
@@ -167,6 +189,7 @@ def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None):
 
     def note(**kw):
         if trace is not None:
+            kw.update(last)
             kw.update(x=x, x_old=x_old, g=g, loss=l, pred=pred, step=step, loss_best=loss_best, f_prev=f_prev, loss_best_last=loss_best_last,
                       inc=inc, reduced_last=reduced_last, robust=robust, x_best=x_best, g_best=g_best, x_best_adv=x_best_adv)
             trace.append({k: v.clone() for k, v in kw.items()})
@@ -200,22 +223,48 @@ def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None):
     return torch.where(robust.view(shape), x0, x_best_adv), robust, loss_best
 
 
-def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None):
+def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None, eot_iter=1):
     """One APGD run (Linf, eps = args.epsilon, num_steps iterations) on loss 'ce', 'dlr' or 'dlr_t' (targeted at `y_target`).  Returns
     (x_adv, robust): the inputs, with every sample that some iterate fooled replaced by such an iterate, and the [B] bool flags of the samples
     that stayed correctly classified throughout.  The start point is the project's uniform start, clamp(x0 + U(-eps, eps), 0, 1) (`noise=`
     injects the draw); the public implementation rescales each sample's draw to the full radius first - that normalisation is deliberately
     left out.  The model runs in the mode the caller left it in.  On the device the targeted DLR denominator is formed as the mean of
     z_p1 - z_p3 and z_p1 - z_p4 (csrc/ee_apgd.hip: no cancellation against a rounded sum); the host path below keeps
-    z_p1 - (z_p3 + z_p4)/2, so an fp32 host run and a device run differ in the last bits of the `dlr_t` loss."""
+    z_p1 - (z_p3 + z_p4)/2, so an fp32 host run and a device run differ in the last bits of the `dlr_t` loss.  eot_iter = E > 1 (for a
+    defence that redraws at every forward): every gradient is the mean over E forwards, the loss the run keeps books on is the mean of
+    their row losses, and a sample counts as fooled when the last of the E draws of some iterate misclassifies it."""
+    eot_iter = int(eot_iter)
+    if eot_iter < 1:
+        raise ValueError("APGD needs eot_iter >= 1, got %d" % eot_iter)
     x0 = inputs.detach()
     eps = float(args.epsilon)
     x = _uniform_start(x0, eps, noise)
     if runtime.require_device(x0, "APGD"):
-        x_adv, robust, _ = engine.apgd_loop(model, x0, x, targets, num_steps, eps, loss, y_target)
+        x_adv, robust, _ = engine.apgd_loop(model, x0, x, targets, num_steps, eps, loss, y_target, eot_iter=eot_iter)
     else:
-        x_adv, robust, _ = _apgd_host(model, x0, x, targets, num_steps, eps, loss, y_target)
+        x_adv, robust, _ = _apgd_host(model, x0, x, targets, num_steps, eps, loss, y_target, eot_iter=eot_iter)
     return x_adv, robust
+
+
+def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None, noise=None):
+    """The order of the public ensemble's `rand` version, for defences that redraw at every forward: APGD-CE, then APGD-DLR (the untargeted
+    DLR loss), each one run of num_steps iterations with every gradient averaged over eot_iter forwards, each on the whole batch.  Returns
+    (x_adv, robust) with the flags ANDed and, per sample, the first fooling point - as APGD_T combines its runs.  The DLR loss reads the three
+    largest logits: `nclass` (default: read off one clean forward) must be at least 3."""
+    eot_iter = int(eot_iter)
+    if eot_iter < 1:
+        raise ValueError("APGD_Rand needs eot_iter >= 1, got %d" % eot_iter)
+    x0 = inputs.detach()
+    if nclass is None:
+        with torch.no_grad():
+            nclass = model(x0).shape[1]
+    if int(nclass) < 3:
+        raise ValueError("APGD_Rand runs APGD-DLR, whose loss is normalised by the spread of the three largest logits: it needs at least 3 "
+                         "classes and this model has %d (MNIST's 10 are enough; only the targeted DLR loss of APGD-T needs 4)" % int(nclass))
+    x_adv, robust = APGD(model, args, inputs, targets, num_steps, 'ce', None, noise, eot_iter)
+    xd, rd = APGD(model, args, inputs, targets, num_steps, 'dlr', None, noise, eot_iter)
+    x_adv = torch.where((robust & ~rd).view((-1,) + (1,) * (x0.dim() - 1)), xd, x_adv)
+    return x_adv, robust & rd
 
 
 def _class_order(model, x0, n_t, what, order=None):
@@ -329,7 +378,7 @@ def Square(model, args, inputs, targets, n_queries=5000, seed=None):
 # FAB-T (Croce & Hein 2020, Linf, targeted): the minimum-norm member of AutoAttack's `standard` version - it walks along linearised
 # decision boundaries instead of ascending a loss.  Built from the published algorithm with the constants `standard`
 # runs it with (eta = 1.05, beta = 0.9, alpha_max = 0.1, 9 target classes, one run from the clean point: deterministic).  Untargeted FAB,
-# L2 / L1, restarts with the random start, the final line search and EOT are NOT here.
+# L2 / L1, restarts with the random start, the final line search and EOT for FAB are NOT here.
 # ---------------------------------------------------------------------------------------------------------
 _FAB_ETA, _FAB_BETA, _FAB_ALPHA_MAX = 1.05, 0.9, 0.1
 

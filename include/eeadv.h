@@ -209,7 +209,7 @@ int ee_reduce_rows_f64(const double *rows, int64_t n, double scale, double *out,
 int ee_topk_i64(const float *logits, const int64_t *labels, int B, int K, int k, int64_t *idx, int64_t *correct,
                 void *stream);
 
-/* ---- APGD (Croce & Hein 2020, Linf, one run, no EOT): the per-iteration work around the classifier, ee_apgd.hip ----
+/* ---- APGD (Croce & Hein 2020, Linf, one run; EOT: the next section): the per-iteration work around the classifier, ee_apgd.hip ----
  * State of one attack on B samples of per_sample elements each, all in device memory:
  *   x, x_old, x0, g, x_best, g_best, x_best_adv   float [B, per_sample]
  *   fstate  float [4, B]: rows EE_APGD_F_*  (step size, best loss, previous loss, best loss at the last checkpoint)
@@ -262,6 +262,24 @@ int ee_apgd_book_f32(const float *loss, const int *pred, float *fstate, int *ist
  * per_sample == 0 is no attack: nothing is launched and the counter stays. */
 int ee_apgd_select_f32(float *x, float *g, float *x_best, float *g_best, float *x_best_adv, const int *flags, int *counter, int B,
                        int64_t per_sample, void *stream);
+
+/* ---- EOT for APGD (the `rand` version of the public ensemble: each gradient is the mean over E forwards of a randomised defence), ee_eot.hip ----
+ * State next to the APGD run's, all in device memory:
+ *   g_acc     float  [B, per_sample]  the sum, then the mean, of the E input gradients of one iterate
+ *   loss_acc  double [B]              the sum of their row losses, in draw order
+ *   loss_mean float  [B]              (float)(loss_acc / E): what ee_apgd_book_f32 reads in an EOT run
+ * An iteration is step -> E x (classifier forward -> loss -> classifier backward -> eot_acc) -> book -> select; book sees loss_mean and the
+ * LAST draw's pred.  k and E are host values, constants of a captured graph's nodes. */
+
+/* One launch after draw k's backward (0 <= k < E), with inv = 1.0f / E formed in fp32 on the host:
+ *     g_acc = (k == 0 ? g : g_acc + g);   if k == E - 1: g_acc = g_acc * inv       (the add is rounded, then the product: never fused)
+ *     loss_acc = (k == 0 ? loss : loss_acc + loss) in double;   if k == E - 1: loss_mean = (float)(loss_acc / E)
+ * so k == 0 overwrites whatever the accumulators held, E == 1 gives g * 1.0f, and E equal losses give back that loss bit for bit.
+ * 16-byte accesses when g_acc and g are 16-byte aligned (a vector may straddle samples; B * per_sample need not be a multiple of 4),
+ * element by element otherwise.  12 B of HBM traffic per element (8 B at k == 0).  E < 1 or k outside [0, E): EE_ERR_SHAPE; g_acc == g:
+ * EE_ERR_SHAPE; loss_acc 8-byte, the rest 4-byte aligned (EE_ERR_ALIGN).  B == 0 or per_sample == 0 launches nothing. */
+int ee_apgd_eot_acc_f32(float *g_acc, const float *g, double *loss_acc, const float *loss, float *loss_mean, int k, int E, int64_t B,
+                        int64_t per_sample, void *stream);
 
 /* ---- Square attack (Andriushchenko et al. 2020, Linf, score-based; the schedule of AutoAttack's `standard` version), ee_sqatk.hip ----
  * The ATTACK - not the Add_Square defence (ee_add_square_*, ee_square_draw_f32).  State of one attack on B images [C,H,W], all in
