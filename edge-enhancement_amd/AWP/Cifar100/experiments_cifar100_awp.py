@@ -115,7 +115,7 @@ def validate(val_loader, model, criterion, args, device, num_steps, step_size, l
             _log(fmt.format(i, len(val_loader), tag='Test_adv', batch_time=batch_time, loss=la, top1=t1a, top5=t5a), log_dir + 'log.txt')
     lc, la, t1c, t5c, t1a, t5a = meters.read()
     _log(' * Clean Prec@1 {top1.avg:.3f} Prec@5 {top5.avg:.3f}'.format(top1=t1c, top5=t5c), log_dir + 'log.txt')
-    _log(' * Adv Prec@1 {top1.avg:.3f} Prec@5 {top5.avg:.3f}'.format(top1=t1a, top5=t5a), log_dir + 'log.txt')
+    _log(' * Adv Prec@1 {top1.avg:.3f} Prec@5 {top5.avg:.3f}'.format(top1=t1a, top5=t5a) + trainer.norm_tag(args), log_dir + 'log.txt')
     return t1a.avg, t5a.avg
 
 
@@ -126,6 +126,7 @@ def main(argv=None):
         raise NotImplementedError("--attack_method %s: validation runs PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T, APGD+FAB+Square, Cascade, APGD-DLR, Rand or Cascade-Rand" % args.attack_method)  # experiments_cifar100_awp.py:374-380
     driver.data_source(args.data, SPEC)  # an unusable --data fails here, before a model is built
     trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
+    trainer.norm_for(args)  # and a --norm it has no L2 for
     for key, default in (("step_size_2", args.get("step_size_1")), ("num_steps_3", args.get("num_steps_2"))):
         args.setdefault(key, default)
     args.setdefault("step_size_3", args.step_size_2)

@@ -123,7 +123,7 @@ def validate(val_loader, model, criterion, args, device, num_steps, step_size, l
             _log(fmt.format(i, len(val_loader), tag='Test_adv', batch_time=batch_time, loss=la, top1=t1a, top5=t5a), log_dir + 'log_pgd.txt')
     lc, la, t1c, t5c, t1a, t5a = meters.read()
     _log(' * Clean Prec@1 {top1.avg:.3f} Prec@5 {top5.avg:.3f}'.format(top1=t1c, top5=t5c), log_dir + 'log_pgd.txt')
-    _log(' * Adv Prec@1 {top1.avg:.3f} Prec@5 {top5.avg:.3f}'.format(top1=t1a, top5=t5a), log_dir + 'log_pgd.txt')
+    _log(' * Adv Prec@1 {top1.avg:.3f} Prec@5 {top5.avg:.3f}'.format(top1=t1a, top5=t5a) + trainer.norm_tag(args), log_dir + 'log_pgd.txt')
     return t1a.avg, t5a.avg
 
 
@@ -135,6 +135,7 @@ def main(argv=None):
                          else "--attack_method %s: the AWP driver validates with PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T, APGD+FAB+Square, Cascade, APGD-DLR, Rand or Cascade-Rand" % args.attack_method)
     driver.data_source(args.data, SPEC)  # an unusable --data fails here, before a model is built
     trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
+    trainer.norm_for(args)  # and a --norm it has no L2 for
     args.setdefault("cize", 64)
     args.num_classes = SPEC["num_classes"]
     use_cuda = not args.no_cuda and torch.cuda.is_available()

@@ -38,16 +38,18 @@ def default_stages(args, num_steps, n_class, n_target_classes=9):
     ]
 
 
-def rand_stages(args, num_steps, eot_iter=None):
+def rand_stages(args, num_steps, eot_iter=None, norm="Linf"):
     """[(name, fn)] of the public ensemble's `rand` order for randomised defences: APGD-CE, then APGD-DLR on its survivors, every gradient
-    averaged over eot_iter forwards (default args.eot_iter, else 20)."""
+    averaged over eot_iter forwards (default args.eot_iter, else 20).  norm: 'Linf' or 'L2', for both stages
+    (DESIGN.md section 16)."""
+    kw = A._norm_kw(norm)  # empty for Linf
     E = eot_iter if eot_iter is not None else getattr(args, "eot_iter", None)
     E = 20 if E is None else int(E)
     if E < 1:
         raise ValueError("the rand stages need eot_iter >= 1, got %d" % E)
     return [
-        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", eot_iter=E)),
-        ("APGD-DLR", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "dlr", eot_iter=E)),
+        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", eot_iter=E, **kw)),
+        ("APGD-DLR", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "dlr", eot_iter=E, **kw)),
     ]
 
 

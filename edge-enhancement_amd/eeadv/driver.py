@@ -40,6 +40,7 @@ def make_parser(description, default_data="synthetic", with_local_rank=False):
     parser.add_argument('-e', '--evaluate', dest='evaluate', action='store_true', help='evaluate model on validation set')
     parser.add_argument('--attack_method', default='PGD', type=str, metavar='PATH', help='attack method in validation: PGD, FGSM, CW, APGD-CE, APGD-T, APGD (CE then T), Square, APGD+Square (CE, T, then Square), FAB-T, APGD+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch) Cascade (the same four, each on the samples still robust, over the whole split), APGD-DLR, Rand (APGD-CE then APGD-DLR, every gradient averaged over --eot_iter forwards: for defences that redraw at every forward) or Cascade-Rand (the same two, APGD-DLR on the survivors only), (default: PGD)')
     parser.add_argument('--eot_iter', default=None, type=int, help='forwards every APGD gradient is averaged over (EOT); default: 20 for Rand and Cascade-Rand, 1 for APGD-CE and APGD-DLR; the other attacks have no EOT and refuse a value above 1')
+    parser.add_argument('--norm', default='Linf', type=str, help='threat model of the evaluation attack, radius --epsilon of the config: Linf (default) or L2; L2 exists for APGD-CE, APGD-T, APGD, APGD-DLR, Rand and Cascade-Rand and every other method refuses it')
     parser.add_argument('--square_queries', default=5000, type=int, help='forwards per sample of the Square attack at most (default: 5000); not the defence\'s n_queries')
     parser.add_argument('--fab_iters', default=100, type=int, help='iterations of FAB-T per target class (default: 100)')
     parser.add_argument('--no-cuda', action='store_true', default=False, help='disables CUDA training')
@@ -224,14 +225,14 @@ def validate_cascade(val_loader, model, args, device, num_steps, n_class, log):
         raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
     model.eval()
     start = time.time()
-    eot_iter, stages = trainer.eot_iter_for(args), None
+    eot_iter, stages, tag = trainer.eot_iter_for(args), None, trainer.norm_tag(args)
     if args.attack_method == trainer.CASCADE_RAND_METHOD:
         if n_class < 3:
             raise ValueError("--attack_method Cascade-Rand runs APGD-DLR, which needs at least 3 classes, not %d" % n_class)
-        stages = cascade.rand_stages(args, int(num_steps), eot_iter)
+        stages = cascade.rand_stages(args, int(num_steps), eot_iter, trainer.norm_for(args))
     res = cascade.evaluate(model, args, val_loader, n_class, num_steps=num_steps, device=device, stages=stages)
     log(' * Cascade: {0} samples, {1} attacked rows per stage {2}, {3:.1f} s'.format(
-        res.n, '/'.join(res.stage_names), '/'.join(str(r) for r in res.rows_attacked), time.time() - start))
+        res.n, '/'.join(res.stage_names), '/'.join(str(r) for r in res.rows_attacked), time.time() - start) + tag)
     log(' * Cascade clean accuracy {0:.3f}'.format(100.0 * res.clean_correct / res.n))
     for name, left in zip(res.stage_names, res.robust_after):
         log(' * Cascade robust accuracy after {0} {1:.3f}'.format(name, 100.0 * left / res.n))
@@ -270,7 +271,7 @@ def validate(val_loader, model, criterion, args, device, num_steps, step_size, l
     lc, la, t1c, t5c, t1a, t5a = meters.read()
     c1, c5, a1, a5 = ddp.gather_mean(t1c.avg, t5c.avg, t1a.avg, t5a.avg)  # experiments_imagenet.py:369-384
     _log(' * Clean Prec@1 {0:.3f} Prec@5 {1:.3f}'.format(c1, c5), log_dir)
-    _log(' * Adv Prec@1 {0:.3f} Prec@5 {1:.3f}'.format(a1, a5), log_dir)
+    _log(' * Adv Prec@1 {0:.3f} Prec@5 {1:.3f}'.format(a1, a5) + trainer.norm_tag(args), log_dir)
     if local_result:
         _log(' * Cl Prec@1 {top1.avg:.3f} Prec@5 {top5.avg:.3f}'.format(top1=t1c, top5=t5c), log_dir)  # AT_free_imagenet_ddp.py:400-401
         _log(' * Ad Prec@1 {top1.avg:.3f} Prec@5 {top5.avg:.3f}'.format(top1=t1a, top5=t5a), log_dir)
@@ -285,6 +286,7 @@ def run(spec, build_model, argv=None):
     spec = sized(spec, args)
     data_source(args.data, spec)  # an unusable --data fails here, before a model is built
     trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
+    trainer.norm_for(args)  # and a --norm it has no L2 for
     for key, default in (("type_canny", None), ("step_size_3", args.get("step_size_2")), ("num_steps_3", args.get("num_steps_2")),
                          ("n_queries", 1), ("cize", spec["shape"][-1]), ("beta", 1.0)):
         if key not in args:

@@ -263,9 +263,18 @@ def pgd_loop(model, x0, x_init, spec, num_steps, step_size, eps, direction=1, lo
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# APGD (Croce & Hein 2020; Linf, one run): APGD-CE, APGD-DLR and, on the targeted DLR loss, the runs of APGD-T; eot_iter > 1 averages every
-# gradient over that many forwards of a randomised defence
+# APGD (Croce & Hein 2020; Linf or L2, one run): APGD-CE, APGD-DLR and, on the targeted DLR loss, the runs of APGD-T; eot_iter > 1 averages
+# every gradient over that many forwards of a randomised defence; norm = "L2" swaps the step launch (section 16)
 # ---------------------------------------------------------------------------------------------------------------------------------------
+APGD_NORMS = ("Linf", "L2")
+
+
+def _check_norm(norm):
+    if norm not in APGD_NORMS:
+        raise ValueError("APGD norm must be one of %s, got %r" % (list(APGD_NORMS), norm))
+    return norm
+
+
 def apgd_schedule(n_iter):
     """sched[i] = the window length k when a checkpoint closes iteration i (0-based), else 0.  k starts at max(int(0.22 n), 1) and
     shrinks by max(int(0.03 n), 1) per checkpoint down to max(int(0.06 n), 1): n = 100 puts checkpoints after iterations 22, 41, 57, 70, 80,
@@ -304,11 +313,15 @@ class _ApgdRun:
     initial state: a handful of small launches, once per attack) and `iteration` (step, forward, loss, bookkeeping, backward, copies: what
     a captured graph replays).  No host read anywhere.  eot_iter = E > 1: every gradient is the mean over E forward/backward pairs, summed
     into `g` by ee_apgd_eot_acc_f32 (so `g` is the one gradient buffer of the run), and the bookkeeping runs once per iterate on the mean
-    of the E row losses and the last draw's pred.  `trace` (a list, eager runs only) receives one dict per gradient evaluation."""
+    of the E row losses and the last draw's pred.  norm = "L2": the run owns `norms` [3, B] and `iteration` launches ee_apgd_step_l2_f32 in
+    the place of ee_apgd_step_f32 - nothing else knows the norm.  `trace` (a list, eager runs only) receives one dict per gradient
+    evaluation."""
 
-    def __init__(self, x0, y, n_iter, eps, loss, eot_iter=1):
+    def __init__(self, x0, y, n_iter, eps, loss, eot_iter=1, norm="Linf"):
         B, dev = x0.shape[0], x0.device
         self.loss, self.eps, self.n_iter, self.eot_iter = loss, float(eps), int(n_iter), int(eot_iter)
+        self.norm = _check_norm(norm)
+        self.norms = torch.zeros((3, B), dtype=torch.float32, device=dev) if norm == "L2" else None
         self.trace = None
         if self.eot_iter > 1:
             self.loss_acc = torch.empty(B, dtype=torch.float64, device=dev)
@@ -389,9 +402,19 @@ class _ApgdRun:
     def iteration(self, model, g):
         """One iteration from the gradient `g` of the current iterate; returns the gradient of the next one (a fresh tensor, restored in
         place for the samples a checkpoint sent back)."""
-        if self.trace is not None:
-            self.trace.append(dict(step_g=g.clone()))
-        ops.apgd_step_(self.x.detach(), self.x_old, g, self.x0, self.fstate[ops.APGD_F_STEP], self.counter, self.eps)
+        if self.norms is None:
+            if self.trace is not None:
+                self.trace.append(dict(step_g=g.clone()))
+            ops.apgd_step_(self.x.detach(), self.x_old, g, self.x0, self.fstate[ops.APGD_F_STEP], self.counter, self.eps)
+        else:
+            entry = None
+            if self.trace is not None:
+                entry = dict(step_g=g.clone(), x_in=self.x.detach().clone(), x_old_in=self.x_old.clone(),
+                             step=self.fstate[ops.APGD_F_STEP].clone(), counter=int(self.counter.item()))
+                self.trace.append(entry)
+            ops.apgd_step_l2_(self.x.detach(), self.x_old, g, self.x0, self.fstate[ops.APGD_F_STEP], self.counter, self.eps, self.norms)
+            if entry is not None:
+                entry.update(norms=self.norms.clone(), x=self.x.detach().clone(), x_old=self.x_old.clone())
         g_new = self.gradient(model)
         ops.apgd_select_(self.x.detach(), g_new, self.x_best, self.g_best, self.x_best_adv, self.istate[ops.APGD_I_FLAGS], self.counter)
         return g_new
@@ -402,8 +425,11 @@ class _ApgdRun:
             return _adv_where_fooled(robust, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
 
 
-def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, eot_iter=1, trace=None):
+def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, eot_iter=1, trace=None, norm="Linf"):
     """One APGD run of n_iter iterations from x_init inside the eps-ball around x0, on loss 'ce', 'dlr' or 'dlr_t' (which takes `targets`).
+    norm: 'Linf' (the default: exactly what ran before the parameter existed) or 'L2' - the ball is then the L2 ball of radius eps and the
+    step ee_apgd_step_l2_f32; start, losses, bookkeeping, copies, EOT, the initial step 2 eps and the schedule are
+    shared, and the trace's {"step_g"} entries also hold "x_in", "x_old_in", "step", "counter", "norms" [3, B], "x" and "x_old".
     Returns (x_adv, robust, loss_best): x0 with the rows that were fooled at any point replaced by a fooling point, robust [B] bool,
     the best row loss seen [B].  The model's mode is left as the caller set it.  Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a
     captured graph of up to MAX_ITERS_PER_GRAPH iterations; both give the same bits.
@@ -421,6 +447,7 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
     eot_iter = int(eot_iter)
     if eot_iter < 1:
         raise ValueError("APGD needs eot_iter >= 1, got %d" % eot_iter)
+    _check_norm(norm)
     model = _unwrap(model)
     x0 = x0.detach().contiguous()
     x_init = x_init.detach().contiguous()
@@ -430,7 +457,7 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
     if use_graph and trace is not None:
         raise ValueError("the APGD trace is recorded by eager runs only")
     if not use_graph:
-        run = _ApgdRun(x0, y, n_iter, eps, loss, eot_iter)
+        run = _ApgdRun(x0, y, n_iter, eps, loss, eot_iter, norm)
         run.trace = trace
         run.load(x_init, x0, y, targets)
         run.start(model)
@@ -439,10 +466,10 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
             g = run.iteration(model, g)
         return run.result()
     chunk = _eot_chunk(n_iter, eot_iter)
-    key = ("apgd", id(model), model.training, tuple(x0.shape), loss, n_iter, float(eps), x0.device.index, chunk, eot_iter)
+    key = ("apgd", id(model), model.training, tuple(x0.shape), loss, norm, n_iter, float(eps), x0.device.index, chunk, eot_iter)
 
     def build():
-        run = _ApgdRun(x0, y, n_iter, eps, loss, eot_iter)
+        run = _ApgdRun(x0, y, n_iter, eps, loss, eot_iter, norm)
         run.load(x_init, x0, y, targets)
 
         def body(model):  # the gradient enters through run.g and leaves through it (one copy per replay): inside the graph each

@@ -431,6 +431,30 @@ def apgd_step_(x, x_old, g, x0, step, counter, eps):
     return x
 
 
+APGD_L2_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_APGD_L2_PATH_*
+APGD_L2_RESIDENT = 12288  # per-sample size up to which the resident path exists
+
+
+def apgd_step_l2_(x, x_old, g, x0, step, counter, eps, norms=None, path="auto"):
+    """The step of an L2 run (ee_apgd_l2.hip) in place on x and x_old [B, ...]; step [B] float32, counter [1] int32.  Returns norms [3, B]
+    (||g||, ||z - x0|| after the gradient step, ||m - x0|| after the momentum mix), written into `norms` when given.  path: 'auto',
+    'resident' (per-sample size <= 12288) or 'streaming'; the same bits."""
+    B = x.shape[0]
+    px = _chk(x, torch.float32, "x")
+    po = _chk(x_old, torch.float32, "x_old", x.shape)
+    pg = _chk(g, torch.float32, "g", x.shape)
+    p0 = _chk(x0, torch.float32, "x0", x.shape)
+    ps = _chk(step, torch.float32, "step", (B,))
+    pc = _chk(counter, torch.int32, "counter", (1,))
+    if path not in APGD_L2_PATHS:
+        raise ValueError("the L2 step's path must be one of %s, got %r" % (sorted(APGD_L2_PATHS), path))
+    norms = torch.empty((3, B), dtype=torch.float32, device=x.device) if norms is None else norms
+    pn = _chk(norms, torch.float32, "norms", (3, B))
+    N.check(N.lib.ee_apgd_step_l2_f32(px, po, pg, p0, ps, pc, pn, B, x.numel() // B if B else 0, eps, APGD_L2_PATHS[path], _stream()),
+            "ee_apgd_step_l2_f32")
+    return norms
+
+
 def apgd_loss(logits, labels, kind, targets=None):
     """(row losses [B] float32, dlogits [B,K] of their sum, pred [B] int32) for kind 'ce', 'dlr' or 'dlr_t' (which reads targets)."""
     B, K = logits.shape

@@ -679,10 +679,34 @@ def eot_iter_for(args):
     return 1
 
 
+L2_MESSAGE = ("the L2 threat model is built for APGD-CE, APGD-T, APGD, APGD-DLR, Rand and Cascade-Rand only - L2 Square and L2 FAB are different "
+              "algorithms and are not built, so Square, APGD+Square, FAB-T, APGD+FAB+Square and Cascade have no L2, and the reference's own "
+              "attacks (PGD, FGSM, CW) are Linf")
+
+
+def norm_for(args):
+    """The threat model of args.attack_method from args.norm (--norm; None / absent: 'Linf').  'L2' with a method that has no L2, or any other
+    value, stops here with the list of methods that have it: nothing is silently run in Linf."""
+    norm = getattr(args, 'norm', None)
+    if norm is None or norm == 'Linf':
+        return 'Linf'
+    if norm != 'L2':
+        raise ValueError("--norm must be Linf or L2, got %r; %s" % (norm, L2_MESSAGE))
+    if args.attack_method not in L2_METHODS:
+        raise NotImplementedError("--norm L2 with --attack_method %s: %s" % (args.attack_method, L2_MESSAGE))
+    return 'L2'
+
+
+def norm_tag(args):
+    """What a validation log line carries after its numbers: nothing for Linf (the lines stay as they were), ' [norm L2]' for L2."""
+    return '' if norm_for(args) == 'Linf' else ' [norm L2]'
+
+
 def attack_for_validation(model, args, input, target, device, num_steps, step_size, n_class):
     """experiments_tinyimagenet.py:354-374."""
     targeted = "tar" in args.method_name
     eot_iter = eot_iter_for(args)
+    nkw = A._norm_kw(norm_for(args))  # empty for Linf: the calls below are then the ones made before --norm existed
     if args.attack_method == 'PGD':
         if targeted:
             return A.targeted_PGD(model, args, input, target, num_steps, step_size, n_class, device)[0]
@@ -706,9 +730,9 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
         x_adv, robust = None, None
         if args.attack_method in ('APGD-CE', 'APGD'):
-            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', eot_iter=eot_iter)
+            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', eot_iter=eot_iter, **nkw)
         if args.attack_method in ('APGD-T', 'APGD'):
-            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class)
+            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class, **nkw)
             if x_adv is None:
                 return xt
             x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
@@ -753,8 +777,8 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         if targeted:
             raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
         if args.attack_method == 'APGD-DLR':
-            return A.APGD(model, args, input, target, num_steps, 'dlr', eot_iter=eot_iter)[0]
-        return A.APGD_Rand(model, args, input, target, num_steps, eot_iter, n_class)[0]
+            return A.APGD(model, args, input, target, num_steps, 'dlr', eot_iter=eot_iter, **nkw)[0]
+        return A.APGD_Rand(model, args, input, target, num_steps, eot_iter, n_class, **nkw)[0]
     if args.attack_method == CASCADE_RAND_METHOD:
         raise NotImplementedError("--attack_method Cascade-Rand regroups the survivors of a whole split: it runs as eeadv.cascade.evaluate over the "
                                   "loader (driver.validate_cascade), not batch by batch")
@@ -771,6 +795,7 @@ RAND_METHODS = ('APGD-DLR', 'Rand')  # Rand: APGD-CE then APGD-DLR with EOT, the
 CASCADE_RAND_METHOD = 'Cascade-Rand'  # the same two, APGD-DLR on the survivors of APGD-CE only, over the whole split
 CASCADE_METHOD = 'Cascade'  # the same four attacks, each on the samples the ones before it left standing (eeadv.cascade)
 CASCADE_METHODS = (CASCADE_METHOD, CASCADE_RAND_METHOD)
+L2_METHODS = APGD_METHODS + RAND_METHODS + (CASCADE_RAND_METHOD,)  # every attack in them is an APGD run: --norm L2
 # what the AWP drivers validate with next to PGD
 EVAL_METHODS = APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS
 

@@ -40,6 +40,20 @@ def _uniform_start(x0, eps, noise=None):
     return torch.clamp(x0 + nz, 0, 1)
 
 
+def _l2_norms(v):
+    """||v[b]||_2 per sample [B] in v's dtype: the squares summed in float64, the root taken there, then cast."""
+    return torch.sqrt((v.reshape(v.shape[0], -1).to(torch.float64) ** 2).sum(dim=1)).to(v.dtype)
+
+
+def _l2_start(x0, eps, noise=None):
+    """The published start of APGD in the L2 threat model: clamp(x0 + eps * n / (||n||_2 + 1e-12), 0, 1) with n a standard normal draw per
+    element (`noise=` injects n) and the norm per sample.  Once per attack, in torch ops on whatever device x0 lives on."""
+    n = torch.randn_like(x0) if noise is None else noise.to(x0.device, x0.dtype)
+    tiny = torch.tensor(1e-12, dtype=torch.float32).to(x0.dtype)  # the constant is a float32 one in every dtype
+    scale = (torch.tensor(eps, dtype=x0.dtype) / (_l2_norms(n) + tiny)).view((-1,) + (1,) * (x0.dim() - 1))
+    return torch.clamp(x0 + n * scale, 0, 1)
+
+
 def _randn_start(x0, noise=None, scale=0.001):
     """attacks.py:250 / :406: x_natural + 0.001 * randn (NOT clamped)."""
     if runtime.require_device(x0, "random start"):
@@ -119,8 +133,9 @@ def targeted_PGD_trick(model, args, inputs, labels, num_steps, step_size, nclass
 # APGD-CE and APGD-T (Croce & Hein 2020): the two gradient attacks of AutoAttack's `standard` version.  Not in the
 # reference's utils/attacks.py - its drivers call the `autoattack` package for them.  Square, the black-box member, and FAB-T follow below;
 # `eot_iter` averages every gradient over that many forwards (EOT), and APGD_Rand is the `rand` version's order, APGD-CE then APGD-DLR with
-# EOT.  EOT for APGD-T, Square and FAB-T, the L2 / L1 norms and restarts are NOT here, so the result is not an
-# AutoAttack number.
+# EOT.  `norm="L2"` runs APGD (every loss, EOT included) in the L2 threat model of radius args.epsilon: the published
+# L2 step and start, everything else shared.  EOT for APGD-T, Square and FAB-T, L2 Square and L2 FAB, the L1 norm
+# and restarts are NOT here, so the result is not an AutoAttack number.
 # ---------------------------------------------------------------------------------------------------------
 def _apgd_row_losses(z, y, loss, t=None):
     """Row losses [B] of logits [B,K] in z's dtype; classes ordered by value descending, ties to the lower index."""
@@ -141,14 +156,23 @@ def _apgd_row_losses(z, y, loss, t=None):
     raise ValueError("APGD loss must be 'ce', 'dlr' or 'dlr_t', got %r" % (loss,))
 
 
-def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=1):
+def _check_norm(norm):
+    if norm not in engine.APGD_NORMS:
+        raise ValueError("APGD norm must be one of %s, got %r" % (list(engine.APGD_NORMS), norm))
+    return norm
+
+
+def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=1, norm="Linf"):
     """Plumbing path for CPU tensors (opt-in), the counterpart of _host_loop: the iteration of engine.apgd_loop in plain torch ops, in the
     input's dtype.  `trace`, a list, receives one dict of clones per iteration (the start point first).  eot_iter = E > 1: every gradient
     is the sum of E draws' gradients in draw order times 1/E (formed in the input's dtype), the loss the mean of their row losses summed
-    in float64, pred the last draw's; the trace then also holds draw_loss / draw_g / draw_pred, stacked over the draws."""
+    in float64, pred the last draw's; the trace then also holds draw_loss / draw_g / draw_pred, stacked over the draws.  norm = "L2": the
+    step is the one of csrc/ee_apgd_l2.hip in torch ops (each norm the root of the squares summed in float64, cast to the dtype; a sample
+    whose gradient norm is not finite takes no gradient step) and the trace also holds norms [3, B]; everything else is shared."""
     E = int(eot_iter)
     if E < 1:
         raise ValueError("APGD needs eot_iter >= 1, got %d" % E)
+    _check_norm(norm)
     last = {}
 
     def grad_at(xc):
@@ -177,6 +201,27 @@ def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=
         return torch.clamp(torch.min(torch.max(v, x0 - eps), x0 + eps), 0, 1)
 
     shape = (-1,) + (1,) * (x0.dim() - 1)
+
+    def step_linf(x, x_old, g, step, a):
+        z = proj(x + step.view(shape) * torch.sign(g))
+        return proj((x + (z - x) * a) + (x - x_old) * (1.0 - a))
+
+    def step_l2(x, x_old, g, step, a):
+        tiny = torch.tensor(1e-12, dtype=torch.float32).to(x.dtype)  # the constant is a float32 one in every dtype
+        radius = torch.tensor(eps, dtype=x.dtype)
+        ng = _l2_norms(g)
+        sg = step / (ng + tiny)
+        z = torch.where(torch.isfinite(ng).view(shape), x + g * sg.view(shape), x)
+        d = z - x0
+        n1 = _l2_norms(d)
+        z = torch.clamp(x0 + d * (torch.minimum(radius, n1) / (n1 + tiny)).view(shape), 0, 1)
+        m = (x + (z - x) * a) + (x - x_old) * (1.0 - a)
+        d = m - x0
+        n2 = _l2_norms(d)
+        last.update(norms=torch.stack([ng, n1, n2]))
+        return torch.clamp(x0 + d * (torch.minimum(radius, n2) / (n2 + tiny)).view(shape), 0, 1)
+
+    step_fn = step_l2 if norm == "L2" else step_linf
     sched = engine.apgd_schedule(n_iter)
     x = x.detach()
     l, g, pred = grad_at(x)
@@ -196,8 +241,7 @@ def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=
     note()
     for i in range(n_iter):
         a = 1.0 if i == 0 else 0.75
-        z = proj(x + step.view(shape) * torch.sign(g))
-        x_new = proj((x + (z - x) * a) + (x - x_old) * (1.0 - a))
+        x_new = step_fn(x, x_old, g, step, a)
         x_old, x = x, x_new
         l, g, pred = grad_at(x)
         fooled = ~pred
@@ -223,8 +267,8 @@ def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=
     return torch.where(robust.view(shape), x0, x_best_adv), robust, loss_best
 
 
-def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None, eot_iter=1):
-    """One APGD run (Linf, eps = args.epsilon, num_steps iterations) on loss 'ce', 'dlr' or 'dlr_t' (targeted at `y_target`).  Returns
+def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None, eot_iter=1, norm="Linf"):
+    """One APGD run (norm 'Linf' or 'L2', radius args.epsilon, num_steps iterations) on loss 'ce', 'dlr' or 'dlr_t' (targeted at `y_target`).  Returns
     (x_adv, robust): the inputs, with every sample that some iterate fooled replaced by such an iterate, and the [B] bool flags of the samples
     that stayed correctly classified throughout.  The start point is the project's uniform start, clamp(x0 + U(-eps, eps), 0, 1) (`noise=`
     injects the draw); the public implementation rescales each sample's draw to the full radius first - that normalisation is deliberately
@@ -232,28 +276,39 @@ def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, nois
     z_p1 - z_p3 and z_p1 - z_p4 (csrc/ee_apgd.hip: no cancellation against a rounded sum); the host path below keeps
     z_p1 - (z_p3 + z_p4)/2, so an fp32 host run and a device run differ in the last bits of the `dlr_t` loss.  eot_iter = E > 1 (for a
     defence that redraws at every forward): every gradient is the mean over E forwards, the loss the run keeps books on is the mean of
-    their row losses, and a sample counts as fooled when the last of the E draws of some iterate misclassifies it."""
+    their row losses, and a sample counts as fooled when the last of the E draws of some iterate misclassifies it.
+    norm = "L2": the ball is the L2 ball, the step the published L2 step (csrc/ee_apgd_l2.hip; a rescale onto the ball followed by the
+    clamp, not the exact projection onto ball and box) and the start the published one, clamp(x0 + eps n / ||n||_2, 0, 1) - `noise=` then
+    injects the standard normal draw n."""
     eot_iter = int(eot_iter)
     if eot_iter < 1:
         raise ValueError("APGD needs eot_iter >= 1, got %d" % eot_iter)
+    _check_norm(norm)
     x0 = inputs.detach()
     eps = float(args.epsilon)
-    x = _uniform_start(x0, eps, noise)
+    x = _uniform_start(x0, eps, noise) if norm == "Linf" else _l2_start(x0, eps, noise)
+    kw = {} if norm == "Linf" else {"norm": norm}  # a Linf run makes exactly the calls made before the parameter existed
     if runtime.require_device(x0, "APGD"):
-        x_adv, robust, _ = engine.apgd_loop(model, x0, x, targets, num_steps, eps, loss, y_target, eot_iter=eot_iter)
+        x_adv, robust, _ = engine.apgd_loop(model, x0, x, targets, num_steps, eps, loss, y_target, eot_iter=eot_iter, **kw)
     else:
-        x_adv, robust, _ = _apgd_host(model, x0, x, targets, num_steps, eps, loss, y_target, eot_iter=eot_iter)
+        x_adv, robust, _ = _apgd_host(model, x0, x, targets, num_steps, eps, loss, y_target, eot_iter=eot_iter, **kw)
     return x_adv, robust
 
 
-def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None, noise=None):
+def _norm_kw(norm):
+    """The keyword the composites hand on to APGD: none for Linf, so that a Linf call is the call made before the parameter existed."""
+    return {} if _check_norm(norm) == "Linf" else {"norm": norm}
+
+
+def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None, noise=None, norm="Linf"):
     """The order of the public ensemble's `rand` version, for defences that redraw at every forward: APGD-CE, then APGD-DLR (the untargeted
     DLR loss), each one run of num_steps iterations with every gradient averaged over eot_iter forwards, each on the whole batch.  Returns
     (x_adv, robust) with the flags ANDed and, per sample, the first fooling point - as APGD_T combines its runs.  The DLR loss reads the three
-    largest logits: `nclass` (default: read off one clean forward) must be at least 3."""
+    largest logits: `nclass` (default: read off one clean forward) must be at least 3.  norm: 'Linf' or 'L2', for both runs."""
     eot_iter = int(eot_iter)
     if eot_iter < 1:
         raise ValueError("APGD_Rand needs eot_iter >= 1, got %d" % eot_iter)
+    kw = _norm_kw(norm)
     x0 = inputs.detach()
     if nclass is None:
         with torch.no_grad():
@@ -261,8 +316,8 @@ def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None,
     if int(nclass) < 3:
         raise ValueError("APGD_Rand runs APGD-DLR, whose loss is normalised by the spread of the three largest logits: it needs at least 3 "
                          "classes and this model has %d (MNIST's 10 are enough; only the targeted DLR loss of APGD-T needs 4)" % int(nclass))
-    x_adv, robust = APGD(model, args, inputs, targets, num_steps, 'ce', None, noise, eot_iter)
-    xd, rd = APGD(model, args, inputs, targets, num_steps, 'dlr', None, noise, eot_iter)
+    x_adv, robust = APGD(model, args, inputs, targets, num_steps, 'ce', None, noise, eot_iter, **kw)
+    xd, rd = APGD(model, args, inputs, targets, num_steps, 'dlr', None, noise, eot_iter, **kw)
     x_adv = torch.where((robust & ~rd).view((-1,) + (1,) * (x0.dim() - 1)), xd, x_adv)
     return x_adv, robust & rd
 
@@ -282,11 +337,13 @@ def _class_order(model, x0, n_t, what, order=None):
     return torch.sort(z, dim=1, descending=True, stable=True)[1][:, :n_t + 1]
 
 
-def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None, order=None):
+def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None, order=None, norm="Linf"):
     """Targeted APGD on the DLR loss: one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most
     nclass - 1 of them), each on the whole batch - samples fooled by an earlier target are carried along, which keeps one shape (one captured
     graph) for all runs.  Returns (x_adv, robust) with the flags ANDed over the runs and, per sample, the first fooling point.  `order`
-    [B, n_t + 1]: the class order of the clean logits if the caller has it already - the clean forward is then skipped."""
+    [B, n_t + 1]: the class order of the clean logits if the caller has it already - the clean forward is then skipped.  norm: 'Linf' or
+    'L2', for every run; the class order does not know the norm."""
+    kw = _norm_kw(norm)
     x0 = inputs.detach()
     n_t = min(int(n_target_classes), int(nclass) - 1)
     order = _class_order(model, x0, n_t, "APGD_T", order)
@@ -294,7 +351,7 @@ def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, 
     robust = torch.ones(x0.shape[0], dtype=torch.bool, device=x0.device)
     shape = (-1,) + (1,) * (x0.dim() - 1)
     for j in range(1, n_t + 1):
-        xa, rb = APGD(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise)
+        xa, rb = APGD(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise, **kw)
         x_adv = torch.where((robust & ~rb).view(shape), xa, x_adv)
         robust = robust & rb
     return x_adv, robust

@@ -240,6 +240,29 @@ int ee_topk_i64(const float *logits, const int64_t *labels, int B, int K, int k,
 int ee_apgd_step_f32(float *x, float *x_old, const float *g, const float *x0, const float *step, const int *counter, int64_t B,
                      int64_t per_sample, float eps, void *stream);
 
+/* The step of an APGD run in the L2 threat model (ee_apgd_l2.hip), one launch in the place of ee_apgd_step_f32, in place on x and x_old.
+ * Per sample b, with step = step[b], a = 1 when counter[0] == 0, else 0.75, tiny = 1e-12f, every operation rounded once in f32:
+ *     ng = ||g||_2                 sg = step / (ng + tiny)
+ *     z  = x + g * sg                                       (z = x when ng is not finite: a NaN or Inf gradient takes no gradient step)
+ *     d  = z - x0      n1 = ||d||_2      s1 = min(eps, n1) / (n1 + tiny)
+ *     z  = clamp(x0 + d * s1, 0, 1)
+ *     m  = (x + (z - x) * a) + (x - x_old) * (1 - a)
+ *     d  = m - x0      n2 = ||d||_2      s2 = min(eps, n2) / (n2 + tiny)
+ *     x_new = clamp(x0 + d * s2, 0, 1);   x_old = x;   x = x_new
+ * The rescale followed by the clamp is the published step, not the exact projection onto the intersection of ball and box.  clamp and min
+ * propagate NaN.  Each norm is (float) sqrt(S), S the sum of the exact squares in double in an order fixed by per_sample and the launch
+ * shape; norms [3, B] receives ng, n1, n2 (required: the trace and the tests read it).  One workgroup per sample; it reads step[b] and
+ * counter[0] and advances nothing.  path: EE_APGD_L2_PATH_AUTO picks by size, _RESIDENT keeps a sample's x, x_old, g, x0 in registers
+ * across the three reductions (per_sample <= 12288, else EE_ERR_UNSUPPORTED; 24 B of HBM traffic per element), _STREAMING re-reads them
+ * (any per_sample; no scratch tensor); the two return the same bits.  16-byte accesses when per_sample % 4 == 0 and x, x_old, g, x0 are
+ * 16-byte aligned, element-wise otherwise - the same sums.  eps < 0 or NaN, a path outside the three: EE_ERR_SHAPE.  B == 0 or
+ * per_sample == 0 launches nothing. */
+#define EE_APGD_L2_PATH_AUTO 0
+#define EE_APGD_L2_PATH_RESIDENT 1
+#define EE_APGD_L2_PATH_STREAMING 2
+int ee_apgd_step_l2_f32(float *x, float *x_old, const float *g, const float *x0, const float *step, const int *counter, float *norms,
+                        int64_t B, int64_t per_sample, float eps, int path, void *stream);
+
 /* Per row of logits [B,K]: row_loss[B] (fp32), dlogits[B,K] = d sum_b loss_b / d logits, pred[B] = (p1 == y), where p1, p2, ...
  * are the classes by value descending, ties to the lower index (the order of ee_topk_i64).  kind = EE_APGD_CE / _DLR / _DLR_T;
  * targets [B] is read for EE_APGD_DLR_T only.  K below the kind's minimum: EE_ERR_UNSUPPORTED.  The targeted denominator is formed
