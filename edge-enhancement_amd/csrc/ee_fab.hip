@@ -20,6 +20,11 @@
 // floats are exact there) in one fixed order - thread t takes the float4 groups t, t + 512, ... in turn, wavefronts are reduced by
 // xor-shuffles, the eight partial sums are added in index order - which the resident path (a problem's |w_i| and r_i stay in registers across
 // all passes, D <= 12288) and the streaming path (re-read through L2) share, so the two return the same bits.
+//
+// The L2 threat model changes the metric at three points and nothing else: ee_fab_proj_l2_f32 (the least-||.||_2
+// delta: delta_i = -sign(v_i) min(mu |v_i|, r_i), g(mu) = sum_i |v_i| min(mu |v_i|, r_i), breakpoints t_i = r_i / |v_i| - the same 31-step
+// search and exact segment solve, mu = (c' - sum_{t_i <= T} |v_i| r_i) / sum_{t_i > T} v_i^2), ee_fab_step_l2_f32 (rebuilds those deltas)
+// and ee_fab_commit_l2_f32 (||x - x0||_2 in double in the fixed order above).  ee_fab_diff_f32 is shared.
 #include <math.h>
 
 #include "ee_rows.hpp"
@@ -226,6 +231,151 @@ __global__ __launch_bounds__(kProjBlock) void proj_kernel(const float *__restric
     if (threadIdx.x == 0) *lam_out = lam, *sgn_out = s, *nrm_out = fminf(lam, rmax);
 }
 
+// ---- the L2 projection -----------------------------------------------------------------------------------------------------------------
+// The breakpoint of a coordinate: the f32 quotient, rounded once - the one definition both paths (and the host path) classify by.  A
+// denormal |v_i| overflows it to +inf: that coordinate never saturates.  |v_i| = 0 (its room is 0 too) gives 0: the coordinate counts as
+// saturated from the start and adds exact zeros, so no pass ever forms inf * 0.
+__device__ __forceinline__ float ratio(float a, float r) { return a != 0.0f ? r / a : 0.0f; }
+
+// each_element with the breakpoint: the resident path keeps t[] next to a[] / r[], the streaming path recomputes it from what it re-reads
+template <bool RES, bool VEC, class F>
+__device__ __forceinline__ void each_element_l2(const float *__restrict__ w, const float *__restrict__ p, int64_t D, int groups, float s,
+                                                const float (&a)[kProjVecs * 4], const float (&r)[kProjVecs * 4],
+                                                const float (&t)[kProjVecs * 4], F body) {
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kProjVecs * 4; ++k) body(a[k], r[k], t[k]);
+    } else {
+        for (int g = 0; g < groups; ++g) {
+            const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+            float wv[4], pv[4];
+            load4<VEC>(w, e, D, wv);
+            load4<VEC>(p, e, D, pv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float av = fabsf(wv[j]), rv = room(s * wv[j], pv[j]);
+                body(av, rv, ratio(av, rv));
+            }
+        }
+    }
+}
+
+template <bool RES, bool VEC>
+__global__ __launch_bounds__(kProjBlock) void proj_l2_kernel(const float *__restrict__ x, const float *__restrict__ x0,
+                                                             const float *__restrict__ w, const float *__restrict__ df, int B, int64_t D,
+                                                             float *__restrict__ out) {
+    __shared__ double sh[2 * kProjWaves];
+    Reducer red{sh, 0};
+    const int q = blockIdx.x, b = q < B ? q : q - B;
+    const bool second = q >= B;  // problem B + b projects x0, problem b projects x
+    const float *xr = x + static_cast<int64_t>(b) * D, *x0r = x0 + static_cast<int64_t>(b) * D, *wr = w + static_cast<int64_t>(b) * D;
+    const float *pr = second ? x0r : xr;
+    const int groups = static_cast<int>((D + 4 * kProjBlock - 1) / (4 * kProjBlock));  // float4 groups per thread; <= kProjVecs when RES
+    float *mu_out = out + q, *sgn_out = out + 2 * static_cast<int64_t>(B) + q, *nrm_out = out + 4 * static_cast<int64_t>(B) + q;
+
+    // pass 1, as in proj_kernel: sum |w_i| and sum w_i (x0_i - x_i); the resident path keeps w in a[] and the point in r[]
+    float a[kProjVecs * 4], r[kProjVecs * 4], t[kProjVecs * 4];
+    double sabs = 0.0, dot = 0.0;
+    auto first = [&](int g) {
+        const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+        float wv[4], xv[4], ov[4];
+        load4<VEC>(wr, e, D, wv);
+        load4<VEC>(xr, e, D, xv);
+        load4<VEC>(x0r, e, D, ov);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            sabs += static_cast<double>(fabsf(wv[j]));
+            dot = fma(static_cast<double>(wv[j]), static_cast<double>(ov[j] - xv[j]), dot);
+            if (RES) {
+                a[g * 4 + j] = wv[j];
+                r[g * 4 + j] = second ? ov[j] : xv[j];
+            }
+        }
+    };
+    if (RES) {
+#pragma unroll
+        for (int g = 0; g < kProjVecs; ++g) first(g);
+    } else {
+        for (int g = 0; g < groups; ++g) first(g);
+    }
+    sabs = red.sum(sabs);
+    dot = red.sum(dot);
+    const float d = df[b];
+    // every decision below is taken on values all threads of the workgroup hold alike: the early exits are uniform
+    if (!(isfinite(d) && d != 0.0f && isfinite(sabs) && sabs > 0.0)) {  // no hyperplane to project onto: both problems of the sample rest
+        if (threadIdx.x == 0) *mu_out = 0.0f, *sgn_out = 0.0f, *nrm_out = 0.0f;
+        return;
+    }
+    const float c = second ? static_cast<float>(static_cast<double>(d) + dot) : d;
+    const float s = c >= 0.0f ? 1.0f : -1.0f;  // NaN cannot come here: d and dot are finite
+    const float cp = fabsf(c);
+    if (!isfinite(c) || cp == 0.0f) {  // c = 0: the point lies on the hyperplane
+        if (threadIdx.x == 0) *mu_out = 0.0f, *sgn_out = 1.0f, *nrm_out = 0.0f;
+        return;
+    }
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kProjVecs * 4; ++k) {
+            const float wv = a[k];
+            r[k] = room(s * wv, r[k]);
+            a[k] = fabsf(wv);
+            t[k] = ratio(a[k], r[k]);
+        }
+    }
+    // g(inf) = sum |v_i| r_i
+    double ginf = 0.0;
+    each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t,
+                              [&](float av, float rv, float) { ginf = fma(static_cast<double>(av), static_cast<double>(rv), ginf); });
+    ginf = red.sum(ginf);
+    const double cpd = static_cast<double>(cp);
+    if (cpd >= ginf) {  // infeasible inside the box: every coordinate that can move goes to its bound
+        double rs = 0.0;
+        each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t, [&](float av, float rv, float) {
+            if (av != 0.0f) rs = fma(static_cast<double>(rv), static_cast<double>(rv), rs);
+        });
+        rs = red.sum(rs);
+        if (threadIdx.x == 0) *mu_out = INFINITY, *sgn_out = s, *nrm_out = static_cast<float>(sqrt(rs));
+        return;
+    }
+    // g(T) = sum_{t_i <= T} |v_i| r_i + T sum_{t_i > T} v_i^2 (v_i^2 is exact in double).  T: the largest non-negative float with
+    // g(T) < c'.  g(0) = 0 < c' holds; at T = +inf every coordinate is saturated and the sum is ginf, term for term, which is not below
+    // c' - so T stays finite and no candidate is a NaN pattern.
+    uint32_t T = 0u;
+    for (int bit = 30; bit >= 0; --bit) {
+        const uint32_t cand = T | (1u << bit);
+        const float tf = __uint_as_float(cand);
+        const double td = static_cast<double>(tf);
+        double part = 0.0;
+        each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t, [&](float av, float rv, float tv) {
+            const double ad = static_cast<double>(av);
+            const bool sat = tv <= tf;
+            part = fma(sat ? ad : ad * ad, sat ? static_cast<double>(rv) : td, part);
+        });
+        if (red.sum(part) < cpd) T = cand;
+    }
+    // the segment (T, next breakpoint]: g(mu) = S + mu A there
+    const float tl = __uint_as_float(T);
+    double S = 0.0, A = 0.0;
+    each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t, [&](float av, float rv, float tv) {
+        const double ad = static_cast<double>(av);
+        if (tv <= tl)
+            S = fma(ad, static_cast<double>(rv), S);
+        else
+            A = fma(ad, ad, A);
+    });
+    S = red.sum(S);
+    A = red.sum(A);
+    const double mud = A > 0.0 ? (cpd - S) / A : static_cast<double>(INFINITY);
+    // ||delta||_2 from the solution before its rounding to float: the emitted norm is the correctly rounded one (or its neighbour)
+    double n2 = 0.0;
+    each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t, [&](float av, float rv, float) {
+        const double m = av != 0.0f ? fmin(mud * static_cast<double>(av), static_cast<double>(rv)) : 0.0;  // never inf * 0
+        n2 = fma(m, m, n2);
+    });
+    n2 = red.sum(n2);
+    if (threadIdx.x == 0) *mu_out = static_cast<float>(mud), *sgn_out = s, *nrm_out = static_cast<float>(sqrt(n2));
+}
+
 // ---- the step ------------------------------------------------------------------------------------------------------------------------
 struct StepSample {
     float l1, s1, l2, s2, alpha;
@@ -240,15 +390,22 @@ __device__ __forceinline__ StepSample step_sample(const float *__restrict__ scal
     return r;
 }
 
+// L2: delta_i = -sign(v_i) min(mu |v_i|, r_i), the product rounded once; |v_i| = 0 rests, so mu = inf never meets a 0
+__device__ __forceinline__ float delta_l2(float v, float p, float mu) {
+    const float a = fabsf(v);
+    return a != 0.0f ? -sgn(v) * tmin(mu * a, room(v, p)) : 0.0f;
+}
+
+template <bool L2>
 __device__ __forceinline__ float step_op(float x, float x0, float w, const StepSample &sm) {
     if (sm.s1 == 0.0f) return x;  // a sample without a hyperplane stays where it is
     const float v1 = sm.s1 * w, v2 = sm.s2 * w;
-    const float d1 = -sgn(v1) * fminf(sm.l1, room(v1, x));
-    const float d2 = -sgn(v2) * fminf(sm.l2, room(v2, x0));
+    const float d1 = L2 ? delta_l2(v1, x, sm.l1) : -sgn(v1) * fminf(sm.l1, room(v1, x));
+    const float d2 = L2 ? delta_l2(v2, x0, sm.l2) : -sgn(v2) * fminf(sm.l2, room(v2, x0));
     return tclamp((x + kEta * d1) * (1.0f - sm.alpha) + (x0 + kEta * d2) * sm.alpha, 0.0f, 1.0f);
 }
 
-template <int VEC>
+template <int VEC, bool L2 = false>
 __global__ __launch_bounds__(kBlock) void step_kernel(float *x, const float *__restrict__ x0, const float *__restrict__ w,
                                                       const float *__restrict__ scal, int64_t B, int64_t per_sample) {
     const int64_t n = B * per_sample;
@@ -266,32 +423,22 @@ __global__ __launch_bounds__(kBlock) void step_kernel(float *x, const float *__r
         if (base - b * per_sample + 4 <= per_sample) {  // the four elements belong to one sample
             const StepSample sm = step_sample(scal, B, b);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) out[k] = step_op(xi[k], oi[k], wi[k], sm);
+            for (int k = 0; k < 4; ++k) out[k] = step_op<L2>(xi[k], oi[k], wi[k], sm);
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) out[k] = step_op(xi[k], oi[k], wi[k], step_sample(scal, B, (base + k) / per_sample));  // base + k < n
+            for (int k = 0; k < 4; ++k) out[k] = step_op<L2>(xi[k], oi[k], wi[k], step_sample(scal, B, (base + k) / per_sample));  // base + k < n
         }
         reinterpret_cast<float4 *>(x)[v] = make_float4(out[0], out[1], out[2], out[3]);
     }
-    for (int64_t e = (nv << 2) + i; e < n; e += stride) x[e] = step_op(x[e], x0[e], w[e], step_sample(scal, B, e / per_sample));
+    for (int64_t e = (nv << 2) + i; e < n; e += stride) x[e] = step_op<L2>(x[e], x0[e], w[e], step_sample(scal, B, e / per_sample));
 }
 
 // ---- the check after the second forward ------------------------------------------------------------------------------------------------
+// ||x - x0||_inf of the sample at `off`; every thread gets it
 template <int VEC>
-__global__ __launch_bounds__(kCommitBlock) void commit_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels, int K, float *x,
-                                                              const float *__restrict__ x0, float *adv, float *res, int *__restrict__ pred,
-                                                              int *__restrict__ flags, int *counter, int64_t per_sample) {
+__device__ __forceinline__ float commit_norm_linf(const float *x, const float *x0, int64_t off, int64_t per_sample) {
     __shared__ float sh_max[kCommitWaves];
-    __shared__ int sh_first, sh_nan;
-    const int b = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
-    if (b == 0 && threadIdx.x == 0) counter[0] = counter[0] + 1;  // nobody reads the counter in this launch
-    const float best = res[b];  // read by every thread before the barrier below, written by thread 0 after it
-    if (wave == 0) {
-        bool nan;
-        const int first = row_first(logits + static_cast<size_t>(b) * K, K, lane, nan);
-        if (lane == 0) sh_first = first, sh_nan = nan ? 1 : 0;
-    }
-    const int64_t off = static_cast<int64_t>(b) * per_sample;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     float m = 0.0f;
     if (VEC == 4) {  // per_sample % 4 == 0 and 16-byte bases: a sample is a whole number of aligned vectors
         const float4 *vx = reinterpret_cast<const float4 *>(x + off), *v0 = reinterpret_cast<const float4 *>(x0 + off);
@@ -308,6 +455,55 @@ __global__ __launch_bounds__(kCommitBlock) void commit_kernel(const float *__res
     m = sh_max[0];
 #pragma unroll
     for (int i = 1; i < kCommitWaves; ++i) m = fmaxf(m, sh_max[i]);
+    return m;
+}
+
+// ||x - x0||_2 of the sample at `off` - the squares of the f32 differences summed in double in the order of the projection (thread t takes
+// the groups of four elements t, t + 512, ... whatever the access width), so vector and element-wise calls return the same bits
+template <bool VEC>
+__device__ __forceinline__ float commit_norm_l2(const float *x, const float *x0, int64_t off, int64_t per_sample) {
+    __shared__ double sh_sum[kCommitWaves];
+    double sq = 0.0;
+    for (int64_t e = static_cast<int64_t>(threadIdx.x) * 4; e < per_sample; e += kCommitBlock * 4) {
+        float pv[4], ov[4];
+        load4<VEC>(x + off, e, per_sample, pv);
+        load4<VEC>(x0 + off, e, per_sample, ov);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double d = static_cast<double>(pv[j] - ov[j]);
+            sq = fma(d, d, sq);
+        }
+    }
+    sq = wave_sum(sq);
+    if ((threadIdx.x & (kWave - 1)) == 0) sh_sum[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    double r = sh_sum[0];
+#pragma unroll
+    for (int i = 1; i < kCommitWaves; ++i) r += sh_sum[i];
+    return static_cast<float>(sqrt(r));
+}
+
+// L2 = false: the distance is ||x - x0||_inf; true: ||x - x0||_2.  Everything else is one code.
+template <int VEC, bool L2 = false>
+__global__ __launch_bounds__(kCommitBlock) void commit_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels, int K, float *x,
+                                                              const float *__restrict__ x0, float *adv, float *res, int *__restrict__ pred,
+                                                              int *__restrict__ flags, int *counter, int64_t per_sample) {
+    __shared__ int sh_first, sh_nan;
+    const int b = blockIdx.x, lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+    if (b == 0 && threadIdx.x == 0) counter[0] = counter[0] + 1;  // nobody reads the counter in this launch
+    const float best = res[b];  // read by every thread before the barrier below, written by thread 0 after it
+    if (wave == 0) {
+        bool nan;
+        const int first = row_first(logits + static_cast<size_t>(b) * K, K, lane, nan);
+        if (lane == 0) sh_first = first, sh_nan = nan ? 1 : 0;
+    }
+    const int64_t off = static_cast<int64_t>(b) * per_sample;
+    // the distance; the barrier inside also publishes sh_first / sh_nan
+    float m;
+    if constexpr (L2)
+        m = commit_norm_l2<VEC == 4>(x, x0, off, per_sample);
+    else
+        m = commit_norm_linf<VEC>(x, x0, off, per_sample);
     const int64_t y = labels[b];
     const int first = sh_first;
     const bool is_adv = !sh_nan && y >= 0 && y < K && first != y;  // a row with a NaN logit is never adversarial
@@ -410,5 +606,63 @@ EE_API int ee_fab_commit_f32(const float *logits, const int64_t *labels, int B, 
     else
         EE_LAUNCH(commit_kernel<1>, dim3(static_cast<unsigned>(B)), dim3(kCommitBlock), 0, as_stream(stream), logits, labels, K, x, x0, adv, res,
                   pred, flags, counter, per_sample);
+    return launch_status();
+}
+
+EE_API int ee_fab_proj_l2_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path,
+                              float *out, void *stream) {
+    if (bad_shape(B, per_sample) || per_sample < 1 || path < EE_FAB_PATH_AUTO || path > EE_FAB_PATH_STREAMING) return EE_ERR_SHAPE;
+    if (path == EE_FAB_PATH_RESIDENT && per_sample > kProjResident) return EE_ERR_UNSUPPORTED;
+    if (B == 0) return EE_OK;
+    if (!x || !x0 || !w || !df || !out) return EE_ERR_NULL;
+    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(df) || !aligned4(out)) return EE_ERR_ALIGN;
+    const bool res = path == EE_FAB_PATH_RESIDENT || (path == EE_FAB_PATH_AUTO && per_sample <= kProjResident);
+    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x0) && aligned16(w);  // every row then starts 16-byte aligned
+    const dim3 grid(static_cast<unsigned>(2 * B)), block(kProjBlock);
+    const int nb = static_cast<int>(B);
+    ProfScope prof(EE_K_FAB_PROJ, as_stream(stream));
+    if (res && vec)
+        EE_LAUNCH((proj_l2_kernel<true, true>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+    else if (res)
+        EE_LAUNCH((proj_l2_kernel<true, false>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+    else if (vec)
+        EE_LAUNCH((proj_l2_kernel<false, true>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+    else
+        EE_LAUNCH((proj_l2_kernel<false, false>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+    return launch_status();
+}
+
+EE_API int ee_fab_step_l2_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
+    if (bad_shape(B, per_sample)) return EE_ERR_SHAPE;
+    const int64_t n = B * per_sample;
+    if (n == 0) return EE_OK;
+    if (!x || !x0 || !w || !scal) return EE_ERR_NULL;
+    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(scal)) return EE_ERR_ALIGN;
+    const bool vec = aligned16(x) && aligned16(x0) && aligned16(w);
+    const unsigned blocks = grid_for(vec ? (n + 3) / 4 : n);
+    ProfScope prof(EE_K_FAB_STEP, as_stream(stream));
+    if (vec)
+        EE_LAUNCH((step_kernel<4, true>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+    else
+        EE_LAUNCH((step_kernel<1, true>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+    return launch_status();
+}
+
+EE_API int ee_fab_commit_l2_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res,
+                                int *pred, int *flags, int *counter, int64_t per_sample, void *stream) {
+    if (B < 0 || K < 2 || K > 65536 || bad_shape(B, per_sample)) return EE_ERR_SHAPE;
+    if (B == 0 || per_sample == 0) return EE_OK;  // an empty batch is no attack: nothing is launched, the counter stays
+    if (!logits || !labels || !x || !x0 || !adv || !res || !pred || !flags || !counter) return EE_ERR_NULL;
+    if (!aligned4(logits) || !aligned4(x) || !aligned4(x0) || !aligned4(adv) || !aligned4(res) || !aligned4(pred) || !aligned4(flags) ||
+        !aligned4(counter) || (reinterpret_cast<uintptr_t>(labels) & 7u))
+        return EE_ERR_ALIGN;
+    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x0) && aligned16(adv);
+    ProfScope prof(EE_K_FAB_COMMIT, as_stream(stream));
+    if (vec)
+        EE_LAUNCH((commit_kernel<4, true>), dim3(static_cast<unsigned>(B)), dim3(kCommitBlock), 0, as_stream(stream), logits, labels, K, x, x0,
+                  adv, res, pred, flags, counter, per_sample);
+    else
+        EE_LAUNCH((commit_kernel<1, true>), dim3(static_cast<unsigned>(B)), dim3(kCommitBlock), 0, as_stream(stream), logits, labels, K, x, x0,
+                  adv, res, pred, flags, counter, per_sample);
     return launch_status();
 }

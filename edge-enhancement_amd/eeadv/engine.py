@@ -625,8 +625,21 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# FAB-T (Croce & Hein 2020; Linf, targeted, eta = 1.05, beta = 0.9, alpha_max = 0.1, one run from x0, no EOT): DESIGN.md section 13
+# FAB-T (Croce & Hein 2020; Linf or L2, targeted, eta = 1.05, beta = 0.9, alpha_max = 0.1, one run from x0, no EOT): DESIGN.md sections
+# 13 and 17
 # ---------------------------------------------------------------------------------------------------------------------------------------
+FAB_NORMS = ("Linf", "L2")
+
+
+def _fab_ops(norm):
+    """(projection, step, commit) of a FAB run in the threat model `norm`: the metric enters FAB at these three launches only."""
+    if norm == "Linf":
+        return ops.fab_proj_linf, ops.fab_step_, ops.fab_commit_
+    if norm == "L2":
+        return ops.fab_proj_l2, ops.fab_step_l2_, ops.fab_commit_l2_
+    raise ValueError("FAB norm must be one of %s, got %r" % (list(FAB_NORMS), norm))
+
+
 class _FabSpec:
     """The loss-gradient step of `_body_input_grad` for a FAB run: df = z_t - z_y, its logit gradient and `pred` in one launch.  The kind is
     none of the CE kinds, so the route is the generic one (logits -> this -> autograd), through the whole model for edge-enhanced ones."""
@@ -644,9 +657,10 @@ class _FabRun:
     """The device state of one FAB-T run (include/eeadv.h, "FAB-T") and its two pieces: `start` (the initial state: a few fills, once per
     run) and `iteration` (forward, diff, backward, projection, step, forward, commit: what a captured graph replays).  No host read anywhere."""
 
-    def __init__(self, x0, y, n_iter, path="auto"):
+    def __init__(self, x0, y, n_iter, path="auto", norm="Linf"):
         B, dev = x0.shape[0], x0.device
-        self.n_iter, self.path = int(n_iter), path
+        self.n_iter, self.path, self.norm = int(n_iter), path, norm
+        self.proj, self.step_, self.commit_ = _fab_ops(norm)
         self.x = torch.empty_like(x0).requires_grad_(True)
         self.x0, self.adv = torch.empty_like(x0), torch.empty_like(x0)
         self.y = torch.empty(B, dtype=torch.int64, device=dev)
@@ -676,11 +690,11 @@ class _FabRun:
     def iteration(self, model):
         w = input_gradient(model, self.x, self.spec).contiguous()
         x = self.x.detach()
-        ops.fab_proj_linf(x, self.x0, w, self.df, self.path, self.scal)
-        ops.fab_step_(x, self.x0, w, self.scal)
+        self.proj(x, self.x0, w, self.df, self.path, self.scal)
+        self.step_(x, self.x0, w, self.scal)
         with torch.no_grad():
             z = model(self.x)
-        ops.fab_commit_(z.detach().float().contiguous(), self.y, x, self.x0, self.adv, self.res, self.pred, self.flags, self.counter)
+        self.commit_(z.detach().float().contiguous(), self.y, x, self.x0, self.adv, self.res, self.pred, self.flags, self.counter)
 
     def result(self, eps):
         with torch.no_grad():
@@ -688,9 +702,10 @@ class _FabRun:
             return _adv_where_fooled(robust, self.x0, self.adv), robust, self.res.clone()
 
 
-def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto"):
-    """One FAB-T run (Linf) of n_iter iterations from x0 towards the classes `targets` [B].  Returns (x_adv, robust, norm): norm [B] is the
-    smallest ||adv - x0||_inf over the adversarial iterates (+inf if there was none), robust = not (norm <= eps), and x_adv is x0 with the
+def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", norm="Linf"):
+    """One FAB-T run of n_iter iterations from x0 towards the classes `targets` [B] in the threat model `norm` ('Linf' or 'L2': the metric of
+    the projections, of alpha and of the result).  Returns (x_adv, robust, norm): norm [B] is the smallest ||adv - x0|| in that metric
+    over the adversarial iterates (+inf if there was none), robust = not (norm <= eps), and x_adv is x0 with the
     non-robust rows replaced by that closest adversarial point.  The search itself is not confined to the eps-ball: FAB looks for the
     minimum norm and eps only thresholds its result.  Deterministic - no random start, no draws of its own.  The model's mode is left as the
     caller set it.  Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of up to MAX_ITERS_PER_GRAPH iterations; both
@@ -702,22 +717,23 @@ def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto"):
         raise ValueError("FAB needs n_iter >= 1")
     if path not in ops.FAB_PATHS:
         raise ValueError("FAB projection path must be one of %s, got %r" % (sorted(ops.FAB_PATHS), path))
+    _fab_ops(norm)
     if x0.shape[0] == 0:
         return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=torch.float32, device=x0.device)
     if use_graph is None:
         use_graph = graphs_enabled()
     if not use_graph:
-        run = _FabRun(x0, y, n_iter, path)
+        run = _FabRun(x0, y, n_iter, path, norm)
         run.load(x0, y, targets)
         run.start()
         for _ in range(n_iter):
             run.iteration(model)
         return run.result(float(eps))
     chunk = _chunk(n_iter)
-    key = ("fab", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk)
+    key = ("fab", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk, norm)
 
     def build():
-        run = _FabRun(x0, y, n_iter, path)
+        run = _FabRun(x0, y, n_iter, path, norm)
         run.load(x0, y, targets)
         return _Captured(model, x0.device, chunk, run).capture(model, _times(chunk, run.iteration), start=run.start)
 

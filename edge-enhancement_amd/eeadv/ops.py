@@ -544,7 +544,7 @@ def sqatk_step_(x_best, x_new, x0, flags, margin_min, counter, sizes, seed, eps)
 # ---- FAB-T (ee_fab.hip) ----------------------------------------------------------------------------------------------
 FAB_ADV, FAB_IMPROVED = 1, 2  # bits of the flags of fab_commit_ (EE_FAB_*)
 FAB_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_FAB_PATH_*
-FAB_LAMBDA, FAB_SIGN, FAB_NORM = range(3)  # rows of the projection scalars [3, 2B]
+FAB_LAMBDA, FAB_SIGN, FAB_NORM = range(3)  # rows of the projection scalars [3, 2B] (row 0 is mu in L2)
 
 
 def fab_diff(logits, labels, targets):
@@ -559,9 +559,7 @@ def fab_diff(logits, labels, targets):
     return df, d, pred
 
 
-def fab_proj_linf(x, x0, w, df, path="auto", out=None):
-    """The scalars [3, 2B] (rows lambda, sign, ||delta||_inf) of the two projections of every sample: column b projects x[b] with c = df[b],
-    column B + b projects x0[b] with c = df[b] + <w[b], x0[b] - x[b]>.  path: 'auto', 'resident' (per-sample size <= 12288) or 'streaming'."""
+def _fab_proj(fn, name, x, x0, w, df, path, out):
     B = x.shape[0]
     px = _chk(x, torch.float32, "x")
     p0 = _chk(x0, torch.float32, "x0", x.shape)
@@ -570,28 +568,57 @@ def fab_proj_linf(x, x0, w, df, path="auto", out=None):
     out = torch.empty((3, 2 * B), dtype=torch.float32, device=x.device) if out is None else out
     po = _chk(out, torch.float32, "out", (3, 2 * B))
     if B:
-        N.check(N.lib.ee_fab_proj_linf_f32(px, p0, pw, pd, B, x.numel() // B, FAB_PATHS[path], po, _stream()), "ee_fab_proj_linf_f32")
+        N.check(fn(px, p0, pw, pd, B, x.numel() // B, FAB_PATHS[path], po, _stream()), name)
     return out
+
+
+def fab_proj_linf(x, x0, w, df, path="auto", out=None):
+    """The scalars [3, 2B] (rows lambda, sign, ||delta||_inf) of the two projections of every sample: column b projects x[b] with c = df[b],
+    column B + b projects x0[b] with c = df[b] + <w[b], x0[b] - x[b]>.  path: 'auto', 'resident' (per-sample size <= 12288) or 'streaming'."""
+    return _fab_proj(N.lib.ee_fab_proj_linf_f32, "ee_fab_proj_linf_f32", x, x0, w, df, path, out)
+
+
+def fab_proj_l2(x, x0, w, df, path="auto", out=None):
+    """fab_proj_linf for the least-L2 projections: rows mu, sign, ||delta||_2 (delta_i = -sign(s w_i) min(mu |w_i|, r_i))."""
+    return _fab_proj(N.lib.ee_fab_proj_l2_f32, "ee_fab_proj_l2_f32", x, x0, w, df, path, out)
+
+
+def _fab_step(fn, name, x, x0, w, scal):
+    B = x.shape[0]
+    px = _chk(x, torch.float32, "x")
+    N.check(fn(px, _chk(x0, torch.float32, "x0", x.shape), _chk(w, torch.float32, "w", x.shape),
+               _chk(scal, torch.float32, "scal", (3, 2 * B)), B, x.numel() // B if B else 0, _stream()), name)
+    return x
 
 
 def fab_step_(x, x0, w, scal):
     """The FAB step in place on x [B, ...] from the projection scalars [3, 2B]."""
-    B = x.shape[0]
-    px = _chk(x, torch.float32, "x")
-    N.check(N.lib.ee_fab_step_f32(px, _chk(x0, torch.float32, "x0", x.shape), _chk(w, torch.float32, "w", x.shape),
-                                  _chk(scal, torch.float32, "scal", (3, 2 * B)), B, x.numel() // B if B else 0, _stream()), "ee_fab_step_f32")
-    return x
+    return _fab_step(N.lib.ee_fab_step_f32, "ee_fab_step_f32", x, x0, w, scal)
+
+
+def fab_step_l2_(x, x0, w, scal):
+    """The FAB step in place on x [B, ...] from the scalars [3, 2B] of fab_proj_l2."""
+    return _fab_step(N.lib.ee_fab_step_l2_f32, "ee_fab_step_l2_f32", x, x0, w, scal)
+
+
+def _fab_commit(fn, name, logits, labels, x, x0, adv, res, pred, flags, counter):
+    B, K = logits.shape
+    N.check(fn(_chk(logits, torch.float32, "logits", (x.shape[0], K)), _chk(labels, torch.int64, "labels", (B,)), B, K,
+               _chk(x, torch.float32, "x"), _chk(x0, torch.float32, "x0", x.shape), _chk(adv, torch.float32, "adv", x.shape),
+               _chk(res, torch.float32, "res", (B,)), _chk(pred, torch.int32, "pred", (B,)),
+               _chk(flags, torch.int32, "flags", (B,)), _chk(counter, torch.int32, "counter", (1,)),
+               x.numel() // B if B else 0, _stream()), name)
+    return flags
 
 
 def fab_commit_(logits, labels, x, x0, adv, res, pred, flags, counter):
     """The check after the second forward, in place on x, adv [B, ...], res [B]; pred, flags [B] int32 are written; counter += 1."""
-    B, K = logits.shape
-    N.check(N.lib.ee_fab_commit_f32(_chk(logits, torch.float32, "logits", (x.shape[0], K)), _chk(labels, torch.int64, "labels", (B,)), B, K,
-                                    _chk(x, torch.float32, "x"), _chk(x0, torch.float32, "x0", x.shape), _chk(adv, torch.float32, "adv", x.shape),
-                                    _chk(res, torch.float32, "res", (B,)), _chk(pred, torch.int32, "pred", (B,)),
-                                    _chk(flags, torch.int32, "flags", (B,)), _chk(counter, torch.int32, "counter", (1,)),
-                                    x.numel() // B if B else 0, _stream()), "ee_fab_commit_f32")
-    return flags
+    return _fab_commit(N.lib.ee_fab_commit_f32, "ee_fab_commit_f32", logits, labels, x, x0, adv, res, pred, flags, counter)
+
+
+def fab_commit_l2_(logits, labels, x, x0, adv, res, pred, flags, counter):
+    """fab_commit_ with res [B] holding L2 distances."""
+    return _fab_commit(N.lib.ee_fab_commit_l2_f32, "ee_fab_commit_l2_f32", logits, labels, x, x0, adv, res, pred, flags, counter)
 
 
 # ---- sample pools of the attack cascade (ee_cascade.hip) -------------------------------------------------------------

@@ -434,8 +434,9 @@ def Square(model, args, inputs, targets, n_queries=5000, seed=None):
 # ---------------------------------------------------------------------------------------------------------
 # FAB-T (Croce & Hein 2020, Linf, targeted): the minimum-norm member of AutoAttack's `standard` version - it walks along linearised
 # decision boundaries instead of ascending a loss.  Built from the published algorithm with the constants `standard`
-# runs it with (eta = 1.05, beta = 0.9, alpha_max = 0.1, 9 target classes, one run from the clean point: deterministic).  Untargeted FAB,
-# L2 / L1, restarts with the random start, the final line search and EOT for FAB are NOT here.
+# runs it with (eta = 1.05, beta = 0.9, alpha_max = 0.1, 9 target classes, one run from the clean point: deterministic).  norm="L2" is
+# the same iteration in the other metric.  Untargeted FAB, L1, restarts with the random start, the final line
+# search and EOT for FAB are NOT here.
 # ---------------------------------------------------------------------------------------------------------
 _FAB_ETA, _FAB_BETA, _FAB_ALPHA_MAX = 1.05, 0.9, 0.1
 
@@ -471,9 +472,55 @@ def _fab_delta(p, w, lam, s):
     return -torch.sign(v) * torch.minimum(lam.view(-1, 1), r)
 
 
-def _fab_host_iteration(model, x, x0, y, t, adv, res):
+def _fab_projection_l2(p, w, c):
+    """_fab_projection for the least-||.||_2 delta: (mu, s, ||delta||_2) per row, delta_i = -sign(s w_i) min(mu |w_i|, r_i), mu the smallest
+    value with g(mu) = sum_i |w_i| min(mu |w_i|, r_i) = |c|.  The breakpoints are t_i = r_i / |w_i| (0 where w_i == 0: such a coordinate adds
+    zeros on either side); sort by them, cumulative sums (sum_{t_j > t_k} w_j^2 taken from the top, so nothing cancels) and the closed form
+    on the segment that holds mu.  c = 0: mu = 0; c' >= g(inf): mu = inf."""
+    s = torch.where(c >= 0, torch.ones_like(c), -torch.ones_like(c))
+    v = s.view(-1, 1) * w
+    a = v.abs()
+    r = torch.where(v > 0, p, torch.where(v < 0, 1 - p, torch.zeros_like(p))).clamp_min(0)
+    cp = c.abs()
+    moving = a != 0
+    t = torch.where(moving, r / torch.where(moving, a, torch.ones_like(a)), torch.zeros_like(r))
+    ts, order = torch.sort(t, dim=1)
+    a_s, r_s = a.gather(1, order), r.gather(1, order)
+    aa = a_s * a_s
+    below = torch.cumsum(a_s * r_s, dim=1)  # sum_{j <= k} a_j r_j
+    top = torch.flip(torch.cumsum(torch.flip(aa, [1]), dim=1), [1])  # sum_{j >= k} a_j^2
+    above = torch.cat([top[:, 1:], torch.zeros_like(top[:, :1])], dim=1)  # sum_{j > k} a_j^2
+    g = below + torch.where(above > 0, ts * above, torch.zeros_like(above))  # g at breakpoint k (t_k = inf meets no 0)
+    zero = torch.zeros_like(cp).view(-1, 1)
+    k = (g < cp.view(-1, 1)).sum(dim=1, keepdim=True)  # breakpoints strictly below the solution
+    S = torch.cat([zero, below], dim=1).gather(1, k).squeeze(1)
+    A = torch.cat([top[:, :1], above], dim=1).gather(1, k).squeeze(1)
+    mu = (cp - S) / A
+    mu = torch.where(cp >= below[:, -1], torch.full_like(mu, _INF), mu)
+    mu = torch.where(cp == 0, torch.zeros_like(mu), mu)
+    return mu, s, _l2_norms(_fab_delta_l2(p, w, mu, s))
+
+
+def _fab_delta_l2(p, w, mu, s):
+    v = s.view(-1, 1) * w
+    a = v.abs()
+    r = torch.where(v > 0, p, torch.where(v < 0, 1 - p, torch.zeros_like(p))).clamp_min(0)
+    m = torch.where(a != 0, torch.minimum(mu.view(-1, 1) * a, r), torch.zeros_like(r))  # mu = inf never meets a zero
+    return -torch.sign(v) * m
+
+
+def _check_fab_norm(norm):
+    if norm not in engine.FAB_NORMS:
+        raise ValueError("FAB norm must be one of %s, got %r" % (list(engine.FAB_NORMS), norm))
+    return norm
+
+
+def _fab_host_iteration(model, x, x0, y, t, adv, res, norm="Linf"):
     """One FAB-T iteration in plain torch ops, in the input's dtype: (x, adv, res) -> (x, adv, res, info).  `info` holds every
-    intermediate quantity (df, w, the projection scalars, alpha, the stepped point, pred, the flags)."""
+    intermediate quantity (df, w, the projection scalars, alpha, the stepped point, pred, the flags).  norm: 'Linf' or 'L2' - the metric of
+    the two projections (lam1 / lam2 then hold mu), of alpha and of nrm / res."""
+    in_l2 = _check_fab_norm(norm) == "L2"
+    project, delta = (_fab_projection_l2, _fab_delta_l2) if in_l2 else (_fab_projection, _fab_delta)
     B = x0.shape[0]
     rows = torch.arange(B, device=x0.device)
     xc = x.detach().clone().requires_grad_()
@@ -488,11 +535,11 @@ def _fab_host_iteration(model, x, x0, y, t, adv, res):
     safe_w = torch.where(on.view(-1, 1), w, torch.ones_like(w))  # rows without a hyperplane are computed on stand-ins and masked below
     c1 = torch.where(on, df, torch.ones_like(df))
     c2 = torch.where(on, df + (safe_w * (x0f - xf)).sum(dim=1), torch.ones_like(df))  # a sum of differences: <w, x0> - <w, x> would cancel
-    l1, s1, n1 = _fab_projection(xf, safe_w, c1)
-    l2, s2, n2 = _fab_projection(x0f, safe_w, c2)
+    l1, s1, n1 = project(xf, safe_w, c1)
+    l2, s2, n2 = project(x0f, safe_w, c2)
     zero = torch.zeros_like(df)
     l1, s1, n1, l2, s2, n2 = (torch.where(on, q, zero) for q in (l1, s1, n1, l2, s2, n2))
-    d1, d2 = _fab_delta(xf, safe_w, l1, s1), _fab_delta(x0f, safe_w, l2, s2)
+    d1, d2 = delta(xf, safe_w, l1, s1), delta(x0f, safe_w, l2, s2)
     a1, a2 = n1.clamp_min(1e-8), n2.clamp_min(1e-8)
     alpha = torch.minimum(a1 / (a1 + a2), torch.full_like(a1, _FAB_ALPHA_MAX))
     al = alpha.view(-1, 1)
@@ -502,7 +549,7 @@ def _fab_host_iteration(model, x, x0, y, t, adv, res):
         z2 = model(x_step.view(x0.shape))
     pred = torch.sort(z2, dim=1, descending=True, stable=True)[1][:, 0]
     is_adv = (pred != y) & ~torch.isnan(z2).any(dim=1)
-    nrm = (x_step - x0f).abs().max(dim=1)[0]
+    nrm = _l2_norms(x_step - x0f) if in_l2 else (x_step - x0f).abs().max(dim=1)[0]
     improved = is_adv & (nrm < res)
     adv = torch.where(improved.view(-1, 1), x_step, adv.reshape(B, -1)).view(x0.shape)
     res = torch.where(improved, nrm, res)
@@ -512,21 +559,22 @@ def _fab_host_iteration(model, x, x0, y, t, adv, res):
     return x_new, adv, res, info
 
 
-def _fab_host(model, x0, y, t, n_iter, trace=None):
+def _fab_host(model, x0, y, t, n_iter, trace=None, norm="Linf"):
     """Plumbing path for CPU tensors (opt-in), the counterpart of _host_loop: the iteration of engine.fab_loop in plain torch ops, in the
     input's dtype.  Returns (adv, res).  `trace`, a list, receives one dict of clones per iteration."""
+    _check_fab_norm(norm)
     x, adv = x0.clone(), x0.clone()
     res = torch.full((x0.shape[0],), _INF, dtype=x0.dtype, device=x0.device)
     for _ in range(int(n_iter)):
-        x, adv, res, info = _fab_host_iteration(model, x, x0, y, t, adv, res)
+        x, adv, res, info = _fab_host_iteration(model, x, x0, y, t, adv, res, norm)
         if trace is not None:
             info.update(x=x, adv=adv, res=res)
             trace.append({k: v.clone() for k, v in info.items()})
     return adv, res
 
 
-def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, order=None):
-    """Targeted FAB (Linf): one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most nclass - 1 of
+def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, order=None, norm="Linf"):
+    """Targeted FAB (norm: 'Linf', or 'L2' - every ||.||_inf below is then ||.||_2 and args.epsilon the L2 radius): one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most nclass - 1 of
     them, taken as APGD_T takes them), each on the whole batch from the clean point.  Returns (x_adv, robust, norm): norm [B] is the smallest
     ||adv - x0||_inf over all runs (+inf if no run found an adversarial point, 0 for a sample the clean forward already misclassifies),
     robust = not (norm <= args.epsilon), and x_adv is the inputs with every non-robust sample replaced by the point that attains its norm
@@ -536,6 +584,7 @@ def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, 
     [B, n_t + 1]: the class order of the clean logits if the caller has it already - the clean forward is then skipped."""
     x0 = inputs.detach()
     eps = float(args.epsilon)
+    kw = {} if _check_fab_norm(norm) == "Linf" else {"norm": norm}  # the Linf call is the call it always was
     n_t = min(int(n_target_classes), int(nclass) - 1)
     on_dev = runtime.require_device(x0, "FAB_T")
     order = _class_order(model, x0, n_t, "FAB_T", order)
@@ -546,9 +595,9 @@ def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, 
     for j in range(1, n_t + 1):
         t = order[:, j].contiguous()
         if on_dev:
-            xa, _, nj = engine.fab_loop(model, x0, targets, t, n_iter, eps)
+            xa, _, nj = engine.fab_loop(model, x0, targets, t, n_iter, eps, **kw)
         else:
-            xa, nj = _fab_host(model, x0, targets, t, n_iter)
+            xa, nj = _fab_host(model, x0, targets, t, n_iter, **kw)
         closer = (nj < norm) & (nj <= eps)
         x_adv = torch.where(closer.view(shape), xa, x_adv)
         norm = torch.minimum(norm, nj)

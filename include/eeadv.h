@@ -385,6 +385,32 @@ int ee_fab_step_f32(float *x, const float *x0, const float *w, const float *scal
 int ee_fab_commit_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res, int *pred,
                       int *flags, int *counter, int64_t per_sample, void *stream);
 
+/* ---- FAB-T in the L2 threat model.  The iteration, the state, the flags, the paths and ee_fab_diff_f32 are the
+ * ones above; three launches take the place of their Linf siblings and record under the same EE_K_FAB_* families.  res then holds
+ * ||adv - x0||_2 and row 2 of scal holds ||delta||_2. */
+
+/* The scalars of the two box-constrained L2 projections of every sample, problems and degenerate-sample rules as in
+ * ee_fab_proj_linf_f32: delta = the vector of least ||.||_2 with <w, p + delta> = <w, p> - c and 0 <= p + delta <= 1, which is
+ * delta_i = -sign(v_i) min(mu a_i, r_i) (v = s w, a_i = |v_i|, rooms r_i as above; v_i == 0 exactly: delta_i = 0) for the smallest mu >= 0
+ * with sum_i a_i min(mu a_i, r_i) = |c|.  out[0][q] = mu (+inf: infeasible, every moving coordinate goes to its bound), out[1][q] = s,
+ * out[2][q] = ||delta||_2 = (float) sqrt(sum_i min(mu a_i, r_i)^2) with mu before its rounding to float.  The breakpoint of a
+ * coordinate is the f32 quotient r_i / a_i (a denormal a_i: +inf, it never saturates); mu is the exact solve of the segment that the
+ * 31-step search over the bit patterns finds.  All sums in double in one fixed order: both paths and both access widths return the
+ * same bits.  One workgroup of 512 threads per problem; resident up to 12288 elements, streaming for any size. */
+int ee_fab_proj_l2_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path, float *out,
+                       void *stream);
+
+/* ee_fab_step_f32 with the deltas of ee_fab_proj_l2_f32: delta_k_i = -sign(s_k w_i) min(mu_k |w_i|, r_i) - the product is one f32
+ * multiplication, min propagates NaN - and 0 where w_i == 0 (mu = +inf never meets a zero); a_k, alpha, the convex combination, the clamp
+ * and the s1 = 0 rule are unchanged. */
+int ee_fab_step_l2_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream);
+
+/* ee_fab_commit_f32 with n = ||x - x0||_2: the squares of the f32 differences summed in double - thread t takes the groups of four
+ * elements t, t + 512, ..., then an xor-shuffle tree, then eight partial sums in index order - and n = (float) sqrt(sum).  Vector and
+ * element-wise accesses return the same bits.  Everything else is ee_fab_commit_f32's. */
+int ee_fab_commit_l2_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res,
+                         int *pred, int *flags, int *counter, int64_t per_sample, void *stream);
+
 /* CannyFilter_BPDA (utils/core.py:386-505; AWP configs): no alpha mask, NMS by multiplication, thresholds through
  * To_compare (core.py:329-358), hysteresis through To_eq (core.py:361-382).  thresholds given, hysteresis=True.
  *   forward: edge, thin (the thinned magnitude), t2 (the {0, .5, 1} threshold map) [B,1,H,W]; thin / t2 feed the backward.
@@ -902,9 +928,9 @@ int ee_cascade_resolve_f32(const uint8_t *robust, const int64_t *id, const float
 #define EE_K_SQATK_MARGIN 24 /* ee_sqatk_margin_f32 */
 #define EE_K_SQATK_STEP 25   /* ee_sqatk_step_f32 */
 #define EE_K_FAB_DIFF 26     /* ee_fab_diff_f32 */
-#define EE_K_FAB_PROJ 27     /* ee_fab_proj_linf_f32 */
-#define EE_K_FAB_STEP 28     /* ee_fab_step_f32 */
-#define EE_K_FAB_COMMIT 29   /* ee_fab_commit_f32 */
+#define EE_K_FAB_PROJ 27     /* ee_fab_proj_linf_f32, ee_fab_proj_l2_f32 */
+#define EE_K_FAB_STEP 28     /* ee_fab_step_f32, ee_fab_step_l2_f32 */
+#define EE_K_FAB_COMMIT 29   /* ee_fab_commit_f32, ee_fab_commit_l2_f32 */
 #define EE_K_COUNT 30
 int ee_prof_enable(int on);
 /* records one empty start/stop bracket on `stream` (family EE_K_EMPTY): callers subtract its mean from the other

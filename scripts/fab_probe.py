@@ -9,7 +9,10 @@ forward: a captured graph of 16 forwards under no_grad, per forward.  The projec
 on a gradient and an iterate taken from a real run): CUDA events around 50 launches, per launch, on both paths.  The networks are
 untrained: labels are their own clean predictions.
 
-    python scripts/fab_probe.py [reps]      -> a few text lines, then one JSON line per model
+--norm L2 times the L2 iteration (engine.fab_loop(norm="L2"), eps = 0.5) and the L2 projection launch beside the Linf ones, in the same
+run, the three attacks alternating.
+
+    python scripts/fab_probe.py [reps] [--norm Linf|L2]      -> a few text lines, then one JSON line per model
 """
 import json
 import os
@@ -28,7 +31,16 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("fab_probe: needs a ROCm device (a time taken on the host says nothing)")
-    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
+    argv = sys.argv[1:]
+    norm = "Linf"
+    if "--norm" in argv:
+        k = argv.index("--norm")
+        if k + 1 >= len(argv) or argv[k + 1] not in engine.FAB_NORMS:
+            raise SystemExit("fab_probe: --norm takes one of %s" % (list(engine.FAB_NORMS),))
+        norm = argv[k + 1]
+        del argv[k:k + 2]
+    l2 = norm == "L2"
+    reps = int(argv[0]) if argv else 7
     dev = torch.device("cuda", 0)
     eps = 16 / 255
 
@@ -60,6 +72,8 @@ def main():
             order = ops.topk(m(x).float().contiguous(), None, 2)[0]
         y, t = order[:, 0].contiguous(), order[:, 1].contiguous()
         runs = {"pgd": lambda k: A.PGD(m, Args, x, y, k, 2 / 255), "fab_t": lambda k: engine.fab_loop(m, x, y, t, k, eps)}
+        if l2:
+            runs["fab_t_l2"] = lambda k: engine.fab_loop(m, x, y, t, k, 0.5, norm="L2")
         for fn in runs.values():  # captures and warm-up of both lengths
             for k in (100, 20, 100, 20):
                 fn(k)
@@ -103,9 +117,30 @@ def main():
             out["proj_%s_us" % path] = round(1e3 * median([timed(launch) for _ in range(reps)]) / 50, 2)
         res = engine.fab_loop(m, x, y, t, 100, eps)
         out["fab_t_non_robust_after_one_target"] = round(1.0 - float(res[1].float().mean()), 3)
+        if l2:
+            out["fab_l2_over_linf"] = round(out["fab_t_l2_iter_ms"] / out["fab_t_iter_ms"], 4)
+            out["fab_l2_minus_linf_us_per_iter"] = round(1e3 * (out["fab_t_l2_iter_ms"] - out["fab_t_iter_ms"]), 1)
+            run2 = engine._FabRun(x, y, 3, norm="L2")  # the L2 projection launch on the state of an L2 run's third iteration
+            run2.load(x, y, t)
+            run2.start()
+            for _ in range(2):
+                run2.iteration(m)
+            w2 = engine.input_gradient(m, run2.x, run2.spec).contiguous()
+            x2 = run2.x.detach()
+            for path in ("resident", "streaming"):
+                launch = lambda: [ops.fab_proj_l2(x2, run2.x0, w2, run2.df, path, run2.scal) for _ in range(50)]
+                launch()
+                torch.cuda.synchronize()
+                out["proj_l2_%s_us" % path] = round(1e3 * median([timed(launch) for _ in range(reps)]) / 50, 2)
+            res = engine.fab_loop(m, x, y, t, 100, 0.5, norm="L2")
+            out["fab_t_l2_non_robust_after_one_target"] = round(1.0 - float(res[1].float().mean()), 3)
         print("%s: PGD %.4f ms/iter + eval forward %.4f ms = %.4f ms; FAB-T %.4f ms/iter (x%.3f, +%.1f us); projection launch %.1f us resident, "
               "%.1f us streaming" % (name, out["pgd_iter_ms"], out["eval_fwd_ms"], shared, out["fab_t_iter_ms"], out["fab_over_shared"],
                                      out["fab_extra_us_per_iter"], out["proj_resident_us"], out["proj_streaming_us"]), flush=True)
+        if l2:
+            print("%s: L2 FAB-T %.4f ms/iter (x%.3f of the Linf iteration, %+.1f us); L2 projection launch %.1f us resident, %.1f us streaming"
+                  % (name, out["fab_t_l2_iter_ms"], out["fab_l2_over_linf"], out["fab_l2_minus_linf_us_per_iter"], out["proj_l2_resident_us"],
+                     out["proj_l2_streaming_us"]), flush=True)
         print(json.dumps(out), flush=True)
 
 
