@@ -159,8 +159,10 @@ __global__ __launch_bounds__(HEAD_NT) void ce_pool_linear_bwd_kernel(const float
     }
     __syncthreads();
     const float mx = stats[0], lse = stats[1];
-    const int y = static_cast<int>(labels[b]);
-    for (int k = threadIdx.x; k < K; k += HEAD_NT) dl[k] = ce_grad(z[k], mx, lse, k == y, gscale);
+    const int64_t y64 = labels[b];
+    const bool bad = y64 < 0 || y64 >= K;  // a label outside the row: ee_ce_f32's zero gradient, through the same way back
+    const int y = static_cast<int>(y64);
+    for (int k = threadIdx.x; k < K; k += HEAD_NT) dl[k] = bad ? 0.0f : ce_grad(z[k], mx, lse, k == y, gscale);
     __syncthreads();
     dlogits_to_dfeat(dl, w, dfeat, b, C, HW, K);
 }

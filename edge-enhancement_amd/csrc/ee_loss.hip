@@ -20,7 +20,14 @@ __global__ __launch_bounds__(kBlock) void ce_kernel(const float *__restrict__ lo
     const int row = blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (row >= B) return;
     const float *z = logits + static_cast<size_t>(row) * K;
-    const int y = static_cast<int>(labels[row]);
+    const int64_t y64 = labels[row];
+    if (y64 < 0 || y64 >= K) {  // a label outside the row is never dereferenced: NaN row loss, no gradient (as ee_apgd.hip's loss_kernel)
+        if (dlogits)
+            for (int k = lane; k < K; k += kWave) dlogits[static_cast<size_t>(row) * K + k] = 0.0f;
+        if (row_loss && lane == 0) row_loss[row] = static_cast<double>(NAN);
+        return;
+    }
+    const int y = static_cast<int>(y64);
     float mx, lse;
     row_stats(z, K, lane, mx, lse);
     const float w_off = smoothing / (static_cast<float>(K) - 1.0f), w_on = 1.0f - smoothing;
@@ -146,7 +153,8 @@ __global__ __launch_bounds__(kBlock) void topk_kernel(const float *__restrict__ 
 #pragma unroll
     for (int j = 0; j < kMaxTopK; ++j) chosen[j] = -1;
     int hit = -1;
-    const int y = labels ? static_cast<int>(labels[row]) : -1;
+    const int64_t y64 = labels ? labels[row] : -1;
+    const int y = (y64 < 0 || y64 >= K) ? -1 : static_cast<int>(y64);  // a label outside the row is no class: never "correct"
 #pragma unroll
     for (int j = 0; j < kMaxTopK; ++j) {
         if (j < k) {
@@ -214,9 +222,11 @@ __global__ __launch_bounds__(kBlock) void fc_ce_grad_kernel(const float *__restr
     if (wave == 0) {
         float mx, lse;
         row_stats(lg, K, lane, mx, lse);
-        const int y = static_cast<int>(labels[row]);
+        const int64_t y64 = labels[row];
+        const bool bad = y64 < 0 || y64 >= K;  // a label outside the row: no gradient (ee_ce_f32's rule), the logits are still written
+        const int y = static_cast<int>(y64);
         for (int k = lane; k < K; k += kWave) {
-            dl[k] = ce_grad(lg[k], mx, lse, k == y, gscale);
+            dl[k] = bad ? 0.0f : ce_grad(lg[k], mx, lse, k == y, gscale);
             if (logits_out) logits_out[static_cast<size_t>(row) * K + k] = lg[k];
         }
     }
@@ -271,8 +281,10 @@ __global__ __launch_bounds__(kBlock) void fc_ce_grad_small_kernel(const float *_
     if (wave == 0) {
         float mx, lse;
         row_stats(lg, K, lane, mx, lse);
-        const int y = static_cast<int>(labels[row]);
-        if (lane < KM) dl[lane] = lane < K ? ce_grad(lg[lane], mx, lse, lane == y, gscale) : 0.0f;
+        const int64_t y64 = labels[row];
+        const bool bad = y64 < 0 || y64 >= K;  // as fc_ce_grad_kernel
+        const int y = static_cast<int>(y64);
+        if (lane < KM) dl[lane] = (lane < K && !bad) ? ce_grad(lg[lane], mx, lse, lane == y, gscale) : 0.0f;
         if (logits_out && lane < K) logits_out[static_cast<size_t>(row) * K + lane] = lg[lane];
     }
     __syncthreads();

@@ -175,12 +175,14 @@ int ee_pgd_step_bcast_f32(float *x, const float *g_lp, const float *g_edge, cons
 
 /* F.cross_entropy incl. label smoothing (attacks.py:23 sum, :255 mean, :89-99 LabelSmoothLoss):
  *     row_loss_b = -sum_k w_bk log_softmax(z_b)_k,  w = smoothing/(K-1) off target, 1-smoothing on it
- *     dz = gscale * (softmax(z) - w)           gscale = 1 ('sum') or 1/B ('mean')            */
+ *     dz = gscale * (softmax(z) - w)           gscale = 1 ('sum') or 1/B ('mean')
+ * A label outside [0, K) gives a NaN row loss and a zero gradient. */
 int ee_ce_f32(const float *logits, const int64_t *labels, int B, int K, float smoothing, float gscale,
               double *row_loss, float *dlogits, void *stream);
 /* The last two layers of the MNIST classifier and the loss behind them, gradient only (MNIST/models_mnist/Net2.py:27-28 + attacks.py:23):
  * d CrossEntropyLoss(fc2(relu(z1)), labels) / d z1 in one launch.  z1 [B,Hd] = fc1's output, w2 [K,Hd], b2 [K] or NULL, labels [B] ->
- * dz1 [B,Hd] (and the logits [B,K] if logits_out != NULL); gscale = 1 ("sum") or 1/B ("mean").  K <= 64, Hd <= 8192. */
+ * dz1 [B,Hd] (and the logits [B,K] if logits_out != NULL); gscale = 1 ("sum") or 1/B ("mean").  K <= 64, Hd <= 8192.
+ * A label outside [0, K) gives a NaN row loss and a zero gradient: that image's dz1 is zero (its logits are still written). */
 int ee_fc_ce_grad_f32(const float *z1, const float *w2, const float *b2, const int64_t *labels, float *dz1, float *logits_out, int B, int Hd,
                       int K, float gscale, void *stream);
 
@@ -205,7 +207,8 @@ int ee_reduce_rows_f64(const double *rows, int64_t n, double scale, double *out,
 
 /* utils/helper.py:39-55 accuracy / attacks.py:131-132 predict_from_logits:
  * idx[B,k] = sorted top-k class indices (ties: lower index first), correct[k] (int64, zeroed by the
- * call) = number of rows whose label is among the first j+1 indices.  labels nullable. */
+ * call) = number of rows whose label is among the first j+1 indices.  labels nullable; a label outside [0, K) is among no
+ * row's indices. */
 int ee_topk_i64(const float *logits, const int64_t *labels, int B, int K, int k, int64_t *idx, int64_t *correct,
                 void *stream);
 
@@ -771,7 +774,8 @@ int ee_pool_linear_fwd_f32(const float *feat, const float *weight, const float *
                            int C, int HW, int K, void *stream);
 int ee_pool_linear_bwd_f32(const float *dlogits, const float *weight, float *dfeat, int B, int C, int HW, int K, void *stream);
 /* ... with the cross-entropy gradient formed inside the same launch (the attack loop: attacks.py:23 sum, :255 mean): logits [B,K] as
- * ee_pool_linear_fwd_f32 wrote them, labels [B], gscale = 1 or 1 / B -> dfeat [B,C,HW]; the bits of ee_ce_f32 + ee_pool_linear_bwd_f32. */
+ * ee_pool_linear_fwd_f32 wrote them, labels [B], gscale = 1 or 1 / B -> dfeat [B,C,HW]; the bits of ee_ce_f32 + ee_pool_linear_bwd_f32.
+ * A label outside [0, K) gives a NaN row loss and a zero gradient: that image's dfeat is zero. */
 int ee_ce_pool_linear_bwd_f32(const float *logits, const int64_t *labels, float gscale, const float *weight, float *dfeat, int B, int C, int HW,
                               int K, void *stream);
 
