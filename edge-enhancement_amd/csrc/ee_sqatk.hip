@@ -10,13 +10,11 @@
 #include <math.h>
 
 #include "ee_rows.hpp"
+#include "ee_sqatk.hpp"
 
 namespace {
 
 using namespace ee;
-
-constexpr uint32_t kStreamWindow = 11u;  // Philox stream ids; 0 (the default) and 7 (ee_net2.hip) are taken
-constexpr uint32_t kStreamStripe = 12u;
 
 // ---- start ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void init_kernel(float *__restrict__ x_best, float *__restrict__ x_new, const float *__restrict__ x0,
@@ -88,9 +86,9 @@ __device__ __forceinline__ Sample sample_of(int64_t b, const int *__restrict__ f
     r.vh = r.vw = 0;
     r.bits = 0u;
     if (r.propose) {
-        const uint4 d = ph((static_cast<uint64_t>(static_cast<uint32_t>(it)) << 32) | static_cast<uint32_t>(b), kStreamWindow);
-        r.vh = static_cast<int>(__umulhi(d.x, static_cast<uint32_t>(H - s + 1)));
-        r.vw = static_cast<int>(__umulhi(d.y, static_cast<uint32_t>(W - s + 1)));
+        const WindowDraw d = draw_window(ph, it, b, s, H, W, kStreamWindow);
+        r.vh = d.vh;
+        r.vw = d.vw;
         r.bits = d.z;
     }
     return r;
@@ -182,19 +180,11 @@ __global__ __launch_bounds__(kBlock) void step_kernel(float *x_best, float *x_ne
     }
 }
 
-// B, C, H, W of an image batch whose element count and per-sample size fit the kernels' arithmetic
-int check_shape(int B, int C, int H, int W) {
-    if (B < 0 || C < 1 || H < 1 || W < 1) return EE_ERR_SHAPE;
-    if (static_cast<int64_t>(C) * H * W > INT32_MAX) return EE_ERR_SHAPE;
-    if (C > 32) return EE_ERR_UNSUPPORTED;  // one sign bit per channel in a 32-bit draw
-    return EE_OK;
-}
-
 }  // namespace
 
 EE_API int ee_sqatk_init_f32(float *x_best, float *x_new, const float *x0, const int64_t *seed, int B, int C, int H, int W, float eps,
                              void *stream) {
-    const int rc = check_shape(B, C, H, W);
+    const int rc = sqatk_check_shape(B, C, H, W);
     if (rc != EE_OK) return rc;
     if (B == 0) return EE_OK;
     if (!x_best || !x_new || !x0 || !seed) return EE_ERR_NULL;
@@ -221,7 +211,7 @@ EE_API int ee_sqatk_margin_f32(const float *logits, const int64_t *labels, int B
 
 EE_API int ee_sqatk_step_f32(float *x_best, float *x_new, const float *x0, const int *flags, const float *margin_min, const int *counter,
                              const int *sizes, int n_sizes, const int64_t *seed, int B, int C, int H, int W, float eps, void *stream) {
-    const int rc = check_shape(B, C, H, W);
+    const int rc = sqatk_check_shape(B, C, H, W);
     if (rc != EE_OK) return rc;
     if (n_sizes < 0) return EE_ERR_SHAPE;
     if (B == 0) return EE_OK;

@@ -1,0 +1,496 @@
+// ee_sqatk_l2.hip - the Square attack in the L2 threat model (Andriushchenko et al. 2020, Alg. 3): the two launches that
+// stand in the place of ee_sqatk_init_f32 and ee_sqatk_step_f32 in an L2 run.  The margin launch, the counter, the flags and the query
+// count do not know the norm (ee_sqatk.hip).
+//
+// Start, per sample, with eta0 = the [s0, s0] table, tiny = 1e-12f - every operation rounded once in f32:
+//     d   = +-eta0 (or its transpose) on each of the nh x nw tiles, sign per (tile, channel), transpose per tile; 0 outside the tiling
+//     n0  = ||d||_2        q = eps / (n0 + tiny)        x_best = x_new = clamp(x0 + d * q, 0, 1)
+// Proposal i, per sample, with s = sizes[i], eta = the table at eta_off[i], W1 / W2 the two s x s windows, delta = x_best - x0:
+//     n_img = ||delta||_2        n_un = ||delta on W1 u W2||_2        n_w[c] = ||delta[c, W1]||_2
+//     new[c]   = +-eta + delta[c, W1] / (tiny + n_w[c])                            n_new[c] = ||new[c]||_2
+//     scale    = sqrt(max(eps * eps - n_img * n_img, 0) / C + n_un * n_un)
+//     delta[:, W2] = 0;   delta[c, W1] = new[c] / (tiny + n_new[c]) * scale          n_d = ||delta||_2
+//     x_new    = clamp(x0 + delta / (tiny + n_d) * eps, 0, 1)
+//
+// One workgroup of 512 threads per sample, as in ee_apgd_l2.hip: the norms depend on each other in three rounds ({n_img, n_un, n_w},
+// {n_new}, {n_d}) and never cross a workgroup.  A norm is (float) sqrt(S), S the sum of the squares in double (the square of a float is
+// exact there) in one fixed order: thread t takes the groups of four elements t, t + 512, ... in turn, wavefronts are reduced by
+// xor-shuffles, the eight partial sums are added in index order.  An element outside a window adds an exact zero to that window's sum (or
+// is skipped, which is the same number), so the order depends on the shape only and the resident path (x0, the difference and what is
+// known of each element stay in registers across the rounds, C*H*W <= 12288), the streaming path (every pass re-reads x_best and x0 and
+// recomputes from the scalars already known; no scratch tensor) and the vector / element-wise accesses all return the same bits.
+// flags[b] and margin_min[b] are read by sample b's workgroup only and are uniform in it.  x_best is written in the first pass only
+// (the commit), x_new in the last, each element by the thread that read it.
+#include <math.h>
+
+#include "ee_rows.hpp"
+#include "ee_sqatk.hpp"
+
+namespace {
+
+using namespace ee;
+
+constexpr int kL2Block = 512;  // 8 wavefronts per sample
+constexpr int kL2Waves = kL2Block / kWave;
+constexpr int kL2Vecs = 6;                           // groups of four elements per thread the resident path keeps
+constexpr int kL2Elems = kL2Vecs * 4;
+constexpr int kL2Resident = kL2Block * kL2Elems;     // 12288 = 3*64*64
+constexpr int kMaxC = 32;                            // one sign bit per channel
+constexpr float kTiny = 1e-12f;
+
+// bits of Info::f
+constexpr uint32_t kIn1 = 1u, kIn2 = 2u;
+
+struct Geo {
+    int C, H, W, HW;
+    int64_t D;
+};
+
+// what a launch knows of one element: f = kIn1 | kIn2 | channel << 8, idx = its place in the eta table (window 1 / a tile only)
+struct Info {
+    uint32_t f;
+    int idx;
+};
+
+__device__ __forceinline__ int channel_of(const Info &i) { return static_cast<int>(i.f >> 8); }
+
+// the sums of one round: put() every slot, then norms() - two barriers a round, whatever the number of slots
+struct Reducer {
+    double *part;  // [2 + kMaxC][kL2Waves]
+    __device__ __forceinline__ void put(int slot, double v) {
+        v = wave_sum(v);
+        if ((threadIdx.x & (kWave - 1)) == 0) part[slot * kL2Waves + (threadIdx.x >> 6)] = v;
+    }
+    // out[k] = (float) sqrt(the sum of slot k's partials in index order), k < n; also stored to global[row(k) * B + b]
+    template <class Row>
+    __device__ __forceinline__ void norms(int n, float *out, float *__restrict__ global, int64_t B, int64_t b, Row row) {
+        __syncthreads();
+        if (static_cast<int>(threadIdx.x) < n) {
+            const double *p = part + threadIdx.x * kL2Waves;
+            double r = p[0];
+#pragma unroll
+            for (int i = 1; i < kL2Waves; ++i) r += p[i];
+            const float v = static_cast<float>(sqrt(r));
+            out[threadIdx.x] = v;
+            if (global) global[static_cast<int64_t>(row(static_cast<int>(threadIdx.x))) * B + b] = v;
+        }
+        __syncthreads();
+    }
+};
+
+// four consecutive elements of a row from element e on; elements at or past D read as 0
+template <bool VEC>
+__device__ __forceinline__ void load4(const float *row, int64_t e, int64_t D, float (&o)[4]) {
+    if (VEC && e + 3 < D) {
+        const float4 v = *reinterpret_cast<const float4 *>(row + e);
+        o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = e + j < D ? row[e + j] : 0.0f;
+    }
+}
+
+template <bool VEC>
+__device__ __forceinline__ void store4(float *row, int64_t e, int64_t D, const float (&v)[4]) {
+    if (VEC && e + 3 < D) {
+        *reinterpret_cast<float4 *>(row + e) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (e + j < D) row[e + j] = v[j];
+    }
+}
+
+__device__ __forceinline__ int64_t group_element(int g) { return (static_cast<int64_t>(g) * kL2Block + threadIdx.x) * 4; }
+__device__ __forceinline__ int groups_of(int64_t D) { return static_cast<int>((D + 4 * kL2Block - 1) / (4 * kL2Block)); }
+
+// Info of the four elements from e on, `one(c, h, w)` giving an element's; elements at or past D get {0, 0}
+template <class F>
+__device__ __forceinline__ void infos4(int64_t e, const Geo &g, Info (&o)[4], F one) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = Info{0u, 0};
+    if (e >= g.D) return;
+    const int r = static_cast<int>(e);
+    int c = r / g.HW;
+    const int rem = r - c * g.HW;
+    int h = rem / g.W, w = rem - h * g.W;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (e + j < g.D) o[j] = one(c, h, w);
+        if (++w == g.W) {
+            w = 0;
+            if (++h == g.H) h = 0, ++c;
+        }
+    }
+}
+
+__device__ __forceinline__ double square(float v) {
+    const double d = static_cast<double>(v);
+    return d * d;
+}
+
+// ---- start ---------------------------------------------------------------------------------------------------------------------------
+struct Tiling {
+    int s0, nh, nw, oh, ow;
+    int64_t id;
+    const float *eta;
+    // d of element (c, h, w): +-eta0[r][q], transposed by the tile's coin; 0 outside the tiling
+    __device__ __forceinline__ float value(const Philox &ph, int c, int h, int w) const {
+        const int th = h - oh, tw = w - ow;
+        if (th < 0 || tw < 0) return 0.0f;
+        const int a = th / s0, bt = tw / s0;
+        if (a >= nh || bt >= nw) return 0.0f;
+        const int r = th - a * s0, q = tw - bt * s0;
+        const uint4 d = ph((static_cast<uint64_t>(id) << 32) | static_cast<uint32_t>(a * nw + bt), kStreamTile);
+        const float e = eta[(d.y & 1u) ? q * s0 + r : r * s0 + q];
+        return ((d.x >> c) & 1u) ? e : -e;
+    }
+};
+
+template <bool RES, bool VEC>
+__global__ __launch_bounds__(kL2Block) void init_l2_kernel(float *__restrict__ x_best, float *__restrict__ x_new, const float *__restrict__ x0,
+                                                           const int64_t *__restrict__ seed, const float *__restrict__ eta, int s0, int C, int H,
+                                                           int W, float eps) {
+    __shared__ double part[kL2Waves];
+    __shared__ float sn[1];
+    Reducer red{part};
+    const Geo geo{C, H, W, H * W, static_cast<int64_t>(C) * H * W};
+    const int64_t b = blockIdx.x, D = geo.D;
+    const float *cr = x0 + b * D;
+    float *br = x_best + b * D, *nr = x_new + b * D;
+    const int groups = groups_of(D);
+    const Philox ph(static_cast<uint64_t>(seed[0]));
+    Tiling tl;
+    tl.s0 = s0, tl.nh = H / s0, tl.nw = W / s0, tl.oh = (H - tl.nh * s0) / 2, tl.ow = (W - tl.nw * s0) / 2, tl.id = b, tl.eta = eta;
+    // an element's d travels in Info::idx as its bits
+    const auto one = [&](int c, int h, int w) { return Info{0u, __float_as_int(tl.value(ph, c, h, w))}; };
+
+    float rc[kL2Elems], rd[kL2Elems];
+    double acc = 0.0;
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kL2Vecs; ++k) {
+            const int64_t e = group_element(k);
+            float cv[4];
+            Info in[4];
+            load4<VEC>(cr, e, D, cv);
+            infos4(e, geo, in, one);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                rc[k * 4 + j] = cv[j], rd[k * 4 + j] = __int_as_float(in[j].idx);
+                acc += square(rd[k * 4 + j]);
+            }
+        }
+    } else {
+        for (int k = 0; k < groups; ++k) {
+            Info in[4];
+            infos4(group_element(k), geo, in, one);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc += square(__int_as_float(in[j].idx));
+        }
+    }
+    red.put(0, acc);
+    red.norms(1, sn, nullptr, 0, 0, [](int k) { return k; });
+    const float q = eps / (sn[0] + kTiny);
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kL2Vecs; ++k) {
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = tclamp(rc[k * 4 + j] + rd[k * 4 + j] * q, 0.0f, 1.0f);
+            store4<VEC>(br, group_element(k), D, o);
+            store4<VEC>(nr, group_element(k), D, o);
+        }
+    } else {
+        for (int k = 0; k < groups; ++k) {
+            const int64_t e = group_element(k);
+            float cv[4], o[4];
+            Info in[4];
+            load4<VEC>(cr, e, D, cv);
+            infos4(e, geo, in, one);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = tclamp(cv[j] + __int_as_float(in[j].idx) * q, 0.0f, 1.0f);
+            store4<VEC>(br, e, D, o);
+            store4<VEC>(nr, e, D, o);
+        }
+    }
+}
+
+// ---- commit and proposal -------------------------------------------------------------------------------------------------------------
+// the element-wise lines of a proposal; the scalars are filled in as the norms become known (n_w, n_new live in LDS)
+struct Proposal {
+    int s, vh, vw, vh2, vw2;
+    uint32_t signs;
+    bool transpose;
+    const float *eta;
+    const float *n_w, *n_new;
+    float scale, n_d, eps;
+
+    __device__ __forceinline__ Info info(int c, int h, int w) const {
+        Info r{static_cast<uint32_t>(c) << 8, 0};
+        const int a = h - vh, q = w - vw;
+        if (a >= 0 && a < s && q >= 0 && q < s) r.f |= kIn1, r.idx = transpose ? q * s + a : a * s + q;
+        if (h >= vh2 && h < vh2 + s && w >= vw2 && w < vw2 + s) r.f |= kIn2;
+        return r;
+    }
+    // delta -> new on window 1, 0 on the rest of window 2, delta elsewhere
+    __device__ __forceinline__ float stage1(float delta, const Info &i) const {
+        if (i.f & kIn1) {
+            const int c = channel_of(i);
+            const float e = eta[i.idx];
+            return (((signs >> c) & 1u) ? e : -e) + delta / (kTiny + n_w[c]);
+        }
+        return (i.f & kIn2) ? 0.0f : delta;
+    }
+    // new -> new / (tiny + n_new) * scale on window 1
+    __device__ __forceinline__ float stage2(float v, const Info &i) const {
+        return (i.f & kIn1) ? v / (kTiny + n_new[channel_of(i)]) * scale : v;
+    }
+    __device__ __forceinline__ float next(float x0, float v) const { return tclamp(x0 + v / (kTiny + n_d) * eps, 0.0f, 1.0f); }
+};
+
+__device__ __forceinline__ bool any_in1(const Info (&in)[4], int c) {
+    bool r = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r |= (in[j].f & kIn1) && channel_of(in[j]) == c;
+    return r;
+}
+
+template <bool RES, bool VEC>
+__global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x_best, float *x_new, const float *__restrict__ x0, const int *__restrict__ flags,
+                                                           const float *__restrict__ margin_min, const int *__restrict__ counter,
+                                                           const int *__restrict__ sizes, const int *__restrict__ eta_off,
+                                                           const float *__restrict__ eta, int n_sizes, const int64_t *__restrict__ seed,
+                                                           float *__restrict__ norms, int64_t B, int C, int H, int W, float eps) {
+    __shared__ double part[(2 + kMaxC) * kL2Waves];
+    __shared__ float sn1[2 + kMaxC], sn2[kMaxC], sn3[1];
+    Reducer red{part};
+    const Geo geo{C, H, W, H * W, static_cast<int64_t>(C) * H * W};
+    const int64_t b = blockIdx.x, D = geo.D;
+    const int it = counter[0];
+    int s = (it >= 0 && it < n_sizes) ? sizes[it] : 0;  // 0: no proposal in this launch (commit only)
+    if (s < 1 || s > H || s > W) s = 0;                 // a size the window arithmetic cannot take is no proposal either
+    const int off = s ? eta_off[it] : 0;
+    if (off < 0) s = 0;
+    const bool commit = flags[b] != 0, propose = s > 0 && !(margin_min[b] <= 0.0f);  // uniform over the workgroup
+    if (!propose && static_cast<int>(threadIdx.x) < 3 + 2 * C) norms[static_cast<int64_t>(threadIdx.x) * B + b] = 0.0f;
+    if (!commit && !propose) return;
+    const float *cr = x0 + b * D;
+    float *br = x_best + b * D, *nr = x_new + b * D;
+    const int groups = groups_of(D);
+    if (!propose) {  // the commit alone
+        for (int k = 0; k < groups; ++k) {
+            float v[4];
+            load4<VEC>(nr, group_element(k), D, v);
+            store4<VEC>(br, group_element(k), D, v);
+        }
+        return;
+    }
+    const Philox ph(static_cast<uint64_t>(seed[0]));
+    const WindowDraw w1 = draw_window(ph, it, b, s, H, W, kStreamWindow), w2 = draw_window(ph, it, b, s, H, W, kStreamWindow2);
+    Proposal p;
+    p.s = s, p.vh = w1.vh, p.vw = w1.vw, p.vh2 = w2.vh, p.vw2 = w2.vw, p.signs = w1.z, p.transpose = (w1.w & 1u) != 0;
+    p.eta = eta + off, p.n_w = sn1 + 2, p.n_new = sn2, p.scale = 0.0f, p.n_d = 0.0f, p.eps = eps;
+    const auto one = [&](int c, int h, int w) { return p.info(c, h, w); };
+
+    // round 1: n_img, n_un over the whole sample - the pass that commits, and that takes the sample into registers on the resident path
+    float rc[kL2Elems], rv[kL2Elems];
+    Info ri[kL2Elems];
+    double a_img = 0.0, a_un = 0.0;
+    const auto first = [&](int64_t e, float (&cv)[4], float (&dv)[4], Info (&in)[4]) {
+        float xv[4];
+        load4<VEC>(commit ? nr : br, e, D, xv);
+        if (commit) store4<VEC>(br, e, D, xv);
+        load4<VEC>(cr, e, D, cv);
+        infos4(e, geo, in, one);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            dv[j] = xv[j] - cv[j];
+            const double q = square(dv[j]);
+            a_img += q;
+            a_un += (in[j].f & (kIn1 | kIn2)) ? q : 0.0;
+        }
+    };
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kL2Vecs; ++k) {
+            float cv[4], dv[4];
+            Info in[4];
+            first(group_element(k), cv, dv, in);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) rc[k * 4 + j] = cv[j], rv[k * 4 + j] = dv[j], ri[k * 4 + j] = in[j];
+        }
+    } else {
+        for (int k = 0; k < groups; ++k) {
+            float cv[4], dv[4];
+            Info in[4];
+            first(group_element(k), cv, dv, in);
+        }
+    }
+    red.put(0, a_img);
+    red.put(1, a_un);
+    // the streaming path from here on: (x0, delta, info) of a group, skipped when `want` says the pass has no use for it
+    const auto stream = [&](int k, auto want, auto body) {
+        const int64_t e = group_element(k);
+        Info in[4];
+        infos4(e, geo, in, one);
+        if (!want(in)) return;
+        float xv[4], cv[4], dv[4];
+        load4<VEC>(br, e, D, xv);
+        load4<VEC>(cr, e, D, cv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dv[j] = xv[j] - cv[j];
+        body(e, cv, dv, in);
+    };
+    // n_w[c]: window 1 of channel c
+    for (int c = 0; c < C; ++c) {
+        double acc = 0.0;
+        if (RES) {
+#pragma unroll
+            for (int k = 0; k < kL2Elems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? square(rv[k]) : 0.0;
+        } else {
+            for (int k = 0; k < groups; ++k)
+                stream(k, [&](const Info(&in)[4]) { return any_in1(in, c); },
+                       [&](int64_t, const float(&)[4], const float(&dv)[4], const Info(&in)[4]) {
+#pragma unroll
+                           for (int j = 0; j < 4; ++j) acc += ((in[j].f & kIn1) && channel_of(in[j]) == c) ? square(dv[j]) : 0.0;
+                       });
+        }
+        red.put(2 + c, acc);
+    }
+    red.norms(2 + C, sn1, norms, B, b, [](int k) { return k < 2 ? k : k + 1; });
+    {
+        const float n_img = sn1[0], n_un = sn1[1];
+        const float room = tmax(eps * eps - n_img * n_img, 0.0f);
+        p.scale = static_cast<float>(sqrt(static_cast<double>(room / static_cast<float>(C) + n_un * n_un)));  // the f32 root, rounded once
+    }
+
+    // round 2: n_new[c]
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kL2Elems; ++k) rv[k] = p.stage1(rv[k], ri[k]);
+    }
+    for (int c = 0; c < C; ++c) {
+        double acc = 0.0;
+        if (RES) {
+#pragma unroll
+            for (int k = 0; k < kL2Elems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? square(rv[k]) : 0.0;
+        } else {
+            for (int k = 0; k < groups; ++k)
+                stream(k, [&](const Info(&in)[4]) { return any_in1(in, c); },
+                       [&](int64_t, const float(&)[4], const float(&dv)[4], const Info(&in)[4]) {
+#pragma unroll
+                           for (int j = 0; j < 4; ++j)
+                               acc += ((in[j].f & kIn1) && channel_of(in[j]) == c) ? square(p.stage1(dv[j], in[j])) : 0.0;
+                       });
+        }
+        red.put(c, acc);
+    }
+    red.norms(C, sn2, norms, B, b, [C](int k) { return 3 + C + k; });
+
+    // round 3: n_d over the whole sample
+    double a_d = 0.0;
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kL2Elems; ++k) {
+            rv[k] = p.stage2(rv[k], ri[k]);
+            a_d += square(rv[k]);
+        }
+    } else {
+        for (int k = 0; k < groups; ++k)
+            stream(k, [](const Info(&)[4]) { return true; }, [&](int64_t, const float(&)[4], const float(&dv)[4], const Info(&in)[4]) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) a_d += square(p.stage2(p.stage1(dv[j], in[j]), in[j]));
+            });
+    }
+    red.put(0, a_d);
+    red.norms(1, sn3, norms, B, b, [](int) { return 2; });
+    p.n_d = sn3[0];
+
+    // final pass: the one place x_new is written
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kL2Vecs; ++k) {
+            float o[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = p.next(rc[k * 4 + j], rv[k * 4 + j]);
+            store4<VEC>(nr, group_element(k), D, o);
+        }
+    } else {
+        for (int k = 0; k < groups; ++k)
+            stream(k, [](const Info(&)[4]) { return true; }, [&](int64_t e, const float(&cv)[4], const float(&dv)[4], const Info(&in)[4]) {
+                float o[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = p.next(cv[j], p.stage2(p.stage1(dv[j], in[j]), in[j]));
+                store4<VEC>(nr, e, D, o);
+            });
+    }
+}
+
+// what both entry points check of (B, C, H, W, eps, path); *res: the resident path runs
+int check_l2(int B, int C, int H, int W, float eps, int path, bool *res) {
+    const int rc = sqatk_check_shape(B, C, H, W);
+    if (rc != EE_OK) return rc;
+    if (path < EE_SQATK_L2_PATH_AUTO || path > EE_SQATK_L2_PATH_STREAMING || !(eps >= 0.0f)) return EE_ERR_SHAPE;
+    const int64_t D = static_cast<int64_t>(C) * H * W;
+    if (path == EE_SQATK_L2_PATH_RESIDENT && D > kL2Resident) return EE_ERR_UNSUPPORTED;
+    *res = path == EE_SQATK_L2_PATH_RESIDENT || (path == EE_SQATK_L2_PATH_AUTO && D <= kL2Resident);
+    return EE_OK;
+}
+
+}  // namespace
+
+EE_API int ee_sqatk_init_l2_f32(float *x_best, float *x_new, const float *x0, const int64_t *seed, const float *eta, int s0, int B, int C, int H,
+                                int W, float eps, int path, void *stream) {
+    bool res = false;
+    const int rc = check_l2(B, C, H, W, eps, path, &res);
+    if (rc != EE_OK) return rc;
+    if (s0 < 1 || s0 > H || s0 > W) return EE_ERR_SHAPE;
+    if (B == 0) return EE_OK;
+    if (!x_best || !x_new || !x0 || !seed || !eta) return EE_ERR_NULL;
+    if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || !aligned4(eta) || (reinterpret_cast<uintptr_t>(seed) & 7u)) return EE_ERR_ALIGN;
+    const bool vec = ((static_cast<int64_t>(C) * H * W) & 3) == 0 && aligned16(x_best) && aligned16(x_new) && aligned16(x0);
+    const dim3 grid(static_cast<unsigned>(B)), block(kL2Block);
+    ProfScope prof(EE_K_SQATK_INIT, as_stream(stream));
+    if (res && vec)
+        EE_LAUNCH((init_l2_kernel<true, true>), grid, block, 0, as_stream(stream), x_best, x_new, x0, seed, eta, s0, C, H, W, eps);
+    else if (res)
+        EE_LAUNCH((init_l2_kernel<true, false>), grid, block, 0, as_stream(stream), x_best, x_new, x0, seed, eta, s0, C, H, W, eps);
+    else if (vec)
+        EE_LAUNCH((init_l2_kernel<false, true>), grid, block, 0, as_stream(stream), x_best, x_new, x0, seed, eta, s0, C, H, W, eps);
+    else
+        EE_LAUNCH((init_l2_kernel<false, false>), grid, block, 0, as_stream(stream), x_best, x_new, x0, seed, eta, s0, C, H, W, eps);
+    return launch_status();
+}
+
+EE_API int ee_sqatk_step_l2_f32(float *x_best, float *x_new, const float *x0, const int *flags, const float *margin_min, const int *counter,
+                                const int *sizes, const int *eta_off, const float *eta, int n_sizes, const int64_t *seed, float *norms, int B,
+                                int C, int H, int W, float eps, int path, void *stream) {
+    bool res = false;
+    const int rc = check_l2(B, C, H, W, eps, path, &res);
+    if (rc != EE_OK) return rc;
+    if (n_sizes < 0) return EE_ERR_SHAPE;
+    if (B == 0) return EE_OK;
+    if (!x_best || !x_new || !x0 || !flags || !margin_min || !counter || !seed || !norms || (n_sizes > 0 && (!sizes || !eta_off || !eta)))
+        return EE_ERR_NULL;
+    if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || !aligned4(flags) || !aligned4(margin_min) || !aligned4(counter) ||
+        !aligned4(sizes) || !aligned4(eta_off) || !aligned4(eta) || !aligned4(norms) || (reinterpret_cast<uintptr_t>(seed) & 7u))
+        return EE_ERR_ALIGN;
+    const bool vec = ((static_cast<int64_t>(C) * H * W) & 3) == 0 && aligned16(x_best) && aligned16(x_new) && aligned16(x0);
+    const dim3 grid(static_cast<unsigned>(B)), block(kL2Block);
+    const int64_t Bl = B;
+    ProfScope prof(EE_K_SQATK_STEP, as_stream(stream));
+    if (res && vec)
+        EE_LAUNCH((step_l2_kernel<true, true>), grid, block, 0, as_stream(stream), x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off,
+                  eta, n_sizes, seed, norms, Bl, C, H, W, eps);
+    else if (res)
+        EE_LAUNCH((step_l2_kernel<true, false>), grid, block, 0, as_stream(stream), x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off,
+                  eta, n_sizes, seed, norms, Bl, C, H, W, eps);
+    else if (vec)
+        EE_LAUNCH((step_l2_kernel<false, true>), grid, block, 0, as_stream(stream), x_best, x_new, x0, flags, margin_min, counter, sizes,
+                  eta_off, eta, n_sizes, seed, norms, Bl, C, H, W, eps);
+    else
+        EE_LAUNCH((step_l2_kernel<false, false>), grid, block, 0, as_stream(stream), x_best, x_new, x0, flags, margin_min, counter, sizes,
+                  eta_off, eta, n_sizes, seed, norms, Bl, C, H, W, eps);
+    return launch_status();
+}

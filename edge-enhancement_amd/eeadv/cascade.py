@@ -25,16 +25,19 @@ from . import ops, runtime
 STAGES = ("APGD-CE", "APGD-T", "FAB-T", "Square")
 
 
-def default_stages(args, num_steps, n_class, n_target_classes=9):
+def default_stages(args, num_steps, n_class, n_target_classes=9, norm="Linf"):
     """[(name, fn)] of AutoAttack's `standard` order; fn(model, args, x, y, order) -> (x_adv, robust) runs one stage on one full batch, `order`
-    being the class order of the clean logits [B, n_t + 1] (the targets of APGD-T and FAB-T: no clean forward of their own)."""
+    being the class order of the clean logits [B, n_t + 1] (the targets of APGD-T and FAB-T: no clean forward of their own).  norm: 'Linf'
+    (the default: the calls made before the parameter existed) or 'L2' - every stage then runs in the L2 ball of radius args.epsilon
+    (DESIGN.md sections 16 - 18), so evaluate(..., stages=default_stages(..., norm="L2")) is the L2 `standard` cascade."""
     fab_iters = int(getattr(args, "fab_iters", 100))
     queries = int(getattr(args, "square_queries", 5000))
+    kw = A._norm_kw(norm)  # empty for Linf
     return [
-        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce")),
-        ("APGD-T", lambda model, a, x, y, order: A.APGD_T(model, a, x, y, num_steps, n_class, n_target_classes, order=order)),
-        ("FAB-T", lambda model, a, x, y, order: A.FAB_T(model, a, x, y, n_class, fab_iters, n_target_classes, order=order)[:2]),
-        ("Square", lambda model, a, x, y, order: A.Square(model, a, x, y, queries)[:2]),
+        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", **kw)),
+        ("APGD-T", lambda model, a, x, y, order: A.APGD_T(model, a, x, y, num_steps, n_class, n_target_classes, order=order, **kw)),
+        ("FAB-T", lambda model, a, x, y, order: A.FAB_T(model, a, x, y, n_class, fab_iters, n_target_classes, order=order, **kw)[:2]),
+        ("Square", lambda model, a, x, y, order: A.Square(model, a, x, y, queries, **kw)[:2]),
     ]
 
 

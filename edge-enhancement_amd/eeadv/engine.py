@@ -491,9 +491,17 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# Square attack (Andriushchenko et al. 2020; Linf, margin loss, p_init = 0.8 with the rescaled schedule, one run, no EOT): DESIGN.md section 12
+# Square attack (Andriushchenko et al. 2020; Linf or L2, margin loss, p_init = 0.8 with the rescaled schedule, one run, no EOT): DESIGN.md
+# sections 12 and 18
 # ---------------------------------------------------------------------------------------------------------------------------------------
 SQUARE_CHECK_EVERY = 64  # iterations between two host reads of "is any sample still active" (the only host read of the attack)
+SQUARE_NORMS = ("Linf", "L2")
+
+
+def _check_square_norm(norm):
+    if norm not in SQUARE_NORMS:
+        raise ValueError("Square norm must be one of %s, got %r" % (list(SQUARE_NORMS), norm))
+    return norm
 
 
 def square_schedule(n_queries, H, W):
@@ -510,9 +518,11 @@ def _signed64(seed):
 class _SquareRun:
     """The device state of one Square attack (include/eeadv.h, "Square attack") and its pieces: `start` (the striped start and its forward,
     once per attack), `iteration` (step, eval forward under no_grad, margin: what a captured graph replays) and `finish` (the commit of the
-    last accepted proposal).  No host read anywhere."""
+    last accepted proposal).  No host read anywhere.  norm = "L2": the run owns `norms` [3 + 2C, B], the pattern tables `eta` with `eta_off`
+    and the L2 schedule, and init / step are the launches of ee_sqatk_l2.hip (`path` picks their path) - nothing else knows the norm."""
 
-    def __init__(self, x0, y, n_queries, eps):
+    def __init__(self, x0, y, n_queries, eps, norm="Linf", path="auto"):
+        _check_square_norm(norm)
         if x0.dim() != 4:
             raise ValueError("the Square attack takes image batches [B,C,H,W], got shape %s" % (tuple(x0.shape),))
         B, dev = x0.shape[0], x0.device
@@ -525,8 +535,22 @@ class _SquareRun:
         self.flags = torch.zeros(B, dtype=torch.int32, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.sizes = torch.tensor(square_schedule(n_queries, x0.shape[2], x0.shape[3]), dtype=torch.int32).to(dev)
-        self.trace = None
+        self.norm, self.path, self.norms = norm, path, None
+        if norm == "L2":
+            if path not in ops.SQATK_L2_PATHS:
+                raise ValueError("the L2 Square kernels' path must be one of %s, got %r" % (sorted(ops.SQATK_L2_PATHS), path))
+            C, H, W = x0.shape[1:]
+            sizes = sqatk.square_schedule_l2(n_queries, H, W)
+            s0 = sqatk.start_size(H, W)
+            eta, eta_off, off0 = sqatk.eta_tables(sizes, s0)
+            self.sizes = torch.tensor(sizes, dtype=torch.int32).to(dev)
+            self.eta = torch.from_numpy(eta).to(dev)
+            self.eta_off = torch.from_numpy(eta_off).to(dev)
+            self.eta0 = self.eta[off0:off0 + s0 * s0].view(s0, s0)  # the start's table: a view, nothing of its own
+            self.norms = torch.zeros((3 + 2 * C, B), dtype=torch.float32, device=dev)
+        else:
+            self.sizes = torch.tensor(square_schedule(n_queries, x0.shape[2], x0.shape[3]), dtype=torch.int32).to(dev)
+        self.trace, self.step_entry = None, None
 
     def load(self, x0, y, seed):
         with torch.no_grad():
@@ -539,7 +563,10 @@ class _SquareRun:
             z = model(self.x_new)
         ops.sqatk_margin_(z.detach().float().contiguous(), self.y, self.margin_out, self.margin_min, self.queries, self.flags, self.counter)
         if self.trace is not None:
-            self.trace.append({"margin": self.margin_out.clone(), "flags": self.flags.clone()})
+            entry = {"margin": self.margin_out.clone(), "flags": self.flags.clone()}
+            entry.update(self.step_entry or {})  # an L2 run: what the step before this forward read and wrote
+            self.step_entry = None
+            self.trace.append(entry)
 
     def start(self, model):
         with torch.no_grad():
@@ -547,16 +574,32 @@ class _SquareRun:
             self.queries.zero_()
             self.flags.zero_()
             self.counter.fill_(-1)  # the start's margin launch brings it to proposal 0
-        ops.sqatk_init_(self.x_best, self.x_new, self.x0, self.seed, self.eps)
+        if self.norms is None:
+            ops.sqatk_init_(self.x_best, self.x_new, self.x0, self.seed, self.eps)
+        else:
+            ops.sqatk_init_l2_(self.x_best, self.x_new, self.x0, self.seed, self.eta0, self.eps, self.path)
         self._query(model)
 
+    def _step(self, sizes):
+        if self.norms is None:
+            ops.sqatk_step_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, sizes, self.seed, self.eps)
+            return
+        entry = None
+        if self.trace is not None:
+            entry = dict(x_best_in=self.x_best.clone(), x_new_in=self.x_new.clone(), counter=int(self.counter.item()))
+        ops.sqatk_step_l2_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, sizes, self.eta_off, self.eta, self.seed,
+                           self.eps, self.norms, self.path)
+        if entry is not None:
+            entry.update(norms=self.norms.clone(), x_new=self.x_new.clone())
+            self.step_entry = entry
+
     def iteration(self, model):
-        ops.sqatk_step_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, self.sizes, self.seed, self.eps)
+        self._step(self.sizes)
         self._query(model)
 
     def finish(self):
         """The flags of the last margin launch are still to be committed: a step without a table commits and proposes nothing."""
-        ops.sqatk_step_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, None, self.seed, self.eps)
+        self._step(None)
 
     def any_active(self):
         return bool((~(self.margin_min <= 0)).any().item())
@@ -567,7 +610,7 @@ class _SquareRun:
             return _adv_where_fooled(robust, self.x0, self.x_best), robust, self.queries.clone()
 
 
-def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=None, early_exit=True):
+def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=None, early_exit=True, norm="Linf", path="auto"):
     """One Square attack of at most n_queries forwards per sample inside the eps-ball around x0 [B,C,H,W].  Returns (x_adv, robust,
     queries): x0 with the fooled rows (margin_min <= 0) replaced by their fooling point, robust [B] bool (margin_min > 0), and the number
     of forwards each sample was active for (int32 [B]).  `seed` keys the draws (None: a ticket from torch's generator of the device, so
@@ -575,7 +618,11 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
     from a captured graph of MAX_ITERS_PER_GRAPH iterations, the remainder running eagerly; both give the same bits.  early_exit: the
     host reads "is any sample still active" once per SQUARE_CHECK_EVERY iterations and stops when none is - fooled samples are frozen, so
     the result is the same bits either way.  `trace` (a list, eager only) receives {"margin", "flags"} of every forward, the start's
-    first."""
+    first.  norm: 'Linf' (the default: exactly what ran before the parameter existed) or 'L2' - the ball is then the L2 ball of radius eps,
+    start and proposal those of ee_sqatk_l2.hip (DESIGN.md section 18; `path` picks the kernels' path, the same bits) on the L2 schedule;
+    margin, accept rule, counter, query count, early exit and the graph are shared, and the trace entry of a forward that follows a step
+    also holds "x_best_in", "x_new_in", "counter", "norms" [3 + 2C, B] and "x_new"."""
+    _check_square_norm(norm)
     model = _unwrap(model)
     x0 = x0.detach().contiguous()
     n_queries = int(n_queries)
@@ -594,12 +641,12 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
     if x0.shape[0] == 0:
         return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=torch.int32, device=x0.device)
     if not use_graph or chunk == 0:
-        run, gs = _SquareRun(x0, y, n_queries, eps), None
+        run, gs = _SquareRun(x0, y, n_queries, eps, norm, path), None
     else:
-        key = ("square", id(model), model.training, tuple(x0.shape), n_queries, float(eps), x0.device.index, chunk)
+        key = ("square", id(model), model.training, tuple(x0.shape), n_queries, float(eps), x0.device.index, chunk, norm, path)
 
         def build():
-            run = _SquareRun(x0, y, n_queries, eps)
+            run = _SquareRun(x0, y, n_queries, eps, norm, path)
             run.load(x0, y, seed)
             return _Captured(model, x0.device, chunk, run).capture(model, _times(chunk, run.iteration), start=lambda: run.start(model))
 

@@ -541,6 +541,49 @@ def sqatk_step_(x_best, x_new, x0, flags, margin_min, counter, sizes, seed, eps)
     return x_new
 
 
+# ---- Square attack in the L2 threat model (ee_sqatk_l2.hip) -----------------------------------------------------------
+SQATK_L2_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_SQATK_L2_PATH_*
+SQATK_L2_RESIDENT = 12288  # per-sample size up to which the resident path exists
+
+
+def _sqatk_l2_path(path):
+    if path not in SQATK_L2_PATHS:
+        raise ValueError("the L2 Square kernels' path must be one of %s, got %r" % (sorted(SQATK_L2_PATHS), path))
+    return SQATK_L2_PATHS[path]
+
+
+def sqatk_init_l2_(x_best, x_new, x0, seed, eta0, eps, path="auto"):
+    """The tiled start of an L2 run into x_best and x_new [B,C,H,W]; eta0 float32 [s0, s0] on the device (eeadv.sqatk.eta), seed int64 [1]."""
+    B, C, H, W = x_best.shape
+    pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
+    if eta0.dim() != 2 or eta0.shape[0] != eta0.shape[1]:
+        raise ValueError("eta0 must be a square table [s0, s0], got shape %s" % (tuple(eta0.shape),))
+    N.check(N.lib.ee_sqatk_init_l2_f32(pb, pn, p0, _chk(seed, torch.int64, "seed", (1,)), _chk(eta0, torch.float32, "eta0"), int(eta0.shape[0]),
+                                       B, C, H, W, eps, _sqatk_l2_path(path), _stream()), "ee_sqatk_init_l2_f32")
+    return x_best
+
+
+def sqatk_step_l2_(x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off, eta, seed, eps, norms=None, path="auto"):
+    """Commit under flags [B], then L2 proposal counter[0]: window edge sizes[counter[0]], pattern table eta[eta_off[counter[0]]:] (sizes
+    None or empty: commit only; eta_off and eta are then not read).  Returns norms [3 + 2C, B] (n_img, n_un, n_d, n_w[c], n_new[c]; zeros
+    for a sample that made no proposal), written into `norms` when given.  path: 'auto', 'resident' (C*H*W <= 12288) or 'streaming'; the
+    same bits."""
+    B, C, H, W = x_best.shape
+    pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
+    n_sizes = 0 if sizes is None else int(sizes.numel())
+    ps = po = pe = None
+    if n_sizes:
+        ps = _chk(sizes, torch.int32, "sizes", (n_sizes,))
+        po = _chk(eta_off, torch.int32, "eta_off", (n_sizes,))
+        pe = _chk(eta, torch.float32, "eta")
+    norms = torch.zeros((3 + 2 * C, B), dtype=torch.float32, device=x_best.device) if norms is None else norms
+    N.check(N.lib.ee_sqatk_step_l2_f32(pb, pn, p0, _chk(flags, torch.int32, "flags", (B,)), _chk(margin_min, torch.float32, "margin_min", (B,)),
+                                       _chk(counter, torch.int32, "counter", (1,)), ps, po, pe, n_sizes, _chk(seed, torch.int64, "seed", (1,)),
+                                       _chk(norms, torch.float32, "norms", (3 + 2 * C, B)), B, C, H, W, eps, _sqatk_l2_path(path), _stream()),
+            "ee_sqatk_step_l2_f32")
+    return norms
+
+
 # ---- FAB-T (ee_fab.hip) ----------------------------------------------------------------------------------------------
 FAB_ADV, FAB_IMPROVED = 1, 2  # bits of the flags of fab_commit_ (EE_FAB_*)
 FAB_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_FAB_PATH_*

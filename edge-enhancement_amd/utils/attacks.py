@@ -134,7 +134,7 @@ def targeted_PGD_trick(model, args, inputs, labels, num_steps, step_size, nclass
 # reference's utils/attacks.py - its drivers call the `autoattack` package for them.  Square, the black-box member, and FAB-T follow below;
 # `eot_iter` averages every gradient over that many forwards (EOT), and APGD_Rand is the `rand` version's order, APGD-CE then APGD-DLR with
 # EOT.  `norm="L2"` runs APGD (every loss, EOT included) in the L2 threat model of radius args.epsilon: the published
-# L2 step and start, everything else shared.  EOT for APGD-T, Square and FAB-T, L2 Square and L2 FAB, the L1 norm
+# L2 step and start, everything else shared.  EOT for APGD-T, Square and FAB-T, the L1 norm
 # and restarts are NOT here, so the result is not an AutoAttack number.
 # ---------------------------------------------------------------------------------------------------------
 def _apgd_row_losses(z, y, loss, t=None):
@@ -358,7 +358,7 @@ def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, 
 
 
 # ---------------------------------------------------------------------------------------------------------
-# Square (Andriushchenko et al. 2020, Linf): the black-box member of AutoAttack's `standard` version - score-based random search on the
+# Square (Andriushchenko et al. 2020, Linf; norm="L2": its L2 form): the black-box member of AutoAttack's `standard` version - score-based random search on the
 # margin loss, p_init = 0.8 with the rescaled schedule, one run, no EOT.  Built from the published description;
 # every sample draws a window of its own (the paper's form), so a sample's trajectory does not depend on who shares its batch.
 # ---------------------------------------------------------------------------------------------------------
@@ -373,14 +373,107 @@ def _square_margin(z, y):
     return torch.where(bad, torch.full_like(zy, float("nan")), zy - other)
 
 
-def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early_exit=True):
-    """Plumbing path for CPU tensors (opt-in): the iteration of engine.square_loop in plain torch ops, in the input's dtype, with the
-    kernels' draws (eeadv.sqatk: the same Philox key, counters and stream ids).  `ids` [B]: the batch index each sample draws under
-    (default 0 .. B-1).  Returns (x_best, margin_min, queries); `trace`, a list, receives {"margin", "flags"} of every forward."""
+def _check_square_norm(norm):
+    if norm not in engine.SQUARE_NORMS:
+        raise ValueError("Square norm must be one of %s, got %r" % (list(engine.SQUARE_NORMS), norm))
+    return norm
+
+
+def _square_l2_norms(v, planes=False):
+    """||v[b]||_2 [B] (planes: ||v[b, c]||_2 [B, C]) in v's dtype for the L2 Square host path: the root, rounded once, of the squares summed in
+    float64.  The squares of float32 (and narrower) values are exact there and torch's sum is then far inside the last bit of the result;
+    float64 values are split into halves whose products are exact and summed without error (math.fsum), so that a float64 run - what the
+    tests compare bit for bit - has norms rounded once as well."""
+    import math
+    rows = v.reshape(v.shape[0] * v.shape[1] if planes else v.shape[0], -1).detach().cpu()
+    if v.dtype == torch.float64:
+        a = rows.numpy()
+        c = a * 134217729.0  # Veltkamp: hi holds the upper 26 bits
+        hi = c - (c - a)
+        lo = a - hi
+        terms = np.concatenate([hi * hi, 2.0 * hi * lo, lo * lo], axis=1)
+        sums = np.array([math.fsum(r) for r in terms.tolist()], dtype=np.float64)
+    else:
+        sums = (rows.to(torch.float64) ** 2).sum(dim=1).numpy()
+    out = torch.from_numpy(np.sqrt(sums)).to(v.dtype).to(v.device)
+    return out.view(v.shape[0], v.shape[1]) if planes else out
+
+
+def _square_l2_start(x0, eps, seed, ids):
+    """The tiled start of an L2 run: (x_best, n0)."""
     from eeadv import sqatk
     B, C, H, W = x0.shape
+    s0 = sqatk.start_size(H, W)
+    nh, nw = H // s0, W // s0
+    oh, ow = (H - nh * s0) // 2, (W - nw * s0) // 2
+    bits, tr = (torch.from_numpy(a) for a in sqatk.tiles(seed, ids, nh * nw))
+    eta0 = torch.from_numpy(sqatk.eta(s0)).to(x0.dtype)
+    one = torch.ones((), dtype=x0.dtype)
+    cc = torch.arange(C).view(1, C)
+    d = torch.zeros(x0.shape, dtype=x0.dtype)
+    for a in range(nh):
+        for b in range(nw):
+            k = a * nw + b
+            block = torch.where(tr[:, k].bool().view(B, 1, 1), eta0.t().unsqueeze(0), eta0.unsqueeze(0))
+            sign = torch.where(((bits[:, k].view(B, 1) >> cc) & 1).bool(), one, -one)
+            d[:, :, oh + a * s0:oh + (a + 1) * s0, ow + b * s0:ow + (b + 1) * s0] = sign.view(B, C, 1, 1) * block.view(B, 1, s0, s0)
+    d = d.to(x0.device)
+    tiny = torch.tensor(1e-12, dtype=torch.float32).to(x0.dtype)  # the constant is a float32 one in every dtype
+    n0 = _square_l2_norms(d)
+    q = torch.tensor(eps, dtype=x0.dtype) / (n0 + tiny)
+    return torch.clamp(x0 + d * q.view(B, 1, 1, 1), 0, 1), n0
+
+
+def _square_l2_propose(x_best, x0, eps, seed, i, ids, s):
+    """Proposal i of an L2 run for every sample: (x_new, norms [3 + 2C, B])."""
+    from eeadv import sqatk
+    B, C, H, W = x0.shape
+    dt = x0.dtype
+    vh, vw, bits, tr = sqatk.windows_l2(seed, i, ids, H, W, s)
+    vh2, vw2 = sqatk.windows2(seed, i, ids, H, W, s)
+    eta_s = torch.from_numpy(sqatk.eta(s)).to(dt)
+    pattern = torch.zeros((B, H, W), dtype=dt)
+    for b in range(B):
+        pattern[b, vh[b]:vh[b] + s, vw[b]:vw[b] + s] = eta_s.t() if tr[b] else eta_s
+    hh, ww, cc = torch.arange(H).view(1, H), torch.arange(W).view(1, W), torch.arange(C).view(1, C)
+
+    def inside(ah, aw):
+        ah, aw = torch.from_numpy(ah).view(B, 1), torch.from_numpy(aw).view(B, 1)
+        return (((hh >= ah) & (hh < ah + s)).view(B, 1, H, 1) & ((ww >= aw) & (ww < aw + s)).view(B, 1, 1, W)).to(x0.device)
+
+    in1, in2 = inside(vh, vw), inside(vh2, vw2)
+    one, zero = torch.ones((), dtype=dt), torch.zeros((), dtype=dt)
+    sign = torch.where(((torch.from_numpy(bits).view(B, 1) >> cc) & 1).bool(), one, -one).view(B, C, 1, 1).to(x0.device)
+    tiny = torch.tensor(1e-12, dtype=torch.float32).to(dt)  # the constant is a float32 one in every dtype
+    e = torch.tensor(eps, dtype=dt)
+    delta = x_best - x0
+    n_img = _square_l2_norms(delta)
+    n_un = _square_l2_norms(torch.where(in1 | in2, delta, zero))
+    n_w = _square_l2_norms(torch.where(in1, delta, zero), planes=True)
+    new = torch.where(in1, pattern.to(x0.device).view(B, 1, H, W) * sign + delta / (tiny + n_w).view(B, C, 1, 1), zero)
+    n_new = _square_l2_norms(new, planes=True)
+    room = torch.clamp(e * e - n_img * n_img, min=0) / C + n_un * n_un
+    scale = torch.from_numpy(np.sqrt(room.cpu().numpy())).to(x0.device)  # the root rounded once: torch's vectorised CPU sqrt may miss the last bit
+    new = new / (tiny + n_new).view(B, C, 1, 1) * scale.view(B, 1, 1, 1)
+    delta = torch.where(in1, new, torch.where(in2, zero, delta))
+    n_d = _square_l2_norms(delta)
+    x_new = torch.clamp(x0 + delta / (tiny + n_d).view(B, 1, 1, 1) * e, 0, 1)
+    return x_new, torch.cat([torch.stack([n_img, n_un, n_d]), n_w.t(), n_new.t()])
+
+
+def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early_exit=True, norm="Linf"):
+    """Plumbing path for CPU tensors (opt-in): the iteration of engine.square_loop in plain torch ops, in the input's dtype, with the
+    kernels' draws (eeadv.sqatk: the same Philox key, counters and stream ids).  `ids` [B]: the batch index each sample draws under
+    (default 0 .. B-1).  Returns (x_best, margin_min, queries); `trace`, a list, receives {"margin", "flags"} of every forward.
+    norm = "L2": start and proposals are those of csrc/ee_sqatk_l2.hip in torch ops on the L2 schedule (each norm the root of the squares
+    summed in float64, cast to the dtype); the trace entries then also hold "x_new" and "norms" ([1, B] for the start: n0; [3 + 2C, B] for
+    a proposal, zeros for a sample that made none).  Everything else is shared."""
+    from eeadv import sqatk
+    _check_square_norm(norm)
+    B, C, H, W = x0.shape
     ids = np.arange(B) if ids is None else np.asarray(ids)
-    sizes = engine.square_schedule(n_queries, H, W)
+    l2 = norm == "L2"
+    sizes = sqatk.square_schedule_l2(n_queries, H, W) if l2 else engine.square_schedule(n_queries, H, W)
     inf = torch.full((B,), _INF, dtype=x0.dtype, device=x0.device)
     state = {"margin_min": inf, "queries": torch.zeros(B, dtype=torch.int32, device=x0.device)}
 
@@ -392,17 +485,28 @@ def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early
         state["margin_min"] = torch.where(accept, m, state["margin_min"])
         state["queries"] = state["queries"] + active.to(torch.int32)
         if trace is not None:
-            trace.append({"margin": m.clone(), "flags": accept.clone()})
+            trace.append(dict(extra, margin=m.clone(), flags=accept.clone()))
         return torch.where(accept.view(-1, 1, 1, 1), x_new, x_best)
 
-    stripe = torch.from_numpy(sqatk.stripes(seed, ids, C, W)).to(x0.dtype).to(x0.device)
-    x_best = torch.clamp(x0 + eps * stripe.view(B, C, 1, W), 0, 1)
+    extra = {}
+    if l2:
+        x_best, n0 = _square_l2_start(x0, eps, seed, ids)
+        extra = {"x_new": x_best.clone(), "norms": n0.view(1, B).clone()}
+    else:
+        stripe = torch.from_numpy(sqatk.stripes(seed, ids, C, W)).to(x0.dtype).to(x0.device)
+        x_best = torch.clamp(x0 + eps * stripe.view(B, C, 1, W), 0, 1)
     x_best = query(x_best, x_best)
     hh, ww, cc = torch.arange(H).view(1, H), torch.arange(W).view(1, W), torch.arange(C).view(1, C)
     for i, s in enumerate(sizes):
         active = ~(state["margin_min"] <= 0)
         if early_exit and not bool(active.any()):
             break
+        if l2:
+            prop, norms = _square_l2_propose(x_best, x0, eps, seed, i, ids, s)
+            x_new = torch.where(active.view(-1, 1, 1, 1), prop, x_best)
+            extra = {"x_new": x_new.clone(), "norms": torch.where(active.view(1, B), norms, torch.zeros((), dtype=norms.dtype))}
+            x_best = query(x_new, x_best)
+            continue
         vh, vw, bits = (torch.from_numpy(a).view(B, 1) for a in sqatk.windows(seed, i, ids, H, W, s))
         inside = ((hh >= vh) & (hh < vh + s)).view(B, 1, H, 1) & ((ww >= vw) & (ww < vw + s)).view(B, 1, 1, W)
         up = torch.tensor(2.0 * eps, dtype=x0.dtype)  # a 0-dim tensor of the input's dtype: two Python scalars would make float32 of it
@@ -414,19 +518,20 @@ def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early
     return x_best, state["margin_min"], state["queries"]
 
 
-def Square(model, args, inputs, targets, n_queries=5000, seed=None):
-    """One Square attack (Linf, eps = args.epsilon, at most n_queries forwards per sample).  Returns (x_adv, robust, queries): the inputs
+def Square(model, args, inputs, targets, n_queries=5000, seed=None, norm="Linf"):
+    """One Square attack (norm 'Linf' or 'L2', eps = args.epsilon, at most n_queries forwards per sample).  Returns (x_adv, robust, queries): the inputs
     with every fooled sample (margin z_y - max_{j != y} z_j <= 0 at some query) replaced by its fooling point, the [B] bool flags of the
     samples whose margin stayed positive, and the number of forwards each sample was active for.  `seed` keys the counter-based draws;
     None takes it from torch's generator (torch.manual_seed governs it).  The model runs in the mode the caller left it in; a defence that
     redraws at every forward (Add_Square) makes the margins noisy, and a lucky low margin sticks - what the non-EOT version does."""
+    kw = {} if _check_square_norm(norm) == "Linf" else {"norm": norm}  # a Linf call is the call made before the parameter existed
     x0 = inputs.detach()
     eps = float(args.epsilon)
     if runtime.require_device(x0, "Square"):
-        return engine.square_loop(model, x0, targets, n_queries, eps, seed)
+        return engine.square_loop(model, x0, targets, n_queries, eps, seed, **kw)
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-    x_best, margin_min, queries = _square_host(model, x0, targets, n_queries, eps, seed)
+    x_best, margin_min, queries = _square_host(model, x0, targets, n_queries, eps, seed, **kw)
     robust = margin_min > 0
     return torch.where(robust.view(-1, 1, 1, 1), x0, x_best), robust, queries
 

@@ -341,6 +341,47 @@ int ee_sqatk_margin_f32(const float *logits, const int64_t *labels, int B, int K
 int ee_sqatk_step_f32(float *x_best, float *x_new, const float *x0, const int *flags, const float *margin_min, const int *counter,
                       const int *sizes, int n_sizes, const int64_t *seed, int B, int C, int H, int W, float eps, void *stream);
 
+/* ---- Square attack in the L2 threat model (Andriushchenko et al. 2020, Alg. 3), ee_sqatk_l2.hip ----
+ * The two launches that stand in the place of ee_sqatk_init_f32 / ee_sqatk_step_f32 in an L2 run; ee_sqatk_margin_f32, the counter, the
+ * flags and the query count are shared.  Next to the state above, all in device memory:
+ *   eta      float [sum of s*s]  one [s, s] table per distinct window size of the schedule and one for the start's s0: a piecewise-constant
+ *                                pattern of unit L2 norm, positive on its top s/2 rows and negative below (eeadv.sqatk.eta forms it in
+ *                                float64 and rounds once); the kernels read eta[r][q], or eta[q][r] under a transpose coin
+ *   eta_off  int   [n_sizes]     offset in eta of the table of proposal i (its size is sizes[i])
+ *   norms    float [3 + 2C, B]   n_img, n_un, n_d, n_w[0..C), n_new[0..C) of the last proposal (zeros for a sample that made none)
+ * Draws: window 1 is the Linf window draw (stream 11, ctr = (i << 32) | b: vh, vw from r.x, r.y; bit c of r.z is channel c's sign, bit 0
+ * of r.w the transpose coin); window 2 is the same ctr on stream 13 (vh2, vw2 from r.x, r.y; it may overlap window 1); tile k of the start
+ * is stream 14, ctr = (b << 32) | k (bit c of r.x channel c's sign, bit 0 of r.y the transpose coin).
+ * tiny = 1e-12f; every operation is rounded once in f32; max and clamp propagate NaN.  Each norm is (float) sqrt(S), S the sum of the exact
+ * squares in double in an order fixed by C*H*W and the launch shape (one workgroup of 512 threads per sample).  path: EE_SQATK_L2_PATH_AUTO
+ * picks by size, _RESIDENT keeps a sample in registers across the reductions (C*H*W <= 12288, else EE_ERR_UNSUPPORTED), _STREAMING
+ * re-reads it (any size; no scratch tensor); the two return the same bits.  16-byte accesses when C*H*W % 4 == 0 and x_best, x_new, x0
+ * are 16-byte aligned, element-wise otherwise - the same bits.  eps < 0 or NaN, a path outside the three: EE_ERR_SHAPE; C > 32:
+ * EE_ERR_UNSUPPORTED.  B == 0 launches nothing.  Both record under EE_K_SQATK_INIT / EE_K_SQATK_STEP. */
+#define EE_SQATK_L2_PATH_AUTO 0
+#define EE_SQATK_L2_PATH_RESIDENT 1
+#define EE_SQATK_L2_PATH_STREAMING 2
+
+/* The tiled start.  eta: the [s0, s0] table; nh = H / s0 by nw = W / s0 tiles from ((H - nh s0) / 2, (W - nw s0) / 2) on, tile k = a * nw + b':
+ *     d = +-eta (transposed by the tile's coin) on the tiles, 0 outside;   n0 = ||d||_2;   q = eps / (n0 + tiny)
+ *     x_best = x_new = clamp(x0 + d * q, 0, 1)
+ * s0 outside [1, min(H, W)]: EE_ERR_SHAPE. */
+int ee_sqatk_init_l2_f32(float *x_best, float *x_new, const float *x0, const int64_t *seed, const float *eta, int s0, int B, int C, int H,
+                         int W, float eps, int path, void *stream);
+
+/* Commit and propose, in place.  Per sample: flags[b]: x_best = x_new.  Then, if the sample is not fooled and i = counter[0] is inside
+ * [0, n_sizes): with s = sizes[i] (1 <= s <= min(H, W), else no proposal), W1 / W2 the two windows and delta = x_best - x0,
+ *     n_img = ||delta||_2     n_un = ||delta on W1 u W2||_2 (all channels)     n_w[c] = ||delta[c, W1]||_2
+ *     new[c]   = +-eta + delta[c, W1] / (tiny + n_w[c])                          n_new[c] = ||new[c]||_2
+ *     scale    = sqrt(max(eps * eps - n_img * n_img, 0) / C + n_un * n_un)
+ *     delta[:, W2] = 0;  then  delta[c, W1] = new[c] / (tiny + n_new[c]) * scale  n_d = ||delta||_2
+ *     x_new    = clamp(x0 + delta / (tiny + n_d) * eps, 0, 1)
+ * A fooled sample keeps x_new = x_best; a counter outside the table (or n_sizes = 0: sizes, eta_off and eta then nullable) commits only.
+ * eps = 0 gives x_new = x0; nothing here makes a NaN of finite images. */
+int ee_sqatk_step_l2_f32(float *x_best, float *x_new, const float *x0, const int *flags, const float *margin_min, const int *counter,
+                         const int *sizes, const int *eta_off, const float *eta, int n_sizes, const int64_t *seed, float *norms, int B,
+                         int C, int H, int W, float eps, int path, void *stream);
+
 /* ---- FAB-T (Croce & Hein 2020, "Minimally distorted adversarial examples with a fast adaptive boundary attack"; Linf, targeted, one run,
  * eta = 1.05, beta = 0.9, alpha_max = 0.1 - the constants of AutoAttack's `standard` version), ee_fab.hip ----
  * State of one run on B samples of per_sample elements each, all in device memory:
