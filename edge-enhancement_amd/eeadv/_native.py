@@ -58,6 +58,12 @@ SIGNATURES = {
     "ee_apgd_step_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_f, c_p],
     # x, x_old, g, x0, step, counter, norms, B, per_sample, eps, path, stream
     "ee_apgd_step_l2_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_f, c_i, c_p],
+    # z, u, x0, scal, B, per_sample, eps, path, stream
+    "ee_l1_proj_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_f, c_i, c_p],
+    # x, g, x0, step, topk, scal, B, per_sample, eps, path, stream
+    "ee_apgd_step_l1_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_f, c_i, c_p],
+    # loss, pred, x, x_best, x0, fstate, istate, topk, spstate, counter, sched, n_iter, B, per_sample, eps, stream
+    "ee_apgd_book_l1_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_l, c_f, c_p],
     # logits, labels, targets, B, K, kind, row_loss, dlogits, pred, stream
     "ee_apgd_loss_f32": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     # loss, pred, fstate, istate, counter, sched, n_iter, B, stream

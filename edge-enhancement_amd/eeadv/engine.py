@@ -491,6 +491,195 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
+# APGD in the L1 threat model (Croce & Hein 2021; one run, no momentum, no EOT, no restarts, no large-radius warm-up): a door of its own
+# next to apgd_loop, which keeps refusing norm = "L1" 
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def apgd_l1_schedule(n_iter):
+    """sched[i] = the window length k when a checkpoint closes iteration i (0-based), else 0: the first window is max(int(0.04 n), 1)
+    iterations, every later one max(int(0.06 n), 1) - n = 100 puts checkpoints after iterations 4, 10, 16, ... (counted from 1)."""
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("APGD needs n_iter >= 1")
+    k, k_next = max(int(0.04 * n_iter), 1), max(int(0.06 * n_iter), 1)
+    sched, since = [0] * n_iter, 0
+    for i in range(n_iter):
+        since += 1
+        if since == k:
+            sched[i], since, k = k, 0, k_next
+    return sched
+
+
+class _ApgdL1Spec:
+    """The loss-gradient step of `_body_input_grad` for an L1 run: ee_apgd_loss_f32, then - past the start point - ee_apgd_book_l1_f32."""
+
+    def __init__(self, run):
+        self.kind, self.payload, self.run = "apgd_l1_" + run.loss, run.y, run
+
+    def dlogits(self, logits):
+        r = self.run
+        r.loss_rows, d, r.pred = ops.apgd_loss(logits.detach(), r.y, r.loss, r.t)
+        if r.started:
+            ops.apgd_book_l1_(r.loss_rows, r.pred, r.x.detach(), r.x_best, r.x0, r.fstate, r.istate, r.topk, r.spstate, r.counter, r.sched,
+                              r.eps)
+        return d
+
+
+class _ApgdL1Run:
+    """The device state of one L1-APGD run (include/eeadv.h, "APGD in the L1 threat model") and its two pieces: `start` (the projection of
+    the start point, its forward/backward and the initial state, once per attack) and `iteration` (step, forward, loss, bookkeeping,
+    backward, copies: what a captured graph replays).  No host read anywhere.  `trace` (a list, eager runs only) receives one dict for the
+    start and one per iteration."""
+
+    def __init__(self, x0, y, n_iter, eps, loss, path="auto"):
+        B, dev = x0.shape[0], x0.device
+        self.loss, self.eps, self.n_iter, self.path = loss, float(eps), int(n_iter), path
+        self.per_sample = x0.numel() // B if B else 0
+        self.trace = None
+        self.x = torch.empty_like(x0).requires_grad_(True)
+        self.x0, self.g = torch.empty_like(x0), torch.empty_like(x0)
+        self.x_best, self.g_best, self.x_best_adv = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
+        self.y = torch.empty(B, dtype=torch.int64, device=dev)
+        self.t = torch.empty(B, dtype=torch.int64, device=dev) if loss == "dlr_t" else None
+        self.fstate = torch.empty((4, B), dtype=torch.float32, device=dev)
+        self.istate = torch.empty((4, B), dtype=torch.int32, device=dev)
+        self.topk = torch.empty(B, dtype=torch.float32, device=dev)
+        self.spstate = torch.empty((2, B), dtype=torch.int32, device=dev)
+        self.scal = torch.zeros((ops.L1_SCAL_ROWS, B), dtype=torch.float32, device=dev)
+        self.scal0 = torch.zeros((ops.L1_SCAL_ROWS, B), dtype=torch.float32, device=dev)  # the start projection's
+        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.sched = torch.tensor(apgd_l1_schedule(n_iter), dtype=torch.int32).to(dev)
+        self.loss_rows = self.pred = None
+        self.started = False
+        self.spec = _ApgdL1Spec(self)
+
+    def load(self, x_init, x0, y, targets):
+        with torch.no_grad():
+            self.x.detach().copy_(x_init)
+            self.x0.copy_(x0)
+            self.y.copy_(y)
+            if self.t is not None:
+                self.t.copy_(targets)
+
+    def gradient(self, model):
+        return input_gradient(model, self.x, self.spec).contiguous()
+
+    def _state(self):
+        return dict(step=self.fstate[ops.APGD_F_STEP].clone(), topk=self.topk.clone(), sp_old=self.spstate[0].clone())
+
+    def start(self, model):
+        self.started = False
+        x = self.x.detach()
+        u = x.clone() if self.trace is not None else None
+        ops.l1_proj(x, self.x0, self.eps, out=x, scal=self.scal0, path=self.path)  # x = P(x0 + n): the step's projection, by itself
+        g = self.gradient(model)
+        self.started = True
+        with torch.no_grad():
+            for t in (self.x_best, self.x_best_adv):
+                t.copy_(x)
+            self.g.copy_(g)
+            self.g_best.copy_(g)
+            self.fstate[ops.APGD_F_STEP].fill_(self.eps)
+            self.fstate[ops.APGD_F_LOSS_BEST:].copy_(self.loss_rows.expand(3, -1))
+            self.istate.zero_()
+            self.istate[ops.APGD_I_ROBUST].copy_(self.pred)
+            self.topk.fill_(0.2)
+            self.spstate[0].fill_(self.per_sample)
+            self.spstate[1].zero_()
+            self.counter.zero_()
+        if self.trace is not None:
+            self.trace.append(dict(start=True, u=u, scal=self.scal0.clone(), x=x.clone(), loss=self.loss_rows.clone(), pred=self.pred.clone(),
+                                   g=g.clone(), **self._state()))
+
+    def iteration(self, model, g):
+        """One iteration from the gradient `g` of the current iterate; returns the gradient of the next one (a fresh tensor, restored in
+        place for the samples a checkpoint sent back)."""
+        entry = None
+        if self.trace is not None:
+            entry = dict(step_g=g.clone(), x_in=self.x.detach().clone(), counter=int(self.counter.item()),
+                         **{k + "_in": v for k, v in self._state().items()})
+        ops.apgd_step_l1_(self.x.detach(), g, self.x0, self.fstate[ops.APGD_F_STEP], self.topk, self.eps, self.scal, self.path)
+        if entry is not None:
+            entry.update(scal=self.scal.clone(), x=self.x.detach().clone())
+        g_new = self.gradient(model)
+        if entry is not None:
+            entry.update(loss=self.loss_rows.clone(), pred=self.pred.clone(), g=g_new.clone(), flags=self.istate[ops.APGD_I_FLAGS].clone(),
+                         sp=self.spstate[1].clone(), loss_best=self.fstate[ops.APGD_F_LOSS_BEST].clone(), **self._state())
+        ops.apgd_select_(self.x.detach(), g_new, self.x_best, self.g_best, self.x_best_adv, self.istate[ops.APGD_I_FLAGS], self.counter)
+        if entry is not None:
+            entry.update(x_out=self.x.detach().clone(), g_out=g_new.clone(), x_best=self.x_best.clone(), x_best_adv=self.x_best_adv.clone())
+            self.trace.append(entry)
+        return g_new
+
+    def result(self):
+        with torch.no_grad():
+            robust = self.istate[ops.APGD_I_ROBUST] != 0
+            return _adv_where_fooled(robust, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
+
+
+def apgd_l1_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, trace=None, path="auto"):
+    """One L1-APGD run of n_iter iterations inside {z : ||z - x0||_1 <= eps} n [0,1]^D, on loss 'ce', 'dlr' or 'dlr_t' (which takes
+    `targets`).  x_init is the unprojected start x0 + n: the run starts at P(x_init), the exact projection (ee_l1_proj_f32).  An
+    iteration is ee_apgd_step_l1_f32 -> forward -> ee_apgd_loss_f32 -> ee_apgd_book_l1_f32 -> backward -> ee_apgd_select_f32 on the
+    schedule apgd_l1_schedule(n_iter); step starts at eps, topk at 0.2, sp_old at the per-sample size.  Returns
+    (x_adv, robust, loss_best) as apgd_loop does.  The model's mode is left as the caller set it.  Eager, or - under EEADV_GRAPH=1 /
+    use_graph - replayed from a captured graph of up to MAX_ITERS_PER_GRAPH iterations; both give the same bits.  `path` picks the
+    kernels' path ('auto', 'resident', 'streaming'; the same bits).  `trace` (a list, eager only) receives the start's dict {"start", "u",
+    "scal", "x", "loss", "pred", "g", "step", "topk", "sp_old"} and, per iteration, {"step_g", "x_in", "counter", "step_in", "topk_in",
+    "sp_old_in", "scal", "x", "loss", "pred", "g", "flags", "sp", "loss_best", "step", "topk", "sp_old", "x_out", "g_out", "x_best",
+    "x_best_adv"}: what the step read and wrote, what the bookkeeping decided, and the state after the copies."""
+    if loss not in ops.APGD_KINDS:
+        raise ValueError("APGD loss must be one of %s, got %r" % (sorted(ops.APGD_KINDS), loss))
+    if loss == "dlr_t" and targets is None:
+        raise ValueError("the targeted DLR loss needs targets")
+    if path not in ops.APGD_L1_PATHS:
+        raise ValueError("the L1 kernels' path must be one of %s, got %r" % (sorted(ops.APGD_L1_PATHS), path))
+    if not float(eps) >= 0.0:
+        raise ValueError("L1-APGD needs eps >= 0, got %r" % (eps,))
+    model = _unwrap(model)
+    x0 = x0.detach().contiguous()
+    x_init = x_init.detach().contiguous()
+    n_iter = int(n_iter)
+    apgd_l1_schedule(n_iter)
+    if x0.shape[0] == 0:
+        return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=torch.float32, device=x0.device)
+    if use_graph is None:
+        use_graph = graphs_enabled() and trace is None
+    if use_graph and trace is not None:
+        raise ValueError("the APGD trace is recorded by eager runs only")
+    if not use_graph:
+        run = _ApgdL1Run(x0, y, n_iter, eps, loss, path)
+        run.trace = trace
+        run.load(x_init, x0, y, targets)
+        run.start(model)
+        g = run.g
+        for _ in range(n_iter):
+            g = run.iteration(model, g)
+        return run.result()
+    chunk = _chunk(n_iter)
+    key = ("apgd_l1", id(model), model.training, tuple(x0.shape), loss, n_iter, float(eps), x0.device.index, chunk, path)
+
+    def build():
+        run = _ApgdL1Run(x0, y, n_iter, eps, loss, path)
+        run.load(x_init, x0, y, targets)
+
+        def body(model):  # the gradient enters through run.g and leaves through it (one copy per replay), as in apgd_loop
+            g = run.g
+            for _ in range(chunk):
+                g = run.iteration(model, g)
+            run.g.copy_(g)
+
+        return _Captured(model, x0.device, chunk, run).capture(model, body, start=lambda: run.start(model))
+
+    gs = _cached(key, model, build)
+    gs.run.load(x_init, x0, y, targets)
+    refresh_dense_weights()
+    gs.run.start(model)
+    for _ in range(n_iter // gs.iters):
+        gs.graph.replay()
+    return gs.run.result()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
 # Square attack (Andriushchenko et al. 2020; Linf or L2, margin loss, p_init = 0.8 with the rescaled schedule, one run, no EOT): DESIGN.md
 # sections 12 and 18
 # ---------------------------------------------------------------------------------------------------------------------------------------

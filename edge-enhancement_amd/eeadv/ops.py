@@ -491,6 +491,67 @@ def apgd_select_(x, g, x_best, g_best, x_best_adv, flags, counter):
     return x
 
 
+# ---- APGD in the L1 threat model (ee_apgd_l1.hip) --------------------------------------------------------------------
+APGD_L1_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_APGD_L1_PATH_*
+APGD_L1_RESIDENT = 12288  # per-sample size up to which the resident path exists
+L1_S_LAMBDA, L1_S_H0, L1_S_ACTIVE, L1_S_DIST, L1_S_TAU, L1_S_M, L1_S_J = range(7)  # rows of scal
+L1_SCAL_ROWS = 7
+
+
+def _l1_path(path):
+    if path not in APGD_L1_PATHS:
+        raise ValueError("the L1 kernels' path must be one of %s, got %r" % (sorted(APGD_L1_PATHS), path))
+    return APGD_L1_PATHS[path]
+
+
+def _l1_scal(scal, x):
+    B = x.shape[0]
+    scal = torch.zeros((L1_SCAL_ROWS, B), dtype=torch.float32, device=x.device) if scal is None else scal
+    return scal, _chk(scal, torch.float32, "scal", (L1_SCAL_ROWS, B))
+
+
+def l1_proj(u, x0, eps, out=None, scal=None, path="auto"):
+    """P(u): the Euclidean projection of u [B, ...] onto the L1 ball of radius eps around x0 intersected with [0,1]^D, per sample.
+    Returns (z, scal): z is `out` when given (it may be u itself), scal [7, B] has rows L1_S_LAMBDA, _H0, _ACTIVE, _DIST written."""
+    B = u.shape[0]
+    out = torch.empty_like(u) if out is None else out
+    pu = _chk(u, torch.float32, "u")
+    pz = _chk(out, torch.float32, "out", u.shape)
+    p0 = _chk(x0, torch.float32, "x0", u.shape)
+    scal, ps = _l1_scal(scal, u)
+    N.check(N.lib.ee_l1_proj_f32(pz, pu, p0, ps, B, u.numel() // B if B else 0, eps, _l1_path(path), _stream()), "ee_l1_proj_f32")
+    return out, scal
+
+
+def apgd_step_l1_(x, g, x0, step, topk, eps, scal=None, path="auto"):
+    """The step of an L1 run in place on x [B, ...]: selection, sparse sign step, projection; step, topk [B] float32.  Returns scal
+    [7, B] (rows L1_S_*), written into `scal` when given.  path: 'auto', 'resident' (per-sample size <= 12288) or 'streaming'."""
+    B = x.shape[0]
+    px = _chk(x, torch.float32, "x")
+    pg = _chk(g, torch.float32, "g", x.shape)
+    p0 = _chk(x0, torch.float32, "x0", x.shape)
+    pst = _chk(step, torch.float32, "step", (B,))
+    pt = _chk(topk, torch.float32, "topk", (B,))
+    scal, ps = _l1_scal(scal, x)
+    N.check(N.lib.ee_apgd_step_l1_f32(px, pg, p0, pst, pt, ps, B, x.numel() // B if B else 0, eps, _l1_path(path), _stream()),
+            "ee_apgd_step_l1_f32")
+    return scal
+
+
+def apgd_book_l1_(loss, pred, x, x_best, x0, fstate, istate, topk, spstate, counter, sched, eps):
+    """One iteration's bookkeeping of an L1 run in place on fstate [4,B] / istate [4,B] (the APGD run's), topk [B] float32 and spstate
+    [2,B] int32 (sp_old, the last count); the flags row of istate is the result."""
+    B = loss.shape[0]
+    px = _chk(x, torch.float32, "x")
+    N.check(N.lib.ee_apgd_book_l1_f32(_chk(loss, torch.float32, "loss", (B,)), _chk(pred, torch.int32, "pred", (B,)), px,
+                                      _chk(x_best, torch.float32, "x_best", x.shape), _chk(x0, torch.float32, "x0", x.shape),
+                                      _chk(fstate, torch.float32, "fstate", (4, B)), _chk(istate, torch.int32, "istate", (4, B)),
+                                      _chk(topk, torch.float32, "topk", (B,)), _chk(spstate, torch.int32, "spstate", (2, B)),
+                                      _chk(counter, torch.int32, "counter", (1,)), _chk(sched, torch.int32, "sched"), sched.numel(), B,
+                                      x.numel() // B if B else 0, eps, _stream()), "ee_apgd_book_l1_f32")
+    return istate[APGD_I_FLAGS]
+
+
 # ---- EOT for APGD (ee_eot.hip) ---------------------------------------------------------------------------------------
 def apgd_eot_acc_(g_acc, g, loss_acc, loss, loss_mean, k, E):
     """Draw k of E in place: g_acc [B, ...] takes g (k == 0) or g_acc + g, and * (1/E) after the last draw; loss_acc [B] float64 takes the

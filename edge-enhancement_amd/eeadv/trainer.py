@@ -698,8 +698,11 @@ def norm_for(args):
 
 
 def norm_tag(args):
-    """What a validation log line carries after its numbers: nothing for Linf (the lines stay as they were), ' [norm L2]' for L2."""
-    return '' if norm_for(args) == 'Linf' else ' [norm L2]'
+    """What a validation log line carries after its numbers: nothing for Linf (the lines stay as they were), ' [norm L2]' for L2, and
+    ' [norm L1]' for the L1 methods, whose threat model is in their name (--norm stays refused with them, by norm_for)."""
+    if norm_for(args) == 'Linf':
+        return ' [norm L1]' if args.attack_method in L1_METHODS else ''
+    return ' [norm L2]'
 
 
 def attack_for_validation(model, args, input, target, device, num_steps, step_size, n_class):
@@ -733,6 +736,20 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', eot_iter=eot_iter, **nkw)
         if args.attack_method in ('APGD-T', 'APGD'):
             xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class, **nkw)
+            if x_adv is None:
+                return xt
+            x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
+        return x_adv
+    if args.attack_method in L1_METHODS:
+        # APGD in the L1 threat model, radius args.epsilon: CE, T on the DLR loss, or CE then T with the flags ANDed and
+        # the first fooling point kept.  The methods carry their norm in the name; eot_iter_for and norm_for have refused --eot_iter / --norm.
+        if targeted:
+            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+        x_adv, robust = None, None
+        if args.attack_method in ('APGD-L1-CE', 'APGD-L1'):
+            x_adv, robust = A.APGD_L1(model, args, input, target, num_steps, 'ce')
+        if args.attack_method in ('APGD-L1-T', 'APGD-L1'):
+            xt, rt = A.APGD_T_L1(model, args, input, target, num_steps, n_class)
             if x_adv is None:
                 return xt
             x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
@@ -797,7 +814,8 @@ CASCADE_METHOD = 'Cascade'  # the same four attacks, each on the samples the one
 CASCADE_METHODS = (CASCADE_METHOD, CASCADE_RAND_METHOD)
 L2_METHODS = APGD_METHODS + RAND_METHODS + (CASCADE_RAND_METHOD,)  # every attack in them is an APGD run: --norm L2
 # what the AWP drivers validate with next to PGD
-EVAL_METHODS = APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS
+L1_METHODS = ('APGD-L1-CE', 'APGD-L1-T', 'APGD-L1')  # L1-APGD through doors of their own; not in L2_METHODS
+EVAL_METHODS = APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS + L1_METHODS
 
 
 def validate_batch(model, criterion, args, input, target, device, num_steps, step_size, n_class):

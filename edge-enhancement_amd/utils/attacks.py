@@ -322,6 +322,179 @@ def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None,
     return x_adv, robust & rd
 
 
+# ---------------------------------------------------------------------------------------------------------
+# APGD in the L1 threat model (Croce & Hein 2021, "Mind the box"): doors of their own - APGD(norm="L1") stays refused.  One run, no
+# momentum, the sparse sign step, the exact projection onto ball and box, the sparsity / step-size checkpoints.
+# The large-radius warm-up, restarts, EOT, L1 FAB-T / Square and L1 inside Cascade / Rand are NOT here.
+# ---------------------------------------------------------------------------------------------------------
+def _f32c(v, dtype):
+    """The float32 constant v in `dtype`: the constants of the L1 run are float32 ones in every dtype."""
+    return torch.tensor(v, dtype=torch.float32).to(dtype)
+
+
+def _l1_multiplier(a, lo, eps):
+    """lambda of one sample as a Python float: a, lo 1-D float64 tensors (finite, 0 <= lo <= a).  The segment is located on sorted
+    breakpoints with cumulative sums, confirmed with exactly summed h (math.fsum), and solved with an exactly summed numerator."""
+    import math
+
+    def h(t):
+        return math.fsum(a.tolist() + (-torch.minimum(torch.clamp(lo, min=t), a)).tolist())
+
+    if h(0.0) <= eps:
+        return 0.0
+    bp = torch.unique(torch.cat([lo, a, a.new_zeros(1)]))  # sorted
+    a_s, lo_s = torch.sort(a)[0], torch.sort(lo)[0]
+    ca, cl = torch.cat([a.new_zeros(1), torch.cumsum(a_s, 0)]), torch.cat([a.new_zeros(1), torch.cumsum(lo_s, 0)])
+    na = torch.searchsorted(a_s, bp, right=True)    # a_i <= t
+    nl = torch.searchsorted(lo_s, bp, right=True)   # lo_i <= t
+    cut = ca[na] + (cl[-1] - cl[nl]) + bp * (nl - na).to(bp.dtype)
+    above = (ca[-1] - cut) > eps
+    k = int(above.nonzero().max()) if bool(above.any()) else 0
+    while k + 1 < bp.numel() - 1 and h(float(bp[k + 1])) > eps:  # the cumulative sums round: settle the segment exactly
+        k += 1
+    while k > 0 and not h(float(bp[k])) > eps:
+        k -= 1
+    t = float(bp[k])
+    act, fixed = (lo <= t) & (a > t), (lo > t) & (a > t)
+    n = int(act.sum())
+    if n == 0:
+        return float(bp[k + 1])
+    return math.fsum(a[fixed].tolist() + (-lo[fixed]).tolist() + a[act].tolist() + [-float(eps)]) / n
+
+
+def _l1_project(u, x0, eps):
+    """P(u): the Euclidean projection onto {z : ||z - x0||_1 <= eps} n [0,1]^D per sample, in u's dtype, as csrc/ee_apgd_l1.hip states it.
+    Returns (z, lam [B]).  A sample whose u - x0 is not finite is returned as x0."""
+    B = u.shape[0]
+    w = (u - x0).reshape(B, -1)
+    uf, cf = u.reshape(B, -1), x0.reshape(B, -1)
+    a = w.abs()
+    lo = torch.minimum(torch.clamp(-torch.minimum(1 - uf, uf), min=0), a)
+    bad = ~torch.isfinite(w).all(dim=1)
+    lam = torch.zeros(B, dtype=u.dtype)
+    for b in range(B):
+        if not bool(bad[b]):
+            lam[b] = _l1_multiplier(a[b].to(torch.float64), lo[b].to(torch.float64), float(eps))
+    cut = torch.minimum(torch.maximum(lam.view(-1, 1), lo), a)
+    z = torch.clamp(cf + torch.sign(w) * (a - cut), 0, 1)
+    z = torch.where(bad.view(-1, 1), cf, z)
+    return z.reshape(u.shape), lam
+
+
+def _l1_step(x, g, x0, step, topk, eps):
+    """The sparse sign step and the projection of an L1 run in torch ops, in x's dtype.  Returns (x_new, info)."""
+    B = x.shape[0]
+    D = x[0].numel()
+    dt = x.dtype
+    gf, xf = g.reshape(B, -1), x.reshape(B, -1)
+    v = torch.floor((1 - topk) * D)
+    j = torch.where(v >= 0, torch.clamp(v, max=D - 1), torch.zeros_like(v)).to(torch.int64)  # a NaN selects 0
+    ab = gf.abs()
+    bits = ab.view(torch.int32 if dt == torch.float32 else torch.int64)  # non-negative patterns: the integer order is the kernel's
+    tau_bits = torch.sort(bits, dim=1)[0].gather(1, j.view(-1, 1))
+    mask = bits >= tau_bits
+    s = torch.sign(torch.nan_to_num(gf, nan=0.0))
+    m = (mask & (s != 0)).sum(dim=1)
+    sg = step / (m.to(dt) + _f32c(1e-10, dt))
+    finite = torch.isfinite(gf).all(dim=1)
+    u = torch.where(mask & (s != 0) & finite.view(-1, 1), xf + sg.view(-1, 1) * s, xf)
+    z, lam = _l1_project(u.reshape(x.shape), x0, eps)
+    return z, dict(j=j, tau=tau_bits.view(dt).reshape(B), m=m, lam=lam, u=u.reshape(x.shape))
+
+
+def _apgd_l1_host(model, x0, x_init, y, n_iter, eps, loss, t=None, trace=None):
+    """Plumbing path for CPU tensors (opt-in): the iteration of engine.apgd_l1_loop in plain torch ops, in the input's dtype, with
+    sort-based selection and projection.  x_init is the unprojected start x0 + n.  `trace`, a list, receives one dict of clones per
+    iteration (the start point first)."""
+    if loss not in ops.APGD_KINDS:
+        raise ValueError("APGD loss must be one of %s, got %r" % (sorted(ops.APGD_KINDS), loss))
+    sched = engine.apgd_l1_schedule(n_iter)
+    dt = x0.dtype
+    B, D = x0.shape[0], x0[0].numel()
+    shape = (-1,) + (1,) * (x0.dim() - 1)
+
+    def grad_at(xc):
+        xc = xc.detach().requires_grad_()
+        with torch.enable_grad():
+            z = model(xc)
+            rows = _apgd_row_losses(z, y, loss, t)
+        g = torch.autograd.grad(rows.sum(), [xc])[0]
+        first = torch.sort(z.detach(), dim=1, descending=True, stable=True)[1][:, 0]
+        return rows.detach(), g.detach(), first == y
+
+    radius = torch.tensor(eps, dtype=dt)
+    x, lam0 = _l1_project(x_init.detach(), x0, eps)
+    l, g, pred = grad_at(x)
+    step = torch.full_like(l, eps)
+    topk = torch.full_like(l, 1.0) * _f32c(0.2, dt)
+    sp_old = torch.full((B,), D, dtype=torch.int64)
+    loss_best, robust = l.clone(), pred.clone()
+    x_best, x_best_adv, g_best = x.clone(), x.clone(), g.clone()
+
+    def note(**kw):
+        if trace is not None:
+            kw.update(x=x, g=g, loss=l, pred=pred, step=step, topk=topk, sp_old=sp_old, loss_best=loss_best, robust=robust, x_best=x_best,
+                      g_best=g_best, x_best_adv=x_best_adv)
+            trace.append({k: v.clone() for k, v in kw.items()})
+    note(lam=lam0)
+    for i in range(n_iter):
+        x, info = _l1_step(x, g, x0, step, topk, eps)
+        l, g, pred = grad_at(x)
+        x_new, g_new = x, g
+        fooled = ~pred
+        robust = robust & pred
+        x_best_adv = torch.where(fooled.view(shape), x, x_best_adv)
+        improved = l > loss_best
+        loss_best = torch.where(improved, l, loss_best)
+        x_best = torch.where(improved.view(shape), x, x_best)
+        g_best = torch.where(improved.view(shape), g, g_best)
+        reduced = torch.zeros_like(pred)
+        sp = torch.zeros_like(sp_old)
+        if sched[i]:
+            sp = (x_best != x0).reshape(B, -1).sum(dim=1)
+            reduced = (sp.to(dt) / sp_old.to(dt)) < _f32c(0.95, dt)
+            topk = sp.to(dt) / torch.tensor(D, dtype=dt) / _f32c(1.5, dt)
+            step = torch.minimum(torch.maximum(torch.where(reduced, radius, step / _f32c(1.5, dt)), radius / _f32c(10.0, dt)), radius)
+            sp_old = sp
+            x = torch.where(reduced.view(shape), x_best, x)
+            g = torch.where(reduced.view(shape), g_best, g)
+        note(improved=improved, fooled=fooled, reduced=reduced, sp=sp, x_new=x_new, g_new=g_new, **info)
+    return torch.where(robust.view(shape), x0, x_best_adv), robust, loss_best
+
+
+def APGD_L1(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None):
+    """One APGD run in the L1 threat model (radius args.epsilon, num_steps iterations) on loss 'ce', 'dlr' or 'dlr_t' (targeted at
+    `y_target`).  Returns (x_adv, robust) as APGD does.  The start is P(x0 + n), n a standard normal draw per element (`noise=` injects n)
+    and P the exact projection onto the L1 ball intersected with the box; the step is the sparse sign step followed by P; the
+    checkpoints adapt a per-sample sparsity and step size.  The public ensemble's large-radius warm-up
+    (3 eps -> 2 eps -> eps), restarts and EOT are not built."""
+    x0 = inputs.detach()
+    eps = float(args.epsilon)
+    n = torch.randn_like(x0) if noise is None else noise.to(x0.device, x0.dtype)
+    x_init = x0 + n
+    if runtime.require_device(x0, "APGD_L1"):
+        x_adv, robust, _ = engine.apgd_l1_loop(model, x0, x_init, targets, num_steps, eps, loss, y_target)
+    else:
+        x_adv, robust, _ = _apgd_l1_host(model, x0, x_init, targets, num_steps, eps, loss, y_target)
+    return x_adv, robust
+
+
+def APGD_T_L1(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None, order=None):
+    """Targeted L1-APGD on the DLR loss: one run per target class as APGD_T takes them, each on the whole batch; the flags are ANDed over
+    the runs and, per sample, the first fooling point is kept."""
+    x0 = inputs.detach()
+    n_t = min(int(n_target_classes), int(nclass) - 1)
+    order = _class_order(model, x0, n_t, "APGD_T_L1", order)
+    x_adv = x0.clone()
+    robust = torch.ones(x0.shape[0], dtype=torch.bool, device=x0.device)
+    shape = (-1,) + (1,) * (x0.dim() - 1)
+    for j in range(1, n_t + 1):
+        xa, rb = APGD_L1(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise)
+        x_adv = torch.where((robust & ~rb).view(shape), xa, x_adv)
+        robust = robust & rb
+    return x_adv, robust
+
+
 def _class_order(model, x0, n_t, what, order=None):
     """The first n_t + 1 classes of the clean logits [B, n_t + 1] int64, by value descending, ties to the lower index; `order`, the same thing
     computed by the caller (the cascade takes it from its own clean forward), is checked and returned without a forward."""

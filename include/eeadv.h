@@ -289,6 +289,59 @@ int ee_apgd_book_f32(const float *loss, const int *pred, float *fstate, int *ist
 int ee_apgd_select_f32(float *x, float *g, float *x_best, float *g_best, float *x_best_adv, const int *flags, int *counter, int B,
                        int64_t per_sample, void *stream);
 
+/* ---- APGD in the L1 threat model (Croce & Hein 2021, "Mind the box"; one run, no momentum, no EOT), ee_apgd_l1.hip ----
+ * State next to the APGD run's (x, x0, g, x_best, g_best, x_best_adv, fstate rows EE_APGD_F_STEP / _LOSS_BEST, istate rows
+ * EE_APGD_I_ROBUST / _FLAGS, counter, sched), all in device memory:
+ *   topk    float [B]   : the share of coordinates the next step moves (starts at 0.2f)
+ *   spstate int   [2, B]: row 0 sp_old, the nonzero count of x_best - x0 at the last checkpoint (starts at per_sample); row 1 the count
+ *                         the last checkpoint took (for traces and tests)
+ *   scal    float [EE_L1_SCAL_ROWS, B]: rows EE_L1_S_*, written by the projection (rows 0-3) and the step (all rows); counts are stored
+ *                         as float values, exact below 2^24
+ * An iteration is step_l1 -> classifier forward -> ee_apgd_loss_f32 -> book_l1 -> classifier backward -> ee_apgd_select_f32.
+ * One workgroup of 512 threads per sample in all three launches. */
+#define EE_APGD_L1_PATH_AUTO 0
+#define EE_APGD_L1_PATH_RESIDENT 1  /* a sample stays in registers across all passes; per_sample > 12288: EE_ERR_UNSUPPORTED */
+#define EE_APGD_L1_PATH_STREAMING 2 /* every pass re-reads its inputs; any per_sample, no scratch tensor; the same bits */
+#define EE_L1_S_LAMBDA 0 /* the multiplier of the projection (0: the ball is inactive) */
+#define EE_L1_S_H0 1     /* h(0) = sum_i (|w_i| - lo_i) as a float; +inf for a sample written as x0 */
+#define EE_L1_S_ACTIVE 2 /* |A|, the coordinates strictly between their breakpoints on lambda's segment */
+#define EE_L1_S_DIST 3   /* ||z - x0||_1 of what was written (summed in double) */
+#define EE_L1_S_TAU 4    /* the step only: the threshold on |g| */
+#define EE_L1_S_M 5      /*                the number of coordinates that moved */
+#define EE_L1_S_J 6      /*                the rank of tau */
+#define EE_L1_SCAL_ROWS 7
+
+/* z = P(u), the Euclidean projection of u onto {z : ||z - x0||_1 <= eps} n [0,1]^D, per sample.  Per coordinate w = u - x0, a = |w|,
+ * lo = min(max(0, -min(1 - u, u)), a) (how far u lies outside the box), every f32 operation rounded once:
+ *     z = clamp(x0 + sign(w) * (a - min(max(lambda, lo), a)), 0, 1)
+ * lambda = 0 when h(0) <= eps, else the root of h(lambda) = sum_i (a_i - min(max(lambda, lo_i), a_i)) = eps: T, the largest float with
+ * h(T) > eps, comes from 31 steps over the bit pattern of non-negative floats; on (T, T+] (T+ the next float) the root is
+ * (sum_{lo_i > T} (a_i - lo_i) + sum_{lo_i <= T < a_i} a_i - eps) / |A|, rounded to float and kept inside [T, T+]; |A| = 0 takes T+.
+ * All sums in double in an order fixed by per_sample and the launch shape.  eps = 0 returns x0 exactly.  A sample whose u - x0 holds a
+ * NaN or an Inf is written as x0 (lambda 0, h0 +inf).  x0 outside [0,1] is outside the contract and only loses optimality.  z may be u.
+ * scal [>= 4, B] receives rows EE_L1_S_LAMBDA .. _DIST.  Paths, 16-byte accesses and error codes as ee_apgd_step_l2_f32; per_sample above
+ * INT32_MAX - 2048 is EE_ERR_SHAPE in the three L1 entry points (a pass counts the padded slots of its last float4 group in an int). */
+int ee_l1_proj_f32(float *z, const float *u, const float *x0, float *scal, int64_t B, int64_t per_sample, float eps, int path, void *stream);
+
+/* The step of an L1 run, in place on x: selection, sparse sign step and projection in one launch.  Per sample, D = per_sample:
+ *     j   = clamp((int) floorf((1.0f - topk[b]) * (float) D), 0, D - 1)     tau = the j-th smallest |g_i| (0-based, by bit pattern)
+ *     m   = #{i : |g_i| >= tau, g_i < 0 or g_i > 0}                         sg  = step[b] / ((float) m + 1e-10f)
+ *     u_i = x_i + sg * sign(g_i) where |g_i| >= tau and g_i != 0, else x_i;     x = P(u) as ee_l1_proj_f32
+ * Ties at tau all move.  A gradient that holds a NaN or an Inf takes no gradient step (u = x); the projection still runs.
+ * scal [EE_L1_SCAL_ROWS, B] receives every row. */
+int ee_apgd_step_l1_f32(float *x, const float *g, const float *x0, const float *step, const float *topk, float *scal, int64_t B,
+                        int64_t per_sample, float eps, int path, void *stream);
+
+/* The per-sample bookkeeping of one iteration of an L1 run, with k = sched[counter[0]] (a counter outside [0, n_iter) is no checkpoint):
+ *     robust &= pred;  fooled = !pred;  improved = loss > loss_best -> loss_best = loss
+ *     if k > 0:  sp = #{i : v_i != x0_i}, v = improved ? x : x_best;   reduced = ((float) sp / (float) sp_old) < 0.95f
+ *                topk = (float) sp / (float) D / 1.5f;   step = clamp(reduced ? eps : step / 1.5f, eps / 10.0f, eps);   sp_old = sp
+ * and writes the three decisions to the flags row of istate (EE_APGD_IMPROVED / _FOOLED / _REDUCED: what ee_apgd_select_f32 reads).
+ * fstate [4, B] / istate [4, B] are the APGD run's; only the rows named above are touched. */
+int ee_apgd_book_l1_f32(const float *loss, const int *pred, const float *x, const float *x_best, const float *x0, float *fstate,
+                        int *istate, float *topk, int *spstate, const int *counter, const int *sched, int n_iter, int64_t B,
+                        int64_t per_sample, float eps, void *stream);
+
 /* ---- EOT for APGD (the `rand` version of the public ensemble: each gradient is the mean over E forwards of a randomised defence), ee_eot.hip ----
  * State next to the APGD run's, all in device memory:
  *   g_acc     float  [B, per_sample]  the sum, then the mean, of the E input gradients of one iterate
