@@ -17,87 +17,19 @@
 // - the segment solve of the sort-based formulation, not a bisection stopped at a tolerance; |A| = 0 takes T+.  tau comes from the same kind
 // of search on integers: the largest pattern T with #{|g_i| < T} <= j.
 //
-// One workgroup of 512 threads per sample in all three launches, so no launch writes a per-sample scalar that another workgroup of that
-// launch reads.  Counts are integer sums, real sums are double (differences of two floats are exact there) in one fixed order - thread t
-// takes the float4 groups t, t + 512, ... in turn, wavefronts are reduced by xor-shuffles, the eight partial sums are added in index order -
-// which the resident path (a sample stays in registers across all passes, per_sample <= 12288) and the streaming path (every pass re-reads
-// its inputs and recomputes u from tau and sg; no scratch tensor) share, so the two return the same bits.  Every loop has a trip count
-// fixed by per_sample and the launch shape; the branches around the searches are taken on values the whole workgroup holds alike.
+// One workgroup per sample in all three launches, so no launch writes a per-sample scalar that another workgroup of that launch reads.
+// Counts are integer sums, real sums are double (differences of two floats are exact there) in the one order of ee_sample.hpp, which the
+// resident path (a sample stays in registers across all passes) and the streaming path (every pass re-reads its inputs and recomputes u
+// from tau and sg) share, so the two return the same bits.  Every loop has a trip count fixed by per_sample and the launch shape; the
+// branches around the searches are taken on values the whole workgroup holds alike.
 // The output is written in the final pass only, each element by the thread that read it.
 #include <math.h>
 
-#include "ee_rows.hpp"
+#include "ee_sample.hpp"
 
 namespace {
 
 using namespace ee;
-
-constexpr int kL1Block = 512;                            // 8 wavefronts per sample
-constexpr int kL1Waves = kL1Block / kWave;
-constexpr int kL1Vecs = 6;                               // float4 groups per thread the resident path keeps
-constexpr int kL1Resident = kL1Block * kL1Vecs * 4;      // 12288 = 3*64*64
-constexpr int kL1Slots = kL1Block * 4;                   // elements one float4 group per thread covers
-
-// (a name of its own: an overload here would hide ee::wave_sum(double) from this namespace)
-__device__ __forceinline__ int wave_count(int v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
-// sums over the workgroup; consecutive reductions of a type alternate halves of its buffer, so one barrier per reduction is enough
-struct L1Reducer {
-    double *shd;  // [2][kL1Waves]
-    int *shi;     // [2][kL1Waves]
-    int pd, pi;
-    __device__ __forceinline__ double sum(double v) {
-        v = ee::wave_sum(v);
-        double *buf = shd + pd * kL1Waves;
-        pd ^= 1;
-        if ((threadIdx.x & (kWave - 1)) == 0) buf[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double r = buf[0];
-#pragma unroll
-        for (int i = 1; i < kL1Waves; ++i) r += buf[i];
-        return r;
-    }
-    __device__ __forceinline__ int sum(int v) {
-        v = wave_count(v);
-        int *buf = shi + pi * kL1Waves;
-        pi ^= 1;
-        if ((threadIdx.x & (kWave - 1)) == 0) buf[threadIdx.x >> 6] = v;
-        __syncthreads();
-        int r = buf[0];
-#pragma unroll
-        for (int i = 1; i < kL1Waves; ++i) r += buf[i];
-        return r;
-    }
-};
-
-// four consecutive elements of a row from element e on; elements at or past D read as 0
-template <bool VEC>
-__device__ __forceinline__ void load4(const float *row, int64_t e, int64_t D, float (&o)[4]) {
-    if (VEC && e + 3 < D) {
-        const float4 v = *reinterpret_cast<const float4 *>(row + e);
-        o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = e + j < D ? row[e + j] : 0.0f;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store4(float *row, int64_t e, int64_t D, const float (&v)[4]) {
-    if (VEC && e + 3 < D) {
-        *reinterpret_cast<float4 *>(row + e) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (e + j < D) row[e + j] = v[j];
-    }
-}
-
-__device__ __forceinline__ int64_t group_element(int g) { return (static_cast<int64_t>(g) * kL1Block + threadIdx.x) * 4; }
 
 __device__ __forceinline__ uint32_t abs_bits(float g) { return __float_as_uint(g) & 0x7FFFFFFFu; }
 
@@ -126,10 +58,10 @@ struct L1Coord {
 
 // the gradient of every element of the thread, in the same order on both paths (zeros past D)
 template <bool RES, bool VEC, class F>
-__device__ __forceinline__ void each_g(const float *gr, int64_t D, int groups, const float (&rg)[kL1Vecs * 4], F body) {
+__device__ __forceinline__ void each_g(const float *gr, int64_t D, int groups, const float (&rg)[kSampleElems], F body) {
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL1Vecs * 4; ++k) body(rg[k]);
+        for (int k = 0; k < kSampleElems; ++k) body(rg[k]);
     } else {
         for (int g = 0; g < groups; ++g) {
             float gv[4];
@@ -144,11 +76,11 @@ __device__ __forceinline__ void each_g(const float *gr, int64_t D, int groups, c
 // live in rw / rl / rc.  Otherwise every pass re-reads its rows; a step launch (STEP) recomputes u from x and g.
 template <bool RES, bool VEC, bool STEP, class F>
 __device__ __forceinline__ void each_c(const float *ur, const float *gr, const float *cr, int64_t D, int groups, const L1StepOp &op,
-                                       const float (&rw)[kL1Vecs * 4], const float (&rl)[kL1Vecs * 4], const float (&rc)[kL1Vecs * 4],
+                                       const float (&rw)[kSampleElems], const float (&rl)[kSampleElems], const float (&rc)[kSampleElems],
                                        F body) {
     if (RES) {
 #pragma unroll
-        for (int g = 0; g < kL1Vecs; ++g) {
+        for (int g = 0; g < kSampleVecs; ++g) {
             float wv[4] = {rw[g * 4], rw[g * 4 + 1], rw[g * 4 + 2], rw[g * 4 + 3]};
             float lv[4] = {rl[g * 4], rl[g * 4 + 1], rl[g * 4 + 2], rl[g * 4 + 3]};
             const float cv[4] = {rc[g * 4], rc[g * 4 + 1], rc[g * 4 + 2], rc[g * 4 + 3]};
@@ -183,22 +115,22 @@ __device__ __forceinline__ void each_c(const float *ur, const float *gr, const f
 
 // STEP: z == u_in is x (in place), g the gradient; scal [7, B].  Otherwise the projection alone: u_in -> z, g unused; scal [4, B].
 template <bool RES, bool VEC, bool STEP>
-__global__ __launch_bounds__(kL1Block) void l1_kernel(float *z, const float *u_in, const float *g, const float *x0, const float *step,
+__global__ __launch_bounds__(kSampleBlock) void l1_kernel(float *z, const float *u_in, const float *g, const float *x0, const float *step,
                                                       const float *topk, float *scal, int64_t B, int64_t D, float eps) {
-    __shared__ double shd[2 * kL1Waves];
-    __shared__ int shi[2 * kL1Waves];
-    L1Reducer red{shd, shi, 0, 0};
+    __shared__ double shd[2 * kSampleWaves];
+    __shared__ int shi[2 * kSampleWaves];
+    SampleReducer red{shd, shi};
     const int64_t b = blockIdx.x;
     float *zr = z + b * D;
     const float *ur = u_in + b * D, *cr = x0 + b * D;
     const float *gr = STEP ? g + b * D : nullptr;
-    const int groups = static_cast<int>((D + kL1Slots - 1) / kL1Slots);  // float4 groups per thread; <= kL1Vecs when RES
-    const int64_t pad = static_cast<int64_t>(RES ? kL1Vecs : groups) * kL1Slots - D;  // slots past D: they read as zeros
+    const int groups = groups_of(D);
+    const int64_t pad = static_cast<int64_t>(RES ? kSampleVecs : groups) * kSampleSlots - D;  // slots past D: they read as zeros
 
-    float ru[kL1Vecs * 4], rg[kL1Vecs * 4], rc[kL1Vecs * 4], rl[kL1Vecs * 4];  // ru: x, then u, then w = u - x0
+    float ru[kSampleElems], rg[kSampleElems], rc[kSampleElems], rl[kSampleElems];  // ru: x, then u, then w = u - x0
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL1Vecs; ++k) {
+        for (int k = 0; k < kSampleVecs; ++k) {
             const int64_t e = group_element(k);
             float uv[4], cv[4], gv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             load4<VEC>(ur, e, D, uv);
@@ -237,13 +169,13 @@ __global__ __launch_bounds__(kL1Block) void l1_kernel(float *z, const float *u_i
         op.sg = step[b] / (static_cast<float>(m) + 1e-10f);
         if (RES) {
 #pragma unroll
-            for (int k = 0; k < kL1Vecs * 4; ++k) ru[k] = op(ru[k], rg[k]);
+            for (int k = 0; k < kSampleElems; ++k) ru[k] = op(ru[k], rg[k]);
         }
     }
 
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL1Vecs * 4; ++k) {
+        for (int k = 0; k < kSampleElems; ++k) {
             const L1Coord c = L1Coord::of(ru[k], rc[k]);
             ru[k] = c.w, rl[k] = c.lo;
         }
@@ -330,14 +262,14 @@ __global__ __launch_bounds__(kL1Block) void l1_kernel(float *z, const float *u_i
 
 // ---- bookkeeping ---------------------------------------------------------------------------------------------------------------------
 template <bool VEC>
-__global__ __launch_bounds__(kL1Block) void book_l1_kernel(const float *__restrict__ loss, const int *__restrict__ pred,
+__global__ __launch_bounds__(kSampleBlock) void book_l1_kernel(const float *__restrict__ loss, const int *__restrict__ pred,
                                                            const float *__restrict__ x, const float *__restrict__ x_best,
                                                            const float *__restrict__ x0, float *fstate, int *istate, float *topk, int *spstate,
                                                            const int *__restrict__ counter, const int *__restrict__ sched, int n_iter,
                                                            int64_t B, int64_t D, float eps) {
-    __shared__ double shd[2 * kL1Waves];
-    __shared__ int shi[2 * kL1Waves];
-    L1Reducer red{shd, shi, 0, 0};
+    __shared__ double shd[2 * kSampleWaves];
+    __shared__ int shi[2 * kSampleWaves];
+    SampleReducer red{shd, shi};
     const int64_t b = blockIdx.x;
     float *step = fstate + EE_APGD_F_STEP * B, *loss_best = fstate + EE_APGD_F_LOSS_BEST * B;
     int *robust = istate + EE_APGD_I_ROBUST * B, *flags = istate + EE_APGD_I_FLAGS * B;
@@ -351,7 +283,7 @@ __global__ __launch_bounds__(kL1Block) void book_l1_kernel(const float *__restri
     int sp = 0;
     if (k > 0) {  // uniform over the launch: the schedule decides it, not the data
         const float *vr = (improved ? x : x_best) + b * D, *cr = x0 + b * D;
-        const int groups = static_cast<int>((D + kL1Slots - 1) / kL1Slots);
+        const int groups = groups_of(D);
         int c = 0;
         for (int g = 0; g < groups; ++g) {
             const int64_t e = group_element(g);
@@ -386,29 +318,23 @@ __global__ __launch_bounds__(kL1Block) void book_l1_kernel(const float *__restri
     flags[b] = f;
 }
 
-int check_l1(int64_t B, int64_t per_sample, float eps, int path) {
+// what the projection and the step check of (B, per_sample, eps, path); *res: the resident path runs
+int check_l1(int64_t B, int64_t per_sample, float eps, int path, bool *res) {
     // per_sample plus the padded slots of the last float4 group must fit the integer counts of a pass
-    if (B < 0 || per_sample < 0 || B > INT32_MAX || per_sample > INT32_MAX - kL1Slots || (per_sample > 0 && B > INT64_MAX / per_sample))
+    if (B < 0 || per_sample < 0 || B > INT32_MAX || per_sample > INT32_MAX - kSampleSlots || (per_sample > 0 && B > INT64_MAX / per_sample))
         return EE_ERR_SHAPE;
-    if (path < EE_APGD_L1_PATH_AUTO || path > EE_APGD_L1_PATH_STREAMING || !(eps >= 0.0f)) return EE_ERR_SHAPE;
-    if (path == EE_APGD_L1_PATH_RESIDENT && per_sample > kL1Resident) return EE_ERR_UNSUPPORTED;
-    return EE_OK;
+    if (!(eps >= 0.0f)) return EE_ERR_SHAPE;
+    return sample_path(path, per_sample, res);
 }
 
 template <bool STEP>
 int launch_l1(float *z, const float *u, const float *g, const float *x0, const float *step, const float *topk, float *scal, int64_t B,
-              int64_t per_sample, float eps, int path, void *stream) {
-    const bool res = path == EE_APGD_L1_PATH_RESIDENT || (path == EE_APGD_L1_PATH_AUTO && per_sample <= kL1Resident);
-    const bool vec = (per_sample & 3) == 0 && aligned16(z) && aligned16(u) && aligned16(x0) && (!STEP || aligned16(g));  // every row then starts 16-byte aligned
-    const dim3 grid(static_cast<unsigned>(B)), block(kL1Block);
-    if (res && vec)
-        EE_LAUNCH((l1_kernel<true, true, STEP>), grid, block, 0, as_stream(stream), z, u, g, x0, step, topk, scal, B, per_sample, eps);
-    else if (res)
-        EE_LAUNCH((l1_kernel<true, false, STEP>), grid, block, 0, as_stream(stream), z, u, g, x0, step, topk, scal, B, per_sample, eps);
-    else if (vec)
-        EE_LAUNCH((l1_kernel<false, true, STEP>), grid, block, 0, as_stream(stream), z, u, g, x0, step, topk, scal, B, per_sample, eps);
-    else
-        EE_LAUNCH((l1_kernel<false, false, STEP>), grid, block, 0, as_stream(stream), z, u, g, x0, step, topk, scal, B, per_sample, eps);
+              int64_t per_sample, float eps, bool res, void *stream) {
+    const bool vec = sample_vec(per_sample, z, u, x0) && (!STEP || aligned16(g));
+    sample_launch(res, vec, [&](auto RES, auto VEC) {
+        EE_LAUNCH((l1_kernel<RES, VEC, STEP>), dim3(static_cast<unsigned>(B)), dim3(kSampleBlock), 0, as_stream(stream), z, u, g, x0, step, topk,
+                  scal, B, per_sample, eps);
+    });
     return launch_status();
 }
 
@@ -416,34 +342,35 @@ int launch_l1(float *z, const float *u, const float *g, const float *x0, const f
 
 EE_API int ee_l1_proj_f32(float *z, const float *u, const float *x0, float *scal, int64_t B, int64_t per_sample, float eps, int path,
                           void *stream) {
-    if (const int rc = check_l1(B, per_sample, eps, path)) return rc;
+    bool res;
+    if (const int rc = check_l1(B, per_sample, eps, path, &res)) return rc;
     if (B == 0 || per_sample == 0) return EE_OK;
     if (!z || !u || !x0 || !scal) return EE_ERR_NULL;
     if (!aligned4(z) || !aligned4(u) || !aligned4(x0) || !aligned4(scal)) return EE_ERR_ALIGN;
-    return launch_l1<false>(z, u, nullptr, x0, nullptr, nullptr, scal, B, per_sample, eps, path, stream);
+    return launch_l1<false>(z, u, nullptr, x0, nullptr, nullptr, scal, B, per_sample, eps, res, stream);
 }
 
 EE_API int ee_apgd_step_l1_f32(float *x, const float *g, const float *x0, const float *step, const float *topk, float *scal, int64_t B,
                                int64_t per_sample, float eps, int path, void *stream) {
-    if (const int rc = check_l1(B, per_sample, eps, path)) return rc;
+    bool res;
+    if (const int rc = check_l1(B, per_sample, eps, path, &res)) return rc;
     if (B == 0 || per_sample == 0) return EE_OK;
     if (!x || !g || !x0 || !step || !topk || !scal) return EE_ERR_NULL;
     if (!aligned4(x) || !aligned4(g) || !aligned4(x0) || !aligned4(step) || !aligned4(topk) || !aligned4(scal)) return EE_ERR_ALIGN;
-    return launch_l1<true>(x, x, g, x0, step, topk, scal, B, per_sample, eps, path, stream);
+    return launch_l1<true>(x, x, g, x0, step, topk, scal, B, per_sample, eps, res, stream);
 }
 
 EE_API int ee_apgd_book_l1_f32(const float *loss, const int *pred, const float *x, const float *x_best, const float *x0, float *fstate,
                                int *istate, float *topk, int *spstate, const int *counter, const int *sched, int n_iter, int64_t B,
                                int64_t per_sample, float eps, void *stream) {
-    if (B < 0 || per_sample < 0 || B > INT32_MAX || per_sample > INT32_MAX - kL1Slots || n_iter < 1 || !(eps >= 0.0f)) return EE_ERR_SHAPE;
+    if (B < 0 || per_sample < 0 || B > INT32_MAX || per_sample > INT32_MAX - kSampleSlots || n_iter < 1 || !(eps >= 0.0f)) return EE_ERR_SHAPE;
     if (B == 0 || per_sample == 0) return EE_OK;
     if (!loss || !pred || !x || !x_best || !x0 || !fstate || !istate || !topk || !spstate || !counter || !sched) return EE_ERR_NULL;
     if (!aligned4(loss) || !aligned4(pred) || !aligned4(x) || !aligned4(x_best) || !aligned4(x0) || !aligned4(fstate) || !aligned4(istate) ||
         !aligned4(topk) || !aligned4(spstate) || !aligned4(counter) || !aligned4(sched))
         return EE_ERR_ALIGN;
-    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x_best) && aligned16(x0);
-    const dim3 grid(static_cast<unsigned>(B)), block(kL1Block);
-    if (vec)
+    const dim3 grid(static_cast<unsigned>(B)), block(kSampleBlock);
+    if (sample_vec(per_sample, x, x_best, x0))
         EE_LAUNCH(book_l1_kernel<true>, grid, block, 0, as_stream(stream), loss, pred, x, x_best, x0, fstate, istate, topk, spstate, counter,
                   sched, n_iter, B, per_sample, eps);
     else

@@ -13,23 +13,18 @@
 //
 // One workgroup per sample: the three norms depend on each other (n1 needs ng, n2 needs n1) and never cross a workgroup, so no launch writes
 // a per-sample scalar that another workgroup of the same launch reads.  A norm is (float) sqrt(S), S the sum of the squares in double (the
-// square of a float is exact there), in one fixed order - thread t takes the float4 groups t, t + 512, ... in turn, wavefronts are reduced
-// by xor-shuffles, the eight partial sums are added in index order - which the resident path (a sample's x, xo, g, x0 stay in registers
-// across the three reductions, per_sample <= 12288) and the streaming path (every pass re-reads its inputs and recomputes z / m from the
-// scalars already known; no scratch tensor) share, so the two return the same bits.  Every loop has a trip count fixed by per_sample.
+// square of a float is exact there) in the one order of ee_sample.hpp, which the resident path (a sample's x, xo, g, x0 stay in registers
+// across the three reductions) and the streaming path (every pass re-reads its inputs and recomputes z / m from the scalars already known)
+// share, so the two return the same bits.  Every loop has a trip count fixed by per_sample.
 // x and x_old are written in the final pass only, each element by the thread that read it.
 #include <math.h>
 
-#include "ee_rows.hpp"
+#include "ee_sample.hpp"
 
 namespace {
 
 using namespace ee;
 
-constexpr int kL2Block = 512;                            // 8 wavefronts per sample
-constexpr int kL2Waves = kL2Block / kWave;
-constexpr int kL2Vecs = 6;                               // float4 groups per thread the resident path keeps
-constexpr int kL2Resident = kL2Block * kL2Vecs * 4;      // 12288 = 3*64*64
 constexpr float kTiny = 1e-12f;
 
 // the element-wise lines of the step; the scalars are filled in as the norms become known
@@ -54,57 +49,15 @@ struct L2Op {
 // min(eps, n) / (n + tiny), NaN in n propagating as torch.min does
 __device__ __forceinline__ float rescale(float eps, float n) { return tmin(eps, n) / (n + kTiny); }
 
-// the sum over the workgroup; consecutive reductions alternate halves of sh, so one barrier per reduction is enough
-struct L2Reducer {
-    double *sh;  // [2][kL2Waves]
-    int phase;
-    __device__ __forceinline__ double sum(double v) {
-        v = wave_sum(v);
-        double *buf = sh + phase * kL2Waves;
-        phase ^= 1;
-        if ((threadIdx.x & (kWave - 1)) == 0) buf[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double r = buf[0];
-#pragma unroll
-        for (int i = 1; i < kL2Waves; ++i) r += buf[i];
-        return r;
-    }
-};
-
-// four consecutive elements of a row from element e on; elements at or past D read as 0
-template <bool VEC>
-__device__ __forceinline__ void load4(const float *row, int64_t e, int64_t D, float (&o)[4]) {
-    if (VEC && e + 3 < D) {
-        const float4 v = *reinterpret_cast<const float4 *>(row + e);
-        o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = e + j < D ? row[e + j] : 0.0f;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store4(float *row, int64_t e, int64_t D, const float (&v)[4]) {
-    if (VEC && e + 3 < D) {
-        *reinterpret_cast<float4 *>(row + e) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (e + j < D) row[e + j] = v[j];
-    }
-}
-
-__device__ __forceinline__ int64_t group_element(int g) { return (static_cast<int64_t>(g) * kL2Block + threadIdx.x) * 4; }
-
-// RES: groups 0 .. kL2Vecs-1 of this thread live in rx / ro / rg / rc (zeros past D); otherwise every pass re-reads the four rows.
+// RES: groups 0 .. kSampleVecs-1 of this thread live in rx / ro / rg / rc (zeros past D); otherwise every pass re-reads the four rows.
 // The body sees (element, x, xo, g, x0) of every float4 group of the thread in the same order on both paths.
 template <bool RES, bool VEC, class F>
 __device__ __forceinline__ void each_group(const float *xr, const float *xor_, const float *gr, const float *cr, int64_t D, int groups,
-                                           const float (&rx)[kL2Vecs * 4], const float (&ro)[kL2Vecs * 4], const float (&rg)[kL2Vecs * 4],
-                                           const float (&rc)[kL2Vecs * 4], F body) {
+                                           const float (&rx)[kSampleElems], const float (&ro)[kSampleElems],
+                                           const float (&rg)[kSampleElems], const float (&rc)[kSampleElems], F body) {
     if (RES) {
 #pragma unroll
-        for (int g = 0; g < kL2Vecs; ++g) {
+        for (int g = 0; g < kSampleVecs; ++g) {
             const float xv[4] = {rx[g * 4], rx[g * 4 + 1], rx[g * 4 + 2], rx[g * 4 + 3]};
             const float ov[4] = {ro[g * 4], ro[g * 4 + 1], ro[g * 4 + 2], ro[g * 4 + 3]};
             const float gv[4] = {rg[g * 4], rg[g * 4 + 1], rg[g * 4 + 2], rg[g * 4 + 3]};
@@ -125,24 +78,25 @@ __device__ __forceinline__ void each_group(const float *xr, const float *xor_, c
 }
 
 template <bool RES, bool VEC>
-__global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x, float *x_old, const float *__restrict__ g, const float *__restrict__ x0,
-                                                           const float *__restrict__ step, const int *__restrict__ counter,
-                                                           float *__restrict__ norms, int64_t B, int64_t D, float eps) {
-    __shared__ double sh[2 * kL2Waves];
-    L2Reducer red{sh, 0};
+__global__ __launch_bounds__(kSampleBlock) void step_l2_kernel(float *x, float *x_old, const float *__restrict__ g,
+                                                               const float *__restrict__ x0, const float *__restrict__ step,
+                                                               const int *__restrict__ counter, float *__restrict__ norms, int64_t B, int64_t D,
+                                                               float eps) {
+    __shared__ double sh[2 * kSampleWaves];
+    SampleReducer red{sh};
     const int64_t b = blockIdx.x;
     float *xr = x + b * D, *xor_ = x_old + b * D;
     const float *gr = g + b * D, *cr = x0 + b * D;
-    const int groups = static_cast<int>((D + 4 * kL2Block - 1) / (4 * kL2Block));  // float4 groups per thread; <= kL2Vecs when RES
+    const int groups = groups_of(D);
     const float a = counter[0] == 0 ? 1.0f : 0.75f;
     L2Op op{a, 1.0f - a, eps, false, 0.0f, 0.0f, 0.0f};
 
     // pass 1: ||g||; the resident path takes the sample into registers here
-    float rx[kL2Vecs * 4], ro[kL2Vecs * 4], rg[kL2Vecs * 4], rc[kL2Vecs * 4];
+    float rx[kSampleElems], ro[kSampleElems], rg[kSampleElems], rc[kSampleElems];
     double acc = 0.0;
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL2Vecs; ++k) {
+        for (int k = 0; k < kSampleVecs; ++k) {
             const int64_t e = group_element(k);
             float xv[4], ov[4], gv[4], cv[4];
             load4<VEC>(xr, e, D, xv);
@@ -214,22 +168,16 @@ __global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x, float *x_ol
 EE_API int ee_apgd_step_l2_f32(float *x, float *x_old, const float *g, const float *x0, const float *step, const int *counter, float *norms,
                                int64_t B, int64_t per_sample, float eps, int path, void *stream) {
     if (B < 0 || per_sample < 0 || B > INT32_MAX || per_sample > INT32_MAX || (per_sample > 0 && B > INT64_MAX / per_sample)) return EE_ERR_SHAPE;
-    if (path < EE_APGD_L2_PATH_AUTO || path > EE_APGD_L2_PATH_STREAMING || !(eps >= 0.0f)) return EE_ERR_SHAPE;
-    if (path == EE_APGD_L2_PATH_RESIDENT && per_sample > kL2Resident) return EE_ERR_UNSUPPORTED;
+    if (!(eps >= 0.0f)) return EE_ERR_SHAPE;
+    bool res;
+    if (const int rc = sample_path(path, per_sample, &res)) return rc;
     if (B == 0 || per_sample == 0) return EE_OK;
     if (!x || !x_old || !g || !x0 || !step || !counter || !norms) return EE_ERR_NULL;
     if (!aligned4(x) || !aligned4(x_old) || !aligned4(g) || !aligned4(x0) || !aligned4(step) || !aligned4(counter) || !aligned4(norms))
         return EE_ERR_ALIGN;
-    const bool res = path == EE_APGD_L2_PATH_RESIDENT || (path == EE_APGD_L2_PATH_AUTO && per_sample <= kL2Resident);
-    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x_old) && aligned16(g) && aligned16(x0);  // every row then starts 16-byte aligned
-    const dim3 grid(static_cast<unsigned>(B)), block(kL2Block);
-    if (res && vec)
-        EE_LAUNCH((step_l2_kernel<true, true>), grid, block, 0, as_stream(stream), x, x_old, g, x0, step, counter, norms, B, per_sample, eps);
-    else if (res)
-        EE_LAUNCH((step_l2_kernel<true, false>), grid, block, 0, as_stream(stream), x, x_old, g, x0, step, counter, norms, B, per_sample, eps);
-    else if (vec)
-        EE_LAUNCH((step_l2_kernel<false, true>), grid, block, 0, as_stream(stream), x, x_old, g, x0, step, counter, norms, B, per_sample, eps);
-    else
-        EE_LAUNCH((step_l2_kernel<false, false>), grid, block, 0, as_stream(stream), x, x_old, g, x0, step, counter, norms, B, per_sample, eps);
+    sample_launch(res, sample_vec(per_sample, x, x_old, g, x0), [&](auto RES, auto VEC) {
+        EE_LAUNCH((step_l2_kernel<RES, VEC>), dim3(static_cast<unsigned>(B)), dim3(kSampleBlock), 0, as_stream(stream), x, x_old, g, x0, step,
+                  counter, norms, B, per_sample, eps);
+    });
     return launch_status();
 }

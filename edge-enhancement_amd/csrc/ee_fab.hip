@@ -17,17 +17,16 @@
 // workgroup-wide sum each), and then solves the segment that contains lambda in closed form: lambda = (c' - sum_{r_i <= T} |v_i| r_i) /
 // sum_{r_i > T} |v_i|.  No breakpoint lies strictly between T and lambda, so this IS the segment solve of the sort-based formulation - not a
 // bisection stopped at a tolerance - and every loop has a trip count fixed by D and the launch shape.  All sums are double (products of two
-// floats are exact there) in one fixed order - thread t takes the float4 groups t, t + 512, ... in turn, wavefronts are reduced by
-// xor-shuffles, the eight partial sums are added in index order - which the resident path (a problem's |w_i| and r_i stay in registers across
-// all passes, D <= 12288) and the streaming path (re-read through L2) share, so the two return the same bits.
+// floats are exact there) in the one order of ee_sample.hpp, which the resident path (a problem's |w_i| and r_i stay in registers across
+// all passes) and the streaming path (re-read through L2) share, so the two return the same bits.
 //
 // The L2 threat model changes the metric at three points and nothing else: ee_fab_proj_l2_f32 (the least-||.||_2
 // delta: delta_i = -sign(v_i) min(mu |v_i|, r_i), g(mu) = sum_i |v_i| min(mu |v_i|, r_i), breakpoints t_i = r_i / |v_i| - the same 31-step
 // search and exact segment solve, mu = (c' - sum_{t_i <= T} |v_i| r_i) / sum_{t_i > T} v_i^2), ee_fab_step_l2_f32 (rebuilds those deltas)
-// and ee_fab_commit_l2_f32 (||x - x0||_2 in double in the fixed order above).  ee_fab_diff_f32 is shared.
+// and ee_fab_commit_l2_f32 (||x - x0||_2 in double in the same order).  ee_fab_diff_f32 is shared.
 #include <math.h>
 
-#include "ee_rows.hpp"
+#include "ee_sample.hpp"
 
 namespace {
 
@@ -35,12 +34,6 @@ using namespace ee;
 
 constexpr float kEta = 1.05f, kBeta = 0.9f, kAlphaMax = 0.1f;
 
-constexpr int kProjBlock = 512;                               // 8 wavefronts per problem
-constexpr int kProjWaves = kProjBlock / kWave;
-constexpr int kProjVecs = 6;                                  // float4 groups per thread the resident path keeps
-constexpr int kProjResident = kProjBlock * kProjVecs * 4;     // 12288 = 3*64*64
-constexpr int kCommitBlock = 512;
-constexpr int kCommitWaves = kCommitBlock / kWave;
 
 // the room of a coordinate at p that v pushes down (v > 0: to 0) or up (v < 0: to 1); 0 where v is 0 or NaN.  Never negative.
 __device__ __forceinline__ float room(float v, float p) { return fmaxf(v > 0.0f ? p : (v < 0.0f ? 1.0f - p : 0.0f), 0.0f); }
@@ -66,56 +59,17 @@ __global__ __launch_bounds__(kBlock) void diff_kernel(const float *__restrict__ 
 }
 
 // ---- the projection ------------------------------------------------------------------------------------------------------------------
-struct Reducer {
-    double *sh;  // [2][kProjWaves]: consecutive reductions alternate halves, so one barrier per reduction is enough
-    int phase;
-    __device__ __forceinline__ double finish(double v) {
-        double *buf = sh + phase * kProjWaves;
-        phase ^= 1;
-        if ((threadIdx.x & (kWave - 1)) == 0) buf[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double r = buf[0];
-#pragma unroll
-        for (int i = 1; i < kProjWaves; ++i) r += buf[i];
-        return r;
-    }
-    __device__ __forceinline__ double sum(double v) { return finish(wave_sum(v)); }
-    __device__ __forceinline__ double max(double v) {
-        v = wave_max(v);
-        double *buf = sh + phase * kProjWaves;
-        phase ^= 1;
-        if ((threadIdx.x & (kWave - 1)) == 0) buf[threadIdx.x >> 6] = v;
-        __syncthreads();
-        double r = buf[0];
-#pragma unroll
-        for (int i = 1; i < kProjWaves; ++i) r = fmax(r, buf[i]);
-        return r;
-    }
-};
-
-// four consecutive elements of a row from element e on; elements at or past D read as 0
-template <bool VEC>
-__device__ __forceinline__ void load4(const float *__restrict__ row, int64_t e, int64_t D, float (&o)[4]) {
-    if (VEC && e + 3 < D) {
-        const float4 v = *reinterpret_cast<const float4 *>(row + e);
-        o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = e + j < D ? row[e + j] : 0.0f;
-    }
-}
-
-// RES: groups 0 .. kProjVecs-1 of this thread live in a[] / r[] (zeros past D); otherwise every pass re-reads w and p.
+// RES: groups 0 .. kSampleVecs-1 of this thread live in a[] / r[] (zeros past D); otherwise every pass re-reads w and p.
 // The body sees (|w|, room) of every element of the thread in the same order on both paths.
 template <bool RES, bool VEC, class F>
 __device__ __forceinline__ void each_element(const float *__restrict__ w, const float *__restrict__ p, int64_t D, int groups, float s,
-                                             const float (&a)[kProjVecs * 4], const float (&r)[kProjVecs * 4], F body) {
+                                             const float (&a)[kSampleElems], const float (&r)[kSampleElems], F body) {
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kProjVecs * 4; ++k) body(a[k], r[k]);
+        for (int k = 0; k < kSampleElems; ++k) body(a[k], r[k]);
     } else {
         for (int g = 0; g < groups; ++g) {
-            const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+            const int64_t e = group_element(g);
             float wv[4], pv[4];
             load4<VEC>(w, e, D, wv);
             load4<VEC>(p, e, D, pv);
@@ -126,24 +80,24 @@ __device__ __forceinline__ void each_element(const float *__restrict__ w, const 
 }
 
 template <bool RES, bool VEC>
-__global__ __launch_bounds__(kProjBlock) void proj_kernel(const float *__restrict__ x, const float *__restrict__ x0, const float *__restrict__ w,
+__global__ __launch_bounds__(kSampleBlock) void proj_kernel(const float *__restrict__ x, const float *__restrict__ x0, const float *__restrict__ w,
                                                           const float *__restrict__ df, int B, int64_t D, float *__restrict__ out) {
-    __shared__ double sh[2 * kProjWaves];
-    Reducer red{sh, 0};
+    __shared__ double sh[2 * kSampleWaves];
+    SampleReducer red{sh};
     const int q = blockIdx.x, b = q < B ? q : q - B;
     const bool second = q >= B;  // problem B + b projects x0, problem b projects x
     const float *xr = x + static_cast<int64_t>(b) * D, *x0r = x0 + static_cast<int64_t>(b) * D, *wr = w + static_cast<int64_t>(b) * D;
     const float *pr = second ? x0r : xr;
-    const int groups = static_cast<int>((D + 4 * kProjBlock - 1) / (4 * kProjBlock));  // float4 groups per thread; <= kProjVecs when RES
+    const int groups = groups_of(D);
     float *lam_out = out + q, *sgn_out = out + 2 * static_cast<int64_t>(B) + q, *nrm_out = out + 4 * static_cast<int64_t>(B) + q;
 
     // pass 1: sum |w_i| and sum w_i (x0_i - x_i); the resident path keeps w in a[] and the point in r[]
-    float a[kProjVecs * 4], r[kProjVecs * 4];
+    float a[kSampleElems], r[kSampleElems];
     double sabs = 0.0, dot = 0.0;
     if (RES) {
 #pragma unroll
-        for (int g = 0; g < kProjVecs; ++g) {
-            const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+        for (int g = 0; g < kSampleVecs; ++g) {
+            const int64_t e = group_element(g);
             float wv[4], xv[4], ov[4];
             load4<VEC>(wr, e, D, wv);
             load4<VEC>(xr, e, D, xv);
@@ -158,7 +112,7 @@ __global__ __launch_bounds__(kProjBlock) void proj_kernel(const float *__restric
         }
     } else {
         for (int g = 0; g < groups; ++g) {
-            const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+            const int64_t e = group_element(g);
             float wv[4], xv[4], ov[4];
             load4<VEC>(wr, e, D, wv);
             load4<VEC>(xr, e, D, xv);
@@ -187,7 +141,7 @@ __global__ __launch_bounds__(kProjBlock) void proj_kernel(const float *__restric
     }
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kProjVecs * 4; ++k) {
+        for (int k = 0; k < kSampleElems; ++k) {
             const float wv = a[k];
             r[k] = room(s * wv, r[k]);
             a[k] = fabsf(wv);
@@ -240,14 +194,14 @@ __device__ __forceinline__ float ratio(float a, float r) { return a != 0.0f ? r 
 // each_element with the breakpoint: the resident path keeps t[] next to a[] / r[], the streaming path recomputes it from what it re-reads
 template <bool RES, bool VEC, class F>
 __device__ __forceinline__ void each_element_l2(const float *__restrict__ w, const float *__restrict__ p, int64_t D, int groups, float s,
-                                                const float (&a)[kProjVecs * 4], const float (&r)[kProjVecs * 4],
-                                                const float (&t)[kProjVecs * 4], F body) {
+                                                const float (&a)[kSampleElems], const float (&r)[kSampleElems],
+                                                const float (&t)[kSampleElems], F body) {
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kProjVecs * 4; ++k) body(a[k], r[k], t[k]);
+        for (int k = 0; k < kSampleElems; ++k) body(a[k], r[k], t[k]);
     } else {
         for (int g = 0; g < groups; ++g) {
-            const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+            const int64_t e = group_element(g);
             float wv[4], pv[4];
             load4<VEC>(w, e, D, wv);
             load4<VEC>(p, e, D, pv);
@@ -261,23 +215,23 @@ __device__ __forceinline__ void each_element_l2(const float *__restrict__ w, con
 }
 
 template <bool RES, bool VEC>
-__global__ __launch_bounds__(kProjBlock) void proj_l2_kernel(const float *__restrict__ x, const float *__restrict__ x0,
+__global__ __launch_bounds__(kSampleBlock) void proj_l2_kernel(const float *__restrict__ x, const float *__restrict__ x0,
                                                              const float *__restrict__ w, const float *__restrict__ df, int B, int64_t D,
                                                              float *__restrict__ out) {
-    __shared__ double sh[2 * kProjWaves];
-    Reducer red{sh, 0};
+    __shared__ double sh[2 * kSampleWaves];
+    SampleReducer red{sh};
     const int q = blockIdx.x, b = q < B ? q : q - B;
     const bool second = q >= B;  // problem B + b projects x0, problem b projects x
     const float *xr = x + static_cast<int64_t>(b) * D, *x0r = x0 + static_cast<int64_t>(b) * D, *wr = w + static_cast<int64_t>(b) * D;
     const float *pr = second ? x0r : xr;
-    const int groups = static_cast<int>((D + 4 * kProjBlock - 1) / (4 * kProjBlock));  // float4 groups per thread; <= kProjVecs when RES
+    const int groups = groups_of(D);
     float *mu_out = out + q, *sgn_out = out + 2 * static_cast<int64_t>(B) + q, *nrm_out = out + 4 * static_cast<int64_t>(B) + q;
 
     // pass 1, as in proj_kernel: sum |w_i| and sum w_i (x0_i - x_i); the resident path keeps w in a[] and the point in r[]
-    float a[kProjVecs * 4], r[kProjVecs * 4], t[kProjVecs * 4];
+    float a[kSampleElems], r[kSampleElems], t[kSampleElems];
     double sabs = 0.0, dot = 0.0;
     auto first = [&](int g) {
-        const int64_t e = (static_cast<int64_t>(g) * kProjBlock + threadIdx.x) * 4;
+        const int64_t e = group_element(g);
         float wv[4], xv[4], ov[4];
         load4<VEC>(wr, e, D, wv);
         load4<VEC>(xr, e, D, xv);
@@ -294,7 +248,7 @@ __global__ __launch_bounds__(kProjBlock) void proj_l2_kernel(const float *__rest
     };
     if (RES) {
 #pragma unroll
-        for (int g = 0; g < kProjVecs; ++g) first(g);
+        for (int g = 0; g < kSampleVecs; ++g) first(g);
     } else {
         for (int g = 0; g < groups; ++g) first(g);
     }
@@ -315,7 +269,7 @@ __global__ __launch_bounds__(kProjBlock) void proj_l2_kernel(const float *__rest
     }
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kProjVecs * 4; ++k) {
+        for (int k = 0; k < kSampleElems; ++k) {
             const float wv = a[k];
             r[k] = room(s * wv, r[k]);
             a[k] = fabsf(wv);
@@ -405,7 +359,7 @@ __device__ __forceinline__ float step_op(float x, float x0, float w, const StepS
     return tclamp((x + kEta * d1) * (1.0f - sm.alpha) + (x0 + kEta * d2) * sm.alpha, 0.0f, 1.0f);
 }
 
-template <int VEC, bool L2 = false>
+template <int VEC, bool L2>
 __global__ __launch_bounds__(kBlock) void step_kernel(float *x, const float *__restrict__ x0, const float *__restrict__ w,
                                                       const float *__restrict__ scal, int64_t B, int64_t per_sample) {
     const int64_t n = B * per_sample;
@@ -437,34 +391,35 @@ __global__ __launch_bounds__(kBlock) void step_kernel(float *x, const float *__r
 // ||x - x0||_inf of the sample at `off`; every thread gets it
 template <int VEC>
 __device__ __forceinline__ float commit_norm_linf(const float *x, const float *x0, int64_t off, int64_t per_sample) {
-    __shared__ float sh_max[kCommitWaves];
+    __shared__ float sh_max[kSampleWaves];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
     float m = 0.0f;
     if (VEC == 4) {  // per_sample % 4 == 0 and 16-byte bases: a sample is a whole number of aligned vectors
         const float4 *vx = reinterpret_cast<const float4 *>(x + off), *v0 = reinterpret_cast<const float4 *>(x0 + off);
-        for (int64_t v = threadIdx.x; v < (per_sample >> 2); v += kCommitBlock) {
+        for (int64_t v = threadIdx.x; v < (per_sample >> 2); v += kSampleBlock) {
             const float4 p = vx[v], o = v0[v];
             m = fmaxf(m, fmaxf(fmaxf(fabsf(p.x - o.x), fabsf(p.y - o.y)), fmaxf(fabsf(p.z - o.z), fabsf(p.w - o.w))));
         }
     } else {
-        for (int64_t k = threadIdx.x; k < per_sample; k += kCommitBlock) m = fmaxf(m, fabsf(x[off + k] - x0[off + k]));
+        for (int64_t k = threadIdx.x; k < per_sample; k += kSampleBlock) m = fmaxf(m, fabsf(x[off + k] - x0[off + k]));
     }
     m = wave_max(m);
     if (lane == 0) sh_max[wave] = m;
     __syncthreads();
     m = sh_max[0];
 #pragma unroll
-    for (int i = 1; i < kCommitWaves; ++i) m = fmaxf(m, sh_max[i]);
+    for (int i = 1; i < kSampleWaves; ++i) m = fmaxf(m, sh_max[i]);
     return m;
 }
 
-// ||x - x0||_2 of the sample at `off` - the squares of the f32 differences summed in double in the order of the projection (thread t takes
-// the groups of four elements t, t + 512, ... whatever the access width), so vector and element-wise calls return the same bits
+// ||x - x0||_2 of the sample at `off` - the squares of the f32 differences summed in double in the order of the projection (ee_sample.hpp's,
+// whatever the access width), so vector and element-wise calls return the same bits
 template <bool VEC>
 __device__ __forceinline__ float commit_norm_l2(const float *x, const float *x0, int64_t off, int64_t per_sample) {
-    __shared__ double sh_sum[kCommitWaves];
+    __shared__ double sh_sum[kSampleWaves];  // one reduction: it uses the first half of the reducer's buffer only
+    SampleReducer red{sh_sum};
     double sq = 0.0;
-    for (int64_t e = static_cast<int64_t>(threadIdx.x) * 4; e < per_sample; e += kCommitBlock * 4) {
+    for (int64_t e = static_cast<int64_t>(threadIdx.x) * 4; e < per_sample; e += kSampleBlock * 4) {
         float pv[4], ov[4];
         load4<VEC>(x + off, e, per_sample, pv);
         load4<VEC>(x0 + off, e, per_sample, ov);
@@ -474,18 +429,12 @@ __device__ __forceinline__ float commit_norm_l2(const float *x, const float *x0,
             sq = fma(d, d, sq);
         }
     }
-    sq = wave_sum(sq);
-    if ((threadIdx.x & (kWave - 1)) == 0) sh_sum[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    double r = sh_sum[0];
-#pragma unroll
-    for (int i = 1; i < kCommitWaves; ++i) r += sh_sum[i];
-    return static_cast<float>(sqrt(r));
+    return static_cast<float>(sqrt(red.sum(sq)));
 }
 
 // L2 = false: the distance is ||x - x0||_inf; true: ||x - x0||_2.  Everything else is one code.
-template <int VEC, bool L2 = false>
-__global__ __launch_bounds__(kCommitBlock) void commit_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels, int K, float *x,
+template <int VEC, bool L2>
+__global__ __launch_bounds__(kSampleBlock) void commit_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels, int K, float *x,
                                                               const float *__restrict__ x0, float *adv, float *res, int *__restrict__ pred,
                                                               int *__restrict__ flags, int *counter, int64_t per_sample) {
     __shared__ int sh_first, sh_nan;
@@ -517,13 +466,13 @@ __global__ __launch_bounds__(kCommitBlock) void commit_kernel(const float *__res
     if (VEC == 4) {
         float4 *vx = reinterpret_cast<float4 *>(x + off), *va = reinterpret_cast<float4 *>(adv + off);
         const float4 *v0 = reinterpret_cast<const float4 *>(x0 + off);
-        for (int64_t v = threadIdx.x; v < (per_sample >> 2); v += kCommitBlock) {
+        for (int64_t v = threadIdx.x; v < (per_sample >> 2); v += kSampleBlock) {
             const float4 p = vx[v], o = v0[v];
             if (improve) va[v] = p;
             vx[v] = make_float4(o.x + kBeta * (p.x - o.x), o.y + kBeta * (p.y - o.y), o.z + kBeta * (p.z - o.z), o.w + kBeta * (p.w - o.w));
         }
     } else {
-        for (int64_t k = threadIdx.x; k < per_sample; k += kCommitBlock) {
+        for (int64_t k = threadIdx.x; k < per_sample; k += kSampleBlock) {
             const float p = x[off + k], o = x0[off + k];
             if (improve) adv[off + k] = p;
             x[off + k] = o + kBeta * (p - o);
@@ -533,6 +482,63 @@ __global__ __launch_bounds__(kCommitBlock) void commit_kernel(const float *__res
 
 bool bad_shape(int64_t B, int64_t per_sample) {
     return B < 0 || per_sample < 0 || B > INT32_MAX / 2 || per_sample > INT32_MAX || (per_sample > 0 && B > INT64_MAX / per_sample);
+}
+
+// ---- the launches that differ between Linf and L2 in one template argument ---------------------------------------------------------------
+template <bool L2>
+int launch_proj(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path, float *out,
+                void *stream) {
+    if (bad_shape(B, per_sample) || per_sample < 1) return EE_ERR_SHAPE;
+    bool res;
+    if (const int rc = sample_path(path, per_sample, &res)) return rc;
+    if (B == 0) return EE_OK;
+    if (!x || !x0 || !w || !df || !out) return EE_ERR_NULL;
+    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(df) || !aligned4(out)) return EE_ERR_ALIGN;
+    const dim3 grid(static_cast<unsigned>(2 * B)), block(kSampleBlock);
+    const int nb = static_cast<int>(B);
+    ProfScope prof(EE_K_FAB_PROJ, as_stream(stream));
+    sample_launch(res, sample_vec(per_sample, x, x0, w), [&](auto RES, auto VEC) {
+        if constexpr (L2)
+            EE_LAUNCH((proj_l2_kernel<RES, VEC>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+        else
+            EE_LAUNCH((proj_kernel<RES, VEC>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+    });
+    return launch_status();
+}
+
+template <bool L2>
+int launch_step(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
+    if (bad_shape(B, per_sample)) return EE_ERR_SHAPE;
+    const int64_t n = B * per_sample;
+    if (n == 0) return EE_OK;
+    if (!x || !x0 || !w || !scal) return EE_ERR_NULL;
+    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(scal)) return EE_ERR_ALIGN;
+    const bool vec = aligned16(x) && aligned16(x0) && aligned16(w);
+    const unsigned blocks = grid_for(vec ? (n + 3) / 4 : n);
+    ProfScope prof(EE_K_FAB_STEP, as_stream(stream));
+    if (vec)
+        EE_LAUNCH((step_kernel<4, L2>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+    else
+        EE_LAUNCH((step_kernel<1, L2>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+    return launch_status();
+}
+
+template <bool L2>
+int launch_commit(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res, int *pred,
+                  int *flags, int *counter, int64_t per_sample, void *stream) {
+    if (B < 0 || K < 2 || K > 65536 || bad_shape(B, per_sample)) return EE_ERR_SHAPE;
+    if (B == 0 || per_sample == 0) return EE_OK;  // an empty batch is no attack: nothing is launched, the counter stays
+    if (!logits || !labels || !x || !x0 || !adv || !res || !pred || !flags || !counter) return EE_ERR_NULL;
+    if (!aligned4(logits) || !aligned4(x) || !aligned4(x0) || !aligned4(adv) || !aligned4(res) || !aligned4(pred) || !aligned4(flags) ||
+        !aligned4(counter) || (reinterpret_cast<uintptr_t>(labels) & 7u))
+        return EE_ERR_ALIGN;
+    const dim3 grid(static_cast<unsigned>(B)), block(kSampleBlock);
+    ProfScope prof(EE_K_FAB_COMMIT, as_stream(stream));
+    if (sample_vec(per_sample, x, x0, adv))
+        EE_LAUNCH((commit_kernel<4, L2>), grid, block, 0, as_stream(stream), logits, labels, K, x, x0, adv, res, pred, flags, counter, per_sample);
+    else
+        EE_LAUNCH((commit_kernel<1, L2>), grid, block, 0, as_stream(stream), logits, labels, K, x, x0, adv, res, pred, flags, counter, per_sample);
+    return launch_status();
 }
 
 }  // namespace
@@ -553,116 +559,28 @@ EE_API int ee_fab_diff_f32(const float *logits, const int64_t *labels, const int
 
 EE_API int ee_fab_proj_linf_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path,
                                 float *out, void *stream) {
-    if (bad_shape(B, per_sample) || per_sample < 1 || path < EE_FAB_PATH_AUTO || path > EE_FAB_PATH_STREAMING) return EE_ERR_SHAPE;
-    if (path == EE_FAB_PATH_RESIDENT && per_sample > kProjResident) return EE_ERR_UNSUPPORTED;
-    if (B == 0) return EE_OK;
-    if (!x || !x0 || !w || !df || !out) return EE_ERR_NULL;
-    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(df) || !aligned4(out)) return EE_ERR_ALIGN;
-    const bool res = path == EE_FAB_PATH_RESIDENT || (path == EE_FAB_PATH_AUTO && per_sample <= kProjResident);
-    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x0) && aligned16(w);  // every row then starts 16-byte aligned
-    const dim3 grid(static_cast<unsigned>(2 * B)), block(kProjBlock);
-    const int nb = static_cast<int>(B);
-    ProfScope prof(EE_K_FAB_PROJ, as_stream(stream));
-    if (res && vec)
-        EE_LAUNCH((proj_kernel<true, true>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-    else if (res)
-        EE_LAUNCH((proj_kernel<true, false>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-    else if (vec)
-        EE_LAUNCH((proj_kernel<false, true>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-    else
-        EE_LAUNCH((proj_kernel<false, false>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-    return launch_status();
-}
-
-EE_API int ee_fab_step_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
-    if (bad_shape(B, per_sample)) return EE_ERR_SHAPE;
-    const int64_t n = B * per_sample;
-    if (n == 0) return EE_OK;
-    if (!x || !x0 || !w || !scal) return EE_ERR_NULL;
-    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(scal)) return EE_ERR_ALIGN;
-    const bool vec = aligned16(x) && aligned16(x0) && aligned16(w);
-    const unsigned blocks = grid_for(vec ? (n + 3) / 4 : n);
-    ProfScope prof(EE_K_FAB_STEP, as_stream(stream));
-    if (vec)
-        EE_LAUNCH(step_kernel<4>, dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
-    else
-        EE_LAUNCH(step_kernel<1>, dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
-    return launch_status();
-}
-
-EE_API int ee_fab_commit_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res, int *pred,
-                             int *flags, int *counter, int64_t per_sample, void *stream) {
-    if (B < 0 || K < 2 || K > 65536 || bad_shape(B, per_sample)) return EE_ERR_SHAPE;
-    if (B == 0 || per_sample == 0) return EE_OK;  // an empty batch is no attack: nothing is launched, the counter stays
-    if (!logits || !labels || !x || !x0 || !adv || !res || !pred || !flags || !counter) return EE_ERR_NULL;
-    if (!aligned4(logits) || !aligned4(x) || !aligned4(x0) || !aligned4(adv) || !aligned4(res) || !aligned4(pred) || !aligned4(flags) ||
-        !aligned4(counter) || (reinterpret_cast<uintptr_t>(labels) & 7u))
-        return EE_ERR_ALIGN;
-    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x0) && aligned16(adv);
-    ProfScope prof(EE_K_FAB_COMMIT, as_stream(stream));
-    if (vec)
-        EE_LAUNCH(commit_kernel<4>, dim3(static_cast<unsigned>(B)), dim3(kCommitBlock), 0, as_stream(stream), logits, labels, K, x, x0, adv, res,
-                  pred, flags, counter, per_sample);
-    else
-        EE_LAUNCH(commit_kernel<1>, dim3(static_cast<unsigned>(B)), dim3(kCommitBlock), 0, as_stream(stream), logits, labels, K, x, x0, adv, res,
-                  pred, flags, counter, per_sample);
-    return launch_status();
+    return launch_proj<false>(x, x0, w, df, B, per_sample, path, out, stream);
 }
 
 EE_API int ee_fab_proj_l2_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path,
                               float *out, void *stream) {
-    if (bad_shape(B, per_sample) || per_sample < 1 || path < EE_FAB_PATH_AUTO || path > EE_FAB_PATH_STREAMING) return EE_ERR_SHAPE;
-    if (path == EE_FAB_PATH_RESIDENT && per_sample > kProjResident) return EE_ERR_UNSUPPORTED;
-    if (B == 0) return EE_OK;
-    if (!x || !x0 || !w || !df || !out) return EE_ERR_NULL;
-    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(df) || !aligned4(out)) return EE_ERR_ALIGN;
-    const bool res = path == EE_FAB_PATH_RESIDENT || (path == EE_FAB_PATH_AUTO && per_sample <= kProjResident);
-    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x0) && aligned16(w);  // every row then starts 16-byte aligned
-    const dim3 grid(static_cast<unsigned>(2 * B)), block(kProjBlock);
-    const int nb = static_cast<int>(B);
-    ProfScope prof(EE_K_FAB_PROJ, as_stream(stream));
-    if (res && vec)
-        EE_LAUNCH((proj_l2_kernel<true, true>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-    else if (res)
-        EE_LAUNCH((proj_l2_kernel<true, false>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-    else if (vec)
-        EE_LAUNCH((proj_l2_kernel<false, true>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-    else
-        EE_LAUNCH((proj_l2_kernel<false, false>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-    return launch_status();
+    return launch_proj<true>(x, x0, w, df, B, per_sample, path, out, stream);
+}
+
+EE_API int ee_fab_step_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
+    return launch_step<false>(x, x0, w, scal, B, per_sample, stream);
 }
 
 EE_API int ee_fab_step_l2_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
-    if (bad_shape(B, per_sample)) return EE_ERR_SHAPE;
-    const int64_t n = B * per_sample;
-    if (n == 0) return EE_OK;
-    if (!x || !x0 || !w || !scal) return EE_ERR_NULL;
-    if (!aligned4(x) || !aligned4(x0) || !aligned4(w) || !aligned4(scal)) return EE_ERR_ALIGN;
-    const bool vec = aligned16(x) && aligned16(x0) && aligned16(w);
-    const unsigned blocks = grid_for(vec ? (n + 3) / 4 : n);
-    ProfScope prof(EE_K_FAB_STEP, as_stream(stream));
-    if (vec)
-        EE_LAUNCH((step_kernel<4, true>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
-    else
-        EE_LAUNCH((step_kernel<1, true>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
-    return launch_status();
+    return launch_step<true>(x, x0, w, scal, B, per_sample, stream);
+}
+
+EE_API int ee_fab_commit_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res, int *pred,
+                             int *flags, int *counter, int64_t per_sample, void *stream) {
+    return launch_commit<false>(logits, labels, B, K, x, x0, adv, res, pred, flags, counter, per_sample, stream);
 }
 
 EE_API int ee_fab_commit_l2_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res,
                                 int *pred, int *flags, int *counter, int64_t per_sample, void *stream) {
-    if (B < 0 || K < 2 || K > 65536 || bad_shape(B, per_sample)) return EE_ERR_SHAPE;
-    if (B == 0 || per_sample == 0) return EE_OK;  // an empty batch is no attack: nothing is launched, the counter stays
-    if (!logits || !labels || !x || !x0 || !adv || !res || !pred || !flags || !counter) return EE_ERR_NULL;
-    if (!aligned4(logits) || !aligned4(x) || !aligned4(x0) || !aligned4(adv) || !aligned4(res) || !aligned4(pred) || !aligned4(flags) ||
-        !aligned4(counter) || (reinterpret_cast<uintptr_t>(labels) & 7u))
-        return EE_ERR_ALIGN;
-    const bool vec = (per_sample & 3) == 0 && aligned16(x) && aligned16(x0) && aligned16(adv);
-    ProfScope prof(EE_K_FAB_COMMIT, as_stream(stream));
-    if (vec)
-        EE_LAUNCH((commit_kernel<4, true>), dim3(static_cast<unsigned>(B)), dim3(kCommitBlock), 0, as_stream(stream), logits, labels, K, x, x0,
-                  adv, res, pred, flags, counter, per_sample);
-    else
-        EE_LAUNCH((commit_kernel<1, true>), dim3(static_cast<unsigned>(B)), dim3(kCommitBlock), 0, as_stream(stream), logits, labels, K, x, x0,
-                  adv, res, pred, flags, counter, per_sample);
-    return launch_status();
+    return launch_commit<true>(logits, labels, B, K, x, x0, adv, res, pred, flags, counter, per_sample, stream);
 }

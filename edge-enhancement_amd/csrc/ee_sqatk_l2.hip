@@ -12,29 +12,24 @@
 //     delta[:, W2] = 0;   delta[c, W1] = new[c] / (tiny + n_new[c]) * scale          n_d = ||delta||_2
 //     x_new    = clamp(x0 + delta / (tiny + n_d) * eps, 0, 1)
 //
-// One workgroup of 512 threads per sample, as in ee_apgd_l2.hip: the norms depend on each other in three rounds ({n_img, n_un, n_w},
-// {n_new}, {n_d}) and never cross a workgroup.  A norm is (float) sqrt(S), S the sum of the squares in double (the square of a float is
-// exact there) in one fixed order: thread t takes the groups of four elements t, t + 512, ... in turn, wavefronts are reduced by
-// xor-shuffles, the eight partial sums are added in index order.  An element outside a window adds an exact zero to that window's sum (or
-// is skipped, which is the same number), so the order depends on the shape only and the resident path (x0, the difference and what is
-// known of each element stay in registers across the rounds, C*H*W <= 12288), the streaming path (every pass re-reads x_best and x0 and
-// recomputes from the scalars already known; no scratch tensor) and the vector / element-wise accesses all return the same bits.
+// One workgroup per sample: the norms depend on each other in three rounds ({n_img, n_un, n_w}, {n_new}, {n_d}) and never cross a
+// workgroup.  A norm is (float) sqrt(S), S the sum of the squares in double (the square of a float is exact there) in the one order of
+// ee_sample.hpp; the Reducer below takes a round's sums together and adds each one's eight partials in that index order.  An element
+// outside a window adds an exact zero to that window's sum (or is skipped, which is the same number), so the order depends on the shape
+// only and the resident path (x0, the difference and what is known of each element stay in registers across the rounds), the streaming
+// path (every pass re-reads x_best and x0 and recomputes from the scalars already known) and the vector / element-wise accesses all
+// return the same bits.
 // flags[b] and margin_min[b] are read by sample b's workgroup only and are uniform in it.  x_best is written in the first pass only
 // (the commit), x_new in the last, each element by the thread that read it.
 #include <math.h>
 
-#include "ee_rows.hpp"
+#include "ee_sample.hpp"
 #include "ee_sqatk.hpp"
 
 namespace {
 
 using namespace ee;
 
-constexpr int kL2Block = 512;  // 8 wavefronts per sample
-constexpr int kL2Waves = kL2Block / kWave;
-constexpr int kL2Vecs = 6;                           // groups of four elements per thread the resident path keeps
-constexpr int kL2Elems = kL2Vecs * 4;
-constexpr int kL2Resident = kL2Block * kL2Elems;     // 12288 = 3*64*64
 constexpr int kMaxC = 32;                            // one sign bit per channel
 constexpr float kTiny = 1e-12f;
 
@@ -56,20 +51,20 @@ __device__ __forceinline__ int channel_of(const Info &i) { return static_cast<in
 
 // the sums of one round: put() every slot, then norms() - two barriers a round, whatever the number of slots
 struct Reducer {
-    double *part;  // [2 + kMaxC][kL2Waves]
+    double *part;  // [2 + kMaxC][kSampleWaves]
     __device__ __forceinline__ void put(int slot, double v) {
         v = wave_sum(v);
-        if ((threadIdx.x & (kWave - 1)) == 0) part[slot * kL2Waves + (threadIdx.x >> 6)] = v;
+        if ((threadIdx.x & (kWave - 1)) == 0) part[slot * kSampleWaves + (threadIdx.x >> 6)] = v;
     }
     // out[k] = (float) sqrt(the sum of slot k's partials in index order), k < n; also stored to global[row(k) * B + b]
     template <class Row>
     __device__ __forceinline__ void norms(int n, float *out, float *__restrict__ global, int64_t B, int64_t b, Row row) {
         __syncthreads();
         if (static_cast<int>(threadIdx.x) < n) {
-            const double *p = part + threadIdx.x * kL2Waves;
+            const double *p = part + threadIdx.x * kSampleWaves;
             double r = p[0];
 #pragma unroll
-            for (int i = 1; i < kL2Waves; ++i) r += p[i];
+            for (int i = 1; i < kSampleWaves; ++i) r += p[i];
             const float v = static_cast<float>(sqrt(r));
             out[threadIdx.x] = v;
             if (global) global[static_cast<int64_t>(row(static_cast<int>(threadIdx.x))) * B + b] = v;
@@ -77,32 +72,6 @@ struct Reducer {
         __syncthreads();
     }
 };
-
-// four consecutive elements of a row from element e on; elements at or past D read as 0
-template <bool VEC>
-__device__ __forceinline__ void load4(const float *row, int64_t e, int64_t D, float (&o)[4]) {
-    if (VEC && e + 3 < D) {
-        const float4 v = *reinterpret_cast<const float4 *>(row + e);
-        o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = e + j < D ? row[e + j] : 0.0f;
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void store4(float *row, int64_t e, int64_t D, const float (&v)[4]) {
-    if (VEC && e + 3 < D) {
-        *reinterpret_cast<float4 *>(row + e) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (e + j < D) row[e + j] = v[j];
-    }
-}
-
-__device__ __forceinline__ int64_t group_element(int g) { return (static_cast<int64_t>(g) * kL2Block + threadIdx.x) * 4; }
-__device__ __forceinline__ int groups_of(int64_t D) { return static_cast<int>((D + 4 * kL2Block - 1) / (4 * kL2Block)); }
 
 // Info of the four elements from e on, `one(c, h, w)` giving an element's; elements at or past D get {0, 0}
 template <class F>
@@ -148,10 +117,10 @@ struct Tiling {
 };
 
 template <bool RES, bool VEC>
-__global__ __launch_bounds__(kL2Block) void init_l2_kernel(float *__restrict__ x_best, float *__restrict__ x_new, const float *__restrict__ x0,
+__global__ __launch_bounds__(kSampleBlock) void init_l2_kernel(float *__restrict__ x_best, float *__restrict__ x_new, const float *__restrict__ x0,
                                                            const int64_t *__restrict__ seed, const float *__restrict__ eta, int s0, int C, int H,
                                                            int W, float eps) {
-    __shared__ double part[kL2Waves];
+    __shared__ double part[kSampleWaves];
     __shared__ float sn[1];
     Reducer red{part};
     const Geo geo{C, H, W, H * W, static_cast<int64_t>(C) * H * W};
@@ -165,11 +134,11 @@ __global__ __launch_bounds__(kL2Block) void init_l2_kernel(float *__restrict__ x
     // an element's d travels in Info::idx as its bits
     const auto one = [&](int c, int h, int w) { return Info{0u, __float_as_int(tl.value(ph, c, h, w))}; };
 
-    float rc[kL2Elems], rd[kL2Elems];
+    float rc[kSampleElems], rd[kSampleElems];
     double acc = 0.0;
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL2Vecs; ++k) {
+        for (int k = 0; k < kSampleVecs; ++k) {
             const int64_t e = group_element(k);
             float cv[4];
             Info in[4];
@@ -194,7 +163,7 @@ __global__ __launch_bounds__(kL2Block) void init_l2_kernel(float *__restrict__ x
     const float q = eps / (sn[0] + kTiny);
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL2Vecs; ++k) {
+        for (int k = 0; k < kSampleVecs; ++k) {
             float o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = tclamp(rc[k * 4 + j] + rd[k * 4 + j] * q, 0.0f, 1.0f);
@@ -257,12 +226,12 @@ __device__ __forceinline__ bool any_in1(const Info (&in)[4], int c) {
 }
 
 template <bool RES, bool VEC>
-__global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x_best, float *x_new, const float *__restrict__ x0, const int *__restrict__ flags,
+__global__ __launch_bounds__(kSampleBlock) void step_l2_kernel(float *x_best, float *x_new, const float *__restrict__ x0, const int *__restrict__ flags,
                                                            const float *__restrict__ margin_min, const int *__restrict__ counter,
                                                            const int *__restrict__ sizes, const int *__restrict__ eta_off,
                                                            const float *__restrict__ eta, int n_sizes, const int64_t *__restrict__ seed,
                                                            float *__restrict__ norms, int64_t B, int C, int H, int W, float eps) {
-    __shared__ double part[(2 + kMaxC) * kL2Waves];
+    __shared__ double part[(2 + kMaxC) * kSampleWaves];
     __shared__ float sn1[2 + kMaxC], sn2[kMaxC], sn3[1];
     Reducer red{part};
     const Geo geo{C, H, W, H * W, static_cast<int64_t>(C) * H * W};
@@ -294,8 +263,8 @@ __global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x_best, float 
     const auto one = [&](int c, int h, int w) { return p.info(c, h, w); };
 
     // round 1: n_img, n_un over the whole sample - the pass that commits, and that takes the sample into registers on the resident path
-    float rc[kL2Elems], rv[kL2Elems];
-    Info ri[kL2Elems];
+    float rc[kSampleElems], rv[kSampleElems];
+    Info ri[kSampleElems];
     double a_img = 0.0, a_un = 0.0;
     const auto first = [&](int64_t e, float (&cv)[4], float (&dv)[4], Info (&in)[4]) {
         float xv[4];
@@ -313,7 +282,7 @@ __global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x_best, float 
     };
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL2Vecs; ++k) {
+        for (int k = 0; k < kSampleVecs; ++k) {
             float cv[4], dv[4];
             Info in[4];
             first(group_element(k), cv, dv, in);
@@ -347,7 +316,7 @@ __global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x_best, float 
         double acc = 0.0;
         if (RES) {
 #pragma unroll
-            for (int k = 0; k < kL2Elems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? square(rv[k]) : 0.0;
+            for (int k = 0; k < kSampleElems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? square(rv[k]) : 0.0;
         } else {
             for (int k = 0; k < groups; ++k)
                 stream(k, [&](const Info(&in)[4]) { return any_in1(in, c); },
@@ -368,13 +337,13 @@ __global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x_best, float 
     // round 2: n_new[c]
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL2Elems; ++k) rv[k] = p.stage1(rv[k], ri[k]);
+        for (int k = 0; k < kSampleElems; ++k) rv[k] = p.stage1(rv[k], ri[k]);
     }
     for (int c = 0; c < C; ++c) {
         double acc = 0.0;
         if (RES) {
 #pragma unroll
-            for (int k = 0; k < kL2Elems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? square(rv[k]) : 0.0;
+            for (int k = 0; k < kSampleElems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? square(rv[k]) : 0.0;
         } else {
             for (int k = 0; k < groups; ++k)
                 stream(k, [&](const Info(&in)[4]) { return any_in1(in, c); },
@@ -392,7 +361,7 @@ __global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x_best, float 
     double a_d = 0.0;
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL2Elems; ++k) {
+        for (int k = 0; k < kSampleElems; ++k) {
             rv[k] = p.stage2(rv[k], ri[k]);
             a_d += square(rv[k]);
         }
@@ -410,7 +379,7 @@ __global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x_best, float 
     // final pass: the one place x_new is written
     if (RES) {
 #pragma unroll
-        for (int k = 0; k < kL2Vecs; ++k) {
+        for (int k = 0; k < kSampleVecs; ++k) {
             float o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = p.next(rc[k * 4 + j], rv[k * 4 + j]);
@@ -431,11 +400,8 @@ __global__ __launch_bounds__(kL2Block) void step_l2_kernel(float *x_best, float 
 int check_l2(int B, int C, int H, int W, float eps, int path, bool *res) {
     const int rc = sqatk_check_shape(B, C, H, W);
     if (rc != EE_OK) return rc;
-    if (path < EE_SQATK_L2_PATH_AUTO || path > EE_SQATK_L2_PATH_STREAMING || !(eps >= 0.0f)) return EE_ERR_SHAPE;
-    const int64_t D = static_cast<int64_t>(C) * H * W;
-    if (path == EE_SQATK_L2_PATH_RESIDENT && D > kL2Resident) return EE_ERR_UNSUPPORTED;
-    *res = path == EE_SQATK_L2_PATH_RESIDENT || (path == EE_SQATK_L2_PATH_AUTO && D <= kL2Resident);
-    return EE_OK;
+    if (!(eps >= 0.0f)) return EE_ERR_SHAPE;
+    return sample_path(path, static_cast<int64_t>(C) * H * W, res);
 }
 
 }  // namespace
@@ -449,17 +415,11 @@ EE_API int ee_sqatk_init_l2_f32(float *x_best, float *x_new, const float *x0, co
     if (B == 0) return EE_OK;
     if (!x_best || !x_new || !x0 || !seed || !eta) return EE_ERR_NULL;
     if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || !aligned4(eta) || (reinterpret_cast<uintptr_t>(seed) & 7u)) return EE_ERR_ALIGN;
-    const bool vec = ((static_cast<int64_t>(C) * H * W) & 3) == 0 && aligned16(x_best) && aligned16(x_new) && aligned16(x0);
-    const dim3 grid(static_cast<unsigned>(B)), block(kL2Block);
     ProfScope prof(EE_K_SQATK_INIT, as_stream(stream));
-    if (res && vec)
-        EE_LAUNCH((init_l2_kernel<true, true>), grid, block, 0, as_stream(stream), x_best, x_new, x0, seed, eta, s0, C, H, W, eps);
-    else if (res)
-        EE_LAUNCH((init_l2_kernel<true, false>), grid, block, 0, as_stream(stream), x_best, x_new, x0, seed, eta, s0, C, H, W, eps);
-    else if (vec)
-        EE_LAUNCH((init_l2_kernel<false, true>), grid, block, 0, as_stream(stream), x_best, x_new, x0, seed, eta, s0, C, H, W, eps);
-    else
-        EE_LAUNCH((init_l2_kernel<false, false>), grid, block, 0, as_stream(stream), x_best, x_new, x0, seed, eta, s0, C, H, W, eps);
+    sample_launch(res, sample_vec(static_cast<int64_t>(C) * H * W, x_best, x_new, x0), [&](auto RES, auto VEC) {
+        EE_LAUNCH((init_l2_kernel<RES, VEC>), dim3(static_cast<unsigned>(B)), dim3(kSampleBlock), 0, as_stream(stream), x_best, x_new, x0, seed,
+                  eta, s0, C, H, W, eps);
+    });
     return launch_status();
 }
 
@@ -476,21 +436,11 @@ EE_API int ee_sqatk_step_l2_f32(float *x_best, float *x_new, const float *x0, co
     if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || !aligned4(flags) || !aligned4(margin_min) || !aligned4(counter) ||
         !aligned4(sizes) || !aligned4(eta_off) || !aligned4(eta) || !aligned4(norms) || (reinterpret_cast<uintptr_t>(seed) & 7u))
         return EE_ERR_ALIGN;
-    const bool vec = ((static_cast<int64_t>(C) * H * W) & 3) == 0 && aligned16(x_best) && aligned16(x_new) && aligned16(x0);
-    const dim3 grid(static_cast<unsigned>(B)), block(kL2Block);
     const int64_t Bl = B;
     ProfScope prof(EE_K_SQATK_STEP, as_stream(stream));
-    if (res && vec)
-        EE_LAUNCH((step_l2_kernel<true, true>), grid, block, 0, as_stream(stream), x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off,
-                  eta, n_sizes, seed, norms, Bl, C, H, W, eps);
-    else if (res)
-        EE_LAUNCH((step_l2_kernel<true, false>), grid, block, 0, as_stream(stream), x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off,
-                  eta, n_sizes, seed, norms, Bl, C, H, W, eps);
-    else if (vec)
-        EE_LAUNCH((step_l2_kernel<false, true>), grid, block, 0, as_stream(stream), x_best, x_new, x0, flags, margin_min, counter, sizes,
-                  eta_off, eta, n_sizes, seed, norms, Bl, C, H, W, eps);
-    else
-        EE_LAUNCH((step_l2_kernel<false, false>), grid, block, 0, as_stream(stream), x_best, x_new, x0, flags, margin_min, counter, sizes,
-                  eta_off, eta, n_sizes, seed, norms, Bl, C, H, W, eps);
+    sample_launch(res, sample_vec(static_cast<int64_t>(C) * H * W, x_best, x_new, x0), [&](auto RES, auto VEC) {
+        EE_LAUNCH((step_l2_kernel<RES, VEC>), dim3(static_cast<unsigned>(B)), dim3(kSampleBlock), 0, as_stream(stream), x_best, x_new, x0, flags,
+                  margin_min, counter, sizes, eta_off, eta, n_sizes, seed, norms, Bl, C, H, W, eps);
+    });
     return launch_status();
 }

@@ -631,8 +631,7 @@ def apgd_l1_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_grap
         raise ValueError("APGD loss must be one of %s, got %r" % (sorted(ops.APGD_KINDS), loss))
     if loss == "dlr_t" and targets is None:
         raise ValueError("the targeted DLR loss needs targets")
-    if path not in ops.APGD_L1_PATHS:
-        raise ValueError("the L1 kernels' path must be one of %s, got %r" % (sorted(ops.APGD_L1_PATHS), path))
+    ops._sample_path(path, "the L1 kernels'")
     if not float(eps) >= 0.0:
         raise ValueError("L1-APGD needs eps >= 0, got %r" % (eps,))
     model = _unwrap(model)
@@ -726,8 +725,7 @@ class _SquareRun:
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
         self.norm, self.path, self.norms = norm, path, None
         if norm == "L2":
-            if path not in ops.SQATK_L2_PATHS:
-                raise ValueError("the L2 Square kernels' path must be one of %s, got %r" % (sorted(ops.SQATK_L2_PATHS), path))
+            ops._sample_path(path, "the L2 Square kernels'")
             C, H, W = x0.shape[1:]
             sizes = sqatk.square_schedule_l2(n_queries, H, W)
             s0 = sqatk.start_size(H, W)
@@ -951,8 +949,7 @@ def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", no
     n_iter = int(n_iter)
     if n_iter < 1:
         raise ValueError("FAB needs n_iter >= 1")
-    if path not in ops.FAB_PATHS:
-        raise ValueError("FAB projection path must be one of %s, got %r" % (sorted(ops.FAB_PATHS), path))
+    ops._sample_path(path, "FAB projection")
     _fab_ops(norm)
     if x0.shape[0] == 0:
         return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=torch.float32, device=x0.device)

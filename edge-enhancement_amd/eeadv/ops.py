@@ -431,8 +431,18 @@ def apgd_step_(x, x_old, g, x0, step, counter, eps):
     return x
 
 
-APGD_L2_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_APGD_L2_PATH_*
-APGD_L2_RESIDENT = 12288  # per-sample size up to which the resident path exists
+# ---- `path` of the kernels that give a sample one workgroup (csrc/ee_sample.hpp) ---------------------------------------
+SAMPLE_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_PATH_*
+SAMPLE_RESIDENT = 12288  # per-sample size up to which the resident path exists
+APGD_L2_PATHS = APGD_L1_PATHS = SQATK_L2_PATHS = FAB_PATHS = SAMPLE_PATHS
+APGD_L2_RESIDENT = APGD_L1_RESIDENT = SQATK_L2_RESIDENT = SAMPLE_RESIDENT
+
+
+def _sample_path(path, what):
+    """EE_PATH_* of `path`; `what` names the kernels in the error."""
+    if path not in SAMPLE_PATHS:
+        raise ValueError("%s path must be one of %s, got %r" % (what, sorted(SAMPLE_PATHS), path))
+    return SAMPLE_PATHS[path]
 
 
 def apgd_step_l2_(x, x_old, g, x0, step, counter, eps, norms=None, path="auto"):
@@ -446,11 +456,10 @@ def apgd_step_l2_(x, x_old, g, x0, step, counter, eps, norms=None, path="auto"):
     p0 = _chk(x0, torch.float32, "x0", x.shape)
     ps = _chk(step, torch.float32, "step", (B,))
     pc = _chk(counter, torch.int32, "counter", (1,))
-    if path not in APGD_L2_PATHS:
-        raise ValueError("the L2 step's path must be one of %s, got %r" % (sorted(APGD_L2_PATHS), path))
+    path = _sample_path(path, "the L2 step's")
     norms = torch.empty((3, B), dtype=torch.float32, device=x.device) if norms is None else norms
     pn = _chk(norms, torch.float32, "norms", (3, B))
-    N.check(N.lib.ee_apgd_step_l2_f32(px, po, pg, p0, ps, pc, pn, B, x.numel() // B if B else 0, eps, APGD_L2_PATHS[path], _stream()),
+    N.check(N.lib.ee_apgd_step_l2_f32(px, po, pg, p0, ps, pc, pn, B, x.numel() // B if B else 0, eps, path, _stream()),
             "ee_apgd_step_l2_f32")
     return norms
 
@@ -492,16 +501,8 @@ def apgd_select_(x, g, x_best, g_best, x_best_adv, flags, counter):
 
 
 # ---- APGD in the L1 threat model (ee_apgd_l1.hip) --------------------------------------------------------------------
-APGD_L1_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_APGD_L1_PATH_*
-APGD_L1_RESIDENT = 12288  # per-sample size up to which the resident path exists
 L1_S_LAMBDA, L1_S_H0, L1_S_ACTIVE, L1_S_DIST, L1_S_TAU, L1_S_M, L1_S_J = range(7)  # rows of scal
 L1_SCAL_ROWS = 7
-
-
-def _l1_path(path):
-    if path not in APGD_L1_PATHS:
-        raise ValueError("the L1 kernels' path must be one of %s, got %r" % (sorted(APGD_L1_PATHS), path))
-    return APGD_L1_PATHS[path]
 
 
 def _l1_scal(scal, x):
@@ -519,7 +520,8 @@ def l1_proj(u, x0, eps, out=None, scal=None, path="auto"):
     pz = _chk(out, torch.float32, "out", u.shape)
     p0 = _chk(x0, torch.float32, "x0", u.shape)
     scal, ps = _l1_scal(scal, u)
-    N.check(N.lib.ee_l1_proj_f32(pz, pu, p0, ps, B, u.numel() // B if B else 0, eps, _l1_path(path), _stream()), "ee_l1_proj_f32")
+    path = _sample_path(path, "the L1 kernels'")
+    N.check(N.lib.ee_l1_proj_f32(pz, pu, p0, ps, B, u.numel() // B if B else 0, eps, path, _stream()), "ee_l1_proj_f32")
     return out, scal
 
 
@@ -533,7 +535,8 @@ def apgd_step_l1_(x, g, x0, step, topk, eps, scal=None, path="auto"):
     pst = _chk(step, torch.float32, "step", (B,))
     pt = _chk(topk, torch.float32, "topk", (B,))
     scal, ps = _l1_scal(scal, x)
-    N.check(N.lib.ee_apgd_step_l1_f32(px, pg, p0, pst, pt, ps, B, x.numel() // B if B else 0, eps, _l1_path(path), _stream()),
+    path = _sample_path(path, "the L1 kernels'")
+    N.check(N.lib.ee_apgd_step_l1_f32(px, pg, p0, pst, pt, ps, B, x.numel() // B if B else 0, eps, path, _stream()),
             "ee_apgd_step_l1_f32")
     return scal
 
@@ -603,24 +606,15 @@ def sqatk_step_(x_best, x_new, x0, flags, margin_min, counter, sizes, seed, eps)
 
 
 # ---- Square attack in the L2 threat model (ee_sqatk_l2.hip) -----------------------------------------------------------
-SQATK_L2_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_SQATK_L2_PATH_*
-SQATK_L2_RESIDENT = 12288  # per-sample size up to which the resident path exists
-
-
-def _sqatk_l2_path(path):
-    if path not in SQATK_L2_PATHS:
-        raise ValueError("the L2 Square kernels' path must be one of %s, got %r" % (sorted(SQATK_L2_PATHS), path))
-    return SQATK_L2_PATHS[path]
-
-
 def sqatk_init_l2_(x_best, x_new, x0, seed, eta0, eps, path="auto"):
     """The tiled start of an L2 run into x_best and x_new [B,C,H,W]; eta0 float32 [s0, s0] on the device (eeadv.sqatk.eta), seed int64 [1]."""
     B, C, H, W = x_best.shape
     pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
     if eta0.dim() != 2 or eta0.shape[0] != eta0.shape[1]:
         raise ValueError("eta0 must be a square table [s0, s0], got shape %s" % (tuple(eta0.shape),))
+    path = _sample_path(path, "the L2 Square kernels'")
     N.check(N.lib.ee_sqatk_init_l2_f32(pb, pn, p0, _chk(seed, torch.int64, "seed", (1,)), _chk(eta0, torch.float32, "eta0"), int(eta0.shape[0]),
-                                       B, C, H, W, eps, _sqatk_l2_path(path), _stream()), "ee_sqatk_init_l2_f32")
+                                       B, C, H, W, eps, path, _stream()), "ee_sqatk_init_l2_f32")
     return x_best
 
 
@@ -638,16 +632,16 @@ def sqatk_step_l2_(x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off
         po = _chk(eta_off, torch.int32, "eta_off", (n_sizes,))
         pe = _chk(eta, torch.float32, "eta")
     norms = torch.zeros((3 + 2 * C, B), dtype=torch.float32, device=x_best.device) if norms is None else norms
+    path = _sample_path(path, "the L2 Square kernels'")
     N.check(N.lib.ee_sqatk_step_l2_f32(pb, pn, p0, _chk(flags, torch.int32, "flags", (B,)), _chk(margin_min, torch.float32, "margin_min", (B,)),
                                        _chk(counter, torch.int32, "counter", (1,)), ps, po, pe, n_sizes, _chk(seed, torch.int64, "seed", (1,)),
-                                       _chk(norms, torch.float32, "norms", (3 + 2 * C, B)), B, C, H, W, eps, _sqatk_l2_path(path), _stream()),
+                                       _chk(norms, torch.float32, "norms", (3 + 2 * C, B)), B, C, H, W, eps, path, _stream()),
             "ee_sqatk_step_l2_f32")
     return norms
 
 
 # ---- FAB-T (ee_fab.hip) ----------------------------------------------------------------------------------------------
 FAB_ADV, FAB_IMPROVED = 1, 2  # bits of the flags of fab_commit_ (EE_FAB_*)
-FAB_PATHS = {"auto": 0, "resident": 1, "streaming": 2}  # EE_FAB_PATH_*
 FAB_LAMBDA, FAB_SIGN, FAB_NORM = range(3)  # rows of the projection scalars [3, 2B] (row 0 is mu in L2)
 
 
@@ -672,7 +666,7 @@ def _fab_proj(fn, name, x, x0, w, df, path, out):
     out = torch.empty((3, 2 * B), dtype=torch.float32, device=x.device) if out is None else out
     po = _chk(out, torch.float32, "out", (3, 2 * B))
     if B:
-        N.check(fn(px, p0, pw, pd, B, x.numel() // B, FAB_PATHS[path], po, _stream()), name)
+        N.check(fn(px, p0, pw, pd, B, x.numel() // B, _sample_path(path, "FAB projection"), po, _stream()), name)
     return out
 
 

@@ -32,6 +32,13 @@ extern "C" {
 #define EE_ERR_UNSUPPORTED (-3) /* valid request this build has no kernel for (e.g. C > 4) */
 #define EE_ERR_ALIGN (-4)       /* pointer not aligned to the element size */
 
+/* `path` of the launches that give a sample (or a projection problem) one workgroup of 512 threads: ee_fab_proj_*, ee_apgd_step_l2_f32,
+ * ee_l1_proj_f32, ee_apgd_step_l1_f32, ee_sqatk_*_l2_f32.  The two paths return the same bits; a value outside the three: EE_ERR_SHAPE.
+ * EE_FAB_PATH_*, EE_APGD_L2_PATH_*, EE_APGD_L1_PATH_* and EE_SQATK_L2_PATH_* below are these. */
+#define EE_PATH_AUTO 0      /* resident when a sample has at most 12288 elements, else streaming */
+#define EE_PATH_RESIDENT 1  /* a sample stays in registers across all passes; more than 12288 elements: EE_ERR_UNSUPPORTED */
+#define EE_PATH_STREAMING 2 /* every pass re-reads its inputs; any size, no scratch tensor */
+
 #define EEADV_ABI_VERSION 1
 
 int ee_abi_version(void);
@@ -260,9 +267,9 @@ int ee_apgd_step_f32(float *x, float *x_old, const float *g, const float *x0, co
  * (any per_sample; no scratch tensor); the two return the same bits.  16-byte accesses when per_sample % 4 == 0 and x, x_old, g, x0 are
  * 16-byte aligned, element-wise otherwise - the same sums.  eps < 0 or NaN, a path outside the three: EE_ERR_SHAPE.  B == 0 or
  * per_sample == 0 launches nothing. */
-#define EE_APGD_L2_PATH_AUTO 0
-#define EE_APGD_L2_PATH_RESIDENT 1
-#define EE_APGD_L2_PATH_STREAMING 2
+#define EE_APGD_L2_PATH_AUTO EE_PATH_AUTO
+#define EE_APGD_L2_PATH_RESIDENT EE_PATH_RESIDENT
+#define EE_APGD_L2_PATH_STREAMING EE_PATH_STREAMING
 int ee_apgd_step_l2_f32(float *x, float *x_old, const float *g, const float *x0, const float *step, const int *counter, float *norms,
                         int64_t B, int64_t per_sample, float eps, int path, void *stream);
 
@@ -299,9 +306,9 @@ int ee_apgd_select_f32(float *x, float *g, float *x_best, float *g_best, float *
  *                         as float values, exact below 2^24
  * An iteration is step_l1 -> classifier forward -> ee_apgd_loss_f32 -> book_l1 -> classifier backward -> ee_apgd_select_f32.
  * One workgroup of 512 threads per sample in all three launches. */
-#define EE_APGD_L1_PATH_AUTO 0
-#define EE_APGD_L1_PATH_RESIDENT 1  /* a sample stays in registers across all passes; per_sample > 12288: EE_ERR_UNSUPPORTED */
-#define EE_APGD_L1_PATH_STREAMING 2 /* every pass re-reads its inputs; any per_sample, no scratch tensor; the same bits */
+#define EE_APGD_L1_PATH_AUTO EE_PATH_AUTO
+#define EE_APGD_L1_PATH_RESIDENT EE_PATH_RESIDENT
+#define EE_APGD_L1_PATH_STREAMING EE_PATH_STREAMING
 #define EE_L1_S_LAMBDA 0 /* the multiplier of the projection (0: the ball is inactive) */
 #define EE_L1_S_H0 1     /* h(0) = sum_i (|w_i| - lo_i) as a float; +inf for a sample written as x0 */
 #define EE_L1_S_ACTIVE 2 /* |A|, the coordinates strictly between their breakpoints on lambda's segment */
@@ -411,9 +418,9 @@ int ee_sqatk_step_f32(float *x_best, float *x_new, const float *x0, const int *f
  * re-reads it (any size; no scratch tensor); the two return the same bits.  16-byte accesses when C*H*W % 4 == 0 and x_best, x_new, x0
  * are 16-byte aligned, element-wise otherwise - the same bits.  eps < 0 or NaN, a path outside the three: EE_ERR_SHAPE; C > 32:
  * EE_ERR_UNSUPPORTED.  B == 0 launches nothing.  Both record under EE_K_SQATK_INIT / EE_K_SQATK_STEP. */
-#define EE_SQATK_L2_PATH_AUTO 0
-#define EE_SQATK_L2_PATH_RESIDENT 1
-#define EE_SQATK_L2_PATH_STREAMING 2
+#define EE_SQATK_L2_PATH_AUTO EE_PATH_AUTO
+#define EE_SQATK_L2_PATH_RESIDENT EE_PATH_RESIDENT
+#define EE_SQATK_L2_PATH_STREAMING EE_PATH_STREAMING
 
 /* The tiled start.  eta: the [s0, s0] table; nh = H / s0 by nw = W / s0 tiles from ((H - nh s0) / 2, (W - nw s0) / 2) on, tile k = a * nw + b':
  *     d = +-eta (transposed by the tile's coin) on the tiles, 0 outside;   n0 = ||d||_2;   q = eps / (n0 + tiny)
@@ -446,9 +453,9 @@ int ee_sqatk_step_l2_f32(float *x_best, float *x_new, const float *x0, const int
  * commit.  No argument changes from one iteration to the next, so a captured graph of one iteration replays for all of them. */
 #define EE_FAB_ADV 1      /* flags: the iterate is misclassified (and no logit of its row is NaN) */
 #define EE_FAB_IMPROVED 2 /*        ... and closer to x0 than adv was: adv took it */
-#define EE_FAB_PATH_AUTO 0      /* resident when per_sample <= 12288, else streaming */
-#define EE_FAB_PATH_RESIDENT 1  /* a problem's (|w_i|, r_i) stay in registers across all passes; per_sample > 12288: EE_ERR_UNSUPPORTED */
-#define EE_FAB_PATH_STREAMING 2 /* every pass re-reads w and the point; any per_sample */
+#define EE_FAB_PATH_AUTO EE_PATH_AUTO
+#define EE_FAB_PATH_RESIDENT EE_PATH_RESIDENT  /* a problem's (|w_i|, r_i) stay in registers */
+#define EE_FAB_PATH_STREAMING EE_PATH_STREAMING /* every pass re-reads w and the point */
 
 /* Per row of logits [B,K], K >= 2, one wavefront per row: df[b] = z_t - z_y (one fp32 difference), dlogits[b] = +1 at t, -1 at y (0 at
  * both when t == y), pred[b] = the first class by value descending, ties to the lower index, NaN above everything (the order of
