@@ -9,6 +9,12 @@ loss, mode) - the loop body is launch-bound at B = 50..100.
 Semantics kept from the reference: the model's train/eval mode is NOT touched here (PGD() runs in whatever
 mode the caller left, BatchNorm statistics and dropout included); callers are entered under
 torch.enable_grad() so an outer no_grad() does not matter; the result is a new detached tensor.
+
+The evaluation attacks (APGD in Linf / L2 / L1, Square, FAB-T) each keep their device state in a run object with four methods - load(*inputs),
+start(model), body(model, n): n consecutive iterations, result() - and share one driver: `_prepare` (build, capture, cache, load, refresh) and
+`_drive` (eager run, or start + replays + result).  apgd_loop, apgd_l1_loop and fab_loop are argument checks, a cache key and one call of
+`_drive`; square_loop takes `_prepare` and keeps its own replay loop (early exit, eager remainder, finish); pgd_loop, with its probed tail,
+stands by itself ("The attack loops' driver").
 """
 import os
 import weakref
@@ -221,6 +227,49 @@ def _adv_where_fooled(robust, x0, x_adv):
     return torch.where(robust.view(-1, *([1] * (x0.dim() - 1))), x0, x_adv)
 
 
+def _empty_result(x0, dtype):
+    """What an attack returns for an empty batch: (x_adv, robust, its third result in `dtype`)."""
+    return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=dtype, device=x0.device)
+
+
+def _check_norm(norm, allowed, what):
+    if norm not in allowed:
+        raise ValueError("%s norm must be one of %s, got %r" % (what, list(allowed), norm))
+    return norm
+
+
+def _prepare(model, key, make_run, inputs, chunk):
+    """The first half of the driver: the captured loop under `key` - on a miss make_run() is loaded and run.body(model, chunk) captured
+    behind run.start(model) - with its run loaded with `inputs` and the weight-derived buffers its kernels read (functional.Conv3x3Map2Fn)
+    brought up to date.  What is left to the caller: run.start(model), the replays, run.result()."""
+    def build():
+        run = make_run()
+        run.load(*inputs)
+        return _Captured(model, run.x0.device, chunk, run).capture(model, lambda m: run.body(m, chunk), start=lambda: run.start(model))
+
+    gs = _cached(key, model, build)
+    gs.run.load(*inputs)
+    refresh_dense_weights()
+    return gs
+
+
+def _drive(model, key, make_run, inputs, n_iter, chunk, use_graph):
+    """One attack of n_iter iterations on a run object (load(*inputs), start(model), body(model, n, last=False): n consecutive
+    iterations, result()): eager - one body call, told that none follows - or n_iter // chunk replays of the graph cached under `key`.
+    load, start and result stay outside the graph ("The attack loops' driver")."""
+    if not use_graph:
+        run = make_run()
+        run.load(*inputs)
+        run.start(model)
+        run.body(model, n_iter, last=True)
+        return run.result()
+    gs = _prepare(model, key, make_run, inputs, chunk)
+    gs.run.start(model)
+    for _ in range(n_iter // gs.iters):
+        gs.graph.replay()
+    return gs.run.result()
+
+
 def pgd_loop(model, x0, x_init, spec, num_steps, step_size, eps, direction=1, lo=0.0, hi=1.0, use_graph=None):
     """Runs num_steps updates starting from x_init (a fresh tensor the loop may update in place); returns a
     detached tensor.  attacks.py:19-27: x = clamp(min(max(x + dir*alpha*sign(g), x0-eps), x0+eps), 0, 1)."""
@@ -269,73 +318,79 @@ def pgd_loop(model, x0, x_init, spec, num_steps, step_size, eps, direction=1, lo
 APGD_NORMS = ("Linf", "L2")
 
 
-def _check_norm(norm):
-    if norm not in APGD_NORMS:
-        raise ValueError("APGD norm must be one of %s, got %r" % (list(APGD_NORMS), norm))
-    return norm
-
-
-def apgd_schedule(n_iter):
-    """sched[i] = the window length k when a checkpoint closes iteration i (0-based), else 0.  k starts at max(int(0.22 n), 1) and
-    shrinks by max(int(0.03 n), 1) per checkpoint down to max(int(0.06 n), 1): n = 100 puts checkpoints after iterations 22, 41, 57, 70, 80,
-    87, 93, 99 (counted from 1)."""
-    n_iter = int(n_iter)
-    if n_iter < 1:
-        raise ValueError("APGD needs n_iter >= 1")
-    k, n_min, dec = max(int(0.22 * n_iter), 1), max(int(0.06 * n_iter), 1), max(int(0.03 * n_iter), 1)
-    sched, since = [0] * n_iter, 0
+def _schedule(n_iter, first, following):
+    """sched[i] = the window length k when a checkpoint closes iteration i (0-based), else 0: the first window is `first` iterations
+    long, the one after a window of k `following(k)`."""
+    sched, since, k = [0] * n_iter, 0, first
     for i in range(n_iter):
         since += 1
         if since == k:
-            sched[i], since, k = k, 0, max(k - dec, n_min)
+            sched[i], since, k = k, 0, following(k)
     return sched
+
+
+def _n_iter(n_iter):
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("APGD needs n_iter >= 1")
+    return n_iter
+
+
+def apgd_schedule(n_iter):
+    """The checkpoints of a Linf / L2 run (_schedule).  k starts at max(int(0.22 n), 1) and shrinks by max(int(0.03 n), 1) per checkpoint
+    down to max(int(0.06 n), 1): n = 100 puts checkpoints after iterations 22, 41, 57, 70, 80, 87, 93, 99 (counted from 1)."""
+    n = _n_iter(n_iter)
+    n_min, dec = max(int(0.06 * n), 1), max(int(0.03 * n), 1)
+    return _schedule(n, max(int(0.22 * n), 1), lambda k: max(k - dec, n_min))
+
+
+def _apgd_args(loss, targets, trace, use_graph):
+    """The argument checks the APGD loops share; returns use_graph with its default resolved (a trace asks for an eager run)."""
+    if loss not in ops.APGD_KINDS:
+        raise ValueError("APGD loss must be one of %s, got %r" % (sorted(ops.APGD_KINDS), loss))
+    if loss == "dlr_t" and targets is None:
+        raise ValueError("the targeted DLR loss needs targets")
+    if use_graph is None:
+        use_graph = graphs_enabled() and trace is None
+    if use_graph and trace is not None:
+        raise ValueError("the APGD trace is recorded by eager runs only")
+    return use_graph
 
 
 class _ApgdSpec:
     """The loss-gradient step of `_body_input_grad` for an APGD run: the row losses, their logit gradient and `pred` in one launch, then -
-    once the run is past its start point - the per-sample bookkeeping in a second one.  The kind is none of the CE kinds, so the route is the
-    generic one (logits -> this -> autograd): the fused head launches produce no row losses.  In an EOT run (eot_iter > 1) the bookkeeping
-    is not launched here: it runs once per iterate, after the last draw (_ApgdRun.gradient)."""
+    once the run is past its start point - the run's per-sample bookkeeping (run.book()).  The kind is none of the CE kinds, so the route
+    is the generic one (logits -> this -> autograd): the fused head launches produce no row losses."""
 
     def __init__(self, run):
-        self.kind, self.payload, self.run = "apgd_" + run.loss, run.y, run
+        self.kind, self.payload, self.run = run.KIND + run.loss, run.y, run
 
     def dlogits(self, logits):
         r = self.run
         r.loss_rows, d, r.pred = ops.apgd_loss(logits.detach(), r.y, r.loss, r.t)
-        if r.started and r.eot_iter == 1:
-            ops.apgd_book_(r.loss_rows, r.pred, r.fstate, r.istate, r.counter, r.sched)
+        if r.started:
+            r.book()
         return d
 
 
-class _ApgdRun:
-    """The device state of one APGD run (include/eeadv.h, "APGD") and its two pieces: `start` (the forward/backward at the start point and the
-    initial state: a handful of small launches, once per attack) and `iteration` (step, forward, loss, bookkeeping, backward, copies: what
-    a captured graph replays).  No host read anywhere.  eot_iter = E > 1: every gradient is the mean over E forward/backward pairs, summed
-    into `g` by ee_apgd_eot_acc_f32 (so `g` is the one gradient buffer of the run), and the bookkeeping runs once per iterate on the mean
-    of the E row losses and the last draw's pred.  norm = "L2": the run owns `norms` [3, B] and `iteration` launches ee_apgd_step_l2_f32 in
-    the place of ee_apgd_step_f32 - nothing else knows the norm.  `trace` (a list, eager runs only) receives one dict per gradient
-    evaluation."""
+class _ApgdState:
+    """What the APGD runs of every threat model share: the buffers (iterate, clean point, the gradient `g` that travels between
+    iterations, best point / its gradient / first fooling point, labels, targets, the per-sample float and int state, counter,
+    schedule), `load`, `body` and `result`.  A subclass adds the state of its step and its own `start`, `gradient`, `iteration` and
+    `book` (the bookkeeping launch that _ApgdSpec makes inside every forward/backward past the start point).  No host read anywhere."""
 
-    def __init__(self, x0, y, n_iter, eps, loss, eot_iter=1, norm="Linf"):
+    def __init__(self, x0, y, n_iter, eps, loss, sched, trace):
         B, dev = x0.shape[0], x0.device
-        self.loss, self.eps, self.n_iter, self.eot_iter = loss, float(eps), int(n_iter), int(eot_iter)
-        self.norm = _check_norm(norm)
-        self.norms = torch.zeros((3, B), dtype=torch.float32, device=dev) if norm == "L2" else None
-        self.trace = None
-        if self.eot_iter > 1:
-            self.loss_acc = torch.empty(B, dtype=torch.float64, device=dev)
-            self.loss_mean = torch.empty(B, dtype=torch.float32, device=dev)
+        self.loss, self.eps, self.n_iter, self.trace = loss, float(eps), int(n_iter), trace
         self.x = torch.empty_like(x0).requires_grad_(True)
-        self.x0, self.x_old, self.g = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
+        self.x0, self.g = torch.empty_like(x0), torch.empty_like(x0)
         self.x_best, self.g_best, self.x_best_adv = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
         self.y = torch.empty(B, dtype=torch.int64, device=dev)
         self.t = torch.empty(B, dtype=torch.int64, device=dev) if loss == "dlr_t" else None
         self.fstate = torch.empty((4, B), dtype=torch.float32, device=dev)
         self.istate = torch.empty((4, B), dtype=torch.int32, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.sched = torch.tensor(apgd_schedule(n_iter), dtype=torch.int32).to(dev)
-        self.loss0 = torch.empty(B, dtype=torch.float32, device=dev)
+        self.sched = torch.tensor(sched, dtype=torch.int32).to(dev)
         self.loss_rows = self.pred = None
         self.started = False
         self.spec = _ApgdSpec(self)
@@ -347,6 +402,49 @@ class _ApgdRun:
             self.y.copy_(y)
             if self.t is not None:
                 self.t.copy_(targets)
+
+    def body(self, model, n, last=False):
+        """n consecutive iterations.  The gradient enters through self.g and - unless this is the last body of the attack - leaves through
+        it: one copy per replay of a captured graph, inside which each iteration reads the autograd result of the one before (an EOT run
+        sums into self.g itself: no copy)."""
+        g = self.g
+        for _ in range(n):
+            g = self.iteration(model, g)
+        if not last and g is not self.g:
+            self.g.copy_(g)
+
+    def result(self):
+        with torch.no_grad():
+            robust = self.istate[ops.APGD_I_ROBUST] != 0
+            return _adv_where_fooled(robust, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
+
+
+class _ApgdRun(_ApgdState):
+    """The device state of one APGD run (include/eeadv.h, "APGD") and its two pieces: `start` (the forward/backward at the start point and the
+    initial state: a handful of small launches, once per attack) and `iteration` (step, forward, loss, bookkeeping, backward, copies: what
+    a captured graph replays).  eot_iter = E > 1: every gradient is the mean over E forward/backward pairs, summed
+    into `g` by ee_apgd_eot_acc_f32 (so `g` is the one gradient buffer of the run), and the bookkeeping runs once per iterate on the mean
+    of the E row losses and the last draw's pred.  norm = "L2": the run owns `norms` [3, B] and `iteration` launches ee_apgd_step_l2_f32 in
+    the place of ee_apgd_step_f32 - nothing else knows the norm.  `trace` (a list, eager runs only) receives one dict per gradient
+    evaluation."""
+    KIND = "apgd_"
+
+    def __init__(self, x0, y, n_iter, eps, loss, eot_iter=1, norm="Linf", trace=None):
+        self.norm, self.eot_iter = _check_norm(norm, APGD_NORMS, "APGD"), int(eot_iter)
+        B, dev = x0.shape[0], x0.device
+        self.norms = torch.zeros((3, B), dtype=torch.float32, device=dev) if norm == "L2" else None  # its fill stays the run's first launch
+        super().__init__(x0, y, n_iter, eps, loss, apgd_schedule(n_iter), trace)
+        if self.eot_iter > 1:
+            self.loss_acc = torch.empty(B, dtype=torch.float64, device=dev)
+            self.loss_mean = torch.empty(B, dtype=torch.float32, device=dev)
+        self.x_old = torch.empty_like(x0)
+        self.loss0 = torch.empty(B, dtype=torch.float32, device=dev)
+
+    def book(self):
+        """Inside a forward/backward: the bookkeeping of a run without EOT.  An EOT run keeps books once per iterate, after the last draw
+        (`gradient`)."""
+        if self.eot_iter == 1:
+            ops.apgd_book_(self.loss_rows, self.pred, self.fstate, self.istate, self.counter, self.sched)
 
     def gradient(self, model):
         """The gradient of the current iterate and, past the start point, its bookkeeping.  E = 1: one forward/backward, the bookkeeping
@@ -419,11 +517,6 @@ class _ApgdRun:
         ops.apgd_select_(self.x.detach(), g_new, self.x_best, self.g_best, self.x_best_adv, self.istate[ops.APGD_I_FLAGS], self.counter)
         return g_new
 
-    def result(self):
-        with torch.no_grad():
-            robust = self.istate[ops.APGD_I_ROBUST] != 0
-            return _adv_where_fooled(robust, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
-
 
 def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, eot_iter=1, trace=None, norm="Linf"):
     """One APGD run of n_iter iterations from x_init inside the eps-ball around x0, on loss 'ce', 'dlr' or 'dlr_t' (which takes `targets`).
@@ -440,54 +533,19 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
     iterations.  E = 1 launches exactly what the loop launched before EOT existed.  `trace` (a list, eager only) receives, per gradient
     evaluation (the start's first), {"draws": [{"loss", "pred", "g"} per draw], "book_loss", "book_pred", "g_mean", "counter", "flags"}
     (the last two None at the start point) and, before each step, {"step_g"}: the gradient that step reads."""
-    if loss not in ops.APGD_KINDS:
-        raise ValueError("APGD loss must be one of %s, got %r" % (sorted(ops.APGD_KINDS), loss))
-    if loss == "dlr_t" and targets is None:
-        raise ValueError("the targeted DLR loss needs targets")
+    use_graph = _apgd_args(loss, targets, trace, use_graph)
     eot_iter = int(eot_iter)
     if eot_iter < 1:
         raise ValueError("APGD needs eot_iter >= 1, got %d" % eot_iter)
-    _check_norm(norm)
+    _check_norm(norm, APGD_NORMS, "APGD")
     model = _unwrap(model)
     x0 = x0.detach().contiguous()
     x_init = x_init.detach().contiguous()
-    n_iter = int(n_iter)
-    if use_graph is None:
-        use_graph = graphs_enabled() and trace is None
-    if use_graph and trace is not None:
-        raise ValueError("the APGD trace is recorded by eager runs only")
-    if not use_graph:
-        run = _ApgdRun(x0, y, n_iter, eps, loss, eot_iter, norm)
-        run.trace = trace
-        run.load(x_init, x0, y, targets)
-        run.start(model)
-        g = run.g
-        for _ in range(n_iter):
-            g = run.iteration(model, g)
-        return run.result()
+    n_iter = _n_iter(n_iter)
     chunk = _eot_chunk(n_iter, eot_iter)
     key = ("apgd", id(model), model.training, tuple(x0.shape), loss, norm, n_iter, float(eps), x0.device.index, chunk, eot_iter)
-
-    def build():
-        run = _ApgdRun(x0, y, n_iter, eps, loss, eot_iter, norm)
-        run.load(x_init, x0, y, targets)
-
-        def body(model):  # the gradient enters through run.g and leaves through it (one copy per replay): inside the graph each
-            g = run.g     # iteration reads the autograd result of the one before (an EOT run sums into run.g itself: no copy)
-            for _ in range(chunk):
-                g = run.iteration(model, g)
-            if g is not run.g:
-                run.g.copy_(g)
-
-        return _Captured(model, x0.device, chunk, run).capture(model, body, start=lambda: run.start(model))
-
-    gs = _cached(key, model, build)
-    gs.run.load(x_init, x0, y, targets)
-    refresh_dense_weights()
-    gs.run.start(model)
-    for _ in range(n_iter // gs.iters):
-        gs.graph.replay()
-    return gs.run.result()
+    return _drive(model, key, lambda: _ApgdRun(x0, y, n_iter, eps, loss, eot_iter, norm, trace), (x_init, x0, y, targets), n_iter, chunk,
+                  use_graph)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -495,70 +553,32 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
 # next to apgd_loop, which keeps refusing norm = "L1" 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def apgd_l1_schedule(n_iter):
-    """sched[i] = the window length k when a checkpoint closes iteration i (0-based), else 0: the first window is max(int(0.04 n), 1)
-    iterations, every later one max(int(0.06 n), 1) - n = 100 puts checkpoints after iterations 4, 10, 16, ... (counted from 1)."""
-    n_iter = int(n_iter)
-    if n_iter < 1:
-        raise ValueError("APGD needs n_iter >= 1")
-    k, k_next = max(int(0.04 * n_iter), 1), max(int(0.06 * n_iter), 1)
-    sched, since = [0] * n_iter, 0
-    for i in range(n_iter):
-        since += 1
-        if since == k:
-            sched[i], since, k = k, 0, k_next
-    return sched
+    """The checkpoints of an L1 run (_schedule): the first window is max(int(0.04 n), 1) iterations, every later one max(int(0.06 n), 1) -
+    n = 100 puts checkpoints after iterations 4, 10, 16, ... (counted from 1)."""
+    n = _n_iter(n_iter)
+    k_next = max(int(0.06 * n), 1)
+    return _schedule(n, max(int(0.04 * n), 1), lambda k: k_next)
 
 
-class _ApgdL1Spec:
-    """The loss-gradient step of `_body_input_grad` for an L1 run: ee_apgd_loss_f32, then - past the start point - ee_apgd_book_l1_f32."""
-
-    def __init__(self, run):
-        self.kind, self.payload, self.run = "apgd_l1_" + run.loss, run.y, run
-
-    def dlogits(self, logits):
-        r = self.run
-        r.loss_rows, d, r.pred = ops.apgd_loss(logits.detach(), r.y, r.loss, r.t)
-        if r.started:
-            ops.apgd_book_l1_(r.loss_rows, r.pred, r.x.detach(), r.x_best, r.x0, r.fstate, r.istate, r.topk, r.spstate, r.counter, r.sched,
-                              r.eps)
-        return d
-
-
-class _ApgdL1Run:
+class _ApgdL1Run(_ApgdState):
     """The device state of one L1-APGD run (include/eeadv.h, "APGD in the L1 threat model") and its two pieces: `start` (the projection of
     the start point, its forward/backward and the initial state, once per attack) and `iteration` (step, forward, loss, bookkeeping,
-    backward, copies: what a captured graph replays).  No host read anywhere.  `trace` (a list, eager runs only) receives one dict for the
-    start and one per iteration."""
+    backward, copies: what a captured graph replays).  `trace` (a list, eager runs only) receives one dict for the start and one per
+    iteration."""
+    KIND = "apgd_l1_"
 
-    def __init__(self, x0, y, n_iter, eps, loss, path="auto"):
+    def __init__(self, x0, y, n_iter, eps, loss, path="auto", trace=None):
         B, dev = x0.shape[0], x0.device
-        self.loss, self.eps, self.n_iter, self.path = loss, float(eps), int(n_iter), path
-        self.per_sample = x0.numel() // B if B else 0
-        self.trace = None
-        self.x = torch.empty_like(x0).requires_grad_(True)
-        self.x0, self.g = torch.empty_like(x0), torch.empty_like(x0)
-        self.x_best, self.g_best, self.x_best_adv = torch.empty_like(x0), torch.empty_like(x0), torch.empty_like(x0)
-        self.y = torch.empty(B, dtype=torch.int64, device=dev)
-        self.t = torch.empty(B, dtype=torch.int64, device=dev) if loss == "dlr_t" else None
-        self.fstate = torch.empty((4, B), dtype=torch.float32, device=dev)
-        self.istate = torch.empty((4, B), dtype=torch.int32, device=dev)
+        self.path, self.per_sample = path, x0.numel() // B if B else 0
         self.topk = torch.empty(B, dtype=torch.float32, device=dev)
         self.spstate = torch.empty((2, B), dtype=torch.int32, device=dev)
         self.scal = torch.zeros((ops.L1_SCAL_ROWS, B), dtype=torch.float32, device=dev)
         self.scal0 = torch.zeros((ops.L1_SCAL_ROWS, B), dtype=torch.float32, device=dev)  # the start projection's
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.sched = torch.tensor(apgd_l1_schedule(n_iter), dtype=torch.int32).to(dev)
-        self.loss_rows = self.pred = None
-        self.started = False
-        self.spec = _ApgdL1Spec(self)
+        super().__init__(x0, y, n_iter, eps, loss, apgd_l1_schedule(n_iter), trace)  # after the two fills: they stay the run's first launches
 
-    def load(self, x_init, x0, y, targets):
-        with torch.no_grad():
-            self.x.detach().copy_(x_init)
-            self.x0.copy_(x0)
-            self.y.copy_(y)
-            if self.t is not None:
-                self.t.copy_(targets)
+    def book(self):
+        ops.apgd_book_l1_(self.loss_rows, self.pred, self.x.detach(), self.x_best, self.x0, self.fstate, self.istate, self.topk, self.spstate,
+                          self.counter, self.sched, self.eps)
 
     def gradient(self, model):
         return input_gradient(model, self.x, self.spec).contiguous()
@@ -610,11 +630,6 @@ class _ApgdL1Run:
             self.trace.append(entry)
         return g_new
 
-    def result(self):
-        with torch.no_grad():
-            robust = self.istate[ops.APGD_I_ROBUST] != 0
-            return _adv_where_fooled(robust, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
-
 
 def apgd_l1_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, trace=None, path="auto"):
     """One L1-APGD run of n_iter iterations inside {z : ||z - x0||_1 <= eps} n [0,1]^D, on loss 'ce', 'dlr' or 'dlr_t' (which takes
@@ -627,55 +642,19 @@ def apgd_l1_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_grap
     "scal", "x", "loss", "pred", "g", "step", "topk", "sp_old"} and, per iteration, {"step_g", "x_in", "counter", "step_in", "topk_in",
     "sp_old_in", "scal", "x", "loss", "pred", "g", "flags", "sp", "loss_best", "step", "topk", "sp_old", "x_out", "g_out", "x_best",
     "x_best_adv"}: what the step read and wrote, what the bookkeeping decided, and the state after the copies."""
-    if loss not in ops.APGD_KINDS:
-        raise ValueError("APGD loss must be one of %s, got %r" % (sorted(ops.APGD_KINDS), loss))
-    if loss == "dlr_t" and targets is None:
-        raise ValueError("the targeted DLR loss needs targets")
+    use_graph = _apgd_args(loss, targets, trace, use_graph)
     ops._sample_path(path, "the L1 kernels'")
     if not float(eps) >= 0.0:
         raise ValueError("L1-APGD needs eps >= 0, got %r" % (eps,))
     model = _unwrap(model)
     x0 = x0.detach().contiguous()
     x_init = x_init.detach().contiguous()
-    n_iter = int(n_iter)
-    apgd_l1_schedule(n_iter)
+    n_iter = _n_iter(n_iter)
     if x0.shape[0] == 0:
-        return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=torch.float32, device=x0.device)
-    if use_graph is None:
-        use_graph = graphs_enabled() and trace is None
-    if use_graph and trace is not None:
-        raise ValueError("the APGD trace is recorded by eager runs only")
-    if not use_graph:
-        run = _ApgdL1Run(x0, y, n_iter, eps, loss, path)
-        run.trace = trace
-        run.load(x_init, x0, y, targets)
-        run.start(model)
-        g = run.g
-        for _ in range(n_iter):
-            g = run.iteration(model, g)
-        return run.result()
+        return _empty_result(x0, torch.float32)
     chunk = _chunk(n_iter)
     key = ("apgd_l1", id(model), model.training, tuple(x0.shape), loss, n_iter, float(eps), x0.device.index, chunk, path)
-
-    def build():
-        run = _ApgdL1Run(x0, y, n_iter, eps, loss, path)
-        run.load(x_init, x0, y, targets)
-
-        def body(model):  # the gradient enters through run.g and leaves through it (one copy per replay), as in apgd_loop
-            g = run.g
-            for _ in range(chunk):
-                g = run.iteration(model, g)
-            run.g.copy_(g)
-
-        return _Captured(model, x0.device, chunk, run).capture(model, body, start=lambda: run.start(model))
-
-    gs = _cached(key, model, build)
-    gs.run.load(x_init, x0, y, targets)
-    refresh_dense_weights()
-    gs.run.start(model)
-    for _ in range(n_iter // gs.iters):
-        gs.graph.replay()
-    return gs.run.result()
+    return _drive(model, key, lambda: _ApgdL1Run(x0, y, n_iter, eps, loss, path, trace), (x_init, x0, y, targets), n_iter, chunk, use_graph)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -684,12 +663,6 @@ def apgd_l1_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_grap
 # ---------------------------------------------------------------------------------------------------------------------------------------
 SQUARE_CHECK_EVERY = 64  # iterations between two host reads of "is any sample still active" (the only host read of the attack)
 SQUARE_NORMS = ("Linf", "L2")
-
-
-def _check_square_norm(norm):
-    if norm not in SQUARE_NORMS:
-        raise ValueError("Square norm must be one of %s, got %r" % (list(SQUARE_NORMS), norm))
-    return norm
 
 
 def square_schedule(n_queries, H, W):
@@ -710,7 +683,7 @@ class _SquareRun:
     and the L2 schedule, and init / step are the launches of ee_sqatk_l2.hip (`path` picks their path) - nothing else knows the norm."""
 
     def __init__(self, x0, y, n_queries, eps, norm="Linf", path="auto"):
-        _check_square_norm(norm)
+        _check_norm(norm, SQUARE_NORMS, "Square")
         if x0.dim() != 4:
             raise ValueError("the Square attack takes image batches [B,C,H,W], got shape %s" % (tuple(x0.shape),))
         B, dev = x0.shape[0], x0.device
@@ -784,6 +757,10 @@ class _SquareRun:
         self._step(self.sizes)
         self._query(model)
 
+    def body(self, model, n, last=False):
+        for _ in range(n):
+            self.iteration(model)
+
     def finish(self):
         """The flags of the last margin launch are still to be committed: a step without a table commits and proposes nothing."""
         self._step(None)
@@ -809,7 +786,7 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
     start and proposal those of ee_sqatk_l2.hip (DESIGN.md section 18; `path` picks the kernels' path, the same bits) on the L2 schedule;
     margin, accept rule, counter, query count, early exit and the graph are shared, and the trace entry of a forward that follows a step
     also holds "x_best_in", "x_new_in", "counter", "norms" [3 + 2C, B] and "x_new"."""
-    _check_square_norm(norm)
+    _check_norm(norm, SQUARE_NORMS, "Square")
     model = _unwrap(model)
     x0 = x0.detach().contiguous()
     n_queries = int(n_queries)
@@ -826,22 +803,15 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
     n_prop = n_queries - 1
     chunk = min(n_prop, MAX_ITERS_PER_GRAPH)
     if x0.shape[0] == 0:
-        return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=torch.int32, device=x0.device)
+        return _empty_result(x0, torch.int32)
     if not use_graph or chunk == 0:
         run, gs = _SquareRun(x0, y, n_queries, eps, norm, path), None
+        run.load(x0, y, seed)
     else:
         key = ("square", id(model), model.training, tuple(x0.shape), n_queries, float(eps), x0.device.index, chunk, norm, path)
-
-        def build():
-            run = _SquareRun(x0, y, n_queries, eps, norm, path)
-            run.load(x0, y, seed)
-            return _Captured(model, x0.device, chunk, run).capture(model, _times(chunk, run.iteration), start=lambda: run.start(model))
-
-        gs = _cached(key, model, build)
+        gs = _prepare(model, key, lambda: _SquareRun(x0, y, n_queries, eps, norm, path), (x0, y, seed), chunk)
         run = gs.run
-        refresh_dense_weights()
     run.trace = trace
-    run.load(x0, y, seed)
     run.start(model)
     done = 0
     while done < n_prop:
@@ -867,11 +837,9 @@ FAB_NORMS = ("Linf", "L2")
 
 def _fab_ops(norm):
     """(projection, step, commit) of a FAB run in the threat model `norm`: the metric enters FAB at these three launches only."""
-    if norm == "Linf":
-        return ops.fab_proj_linf, ops.fab_step_, ops.fab_commit_
-    if norm == "L2":
+    if _check_norm(norm, FAB_NORMS, "FAB") == "L2":
         return ops.fab_proj_l2, ops.fab_step_l2_, ops.fab_commit_l2_
-    raise ValueError("FAB norm must be one of %s, got %r" % (list(FAB_NORMS), norm))
+    return ops.fab_proj_linf, ops.fab_step_, ops.fab_commit_
 
 
 class _FabSpec:
@@ -889,11 +857,12 @@ class _FabSpec:
 
 class _FabRun:
     """The device state of one FAB-T run (include/eeadv.h, "FAB-T") and its two pieces: `start` (the initial state: a few fills, once per
-    run) and `iteration` (forward, diff, backward, projection, step, forward, commit: what a captured graph replays).  No host read anywhere."""
+    run) and `iteration` (forward, diff, backward, projection, step, forward, commit: what a captured graph replays).  No host read anywhere.
+    `eps` only thresholds `result`: the graph does not know it, so a cached run takes the caller's through `load`."""
 
-    def __init__(self, x0, y, n_iter, path="auto", norm="Linf"):
+    def __init__(self, x0, y, n_iter, eps, path="auto", norm="Linf"):
         B, dev = x0.shape[0], x0.device
-        self.n_iter, self.path, self.norm = int(n_iter), path, norm
+        self.n_iter, self.eps, self.path, self.norm = int(n_iter), float(eps), path, norm
         self.proj, self.step_, self.commit_ = _fab_ops(norm)
         self.x = torch.empty_like(x0).requires_grad_(True)
         self.x0, self.adv = torch.empty_like(x0), torch.empty_like(x0)
@@ -907,13 +876,15 @@ class _FabRun:
         self.df = self.pred_at_x = None
         self.spec = _FabSpec(self)
 
-    def load(self, x0, y, targets):
+    def load(self, x0, y, targets, eps=None):
+        if eps is not None:
+            self.eps = float(eps)
         with torch.no_grad():
             self.x0.copy_(x0)
             self.y.copy_(y)
             self.t.copy_(targets)
 
-    def start(self):
+    def start(self, model):  # the driver's signature; FAB starts at the clean point, without a forward
         with torch.no_grad():
             self.x.detach().copy_(self.x0)
             self.adv.copy_(self.x0)
@@ -930,9 +901,13 @@ class _FabRun:
             z = model(self.x)
         self.commit_(z.detach().float().contiguous(), self.y, x, self.x0, self.adv, self.res, self.pred, self.flags, self.counter)
 
-    def result(self, eps):
+    def body(self, model, n, last=False):
+        for _ in range(n):
+            self.iteration(model)
+
+    def result(self):
         with torch.no_grad():
-            robust = ~(self.res <= eps)
+            robust = ~(self.res <= self.eps)
             return _adv_where_fooled(robust, self.x0, self.adv), robust, self.res.clone()
 
 
@@ -952,28 +927,9 @@ def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", no
     ops._sample_path(path, "FAB projection")
     _fab_ops(norm)
     if x0.shape[0] == 0:
-        return x0.clone(), torch.ones(0, dtype=torch.bool, device=x0.device), torch.zeros(0, dtype=torch.float32, device=x0.device)
+        return _empty_result(x0, torch.float32)
     if use_graph is None:
         use_graph = graphs_enabled()
-    if not use_graph:
-        run = _FabRun(x0, y, n_iter, path, norm)
-        run.load(x0, y, targets)
-        run.start()
-        for _ in range(n_iter):
-            run.iteration(model)
-        return run.result(float(eps))
     chunk = _chunk(n_iter)
     key = ("fab", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk, norm)
-
-    def build():
-        run = _FabRun(x0, y, n_iter, path, norm)
-        run.load(x0, y, targets)
-        return _Captured(model, x0.device, chunk, run).capture(model, _times(chunk, run.iteration), start=run.start)
-
-    gs = _cached(key, model, build)
-    gs.run.load(x0, y, targets)
-    refresh_dense_weights()
-    gs.run.start()
-    for _ in range(n_iter // gs.iters):
-        gs.graph.replay()
-    return gs.run.result(float(eps))
+    return _drive(model, key, lambda: _FabRun(x0, y, n_iter, eps, path, norm), (x0, y, targets, eps), n_iter, chunk, use_graph)

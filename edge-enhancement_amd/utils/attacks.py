@@ -157,9 +157,18 @@ def _apgd_row_losses(z, y, loss, t=None):
 
 
 def _check_norm(norm):
-    if norm not in engine.APGD_NORMS:
-        raise ValueError("APGD norm must be one of %s, got %r" % (list(engine.APGD_NORMS), norm))
-    return norm
+    return engine._check_norm(norm, engine.APGD_NORMS, "APGD")
+
+
+def _apgd_grad_once(model, xc, y, loss, t):
+    """(row losses, their input gradient, pred == y) of one forward/backward at xc: what both APGD host loops evaluate."""
+    xc = xc.detach().requires_grad_()
+    with torch.enable_grad():
+        z = model(xc)
+        rows = _apgd_row_losses(z, y, loss, t)
+    g = torch.autograd.grad(rows.sum(), [xc])[0]
+    first = torch.sort(z.detach(), dim=1, descending=True, stable=True)[1][:, 0]
+    return rows.detach(), g.detach(), first == y
 
 
 def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=1, norm="Linf"):
@@ -188,14 +197,7 @@ def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=
         return (lacc / E).to(draws[0][0].dtype), acc * (torch.ones((), dtype=acc.dtype) / E), draws[-1][2]
 
     def grad_once(xc):
-        xc = xc.detach().requires_grad_()
-        with torch.enable_grad():
-            z = model(xc)
-            rows = _apgd_row_losses(z, y, loss, t)
-        g = torch.autograd.grad(rows.sum(), [xc])[0]
-        zd = z.detach()
-        first = torch.sort(zd, dim=1, descending=True, stable=True)[1][:, 0]
-        return rows.detach(), g.detach(), first == y
+        return _apgd_grad_once(model, xc, y, loss, t)
 
     def proj(v):
         return torch.clamp(torch.min(torch.max(v, x0 - eps), x0 + eps), 0, 1)
@@ -295,6 +297,17 @@ def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, nois
     return x_adv, robust
 
 
+def _first_fooling(x0, runs):
+    """Combines attacks of one batch, taken in order from `runs` (an iterable of (x_adv, robust)): the flags ANDed and, per sample, the
+    first fooling point."""
+    x_adv = x0.clone()
+    robust = torch.ones(x0.shape[0], dtype=torch.bool, device=x0.device)
+    for xa, rb in runs:
+        x_adv = torch.where((robust & ~rb).view((-1,) + (1,) * (x0.dim() - 1)), xa, x_adv)
+        robust = robust & rb
+    return x_adv, robust
+
+
 def _norm_kw(norm):
     """The keyword the composites hand on to APGD: none for Linf, so that a Linf call is the call made before the parameter existed."""
     return {} if _check_norm(norm) == "Linf" else {"norm": norm}
@@ -316,10 +329,7 @@ def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None,
     if int(nclass) < 3:
         raise ValueError("APGD_Rand runs APGD-DLR, whose loss is normalised by the spread of the three largest logits: it needs at least 3 "
                          "classes and this model has %d (MNIST's 10 are enough; only the targeted DLR loss of APGD-T needs 4)" % int(nclass))
-    x_adv, robust = APGD(model, args, inputs, targets, num_steps, 'ce', None, noise, eot_iter, **kw)
-    xd, rd = APGD(model, args, inputs, targets, num_steps, 'dlr', None, noise, eot_iter, **kw)
-    x_adv = torch.where((robust & ~rd).view((-1,) + (1,) * (x0.dim() - 1)), xd, x_adv)
-    return x_adv, robust & rd
+    return _first_fooling(x0, (APGD(model, args, inputs, targets, num_steps, loss, None, noise, eot_iter, **kw) for loss in ('ce', 'dlr')))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -414,13 +424,7 @@ def _apgd_l1_host(model, x0, x_init, y, n_iter, eps, loss, t=None, trace=None):
     shape = (-1,) + (1,) * (x0.dim() - 1)
 
     def grad_at(xc):
-        xc = xc.detach().requires_grad_()
-        with torch.enable_grad():
-            z = model(xc)
-            rows = _apgd_row_losses(z, y, loss, t)
-        g = torch.autograd.grad(rows.sum(), [xc])[0]
-        first = torch.sort(z.detach(), dim=1, descending=True, stable=True)[1][:, 0]
-        return rows.detach(), g.detach(), first == y
+        return _apgd_grad_once(model, xc, y, loss, t)
 
     radius = torch.tensor(eps, dtype=dt)
     x, lam0 = _l1_project(x_init.detach(), x0, eps)
@@ -485,14 +489,8 @@ def APGD_T_L1(model, args, inputs, targets, num_steps, nclass, n_target_classes=
     x0 = inputs.detach()
     n_t = min(int(n_target_classes), int(nclass) - 1)
     order = _class_order(model, x0, n_t, "APGD_T_L1", order)
-    x_adv = x0.clone()
-    robust = torch.ones(x0.shape[0], dtype=torch.bool, device=x0.device)
-    shape = (-1,) + (1,) * (x0.dim() - 1)
-    for j in range(1, n_t + 1):
-        xa, rb = APGD_L1(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise)
-        x_adv = torch.where((robust & ~rb).view(shape), xa, x_adv)
-        robust = robust & rb
-    return x_adv, robust
+    return _first_fooling(x0, (APGD_L1(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise)
+                               for j in range(1, n_t + 1)))
 
 
 def _class_order(model, x0, n_t, what, order=None):
@@ -520,14 +518,8 @@ def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, 
     x0 = inputs.detach()
     n_t = min(int(n_target_classes), int(nclass) - 1)
     order = _class_order(model, x0, n_t, "APGD_T", order)
-    x_adv = x0.clone()
-    robust = torch.ones(x0.shape[0], dtype=torch.bool, device=x0.device)
-    shape = (-1,) + (1,) * (x0.dim() - 1)
-    for j in range(1, n_t + 1):
-        xa, rb = APGD(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise, **kw)
-        x_adv = torch.where((robust & ~rb).view(shape), xa, x_adv)
-        robust = robust & rb
-    return x_adv, robust
+    return _first_fooling(x0, (APGD(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise, **kw)
+                               for j in range(1, n_t + 1)))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -547,9 +539,7 @@ def _square_margin(z, y):
 
 
 def _check_square_norm(norm):
-    if norm not in engine.SQUARE_NORMS:
-        raise ValueError("Square norm must be one of %s, got %r" % (list(engine.SQUARE_NORMS), norm))
-    return norm
+    return engine._check_norm(norm, engine.SQUARE_NORMS, "Square")
 
 
 def _square_l2_norms(v, planes=False):
@@ -788,9 +778,7 @@ def _fab_delta_l2(p, w, mu, s):
 
 
 def _check_fab_norm(norm):
-    if norm not in engine.FAB_NORMS:
-        raise ValueError("FAB norm must be one of %s, got %r" % (list(engine.FAB_NORMS), norm))
-    return norm
+    return engine._check_norm(norm, engine.FAB_NORMS, "FAB")
 
 
 def _fab_host_iteration(model, x, x0, y, t, adv, res, norm="Linf"):

@@ -103,9 +103,9 @@ def main():
         out["fab_over_shared"] = round(out["fab_t_iter_ms"] / shared, 4)
         out["fab_extra_us_per_iter"] = round(1e3 * (out["fab_t_iter_ms"] - shared), 1)
         # the projection launch alone, on the state of a real run's third iteration
-        run = engine._FabRun(x, y, 3)
+        run = engine._FabRun(x, y, 3, eps)
         run.load(x, y, t)
-        run.start()
+        run.start(m)
         for _ in range(2):
             run.iteration(m)
         w = engine.input_gradient(m, run.x, run.spec).contiguous()
@@ -120,9 +120,9 @@ def main():
         if l2:
             out["fab_l2_over_linf"] = round(out["fab_t_l2_iter_ms"] / out["fab_t_iter_ms"], 4)
             out["fab_l2_minus_linf_us_per_iter"] = round(1e3 * (out["fab_t_l2_iter_ms"] - out["fab_t_iter_ms"]), 1)
-            run2 = engine._FabRun(x, y, 3, norm="L2")  # the L2 projection launch on the state of an L2 run's third iteration
+            run2 = engine._FabRun(x, y, 3, eps, norm="L2")  # the L2 projection launch on the state of an L2 run's third iteration
             run2.load(x, y, t)
-            run2.start()
+            run2.start(m)
             for _ in range(2):
                 run2.iteration(m)
             w2 = engine.input_gradient(m, run2.x, run2.spec).contiguous()

@@ -205,3 +205,101 @@ def test_validation_dispatch(host_problem):
     a.method_name, a.attack_method = "AT", "AA"
     with pytest.raises(NotImplementedError):
         trainer.attack_for_validation(model, a, x0, y, "cpu", 2, 0.01, NCLS)
+
+
+# ---- the engine's shared pieces: schedules, norm checks, cache keys --------------------------------------------------------------------
+def _linf_schedule_as_it_was(n_iter):
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("APGD needs n_iter >= 1")
+    k, n_min, dec = max(int(0.22 * n_iter), 1), max(int(0.06 * n_iter), 1), max(int(0.03 * n_iter), 1)
+    sched, since = [0] * n_iter, 0
+    for i in range(n_iter):
+        since += 1
+        if since == k:
+            sched[i], since, k = k, 0, max(k - dec, n_min)
+    return sched
+
+
+def _l1_schedule_as_it_was(n_iter):
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("APGD needs n_iter >= 1")
+    k, k_next = max(int(0.04 * n_iter), 1), max(int(0.06 * n_iter), 1)
+    sched, since = [0] * n_iter, 0
+    for i in range(n_iter):
+        since += 1
+        if since == k:
+            sched[i], since, k = k, 0, k_next
+    return sched
+
+
+def test_both_schedules_are_the_literal_loops():
+    from eeadv import engine
+    for n in range(1, 301):
+        assert engine.apgd_schedule(n) == _linf_schedule_as_it_was(n), n
+        assert engine.apgd_l1_schedule(n) == _l1_schedule_as_it_was(n), n
+    for schedule in (engine.apgd_schedule, engine.apgd_l1_schedule):
+        for n in (0, -3):
+            with pytest.raises(ValueError, match="APGD needs n_iter >= 1"):
+                schedule(n)
+
+
+def test_norm_messages(host_problem):
+    import re
+    from eeadv import engine
+    import utils.attacks as A
+    model, x0, y, noise = host_problem
+    a = Args(epsilon=EPS)
+    said = {what: re.escape("%s norm must be one of ['Linf', 'L2'], got 'L1'" % what) for what in ("APGD", "Square", "FAB")}
+    with pytest.raises(ValueError, match=said["APGD"]):
+        engine.apgd_loop(model, x0, x0, y, 2, EPS, "ce", norm="L1")
+    with pytest.raises(ValueError, match=said["APGD"]):
+        A.APGD(model, a, x0, y, 2, norm="L1")
+    with pytest.raises(ValueError, match=said["Square"]):
+        engine.square_loop(model, x0, y, 3, EPS, seed=1, norm="L1")
+    with pytest.raises(ValueError, match=said["Square"]):
+        A.Square(model, a, x0, y, 3, seed=1, norm="L1")
+    with pytest.raises(ValueError, match=said["FAB"]):
+        engine.fab_loop(model, x0, y, y, 2, EPS, norm="L1")
+    with pytest.raises(ValueError, match=said["FAB"]):
+        A.FAB_T(model, a, x0, y, NCLS, n_iter=2, norm="L1")
+
+
+def test_cache_keys_keep_their_layout(host_problem, monkeypatch):
+    """The key each captured loop hands to engine._cached, tuple for tuple as the loops built them before they shared a driver: tests and
+    scripts read k[0] as the loop's name, k[5] of an "apgd" key as the norm, and look for "Linf" in a key."""
+    from eeadv import engine
+    model, x0, y, noise = host_problem
+
+    class Seen(Exception):
+        pass
+
+    def cached(key, m, build):
+        raise Seen(key)
+
+    monkeypatch.setattr(engine, "_cached", cached)
+    shape, mid, dev = tuple(x0.shape), id(model), x0.device.index
+    calls = [
+        (lambda: engine.pgd_loop(model, x0, x0.clone(), engine.LossSpec(engine.CE_SUM, y), 6, 0.01, EPS, use_graph=True),
+         ("pgd", mid, model.training, shape, engine.CE_SUM, tuple(y.shape), y.dtype, 0.01, float(EPS), 1, 0.0, 1.0, dev, 6)),
+        (lambda: engine.apgd_loop(model, x0, x0, y, 6, EPS, "ce", use_graph=True),
+         ("apgd", mid, model.training, shape, "ce", "Linf", 6, float(EPS), dev, 6, 1)),
+        (lambda: engine.apgd_loop(model, x0, x0, y, 34, EPS, "dlr", use_graph=True, eot_iter=4, norm="L2"),
+         ("apgd", mid, model.training, shape, "dlr", "L2", 34, float(EPS), dev, 2, 4)),
+        (lambda: engine.apgd_l1_loop(model, x0, x0, y, 34, 1.5, "ce", use_graph=True, path="streaming"),
+         ("apgd_l1", mid, model.training, shape, "ce", 34, 1.5, dev, 2, "streaming")),
+        (lambda: engine.square_loop(model, x0, y, 40, EPS, seed=1, use_graph=True),
+         ("square", mid, model.training, shape, 40, float(EPS), dev, 16, "Linf", "auto")),
+        (lambda: engine.square_loop(model, x0, y, 5, 0.5, seed=1, use_graph=True, norm="L2", path="resident"),
+         ("square", mid, model.training, shape, 5, 0.5, dev, 4, "L2", "resident")),
+        (lambda: engine.fab_loop(model, x0, y, y, 6, EPS, use_graph=True),
+         ("fab", mid, model.training, shape, "auto", dev, 6, "Linf")),
+        (lambda: engine.fab_loop(model, x0, y, y, 34, EPS, use_graph=True, path="resident", norm="L2"),
+         ("fab", mid, model.training, shape, "resident", dev, 2, "L2")),
+    ]
+    for call, want in calls:
+        with pytest.raises(Seen) as seen:
+            call()
+        (key,) = seen.value.args
+        assert key == want and [type(v) for v in key] == [type(v) for v in want]

@@ -397,4 +397,4 @@ def test_norm_keyword():
     with pytest.raises(ValueError, match="norm"):
         engine.fab_loop(m, x, y, y, 1, 0.5, norm="L1")
     with pytest.raises(ValueError, match="norm"):
-        engine._FabRun(x, y, 1, norm="l2")
+        engine._FabRun(x, y, 1, 0.5, norm="l2")

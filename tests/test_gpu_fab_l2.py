@@ -300,9 +300,9 @@ def test_teacher_forced_trajectory():
     from eeadv import engine
     n_iter = 4
     m, x0, y, t = _tiny_problem()
-    run = engine._FabRun(x0, y, n_iter, norm="L2")
+    run = engine._FabRun(x0, y, n_iter, 0.5, norm="L2")
     run.load(x0, y, t)
-    run.start()
+    run.start(m)
     recs = []
     proj, step_, commit_ = run.proj, run.step_, run.commit_
 
@@ -326,7 +326,7 @@ def test_teacher_forced_trajectory():
     run.proj, run.step_, run.commit_ = rproj, rstep, rcommit
     for _ in range(n_iter):
         run.iteration(m)
-    got = run.result(0.5)
+    got = run.result()
     plain = engine.fab_loop(m, x0, y, t, n_iter, 0.5, use_graph=False, norm="L2")
     assert all(torch.equal(p, q) for p, q in zip(got, plain))  # the recorded run is the engine's run
     assert len(recs) == n_iter and int(run.counter.item()) == n_iter
@@ -392,6 +392,23 @@ def test_linf_route_is_unchanged_and_the_two_norms_share_the_cache(ops, monkeypa
         assert len([k for k in engine._GRAPHS if k[0] == "fab"]) == 2
         with pytest.raises(ValueError, match="norm"):
             engine.fab_loop(m, x0, y, t, n_iter, eps, norm="L1")
+    finally:
+        engine.clear_graphs()
+
+
+def test_one_cached_graph_thresholds_with_each_callers_eps():
+    """eps only thresholds FAB's result and is not in the cache key: the run cached by the first call answers later calls with THEIR eps."""
+    from eeadv import engine
+    m, x0, y, t = _tiny_problem()
+    engine.clear_graphs()
+    try:
+        got = {}
+        for eps in (1.0, 0.0, 1.0):  # inside the box no Linf distance exceeds 1; none but a clean miss is <= 0
+            want = engine.fab_loop(m, x0, y, t, 4, eps, use_graph=False)
+            got[eps] = engine.fab_loop(m, x0, y, t, 4, eps, use_graph=True)
+            assert all(torch.equal(p, q) for p, q in zip(got[eps], want)), eps
+        assert len([k for k in engine._GRAPHS if k[0] == "fab"]) == 1
+        assert torch.equal(got[1.0][2], got[0.0][2]) and not torch.equal(got[1.0][1], got[0.0][1])  # the same search, other flags
     finally:
         engine.clear_graphs()
 

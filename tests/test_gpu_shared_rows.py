@@ -1,4 +1,4 @@
-"""What csrc/ee_rows.hpp and engine._cached promise: the kernels that share a logit-row expression give each other's bits, and the four
+"""What csrc/ee_rows.hpp and engine._cached promise: the kernels that share a logit-row expression give each other's bits, and the five
 captured attack loops share one cache path (eager = graph, BatchNorm statistics shielded from the capture, no stale graph)."""
 import gc
 
@@ -71,6 +71,8 @@ def _call(loop, model, use_graph):
         out = (engine.pgd_loop(model, x0, x_init, engine.LossSpec(engine.CE_SUM, y), 4, 2 / 255, EPS, use_graph=use_graph),)
     elif loop == "apgd":
         out = engine.apgd_loop(model, x0, x_init, y, 4, EPS, "ce", use_graph=use_graph)
+    elif loop == "apgd_l1":
+        out = engine.apgd_l1_loop(model, x0, x_init, y, 4, 1.0, "ce", use_graph=use_graph)
     elif loop == "square":
         out = engine.square_loop(model, x0, y, 5, EPS, seed=7, use_graph=use_graph)
     else:
@@ -86,7 +88,7 @@ def _same(a, b):
     return len(a) == len(b) and all(torch.equal(p, q) for p, q in zip(a, b))
 
 
-@pytest.mark.parametrize("loop", ["pgd", "apgd", "square", "fab"])
+@pytest.mark.parametrize("loop", ["pgd", "apgd", "apgd_l1", "square", "fab"])
 def test_one_cache_path(loop):
     from eeadv import engine
     engine.clear_graphs()
