@@ -24,6 +24,12 @@
 // delta: delta_i = -sign(v_i) min(mu |v_i|, r_i), g(mu) = sum_i |v_i| min(mu |v_i|, r_i), breakpoints t_i = r_i / |v_i| - the same 31-step
 // search and exact segment solve, mu = (c' - sum_{t_i <= T} |v_i| r_i) / sum_{t_i > T} v_i^2), ee_fab_step_l2_f32 (rebuilds those deltas)
 // and ee_fab_commit_l2_f32 (||x - x0||_2 in double in the same order).  ee_fab_diff_f32 is shared.
+//
+// The L1 threat model enters at the same three points: ee_fab_proj_l1_f32 (the least-||.||_1 delta is a fractional-
+// knapsack fill by descending |v_i|: F(T) = sum_{|v_i| >= T} |v_i| r_i is a non-increasing step function, theta the largest float with
+// F(theta) >= c' - the same 31-step search, no sort - coordinates above theta go to their bounds and those AT theta all take the same
+// fraction phi = (c' - sum_{|v_i| > theta} |v_i| r_i) / sum_{|v_i| = theta} |v_i| r_i of their rooms), ee_fab_step_l1_f32 (rebuilds those
+// deltas from theta and phi) and ee_fab_commit_l1_f32 (||x - x0||_1 in double in the same order).
 #include <math.h>
 
 #include "ee_sample.hpp"
@@ -330,17 +336,135 @@ __global__ __launch_bounds__(kSampleBlock) void proj_l2_kernel(const float *__re
     if (threadIdx.x == 0) *mu_out = static_cast<float>(mud), *sgn_out = s, *nrm_out = static_cast<float>(sqrt(n2));
 }
 
+// ---- the L1 projection -----------------------------------------------------------------------------------------------------------------
+// F(T) = sum_{a_i >= T} a_i r_i in double (the products are exact there), in the one order of ee_sample.hpp: a sum of non-negative terms in
+// a fixed order is monotone in every term, so the computed F is non-increasing in T like the real one and the bit search below is sound.
+// A coordinate with a_i == 0 has the room 0 and adds an exact zero wherever it is counted.
+template <bool RES, bool VEC>
+__global__ __launch_bounds__(kSampleBlock) void proj_l1_kernel(const float *__restrict__ x, const float *__restrict__ x0,
+                                                             const float *__restrict__ w, const float *__restrict__ df, int B, int64_t D,
+                                                             float *__restrict__ out) {
+    __shared__ double sh[2 * kSampleWaves];
+    SampleReducer red{sh};
+    const int q = blockIdx.x, b = q < B ? q : q - B;
+    const bool second = q >= B;  // problem B + b projects x0, problem b projects x
+    const float *xr = x + static_cast<int64_t>(b) * D, *x0r = x0 + static_cast<int64_t>(b) * D, *wr = w + static_cast<int64_t>(b) * D;
+    const float *pr = second ? x0r : xr;
+    const int groups = groups_of(D);
+    const int64_t Q = 2 * static_cast<int64_t>(B);
+    float *theta_out = out + q, *sgn_out = out + Q + q, *nrm_out = out + 2 * Q + q, *phi_out = out + 3 * Q + q;
+
+    // pass 1, as in proj_kernel: sum |w_i| and sum w_i (x0_i - x_i); the resident path keeps w in a[] and the point in r[]
+    float a[kSampleElems], r[kSampleElems];
+    double sabs = 0.0, dot = 0.0;
+    auto first = [&](int g) {
+        const int64_t e = group_element(g);
+        float wv[4], xv[4], ov[4];
+        load4<VEC>(wr, e, D, wv);
+        load4<VEC>(xr, e, D, xv);
+        load4<VEC>(x0r, e, D, ov);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            sabs += static_cast<double>(fabsf(wv[j]));
+            dot = fma(static_cast<double>(wv[j]), static_cast<double>(ov[j] - xv[j]), dot);
+            if (RES) {
+                a[g * 4 + j] = wv[j];
+                r[g * 4 + j] = second ? ov[j] : xv[j];
+            }
+        }
+    };
+    if (RES) {
+#pragma unroll
+        for (int g = 0; g < kSampleVecs; ++g) first(g);
+    } else {
+        for (int g = 0; g < groups; ++g) first(g);
+    }
+    sabs = red.sum(sabs);
+    dot = red.sum(dot);
+    const float d = df[b];
+    // every decision below is taken on values all threads of the workgroup hold alike: the early exits are uniform
+    if (!(isfinite(d) && d != 0.0f && isfinite(sabs) && sabs > 0.0)) {  // no hyperplane to project onto: both problems of the sample rest
+        if (threadIdx.x == 0) *theta_out = 0.0f, *sgn_out = 0.0f, *nrm_out = 0.0f, *phi_out = 0.0f;
+        return;
+    }
+    const float c = second ? static_cast<float>(static_cast<double>(d) + dot) : d;
+    const float s = c >= 0.0f ? 1.0f : -1.0f;  // NaN cannot come here: d and dot are finite
+    const float cp = fabsf(c);
+    if (!isfinite(c) || cp == 0.0f) {  // c = 0: the point lies on the hyperplane; no |v_i| is above theta = +inf, so nothing moves
+        if (threadIdx.x == 0) *theta_out = INFINITY, *sgn_out = 1.0f, *nrm_out = 0.0f, *phi_out = 0.0f;
+        return;
+    }
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kSampleElems; ++k) {
+            const float wv = a[k];
+            r[k] = room(s * wv, r[k]);
+            a[k] = fabsf(wv);
+        }
+    }
+    // F at the smallest positive float: every moving coordinate at its bound
+    double full = 0.0;
+    each_element<RES, VEC>(wr, pr, D, groups, s, a, r,
+                           [&](float av, float rv) { full = fma(static_cast<double>(av), static_cast<double>(rv), full); });
+    full = red.sum(full);
+    const double cpd = static_cast<double>(cp);
+    if (cpd > full) {  // infeasible inside the box: every coordinate that can move goes to its bound (all |v_i| != 0 are above theta = 0)
+        double rs = 0.0;
+        each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
+            rs += av != 0.0f ? static_cast<double>(rv) : 0.0;
+        });
+        rs = red.sum(rs);
+        if (threadIdx.x == 0) *theta_out = 0.0f, *sgn_out = s, *nrm_out = static_cast<float>(rs), *phi_out = 1.0f;
+        return;
+    }
+    // theta: the largest positive float with F(theta) >= c'.  F(2^-149) = full >= c' holds, so bit 0 at the latest is taken and theta > 0;
+    // w is finite (sabs is), so F is 0 < c' at +inf and at every NaN pattern (no a_i >= NaN): theta stays finite.
+    uint32_t T = 0u;
+    for (int bit = 30; bit >= 0; --bit) {
+        const uint32_t cand = T | (1u << bit);
+        const float tf = __uint_as_float(cand);
+        double part = 0.0;
+        each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
+            part = fma(static_cast<double>(av), av >= tf ? static_cast<double>(rv) : 0.0, part);  // an exact zero below T
+        });
+        if (red.sum(part) >= cpd) T = cand;
+    }
+    // the fill: S and N above theta (at their bounds), P and R at theta (they share what is left of c')
+    const float theta = __uint_as_float(T);
+    double S = 0.0, N = 0.0, P = 0.0, R = 0.0;
+    each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
+        const double ad = static_cast<double>(av), rd = static_cast<double>(rv);
+        const double above = av > theta ? rd : 0.0, at = av == theta ? rd : 0.0;  // adding an exact zero changes no sum
+        S = fma(ad, above, S);
+        N += above;
+        P = fma(ad, at, P);
+        R += at;
+    });
+    S = red.sum(S);
+    N = red.sum(N);
+    P = red.sum(P);
+    R = red.sum(R);
+    const double phid = P > 0.0 ? fmin(fmax((cpd - S) / P, 0.0), 1.0) : 0.0;
+    // ||delta||_1 from the fraction before its rounding to float: the emitted norm is rounded once
+    if (threadIdx.x == 0) *theta_out = theta, *sgn_out = s, *nrm_out = static_cast<float>(fma(phid, R, N)), *phi_out = static_cast<float>(phid);
+}
+
 // ---- the step ------------------------------------------------------------------------------------------------------------------------
+enum Metric : int { kLinf = 0, kL2 = 1, kL1 = 2 };  // the three instances of step, commit and the launches
+
 struct StepSample {
     float l1, s1, l2, s2, alpha;
+    float phi1, phi2;  // kL1 only: the fraction of its room a coordinate AT theta takes (row 3 of the [4, 2B] scalars)
 };
 
+template <int M>
 __device__ __forceinline__ StepSample step_sample(const float *__restrict__ scal, int64_t B, int64_t b) {
     StepSample r;
     r.l1 = scal[b], r.l2 = scal[B + b];
     r.s1 = scal[2 * B + b], r.s2 = scal[3 * B + b];
     const float a1 = fmaxf(scal[4 * B + b], 1e-8f), a2 = fmaxf(scal[5 * B + b], 1e-8f);
     r.alpha = fminf(a1 / (a1 + a2), kAlphaMax);
+    if (M == kL1) r.phi1 = scal[6 * B + b], r.phi2 = scal[7 * B + b];
     return r;
 }
 
@@ -350,16 +474,30 @@ __device__ __forceinline__ float delta_l2(float v, float p, float mu) {
     return a != 0.0f ? -sgn(v) * tmin(mu * a, room(v, p)) : 0.0f;
 }
 
-template <bool L2>
+// L1: delta_i = -sign(v_i) m_i, m_i = r_i above theta, phi r_i (one f32 product) at theta, 0 below it - and 0 where v_i is 0 or NaN (no
+// comparison holds), so theta = 0 (infeasible, phi = 1) never moves a coordinate without a direction
+__device__ __forceinline__ float delta_l1(float v, float p, float theta, float phi) {
+    const float a = fabsf(v), r = room(v, p);
+    const float m = a > theta ? r : (a == theta && a != 0.0f ? phi * r : 0.0f);
+    return -sgn(v) * m;
+}
+
+template <int M>
 __device__ __forceinline__ float step_op(float x, float x0, float w, const StepSample &sm) {
     if (sm.s1 == 0.0f) return x;  // a sample without a hyperplane stays where it is
     const float v1 = sm.s1 * w, v2 = sm.s2 * w;
-    const float d1 = L2 ? delta_l2(v1, x, sm.l1) : -sgn(v1) * fminf(sm.l1, room(v1, x));
-    const float d2 = L2 ? delta_l2(v2, x0, sm.l2) : -sgn(v2) * fminf(sm.l2, room(v2, x0));
+    float d1, d2;
+    if constexpr (M == kL1) {
+        d1 = delta_l1(v1, x, sm.l1, sm.phi1);
+        d2 = delta_l1(v2, x0, sm.l2, sm.phi2);
+    } else {
+        d1 = M == kL2 ? delta_l2(v1, x, sm.l1) : -sgn(v1) * fminf(sm.l1, room(v1, x));
+        d2 = M == kL2 ? delta_l2(v2, x0, sm.l2) : -sgn(v2) * fminf(sm.l2, room(v2, x0));
+    }
     return tclamp((x + kEta * d1) * (1.0f - sm.alpha) + (x0 + kEta * d2) * sm.alpha, 0.0f, 1.0f);
 }
 
-template <int VEC, bool L2>
+template <int VEC, int M>
 __global__ __launch_bounds__(kBlock) void step_kernel(float *x, const float *__restrict__ x0, const float *__restrict__ w,
                                                       const float *__restrict__ scal, int64_t B, int64_t per_sample) {
     const int64_t n = B * per_sample;
@@ -375,16 +513,16 @@ __global__ __launch_bounds__(kBlock) void step_kernel(float *x, const float *__r
         const float xi[4] = {vx.x, vx.y, vx.z, vx.w}, oi[4] = {v0.x, v0.y, v0.z, v0.w}, wi[4] = {vw.x, vw.y, vw.z, vw.w};
         float out[4];
         if (base - b * per_sample + 4 <= per_sample) {  // the four elements belong to one sample
-            const StepSample sm = step_sample(scal, B, b);
+            const StepSample sm = step_sample<M>(scal, B, b);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) out[k] = step_op<L2>(xi[k], oi[k], wi[k], sm);
+            for (int k = 0; k < 4; ++k) out[k] = step_op<M>(xi[k], oi[k], wi[k], sm);
         } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) out[k] = step_op<L2>(xi[k], oi[k], wi[k], step_sample(scal, B, (base + k) / per_sample));  // base + k < n
+            for (int k = 0; k < 4; ++k) out[k] = step_op<M>(xi[k], oi[k], wi[k], step_sample<M>(scal, B, (base + k) / per_sample));  // base + k < n
         }
         reinterpret_cast<float4 *>(x)[v] = make_float4(out[0], out[1], out[2], out[3]);
     }
-    for (int64_t e = (nv << 2) + i; e < n; e += stride) x[e] = step_op<L2>(x[e], x0[e], w[e], step_sample(scal, B, e / per_sample));
+    for (int64_t e = (nv << 2) + i; e < n; e += stride) x[e] = step_op<M>(x[e], x0[e], w[e], step_sample<M>(scal, B, e / per_sample));
 }
 
 // ---- the check after the second forward ------------------------------------------------------------------------------------------------
@@ -432,8 +570,24 @@ __device__ __forceinline__ float commit_norm_l2(const float *x, const float *x0,
     return static_cast<float>(sqrt(red.sum(sq)));
 }
 
-// L2 = false: the distance is ||x - x0||_inf; true: ||x - x0||_2.  Everything else is one code.
-template <int VEC, bool L2>
+// ||x - x0||_1 of the sample at `off`: the |f32 differences| summed in double in the order of commit_norm_l2, rounded to float once
+template <bool VEC>
+__device__ __forceinline__ float commit_norm_l1(const float *x, const float *x0, int64_t off, int64_t per_sample) {
+    __shared__ double sh_sum[kSampleWaves];  // one reduction: it uses the first half of the reducer's buffer only
+    SampleReducer red{sh_sum};
+    double sa = 0.0;
+    for (int64_t e = static_cast<int64_t>(threadIdx.x) * 4; e < per_sample; e += kSampleBlock * 4) {
+        float pv[4], ov[4];
+        load4<VEC>(x + off, e, per_sample, pv);
+        load4<VEC>(x0 + off, e, per_sample, ov);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sa += static_cast<double>(fabsf(pv[j] - ov[j]));
+    }
+    return static_cast<float>(red.sum(sa));
+}
+
+// M picks the distance: ||x - x0||_inf, ||x - x0||_2 or ||x - x0||_1.  Everything else is one code.
+template <int VEC, int M>
 __global__ __launch_bounds__(kSampleBlock) void commit_kernel(const float *__restrict__ logits, const int64_t *__restrict__ labels, int K, float *x,
                                                               const float *__restrict__ x0, float *adv, float *res, int *__restrict__ pred,
                                                               int *__restrict__ flags, int *counter, int64_t per_sample) {
@@ -449,8 +603,10 @@ __global__ __launch_bounds__(kSampleBlock) void commit_kernel(const float *__res
     const int64_t off = static_cast<int64_t>(b) * per_sample;
     // the distance; the barrier inside also publishes sh_first / sh_nan
     float m;
-    if constexpr (L2)
+    if constexpr (M == kL2)
         m = commit_norm_l2<VEC == 4>(x, x0, off, per_sample);
+    else if constexpr (M == kL1)
+        m = commit_norm_l1<VEC == 4>(x, x0, off, per_sample);
     else
         m = commit_norm_linf<VEC>(x, x0, off, per_sample);
     const int64_t y = labels[b];
@@ -484,8 +640,8 @@ bool bad_shape(int64_t B, int64_t per_sample) {
     return B < 0 || per_sample < 0 || B > INT32_MAX / 2 || per_sample > INT32_MAX || (per_sample > 0 && B > INT64_MAX / per_sample);
 }
 
-// ---- the launches that differ between Linf and L2 in one template argument ---------------------------------------------------------------
-template <bool L2>
+// ---- the launches that differ between Linf, L2 and L1 in one template argument ------------------------------------------------------------
+template <int M>
 int launch_proj(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path, float *out,
                 void *stream) {
     if (bad_shape(B, per_sample) || per_sample < 1) return EE_ERR_SHAPE;
@@ -498,15 +654,17 @@ int launch_proj(const float *x, const float *x0, const float *w, const float *df
     const int nb = static_cast<int>(B);
     ProfScope prof(EE_K_FAB_PROJ, as_stream(stream));
     sample_launch(res, sample_vec(per_sample, x, x0, w), [&](auto RES, auto VEC) {
-        if constexpr (L2)
+        if constexpr (M == kL2)
             EE_LAUNCH((proj_l2_kernel<RES, VEC>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+        else if constexpr (M == kL1)
+            EE_LAUNCH((proj_l1_kernel<RES, VEC>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
         else
             EE_LAUNCH((proj_kernel<RES, VEC>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
     });
     return launch_status();
 }
 
-template <bool L2>
+template <int M>
 int launch_step(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
     if (bad_shape(B, per_sample)) return EE_ERR_SHAPE;
     const int64_t n = B * per_sample;
@@ -517,13 +675,13 @@ int launch_step(float *x, const float *x0, const float *w, const float *scal, in
     const unsigned blocks = grid_for(vec ? (n + 3) / 4 : n);
     ProfScope prof(EE_K_FAB_STEP, as_stream(stream));
     if (vec)
-        EE_LAUNCH((step_kernel<4, L2>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+        EE_LAUNCH((step_kernel<4, M>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
     else
-        EE_LAUNCH((step_kernel<1, L2>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
+        EE_LAUNCH((step_kernel<1, M>), dim3(blocks), dim3(kBlock), 0, as_stream(stream), x, x0, w, scal, B, per_sample);
     return launch_status();
 }
 
-template <bool L2>
+template <int M>
 int launch_commit(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res, int *pred,
                   int *flags, int *counter, int64_t per_sample, void *stream) {
     if (B < 0 || K < 2 || K > 65536 || bad_shape(B, per_sample)) return EE_ERR_SHAPE;
@@ -535,9 +693,9 @@ int launch_commit(const float *logits, const int64_t *labels, int B, int K, floa
     const dim3 grid(static_cast<unsigned>(B)), block(kSampleBlock);
     ProfScope prof(EE_K_FAB_COMMIT, as_stream(stream));
     if (sample_vec(per_sample, x, x0, adv))
-        EE_LAUNCH((commit_kernel<4, L2>), grid, block, 0, as_stream(stream), logits, labels, K, x, x0, adv, res, pred, flags, counter, per_sample);
+        EE_LAUNCH((commit_kernel<4, M>), grid, block, 0, as_stream(stream), logits, labels, K, x, x0, adv, res, pred, flags, counter, per_sample);
     else
-        EE_LAUNCH((commit_kernel<1, L2>), grid, block, 0, as_stream(stream), logits, labels, K, x, x0, adv, res, pred, flags, counter, per_sample);
+        EE_LAUNCH((commit_kernel<1, M>), grid, block, 0, as_stream(stream), logits, labels, K, x, x0, adv, res, pred, flags, counter, per_sample);
     return launch_status();
 }
 
@@ -559,28 +717,42 @@ EE_API int ee_fab_diff_f32(const float *logits, const int64_t *labels, const int
 
 EE_API int ee_fab_proj_linf_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path,
                                 float *out, void *stream) {
-    return launch_proj<false>(x, x0, w, df, B, per_sample, path, out, stream);
+    return launch_proj<kLinf>(x, x0, w, df, B, per_sample, path, out, stream);
 }
 
 EE_API int ee_fab_proj_l2_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path,
                               float *out, void *stream) {
-    return launch_proj<true>(x, x0, w, df, B, per_sample, path, out, stream);
+    return launch_proj<kL2>(x, x0, w, df, B, per_sample, path, out, stream);
 }
 
 EE_API int ee_fab_step_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
-    return launch_step<false>(x, x0, w, scal, B, per_sample, stream);
+    return launch_step<kLinf>(x, x0, w, scal, B, per_sample, stream);
 }
 
 EE_API int ee_fab_step_l2_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
-    return launch_step<true>(x, x0, w, scal, B, per_sample, stream);
+    return launch_step<kL2>(x, x0, w, scal, B, per_sample, stream);
 }
 
 EE_API int ee_fab_commit_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res, int *pred,
                              int *flags, int *counter, int64_t per_sample, void *stream) {
-    return launch_commit<false>(logits, labels, B, K, x, x0, adv, res, pred, flags, counter, per_sample, stream);
+    return launch_commit<kLinf>(logits, labels, B, K, x, x0, adv, res, pred, flags, counter, per_sample, stream);
 }
 
 EE_API int ee_fab_commit_l2_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res,
                                 int *pred, int *flags, int *counter, int64_t per_sample, void *stream) {
-    return launch_commit<true>(logits, labels, B, K, x, x0, adv, res, pred, flags, counter, per_sample, stream);
+    return launch_commit<kL2>(logits, labels, B, K, x, x0, adv, res, pred, flags, counter, per_sample, stream);
+}
+
+EE_API int ee_fab_proj_l1_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path,
+                              float *out, void *stream) {
+    return launch_proj<kL1>(x, x0, w, df, B, per_sample, path, out, stream);
+}
+
+EE_API int ee_fab_step_l1_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream) {
+    return launch_step<kL1>(x, x0, w, scal, B, per_sample, stream);
+}
+
+EE_API int ee_fab_commit_l1_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res,
+                                int *pred, int *flags, int *counter, int64_t per_sample, void *stream) {
+    return launch_commit<kL1>(logits, labels, B, K, x, x0, adv, res, pred, flags, counter, per_sample, stream);
 }

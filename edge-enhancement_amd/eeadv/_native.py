@@ -94,6 +94,10 @@ SIGNATURES = {
     "ee_fab_proj_l2_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_i, c_p, c_p],
     "ee_fab_step_l2_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_p],
     "ee_fab_commit_l2_f32": [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p],
+    # the L1 siblings: the same arguments (out / scal are [4, 2B])
+    "ee_fab_proj_l1_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_i, c_p, c_p],
+    "ee_fab_step_l1_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_p],
+    "ee_fab_commit_l1_f32": [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p],
     "ee_add_square_fwd_f32": [c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_add_square_bwd_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_square_draw_f32": [c_p, c_l, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],

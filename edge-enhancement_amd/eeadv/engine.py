@@ -12,7 +12,7 @@ torch.enable_grad() so an outer no_grad() does not matter; the result is a new d
 
 The evaluation attacks (APGD in Linf / L2 / L1, Square, FAB-T) each keep their device state in a run object with four methods - load(*inputs),
 start(model), body(model, n): n consecutive iterations, result() - and share one driver: `_prepare` (build, capture, cache, load, refresh) and
-`_drive` (eager run, or start + replays + result).  apgd_loop, apgd_l1_loop and fab_loop are argument checks, a cache key and one call of
+`_drive` (eager run, or start + replays + result).  apgd_loop, apgd_l1_loop, fab_loop and fab_l1_loop are argument checks, a cache key and one call of
 `_drive`; square_loop takes `_prepare` and keeps its own replay loop (early exit, eager remainder, finish); pgd_loop, with its probed tail,
 stands by itself ("The attack loops' driver").
 """
@@ -830,7 +830,7 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # FAB-T (Croce & Hein 2020; Linf or L2, targeted, eta = 1.05, beta = 0.9, alpha_max = 0.1, one run from x0, no EOT): DESIGN.md sections
-# 13 and 17
+# 13 and 17 (L1: fab_l1_loop at the end of this file, section 20)
 # ---------------------------------------------------------------------------------------------------------------------------------------
 FAB_NORMS = ("Linf", "L2")
 
@@ -860,16 +860,19 @@ class _FabRun:
     run) and `iteration` (forward, diff, backward, projection, step, forward, commit: what a captured graph replays).  No host read anywhere.
     `eps` only thresholds `result`: the graph does not know it, so a cached run takes the caller's through `load`."""
 
+    SCAL_ROWS = 3  # rows of the projection scalars [SCAL_ROWS, 2B]
+    metric_ops = staticmethod(_fab_ops)  # norm -> (projection, step, commit)
+
     def __init__(self, x0, y, n_iter, eps, path="auto", norm="Linf"):
         B, dev = x0.shape[0], x0.device
         self.n_iter, self.eps, self.path, self.norm = int(n_iter), float(eps), path, norm
-        self.proj, self.step_, self.commit_ = _fab_ops(norm)
+        self.proj, self.step_, self.commit_ = self.metric_ops(norm)
         self.x = torch.empty_like(x0).requires_grad_(True)
         self.x0, self.adv = torch.empty_like(x0), torch.empty_like(x0)
         self.y = torch.empty(B, dtype=torch.int64, device=dev)
         self.t = torch.empty(B, dtype=torch.int64, device=dev)
         self.res = torch.empty(B, dtype=torch.float32, device=dev)
-        self.scal = torch.zeros((3, 2 * B), dtype=torch.float32, device=dev)
+        self.scal = torch.zeros((self.SCAL_ROWS, 2 * B), dtype=torch.float32, device=dev)
         self.pred = torch.zeros(B, dtype=torch.int32, device=dev)
         self.flags = torch.zeros(B, dtype=torch.int32, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -933,3 +936,41 @@ def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", no
     chunk = _chunk(n_iter)
     key = ("fab", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk, norm)
     return _drive(model, key, lambda: _FabRun(x0, y, n_iter, eps, path, norm), (x0, y, targets, eps), n_iter, chunk, use_graph)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# FAB-T in the L1 threat model: a door of its own - fab_loop(norm="L1") and _FabRun(norm="L1") stay refused
+# ---------------------------------------------------------------------------------------------------------------------------------------
+class _FabL1Run(_FabRun):
+    """_FabRun with the three L1 launches and their [4, 2B] scalars (theta, sign, ||delta||_1, phi); state, start, iteration and result
+    are _FabRun's, and `res` holds L1 distances."""
+    SCAL_ROWS = ops.FAB_L1_ROWS
+
+    @staticmethod
+    def metric_ops(norm):
+        return ops.fab_proj_l1, ops.fab_step_l1_, ops.fab_commit_l1_
+
+    def __init__(self, x0, y, n_iter, eps, path="auto"):
+        super().__init__(x0, y, n_iter, eps, path, "L1")
+
+
+def fab_l1_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto"):
+    """fab_loop in the L1 threat model: one FAB-T run of n_iter iterations from x0 towards the classes `targets` [B], the projections
+    the least-||.||_1 ones (ee_fab_proj_l1_f32: a fill by descending |w_i|, ties sharing one fraction), alpha from their L1 lengths.
+    Returns (x_adv, robust, norm): norm [B] is the smallest ||adv - x0||_1 over the adversarial iterates (+inf if there was none),
+    robust = not (norm <= eps) with eps the L1 radius, x_adv is x0 with the non-robust rows replaced by that closest point.  Eager, or -
+    under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of its own (the key shares nothing with fab_loop's, so Linf, L2 and
+    L1 graphs of one shape coexist); both give the same bits, and so do the paths ('auto', 'resident', 'streaming')."""
+    model = _unwrap(model)
+    x0 = x0.detach().contiguous()
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("FAB needs n_iter >= 1")
+    ops._sample_path(path, "FAB projection")
+    if x0.shape[0] == 0:
+        return _empty_result(x0, torch.float32)
+    if use_graph is None:
+        use_graph = graphs_enabled()
+    chunk = _chunk(n_iter)
+    key = ("fab_l1", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk)
+    return _drive(model, key, lambda: _FabL1Run(x0, y, n_iter, eps, path), (x0, y, targets, eps), n_iter, chunk, use_graph)

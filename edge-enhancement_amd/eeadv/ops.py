@@ -643,6 +643,7 @@ def sqatk_step_l2_(x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off
 # ---- FAB-T (ee_fab.hip) ----------------------------------------------------------------------------------------------
 FAB_ADV, FAB_IMPROVED = 1, 2  # bits of the flags of fab_commit_ (EE_FAB_*)
 FAB_LAMBDA, FAB_SIGN, FAB_NORM = range(3)  # rows of the projection scalars [3, 2B] (row 0 is mu in L2)
+FAB_THETA, FAB_PHI, FAB_L1_ROWS = 0, 3, 4  # L1: the scalars are [4, 2B], row 0 is theta and row 3 the fraction phi taken at theta
 
 
 def fab_diff(logits, labels, targets):
@@ -657,14 +658,14 @@ def fab_diff(logits, labels, targets):
     return df, d, pred
 
 
-def _fab_proj(fn, name, x, x0, w, df, path, out):
+def _fab_proj(fn, name, x, x0, w, df, path, out, rows=3):
     B = x.shape[0]
     px = _chk(x, torch.float32, "x")
     p0 = _chk(x0, torch.float32, "x0", x.shape)
     pw = _chk(w, torch.float32, "w", x.shape)
     pd = _chk(df, torch.float32, "df", (B,))
-    out = torch.empty((3, 2 * B), dtype=torch.float32, device=x.device) if out is None else out
-    po = _chk(out, torch.float32, "out", (3, 2 * B))
+    out = torch.empty((rows, 2 * B), dtype=torch.float32, device=x.device) if out is None else out
+    po = _chk(out, torch.float32, "out", (rows, 2 * B))
     if B:
         N.check(fn(px, p0, pw, pd, B, x.numel() // B, _sample_path(path, "FAB projection"), po, _stream()), name)
     return out
@@ -681,12 +682,18 @@ def fab_proj_l2(x, x0, w, df, path="auto", out=None):
     return _fab_proj(N.lib.ee_fab_proj_l2_f32, "ee_fab_proj_l2_f32", x, x0, w, df, path, out)
 
 
-def _fab_step(fn, name, x, x0, w, scal):
+def _fab_step(fn, name, x, x0, w, scal, rows=3):
     B = x.shape[0]
     px = _chk(x, torch.float32, "x")
     N.check(fn(px, _chk(x0, torch.float32, "x0", x.shape), _chk(w, torch.float32, "w", x.shape),
-               _chk(scal, torch.float32, "scal", (3, 2 * B)), B, x.numel() // B if B else 0, _stream()), name)
+               _chk(scal, torch.float32, "scal", (rows, 2 * B)), B, x.numel() // B if B else 0, _stream()), name)
     return x
+
+
+def fab_proj_l1(x, x0, w, df, path="auto", out=None):
+    """fab_proj_linf for the least-L1 projections: the scalars [4, 2B], rows theta, sign, ||delta||_1, phi (delta_i = -sign(s w_i) m_i,
+    m_i = r_i where |w_i| > theta, phi r_i where |w_i| == theta, 0 below)."""
+    return _fab_proj(N.lib.ee_fab_proj_l1_f32, "ee_fab_proj_l1_f32", x, x0, w, df, path, out, FAB_L1_ROWS)
 
 
 def fab_step_(x, x0, w, scal):
@@ -697,6 +704,11 @@ def fab_step_(x, x0, w, scal):
 def fab_step_l2_(x, x0, w, scal):
     """The FAB step in place on x [B, ...] from the scalars [3, 2B] of fab_proj_l2."""
     return _fab_step(N.lib.ee_fab_step_l2_f32, "ee_fab_step_l2_f32", x, x0, w, scal)
+
+
+def fab_step_l1_(x, x0, w, scal):
+    """The FAB step in place on x [B, ...] from the scalars [4, 2B] of fab_proj_l1."""
+    return _fab_step(N.lib.ee_fab_step_l1_f32, "ee_fab_step_l1_f32", x, x0, w, scal, FAB_L1_ROWS)
 
 
 def _fab_commit(fn, name, logits, labels, x, x0, adv, res, pred, flags, counter):
@@ -717,6 +729,11 @@ def fab_commit_(logits, labels, x, x0, adv, res, pred, flags, counter):
 def fab_commit_l2_(logits, labels, x, x0, adv, res, pred, flags, counter):
     """fab_commit_ with res [B] holding L2 distances."""
     return _fab_commit(N.lib.ee_fab_commit_l2_f32, "ee_fab_commit_l2_f32", logits, labels, x, x0, adv, res, pred, flags, counter)
+
+
+def fab_commit_l1_(logits, labels, x, x0, adv, res, pred, flags, counter):
+    """fab_commit_ with res [B] holding L1 distances."""
+    return _fab_commit(N.lib.ee_fab_commit_l1_f32, "ee_fab_commit_l1_f32", logits, labels, x, x0, adv, res, pred, flags, counter)
 
 
 # ---- sample pools of the attack cascade (ee_cascade.hip) -------------------------------------------------------------

@@ -335,7 +335,7 @@ def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None,
 # ---------------------------------------------------------------------------------------------------------
 # APGD in the L1 threat model (Croce & Hein 2021, "Mind the box"): doors of their own - APGD(norm="L1") stays refused.  One run, no
 # momentum, the sparse sign step, the exact projection onto ball and box, the sparsity / step-size checkpoints.
-# The large-radius warm-up, restarts, EOT, L1 FAB-T / Square and L1 inside Cascade / Rand are NOT here.
+# The large-radius warm-up, restarts, EOT, L1 Square and L1 inside Cascade / Rand are NOT here.
 # ---------------------------------------------------------------------------------------------------------
 def _f32c(v, dtype):
     """The float32 constant v in `dtype`: the constants of the L1 run are float32 ones in every dtype."""
@@ -703,8 +703,8 @@ def Square(model, args, inputs, targets, n_queries=5000, seed=None, norm="Linf")
 # FAB-T (Croce & Hein 2020, Linf, targeted): the minimum-norm member of AutoAttack's `standard` version - it walks along linearised
 # decision boundaries instead of ascending a loss.  Built from the published algorithm with the constants `standard`
 # runs it with (eta = 1.05, beta = 0.9, alpha_max = 0.1, 9 target classes, one run from the clean point: deterministic).  norm="L2" is
-# the same iteration in the other metric.  Untargeted FAB, L1, restarts with the random start, the final line
-# search and EOT for FAB are NOT here.
+# the same iteration in the other metric; L1 comes through FAB_T_L1 below (section 20).  Untargeted FAB, restarts
+# with the random start, the final line search and EOT for FAB are NOT here.
 # ---------------------------------------------------------------------------------------------------------
 _FAB_ETA, _FAB_BETA, _FAB_ALPHA_MAX = 1.05, 0.9, 0.1
 
@@ -781,12 +781,22 @@ def _check_fab_norm(norm):
     return engine._check_norm(norm, engine.FAB_NORMS, "FAB")
 
 
+def _linf_norms(v):
+    return v.abs().max(dim=1)[0]
+
+
 def _fab_host_iteration(model, x, x0, y, t, adv, res, norm="Linf"):
     """One FAB-T iteration in plain torch ops, in the input's dtype: (x, adv, res) -> (x, adv, res, info).  `info` holds every
     intermediate quantity (df, w, the projection scalars, alpha, the stepped point, pred, the flags).  norm: 'Linf' or 'L2' - the metric of
     the two projections (lam1 / lam2 then hold mu), of alpha and of nrm / res."""
-    in_l2 = _check_fab_norm(norm) == "L2"
-    project, delta = (_fab_projection_l2, _fab_delta_l2) if in_l2 else (_fab_projection, _fab_delta)
+    if _check_fab_norm(norm) == "L2":
+        return _fab_iteration(model, x, x0, y, t, adv, res, _fab_projection_l2, _fab_delta_l2, _l2_norms)
+    return _fab_iteration(model, x, x0, y, t, adv, res, _fab_projection, _fab_delta, _linf_norms)
+
+
+def _fab_iteration(model, x, x0, y, t, adv, res, project, delta, dist):
+    """The iteration in the metric of (project, delta, dist): project(p, w, c) -> (lambda, s, ||delta||, *more) per row, delta(p, w, lambda,
+    s, *more) rebuilds the vector from those scalars (L1 has one more, phi), dist(v) is the row norm that nrm / res are measured in."""
     B = x0.shape[0]
     rows = torch.arange(B, device=x0.device)
     xc = x.detach().clone().requires_grad_()
@@ -801,11 +811,10 @@ def _fab_host_iteration(model, x, x0, y, t, adv, res, norm="Linf"):
     safe_w = torch.where(on.view(-1, 1), w, torch.ones_like(w))  # rows without a hyperplane are computed on stand-ins and masked below
     c1 = torch.where(on, df, torch.ones_like(df))
     c2 = torch.where(on, df + (safe_w * (x0f - xf)).sum(dim=1), torch.ones_like(df))  # a sum of differences: <w, x0> - <w, x> would cancel
-    l1, s1, n1 = project(xf, safe_w, c1)
-    l2, s2, n2 = project(x0f, safe_w, c2)
     zero = torch.zeros_like(df)
-    l1, s1, n1, l2, s2, n2 = (torch.where(on, q, zero) for q in (l1, s1, n1, l2, s2, n2))
-    d1, d2 = delta(xf, safe_w, l1, s1), delta(x0f, safe_w, l2, s2)
+    l1, s1, n1, *more1 = (torch.where(on, q, zero) for q in project(xf, safe_w, c1))
+    l2, s2, n2, *more2 = (torch.where(on, q, zero) for q in project(x0f, safe_w, c2))
+    d1, d2 = delta(xf, safe_w, l1, s1, *more1), delta(x0f, safe_w, l2, s2, *more2)
     a1, a2 = n1.clamp_min(1e-8), n2.clamp_min(1e-8)
     alpha = torch.minimum(a1 / (a1 + a2), torch.full_like(a1, _FAB_ALPHA_MAX))
     al = alpha.view(-1, 1)
@@ -815,13 +824,15 @@ def _fab_host_iteration(model, x, x0, y, t, adv, res, norm="Linf"):
         z2 = model(x_step.view(x0.shape))
     pred = torch.sort(z2, dim=1, descending=True, stable=True)[1][:, 0]
     is_adv = (pred != y) & ~torch.isnan(z2).any(dim=1)
-    nrm = _l2_norms(x_step - x0f) if in_l2 else (x_step - x0f).abs().max(dim=1)[0]
+    nrm = dist(x_step - x0f)
     improved = is_adv & (nrm < res)
     adv = torch.where(improved.view(-1, 1), x_step, adv.reshape(B, -1)).view(x0.shape)
     res = torch.where(improved, nrm, res)
     x_new = torch.where(is_adv.view(-1, 1), x0f + _FAB_BETA * (x_step - x0f), x_step).view(x0.shape)
     info = dict(df=df, w=w, lam1=l1, s1=s1, n1=n1, lam2=l2, s2=s2, n2=n2, alpha=alpha, x_step=x_step.view(x0.shape), pred=pred, is_adv=is_adv,
                 improved=improved, nrm=nrm, enabled=on)
+    if more1:
+        info.update(phi1=more1[0], phi2=more2[0])
     return x_new, adv, res, info
 
 
@@ -851,23 +862,114 @@ def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, 
     x0 = inputs.detach()
     eps = float(args.epsilon)
     kw = {} if _check_fab_norm(norm) == "Linf" else {"norm": norm}  # the Linf call is the call it always was
+    return _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, "FAB_T",
+                        lambda t: engine.fab_loop(model, x0, targets, t, n_iter, eps, **kw)[::2],
+                        lambda t: _fab_host(model, x0, targets, t, n_iter, **kw))
+
+
+def _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, what, device_run, host_run):
+    """The runs of FAB_T / FAB_T_L1 over the target classes and their combination; device_run(t) / host_run(t) -> (adv, norm) of one run
+    towards the classes t [B]."""
     n_t = min(int(n_target_classes), int(nclass) - 1)
-    on_dev = runtime.require_device(x0, "FAB_T")
-    order = _class_order(model, x0, n_t, "FAB_T", order)
+    on_dev = runtime.require_device(x0, what)
+    order = _class_order(model, x0, n_t, what, order)
     shape = (-1,) + (1,) * (x0.dim() - 1)
     x_adv = x0.clone()
     inf = torch.full((x0.shape[0],), _INF, dtype=torch.float32 if on_dev else x0.dtype, device=x0.device)
     norm = torch.where(order[:, 0] != targets, torch.zeros_like(inf), inf)
     for j in range(1, n_t + 1):
         t = order[:, j].contiguous()
-        if on_dev:
-            xa, _, nj = engine.fab_loop(model, x0, targets, t, n_iter, eps, **kw)
-        else:
-            xa, nj = _fab_host(model, x0, targets, t, n_iter, **kw)
+        xa, nj = device_run(t) if on_dev else host_run(t)
         closer = (nj < norm) & (nj <= eps)
         x_adv = torch.where(closer.view(shape), xa, x_adv)
         norm = torch.minimum(norm, nj)
     return x_adv, ~(norm <= eps), norm
+
+
+# ---------------------------------------------------------------------------------------------------------
+# FAB-T in the L1 threat model (DESIGN.md section 20): doors of their own - FAB_T(norm="L1") and _fab_host(norm="L1") stay refused.  The
+# iteration is FAB-T's; the projection is the least-||.||_1 one, a fill by descending |w_i| in which every coordinate tied at the
+# threshold takes the same fraction of its room.  Untargeted FAB, restarts, the final line search, L1 Square and L1 inside Cascade are
+# NOT here.
+# ---------------------------------------------------------------------------------------------------------
+def _l1_norms(v):
+    """sum_i |v_i| per row, summed in float64 and rounded to v's dtype once (as the commit kernel does)."""
+    return v.abs().to(torch.float64).sum(dim=1).to(v.dtype)
+
+
+def _fab_projection_l1(p, w, c):
+    """_fab_projection for a delta of least ||.||_1: (theta, s, ||delta||_1, phi) per row, delta_i = -sign(s w_i) m_i with m_i = r_i where
+    a_i = |w_i| > theta, phi r_i where a_i == theta and 0 below.  Sort by a descending, cumulative sums of a_i r_i; theta is the a at which
+    they first reach c' = |c|, and the coordinates AT theta share what is left: phi = (c' - sum_{a_i > theta} a_i r_i) / sum_{a_i == theta}
+    a_i r_i.  The sums are taken in float64, as csrc/ee_fab.hip takes them, and rounded to p's dtype once.  c = 0: theta = inf (nothing
+    moves); c' > sum a_i r_i: theta = 0, phi = 1 (every moving coordinate at its bound)."""
+    dt = p.dtype
+    s = torch.where(c >= 0, torch.ones_like(c), -torch.ones_like(c))
+    v = s.view(-1, 1) * w
+    a = v.abs()
+    r = torch.where(v > 0, p, torch.where(v < 0, 1 - p, torch.zeros_like(p))).clamp_min(0)
+    cp = c.abs().to(torch.float64)
+    r64 = r.to(torch.float64)
+    prod = a.to(torch.float64) * r64
+    a_s, order = torch.sort(a, dim=1, descending=True, stable=True)
+    cum = torch.cumsum(prod.gather(1, order), dim=1)
+    k = (cum < cp.view(-1, 1)).sum(dim=1, keepdim=True).clamp_max(a.shape[1] - 1)  # the first coordinate at which the fill reaches c'
+    theta = a_s.gather(1, k).squeeze(1)
+    above, at = a > theta.view(-1, 1), a == theta.view(-1, 1)
+    zero = torch.zeros_like(prod)
+    S, P = torch.where(above, prod, zero).sum(dim=1), torch.where(at, prod, zero).sum(dim=1)
+    N, R = torch.where(above, r64, zero).sum(dim=1), torch.where(at, r64, zero).sum(dim=1)
+    phi = torch.where(P > 0, ((cp - S) / torch.where(P > 0, P, torch.ones_like(P))).clamp(0, 1), torch.zeros_like(P))
+    n = N + phi * R
+    infeasible = cp > cum[:, -1]
+    theta = torch.where(infeasible, torch.zeros_like(theta), theta)
+    phi = torch.where(infeasible, torch.ones_like(phi), phi)
+    n = torch.where(infeasible, torch.where(a != 0, r64, zero).sum(dim=1), n)
+    on_plane = cp == 0
+    theta = torch.where(on_plane, torch.full_like(theta, _INF), theta)
+    phi = torch.where(on_plane, torch.zeros_like(phi), phi)
+    n = torch.where(on_plane, torch.zeros_like(n), n)
+    return theta, s, n.to(dt), phi.to(dt)
+
+
+def _fab_delta_l1(p, w, theta, s, phi):
+    v = s.view(-1, 1) * w
+    a = v.abs()
+    r = torch.where(v > 0, p, torch.where(v < 0, 1 - p, torch.zeros_like(p))).clamp_min(0)
+    th = theta.view(-1, 1)
+    m = torch.where(a > th, r, torch.where((a == th) & (a != 0), phi.view(-1, 1) * r, torch.zeros_like(r)))
+    return -torch.sign(v) * m
+
+
+def _fab_l1_host_iteration(model, x, x0, y, t, adv, res):
+    """_fab_host_iteration in the L1 threat model: lam1 / lam2 of `info` hold theta, and phi1 / phi2 the fractions."""
+    return _fab_iteration(model, x, x0, y, t, adv, res, _fab_projection_l1, _fab_delta_l1, _l1_norms)
+
+
+def _fab_l1_host(model, x0, y, t, n_iter, trace=None):
+    """_fab_host in the L1 threat model: the iteration of engine.fab_l1_loop in plain torch ops, in the input's dtype.  Returns (adv, res)."""
+    x, adv = x0.clone(), x0.clone()
+    res = torch.full((x0.shape[0],), _INF, dtype=x0.dtype, device=x0.device)
+    for _ in range(int(n_iter)):
+        x, adv, res, info = _fab_l1_host_iteration(model, x, x0, y, t, adv, res)
+        if trace is not None:
+            info.update(x=x, adv=adv, res=res)
+            trace.append({k: v.clone() for k, v in info.items()})
+    return adv, res
+
+
+def FAB_T_L1(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, order=None):
+    """FAB_T in the L1 threat model (args.epsilon is the L1 radius): one run per target class as FAB_T takes them, each on the whole batch
+    from the clean point.  Returns (x_adv, robust, norm): norm [B] is the smallest ||adv - x0||_1 over all runs (+inf if none found an
+    adversarial point, 0 for a sample the clean forward already misclassifies), robust = not (norm <= args.epsilon), and x_adv is the
+    inputs with every non-robust sample replaced by the point that attains its norm.  Deterministic.  Two departures from the public
+    projection_l1: coordinates of equal |w_i| at the threshold all take the same fraction of their room (the public
+    code fills them in the order its argsort returns - the L1 length is the same), and a coordinate takes part exactly when w_i != 0."""
+    x0 = inputs.detach()
+    eps = float(args.epsilon)
+    return _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, "FAB_T_L1",
+                        lambda t: engine.fab_l1_loop(model, x0, targets, t, n_iter, eps)[::2],
+                        lambda t: _fab_l1_host(model, x0, targets, t, n_iter))
 
 
 class LabelSmoothLoss(torch.nn.Module):

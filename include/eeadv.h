@@ -515,6 +515,34 @@ int ee_fab_step_l2_f32(float *x, const float *x0, const float *w, const float *s
 int ee_fab_commit_l2_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res,
                          int *pred, int *flags, int *counter, int64_t per_sample, void *stream);
 
+/* ---- FAB-T in the L1 threat model.  The iteration, the state, the flags, the paths and ee_fab_diff_f32 are the
+ * ones above; three launches take the place of their Linf siblings and record under the same EE_K_FAB_* families.  res then holds
+ * ||adv - x0||_1, and scal is [4, 2B]: rows theta, sign, ||delta||_1, phi. */
+
+/* The scalars of the two box-constrained L1 projections of every sample, problems and degenerate-sample rules as in
+ * ee_fab_proj_linf_f32: delta = a vector of least ||.||_1 with <w, p + delta> = <w, p> - c and 0 <= p + delta <= 1 - a fractional-knapsack
+ * fill by descending a_i = |v_i| (v = s w, rooms r_i as above).  With F(T) = sum_{a_i >= T} a_i r_i:  c' > sum_{a_i != 0} a_i r_i
+ * (infeasible: every moving coordinate goes to its bound): theta = 0, phi = 1, norm = sum_{a_i != 0} r_i;  otherwise theta = the largest
+ * float T with F(T) >= c' (one of the a_i; 31 steps over the bit pattern, no sort), phi = clamp((c' - sum_{a_i > theta} a_i r_i) /
+ * sum_{a_i == theta} a_i r_i, 0, 1), and delta_i = -sign(v_i) m_i with m_i = r_i where a_i > theta, phi r_i where a_i == theta (every
+ * coordinate tied at theta takes the same fraction of its room), 0 where a_i < theta or v_i == 0.  out[0][q] = theta, out[1][q] = s,
+ * out[2][q] = ||delta||_1 = (float)(sum_{a_i > theta} r_i + phi sum_{a_i == theta} r_i) with phi before its rounding to float,
+ * out[3][q] = phi.  A sample without a hyperplane: theta = 0, s = 0, norm = 0, phi = 0 in both problems; c = 0 or not finite in problem
+ * B + b alone: theta = +inf, s = +1, norm = 0, phi = 0.  All sums in double (the products a_i r_i are exact there) in one fixed order:
+ * both paths and both access widths return the same bits.  One workgroup of 512 threads per problem; resident up to 12288 elements,
+ * streaming for any size. */
+int ee_fab_proj_l1_f32(const float *x, const float *x0, const float *w, const float *df, int64_t B, int64_t per_sample, int path, float *out,
+                       void *stream);
+
+/* ee_fab_step_f32 with the deltas of ee_fab_proj_l1_f32, rebuilt from scal [4, 2B]: m_i = r_i above theta_k, phi_k r_i (one f32 product)
+ * at theta_k, 0 below it and where w_i is 0 or NaN; a_k, alpha, the convex combination, the clamp and the s1 = 0 rule are unchanged. */
+int ee_fab_step_l1_f32(float *x, const float *x0, const float *w, const float *scal, int64_t B, int64_t per_sample, void *stream);
+
+/* ee_fab_commit_f32 with n = ||x - x0||_1: the |f32 differences| summed in double in the order of ee_fab_commit_l2_f32, rounded to float
+ * once.  Vector and element-wise accesses return the same bits.  Everything else is ee_fab_commit_f32's. */
+int ee_fab_commit_l1_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res,
+                         int *pred, int *flags, int *counter, int64_t per_sample, void *stream);
+
 /* CannyFilter_BPDA (utils/core.py:386-505; AWP configs): no alpha mask, NMS by multiplication, thresholds through
  * To_compare (core.py:329-358), hysteresis through To_eq (core.py:361-382).  thresholds given, hysteresis=True.
  *   forward: edge, thin (the thinned magnitude), t2 (the {0, .5, 1} threshold map) [B,1,H,W]; thin / t2 feed the backward.
@@ -1033,9 +1061,9 @@ int ee_cascade_resolve_f32(const uint8_t *robust, const int64_t *id, const float
 #define EE_K_SQATK_MARGIN 24 /* ee_sqatk_margin_f32 */
 #define EE_K_SQATK_STEP 25   /* ee_sqatk_step_f32 */
 #define EE_K_FAB_DIFF 26     /* ee_fab_diff_f32 */
-#define EE_K_FAB_PROJ 27     /* ee_fab_proj_linf_f32, ee_fab_proj_l2_f32 */
-#define EE_K_FAB_STEP 28     /* ee_fab_step_f32, ee_fab_step_l2_f32 */
-#define EE_K_FAB_COMMIT 29   /* ee_fab_commit_f32, ee_fab_commit_l2_f32 */
+#define EE_K_FAB_PROJ 27     /* ee_fab_proj_linf_f32, ee_fab_proj_l2_f32, ee_fab_proj_l1_f32 */
+#define EE_K_FAB_STEP 28     /* ee_fab_step_f32, ee_fab_step_l2_f32, ee_fab_step_l1_f32 */
+#define EE_K_FAB_COMMIT 29   /* ee_fab_commit_f32, ee_fab_commit_l2_f32, ee_fab_commit_l1_f32 */
 #define EE_K_COUNT 30
 int ee_prof_enable(int on);
 /* records one empty start/stop bracket on `stream` (family EE_K_EMPTY): callers subtract its mean from the other

@@ -10,9 +10,10 @@ on a gradient and an iterate taken from a real run): CUDA events around 50 launc
 untrained: labels are their own clean predictions.
 
 --norm L2 times the L2 iteration (engine.fab_loop(norm="L2"), eps = 0.5) and the L2 projection launch beside the Linf ones, in the same
-run, the three attacks alternating.
+run, the three attacks alternating.  --norm L1 times the L1 iteration (engine.fab_l1_loop, eps = 12) and the L1 projection launch beside
+the Linf and the L2 ones, in the same run, the four attacks alternating.
 
-    python scripts/fab_probe.py [reps] [--norm Linf|L2]      -> a few text lines, then one JSON line per model
+    python scripts/fab_probe.py [reps] [--norm Linf|L2|L1]   -> a few text lines, then one JSON line per model
 """
 import json
 import os
@@ -35,11 +36,12 @@ def main():
     norm = "Linf"
     if "--norm" in argv:
         k = argv.index("--norm")
-        if k + 1 >= len(argv) or argv[k + 1] not in engine.FAB_NORMS:
-            raise SystemExit("fab_probe: --norm takes one of %s" % (list(engine.FAB_NORMS),))
+        if k + 1 >= len(argv) or argv[k + 1] not in engine.FAB_NORMS + ("L1",):
+            raise SystemExit("fab_probe: --norm takes one of %s" % (list(engine.FAB_NORMS) + ["L1"],))
         norm = argv[k + 1]
         del argv[k:k + 2]
-    l2 = norm == "L2"
+    l1 = norm == "L1"
+    l2 = norm == "L2" or l1  # the L1 run is measured beside both
     reps = int(argv[0]) if argv else 7
     dev = torch.device("cuda", 0)
     eps = 16 / 255
@@ -74,6 +76,8 @@ def main():
         runs = {"pgd": lambda k: A.PGD(m, Args, x, y, k, 2 / 255), "fab_t": lambda k: engine.fab_loop(m, x, y, t, k, eps)}
         if l2:
             runs["fab_t_l2"] = lambda k: engine.fab_loop(m, x, y, t, k, 0.5, norm="L2")
+        if l1:
+            runs["fab_t_l1"] = lambda k: engine.fab_l1_loop(m, x, y, t, k, 12.0)
         for fn in runs.values():  # captures and warm-up of both lengths
             for k in (100, 20, 100, 20):
                 fn(k)
@@ -134,6 +138,24 @@ def main():
                 out["proj_l2_%s_us" % path] = round(1e3 * median([timed(launch) for _ in range(reps)]) / 50, 2)
             res = engine.fab_loop(m, x, y, t, 100, 0.5, norm="L2")
             out["fab_t_l2_non_robust_after_one_target"] = round(1.0 - float(res[1].float().mean()), 3)
+        if l1:
+            out["fab_l1_over_linf"] = round(out["fab_t_l1_iter_ms"] / out["fab_t_iter_ms"], 4)
+            out["fab_l1_over_l2"] = round(out["fab_t_l1_iter_ms"] / out["fab_t_l2_iter_ms"], 4)
+            out["fab_l1_minus_linf_us_per_iter"] = round(1e3 * (out["fab_t_l1_iter_ms"] - out["fab_t_iter_ms"]), 1)
+            run1 = engine._FabL1Run(x, y, 3, 12.0)  # the L1 projection launch on the state of an L1 run's third iteration
+            run1.load(x, y, t)
+            run1.start(m)
+            for _ in range(2):
+                run1.iteration(m)
+            w1 = engine.input_gradient(m, run1.x, run1.spec).contiguous()
+            x1 = run1.x.detach()
+            for path in ("resident", "streaming"):
+                launch = lambda: [ops.fab_proj_l1(x1, run1.x0, w1, run1.df, path, run1.scal) for _ in range(50)]
+                launch()
+                torch.cuda.synchronize()
+                out["proj_l1_%s_us" % path] = round(1e3 * median([timed(launch) for _ in range(reps)]) / 50, 2)
+            res = engine.fab_l1_loop(m, x, y, t, 100, 12.0)
+            out["fab_t_l1_non_robust_after_one_target"] = round(1.0 - float(res[1].float().mean()), 3)
         print("%s: PGD %.4f ms/iter + eval forward %.4f ms = %.4f ms; FAB-T %.4f ms/iter (x%.3f, +%.1f us); projection launch %.1f us resident, "
               "%.1f us streaming" % (name, out["pgd_iter_ms"], out["eval_fwd_ms"], shared, out["fab_t_iter_ms"], out["fab_over_shared"],
                                      out["fab_extra_us_per_iter"], out["proj_resident_us"], out["proj_streaming_us"]), flush=True)
@@ -141,6 +163,10 @@ def main():
             print("%s: L2 FAB-T %.4f ms/iter (x%.3f of the Linf iteration, %+.1f us); L2 projection launch %.1f us resident, %.1f us streaming"
                   % (name, out["fab_t_l2_iter_ms"], out["fab_l2_over_linf"], out["fab_l2_minus_linf_us_per_iter"], out["proj_l2_resident_us"],
                      out["proj_l2_streaming_us"]), flush=True)
+        if l1:
+            print("%s: L1 FAB-T %.4f ms/iter (x%.3f of the Linf iteration, %+.1f us; x%.3f of the L2 one); L1 projection launch %.1f us resident, "
+                  "%.1f us streaming" % (name, out["fab_t_l1_iter_ms"], out["fab_l1_over_linf"], out["fab_l1_minus_linf_us_per_iter"],
+                                         out["fab_l1_over_l2"], out["proj_l1_resident_us"], out["proj_l1_streaming_us"]), flush=True)
         print(json.dumps(out), flush=True)
 
 
