@@ -23,15 +23,14 @@
 // from tau and sg) share, so the two return the same bits.  Every loop has a trip count fixed by per_sample and the launch shape; the
 // branches around the searches are taken on values the whole workgroup holds alike.
 // The output is written in the final pass only, each element by the thread that read it.
+// The projection itself - coordinate, search, segment solve, final pass - is ee_l1_proj.hpp's, shared with ee_sqatk_l1.hip.
 #include <math.h>
 
-#include "ee_sample.hpp"
+#include "ee_l1_proj.hpp"
 
 namespace {
 
 using namespace ee;
-
-__device__ __forceinline__ uint32_t abs_bits(float g) { return __float_as_uint(g) & 0x7FFFFFFFu; }
 
 // the sparse sign step of one element; the scalars are filled in as they become known
 struct L1StepOp {
@@ -42,18 +41,6 @@ struct L1StepOp {
         const float s = sgn(g);  // a zero entry rests whatever sg is (m = 0 makes sg step * 1e10, which may overflow)
         return (take && s != 0.0f && abs_bits(g) >= tau) ? x + sg * s : x;
     }
-};
-
-// one coordinate of the projection problem: a = |u - x0|, lo = how far u lies outside the box (never above a), w keeps the sign
-struct L1Coord {
-    float w, a, lo;
-    __device__ __forceinline__ L1Coord(float w_, float lo_) : w(w_), a(fabsf(w_)), lo(lo_) {}
-    static __device__ __forceinline__ L1Coord of(float u, float x0) {
-        const float w = u - x0;
-        return L1Coord(w, fminf(fmaxf(0.0f, -fminf(1.0f - u, u)), fabsf(w)));
-    }
-    __device__ __forceinline__ float cut(float lam) const { return fminf(fmaxf(lam, lo), a); }  // min(max(lambda, lo), a)
-    __device__ __forceinline__ float point(float x0, float lam) const { return tclamp(x0 + sgn(w) * (a - cut(lam)), 0.0f, 1.0f); }
 };
 
 // the gradient of every element of the thread, in the same order on both paths (zeros past D)
@@ -79,17 +66,7 @@ __device__ __forceinline__ void each_c(const float *ur, const float *gr, const f
                                        const float (&rw)[kSampleElems], const float (&rl)[kSampleElems], const float (&rc)[kSampleElems],
                                        F body) {
     if (RES) {
-#pragma unroll
-        for (int g = 0; g < kSampleVecs; ++g) {
-            float wv[4] = {rw[g * 4], rw[g * 4 + 1], rw[g * 4 + 2], rw[g * 4 + 3]};
-            float lv[4] = {rl[g * 4], rl[g * 4 + 1], rl[g * 4 + 2], rl[g * 4 + 3]};
-            const float cv[4] = {rc[g * 4], rc[g * 4 + 1], rc[g * 4 + 2], rc[g * 4 + 3]};
-            // the values are handed over opaquely: what a pass derives from them (their doubles above all) is then formed inside the pass
-            // and not kept in registers across the 31 passes of a search, which would not fit
-#pragma unroll
-            for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(wv[j]), "+v"(lv[j]));
-            body(group_element(g), wv, lv, cv);
-        }
+        l1_each_resident(rw, rl, rc, body);
     } else {
         for (int g = 0; g < groups; ++g) {
             const int64_t e = group_element(g);
@@ -180,78 +157,12 @@ __global__ __launch_bounds__(kSampleBlock) void l1_kernel(float *z, const float 
             ru[k] = c.w, rl[k] = c.lo;
         }
     }
-    // h(0) and whether u - x0 is finite everywhere
-    double acc = 0.0;
-    int bad = 0;
-    each_c<RES, VEC, STEP>(ur, gr, cr, D, groups, op, ru, rl, rc, [&](int64_t, const float(&wv)[4], const float(&lv)[4], const float(&)[4]) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const L1Coord c(wv[j], lv[j]);
-            bad += abs_bits(c.w) >= 0x7F800000u ? 1 : 0;
-            acc += static_cast<double>(c.a) - static_cast<double>(c.lo);
-        }
-    });
-    const bool rest = red.sum(bad) != 0;  // a non-finite u: the sample is written as x0
-    const double h0 = red.sum(acc), epsd = static_cast<double>(eps);
-    float lam = 0.0f;
-    int active = 0;
-    if (!rest && h0 > epsd) {
-        // T: the largest non-negative float with h(T) > eps.  h(0) > eps holds and h(+inf) = 0 does not, so T stays finite.
-        uint32_t T = 0u;
-#pragma unroll 1
-        for (int bit = 30; bit >= 0; --bit) {
-            const uint32_t cand = T | (1u << bit);
-            const float tf = __uint_as_float(cand);
-            double part = 0.0;
-            each_c<RES, VEC, STEP>(ur, gr, cr, D, groups, op, ru, rl, rc, [&](int64_t, const float(&wv)[4], const float(&lv)[4], const float(&)[4]) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const L1Coord c(wv[j], lv[j]);
-                    part += static_cast<double>(c.a) - static_cast<double>(c.cut(tf));
-                }
-            });
-            if (red.sum(part) > epsd) T = cand;
-        }
-        // the segment (T, T+]: h(lambda) = num - |A| lambda there
-        const float tl = __uint_as_float(T), tn = __uint_as_float(T + 1u);
-        double num = 0.0;
-        int cnt = 0;
-        each_c<RES, VEC, STEP>(ur, gr, cr, D, groups, op, ru, rl, rc, [&](int64_t, const float(&wv)[4], const float(&lv)[4], const float(&)[4]) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const L1Coord c(wv[j], lv[j]);
-                if (c.a > tl) {
-                    if (c.lo > tl) {
-                        num += static_cast<double>(c.a) - static_cast<double>(c.lo);
-                    } else {
-                        num += static_cast<double>(c.a);
-                        ++cnt;
-                    }
-                }
-            }
-        });
-        num = red.sum(num);
-        active = red.sum(cnt);
-        lam = active > 0 ? fminf(fmaxf(static_cast<float>((num - epsd) / static_cast<double>(active)), tl), tn) : tn;
-    }
-
-    // final pass: the one place the output is written, each element by the thread that read it
-    double dist = 0.0;
-    each_c<RES, VEC, STEP>(ur, gr, cr, D, groups, op, ru, rl, rc, [&](int64_t e, const float(&wv)[4], const float(&lv)[4], const float(&cv)[4]) {
-        float r[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            r[j] = rest ? cv[j] : L1Coord(wv[j], lv[j]).point(cv[j], lam);
-            dist += fabs(static_cast<double>(r[j]) - static_cast<double>(cv[j]));
-        }
-        store4<VEC>(zr, e, D, r);
-    });
-    dist = red.sum(dist);
+    // the projection of u (ee_l1_proj.hpp)
+    const auto each = [&](auto body) { each_c<RES, VEC, STEP>(ur, gr, cr, D, groups, op, ru, rl, rc, body); };
+    const L1Root root = l1_root(red, eps, each);
+    const double dist = l1_write(red, root, each, [&](int64_t e, const float(&r)[4]) { store4<VEC>(zr, e, D, r); });
     if (threadIdx.x == 0) {
-        scal[b] = lam;
-        scal[B + b] = rest ? INFINITY : static_cast<float>(h0);
-        scal[2 * B + b] = static_cast<float>(active);
-        scal[3 * B + b] = static_cast<float>(dist);
+        l1_scal(scal, B, b, root, dist);
         if (STEP) {
             scal[4 * B + b] = __uint_as_float(op.tau);
             scal[5 * B + b] = static_cast<float>(m);

@@ -1,7 +1,7 @@
 // ee_sample.hpp - the "one workgroup of 512 threads per sample" expressions, each written once ("The per-sample
 // workgroup kernels").
 //
-// ee_fab.hip, ee_apgd_l2.hip, ee_apgd_l1.hip and ee_sqatk_l2.hip each have a *resident* path (a sample stays in registers across all
+// ee_fab.hip, ee_apgd_l2.hip, ee_apgd_l1.hip, ee_sqatk_l2.hip and ee_sqatk_l1.hip each have a *resident* path (a sample stays in registers across all
 // passes, per_sample <= kSampleResident) and a *streaming* path (every pass re-reads its inputs; any size, no scratch tensor), with 16-byte
 // or element-wise accesses, and promise the same BITS from all of them.  That holds because every sum over a sample is taken in one order:
 //   1. thread t takes the float4 groups t, t + 512, ... in turn (group_element), the four elements of a group in index order; elements at

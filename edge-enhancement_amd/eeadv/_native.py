@@ -82,6 +82,10 @@ SIGNATURES = {
     "ee_sqatk_init_l2_f32": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_p],
     # x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off, eta, n_sizes, seed, norms, B, C, H, W, eps, path, stream
     "ee_sqatk_step_l2_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_i, c_p],
+    # x_best, x_new, x0, seed, eta, s0, scal, B, C, H, W, eps, eps_p, path, stream
+    "ee_sqatk_init_l1_f32": [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p],
+    # x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off, eta, n_sizes, seed, norms, scal, B, C, H, W, eps, eps_p, path, stream
+    "ee_sqatk_step_l1_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_p],
     # logits, labels, targets, B, K, df, dlogits, pred, stream
     "ee_fab_diff_f32": [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p],
     # x, x0, w, df, B, per_sample, path, out, stream

@@ -41,6 +41,20 @@ def default_stages(args, num_steps, n_class, n_target_classes=9, norm="Linf"):
     ]
 
 
+def l1_stages(args, num_steps, n_class, n_target_classes=9):
+    """[(name, fn)] of the `standard` order in the L1 threat model, radius args.epsilon: APGD-L1-CE, APGD-T-L1, FAB-T-L1, Square-L1 through
+    the L1 doors of utils.attacks (DESIGN.md sections 19 to 21), so evaluate(..., stages=l1_stages(...)) is the L1 `standard` cascade.
+    default_stages(norm="L1") stays refused."""
+    fab_iters = int(getattr(args, "fab_iters", 100))
+    queries = int(getattr(args, "square_queries", 5000))
+    return [
+        ("APGD-L1-CE", lambda model, a, x, y, order: A.APGD_L1(model, a, x, y, num_steps, "ce")),
+        ("APGD-T-L1", lambda model, a, x, y, order: A.APGD_T_L1(model, a, x, y, num_steps, n_class, n_target_classes, order=order)),
+        ("FAB-T-L1", lambda model, a, x, y, order: A.FAB_T_L1(model, a, x, y, n_class, fab_iters, n_target_classes, order=order)[:2]),
+        ("Square-L1", lambda model, a, x, y, order: A.Square_L1(model, a, x, y, queries)[:2]),
+    ]
+
+
 def rand_stages(args, num_steps, eot_iter=None, norm="Linf"):
     """[(name, fn)] of the public ensemble's `rand` order for randomised defences: APGD-CE, then APGD-DLR on its survivors, every gradient
     averaged over eot_iter forwards (default args.eot_iter, else 20).  norm: 'Linf' or 'L2', for both stages

@@ -38,7 +38,7 @@ def make_parser(description, default_data="synthetic", with_local_rank=False):
     parser.add_argument('--pretrained', dest='pretrained', action='store_true', help='use pre-trained model')
     parser.add_argument('--resume', default='', type=str, metavar='PATH', help='path to latest checkpoint, (default: None)')
     parser.add_argument('-e', '--evaluate', dest='evaluate', action='store_true', help='evaluate model on validation set')
-    parser.add_argument('--attack_method', default='PGD', type=str, metavar='PATH', help='attack method in validation: PGD, FGSM, CW, APGD-CE, APGD-T, APGD (CE then T), Square, APGD+Square (CE, T, then Square), FAB-T, APGD+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch) Cascade (the same four, each on the samples still robust, over the whole split), APGD-DLR, Rand (APGD-CE then APGD-DLR, every gradient averaged over --eot_iter forwards: for defences that redraw at every forward) or Cascade-Rand (the same two, APGD-DLR on the survivors only), APGD-L1-CE, APGD-L1-T or APGD-L1 (CE then T): APGD in the L1 threat model, radius --epsilon, FAB-L1-T or APGD-L1+FAB (CE, T, then FAB-T): FAB-T in the L1 threat model (default: PGD)')
+    parser.add_argument('--attack_method', default='PGD', type=str, metavar='PATH', help='attack method in validation: PGD, FGSM, CW, APGD-CE, APGD-T, APGD (CE then T), Square, APGD+Square (CE, T, then Square), FAB-T, APGD+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch) Cascade (the same four, each on the samples still robust, over the whole split), APGD-DLR, Rand (APGD-CE then APGD-DLR, every gradient averaged over --eot_iter forwards: for defences that redraw at every forward) or Cascade-Rand (the same two, APGD-DLR on the survivors only), APGD-L1-CE, APGD-L1-T or APGD-L1 (CE then T): APGD in the L1 threat model, radius --epsilon, FAB-L1-T or APGD-L1+FAB (CE, T, then FAB-T): FAB-T in the L1 threat model, Square-L1 or APGD-L1+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch: the full L1 ensemble): Square in the L1 threat model (default: PGD)')
     parser.add_argument('--eot_iter', default=None, type=int, help='forwards every APGD gradient is averaged over (EOT); default: 20 for Rand and Cascade-Rand, 1 for APGD-CE and APGD-DLR; the other attacks have no EOT and refuse a value above 1')
     parser.add_argument('--norm', default='Linf', type=str, help='threat model of the evaluation attack, radius --epsilon of the config: Linf (default) or L2; L2 exists for APGD-CE, APGD-T, APGD, APGD-DLR, Rand and Cascade-Rand and every other method refuses it')
     parser.add_argument('--square_queries', default=5000, type=int, help='forwards per sample of the Square attack at most (default: 5000); not the defence\'s n_queries')

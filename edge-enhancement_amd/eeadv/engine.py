@@ -684,6 +684,17 @@ class _SquareRun:
 
     def __init__(self, x0, y, n_queries, eps, norm="Linf", path="auto"):
         _check_norm(norm, SQUARE_NORMS, "Square")
+        self._state(x0, n_queries, eps)
+        self.norm, self.path, self.norms = norm, path, None
+        if norm == "L2":
+            ops._sample_path(path, "the L2 Square kernels'")
+            self._tables(x0, n_queries)
+            self.norms = torch.zeros((3 + 2 * x0.shape[1], x0.shape[0]), dtype=torch.float32, device=x0.device)
+        else:
+            self.sizes = torch.tensor(square_schedule(n_queries, x0.shape[2], x0.shape[3]), dtype=torch.int32).to(x0.device)
+
+    def _state(self, x0, n_queries, eps):
+        """What no launch of the norm's own sees: images, margins, flags, counter, query count, seed."""
         if x0.dim() != 4:
             raise ValueError("the Square attack takes image batches [B,C,H,W], got shape %s" % (tuple(x0.shape),))
         B, dev = x0.shape[0], x0.device
@@ -696,21 +707,19 @@ class _SquareRun:
         self.flags = torch.zeros(B, dtype=torch.int32, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.seed = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.norm, self.path, self.norms = norm, path, None
-        if norm == "L2":
-            ops._sample_path(path, "the L2 Square kernels'")
-            C, H, W = x0.shape[1:]
-            sizes = sqatk.square_schedule_l2(n_queries, H, W)
-            s0 = sqatk.start_size(H, W)
-            eta, eta_off, off0 = sqatk.eta_tables(sizes, s0)
-            self.sizes = torch.tensor(sizes, dtype=torch.int32).to(dev)
-            self.eta = torch.from_numpy(eta).to(dev)
-            self.eta_off = torch.from_numpy(eta_off).to(dev)
-            self.eta0 = self.eta[off0:off0 + s0 * s0].view(s0, s0)  # the start's table: a view, nothing of its own
-            self.norms = torch.zeros((3 + 2 * C, B), dtype=torch.float32, device=dev)
-        else:
-            self.sizes = torch.tensor(square_schedule(n_queries, x0.shape[2], x0.shape[3]), dtype=torch.int32).to(dev)
         self.trace, self.step_entry = None, None
+
+    def _tables(self, x0, n_queries):
+        """The L2 schedule and the pattern tables eta with eta_off (the L1 run's too): sizes, eta, eta_off, eta0."""
+        dev = x0.device
+        H, W = x0.shape[2:]
+        sizes = sqatk.square_schedule_l2(n_queries, H, W)
+        s0 = sqatk.start_size(H, W)
+        eta, eta_off, off0 = sqatk.eta_tables(sizes, s0)
+        self.sizes = torch.tensor(sizes, dtype=torch.int32).to(dev)
+        self.eta = torch.from_numpy(eta).to(dev)
+        self.eta_off = torch.from_numpy(eta_off).to(dev)
+        self.eta0 = self.eta[off0:off0 + s0 * s0].view(s0, s0)  # the start's table: a view, nothing of its own
 
     def load(self, x0, y, seed):
         with torch.no_grad():
@@ -734,11 +743,14 @@ class _SquareRun:
             self.queries.zero_()
             self.flags.zero_()
             self.counter.fill_(-1)  # the start's margin launch brings it to proposal 0
+        self._init()
+        self._query(model)
+
+    def _init(self):
         if self.norms is None:
             ops.sqatk_init_(self.x_best, self.x_new, self.x0, self.seed, self.eps)
         else:
             ops.sqatk_init_l2_(self.x_best, self.x_new, self.x0, self.seed, self.eta0, self.eps, self.path)
-        self._query(model)
 
     def _step(self, sizes):
         if self.norms is None:
@@ -787,29 +799,25 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
     margin, accept rule, counter, query count, early exit and the graph are shared, and the trace entry of a forward that follows a step
     also holds "x_best_in", "x_new_in", "counter", "norms" [3 + 2C, B] and "x_new"."""
     _check_norm(norm, SQUARE_NORMS, "Square")
-    model = _unwrap(model)
-    x0 = x0.detach().contiguous()
-    n_queries = int(n_queries)
-    if n_queries < 1:
-        raise ValueError("Square needs n_queries >= 1")
-    if use_graph is None:
-        use_graph = graphs_enabled() and trace is None
-    if use_graph and trace is not None:
-        raise ValueError("the Square trace is recorded by eager runs only")
-    if seed is None:
-        # the generator's seed is the same for every attack of a process, its offset is what the ticket advances: both go into the key
-        s, off = runtime.philox_ticket(x0.device, 4)
-        seed = (s + (off + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    model, x0, n_queries, seed, use_graph = _square_args(model, x0, n_queries, seed, use_graph, trace)
+    key = ("square", id(model), model.training, tuple(x0.shape), n_queries, float(eps), x0.device.index, min(n_queries - 1, MAX_ITERS_PER_GRAPH),
+           norm, path)
+    return _square_drive(model, key, lambda: _SquareRun(x0, y, n_queries, eps, norm, path), x0, y, n_queries, seed, use_graph, trace, early_exit)
+
+
+def _square_drive(model, key, make_run, x0, y, n_queries, seed, use_graph, trace, early_exit):
+    """The queries of one Square attack on a run object, whatever its threat model: start, then n_queries - 1 iterations - replays of the
+    graph cached under `key` (whose chunk is min(n_queries - 1, MAX_ITERS_PER_GRAPH)) while a whole chunk is left, eager ones for the
+    remainder - with the early-exit read, then finish and result."""
     n_prop = n_queries - 1
     chunk = min(n_prop, MAX_ITERS_PER_GRAPH)
     if x0.shape[0] == 0:
         return _empty_result(x0, torch.int32)
     if not use_graph or chunk == 0:
-        run, gs = _SquareRun(x0, y, n_queries, eps, norm, path), None
+        run, gs = make_run(), None
         run.load(x0, y, seed)
     else:
-        key = ("square", id(model), model.training, tuple(x0.shape), n_queries, float(eps), x0.device.index, chunk, norm, path)
-        gs = _prepare(model, key, lambda: _SquareRun(x0, y, n_queries, eps, norm, path), (x0, y, seed), chunk)
+        gs = _prepare(model, key, make_run, (x0, y, seed), chunk)
         run = gs.run
     run.trace = trace
     run.start(model)
@@ -826,6 +834,77 @@ def square_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=N
     run.finish()
     run.trace = None
     return run.result()
+
+
+def _square_args(model, x0, n_queries, seed, use_graph, trace):
+    """(model, x0, n_queries, seed, use_graph) as both Square doors take them."""
+    model = _unwrap(model)
+    x0 = x0.detach().contiguous()
+    n_queries = int(n_queries)
+    if n_queries < 1:
+        raise ValueError("Square needs n_queries >= 1")
+    if use_graph is None:
+        use_graph = graphs_enabled() and trace is None
+    if use_graph and trace is not None:
+        raise ValueError("the Square trace is recorded by eager runs only")
+    if seed is None:
+        # the generator's seed is the same for every attack of a process, its offset is what the ticket advances: both go into the key
+        s, off = runtime.philox_ticket(x0.device, 4)
+        seed = (s + (off + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+    return model, x0, n_queries, seed, use_graph
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Square in the L1 threat model (Croce & Hein 2021; DESIGN.md section 21): a door of its own - square_loop(norm="L1") and
+# _SquareRun(norm="L1") stay refused
+# ---------------------------------------------------------------------------------------------------------------------------------------
+class _SquareL1Run(_SquareRun):
+    """_SquareRun with the two launches of ee_sqatk_l1.hip: margin, flags, counter, queries, `finish`, `any_active` and `result` are
+    _SquareRun's; the run owns `norms` [2 + 2C, B], `scal` [4, B] (the projection's rows), the L2 schedule and tables, and eps_p, the
+    radius of every projection (sqatk.l1_eps_p: formed once, here)."""
+
+    def __init__(self, x0, y, n_queries, eps, path="auto"):
+        ops._sample_path(path, "the L1 Square kernels'")
+        self._state(x0, n_queries, eps)
+        self.norm, self.path, self.eps_p = "L1", path, sqatk.l1_eps_p(eps)
+        self._tables(x0, n_queries)
+        B, C, dev = x0.shape[0], x0.shape[1], x0.device
+        self.norms = torch.zeros((2 + 2 * C, B), dtype=torch.float32, device=dev)
+        self.scal = torch.zeros((ops.SQATK_L1_SCAL_ROWS, B), dtype=torch.float32, device=dev)
+
+    def _init(self):
+        ops.sqatk_init_l1_(self.x_best, self.x_new, self.x0, self.seed, self.eta0, self.eps, self.eps_p, self.scal, self.path)
+        if self.trace is not None:
+            self.step_entry = dict(scal=self.scal.clone(), x_new=self.x_new.clone())  # the start's forward carries its projection
+
+    def _step(self, sizes):
+        entry = None
+        if self.trace is not None:
+            entry = dict(x_best_in=self.x_best.clone(), x_new_in=self.x_new.clone(), counter=int(self.counter.item()))
+        ops.sqatk_step_l1_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, sizes, self.eta_off, self.eta, self.seed,
+                           self.eps, self.eps_p, self.norms, self.scal, self.path)
+        if entry is not None:
+            entry.update(norms=self.norms.clone(), scal=self.scal.clone(), x_new=self.x_new.clone())
+            self.step_entry = entry
+
+
+def square_l1_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=None, early_exit=True, path="auto"):
+    """square_loop in the L1 threat model: one Square attack of at most n_queries forwards per sample inside {z : ||z - x0||_1 <= eps} n
+    [0,1]^D around x0 [B,C,H,W].  Start and proposal are those of ee_sqatk_l1.hip: the L2 run's pattern, windows,
+    schedule and draws, the L1 form of the window update, and the exact projection of ee_l1_proj_f32 onto the ball of radius
+    eps_p = float32(eps * (1 - 1e-6)) and the box, inside the step's launch.  Returns (x_adv, robust, queries) as square_loop does; margin,
+    accept rule, counter, query count, early exit and the graph are shared with it (the capture key shares nothing, so Linf, L2 and L1
+    graphs of one shape coexist).  Eager and replayed runs, early_exit or not, and the paths ('auto', 'resident', 'streaming') return the
+    same bits.  `trace` (a list, eager only) receives {"margin", "flags"} of every forward, the start's first - with "scal" [4, B] and
+    "x_new" of the start; the entry of a forward that follows a step also holds "x_best_in", "x_new_in", "counter", "norms" [2 + 2C, B],
+    "scal" [4, B] and "x_new"."""
+    ops._sample_path(path, "the L1 Square kernels'")
+    if not float(eps) >= 0.0:
+        raise ValueError("L1 Square needs eps >= 0, got %r" % (eps,))
+    model, x0, n_queries, seed, use_graph = _square_args(model, x0, n_queries, seed, use_graph, trace)
+    key = ("square_l1", id(model), model.training, tuple(x0.shape), n_queries, float(eps), x0.device.index,
+           min(n_queries - 1, MAX_ITERS_PER_GRAPH), path)
+    return _square_drive(model, key, lambda: _SquareL1Run(x0, y, n_queries, eps, path), x0, y, n_queries, seed, use_graph, trace, early_exit)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------

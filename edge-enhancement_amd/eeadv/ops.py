@@ -640,6 +640,54 @@ def sqatk_step_l2_(x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off
     return norms
 
 
+# ---- Square attack in the L1 threat model (ee_sqatk_l1.hip) -----------------------------------------------------------
+SQATK_L1_SCAL_ROWS = 4  # rows L1_S_LAMBDA .. L1_S_DIST of the launch's projection
+
+
+def _sqatk_l1_scal(scal, x_best):
+    B = x_best.shape[0]
+    scal = torch.zeros((SQATK_L1_SCAL_ROWS, B), dtype=torch.float32, device=x_best.device) if scal is None else scal
+    return scal, _chk(scal, torch.float32, "scal", (SQATK_L1_SCAL_ROWS, B))
+
+
+def sqatk_init_l1_(x_best, x_new, x0, seed, eta0, eps, eps_p, scal=None, path="auto"):
+    """The start of an L1 run into x_best and x_new [B,C,H,W]: P_{eps_p}(x0 + d), d the tiled pattern of the L2 start; eta0 float32
+    [s0, s0] on the device (eeadv.sqatk.eta), seed int64 [1].  Returns scal [4, B] (rows L1_S_LAMBDA .. _DIST), written into `scal` when
+    given."""
+    B, C, H, W = x_best.shape
+    pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
+    if eta0.dim() != 2 or eta0.shape[0] != eta0.shape[1]:
+        raise ValueError("eta0 must be a square table [s0, s0], got shape %s" % (tuple(eta0.shape),))
+    scal, ps = _sqatk_l1_scal(scal, x_best)
+    path = _sample_path(path, "the L1 Square kernels'")
+    N.check(N.lib.ee_sqatk_init_l1_f32(pb, pn, p0, _chk(seed, torch.int64, "seed", (1,)), _chk(eta0, torch.float32, "eta0"), int(eta0.shape[0]),
+                                       ps, B, C, H, W, eps, eps_p, path, _stream()), "ee_sqatk_init_l1_f32")
+    return scal
+
+
+def sqatk_step_l1_(x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off, eta, seed, eps, eps_p, norms=None, scal=None, path="auto"):
+    """Commit under flags [B], then L1 proposal counter[0] and its projection onto the eps_p ball and the box, in one launch: window edge
+    sizes[counter[0]], pattern table eta[eta_off[counter[0]]:] (sizes None or empty: commit only; eta_off and eta are then not read).
+    Returns (norms [2 + 2C, B]: n_img, n_un, n_w[c], n_new[c]; scal [4, B]: rows L1_S_LAMBDA .. _DIST) - zeros for a sample that made no
+    proposal - written into `norms` / `scal` when given.  path: 'auto', 'resident' (C*H*W <= 12288) or 'streaming'; the same bits."""
+    B, C, H, W = x_best.shape
+    pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
+    n_sizes = 0 if sizes is None else int(sizes.numel())
+    ps = po = pe = None
+    if n_sizes:
+        ps = _chk(sizes, torch.int32, "sizes", (n_sizes,))
+        po = _chk(eta_off, torch.int32, "eta_off", (n_sizes,))
+        pe = _chk(eta, torch.float32, "eta")
+    norms = torch.zeros((2 + 2 * C, B), dtype=torch.float32, device=x_best.device) if norms is None else norms
+    scal, pscal = _sqatk_l1_scal(scal, x_best)
+    path = _sample_path(path, "the L1 Square kernels'")
+    N.check(N.lib.ee_sqatk_step_l1_f32(pb, pn, p0, _chk(flags, torch.int32, "flags", (B,)), _chk(margin_min, torch.float32, "margin_min", (B,)),
+                                       _chk(counter, torch.int32, "counter", (1,)), ps, po, pe, n_sizes, _chk(seed, torch.int64, "seed", (1,)),
+                                       _chk(norms, torch.float32, "norms", (2 + 2 * C, B)), pscal, B, C, H, W, eps, eps_p, path, _stream()),
+            "ee_sqatk_step_l1_f32")
+    return norms, scal
+
+
 # ---- FAB-T (ee_fab.hip) ----------------------------------------------------------------------------------------------
 FAB_ADV, FAB_IMPROVED = 1, 2  # bits of the flags of fab_commit_ (EE_FAB_*)
 FAB_LAMBDA, FAB_SIGN, FAB_NORM = range(3)  # rows of the projection scalars [3, 2B] (row 0 is mu in L2)

@@ -1,6 +1,7 @@
 """Host-side pieces of the Square attack (csrc/ee_sqatk.hip): the p schedule shared with the Add_Square defence, and
 a vectorised numpy Philox4x32-10 that makes the kernels' draws - same key, counters and stream ids - for the plain-torch host path.  The
-L2 form (csrc/ee_sqatk_l2.hip) adds its pattern tables eta(s), its schedule and the draws of streams 13 and 14."""
+L2 form (csrc/ee_sqatk_l2.hip) adds its pattern tables eta(s), its schedule and the draws of streams 13 and 14; the
+L1 form (csrc/ee_sqatk_l1.hip; section 21) takes all of those unchanged and adds the radius of its projections."""
 import math
 
 import numpy as np
@@ -161,3 +162,9 @@ def tiles(seed, ids, n_tiles):
     ctr = ((ids[:, None] << np.uint64(32)) | np.arange(n_tiles, dtype=np.uint64)[None, :]).reshape(-1)
     r = philox4x32(seed, ctr, STREAM_TILE).reshape(len(ids), n_tiles, 4)
     return r[:, :, 0].astype(np.int64), (r[:, :, 1] & np.uint32(1)).astype(np.int64)
+
+
+# ---- the L1 form: schedule, start size, tables and draws are the L2 form's ----------------------------------------
+def l1_eps_p(eps):
+    """eps_p, the radius every projection of an L1 run uses: float32(float64(float32(eps)) * (1 - 1e-6)), formed once on the host."""
+    return float(np.float32(np.float64(np.float32(eps)) * (1.0 - 1e-6)))

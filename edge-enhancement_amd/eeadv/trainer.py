@@ -742,9 +742,20 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         return x_adv
     if args.attack_method in L1_METHODS:
         # APGD in the L1 threat model, radius args.epsilon: CE, T on the DLR loss, or CE then T with the flags ANDed and
-        # the first fooling point kept; FAB-L1-T and APGD-L1+FAB add the minimum-norm attack (section 20).  The methods carry their norm in the name; eot_iter_for and norm_for have refused --eot_iter / --norm.
+        # the first fooling point kept; FAB-L1-T and APGD-L1+FAB add the minimum-norm attack (section 20), Square-L1 and APGD-L1+FAB+Square the black-box one (section 21).  The methods carry their norm in the name; eot_iter_for and norm_for have refused --eot_iter / --norm.
         if targeted:
             raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+        if args.attack_method in L1_SQUARE_METHODS:
+            # Square in the L1 threat model, args.square_queries forwards per sample at most: alone, or as the last
+            # member of the L1 ensemble (APGD-L1-CE, APGD-L1-T, FAB-L1-T, Square-L1) - whole batch, flags ANDed, the first fooling point kept
+            queries = int(getattr(args, 'square_queries', 5000))
+            if args.attack_method == 'Square-L1':
+                return A.Square_L1(model, args, input, target, queries)[0]
+            fab_iters = int(getattr(args, 'fab_iters', 100))
+            return A._first_fooling(input.detach(), (A.APGD_L1(model, args, input, target, num_steps, 'ce'),
+                                                     A.APGD_T_L1(model, args, input, target, num_steps, n_class),
+                                                     A.FAB_T_L1(model, args, input, target, n_class, fab_iters)[:2],
+                                                     A.Square_L1(model, args, input, target, queries)[:2]))[0]
         if args.attack_method in L1_FAB_METHODS:
             # FAB-T in the L1 threat model, args.fab_iters iterations per target class, thresholded at args.epsilon:
             # alone, or after APGD-L1-CE and APGD-L1-T - the L1 ensemble minus Square, flags ANDed, the first fooling point kept
@@ -824,8 +835,9 @@ CASCADE_METHODS = (CASCADE_METHOD, CASCADE_RAND_METHOD)
 L2_METHODS = APGD_METHODS + RAND_METHODS + (CASCADE_RAND_METHOD,)  # every attack in them is an APGD run: --norm L2
 # what the AWP drivers validate with next to PGD
 L1_FAB_METHODS = ('FAB-L1-T', 'APGD-L1+FAB')  # FAB-T in L1, alone or after the two L1-APGD runs
-# the L1 attacks through doors of their own (DESIGN.md sections 19 and 20); not in L2_METHODS
-L1_METHODS = ('APGD-L1-CE', 'APGD-L1-T', 'APGD-L1') + L1_FAB_METHODS
+L1_SQUARE_METHODS = ('Square-L1', 'APGD-L1+FAB+Square')  # Square in L1, alone or as the last member of the full L1 ensemble (section 21)
+# the L1 attacks through doors of their own (DESIGN.md sections 19 to 21); not in L2_METHODS
+L1_METHODS = ('APGD-L1-CE', 'APGD-L1-T', 'APGD-L1') + L1_FAB_METHODS + L1_SQUARE_METHODS
 EVAL_METHODS = APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS + L1_METHODS
 
 

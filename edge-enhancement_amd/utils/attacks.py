@@ -335,7 +335,7 @@ def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None,
 # ---------------------------------------------------------------------------------------------------------
 # APGD in the L1 threat model (Croce & Hein 2021, "Mind the box"): doors of their own - APGD(norm="L1") stays refused.  One run, no
 # momentum, the sparse sign step, the exact projection onto ball and box, the sparsity / step-size checkpoints.
-# The large-radius warm-up, restarts, EOT, L1 Square and L1 inside Cascade / Rand are NOT here.
+# The large-radius warm-up, restarts, EOT and L1 inside Cascade / Rand are NOT here (L1 Square: Square_L1 below, section 21).
 # ---------------------------------------------------------------------------------------------------------
 def _f32c(v, dtype):
     """The float32 constant v in `dtype`: the constants of the L1 run are float32 ones in every dtype."""
@@ -562,8 +562,9 @@ def _square_l2_norms(v, planes=False):
     return out.view(v.shape[0], v.shape[1]) if planes else out
 
 
-def _square_l2_start(x0, eps, seed, ids):
-    """The tiled start of an L2 run (DESIGN.md section 18): (x_best, n0)."""
+def _square_tiles(x0, seed, ids):
+    """d, the tiled pattern the L2 and L1 starts share: +-eta(s0) per tile and channel, transposed by the tile's coin,
+    0 outside the tiling."""
     from eeadv import sqatk
     B, C, H, W = x0.shape
     s0 = sqatk.start_size(H, W)
@@ -580,15 +581,22 @@ def _square_l2_start(x0, eps, seed, ids):
             block = torch.where(tr[:, k].bool().view(B, 1, 1), eta0.t().unsqueeze(0), eta0.unsqueeze(0))
             sign = torch.where(((bits[:, k].view(B, 1) >> cc) & 1).bool(), one, -one)
             d[:, :, oh + a * s0:oh + (a + 1) * s0, ow + b * s0:ow + (b + 1) * s0] = sign.view(B, C, 1, 1) * block.view(B, 1, s0, s0)
-    d = d.to(x0.device)
+    return d.to(x0.device)
+
+
+def _square_l2_start(x0, eps, seed, ids):
+    """The tiled start of an L2 run (DESIGN.md section 18): (x_best, n0)."""
+    B = x0.shape[0]
+    d = _square_tiles(x0, seed, ids)
     tiny = torch.tensor(1e-12, dtype=torch.float32).to(x0.dtype)  # the constant is a float32 one in every dtype
     n0 = _square_l2_norms(d)
     q = torch.tensor(eps, dtype=x0.dtype) / (n0 + tiny)
     return torch.clamp(x0 + d * q.view(B, 1, 1, 1), 0, 1), n0
 
 
-def _square_l2_propose(x_best, x0, eps, seed, i, ids, s):
-    """Proposal i of an L2 run for every sample (DESIGN.md section 18): (x_new, norms [3 + 2C, B])."""
+def _square_windows(x0, seed, i, ids, s):
+    """(in1, in2, signed) of proposal i for every sample, as the L2 and L1 proposals share them: the masks [B,1,H,W] of the two windows and
+    +-eta(s) (transposed by the coin, signed per channel) laid on window 1, [B,C,H,W]."""
     from eeadv import sqatk
     B, C, H, W = x0.shape
     dt = x0.dtype
@@ -604,16 +612,24 @@ def _square_l2_propose(x_best, x0, eps, seed, i, ids, s):
         ah, aw = torch.from_numpy(ah).view(B, 1), torch.from_numpy(aw).view(B, 1)
         return (((hh >= ah) & (hh < ah + s)).view(B, 1, H, 1) & ((ww >= aw) & (ww < aw + s)).view(B, 1, 1, W)).to(x0.device)
 
-    in1, in2 = inside(vh, vw), inside(vh2, vw2)
-    one, zero = torch.ones((), dtype=dt), torch.zeros((), dtype=dt)
+    one = torch.ones((), dtype=dt)
     sign = torch.where(((torch.from_numpy(bits).view(B, 1) >> cc) & 1).bool(), one, -one).view(B, C, 1, 1).to(x0.device)
+    return inside(vh, vw), inside(vh2, vw2), pattern.to(x0.device).view(B, 1, H, W) * sign
+
+
+def _square_l2_propose(x_best, x0, eps, seed, i, ids, s):
+    """Proposal i of an L2 run for every sample (DESIGN.md section 18): (x_new, norms [3 + 2C, B])."""
+    B, C, H, W = x0.shape
+    dt = x0.dtype
+    in1, in2, signed = _square_windows(x0, seed, i, ids, s)
+    zero = torch.zeros((), dtype=dt)
     tiny = torch.tensor(1e-12, dtype=torch.float32).to(dt)  # the constant is a float32 one in every dtype
     e = torch.tensor(eps, dtype=dt)
     delta = x_best - x0
     n_img = _square_l2_norms(delta)
     n_un = _square_l2_norms(torch.where(in1 | in2, delta, zero))
     n_w = _square_l2_norms(torch.where(in1, delta, zero), planes=True)
-    new = torch.where(in1, pattern.to(x0.device).view(B, 1, H, W) * sign + delta / (tiny + n_w).view(B, C, 1, 1), zero)
+    new = torch.where(in1, signed + delta / (tiny + n_w).view(B, C, 1, 1), zero)
     n_new = _square_l2_norms(new, planes=True)
     room = torch.clamp(e * e - n_img * n_img, min=0) / C + n_un * n_un
     scale = torch.from_numpy(np.sqrt(room.cpu().numpy())).to(x0.device)  # the root rounded once: torch's vectorised CPU sqrt may miss the last bit
@@ -622,6 +638,32 @@ def _square_l2_propose(x_best, x0, eps, seed, i, ids, s):
     n_d = _square_l2_norms(delta)
     x_new = torch.clamp(x0 + delta / (tiny + n_d).view(B, 1, 1, 1) * e, 0, 1)
     return x_new, torch.cat([torch.stack([n_img, n_un, n_d]), n_w.t(), n_new.t()])
+
+
+class _SquareQueries:
+    """What a host run keeps between its forwards, whatever the threat model: the smallest accepted margin, the query count and the
+    accept rule of ee_sqatk_margin_f32.  `trace`, a list, receives {"margin", "flags"} (and `extra`) of every forward."""
+
+    def __init__(self, model, x0, y, trace=None):
+        B = x0.shape[0]
+        self.model, self.y, self.trace = model, y, trace
+        self.margin_min = torch.full((B,), _INF, dtype=x0.dtype, device=x0.device)
+        self.queries = torch.zeros(B, dtype=torch.int32, device=x0.device)
+
+    def active(self):
+        return ~(self.margin_min <= 0)
+
+    def query(self, x_new, x_best, extra=None):
+        """One forward on x_new: the new x_best."""
+        with torch.no_grad():
+            m = _square_margin(self.model(x_new), self.y)
+        active = self.active()
+        accept = active & (m < self.margin_min)
+        self.margin_min = torch.where(accept, m, self.margin_min)
+        self.queries = self.queries + active.to(torch.int32)
+        if self.trace is not None:
+            self.trace.append(dict(extra or {}, margin=m.clone(), flags=accept.clone()))
+        return torch.where(accept.view(-1, 1, 1, 1), x_new, x_best)
 
 
 def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early_exit=True, norm="Linf"):
@@ -637,38 +679,25 @@ def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early
     ids = np.arange(B) if ids is None else np.asarray(ids)
     l2 = norm == "L2"
     sizes = sqatk.square_schedule_l2(n_queries, H, W) if l2 else engine.square_schedule(n_queries, H, W)
-    inf = torch.full((B,), _INF, dtype=x0.dtype, device=x0.device)
-    state = {"margin_min": inf, "queries": torch.zeros(B, dtype=torch.int32, device=x0.device)}
-
-    def query(x_new, x_best):
-        with torch.no_grad():
-            m = _square_margin(model(x_new), y)
-        active = ~(state["margin_min"] <= 0)
-        accept = active & (m < state["margin_min"])
-        state["margin_min"] = torch.where(accept, m, state["margin_min"])
-        state["queries"] = state["queries"] + active.to(torch.int32)
-        if trace is not None:
-            trace.append(dict(extra, margin=m.clone(), flags=accept.clone()))
-        return torch.where(accept.view(-1, 1, 1, 1), x_new, x_best)
-
-    extra = {}
+    st = _SquareQueries(model, x0, y, trace)
+    extra = None
     if l2:
         x_best, n0 = _square_l2_start(x0, eps, seed, ids)
         extra = {"x_new": x_best.clone(), "norms": n0.view(1, B).clone()}
     else:
         stripe = torch.from_numpy(sqatk.stripes(seed, ids, C, W)).to(x0.dtype).to(x0.device)
         x_best = torch.clamp(x0 + eps * stripe.view(B, C, 1, W), 0, 1)
-    x_best = query(x_best, x_best)
+    x_best = st.query(x_best, x_best, extra)
     hh, ww, cc = torch.arange(H).view(1, H), torch.arange(W).view(1, W), torch.arange(C).view(1, C)
     for i, s in enumerate(sizes):
-        active = ~(state["margin_min"] <= 0)
+        active = st.active()
         if early_exit and not bool(active.any()):
             break
         if l2:
             prop, norms = _square_l2_propose(x_best, x0, eps, seed, i, ids, s)
             x_new = torch.where(active.view(-1, 1, 1, 1), prop, x_best)
             extra = {"x_new": x_new.clone(), "norms": torch.where(active.view(1, B), norms, torch.zeros((), dtype=norms.dtype))}
-            x_best = query(x_new, x_best)
+            x_best = st.query(x_new, x_best, extra)
             continue
         vh, vw, bits = (torch.from_numpy(a).view(B, 1) for a in sqatk.windows(seed, i, ids, H, W, s))
         inside = ((hh >= vh) & (hh < vh + s)).view(B, 1, H, 1) & ((ww >= vw) & (ww < vw + s)).view(B, 1, 1, W)
@@ -677,8 +706,8 @@ def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early
         delta = torch.where(inside, sign, torch.zeros((), dtype=x0.dtype)).to(x0.device)
         prop = torch.clamp(torch.min(torch.max(x_best + delta, x0 - eps), x0 + eps), 0, 1)
         x_new = torch.where(active.view(-1, 1, 1, 1), prop, x_best)
-        x_best = query(x_new, x_best)
-    return x_best, state["margin_min"], state["queries"]
+        x_best = st.query(x_new, x_best)
+    return x_best, st.margin_min, st.queries
 
 
 def Square(model, args, inputs, targets, n_queries=5000, seed=None, norm="Linf"):
@@ -695,6 +724,91 @@ def Square(model, args, inputs, targets, n_queries=5000, seed=None, norm="Linf")
     if seed is None:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     x_best, margin_min, queries = _square_host(model, x0, targets, n_queries, eps, seed, **kw)
+    robust = margin_min > 0
+    return torch.where(robust.view(-1, 1, 1, 1), x0, x_best), robust, queries
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Square in the L1 threat model (Croce & Hein 2021, "Mind the box"): doors of their own - Square(norm="L1") and
+# _square_host(norm="L1") stay refused.  Pattern, windows, schedule and draws are the L2 run's; the window update is its L1 form, and
+# every point is the exact projection (_l1_project) of x0 + delta onto the ball of radius eps_p = float32(eps * (1 - 1e-6)) and the box.
+# Restarts, EOT and L1 inside Cascade / Rand at the command line are NOT here.
+# ---------------------------------------------------------------------------------------------------------
+def _square_l1_norms(v, planes=False):
+    """||v[b]||_1 [B] (planes: ||v[b, c]||_1 [B, C]) in v's dtype for the L1 Square host path: the |values| summed in float64 and rounded
+    once.  float32 (and narrower) values are exact there and torch's sum is far inside the last bit of the result; float64 values are
+    summed without error (math.fsum), so that a float64 run has norms rounded once as well."""
+    import math
+    rows = v.reshape(v.shape[0] * v.shape[1] if planes else v.shape[0], -1).detach().abs().cpu()
+    if v.dtype == torch.float64:
+        sums = torch.tensor([math.fsum(r) for r in rows.tolist()], dtype=torch.float64)
+    else:
+        sums = rows.to(torch.float64).sum(dim=1)
+    out = sums.to(v.dtype).to(v.device)
+    return out.view(v.shape[0], v.shape[1]) if planes else out
+
+
+def _square_l1_propose(x_best, x0, eps, eps_p, seed, i, ids, s):
+    """Proposal i of an L1 run for every sample: (x_new, norms [2 + 2C, B], lam [B])."""
+    B, C, H, W = x0.shape
+    dt = x0.dtype
+    in1, in2, signed = _square_windows(x0, seed, i, ids, s)
+    zero = torch.zeros((), dtype=dt)
+    tiny = torch.tensor(1e-12, dtype=torch.float32).to(dt)  # the constant is a float32 one in every dtype
+    e = torch.tensor(eps, dtype=dt)
+    delta = x_best - x0
+    n_img = _square_l1_norms(delta)
+    n_un = _square_l1_norms(torch.where(in1 | in2, delta, zero))
+    n_w = _square_l1_norms(torch.where(in1, delta, zero), planes=True)
+    new = torch.where(in1, signed + delta / (tiny + n_w).view(B, C, 1, 1), zero)
+    n_new = _square_l1_norms(new, planes=True)
+    scale = torch.clamp(e - n_img, min=0) / torch.tensor(C, dtype=dt) + n_un
+    new = new / (tiny + n_new).view(B, C, 1, 1) * scale.view(B, 1, 1, 1)
+    delta = torch.where(in1, new, torch.where(in2, zero, delta))
+    x_new, lam = _l1_project(x0 + delta, x0, eps_p)
+    return x_new, torch.cat([torch.stack([n_img, n_un]), n_w.t(), n_new.t()]), lam
+
+
+def _square_l1_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early_exit=True):
+    """Plumbing path for CPU tensors (opt-in): the iteration of engine.square_l1_loop in plain torch ops, in the input's dtype, with the
+    kernels' draws (eeadv.sqatk: windows_l2, windows2, tiles).  Each norm is the |values| summed in float64 and rounded once; the
+    projection is the host projection of the L1-APGD host path.  A sample that makes no proposal keeps x_new = x_best untouched: no
+    projection runs on it.  Returns (x_best, margin_min, queries); `trace`, a list, receives {"margin", "flags", "x_new", "lam"} of
+    every forward and, behind a proposal, "norms" [2 + 2C, B] (zeros, like "lam", for a sample that made none)."""
+    from eeadv import sqatk
+    if not float(eps) >= 0.0:
+        raise ValueError("L1 Square needs eps >= 0, got %r" % (eps,))
+    B, C, H, W = x0.shape
+    ids = np.arange(B) if ids is None else np.asarray(ids)
+    eps_p = sqatk.l1_eps_p(eps)
+    sizes = sqatk.square_schedule_l2(n_queries, H, W)
+    st = _SquareQueries(model, x0, y, trace)
+    x_best, lam = _l1_project(x0 + _square_tiles(x0, seed, ids), x0, eps_p)
+    x_best = st.query(x_best, x_best, {"x_new": x_best.clone(), "lam": lam.clone()})
+    for i, s in enumerate(sizes):
+        active = st.active()
+        if early_exit and not bool(active.any()):
+            break
+        prop, norms, lam = _square_l1_propose(x_best, x0, eps, eps_p, seed, i, ids, s)
+        x_new = torch.where(active.view(-1, 1, 1, 1), prop, x_best)
+        zero = torch.zeros((), dtype=norms.dtype)
+        x_best = st.query(x_new, x_best, {"x_new": x_new.clone(), "norms": torch.where(active.view(1, B), norms, zero),
+                                          "lam": torch.where(active, lam, zero)})
+    return x_best, st.margin_min, st.queries
+
+
+def Square_L1(model, args, inputs, targets, n_queries=5000, seed=None):
+    """One Square attack in the L1 threat model (args.epsilon is the L1 radius, at most n_queries forwards per sample).  Returns (x_adv,
+    robust, queries) as Square does: robust = margin_min > 0 over the points that were actually queried.  Every queried point lies in
+    [0,1] and within eps_p + D * 2^-23 of the input in L1 whenever (C + 1) * eps <= D.  `seed` keys the
+    counter-based draws; None takes it from torch's generator."""
+    x0 = inputs.detach()
+    eps = float(args.epsilon)
+    if runtime.require_device(x0, "Square_L1"):
+        return engine.square_l1_loop(model, x0, targets, n_queries, eps, seed)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    x_best, margin_min, queries = _square_l1_host(model, x0, targets, n_queries, eps, seed)
     robust = margin_min > 0
     return torch.where(robust.view(-1, 1, 1, 1), x0, x_best), robust, queries
 
@@ -889,8 +1003,7 @@ def _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, what,
 # ---------------------------------------------------------------------------------------------------------
 # FAB-T in the L1 threat model: doors of their own - FAB_T(norm="L1") and _fab_host(norm="L1") stay refused.  The
 # iteration is FAB-T's; the projection is the least-||.||_1 one, a fill by descending |w_i| in which every coordinate tied at the
-# threshold takes the same fraction of its room.  Untargeted FAB, restarts, the final line search, L1 Square and L1 inside Cascade are
-# NOT here.
+# threshold takes the same fraction of its room.  Untargeted FAB, restarts, the final line search and L1 inside Cascade are NOT here.
 # ---------------------------------------------------------------------------------------------------------
 def _l1_norms(v):
     """sum_i |v_i| per row, summed in float64 and rounded to v's dtype once (as the commit kernel does)."""

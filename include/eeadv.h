@@ -33,7 +33,7 @@ extern "C" {
 #define EE_ERR_ALIGN (-4)       /* pointer not aligned to the element size */
 
 /* `path` of the launches that give a sample (or a projection problem) one workgroup of 512 threads: ee_fab_proj_*, ee_apgd_step_l2_f32,
- * ee_l1_proj_f32, ee_apgd_step_l1_f32, ee_sqatk_*_l2_f32.  The two paths return the same bits; a value outside the three: EE_ERR_SHAPE.
+ * ee_l1_proj_f32, ee_apgd_step_l1_f32, ee_sqatk_*_l2_f32, ee_sqatk_*_l1_f32.  The two paths return the same bits; a value outside the three: EE_ERR_SHAPE.
  * EE_FAB_PATH_*, EE_APGD_L2_PATH_*, EE_APGD_L1_PATH_* and EE_SQATK_L2_PATH_* below are these. */
 #define EE_PATH_AUTO 0      /* resident when a sample has at most 12288 elements, else streaming */
 #define EE_PATH_RESIDENT 1  /* a sample stays in registers across all passes; more than 12288 elements: EE_ERR_UNSUPPORTED */
@@ -441,6 +441,43 @@ int ee_sqatk_init_l2_f32(float *x_best, float *x_new, const float *x0, const int
 int ee_sqatk_step_l2_f32(float *x_best, float *x_new, const float *x0, const int *flags, const float *margin_min, const int *counter,
                          const int *sizes, const int *eta_off, const float *eta, int n_sizes, const int64_t *seed, float *norms, int B,
                          int C, int H, int W, float eps, int path, void *stream);
+
+/* ---- Square attack in the L1 threat model (Croce & Hein 2021, "Mind the box"), ee_sqatk_l1.hip ----
+ * The two launches that stand in the place of ee_sqatk_init_f32 / ee_sqatk_step_f32 in an L1 run; ee_sqatk_margin_f32, the counter, the
+ * flags and the query count are shared, and eta, eta_off, sizes, the draws (streams 11, 13, 14) and tiny are those of the L2 run above.
+ * Two radii: eps, the L1 radius, and eps_p <= eps, the radius every projection uses - the host forms it once as
+ * (float) ((double) eps * (1 - 1e-6)); the kernels do not.  P_r(u) is the projection of ee_l1_proj_f32 onto {z : ||z - x0||_1 <= r} n
+ * [0,1]^D, the same definition in the same order of sums (its edge rules included: r = 0 returns x0, a non-finite u - x0 writes x0).
+ * Next to the state above, all in device memory:
+ *   norms    float [2 + 2C, B]   n_img, n_un, n_w[0..C), n_new[0..C) of the last proposal (zeros for a sample that made none)
+ *   scal     float [4, B]        rows EE_L1_S_LAMBDA .. _DIST of the launch's projection (zeros for a sample that made no proposal)
+ * Each norm is (float) S, S the sum of the |values| in double (exact there) in an order fixed by C*H*W and the launch shape (one workgroup
+ * of 512 threads per sample).  Commit, proposal and projection are one launch.  Paths, 16-byte accesses and error codes as the L2 entries;
+ * eps or eps_p negative or NaN, eps_p > eps: EE_ERR_SHAPE; C > 32: EE_ERR_UNSUPPORTED; C*H*W above INT32_MAX - 2048: EE_ERR_SHAPE.
+ * B == 0 launches nothing.  Both record under EE_K_SQATK_INIT / EE_K_SQATK_STEP. */
+#define EE_SQATK_L1_PATH_AUTO EE_PATH_AUTO
+#define EE_SQATK_L1_PATH_RESIDENT EE_PATH_RESIDENT
+#define EE_SQATK_L1_PATH_STREAMING EE_PATH_STREAMING
+
+/* The tiled start: d the pattern of ee_sqatk_init_l2_f32 bit for bit (not rescaled), u = x0 + d (one addition),
+ *     x_best = x_new = P_{eps_p}(u);      scal [4, B] receives the projection's rows.
+ * s0 outside [1, min(H, W)]: EE_ERR_SHAPE. */
+int ee_sqatk_init_l1_f32(float *x_best, float *x_new, const float *x0, const int64_t *seed, const float *eta, int s0, float *scal, int B,
+                         int C, int H, int W, float eps, float eps_p, int path, void *stream);
+
+/* Commit and propose, in place.  Per sample: flags[b]: x_best = x_new.  Then, if the sample is not fooled and i = counter[0] is inside
+ * [0, n_sizes): with s = sizes[i] (1 <= s <= min(H, W), else no proposal), W1 / W2 the two windows and delta = x_best - x0,
+ *     n_img = ||delta||_1     n_un = ||delta on W1 u W2||_1 (all channels)     n_w[c] = ||delta[c, W1]||_1
+ *     new[c]   = +-eta + delta[c, W1] / (tiny + n_w[c])                          n_new[c] = ||new[c]||_1
+ *     scale    = max(eps - n_img, 0) / (float) C + n_un
+ *     delta[:, W2] = 0;  then  delta[c, W1] = new[c] / (tiny + n_new[c]) * scale
+ *     u = x0 + delta (every element);     x_new = P_{eps_p}(u)
+ * A fooled sample keeps x_new = x_best and runs no projection (P of a point of the set is not the identity in bits); a counter outside
+ * the table (or n_sizes = 0: sizes, eta_off and eta then nullable) commits only.  eps = 0 gives x_new = x0; nothing here makes a NaN of
+ * finite images.  With (C + 1) eps <= C*H*W: x_new in [0,1] and ||x_new - x0||_1 <= eps_p + C*H*W * 2^-23. */
+int ee_sqatk_step_l1_f32(float *x_best, float *x_new, const float *x0, const int *flags, const float *margin_min, const int *counter,
+                         const int *sizes, const int *eta_off, const float *eta, int n_sizes, const int64_t *seed, float *norms,
+                         float *scal, int B, int C, int H, int W, float eps, float eps_p, int path, void *stream);
 
 /* ---- FAB-T (Croce & Hein 2020, "Minimally distorted adversarial examples with a fast adaptive boundary attack"; Linf, targeted, one run,
  * eta = 1.05, beta = 0.9, alpha_max = 0.1 - the constants of AutoAttack's `standard` version), ee_fab.hip ----
