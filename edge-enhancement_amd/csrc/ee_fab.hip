@@ -30,6 +30,11 @@
 // F(theta) >= c' - the same 31-step search, no sort - coordinates above theta go to their bounds and those AT theta all take the same
 // fraction phi = (c' - sum_{|v_i| > theta} |v_i| r_i) / sum_{|v_i| = theta} |v_i| r_i of their rooms), ee_fab_step_l1_f32 (rebuilds those
 // deltas from theta and phi) and ee_fab_commit_l1_f32 (||x - x0||_1 in double in the same order).
+//
+// Untargeted FAB keeps all of the above and changes where w and df come from: per iteration one forward, then per
+// class k one backward pass (the logit gradient from ee_fab_diff_f32 with targets = k) and one ee_fab_select_f32 - the dual norm of that
+// class's gradient, dist = |z_k - z_y| / (1e-12 + n), and a running arg-min per sample that keeps (dist, k, df, the row) of the closest
+// linearised boundary.  One streaming pass and, on improvement, a copy; the reset before class 0 is a `first` flag of the same launch.
 #include <math.h>
 
 #include "ee_sample.hpp"
@@ -636,6 +641,69 @@ __global__ __launch_bounds__(kSampleBlock) void commit_kernel(const float *__res
     }
 }
 
+// ---- untargeted FAB: the running arg-min over the classes -------------------------------------------------------------------------------
+// One launch per class k, after that class's backward pass: n_k = the dual norm of the row g[b] (M = kLinf: sum |g_i|, kL2: sqrt(sum g_i^2),
+// kL1: max |g_i|; the sums in double in the one order of ee_sample.hpp, rounded to float once), dist = |df_k| / (1e-12 + n_k) in float, and -
+// where dist is strictly below best[b] - the sample takes the class: best, best_k, df, and the row copied into w.  Strict `<` over ascending
+// k keeps the lowest class among equal distances.  `first` (class 0's launch) stands in for the reset: the old best / best_k / df are not read
+// and are always written.  A sample belongs to one workgroup; best[b] is read by every thread before the reduction's barrier and written
+// by thread 0 after it.  One streaming pass: a row is read once for the norm and, on improvement, once more (from L2) for the copy - there
+// is nothing to keep resident across passes, so no resident / streaming pair.
+template <bool VEC, int M>
+__global__ __launch_bounds__(kSampleBlock) void select_kernel(const float *__restrict__ g, const float *__restrict__ logits,
+                                                              const int64_t *__restrict__ labels, int k, int K, int first, int64_t D,
+                                                              float *best, int *best_k, float *__restrict__ w, float *df) {
+    __shared__ double sh[2 * kSampleWaves];
+    SampleReducer red{sh};
+    const int b = blockIdx.x;
+    const float *gr = g + static_cast<int64_t>(b) * D;
+    const int groups = groups_of(D);
+    const float cur = first ? INFINITY : best[b];
+    double acc = 0.0;
+    for (int q = 0; q < groups; ++q) {
+        float gv[4];
+        load4<VEC>(gr, group_element(q), D, gv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float a = fabsf(gv[j]);
+            if constexpr (M == kL2)
+                acc = fma(static_cast<double>(a), static_cast<double>(a), acc);
+            else if constexpr (M == kL1)
+                acc = a != a ? static_cast<double>(INFINITY) : fmax(acc, static_cast<double>(a));  // a NaN makes the norm not finite, as in a sum
+            else
+                acc += static_cast<double>(a);
+        }
+    }
+    float n;
+    if constexpr (M == kL2)
+        n = static_cast<float>(sqrt(red.sum(acc)));
+    else if constexpr (M == kL1)
+        n = static_cast<float>(red.max(acc));  // the largest |g_i|, a float: exact
+    else
+        n = static_cast<float>(red.sum(acc));
+    const int64_t y = labels[b];
+    const bool valid = y >= 0 && y < K;  // a label outside the row is never dereferenced
+    const float *z = logits + static_cast<size_t>(b) * K;
+    const float d = valid ? z[k] - z[y] : NAN;
+    const bool live = valid && y != k && isfinite(d) && isfinite(n) && n != 0.0f;
+    const float dist = fabsf(d) / (1e-12f + n);
+    const bool take = live && dist < cur;  // uniform over the workgroup
+    if (threadIdx.x == 0) {
+        if (take)
+            best[b] = dist, best_k[b] = k, df[b] = d;
+        else if (first)
+            best[b] = INFINITY, best_k[b] = -1, df[b] = 0.0f;
+    }
+    if (!take) return;
+    float *wr = w + static_cast<int64_t>(b) * D;
+    for (int q = 0; q < groups; ++q) {
+        const int64_t e = group_element(q);
+        float gv[4];
+        load4<VEC>(gr, e, D, gv);
+        store4<VEC>(wr, e, D, gv);
+    }
+}
+
 bool bad_shape(int64_t B, int64_t per_sample) {
     return B < 0 || per_sample < 0 || B > INT32_MAX / 2 || per_sample > INT32_MAX || (per_sample > 0 && B > INT64_MAX / per_sample);
 }
@@ -699,7 +767,32 @@ int launch_commit(const float *logits, const int64_t *labels, int B, int K, floa
     return launch_status();
 }
 
+template <int M>
+int launch_select(const float *g, const float *logits, const int64_t *labels, int k, int K, int first, int64_t B, int64_t per_sample, float *best,
+                  int *best_k, float *w, float *df, void *stream) {
+    const dim3 grid(static_cast<unsigned>(B)), block(kSampleBlock);
+    if (sample_vec(per_sample, g, w))
+        EE_LAUNCH((select_kernel<true, M>), grid, block, 0, as_stream(stream), g, logits, labels, k, K, first, per_sample, best, best_k, w, df);
+    else
+        EE_LAUNCH((select_kernel<false, M>), grid, block, 0, as_stream(stream), g, logits, labels, k, K, first, per_sample, best, best_k, w, df);
+    return launch_status();
+}
+
 }  // namespace
+
+EE_API int ee_fab_select_f32(const float *g, const float *logits, const int64_t *labels, int k, int metric, int first, int64_t B, int K,
+                             int64_t per_sample, float *best, int *best_k, float *w, float *df, void *stream) {
+    if (bad_shape(B, per_sample) || per_sample < 1 || K < 2 || K > 65536 || k < 0 || k >= K || metric < kLinf || metric > kL1) return EE_ERR_SHAPE;
+    if (B == 0) return EE_OK;
+    if (!g || !logits || !labels || !best || !best_k || !w || !df) return EE_ERR_NULL;
+    if (!aligned4(g) || !aligned4(logits) || !aligned4(best) || !aligned4(best_k) || !aligned4(w) || !aligned4(df) ||
+        (reinterpret_cast<uintptr_t>(labels) & 7u))
+        return EE_ERR_ALIGN;
+    ProfScope prof(EE_K_FAB_DIFF, as_stream(stream));
+    if (metric == kL2) return launch_select<kL2>(g, logits, labels, k, K, first != 0, B, per_sample, best, best_k, w, df, stream);
+    if (metric == kL1) return launch_select<kL1>(g, logits, labels, k, K, first != 0, B, per_sample, best, best_k, w, df, stream);
+    return launch_select<kLinf>(g, logits, labels, k, K, first != 0, B, per_sample, best, best_k, w, df, stream);
+}
 
 EE_API int ee_fab_diff_f32(const float *logits, const int64_t *labels, const int64_t *targets, int B, int K, float *df, float *dlogits, int *pred,
                            void *stream) {

@@ -10,9 +10,9 @@ Semantics kept from the reference: the model's train/eval mode is NOT touched he
 mode the caller left, BatchNorm statistics and dropout included); callers are entered under
 torch.enable_grad() so an outer no_grad() does not matter; the result is a new detached tensor.
 
-The evaluation attacks (APGD in Linf / L2 / L1, Square, FAB-T) each keep their device state in a run object with four methods - load(*inputs),
+The evaluation attacks (APGD in Linf / L2 / L1, Square, FAB-T, untargeted FAB) each keep their device state in a run object with four methods - load(*inputs),
 start(model), body(model, n): n consecutive iterations, result() - and share one driver: `_prepare` (build, capture, cache, load, refresh) and
-`_drive` (eager run, or start + replays + result).  apgd_loop, apgd_l1_loop, fab_loop and fab_l1_loop are argument checks, a cache key and one call of
+`_drive` (eager run, or start + replays + result).  apgd_loop, apgd_l1_loop, fab_loop, fab_l1_loop, fab_u_loop and fab_u_l1_loop are argument checks, a cache key and one call of
 `_drive`; square_loop takes `_prepare` and keeps its own replay loop (early exit, eager remainder, finish); pgd_loop, with its probed tail,
 stands by itself ("The attack loops' driver").
 """
@@ -1053,3 +1053,108 @@ def fab_l1_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto")
     chunk = _chunk(n_iter)
     key = ("fab_l1", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk)
     return _drive(model, key, lambda: _FabL1Run(x0, y, n_iter, eps, path), (x0, y, targets, eps), n_iter, chunk, use_graph)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Untargeted FAB (Linf, L2 and - through a door of its own - L1): the iteration of FAB-T with w and df taken from the
+# CLOSEST linearised boundary among all classes k != y.  One forward, K backward passes off its retained graph, one ee_fab_select_f32 each
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _n_classes(model, x0, nclass):
+    """K of an untargeted run: `nclass`, or the width of one clean forward's logits."""
+    if nclass is None:
+        with torch.no_grad():
+            nclass = model(x0).shape[1]
+    nclass = int(nclass)
+    if nclass < 2:
+        raise ValueError("untargeted FAB needs at least 2 classes, got %d" % nclass)
+    return nclass
+
+
+class _FabURun(_FabRun):
+    """_FabRun whose w and df come from the running arg-min over the classes: `iteration` takes one forward through the generic route (the
+    whole model, attack_forward()), then per class k in index order the logit gradient of z_k - z_y (ops.fab_diff with targets filled with
+    k), one backward pass off the retained forward and ops.fab_select; projection, step, second forward and commit are _FabRun's.  The
+    [B, K, D] Jacobian never exists: a class's gradient is folded into (best, best_k, w, df) before the next is taken."""
+
+    def __init__(self, x0, y, n_iter, eps, nclass, path="auto", norm="Linf"):
+        super().__init__(x0, y, n_iter, eps, path, norm)
+        B, dev = x0.shape[0], x0.device
+        self.K = int(nclass)
+        self.classes = torch.arange(self.K, dtype=torch.int64, device=dev).view(-1, 1).expand(self.K, B).contiguous()  # row k: targets = k
+        self.w = torch.zeros_like(x0)
+        self.df = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.best = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
+        self.best_k = torch.full((B,), -1, dtype=torch.int32, device=dev)
+
+    def load(self, x0, y, eps=None):
+        super().load(x0, y, y, eps)
+
+    def hyperplane(self, model):
+        """(w, df) of the closest linearised boundary at self.x, in the run's buffers."""
+        with torch.enable_grad(), attack_forward():
+            logits = model(self.x)
+        z = logits.detach().float().contiguous()
+        if z.shape[1] != self.K:
+            raise ValueError("untargeted FAB was set up for %d classes, the model returns %d" % (self.K, z.shape[1]))
+        for k in range(self.K):
+            d = ops.fab_diff(z, self.y, self.classes[k])[1]
+            with input_grad_only(), torch.autograd.set_multithreading_enabled(_MT_BACKWARD):
+                (g,) = torch.autograd.grad(logits, [self.x], grad_outputs=d.to(logits.dtype), retain_graph=k + 1 < self.K)
+            ops.fab_select(g.contiguous(), z, self.y, k, self.norm, self.best, self.best_k, self.w, self.df, first=k == 0)
+        return self.w, self.df
+
+    def iteration(self, model):
+        w, df = self.hyperplane(model)
+        x = self.x.detach()
+        self.proj(x, self.x0, w, df, self.path, self.scal)
+        self.step_(x, self.x0, w, self.scal)
+        with torch.no_grad():
+            z = model(self.x)
+        self.commit_(z.detach().float().contiguous(), self.y, x, self.x0, self.adv, self.res, self.pred, self.flags, self.counter)
+
+
+class _FabUL1Run(_FabURun):
+    """_FabURun with the three L1 launches and their [4, 2B] scalars, through the hook _FabL1Run uses; the arg-min measures in max |g_i|."""
+    SCAL_ROWS = ops.FAB_L1_ROWS
+    metric_ops = staticmethod(_FabL1Run.metric_ops)
+
+    def __init__(self, x0, y, n_iter, eps, nclass, path="auto"):
+        super().__init__(x0, y, n_iter, eps, nclass, path, "L1")
+
+
+def _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, name, make_run, *key_tail):
+    model = _unwrap(model)
+    x0 = x0.detach().contiguous()
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("FAB needs n_iter >= 1")
+    ops._sample_path(path, "FAB projection")
+    if x0.shape[0] == 0:
+        return _empty_result(x0, torch.float32)
+    if use_graph is None:
+        use_graph = graphs_enabled()
+    K = _n_classes(model, x0, nclass)
+    # one iteration per graph: a replay's bubble is nothing against K backward passes, and MAX_ITERS_PER_GRAPH iterations of K passes each
+    # would be a graph of thousands of nodes
+    key = (name, id(model), model.training, tuple(x0.shape), path, x0.device.index, K) + key_tail
+    return _drive(model, key, lambda: make_run(model, x0, K), (x0, y, eps), n_iter, 1, use_graph)
+
+
+def fab_u_loop(model, x0, y, n_iter, eps, use_graph=None, path="auto", norm="Linf", nclass=None):
+    """One untargeted FAB run of n_iter iterations from x0 in the threat model `norm` ('Linf' or 'L2'): fab_loop's iteration, contract and
+    result triple (x_adv, robust, norm), with the hyperplane of every iteration the closest one - in the dual norm - among the linearised
+    boundaries z_k - z_y = 0 of all classes k != y (ties to the lower class; a class whose df or gradient norm is not finite, or whose
+    gradient is zero, is skipped; a sample with every class skipped stays where it is).  An iteration costs one forward with autograd, K
+    backward passes off its retained graph and one more forward; K = nclass, or the width of one clean forward's logits.  Deterministic.
+    Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of ONE iteration under a key of its own ("fab_u"); both give
+    the same bits.  On a model that redraws at every forward, all K hyperplanes of an iteration belong to the one draw of its forward."""
+    _fab_ops(norm)
+    return _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, "fab_u",
+                        lambda m, x, K: _FabURun(x, y, n_iter, eps, K, path, norm), norm)
+
+
+def fab_u_l1_loop(model, x0, y, n_iter, eps, use_graph=None, path="auto", nclass=None):
+    """fab_u_loop in the L1 threat model: the projections of fab_l1_loop, the distance to a hyperplane measured in max |g_i|, eps the L1
+    radius.  A graph key of its own ("fab_u_l1")."""
+    return _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, "fab_u_l1",
+                        lambda m, x, K: _FabUL1Run(x, y, n_iter, eps, K, path))

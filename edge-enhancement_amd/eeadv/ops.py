@@ -706,6 +706,28 @@ def fab_diff(logits, labels, targets):
     return df, d, pred
 
 
+FAB_METRICS = {"Linf": 0, "L2": 1, "L1": 2}  # EE_FAB_METRIC_*: the threat model; fab_select measures in its dual norm
+
+
+def fab_select(g, logits, labels, k, metric, best, best_k, w, df, first=None):
+    """One class of untargeted FAB's running arg-min, in place on best [B] float32, best_k [B] int32, w [B, ...] and df [B]: where class k's
+    linearised boundary (gradient g [B, ...], logits [B, K]) is strictly closer in the dual norm of `metric` ('Linf', 'L2', 'L1') than
+    best, the sample takes (dist, k, z_k - z_y, g[b]).  first (default: k == 0) stands in for the reset of best / best_k / df."""
+    B, K = logits.shape
+    if metric not in FAB_METRICS:
+        raise ValueError("FAB metric must be one of %s, got %r" % (sorted(FAB_METRICS), metric))
+    if not 0 <= int(k) < K:
+        raise ValueError("class %r outside [0, %d)" % (k, K))
+    pg = _chk(g, torch.float32, "g")
+    if g.shape[0] != B:
+        raise ValueError("g has %d rows, logits %d" % (g.shape[0], B))
+    N.check(N.lib.ee_fab_select_f32(pg, _chk(logits, torch.float32, "logits"), _chk(labels, torch.int64, "labels", (B,)), int(k),
+                                    FAB_METRICS[metric], int(k == 0 if first is None else first), B, K, g.numel() // B if B else 1,
+                                    _chk(best, torch.float32, "best", (B,)), _chk(best_k, torch.int32, "best_k", (B,)),
+                                    _chk(w, torch.float32, "w", g.shape), _chk(df, torch.float32, "df", (B,)), _stream()), "ee_fab_select_f32")
+    return best_k
+
+
 def _fab_proj(fn, name, x, x0, w, df, path, out, rows=3):
     B = x.shape[0]
     px = _chk(x, torch.float32, "x")

@@ -701,7 +701,7 @@ def norm_tag(args):
     """What a validation log line carries after its numbers: nothing for Linf (the lines stay as they were), ' [norm L2]' for L2, and
     ' [norm L1]' for the L1 methods, whose threat model is in their name (--norm stays refused with them, by norm_for)."""
     if norm_for(args) == 'Linf':
-        return ' [norm L1]' if args.attack_method in L1_METHODS else ''
+        return ' [norm L1]' if args.attack_method in L1_METHODS + L1_FAB_U_METHODS else ''
     return ' [norm L2]'
 
 
@@ -774,6 +774,15 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
                 return xt
             x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
         return x_adv
+    if args.attack_method in FAB_U_METHODS + L1_FAB_U_METHODS:
+        # untargeted FAB: one run of args.fab_iters iterations towards the closest boundary among all classes, n_class
+        # backward passes per iteration, thresholded at args.epsilon - FAB-U in Linf, FAB-L1-U in L1 (the norm is in the name)
+        if targeted:
+            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+        fab_iters = int(getattr(args, 'fab_iters', 100))
+        if args.attack_method in L1_FAB_U_METHODS:
+            return A.FAB_L1(model, args, input, target, fab_iters)[0]
+        return A.FAB(model, args, input, target, fab_iters)[0]
     if args.attack_method in SQUARE_METHODS:
         # Square (black-box, args.square_queries forwards per sample at most), alone or after APGD-CE and APGD-T: flags ANDed, the first
         # fooling point kept
@@ -838,7 +847,10 @@ L1_FAB_METHODS = ('FAB-L1-T', 'APGD-L1+FAB')  # FAB-T in L1, alone or after the 
 L1_SQUARE_METHODS = ('Square-L1', 'APGD-L1+FAB+Square')  # Square in L1, alone or as the last member of the full L1 ensemble (section 21)
 # the L1 attacks through doors of their own (DESIGN.md sections 19 to 21); not in L2_METHODS
 L1_METHODS = ('APGD-L1-CE', 'APGD-L1-T', 'APGD-L1') + L1_FAB_METHODS + L1_SQUARE_METHODS
-EVAL_METHODS = APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS + L1_METHODS
+# untargeted FAB in tuples of their own: FAB_METHODS and L1_METHODS keep their members
+FAB_U_METHODS = ('FAB-U',)
+L1_FAB_U_METHODS = ('FAB-L1-U',)  # L1 by its name, like L1_METHODS: the ' [norm L1]' tag, --norm refused
+EVAL_METHODS = APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS + L1_METHODS + FAB_U_METHODS + L1_FAB_U_METHODS
 
 
 def validate_batch(model, criterion, args, input, target, device, num_steps, step_size, n_class):

@@ -10,7 +10,7 @@ deliberate and documented in DESIGN.md:
   * random starts are drawn on the device (Philox inside the init kernel) unless `noise=` is injected -
     device and host generators differ anyway, parity tests inject the noise;
   * CWLinfAttack(target=None) works (the reference raises TypeError at :152, SURVEY a17);
-  * APGD / APGD_T, Square, FAB_T and APGD_Rand are additions: the reference runs them through the `autoattack` package (DESIGN.md
+  * APGD / APGD_T, Square, FAB_T, FAB and APGD_Rand are additions: the reference runs them through the `autoattack` package (DESIGN.md
     sections 11 - 13 and 15);
   * CPU tensors are refused unless eeadv.runtime.allow_cpu_plumbing(True) was called (--no-cuda drivers).
 """
@@ -817,8 +817,8 @@ def Square_L1(model, args, inputs, targets, n_queries=5000, seed=None):
 # FAB-T (Croce & Hein 2020, Linf, targeted): the minimum-norm member of AutoAttack's `standard` version - it walks along linearised
 # decision boundaries instead of ascending a loss.  Built from the published algorithm with the constants `standard`
 # runs it with (eta = 1.05, beta = 0.9, alpha_max = 0.1, 9 target classes, one run from the clean point: deterministic).  norm="L2" is
-# the same iteration in the other metric; L1 comes through FAB_T_L1 below (section 20).  Untargeted FAB, restarts
-# with the random start, the final line search and EOT for FAB are NOT here.
+# the same iteration in the other metric; L1 comes through FAB_T_L1 below (section 20), untargeted FAB through
+# FAB / FAB_L1 (section 22).  Restarts with the random start, the final line search and EOT for FAB are NOT here.
 # ---------------------------------------------------------------------------------------------------------
 _FAB_ETA, _FAB_BETA, _FAB_ALPHA_MAX = 1.05, 0.9, 0.1
 
@@ -908,17 +908,24 @@ def _fab_host_iteration(model, x, x0, y, t, adv, res, norm="Linf"):
     return _fab_iteration(model, x, x0, y, t, adv, res, _fab_projection, _fab_delta, _linf_norms)
 
 
-def _fab_iteration(model, x, x0, y, t, adv, res, project, delta, dist):
+def _fab_iteration(model, x, x0, y, t, adv, res, project, delta, dist, dual=None):
     """The iteration in the metric of (project, delta, dist): project(p, w, c) -> (lambda, s, ||delta||, *more) per row, delta(p, w, lambda,
-    s, *more) rebuilds the vector from those scalars (L1 has one more, phi), dist(v) is the row norm that nrm / res are measured in."""
+    s, *more) rebuilds the vector from those scalars (L1 has one more, phi), dist(v) is the row norm that nrm / res are measured in.
+    dual (untargeted FAB, t unused): the row norm dual to the metric - the hyperplane is then the closest one among all classes
+    (_fab_closest_plane) and `info` also holds best_k and best."""
     B = x0.shape[0]
     rows = torch.arange(B, device=x0.device)
     xc = x.detach().clone().requires_grad_()
-    with torch.enable_grad():
-        z = model(xc)
-        diff = z[rows, t] - z[rows, y]
-    w = torch.autograd.grad(diff.sum(), [xc])[0].detach().reshape(B, -1)
-    df = diff.detach()
+    more_info = {}
+    if dual is None:
+        with torch.enable_grad():
+            z = model(xc)
+            diff = z[rows, t] - z[rows, y]
+        w = torch.autograd.grad(diff.sum(), [xc])[0].detach().reshape(B, -1)
+        df = diff.detach()
+    else:
+        w, df, best_k, best = _fab_closest_plane(model, xc, y, dual)
+        more_info = dict(best_k=best_k, best=best)
     xf, x0f = x.detach().reshape(B, -1), x0.reshape(B, -1)
     sabs = w.abs().sum(dim=1)
     on = torch.isfinite(df) & (df != 0) & torch.isfinite(sabs) & (sabs > 0)
@@ -947,6 +954,7 @@ def _fab_iteration(model, x, x0, y, t, adv, res, project, delta, dist):
                 improved=improved, nrm=nrm, enabled=on)
     if more1:
         info.update(phi1=more1[0], phi2=more2[0])
+    info.update(more_info)
     return x_new, adv, res, info
 
 
@@ -1003,7 +1011,7 @@ def _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, what,
 # ---------------------------------------------------------------------------------------------------------
 # FAB-T in the L1 threat model: doors of their own - FAB_T(norm="L1") and _fab_host(norm="L1") stay refused.  The
 # iteration is FAB-T's; the projection is the least-||.||_1 one, a fill by descending |w_i| in which every coordinate tied at the
-# threshold takes the same fraction of its room.  Untargeted FAB, restarts, the final line search and L1 inside Cascade are NOT here.
+# threshold takes the same fraction of its room.  Restarts, the final line search and L1 inside Cascade are NOT here.
 # ---------------------------------------------------------------------------------------------------------
 def _l1_norms(v):
     """sum_i |v_i| per row, summed in float64 and rounded to v's dtype once (as the commit kernel does)."""
@@ -1083,6 +1091,127 @@ def FAB_T_L1(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=
     return _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, "FAB_T_L1",
                         lambda t: engine.fab_l1_loop(model, x0, targets, t, n_iter, eps)[::2],
                         lambda t: _fab_l1_host(model, x0, targets, t, n_iter))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Untargeted FAB (the `fab` of the public ensemble's `plus` version and of a `custom` ['apgd-ce', 'fab'] run): the
+# iteration of FAB-T, its hyperplane the closest one - in the dual norm - among the linearised boundaries z_k - z_y = 0 of ALL classes
+# k != y: K backward passes per iteration.  One run from the clean point, deterministic; restarts with the random start, the final search
+# and EOT are NOT here.
+# ---------------------------------------------------------------------------------------------------------
+def _dual_of_linf(g):
+    """sum_i |g_i| per row, summed in float64 and rounded to g's dtype once (as ee_fab_select_f32 does)."""
+    return g.abs().to(torch.float64).sum(dim=1).to(g.dtype)
+
+
+def _dual_of_l1(g):
+    """max_i |g_i| per row; a NaN propagates, so the class is skipped."""
+    return g.abs().max(dim=1)[0]
+
+
+def _fab_closest_plane(model, xc, y, dual):
+    """(w [B,D], df [B], best_k [B], best [B]) at xc (a leaf that requires grad): one forward, then per class k in index order g_k =
+    d(z_k - z_y)/dx off the retained graph, n_k = dual(g_k), dist_k = |df_k| / (1e-12 + n_k); the class of smallest dist_k wins, strict <
+    over ascending k (ties to the lower class).  Skipped: k == y, df_k or n_k not finite, n_k == 0.  Nothing chosen: w = 0, df = 0,
+    best_k = -1 - the iteration then rests."""
+    with torch.enable_grad():
+        z = model(xc)
+    B, K = z.shape
+    zy = z[torch.arange(B, device=z.device), y]
+    w = torch.zeros(B, xc[0].numel(), dtype=xc.dtype, device=xc.device)
+    df = torch.zeros(B, dtype=z.dtype, device=z.device)
+    best = torch.full_like(df, _INF)
+    best_k = torch.full((B,), -1, dtype=torch.int64, device=z.device)
+    for k in range(K):
+        diff = z[:, k] - zy
+        g = torch.autograd.grad(diff.sum(), [xc], retain_graph=True)[0].detach().reshape(B, -1)
+        d, n = diff.detach(), dual(g)
+        dist = d.abs() / (1e-12 + n)
+        take = (y != k) & torch.isfinite(d) & torch.isfinite(n) & (n != 0) & (dist < best)
+        best, best_k, df = torch.where(take, dist, best), torch.where(take, torch.full_like(best_k, k), best_k), torch.where(take, d, df)
+        w = torch.where(take.view(-1, 1), g, w)
+    return w, df, best_k, best
+
+
+_FAB_U_METRICS = {"Linf": (_fab_projection, _fab_delta, _linf_norms, _dual_of_linf),
+                  "L2": (_fab_projection_l2, _fab_delta_l2, _l2_norms, _l2_norms)}
+_FAB_U_L1_METRIC = (_fab_projection_l1, _fab_delta_l1, _l1_norms, _dual_of_l1)
+
+
+def _fab_u_host_iteration(model, x, x0, y, adv, res, norm="Linf"):
+    """One untargeted FAB iteration in plain torch ops, in the input's dtype: _fab_host_iteration with the closest hyperplane."""
+    return _fab_iteration(model, x, x0, y, None, adv, res, *_FAB_U_METRICS[_check_fab_norm(norm)])
+
+
+def _fab_u_l1_host_iteration(model, x, x0, y, adv, res):
+    return _fab_iteration(model, x, x0, y, None, adv, res, *_FAB_U_L1_METRIC)
+
+
+def _fab_u_run(iteration, x0, n_iter, trace):
+    x, adv = x0.clone(), x0.clone()
+    res = torch.full((x0.shape[0],), _INF, dtype=x0.dtype, device=x0.device)
+    for _ in range(int(n_iter)):
+        x, adv, res, info = iteration(x, adv, res)
+        if trace is not None:
+            info.update(x=x, adv=adv, res=res)
+            trace.append({k: v.clone() for k, v in info.items()})
+    return adv, res
+
+
+def _fab_u_host(model, x0, y, n_iter, trace=None, norm="Linf"):
+    """Plumbing path for CPU tensors (opt-in): the iteration of engine.fab_u_loop in plain torch ops, in the input's dtype, the Jacobian
+    taken row by row off one retained forward.  Returns (adv, res).  `trace`, a list, receives one dict of clones per iteration."""
+    _check_fab_norm(norm)
+    return _fab_u_run(lambda x, adv, res: _fab_u_host_iteration(model, x, x0, y, adv, res, norm), x0, n_iter, trace)
+
+
+def _fab_u_l1_host(model, x0, y, n_iter, trace=None):
+    """_fab_u_host in the L1 threat model."""
+    return _fab_u_run(lambda x, adv, res: _fab_u_l1_host_iteration(model, x, x0, y, adv, res), x0, n_iter, trace)
+
+
+def _fab_untargeted(model, x0, targets, eps, what, device_run, host_run):
+    """The one run of FAB / FAB_L1 and FAB_T's result convention; device_run(K) / host_run() -> (adv, norm)."""
+    on_dev = runtime.require_device(x0, what)
+    with torch.no_grad():
+        z = model(x0)
+    if on_dev:
+        first = ops.topk(z.detach().float().contiguous(), None, 1)[0][:, 0]
+    else:
+        first = torch.sort(z, dim=1, descending=True, stable=True)[1][:, 0]
+    inf = torch.full((x0.shape[0],), _INF, dtype=torch.float32 if on_dev else x0.dtype, device=x0.device)
+    norm = torch.where(first != targets, torch.zeros_like(inf), inf)
+    xa, nj = device_run(z.shape[1]) if on_dev else host_run()
+    closer = (nj < norm) & (nj <= eps)
+    x_adv = torch.where(closer.view((-1,) + (1,) * (x0.dim() - 1)), xa, x0)
+    norm = torch.minimum(norm, nj)
+    return x_adv, ~(norm <= eps), norm
+
+
+def FAB(model, args, inputs, targets, n_iter=100, eps=None, norm="Linf"):
+    """Untargeted FAB (norm: 'Linf' or 'L2'; eps, default args.epsilon, is the radius in that metric): one run of n_iter iterations on the
+    whole batch from the clean point, every iteration walking towards the closest linearised decision boundary among all classes k != y -
+    K backward passes per iteration, K the width of the clean logits.  Returns what FAB_T returns: (x_adv, robust, norm), norm [B] the
+    smallest ||adv - x0|| over the adversarial iterates (+inf if there was none, 0 for a sample the clean forward already misclassifies),
+    robust = not (norm <= eps), x_adv the inputs with every non-robust sample replaced by the point that attains its norm.  eps only
+    thresholds the result.  Deterministic.  The model runs in the mode the caller left it in; on a model that redraws at every forward one
+    iteration linearises one draw (no EOT)."""
+    x0 = inputs.detach()
+    eps = float(args.epsilon if eps is None else eps)
+    kw = {} if _check_fab_norm(norm) == "Linf" else {"norm": norm}
+    return _fab_untargeted(model, x0, targets, eps, "FAB",
+                           lambda K: engine.fab_u_loop(model, x0, targets, n_iter, eps, nclass=K, **kw)[::2],
+                           lambda: _fab_u_host(model, x0, targets, n_iter, **kw))
+
+
+def FAB_L1(model, args, inputs, targets, n_iter=100, eps=None):
+    """FAB in the L1 threat model (eps, default args.epsilon, is the L1 radius): the projections of FAB_T_L1, the distance to a hyperplane
+    measured in max_i |g_i|.  Returns what FAB_T_L1 returns."""
+    x0 = inputs.detach()
+    eps = float(args.epsilon if eps is None else eps)
+    return _fab_untargeted(model, x0, targets, eps, "FAB_L1",
+                           lambda K: engine.fab_u_l1_loop(model, x0, targets, n_iter, eps, nclass=K)[::2],
+                           lambda: _fab_u_l1_host(model, x0, targets, n_iter))
 
 
 class LabelSmoothLoss(torch.nn.Module):

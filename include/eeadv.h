@@ -580,6 +580,28 @@ int ee_fab_step_l1_f32(float *x, const float *x0, const float *w, const float *s
 int ee_fab_commit_l1_f32(const float *logits, const int64_t *labels, int B, int K, float *x, const float *x0, float *adv, float *res,
                          int *pred, int *flags, int *counter, int64_t per_sample, void *stream);
 
+/* ---- Untargeted FAB (Linf, L2 and L1).  The iteration, the state, the flags, the projections, the step and the
+ * commit are the ones above; what changes is where w and df come from: every iteration takes, for each class k = 0 .. K-1 in index order,
+ * one backward pass g_k = d(z_k - z_y)/dx off ONE retained forward (its logit gradient from ee_fab_diff_f32 with targets filled with k)
+ * and one ee_fab_select_f32, which keeps the class of the closest linearised boundary: afterwards w = g_k*, df = z_k* - z_y.  Two more
+ * per-sample buffers: best float [B] (the smallest distance so far), best_k int [B] (its class, -1: none). */
+#define EE_FAB_METRIC_LINF 0 /* `metric` of ee_fab_select_f32: the threat model; the distance to a hyperplane is measured in its dual norm */
+#define EE_FAB_METRIC_L2 1
+#define EE_FAB_METRIC_L1 2
+
+/* One class of the running arg-min, one workgroup of 512 threads per sample.  g [B, per_sample] is the gradient of class k, logits [B, K].
+ * n = the dual norm of the row g[b]: sum_i |g_i| (Linf), (float) sqrt(sum_i g_i^2) (L2) - the sums in double, thread t taking the groups
+ * of four elements t, t + 512, ..., then an xor-shuffle tree, then eight partial sums in index order, rounded to float once - or max_i |g_i|
+ * (L1, exact).  d = z_k - z_y (one fp32 difference), dist = |d| / (1e-12f + n) in float: one add, one divide.  The class is skipped when
+ * k == y, when the label lies outside [0, K), or when d or n is not finite or n == 0.  Otherwise, if dist < best[b] strictly: best[b] = dist,
+ * best_k[b] = k, df[b] = d and w[b] = g[b] (strict < over ascending k: the lowest class among equal distances).  first != 0 (the launch of
+ * class 0) stands in for a reset: best[b] is taken as +inf without being read, and a sample that does not take the class gets best = +inf,
+ * best_k = -1, df = 0 (w is left alone: with df = 0 the projections rest, and the step keeps x).  per_sample >= 1, any remainder modulo 4;
+ * 128-bit accesses when per_sample % 4 == 0 and g and w are 16-byte aligned, the same bits either way; 0 <= k < K, 2 <= K <= 65536;
+ * B == 0 launches nothing.  One streaming pass plus, on improvement, the copy; no `path`.  Records under EE_K_FAB_DIFF. */
+int ee_fab_select_f32(const float *g, const float *logits, const int64_t *labels, int k, int metric, int first, int64_t B, int K,
+                      int64_t per_sample, float *best, int *best_k, float *w, float *df, void *stream);
+
 /* CannyFilter_BPDA (utils/core.py:386-505; AWP configs): no alpha mask, NMS by multiplication, thresholds through
  * To_compare (core.py:329-358), hysteresis through To_eq (core.py:361-382).  thresholds given, hysteresis=True.
  *   forward: edge, thin (the thinned magnitude), t2 (the {0, .5, 1} threshold map) [B,1,H,W]; thin / t2 feed the backward.
@@ -1097,7 +1119,7 @@ int ee_cascade_resolve_f32(const uint8_t *robust, const int64_t *id, const float
 #define EE_K_SQATK_INIT 23   /* ee_sqatk_init_f32 */
 #define EE_K_SQATK_MARGIN 24 /* ee_sqatk_margin_f32 */
 #define EE_K_SQATK_STEP 25   /* ee_sqatk_step_f32 */
-#define EE_K_FAB_DIFF 26     /* ee_fab_diff_f32 */
+#define EE_K_FAB_DIFF 26     /* ee_fab_diff_f32, ee_fab_select_f32 */
 #define EE_K_FAB_PROJ 27     /* ee_fab_proj_linf_f32, ee_fab_proj_l2_f32, ee_fab_proj_l1_f32 */
 #define EE_K_FAB_STEP 28     /* ee_fab_step_f32, ee_fab_step_l2_f32, ee_fab_step_l1_f32 */
 #define EE_K_FAB_COMMIT 29   /* ee_fab_commit_f32, ee_fab_commit_l2_f32, ee_fab_commit_l1_f32 */
