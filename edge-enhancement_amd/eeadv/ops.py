@@ -1092,8 +1092,10 @@ def bn_sum_act_bwd(dy, dy2, y, s, gamma, beta, save_mean, save_invstd, running_m
 
 # ---- SyncBatchNorm: the local halves around the two exchanges (ee_bn.hip; the collectives live in eeadv/syncbn.py) --------------------
 def syncbn_supported(x):
-    return x.dim() >= 3 and x.shape[0] > 0 and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and N.lib.ee_syncbn_workspace_floats(
-        x.shape[0], x.shape[1], x[0, 0].numel()) > 0
+    """the ee_syncbn_* kernels read float4: a dense fp32 tensor whose H*W is a multiple of 4 and whose storage starts on a 16-byte boundary
+    (a contiguous view may start anywhere in its storage; the entry points answer EE_ERR_ALIGN to one that does not)"""
+    return x.dim() >= 3 and x.shape[0] > 0 and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.data_ptr() % 16 == 0 and (
+        N.lib.ee_syncbn_workspace_floats(x.shape[0], x.shape[1], x[0, 0].numel()) > 0)
 
 
 def _syncbn_workspace(x, B, C, HW):

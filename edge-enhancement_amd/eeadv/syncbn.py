@@ -126,6 +126,8 @@ class SyncBnActFn(torch.autograd.Function):
         want_params = (need[2] or need[3]) and not EF._INPUT_GRAD_ONLY
         dy = dy.contiguous()
         if x.is_cuda:
+            if dy.data_ptr() % 16:  # a dense view that starts off a 16-byte boundary: the kernels read float4
+                dy = dy.clone()
             local = ops.syncbn_bwd_sums(dy, None, y, x, gamma, beta, sm, si, relu)
             dparams = local.clone() if want_params else None
             total = _all_reduce_sum(local, group)
@@ -168,8 +170,8 @@ _EQUAL_SHARDS = True  # every rank's batch has the same shape (what the referenc
 
 class SyncBatchNorm2d(nn.SyncBatchNorm):
     """nn.SyncBatchNorm (same constructor, parameters, buffers, state_dict) whose training forward / backward run on ee_bn.hip around
-    one collective each way; anything the kernels do not take (non-affine, no running statistics, H*W % 4 != 0, other dtypes) and the
-    eval mode go to the parent class."""
+    one collective each way; anything the kernels do not take (non-affine, no running statistics, H*W % 4 != 0, other dtypes, an input or
+    residual that is not dense or does not start on a 16-byte boundary) and the eval mode go to the parent class."""
 
     def _fast(self, x):
         return (self.training and self.affine and self.track_running_stats and self.momentum is not None and x.dtype == torch.float32 and x.dim() == 4
@@ -181,7 +183,8 @@ class SyncBatchNorm2d(nn.SyncBatchNorm):
 
 def sync_bn_act(bn, x, residual=None, relu=False):
     """[relu]( bn(x) [+ residual] ) for a SyncBatchNorm2d: fused on the kernels in training mode, the parent's path otherwise."""
-    if isinstance(bn, SyncBatchNorm2d) and bn._fast(x) and (residual is None or (residual.is_contiguous() and residual.dtype == torch.float32)):
+    if isinstance(bn, SyncBatchNorm2d) and bn._fast(x) and (residual is None or (
+            residual.is_contiguous() and residual.dtype == torch.float32 and (not residual.is_cuda or residual.data_ptr() % 16 == 0))):
         if bn.num_batches_tracked is not None:
             bn.num_batches_tracked.add_(1)
         return SyncBnActFn.apply(x, residual, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, relu, bn.process_group)

@@ -8,6 +8,9 @@ hard_affine   gamma of both signs and zero, beta of both signs and zero.
 bn_ref64      [x + res_in] -> batch_norm -> [+ residual] -> [relu] composed from plain float64 torch operations, train or eval mode, with
               the backward from float64 autograd on a ReLU branch the CALLER fixes (the fp32 kernel's own y > 0, as tests/branch_replay.py
               does for whole networks): one pre-activation within rounding of zero cannot flip a whole gradient sum.
+deal, gather_back, rank_param_grads64
+              SyncBatchNorm over simulated ranks: the batch dealt to W ranks, the ranks' results put back into whole-batch tensors, and
+              each rank's float64 share of dgamma / dbeta.  The bar stays bn_ref64 over the whole batch.
 """
 import numpy as np
 import torch
@@ -18,6 +21,7 @@ GAMMA_CYCLE = (-1.25, 0.0, 0.0, 0.75, -0.5, 1.5)
 BETA_CYCLE = (0.3, 0.4, -0.4, -0.2, 0.0, 0.1)
 TIE_BAND = 1e-4   # |pre-activation| at or below this: the fp32 mask may legitimately differ from the float64 one
 TIE_CAP = 1e-3    # share of such elements (channels with gamma != 0) a seeded case may have
+STAT_FLOOR = (1e-5, 1e-6)  # (rtol, atol) on mean / invstd / variance / running statistics: test_bn_act_matches_torch's, see the GPU module
 
 
 def kinds(C, roll=0):
@@ -81,6 +85,12 @@ def split_sum(s, seed):
     return s - res, res
 
 
+def exact_addends(t):
+    """(hi, lo) with fp32 hi + lo == t bit for bit: hi keeps the upper half of t's significand, lo = t - hi is the rest (exact)"""
+    hi = (t.contiguous().view(torch.int32) & -4096).view(torch.float32)
+    return hi, t - hi
+
+
 def eps32(eps):
     """the eps the kernels see: they take it as a C float"""
     return float(np.float32(eps))
@@ -137,13 +147,45 @@ def bn_ref64(x, gamma, beta, running_mean, running_var, momentum, eps, training,
     return out
 
 
-def tie_share(pre64, gamma):
-    """share of pre-activations within TIE_BAND of zero, over the channels with gamma != 0"""
+def tie_share(pre64, gamma, leave_out=()):
+    """share of pre-activations within TIE_BAND of zero, over the channels with gamma != 0 that are not in `leave_out`"""
     live = gamma.detach().cpu() != 0
+    live[list(leave_out)] = False
     if not bool(live.any()):
         return 0.0
     p = pre64.detach().cpu()[:, live]
     return float((p.abs() <= TIE_BAND).double().mean())
+
+
+# ---- SyncBatchNorm over simulated ranks: the batch dealt to W ranks, the bar still bn_ref64 over the whole batch ------------------------
+def deal(B, sizes=None, stride=None):
+    """a partition of range(B), one index list per rank: `sizes` images per rank in order, or `stride` ranks dealt range(r, B, stride)"""
+    if stride is not None:
+        return [list(range(r, B, stride)) for r in range(stride)]
+    assert sum(sizes) == B and min(sizes) > 0
+    starts = [sum(sizes[:r]) for r in range(len(sizes))]
+    return [list(range(b, b + n)) for b, n in zip(starts, sizes)]
+
+
+def gather_back(pieces, parts):
+    """the whole-batch tensor whose images parts[r] are pieces[r]"""
+    B = sum(len(idx) for idx in parts)
+    whole = torch.empty((B,) + tuple(pieces[0].shape[1:]), dtype=pieces[0].dtype, device=pieces[0].device)
+    for piece, idx in zip(pieces, parts):
+        whole[idx] = piece
+    return whole
+
+
+def rank_param_grads64(x, mean, invstd, dy, mask, parts, dy2=None):
+    """what each rank adds to the parameter gradients, float64: (dgamma_r, dbeta_r), each [W, C], with dbeta_r = sum over the rank's images
+    of dz and dgamma_r = sum of dz * xhat, where dz = (dy [+ dy2]) * mask and xhat = (x - mean) * invstd on the GLOBAL float64 statistics
+    (bn_ref64's mean / invstd).  Over the ranks they add up to bn_ref64's dgamma / dbeta on the same mask."""
+    d = lambda t: t.detach().double()
+    dz = d(dy) if dy2 is None else d(dy) + d(dy2)
+    if mask is not None:
+        dz = dz * mask.to(dz.device).double()
+    prod = dz * ((d(x) - _bc(d(mean))) * _bc(d(invstd)))
+    return torch.stack([prod[idx].sum((0, 2, 3)) for idx in parts]), torch.stack([dz[idx].sum((0, 2, 3)) for idx in parts])
 
 
 # ---- the seeded cases of tests/test_gpu_bn_hard_channels.py (the host test holds every one of them under TIE_CAP) ----------------------
@@ -163,6 +205,29 @@ BN_POOL_CASES = {"one-group": ((3, 6, 8, 12), 41), "two-images-per-group": ((70,
 STEM_CASE = ((3, 3, 10, 64), 64, 51)  # x shape, K, seed
 WINO_CASES = {16: 61, 8: 62, 4: 63}   # H -> seed (B = 3)
 PAIR_CASES = {16: 71, 8: 72}          # H -> seed (B = 3, 32 -> 64 channels)
+# ee_syncbn_*: name -> (shape, seed), train mode, with and without a residual; SYNC_DEALS: name -> {label: images per rank, in rank order}.
+# A rank's shard runs in split_slices(B_r * H * W / 4 / 2048) slices (the S of the labels); a slice boundary may lie inside an image.
+# [4, 3, 1] and [5, 3, 1] leave the `tail` kind's constant last image alone on a rank; the contiguous deals keep the `outlier` kind's
+# shifted first image on rank 0 only, so the cross term of the rank merge carries that channel's variance.
+SYNC_CASES = {
+    "one-slice": ((8, 6, 4, 4), 81),
+    "hw4": ((9, 6, 2, 2), 82),            # H * W == 4: one quad per image and channel
+    "two-slices": ((7, 6, 56, 56), 83),
+    "four-slices": ((12, 6, 56, 56), 84),
+    "channels-70": ((4, 70, 4, 4), 85),   # the per-channel kernels' second 64-thread block, 6 of its threads in use
+}
+SYNC_DEALS = {
+    "one-slice": {"[8]": deal(8, [8]), "[4,4]": deal(8, [4, 4]), "strided-2": deal(8, stride=2), "[2,2,2,2]": deal(8, [2, 2, 2, 2]), "[4,3,1]": deal(8, [4, 3, 1])},
+    "hw4": {"[5,3,1]": deal(9, [5, 3, 1])},
+    "two-slices": {"[4,3] S=2,2": deal(7, [4, 3]), "[5,2] S=2,1": deal(7, [5, 2])},
+    "four-slices": {"[9,3] S=4,2": deal(12, [9, 3])},  # S = 4: slices of 2.25 images
+    "channels-70": {"[2,2]": deal(4, [2, 2]), "[3,1]": deal(4, [3, 1])},
+}
+# channels-70: with 70 channels the kind cycle (5) and the beta cycle (6) meet at channels 10 and 40 - `const` with beta == 0 and gamma
+# == -0.5.  Without a residual their 128 pre-activations are exactly 0 in float64, which tie_share counts as ties (4.4e-2 of the case).
+# They are none: fp32 gives exactly 0 there as well (x - mean == 0), the mask is closed on both sides, and the GPU test's exact check
+# y == relu(beta) covers them.  The tie count of this case therefore leaves `const` channels out, and is then 0 (the host test asserts it).
+SYNC_TIES_LEAVE_OUT_CONST = ("channels-70",)
 
 
 def shaped_conv_operands(x_shape, w_shape, seed, fan_in):

@@ -135,5 +135,57 @@ def test_every_seeded_case_keeps_its_ties_under_the_cap():
         gamma, beta = R.hard_affine(C)
         r = R.bn_ref64(raw, gamma, beta, None, None, 0.1, 1e-5, True, relu=True)
         worst[(name, True, False, 0)] = R.tie_share(r["pre"], gamma)
+    for name, (shape, seed) in R.SYNC_CASES.items():  # train mode only: eval mode issues no exchange
+        c = R.hard_case(shape, seed)
+        const = [i for i, k in enumerate(c["kinds"]) if k == "const"]
+        for res in (False, True):
+            r = R.bn_ref64(c["x"], c["gamma"], c["beta"], c["rm"], c["rv"], 0.1, 1e-5, True, residual=c["residual"] if res else None, relu=True)
+            if name in R.SYNC_TIES_LEAVE_OUT_CONST:  # see the note next to SYNC_CASES: exact zeros on both sides, not ties
+                dropped = r["pre"][:, const]
+                assert bool((dropped[dropped.abs() <= R.TIE_BAND] == 0).all())
+                assert R.tie_share(r["pre"], c["gamma"], leave_out=const) == 0.0, (name, res)
+                worst[("syncbn " + name, True, res, 0)] = 0.0
+            else:
+                worst[("syncbn " + name, True, res, 0)] = R.tie_share(r["pre"], c["gamma"])
     bad = {k: v for k, v in worst.items() if not v < R.TIE_CAP}
     assert not bad, bad
+
+
+# ---- SyncBatchNorm over simulated ranks: the reference plumbing of the GPU test, and the host restatement of the kernels' merge -----------
+SYNC_DEALS = [(name, label) for name in R.SYNC_CASES for label in R.SYNC_DEALS[name]]
+
+
+def test_every_sync_case_has_its_deals_and_they_are_partitions():
+    assert set(R.SYNC_DEALS) == set(R.SYNC_CASES)
+    for name, label in SYNC_DEALS:
+        B, parts = R.SYNC_CASES[name][0][0], R.SYNC_DEALS[name][label]
+        assert sorted(i for idx in parts for i in idx) == list(range(B)) and all(idx for idx in parts), (name, label)
+        whole = torch.arange(B * 3.0).view(B, 3)
+        assert torch.equal(R.gather_back([whole[idx] for idx in parts], parts), whole), (name, label)
+    assert R.deal(8, stride=2) == [[0, 2, 4, 6], [1, 3, 5, 7]] and R.deal(8, [4, 3, 1]) == [[0, 1, 2, 3], [4, 5, 6], [7]]
+    # the slice counts the labels promise: ee_bn.hip's split_slices, one slice up to 2048 quads per channel
+    slices = lambda name, label: [max(1, -(-(len(idx) * R.SYNC_CASES[name][0][2] * R.SYNC_CASES[name][0][3] // 4) // 2048)) for idx in R.SYNC_DEALS[name][label]]
+    assert slices("two-slices", "[4,3] S=2,2") == [2, 2] and slices("two-slices", "[5,2] S=2,1") == [2, 1]
+    assert slices("four-slices", "[9,3] S=4,2") == [4, 2] and (9 * 56 * 56 // 4) % 4 == 0 and (9 * 56 * 56 // 4 // 4) % (56 * 56 // 4) != 0
+    assert all(s == 1 for name in ("one-slice", "hw4", "channels-70") for label in R.SYNC_DEALS[name] for s in slices(name, label))
+
+
+@pytest.mark.parametrize("res", [False, True])
+@pytest.mark.parametrize("name,label", SYNC_DEALS)
+def test_per_rank_parameter_gradients_add_up_to_the_whole_batch(name, label, res):
+    shape, seed = R.SYNC_CASES[name]
+    c, parts = R.hard_case(shape, seed), R.SYNC_DEALS[name][label]
+    residual = c["residual"] if res else None
+    fwd = R.bn_ref64(c["x"], c["gamma"], c["beta"], c["rm"], c["rv"], 0.1, 1e-5, True, residual=residual, relu=True)
+    mask = fwd["y"] > 0
+    ref = R.bn_ref64(c["x"], c["gamma"], c["beta"], c["rm"], c["rv"], 0.1, 1e-5, True, residual=residual, relu=True, dy=c["dy"], mask=mask)
+    dg, db = R.rank_param_grads64(c["x"], ref["mean"], ref["invstd"], c["dy"], mask, parts)
+    assert dg.shape == db.shape == (len(parts), shape[1])
+    for total, want in ((dg.sum(0), ref["dgamma"]), (db.sum(0), ref["dbeta"])):
+        assert bool(((total - want).abs() <= 1e-12 * want.abs()).all()), (total - want).abs().max()
+    # the two-addend form of the incoming gradient
+    hi, lo = R.exact_addends(c["dy"])
+    dg2, db2 = R.rank_param_grads64(c["x"], ref["mean"], ref["invstd"], hi, mask, parts, dy2=lo)
+    assert torch.equal(dg2, dg) and torch.equal(db2, db)
+    # a rank's images put back where they came from
+    assert torch.equal(R.gather_back([c["x"][idx].contiguous() for idx in parts], parts), c["x"])

@@ -1,6 +1,10 @@
 """Every path that produces BatchNorm batch statistics (ee_bn.hip, ee_fuse.hpp's train_bn_merge, the statistics epilogues of ee_wino.hip /
 ee_s2.hip / ee_conv.hip) on the hard channels of tests/bn_reference.py, against its float64 bar - train mode, and eval mode where the path
 has one.  The rest of the suite feeds these kernels x = randn * 2 + 0.5 with gamma > 0 and compares with fp32 torch or a sibling kernel.
+That includes the sync family, ee_syncbn_{stats,apply,bwd_sums,bwd_apply}_f32 (bn_moments_kernel, bn_sums_kernel, bn_sync_apply_kernel,
+bn_sync_bwd_apply_kernel): SyncBatchNorm's local halves, run here for W simulated ranks in this one process - the batch dealt to the ranks
+by bn_reference.SYNC_DEALS (ranks of unequal size, of one image, with different slice counts, slices that cut through images, H * W == 4,
+70 channels), the all_gather a stack and the all_reduce a sum in rank order - against bn_ref64 over the WHOLE batch.
 
 What is asserted, PER CHANNEL (no allowed error is scaled by a maximum taken over channels):
   * `const` channels (x == 0.75) and the convolution producers' zero-filter channels, train mode: save_mean == the constant,
@@ -18,6 +22,14 @@ What is asserted, PER CHANNEL (no allowed error is scaled by a maximum taken ove
     negative gamma included; a gamma == 0 channel follows beta > 0 as a whole; the mask-from-x backward forms (y = NULL) return the bits
     of the mask-from-y forms.
   * two calls give the same bits.
+  * the sync family, on top of all of the above for the whole batch put back together: every rank's moments of a `const` channel are
+    exactly (0.75, 0, its count); save_mean, save_invstd and both running statistics are the same bits on every rank; each rank's own
+    (sum dz, sum dz * xhat) is held to that rank's float64 share (bn_reference.rank_param_grads64) within max(4 x the error of torch's
+    stock fp32 autograd with the incoming gradient zeroed outside the rank's images, the dgamma / dbeta floor with n the RANK's element
+    count), and their device sum to bn_ref64's dgamma / dbeta; the y = NULL backward, dy given as two addends (dy2) and dresidual asked for
+    or left out return the bits of the plain form; the ranks in the opposite order stay inside the same bounds (other bits are allowed).
+    eeadv.syncbn's module runs the two-slices case as one rank with the global count taken either way (_EQUAL_SHARDS), and sends an
+    input or residual that starts off a 16-byte boundary to nn.SyncBatchNorm's own forward (held to the y and dx floors alone).
 The exactness claims on `const` channels are train-mode claims (batch mean 0.75, M2 0).  In eval mode the running statistics stand in, a
 `const` channel is an ordinary one and goes to the float64 bar; the gamma == 0 channels stay exact in both modes (y == relu(beta), dx == 0;
 their dresidual, dgamma and dbeta go to the bar).
@@ -236,6 +248,73 @@ pair_stats H=16 mt=111222
   running_mean    conv-out 6.7e-08 1.1e-05 1.0e-07
   running_var     conv-out 1.9e-06 1.9e-04 1.8e-06
   conv2(relu(bn)) conv-out 1.2e-06 9.3e-05 1.0e-06
+The syncbn rows fold every deal of a case, with and without a residual and both rank orders, by their maxima; dgamma_r / dbeta_r are the
+ranks' own sums against their float64 shares, folded over the ranks as well.  With C = 6 the `offset` and `outlier` channels carry gamma == 0
+(exact y and dx); channels-70 puts every gamma on every kind, and shows torch's own y and dx on `offset` to be poor (4.6e-3, 1.8e-2).
+syncbn one-slice
+  mean            offset 9.2e-07 3.2e-04 9.2e-07  outlier 1.3e-07 2.2e-05 3.5e-07  tail 6.8e-09 3.0e-06 2.3e-08  plain 1.2e-09 4.2e-06 1.2e-09
+  invstd          offset 4.3e-07 3.9e-05 1.2e-06  outlier 4.3e-09 2.7e-06 1.1e-08  tail 1.8e-08 8.5e-06 7.8e-08  plain 3.6e-09 6.1e-06 3.6e-09
+  running_mean    offset 3.0e-09 3.3e-05 3.0e-09  outlier 1.6e-08 4.2e-06 4.4e-08  tail 5.6e-10 2.3e-06 5.6e-10  plain 1.6e-09 1.3e-06 1.6e-09
+  running_var     offset 6.9e-06 2.8e-05 6.4e-08  outlier 5.6e-07 4.6e-05 8.5e-08  tail 2.7e-08 1.4e-05 2.7e-08  plain 3.8e-08 9.4e-06 3.8e-08
+  y               tail 1.3e-07 4.3e-05 1.8e-07  plain 1.5e-07 5.4e-05 1.5e-07
+  dx              const 1.1e-05 2.4e-03 7.9e-06  tail 1.9e-07 5.6e-05 1.9e-07  plain 2.9e-08 3.1e-05 2.9e-08
+  dgamma          const 0.0e+00 2.3e-04 0.0e+00  offset 5.5e-03 2.2e-02 1.7e-05  outlier 2.1e-07 3.1e-04 7.4e-07  tail 1.0e-06 3.6e-04 1.3e-06  plain 6.7e-07 3.3e-04 1.2e-06
+  dbeta           const 0.0e+00 1.5e-03 0.0e+00  offset 2.7e-07 3.2e-04 9.3e-07  outlier 6.9e-08 3.2e-04 1.0e-06  tail 7.3e-07 5.5e-04 7.3e-07  plain 3.2e-07 3.5e-04 6.3e-07
+  dgamma_r        const 0.0e+00 2.3e-04 0.0e+00  offset 5.5e-03 2.2e-02 2.6e-05  outlier 2.6e-07 3.1e-04 3.8e-07  tail 1.0e-06 3.6e-04 1.0e-06  plain 6.7e-07 3.3e-04 5.8e-07
+  dbeta_r         const 0.0e+00 1.5e-03 0.0e+00  offset 6.8e-07 3.2e-04 1.2e-06  outlier 5.8e-07 3.4e-04 4.4e-07  tail 1.3e-06 5.5e-04 1.3e-06  plain 3.4e-07 3.5e-04 5.0e-07
+syncbn hw4
+  mean            offset 4.7e-06 3.2e-04 9.0e-07  outlier 9.8e-08 1.9e-05 2.1e-08  tail 2.1e-08 5.5e-06 3.8e-08  plain 3.0e-08 5.2e-06 3.0e-08
+  invstd          offset 6.8e-06 4.0e-05 2.3e-06  outlier 1.6e-08 2.9e-06 1.6e-09  tail 5.9e-08 8.3e-06 6.6e-10  plain 7.5e-09 5.7e-06 3.7e-08
+  running_mean    offset 5.7e-07 3.3e-05 9.0e-08  outlier 7.3e-09 3.9e-06 7.3e-09  tail 4.3e-09 2.6e-06 4.3e-09  plain 2.3e-09 1.4e-06 1.4e-09
+  running_var     offset 4.0e-05 1.6e-04 3.7e-08  outlier 1.5e-07 3.7e-05 1.5e-07  tail 7.0e-09 1.4e-05 7.0e-09  plain 1.0e-07 1.0e-05 1.7e-08
+  y               tail 1.2e-07 4.6e-05 2.1e-07  plain 1.5e-07 3.7e-05 1.5e-07
+  dx              const 1.0e-05 2.7e-03 1.1e-05  tail 7.3e-08 4.2e-05 5.1e-08  plain 4.1e-08 2.9e-05 4.2e-08
+  dgamma          const 0.0e+00 1.2e-04 0.0e+00  offset 6.4e-03 2.5e-02 2.1e-05  outlier 8.3e-08 1.5e-04 3.6e-08  tail 8.3e-08 1.7e-04 1.6e-07  plain 1.3e-07 1.5e-04 1.1e-07
+  dbeta           const 0.0e+00 4.8e-04 0.0e+00  offset 4.5e-08 2.4e-04 4.5e-08  outlier 4.7e-08 1.5e-04 1.7e-07  tail 1.6e-07 1.9e-04 1.6e-07  plain 2.9e-07 1.5e-04 2.9e-07
+  dgamma_r        const 0.0e+00 8.9e-05 0.0e+00  offset 7.7e-03 3.1e-02 8.0e-06  outlier 2.6e-08 1.2e-04 1.1e-07  tail 5.7e-08 1.3e-04 1.9e-07  plain 1.8e-07 1.3e-04 2.9e-07
+  dbeta_r         const 0.0e+00 2.9e-04 0.0e+00  offset 1.8e-07 1.4e-04 2.2e-07  outlier 1.3e-07 1.4e-04 1.3e-07  tail 1.4e-07 1.5e-04 1.4e-07  plain 2.6e-07 1.4e-04 2.6e-07
+syncbn two-slices
+  mean            offset 8.4e-06 3.2e-04 3.1e-06  outlier 7.6e-07 2.4e-05 2.8e-07  tail 6.1e-08 5.2e-06 8.8e-08  plain 1.4e-07 6.1e-06 2.0e-08
+  invstd          offset 3.5e-07 4.1e-05 1.3e-07  outlier 5.1e-09 2.7e-06 9.8e-09  tail 1.8e-08 8.1e-06 4.2e-08  plain 5.4e-09 6.0e-06 5.4e-09
+  running_mean    offset 3.6e-07 3.3e-05 3.6e-07  outlier 3.7e-08 4.4e-06 3.7e-08  tail 2.7e-09 2.5e-06 1.2e-08  plain 2.7e-09 1.5e-06 2.7e-09
+  running_var     offset 4.1e-05 1.6e-04 3.8e-08  outlier 3.2e-08 4.5e-05 4.4e-07  tail 1.1e-08 1.4e-05 1.1e-08  plain 3.7e-08 9.5e-06 3.7e-08
+  y               tail 3.7e-07 7.2e-05 3.1e-07  plain 3.0e-07 7.5e-05 3.0e-07
+  dx              const 6.8e-06 2.6e-03 9.8e-06  tail 3.3e-07 6.5e-05 3.3e-07  plain 1.3e-07 4.2e-05 9.3e-08
+  dgamma          const 0.0e+00 3.0e-03 0.0e+00  offset 4.0e-01 1.6e+00 3.2e-04  outlier 1.2e-05 3.9e-03 7.5e-06  tail 2.1e-05 5.5e-03 1.3e-05  plain 1.2e-05 5.3e-03 2.1e-05
+  dbeta           const 0.0e+00 2.2e-01 0.0e+00  offset 7.7e-06 3.5e-03 2.1e-05  outlier 4.8e-06 4.0e-03 8.6e-06  tail 4.9e-06 6.2e-03 2.6e-05  plain 2.2e-05 7.3e-03 2.2e-05
+  dgamma_r        const 0.0e+00 2.5e-03 0.0e+00  offset 3.7e-01 1.5e+00 7.8e-04  outlier 8.5e-06 3.6e-03 1.0e-05  tail 2.5e-05 4.7e-03 1.1e-05  plain 1.8e-05 5.3e-03 2.0e-05
+  dbeta_r         const 0.0e+00 1.6e-01 0.0e+00  offset 1.6e-05 3.8e-03 1.3e-05  outlier 1.2e-05 3.0e-03 8.0e-06  tail 1.2e-05 5.5e-03 2.1e-05  plain 1.5e-05 5.3e-03 1.2e-05
+syncbn four-slices
+  mean            offset 6.0e-06 3.2e-04 1.6e-06  outlier 6.2e-08 1.4e-05 1.8e-07  tail 8.1e-09 3.4e-06 2.2e-08  plain 1.4e-08 5.9e-06 1.4e-08
+  invstd          offset 3.8e-07 4.1e-05 1.4e-07  outlier 2.4e-09 3.1e-06 2.4e-09  tail 4.9e-09 8.9e-06 4.9e-09  plain 4.2e-09 6.0e-06 3.4e-08
+  running_mean    offset 2.7e-07 3.3e-05 2.1e-07  outlier 2.6e-08 3.5e-06 1.9e-08  tail 1.1e-08 2.4e-06 1.1e-08  plain 4.6e-09 1.5e-06 2.9e-09
+  running_var     offset 1.2e-05 5.0e-05 5.0e-08  outlier 6.0e-08 3.2e-05 4.2e-07  tail 1.4e-08 1.4e-05 1.4e-08  plain 4.3e-08 9.5e-06 4.3e-08
+  y               tail 3.4e-07 6.9e-05 2.6e-07  plain 2.2e-07 6.6e-05 4.1e-07
+  dx              const 1.8e-05 2.6e-03 1.3e-05  tail 2.9e-07 7.5e-05 2.3e-07  plain 1.1e-07 4.0e-05 1.3e-07
+  dgamma          const 0.0e+00 3.9e-03 0.0e+00  offset 8.8e-02 3.5e-01 3.7e-04  outlier 6.6e-06 4.7e-03 1.6e-05  tail 1.5e-05 5.9e-03 1.8e-05  plain 3.2e-05 7.4e-03 1.7e-05
+  dbeta           const 0.0e+00 3.8e-01 0.0e+00  offset 1.5e-05 5.1e-03 4.2e-05  outlier 1.3e-05 4.3e-03 1.8e-05  tail 1.2e-05 6.6e-03 2.3e-05  plain 6.1e-06 9.5e-03 3.7e-05
+  dgamma_r        const 0.0e+00 3.4e-03 0.0e+00  offset 1.3e-01 5.0e-01 4.0e-04  outlier 7.7e-06 4.4e-03 1.5e-05  tail 6.9e-06 4.7e-03 1.3e-05  plain 1.4e-05 5.4e-03 2.1e-05
+  dbeta_r         const 0.0e+00 2.9e-01 0.0e+00  offset 1.8e-05 4.7e-03 2.9e-05  outlier 8.8e-06 4.6e-03 1.2e-05  tail 1.9e-05 5.5e-03 1.9e-05  plain 8.5e-06 7.6e-03 3.0e-05
+syncbn channels-70
+  mean            offset 2.9e-06 3.2e-04 2.4e-06  outlier 4.5e-07 4.6e-05 7.0e-07  tail 5.0e-08 1.1e-05 1.6e-07  plain 2.1e-08 1.1e-05 9.9e-08
+  invstd          offset 1.1e-05 5.5e-05 6.8e-06  outlier 2.2e-08 2.5e-06 1.5e-08  tail 5.4e-08 7.6e-06 7.9e-08  plain 3.9e-08 7.5e-06 7.7e-08
+  running_mean    offset 3.4e-07 3.4e-05 2.6e-07  outlier 5.6e-08 6.3e-06 7.0e-08  tail 1.2e-08 3.1e-06 2.3e-08  plain 7.9e-09 2.4e-06 1.0e-08
+  running_var     offset 1.7e-05 6.8e-05 8.0e-08  outlier 9.4e-07 7.9e-05 9.3e-07  tail 6.5e-08 1.5e-05 6.5e-08  plain 5.2e-08 1.6e-05 8.8e-08
+  y               offset 4.6e-03 1.8e-02 9.0e-06  outlier 3.8e-07 8.4e-05 6.7e-07  tail 4.2e-07 6.3e-05 4.7e-07  plain 4.3e-07 6.8e-05 8.1e-07
+  dx              const 1.9e-05 2.8e-03 1.2e-05  offset 1.8e-02 7.1e-02 1.3e-05  outlier 8.4e-08 3.0e-05 5.1e-08  tail 3.4e-07 8.3e-05 3.4e-07  plain 3.3e-07 6.8e-05 3.2e-07
+  dgamma          const 0.0e+00 1.6e-04 0.0e+00  offset 1.2e-02 4.8e-02 1.3e-04  outlier 1.3e-06 3.3e-04 2.6e-06  tail 1.0e-06 4.4e-04 1.3e-06  plain 2.9e-06 3.8e-04 1.8e-06
+  dbeta           const 0.0e+00 8.0e-04 0.0e+00  offset 1.7e-06 6.3e-04 1.7e-06  outlier 1.5e-06 3.5e-04 1.1e-06  tail 1.4e-06 3.6e-04 1.2e-06  plain 1.1e-06 3.5e-04 1.1e-06
+  dgamma_r        const 0.0e+00 1.4e-04 0.0e+00  offset 1.2e-02 4.7e-02 9.7e-05  outlier 1.9e-06 2.9e-04 2.4e-06  tail 1.0e-06 3.9e-04 1.3e-06  plain 2.8e-06 3.6e-04 1.9e-06
+  dbeta_r         const 0.0e+00 6.2e-04 0.0e+00  offset 1.3e-06 5.1e-04 7.5e-07  outlier 1.3e-06 3.2e-04 7.3e-07  tail 1.2e-06 2.8e-04 9.1e-07  plain 7.2e-07 3.7e-04 9.5e-07
+syncbn module two-slices
+  mean            offset 8.4e-06 3.2e-04 7.4e-07  outlier 7.6e-07 2.4e-05 2.0e-07  tail 6.1e-08 5.2e-06 6.1e-08  plain 1.4e-07 6.1e-06 2.0e-08
+  invstd          offset 3.5e-07 4.1e-05 1.3e-07  outlier 5.1e-09 2.7e-06 5.1e-09  tail 1.8e-08 8.1e-06 1.8e-08  plain 5.4e-09 6.0e-06 5.4e-09
+  running_mean    offset 3.6e-07 3.3e-05 1.2e-07  outlier 3.7e-08 4.4e-06 2.3e-08  tail 2.7e-09 2.5e-06 2.7e-09  plain 2.7e-09 1.5e-06 2.7e-09
+  running_var     offset 4.1e-05 1.6e-04 3.8e-08  outlier 3.2e-08 4.5e-05 5.1e-07  tail 1.1e-08 1.4e-05 1.1e-08  plain 3.7e-08 9.5e-06 3.7e-08
+  y               tail 3.7e-07 7.2e-05 2.4e-07  plain 3.0e-07 7.5e-05 3.0e-07
+  dx              const 6.8e-06 2.6e-03 9.8e-06  tail 3.3e-07 6.5e-05 2.5e-07  plain 1.3e-07 4.2e-05 9.3e-08
+  dgamma          const 0.0e+00 3.0e-03 0.0e+00  offset 4.0e-01 1.6e+00 6.5e-05  outlier 1.2e-05 3.9e-03 3.7e-06  tail 2.1e-05 5.5e-03 1.9e-05  plain 1.2e-05 5.3e-03 2.0e-05
+  dbeta           const 0.0e+00 2.2e-01 0.0e+00  offset 7.7e-06 3.5e-03 1.7e-05  outlier 4.8e-06 4.0e-03 9.6e-07  tail 4.9e-06 6.2e-03 4.9e-06  plain 2.2e-05 7.3e-03 8.7e-06
 """
 import ctypes
 
@@ -269,7 +348,7 @@ def _floor(name, n):
     if name in ("y", "yp"):
         return 1e-5, 2e-5
     if name in ("mean", "invstd", "running_mean", "running_var"):
-        return 1e-5, 1e-6
+        return R.STAT_FLOOR  # 1e-5, 1e-6: the host test of eeadv.syncbn's merge takes the same pair
     if name in ("dgamma", "dbeta"):
         return 2e-5, 2e-5 * max(1.0, float(n) ** 0.5)
     return 2e-5, 2e-5  # dx, dresidual
@@ -377,13 +456,16 @@ def _verify(case, c, got, ref, training, res, exact_y, exact_dx, res_in=None):
     still = sorted(set(zero_gamma) | (set(const) if exact_dx else set()))
     if got.get("dx") is not None and still:
         assert bool((got["dx"][:, still] == 0).all()), "%s: dx != 0 on channels %s" % (case, still)
-    _mask_agrees(case, got["y"], ref["pre"].to(DEV), gamma)
     stat_names = ["mean", "invstd", "running_mean", "running_var"] if training else []
-    for name in stat_names + ["y", "dx", "dresidual", "dgamma", "dbeta"]:
-        if got.get(name) is None:
-            continue
-        skip = const if name in stat_names else (flat if name == "y" else (still if name == "dx" else ()))
-        _bounded(case, name, got[name], ref[name], stock[name], ref_stock[name], kinds, n, skip)
+
+    def bounded(names):
+        for name in names:
+            if got.get(name) is not None:
+                skip = const if name in stat_names else (flat if name == "y" else (still if name == "dx" else ()))
+                _bounded(case, name, got[name], ref[name], stock[name], ref_stock[name], kinds, n, skip)
+    bounded(stat_names)  # before the masks: a wrong statistic is the cause, a flipped branch its symptom
+    _mask_agrees(case, got["y"], ref["pre"].to(DEV), gamma)
+    bounded(["y", "dx", "dresidual", "dgamma", "dbeta"])
 
 
 # ---- ee_bn_act_fwd_f32 / ee_bn_act_bwd2_f32: every dispatch branch -------------------------------------------------------------------------
@@ -747,3 +829,202 @@ def test_pair_statistics_feed_the_train_mode_consumer(ops, monkeypatch, H, mt):
     y3b, y1b = ops.conv3x3s2_pair_fwd(x, w10, 64)
     assert torch.equal(y3, y3b) and torch.equal(y1, y1b) and stats.shape[1] * cnt == 3 * (H // 2) ** 2
     _verify_train_pre("pair_stats H=%d mt=%s" % (H, mt), ops, y3, stats, cnt, w2, seed)
+
+
+# ---- ee_syncbn_*: the local halves of SyncBatchNorm, for W simulated ranks in this one process ------------------------------------------
+def _sync_ranks(ops, c, parts, res, two_addends=False, mask_from_x=False, want_dres=None):
+    """The four ee_syncbn_* entry points in the order eeadv.syncbn.SyncBnActFn issues them, for every rank `parts` (index lists, a partition
+    of the batch) deals images to, one rank after another on this device.  The all_gather is a stack of the ranks' moments in rank order,
+    the all_reduce a sum of the ranks' sums in rank order; no process group, nothing spawned.  Returns whole-batch y / dx / dresidual, the
+    statistics as rank 0 holds them (`ranks`: as every rank holds them), every rank's own [C, 2] sums (`local`) and their sum."""
+    shard = lambda t: [t[idx].contiguous() for idx in parts]
+    W = len(parts)
+    xs, dys, d2s = shard(c["x"]), shard(c["dy"]), [None] * W
+    rs = shard(c["residual"]) if res else [None] * W
+    if two_addends:  # dy as two addends whose fp32 sum is exact: the kernels add them on load
+        hi, lo = R.exact_addends(c["dy"])
+        assert torch.equal(hi + lo, c["dy"]) and bool((lo != 0).any())
+        dys, d2s = shard(hi), shard(lo)
+    all_moments = torch.stack([ops.syncbn_stats(x) for x in xs])  # [W, C, 3]
+    ranks = []
+    for x, r in zip(xs, rs):
+        rm, rv = c["rm"].clone(), c["rv"].clone()
+        y, sm, si = ops.syncbn_apply(x, r, c["gamma"], c["beta"], all_moments, rm, rv, MOM, EPS, True)
+        ranks.append({"y": y, "mean": sm, "invstd": si, "running_mean": rm, "running_var": rv})
+    ys = [None if mask_from_x else f["y"] for f in ranks]
+    local = [ops.syncbn_bwd_sums(dy, d2, y, x, c["gamma"], c["beta"], f["mean"], f["invstd"], True) for dy, d2, y, x, f in zip(dys, d2s, ys, xs, ranks)]
+    total = local[0].clone()
+    for s in local[1:]:
+        total = total + s
+    n_global = float(all_moments[:, 0, 2].sum().item())
+    want_dres = res if want_dres is None else want_dres
+    bw = [ops.syncbn_bwd_apply(dy, d2, y, x, c["gamma"], c["beta"], f["mean"], f["invstd"], total, n_global, True, True, want_dres)
+          for dy, d2, y, x, f in zip(dys, d2s, ys, xs, ranks)]
+    out = {k: ranks[0][k] for k in ("mean", "invstd", "running_mean", "running_var")}
+    out.update(y=R.gather_back([f["y"] for f in ranks], parts), dx=R.gather_back([b[0] for b in bw], parts),
+               dresidual=R.gather_back([b[1] for b in bw], parts) if want_dres else None, dgamma=total[:, 1].contiguous(), dbeta=total[:, 0].contiguous(),
+               all_moments=all_moments, ranks=ranks, local=local)
+    return out
+
+
+SYNC_BITS = ("mean", "invstd", "running_mean", "running_var", "y", "dx", "dresidual", "dgamma", "dbeta", "all_moments")
+
+
+def _sync_same_bits(case, a, b, what, keys=SYNC_BITS):
+    for k in keys:
+        assert (a[k] is None and b[k] is None) or torch.equal(a[k], b[k]), "%s: %s %s" % (case, k, what)
+    if "dgamma" in keys:
+        for r, (u, v) in enumerate(zip(a["local"], b["local"])):
+            assert torch.equal(u, v), "%s: rank %d's sums %s" % (case, r, what)
+
+
+def _stock_rank_grads(c, res, parts):
+    """torch's stock fp32 batch_norm / autograd over the whole batch with the incoming gradient zeroed outside one rank's images: that rank's
+    share of (dgamma, dbeta) as the stock kernels sum it, [W, C] each - and the float64 shares on the stock ReLU branch"""
+    w, b = (c[k].clone().requires_grad_(True) for k in ("gamma", "beta"))
+    pre = F.batch_norm(c["x"], c["rm"].clone(), c["rv"].clone(), w, b, True, MOM, EPS)
+    y = F.relu(pre + c["residual"] if res else pre)
+    dg, db = [], []
+    for idx in parts:
+        dy_r = torch.zeros_like(c["dy"])
+        dy_r[idx] = c["dy"][idx]
+        g = torch.autograd.grad(y, [w, b], dy_r, retain_graph=True)
+        dg.append(g[0])
+        db.append(g[1])
+    st = R.bn_ref64(c["x"], c["gamma"], c["beta"], c["rm"], c["rv"], MOM, EPS, True, relu=True)
+    ref_dg, ref_db = R.rank_param_grads64(c["x"], st["mean"], st["invstd"], c["dy"], y.detach() > 0, parts)
+    return torch.stack(dg), torch.stack(db), ref_dg, ref_db
+
+
+def _sync_verify(case, c, got, parts, res):
+    """the whole batch against bn_ref64 (_verify: exact on `const` / gamma == 0 channels, bounded elsewhere, masks), then every rank's own
+    sums against that rank's float64 share, the floor's n the rank's own element count"""
+    ref = R.bn_ref64(c["x"], c["gamma"], c["beta"], c["rm"], c["rv"], MOM, EPS, True, residual=c["residual"] if res else None, relu=True,
+                     dy=c["dy"], mask=got["y"] > 0)
+    _verify(case, c, got, ref, True, res, True, not res)
+    ref_dg, ref_db = R.rank_param_grads64(c["x"], ref["mean"], ref["invstd"], c["dy"], got["y"] > 0, parts)
+    stock_dg, stock_db, sref_dg, sref_db = _stock_rank_grads(c, res, parts)
+    per_image = c["x"][0, 0].numel()
+    for r, idx in enumerate(parts):
+        who = "%s rank %d of %d" % (case, r, len(parts))
+        _bounded(who, "dgamma", got["local"][r][:, 1], ref_dg[r], stock_dg[r], sref_dg[r], c["kinds"], len(idx) * per_image)
+        _bounded(who, "dbeta", got["local"][r][:, 0], ref_db[r], stock_db[r], sref_db[r], c["kinds"], len(idx) * per_image)
+
+
+SYNC_PATHS = [(name, label) for name in R.SYNC_CASES for label in R.SYNC_DEALS[name]]
+
+
+@pytest.mark.parametrize("res", [False, True])
+@pytest.mark.parametrize("name,label", SYNC_PATHS)
+def test_syncbn_kernels_over_simulated_ranks(ops, name, label, res):
+    shape, seed = R.SYNC_CASES[name]
+    parts = R.SYNC_DEALS[name][label]
+    c = _to_dev(R.hard_case(shape, seed))
+    case = "syncbn %s %s%s" % (name, label, " +res" if res else "")
+    assert all(ops.syncbn_supported(c["x"][idx].contiguous()) for idx in parts)
+    got = _sync_ranks(ops, c, parts, res)
+    _sync_same_bits(case, got, _sync_ranks(ops, c, parts, res), "differs between two runs")
+    # every rank merges the same moments in the same order: the statistics are the same bits everywhere
+    for r, f in enumerate(got["ranks"]):
+        for k in ("mean", "invstd", "running_mean", "running_var"):
+            assert torch.equal(f[k], got["ranks"][0][k]), "%s: rank %d's %s differs from rank 0's" % (case, r, k)
+    # a rank's moments of a `const` channel are exactly (0.75, 0, its count); _verify then holds the merged statistics to _exact_stats
+    const = [i for i, k in enumerate(c["kinds"]) if k == "const"]
+    for r, idx in enumerate(parts):
+        want = torch.tensor([R.CONST, 0.0, float(len(idx) * shape[2] * shape[3])], device=DEV)
+        assert bool((got["all_moments"][r, const] == want).all()), "%s: rank %d's moments of the constant channels" % (case, r)
+        assert bool((got["all_moments"][r, :, 2] == want[2]).all()), "%s: rank %d's counts" % (case, r)
+    # the other forms of the backward return the bits of the plain one
+    back = ("dx", "dresidual", "dgamma", "dbeta")
+    if not res:
+        _sync_same_bits(case, got, _sync_ranks(ops, c, parts, res, mask_from_x=True), "with the mask from x differs from the mask from y", back)
+    _sync_same_bits(case, got, _sync_ranks(ops, c, parts, res, two_addends=True), "with dy in two addends differs", back)
+    other = _sync_ranks(ops, c, parts, res, want_dres=not res)
+    _sync_same_bits(case, got, other, "differs when dresidual is %s" % ("left out" if res else "asked for"), ("dx", "dgamma", "dbeta"))
+    if not res:  # dresidual is dz itself
+        assert torch.equal(other["dresidual"], torch.where(got["y"] > 0, c["dy"], torch.zeros_like(c["dy"]))), case + ": dresidual != dy under the mask"
+    _sync_verify(case, c, got, parts, res)
+    # the ranks in the opposite order (the merge and the sum of the sums run backwards): other bits, the same bounds
+    _sync_verify(case + " reversed", c, _sync_ranks(ops, c, parts[::-1], res), parts[::-1], res)
+
+
+def _sync_module(c):
+    """a training-mode eeadv.syncbn.SyncBatchNorm2d (converted from models.BatchNorm2d, no process group) carrying the case's affine pair
+    and running statistics"""
+    from eeadv import models, syncbn
+    bn = models.BatchNorm2d(len(c["kinds"]), eps=EPS, momentum=MOM)
+    sbn = syncbn.convert_sync_batchnorm(torch.nn.Sequential(bn))[0].to(DEV).train()
+    assert isinstance(sbn, syncbn.SyncBatchNorm2d)
+    with torch.no_grad():
+        for p, v in ((sbn.weight, c["gamma"]), (sbn.bias, c["beta"]), (sbn.running_mean, c["rm"]), (sbn.running_var, c["rv"])):
+            p.copy_(v)
+    return sbn
+
+
+@pytest.mark.parametrize("equal_shards", [True, False])
+@pytest.mark.parametrize("res", [False, True])
+def test_syncbn_module_one_rank_on_hard_channels(ops, monkeypatch, res, equal_shards):
+    """eeadv.syncbn.SyncBnActFn through models.bn_act on a converted SyncBatchNorm2d, no process group: the exchange is the identity, the
+    global count host arithmetic (_EQUAL_SHARDS) or read from the moments"""
+    from eeadv import models, syncbn
+    shape, seed = R.SYNC_CASES["two-slices"]
+    c = _to_dev(R.hard_case(shape, seed))
+    monkeypatch.setattr(syncbn, "_EQUAL_SHARDS", equal_shards)
+    seen = []
+    apply = ops.syncbn_apply
+    monkeypatch.setattr(syncbn.ops, "syncbn_apply", lambda *a: seen.append(apply(*a)) or seen[-1])
+    sbn = _sync_module(c)
+    x = c["x"].clone().requires_grad_(True)
+    r = c["residual"].clone().requires_grad_(True) if res else None
+    y = models.bn_act(sbn, x, r, relu=True)
+    y.backward(c["dy"])
+    assert len(seen) == 1, "the module did not take the ee_syncbn_* path"
+    got = {"y": y.detach(), "mean": seen[0][1], "invstd": seen[0][2], "running_mean": sbn.running_mean, "running_var": sbn.running_var, "dx": x.grad,
+           "dresidual": r.grad if res else None, "dgamma": sbn.weight.grad, "dbeta": sbn.bias.grad}
+    ref = R.bn_ref64(c["x"], c["gamma"], c["beta"], c["rm"], c["rv"], MOM, EPS, True, residual=c["residual"] if res else None, relu=True,
+                     dy=c["dy"], mask=got["y"] > 0)
+    _verify("syncbn module two-slices%s equal_shards=%s" % (" +res" if res else "", equal_shards), c, got, ref, True, res, True, not res)
+
+
+@pytest.mark.parametrize("which", ["x", "residual"])
+def test_syncbn_module_sends_a_misaligned_tensor_to_the_parent_path(ops, monkeypatch, which):
+    """a dense view that starts one float into its storage: the ee_syncbn_* entry points refuse it (they read float4), so the module
+    must not offer it to them - nn.SyncBatchNorm's own forward takes over, and the result is still that of bn_ref64"""
+    from eeadv import _native as N, models, syncbn
+    shape, seed = R.SYNC_CASES["one-slice"]
+    c = _to_dev(R.hard_case(shape, seed))
+    with pytest.raises(N.EEError, match="not aligned"):  # ee_syncbn_stats_f32 checks the pointer before its first launch
+        ops.syncbn_stats(_misaligned(c["x"]))
+    assert ops.syncbn_supported(c["x"]) and not ops.syncbn_supported(_misaligned(c["x"]))
+    calls = []
+    stats = ops.syncbn_stats
+    monkeypatch.setattr(syncbn.ops, "syncbn_stats", lambda t: calls.append(1) or stats(t))
+    for res in ((False, True) if which == "x" else (True,)):
+        sbn = _sync_module(c)
+        x = (_misaligned(c["x"]) if which == "x" else c["x"].clone()).requires_grad_(True)
+        r = (_misaligned(c["residual"]) if which == "residual" else c["residual"].clone()).requires_grad_(True) if res else None
+        assert sbn._fast(x) == (which != "x")
+        y = models.bn_act(sbn, x, r, relu=True)
+        y.backward(c["dy"])
+        assert not calls, "a misaligned %s reached the ee_syncbn_* kernels" % which
+        ref = R.bn_ref64(c["x"], c["gamma"], c["beta"], c["rm"], c["rv"], MOM, EPS, True, residual=c["residual"] if res else None, relu=True,
+                         dy=c["dy"], mask=y.detach() > 0)
+        case = "syncbn misaligned %s%s" % (which, " +res" if res else "")
+        n = c["x"].numel() // shape[1]
+        for name, t in (("y", y.detach()), ("dx", x.grad)):  # the floors alone: the reference stands in for the stock side, whose error is then 0
+            _bounded(case, name, t, ref[name], ref[name], ref[name], c["kinds"], n)
+
+
+def test_syncbn_module_copies_a_misaligned_incoming_gradient(ops, monkeypatch):
+    """aligned x and residual take the ee_syncbn_* path; an incoming gradient that starts off a 16-byte boundary is copied, not refused"""
+    from eeadv import models, syncbn
+    shape, seed = R.SYNC_CASES["one-slice"]
+    c = _to_dev(R.hard_case(shape, seed))
+    calls, grads = [], []
+    stats = ops.syncbn_stats
+    monkeypatch.setattr(syncbn.ops, "syncbn_stats", lambda t: calls.append(1) or stats(t))
+    for dy in (c["dy"], _misaligned(c["dy"])):
+        sbn, x = _sync_module(c), c["x"].clone().requires_grad_(True)
+        models.bn_act(sbn, x, c["residual"], relu=True).backward(dy)
+        grads.append((x.grad, sbn.weight.grad, sbn.bias.grad))
+    assert calls == [1, 1] and all(torch.equal(u, v) for u, v in zip(*grads))

@@ -113,6 +113,36 @@ def test_syncbn_two_ranks_gloo_host(tmp_path):
     _check(tmp_path)
 
 
+def _sync_deals():
+    import bn_reference as R
+    return [(name, label) for name in R.SYNC_CASES for label in R.SYNC_DEALS[name]]
+
+
+@pytest.mark.parametrize("name,label", _sync_deals())
+def test_host_merge_of_the_ranks_moments_against_float64(name, label):
+    """the torch restatement of the kernels' exchange (_host_stats per shard, merge_moments in rank order) on the fp32 shards of the hard
+    channels of tests/bn_reference.py, dealt as tests/test_gpu_bn_hard_channels.py deals them to the kernels (one process, no group):
+    merged mean and M2 / n within the statistics floor of the float64 statistics of the whole batch; `const` channels exact."""
+    import bn_reference as R
+    from eeadv import syncbn
+    shape, seed = R.SYNC_CASES[name]
+    c, parts = R.hard_case(shape, seed), R.SYNC_DEALS[name][label]
+    per_image = shape[2] * shape[3]
+    ref = R.bn_ref64(c["x"], c["gamma"], c["beta"], c["rm"], c["rv"], 0.1, 1e-5, True, relu=True)
+    all_m = torch.stack([syncbn._host_stats(c["x"][idx].contiguous()) for idx in parts])
+    assert all_m.dtype == torch.float32 and all_m.shape == (len(parts), shape[1], 3)
+    mean, m2, n = syncbn.merge_moments(all_m)
+    assert bool((n == shape[0] * per_image).all())
+    const = [i for i, k in enumerate(c["kinds"]) if k == "const"]
+    for r, idx in enumerate(parts):
+        assert bool((all_m[r, const, 0] == R.CONST).all()) and bool((all_m[r, const, 1] == 0).all()) and bool((all_m[r, :, 2] == len(idx) * per_image).all())
+    assert bool((mean[const] == R.CONST).all()) and bool((m2[const] == 0).all())
+    rtol, atol = R.STAT_FLOOR
+    for what, got, want in (("mean", mean, ref["mean"]), ("M2 / n", m2 / n, ref["var"])):
+        err = (got.double() - want).abs()
+        assert bool((err <= atol + rtol * want.abs()).all()), (name, label, what, err.tolist())
+
+
 @pytest.mark.gpu
 def test_syncbn_two_ranks_sharing_the_gpu(tmp_path):
     """the same through the HIP kernels (ee_syncbn_*_f32): two processes on cuda:0, the [C, 3] / [C, 2] exchanges staged over gloo"""
