@@ -135,6 +135,7 @@ def main(argv=None):
                          else "--attack_method %s: the AWP driver validates with PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T, APGD+FAB+Square, Cascade, APGD-DLR, Rand or Cascade-Rand" % args.attack_method)
     driver.data_source(args.data, SPEC)  # an unusable --data fails here, before a model is built
     trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
+    trainer.fab_restarts_for(args)  # and a --fab_restarts on a method that runs no FAB
     trainer.norm_for(args)  # and a --norm it has no L2 for
     args.setdefault("cize", 64)
     args.num_classes = SPEC["num_classes"]

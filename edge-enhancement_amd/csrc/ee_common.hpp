@@ -119,5 +119,16 @@ struct Philox {
 };
 // 24 random bits -> [0,1), as torch's uniform_ does for float
 __device__ __forceinline__ float u01(uint32_t r) { return static_cast<float>(r >> 8) * (1.0f / 16777216.0f); }
+// four standard normals from the four words of one call: the Box-Muller pairs (x, y) and (z, w); 1 - u01 keeps the logarithm's argument in (0, 1]
+__device__ __forceinline__ void normal4(const uint4 &r, float (&z)[4]) {
+    const float u0 = 1.0f - u01(r.x), u1 = u01(r.y), u2 = 1.0f - u01(r.z), u3 = u01(r.w);
+    const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
+    z[0] = r0 * cosf(6.28318530717958647692f * u1);
+    z[1] = r0 * sinf(6.28318530717958647692f * u1);
+    z[2] = r1 * cosf(6.28318530717958647692f * u3);
+    z[3] = r1 * sinf(6.28318530717958647692f * u3);
+}
+// Philox stream ids: 0 (the default), 7 (ee_net2.hip) and 11 - 14 (ee_sqatk.hpp) are taken
+constexpr uint32_t kStreamFabStart = 15u;  // the random start of a FAB restart (ee_fab.hip)
 
 }  // namespace ee

@@ -97,12 +97,9 @@ __global__ __launch_bounds__(kBlock) void init_rng_kernel(float *__restrict__ x,
             z[2] = u01(r.z) * span + (-scale);
             z[3] = u01(r.w) * span + (-scale);
         } else {  // Box-Muller, two pairs
-            const float u0 = 1.0f - u01(r.x), u1 = u01(r.y), u2 = 1.0f - u01(r.z), u3 = u01(r.w);
-            const float r0 = sqrtf(-2.0f * logf(u0)), r1 = sqrtf(-2.0f * logf(u2));
-            z[0] = scale * (r0 * cosf(6.28318530717958647692f * u1));
-            z[1] = scale * (r0 * sinf(6.28318530717958647692f * u1));
-            z[2] = scale * (r1 * cosf(6.28318530717958647692f * u3));
-            z[3] = scale * (r1 * sinf(6.28318530717958647692f * u3));
+            normal4(r, z);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) z[k] = scale * z[k];
         }
         const int64_t base = v << 2;
 #pragma unroll

@@ -35,6 +35,9 @@
 // class k one backward pass (the logit gradient from ee_fab_diff_f32 with targets = k) and one ee_fab_select_f32 - the dual norm of that
 // class's gradient, dist = |z_k - z_y| / (1e-12 + n), and a running arg-min per sample that keeps (dist, k, df, the row) of the closest
 // linearised boundary.  One streaming pass and, on improvement, a copy; the reset before class 0 is a `first` flag of the same launch.
+//
+// Restarts add one launch outside the iteration, ee_fab_start_f32: the random point at distance min(res, eps) / 2
+// from x0 that restart r >= 1 begins at - from injected noise or from Philox, in the metric of the run.  The captured graph does not see it.
 #include <math.h>
 
 #include "ee_sample.hpp"
@@ -704,6 +707,105 @@ __global__ __launch_bounds__(kSampleBlock) void select_kernel(const float *__res
     }
 }
 
+// ---- the random start of a restart ---------------------------------------------------------------------------------
+// x = clamp(x0 + ((m t) / n) / 2, 0, 1) with m = min(res[b], eps), t a draw of D elements and n its norm in the threat model's own metric
+// (M = kLinf: max |t_i|, kL2: sqrt(sum t_i^2), kL1: sum |t_i|; the sums in double in the one order of ee_sample.hpp, rounded to float once).
+// DRAW: t comes from Philox, one call per group of four elements under the counter (b << 32) | (e >> 2) - a row's draw depends on (seed, b,
+// element) alone - uniform on [-1, 1) for Linf, standard normal otherwise; else t is the row of `noise`.  RES keeps t in registers between
+// the norm pass and the write pass, the streaming path reads or draws it again.  A row whose n is 0 or not finite is written as x0.  The
+// launch reads res and writes x: no scalar crosses workgroups.
+template <int M, bool DRAW, bool VEC>
+__device__ __forceinline__ void start_fetch(const Philox &ph, const float *noise_row, int b, int64_t e, int64_t D, float (&t)[4]) {
+    if (!DRAW) {
+        load4<VEC>(noise_row, e, D, t);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = 0.0f;
+    if (e >= D) return;  // a group past the row: nothing to draw (e is fixed by the thread and the group, not by data)
+    const uint4 r = ph((static_cast<uint64_t>(static_cast<uint32_t>(b)) << 32) | static_cast<uint64_t>(e >> 2), kStreamFabStart);
+    if (M == kLinf) {
+        t[0] = 2.0f * u01(r.x) - 1.0f;  // exact: u01 is a multiple of 2^-24 in [0, 1)
+        t[1] = 2.0f * u01(r.y) - 1.0f;
+        t[2] = 2.0f * u01(r.z) - 1.0f;
+        t[3] = 2.0f * u01(r.w) - 1.0f;
+    } else {
+        normal4(r, t);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (e + j >= D) t[j] = 0.0f;  // elements at or past D read as 0, as load4's do
+}
+
+template <bool RES, bool VEC, int M, bool DRAW>
+__global__ __launch_bounds__(kSampleBlock) void start_kernel(float *__restrict__ x, const float *__restrict__ x0, const float *__restrict__ res,
+                                                           const float *__restrict__ noise, int64_t D, float eps, uint64_t seed) {
+    __shared__ double sh[2 * kSampleWaves];
+    SampleReducer red{sh};
+    const int b = blockIdx.x;
+    const int64_t off = static_cast<int64_t>(b) * D;
+    const float *x0r = x0 + off, *nr = DRAW ? nullptr : noise + off;
+    float *xr = x + off;
+    const Philox ph(seed);
+    const int groups = groups_of(D);
+
+    // pass 1: the norm of the draw; the resident path keeps the draw in keep[]
+    float keep[kSampleElems];
+    double acc = 0.0;
+    auto first = [&](int g) {
+        float t[4];
+        start_fetch<M, DRAW, VEC>(ph, nr, b, group_element(g), D, t);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float a = fabsf(t[j]);
+            if constexpr (M == kL2)
+                acc = fma(static_cast<double>(a), static_cast<double>(a), acc);
+            else if constexpr (M == kL1)
+                acc += static_cast<double>(a);
+            else
+                acc = a != a ? static_cast<double>(INFINITY) : fmax(acc, static_cast<double>(a));  // a NaN makes the norm not finite, as in a sum
+            if (RES) keep[g * 4 + j] = t[j];
+        }
+    };
+    if (RES) {
+#pragma unroll
+        for (int g = 0; g < kSampleVecs; ++g) first(g);
+    } else {
+        for (int g = 0; g < groups; ++g) first(g);
+    }
+    float n;
+    if constexpr (M == kL2)
+        n = static_cast<float>(sqrt(red.sum(acc)));
+    else if constexpr (M == kL1)
+        n = static_cast<float>(red.sum(acc));
+    else
+        n = static_cast<float>(red.max(acc));  // the largest |t_i|, a float: exact
+    const float m = fminf(res[b], eps);
+    const bool live = isfinite(n) && n != 0.0f;  // uniform over the workgroup
+
+    // pass 2: the point, every operation rounded once
+    auto second = [&](int g) {
+        const int64_t e = group_element(g);
+        float t[4], ov[4], out[4];
+        if (RES) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = keep[g * 4 + j];
+        } else {
+            start_fetch<M, DRAW, VEC>(ph, nr, b, e, D, t);
+        }
+        load4<VEC>(x0r, e, D, ov);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[j] = live ? tclamp(ov[j] + ((m * t[j]) / n) * 0.5f, 0.0f, 1.0f) : ov[j];
+        store4<VEC>(xr, e, D, out);
+    };
+    if (RES) {
+#pragma unroll
+        for (int g = 0; g < kSampleVecs; ++g) second(g);
+    } else {
+        for (int g = 0; g < groups; ++g) second(g);
+    }
+}
+
 bool bad_shape(int64_t B, int64_t per_sample) {
     return B < 0 || per_sample < 0 || B > INT32_MAX / 2 || per_sample > INT32_MAX || (per_sample > 0 && B > INT64_MAX / per_sample);
 }
@@ -778,7 +880,34 @@ int launch_select(const float *g, const float *logits, const int64_t *labels, in
     return launch_status();
 }
 
+template <int M>
+int launch_start(float *x, const float *x0, const float *res, const float *noise, int64_t B, int64_t per_sample, float eps, uint64_t seed,
+                 bool resident, void *stream) {
+    const dim3 grid(static_cast<unsigned>(B)), block(kSampleBlock);
+    sample_launch(resident, sample_vec(per_sample, x, x0, noise), [&](auto RES, auto VEC) {  // a null noise counts as aligned: it is not read
+        if (noise)
+            EE_LAUNCH((start_kernel<RES, VEC, M, false>), grid, block, 0, as_stream(stream), x, x0, res, noise, per_sample, eps, seed);
+        else
+            EE_LAUNCH((start_kernel<RES, VEC, M, true>), grid, block, 0, as_stream(stream), x, x0, res, noise, per_sample, eps, seed);
+    });
+    return launch_status();
+}
+
 }  // namespace
+
+EE_API int ee_fab_start_f32(float *x, const float *x0, const float *res, const float *noise, int64_t B, int64_t per_sample, float eps, int metric,
+                            uint64_t seed, int path, void *stream) {
+    if (bad_shape(B, per_sample) || per_sample < 1 || metric < kLinf || metric > kL1 || !(eps >= 0.0f)) return EE_ERR_SHAPE;
+    bool resident;
+    if (const int rc = sample_path(path, per_sample, &resident)) return rc;
+    if (B == 0) return EE_OK;
+    if (!x || !x0 || !res) return EE_ERR_NULL;
+    if (!aligned4(x) || !aligned4(x0) || !aligned4(res) || !aligned4(noise)) return EE_ERR_ALIGN;
+    ProfScope prof(EE_K_FAB_STEP, as_stream(stream));
+    if (metric == kL2) return launch_start<kL2>(x, x0, res, noise, B, per_sample, eps, seed, resident, stream);
+    if (metric == kL1) return launch_start<kL1>(x, x0, res, noise, B, per_sample, eps, seed, resident, stream);
+    return launch_start<kLinf>(x, x0, res, noise, B, per_sample, eps, seed, resident, stream);
+}
 
 EE_API int ee_fab_select_f32(const float *g, const float *logits, const int64_t *labels, int k, int metric, int first, int64_t B, int K,
                              int64_t per_sample, float *best, int *best_k, float *w, float *df, void *stream) {

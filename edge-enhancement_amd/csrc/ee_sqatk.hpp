@@ -6,7 +6,7 @@
 
 namespace ee {
 
-// Philox stream ids; 0 (the default) and 7 (ee_net2.hip) are taken
+// Philox stream ids; 0 (the default), 7 (ee_net2.hip) and 15 (kStreamFabStart, ee_common.hpp) are taken
 constexpr uint32_t kStreamWindow = 11u;   // window 1 of a proposal (both norms)
 constexpr uint32_t kStreamStripe = 12u;   // the striped start (Linf)
 constexpr uint32_t kStreamWindow2 = 13u;  // window 2 of a proposal (L2)

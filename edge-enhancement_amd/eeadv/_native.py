@@ -104,6 +104,8 @@ SIGNATURES = {
     "ee_fab_commit_l1_f32": [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p],
     # untargeted FAB: g, logits, labels, k, metric, first, B, K, per_sample, best, best_k, w, df, stream
     "ee_fab_select_f32": [c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_i, c_l, c_p, c_p, c_p, c_p, c_p],
+    # the random start of a FAB restart: x, x0, res, noise_or_null, B, per_sample, eps, metric, seed, path, stream
+    "ee_fab_start_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_f, c_i, c_u64, c_i, c_p],
     "ee_add_square_fwd_f32": [c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_add_square_bwd_f32": [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_i, c_p, c_p],
     "ee_square_draw_f32": [c_p, c_l, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],

@@ -25,6 +25,14 @@ from . import ops, runtime
 STAGES = ("APGD-CE", "APGD-T", "FAB-T", "Square")
 
 
+def _fab_restarts_kw(args):
+    """What args.fab_restarts (default 1) adds to the FAB-T stage's call: nothing for one restart."""
+    n = int(getattr(args, "fab_restarts", 1) or 1)
+    if n < 1:
+        raise ValueError("fab_restarts must be at least 1, got %d" % n)
+    return {} if n == 1 else {"n_restarts": n}
+
+
 def default_stages(args, num_steps, n_class, n_target_classes=9, norm="Linf"):
     """[(name, fn)] of AutoAttack's `standard` order; fn(model, args, x, y, order) -> (x_adv, robust) runs one stage on one full batch, `order`
     being the class order of the clean logits [B, n_t + 1] (the targets of APGD-T and FAB-T: no clean forward of their own).  norm: 'Linf'
@@ -33,10 +41,11 @@ def default_stages(args, num_steps, n_class, n_target_classes=9, norm="Linf"):
     fab_iters = int(getattr(args, "fab_iters", 100))
     queries = int(getattr(args, "square_queries", 5000))
     kw = A._norm_kw(norm)  # empty for Linf
+    rkw = _fab_restarts_kw(args)  # empty for one restart
     return [
         ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", **kw)),
         ("APGD-T", lambda model, a, x, y, order: A.APGD_T(model, a, x, y, num_steps, n_class, n_target_classes, order=order, **kw)),
-        ("FAB-T", lambda model, a, x, y, order: A.FAB_T(model, a, x, y, n_class, fab_iters, n_target_classes, order=order, **kw)[:2]),
+        ("FAB-T", lambda model, a, x, y, order: A.FAB_T(model, a, x, y, n_class, fab_iters, n_target_classes, order=order, **kw, **rkw)[:2]),
         ("Square", lambda model, a, x, y, order: A.Square(model, a, x, y, queries, **kw)[:2]),
     ]
 
@@ -47,10 +56,11 @@ def l1_stages(args, num_steps, n_class, n_target_classes=9):
     default_stages(norm="L1") stays refused."""
     fab_iters = int(getattr(args, "fab_iters", 100))
     queries = int(getattr(args, "square_queries", 5000))
+    rkw = _fab_restarts_kw(args)  # empty for one restart
     return [
         ("APGD-L1-CE", lambda model, a, x, y, order: A.APGD_L1(model, a, x, y, num_steps, "ce")),
         ("APGD-T-L1", lambda model, a, x, y, order: A.APGD_T_L1(model, a, x, y, num_steps, n_class, n_target_classes, order=order)),
-        ("FAB-T-L1", lambda model, a, x, y, order: A.FAB_T_L1(model, a, x, y, n_class, fab_iters, n_target_classes, order=order)[:2]),
+        ("FAB-T-L1", lambda model, a, x, y, order: A.FAB_T_L1(model, a, x, y, n_class, fab_iters, n_target_classes, order=order, **rkw)[:2]),
         ("Square-L1", lambda model, a, x, y, order: A.Square_L1(model, a, x, y, queries)[:2]),
     ]
 

@@ -43,6 +43,7 @@ def make_parser(description, default_data="synthetic", with_local_rank=False):
     parser.add_argument('--norm', default='Linf', type=str, help='threat model of the evaluation attack, radius --epsilon of the config: Linf (default) or L2; L2 exists for APGD-CE, APGD-T, APGD, APGD-DLR, Rand and Cascade-Rand and every other method refuses it')
     parser.add_argument('--square_queries', default=5000, type=int, help='forwards per sample of the Square attack at most (default: 5000); not the defence\'s n_queries')
     parser.add_argument('--fab_iters', default=100, type=int, help='iterations of FAB-T per target class, and of the one run of FAB-U / FAB-L1-U (default: 100)')
+    parser.add_argument('--fab_restarts', default=1, type=int, help='runs of every FAB (FAB-T per target class, FAB-U, their L1 forms, the FAB stage of APGD+FAB+Square, APGD-L1+FAB, APGD-L1+FAB+Square and Cascade): the first from the clean point, every later one from a random point at distance min(best norm so far, epsilon) / 2, the best norm kept (default: 1); any other method refuses a value other than 1')
     parser.add_argument('--no-cuda', action='store_true', default=False, help='disables CUDA training')
     parser.add_argument('--max-epochs', type=int, default=None, help='stop after this many epochs (smoke runs)')
     parser.add_argument('--output-root', default=None, help='where checkpoint_<DS>/ is created (default: cwd, as the reference)')
@@ -226,6 +227,8 @@ def validate_cascade(val_loader, model, args, device, num_steps, n_class, log):
     model.eval()
     start = time.time()
     eot_iter, stages, tag = trainer.eot_iter_for(args), None, trainer.norm_tag(args)
+    if trainer.fab_restarts_for(args):
+        log(' * FAB-T: {0} restarts per target class, {1} iterations each'.format(int(args.fab_restarts), int(getattr(args, 'fab_iters', 100))))
     if args.attack_method == trainer.CASCADE_RAND_METHOD:
         if n_class < 3:
             raise ValueError("--attack_method Cascade-Rand runs APGD-DLR, which needs at least 3 classes, not %d" % n_class)
@@ -239,6 +242,12 @@ def validate_cascade(val_loader, model, args, device, num_steps, n_class, log):
     last = 100.0 * (res.robust_after[-1] if res.robust_after else res.clean_correct) / res.n
     a1, = ddp.gather_mean(last)
     return a1, a1
+
+
+def _restarts_tag(args):
+    """What the FAB line of a validation log carries after its numbers: nothing for one restart (the line stays as it was)."""
+    n = trainer.fab_restarts_for(args).get('n_restarts', 1)
+    return '' if n == 1 else ', {0} restarts'.format(n)
 
 
 def validate(val_loader, model, criterion, args, device, num_steps, step_size, log_dir, spec, local_result=False):
@@ -256,7 +265,9 @@ def validate(val_loader, model, criterion, args, device, num_steps, step_size, l
     if args.attack_method in trainer.FAB_U_METHODS + trainer.L1_FAB_U_METHODS:
         # untargeted FAB takes one backward pass per class and iteration: say so before the first batch
         _log(' * {0}: K = {1} classes, {1} backward passes per iteration, {2} iterations'.format(
-            args.attack_method, spec["num_classes"], int(getattr(args, 'fab_iters', 100))), log_dir)
+            args.attack_method, spec["num_classes"], int(getattr(args, 'fab_iters', 100))) + _restarts_tag(args), log_dir)
+    elif trainer.fab_restarts_for(args):
+        _log(' * {0}: FAB-T, {1} iterations per target class'.format(args.attack_method, int(getattr(args, 'fab_iters', 100))) + _restarts_tag(args), log_dir)
     end = time.time()
     for i, (input, target) in enumerate(val_loader):
         target, input = target.to(device), input.to(device)
@@ -291,6 +302,7 @@ def run(spec, build_model, argv=None):
     data_source(args.data, spec)  # an unusable --data fails here, before a model is built
     trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
     trainer.norm_for(args)  # and a --norm it has no L2 for
+    trainer.fab_restarts_for(args)  # and a --fab_restarts on a method that runs no FAB
     for key, default in (("type_canny", None), ("step_size_3", args.get("step_size_2")), ("num_steps_3", args.get("num_steps_2")),
                          ("n_queries", 1), ("cize", spec["shape"][-1]), ("beta", 1.0)):
         if key not in args:

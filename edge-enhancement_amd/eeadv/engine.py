@@ -21,7 +21,7 @@ import weakref
 
 import torch
 
-from . import ops, runtime, sqatk
+from . import fabstart, ops, runtime, sqatk
 from .functional import attack_forward, input_grad_only, refresh_dense_weights
 
 CE_SUM, CE_MEAN, KL, SOFTCE = "ce_sum", "ce_mean", "kl", "softce"
@@ -253,20 +253,23 @@ def _prepare(model, key, make_run, inputs, chunk):
     return gs
 
 
-def _drive(model, key, make_run, inputs, n_iter, chunk, use_graph):
+def _drive(model, key, make_run, inputs, n_iter, chunk, use_graph, n_restarts=1):
     """One attack of n_iter iterations on a run object (load(*inputs), start(model), body(model, n, last=False): n consecutive
     iterations, result()): eager - one body call, told that none follows - or n_iter // chunk replays of the graph cached under `key`.
-    load, start and result stay outside the graph ("The attack loops' driver")."""
+    load, start and result stay outside the graph ("The attack loops' driver").  n_restarts > 1 (FAB, section 23):
+    the same iterations once more behind run.restart(model, r) for r = 1 .. n_restarts - 1 - the same graph, whatever the count."""
     if not use_graph:
         run = make_run()
         run.load(*inputs)
-        run.start(model)
-        run.body(model, n_iter, last=True)
+        for r in range(n_restarts):
+            run.start(model) if r == 0 else run.restart(model, r)
+            run.body(model, n_iter, last=r + 1 == n_restarts)
         return run.result()
     gs = _prepare(model, key, make_run, inputs, chunk)
-    gs.run.start(model)
-    for _ in range(n_iter // gs.iters):
-        gs.graph.replay()
+    for r in range(n_restarts):
+        gs.run.start(model) if r == 0 else gs.run.restart(model, r)
+        for _ in range(n_iter // gs.iters):
+            gs.graph.replay()
     return gs.run.result()
 
 
@@ -848,10 +851,15 @@ def _square_args(model, x0, n_queries, seed, use_graph, trace):
     if use_graph and trace is not None:
         raise ValueError("the Square trace is recorded by eager runs only")
     if seed is None:
-        # the generator's seed is the same for every attack of a process, its offset is what the ticket advances: both go into the key
-        s, off = runtime.philox_ticket(x0.device, 4)
-        seed = (s + (off + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
+        seed = _drawn_seed(x0.device)
     return model, x0, n_queries, seed, use_graph
+
+
+def _drawn_seed(device):
+    """A key from torch's generator of the device, so torch.manual_seed governs it.  The generator's seed is the same for every attack of
+    a process, its offset is what the ticket advances: both go into the key."""
+    s, off = runtime.philox_ticket(device, 4)
+    return (s + (off + 1) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -921,6 +929,26 @@ def _fab_ops(norm):
     return ops.fab_proj_linf, ops.fab_step_, ops.fab_commit_
 
 
+def _fab_restarts(x0, n_restarts, seed, noise, target_index=0):
+    """(n_restarts, seeds, noise) as _FabRun.load takes them.  One restart - the default - draws nothing and takes no ticket: the calls
+    are the ones made before restarts existed.  Otherwise restart r = 1 .. n_restarts - 1 draws under fabstart.seed_of(seed, target_index,
+    r) (seed None: a ticket from torch's generator of the device, as square_loop takes it), or takes noise[r - 1] of the injected
+    `noise` [n_restarts - 1, B, ...]."""
+    n_restarts = int(n_restarts)
+    if n_restarts < 1:
+        raise ValueError("FAB needs n_restarts >= 1, got %d" % n_restarts)
+    if n_restarts == 1:
+        return 1, (), None
+    if noise is not None:
+        noise = noise.detach().to(device=x0.device, dtype=torch.float32).contiguous()
+        if tuple(noise.shape) != (n_restarts - 1,) + tuple(x0.shape):
+            raise ValueError("noise has shape %s, expected %s" % (tuple(noise.shape), (n_restarts - 1,) + tuple(x0.shape)))
+        return n_restarts, (0,) * (n_restarts - 1), noise
+    if seed is None:
+        seed = _drawn_seed(x0.device)
+    return n_restarts, tuple(fabstart.seed_of(seed, target_index, r) for r in range(1, n_restarts)), None
+
+
 class _FabSpec:
     """The loss-gradient step of `_body_input_grad` for a FAB run: df = z_t - z_y, its logit gradient and `pred` in one launch.  The kind is
     none of the CE kinds, so the route is the generic one (logits -> this -> autograd), through the whole model for edge-enhanced ones."""
@@ -957,10 +985,14 @@ class _FabRun:
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self.df = self.pred_at_x = None
         self.spec = _FabSpec(self)
+        self.n_restarts, self.seeds, self.noise = 1, (), None
 
-    def load(self, x0, y, targets, eps=None):
+    def load(self, x0, y, targets, eps=None, seeds=(), noise=None):
+        """seeds: the Philox keys of restarts 1 .. n_restarts - 1 (their count sets n_restarts); noise [n_restarts - 1, B, ...]: their draws,
+        injected in place of the kernel's own.  Neither is seen by the graph."""
         if eps is not None:
             self.eps = float(eps)
+        self.seeds, self.noise, self.n_restarts = tuple(seeds), noise, 1 + len(seeds)
         with torch.no_grad():
             self.x0.copy_(x0)
             self.y.copy_(y)
@@ -971,6 +1003,15 @@ class _FabRun:
             self.x.detach().copy_(self.x0)
             self.adv.copy_(self.x0)
             self.res.fill_(float("inf"))
+            self.flags.zero_()
+            self.counter.zero_()
+
+    def restart(self, model, r):
+        """Restart r >= 1: x <- the random point at distance min(res, eps) / 2 from x0, from the run's own res on the
+        device; flags and counter as in start.  adv and res stay: the commit launch keeps minimising across restarts."""
+        noise = None if self.noise is None else self.noise[r - 1]
+        with torch.no_grad():
+            ops.fab_start_(self.x.detach(), self.x0, self.res, self.eps, self.norm, self.seeds[r - 1], noise, self.path)
             self.flags.zero_()
             self.counter.zero_()
 
@@ -993,12 +1034,16 @@ class _FabRun:
             return _adv_where_fooled(robust, self.x0, self.adv), robust, self.res.clone()
 
 
-def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", norm="Linf"):
+def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", norm="Linf", n_restarts=1, seed=None, noise=None, target_index=0):
     """One FAB-T run of n_iter iterations from x0 towards the classes `targets` [B] in the threat model `norm` ('Linf' or 'L2': the metric of
     the projections, of alpha and of the result).  Returns (x_adv, robust, norm): norm [B] is the smallest ||adv - x0|| in that metric
     over the adversarial iterates (+inf if there was none), robust = not (norm <= eps), and x_adv is x0 with the
     non-robust rows replaced by that closest adversarial point.  The search itself is not confined to the eps-ball: FAB looks for the
-    minimum norm and eps only thresholds its result.  Deterministic - no random start, no draws of its own.  The model's mode is left as the
+    minimum norm and eps only thresholds its result.  With n_restarts = 1 (the default) deterministic - no random start, no draws of its
+    own.  n_restarts > 1: restart r >= 1 runs the same n_iter iterations from a random point at distance
+    min(norm so far, eps) / 2 from x0, drawn under fabstart.seed_of(seed, target_index, r) (seed None: a ticket from torch's generator) or
+    taken from noise[r - 1] (`noise` [n_restarts - 1, B, ...], injected); adv and norm are kept across restarts, so norm is the smallest
+    over all of them.  The graph does not know the count: one cached graph serves any number of restarts.  The model's mode is left as the
     caller set it.  Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of up to MAX_ITERS_PER_GRAPH iterations; both
     give the same bits.  `path` picks the projection kernel's path ('auto', 'resident', 'streaming'; the same bits)."""
     model = _unwrap(model)
@@ -1008,13 +1053,18 @@ def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", no
         raise ValueError("FAB needs n_iter >= 1")
     ops._sample_path(path, "FAB projection")
     _fab_ops(norm)
+    n_restarts = int(n_restarts)
+    if n_restarts < 1:
+        raise ValueError("FAB needs n_restarts >= 1, got %d" % n_restarts)
     if x0.shape[0] == 0:
         return _empty_result(x0, torch.float32)
     if use_graph is None:
         use_graph = graphs_enabled()
     chunk = _chunk(n_iter)
     key = ("fab", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk, norm)
-    return _drive(model, key, lambda: _FabRun(x0, y, n_iter, eps, path, norm), (x0, y, targets, eps), n_iter, chunk, use_graph)
+    n_restarts, seeds, noise = _fab_restarts(x0, n_restarts, seed, noise, target_index)
+    return _drive(model, key, lambda: _FabRun(x0, y, n_iter, eps, path, norm), (x0, y, targets, eps, seeds, noise), n_iter, chunk, use_graph,
+                  n_restarts)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -1033,26 +1083,32 @@ class _FabL1Run(_FabRun):
         super().__init__(x0, y, n_iter, eps, path, "L1")
 
 
-def fab_l1_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto"):
+def fab_l1_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", n_restarts=1, seed=None, noise=None, target_index=0):
     """fab_loop in the L1 threat model: one FAB-T run of n_iter iterations from x0 towards the classes `targets` [B], the projections
     the least-||.||_1 ones (ee_fab_proj_l1_f32: a fill by descending |w_i|, ties sharing one fraction), alpha from their L1 lengths.
     Returns (x_adv, robust, norm): norm [B] is the smallest ||adv - x0||_1 over the adversarial iterates (+inf if there was none),
     robust = not (norm <= eps) with eps the L1 radius, x_adv is x0 with the non-robust rows replaced by that closest point.  Eager, or -
     under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of its own (the key shares nothing with fab_loop's, so Linf, L2 and
-    L1 graphs of one shape coexist); both give the same bits, and so do the paths ('auto', 'resident', 'streaming')."""
+    L1 graphs of one shape coexist); both give the same bits, and so do the paths ('auto', 'resident', 'streaming').  n_restarts, seed,
+    noise and target_index as in fab_loop; the start of a restart lies at L1 distance min(norm so far, eps) / 2."""
     model = _unwrap(model)
     x0 = x0.detach().contiguous()
     n_iter = int(n_iter)
     if n_iter < 1:
         raise ValueError("FAB needs n_iter >= 1")
     ops._sample_path(path, "FAB projection")
+    n_restarts = int(n_restarts)
+    if n_restarts < 1:
+        raise ValueError("FAB needs n_restarts >= 1, got %d" % n_restarts)
     if x0.shape[0] == 0:
         return _empty_result(x0, torch.float32)
     if use_graph is None:
         use_graph = graphs_enabled()
     chunk = _chunk(n_iter)
     key = ("fab_l1", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk)
-    return _drive(model, key, lambda: _FabL1Run(x0, y, n_iter, eps, path), (x0, y, targets, eps), n_iter, chunk, use_graph)
+    n_restarts, seeds, noise = _fab_restarts(x0, n_restarts, seed, noise, target_index)
+    return _drive(model, key, lambda: _FabL1Run(x0, y, n_iter, eps, path), (x0, y, targets, eps, seeds, noise), n_iter, chunk, use_graph,
+                  n_restarts)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -1086,8 +1142,8 @@ class _FabURun(_FabRun):
         self.best = torch.full((B,), float("inf"), dtype=torch.float32, device=dev)
         self.best_k = torch.full((B,), -1, dtype=torch.int32, device=dev)
 
-    def load(self, x0, y, eps=None):
-        super().load(x0, y, y, eps)
+    def load(self, x0, y, eps=None, seeds=(), noise=None):
+        super().load(x0, y, y, eps, seeds, noise)
 
     def hyperplane(self, model):
         """(w, df) of the closest linearised boundary at self.x, in the run's buffers."""
@@ -1122,39 +1178,43 @@ class _FabUL1Run(_FabURun):
         super().__init__(x0, y, n_iter, eps, nclass, path, "L1")
 
 
-def _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, name, make_run, *key_tail):
+def _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, name, make_run, restarts, *key_tail):
     model = _unwrap(model)
     x0 = x0.detach().contiguous()
     n_iter = int(n_iter)
     if n_iter < 1:
         raise ValueError("FAB needs n_iter >= 1")
     ops._sample_path(path, "FAB projection")
+    if int(restarts[0]) < 1:
+        raise ValueError("FAB needs n_restarts >= 1, got %d" % int(restarts[0]))
     if x0.shape[0] == 0:
         return _empty_result(x0, torch.float32)
     if use_graph is None:
         use_graph = graphs_enabled()
     K = _n_classes(model, x0, nclass)
+    n_restarts, seeds, noise = _fab_restarts(x0, *restarts)
     # one iteration per graph: a replay's bubble is nothing against K backward passes, and MAX_ITERS_PER_GRAPH iterations of K passes each
     # would be a graph of thousands of nodes
     key = (name, id(model), model.training, tuple(x0.shape), path, x0.device.index, K) + key_tail
-    return _drive(model, key, lambda: make_run(model, x0, K), (x0, y, eps), n_iter, 1, use_graph)
+    return _drive(model, key, lambda: make_run(model, x0, K), (x0, y, eps, seeds, noise), n_iter, 1, use_graph, n_restarts)
 
 
-def fab_u_loop(model, x0, y, n_iter, eps, use_graph=None, path="auto", norm="Linf", nclass=None):
+def fab_u_loop(model, x0, y, n_iter, eps, use_graph=None, path="auto", norm="Linf", nclass=None, n_restarts=1, seed=None, noise=None):
     """One untargeted FAB run of n_iter iterations from x0 in the threat model `norm` ('Linf' or 'L2'): fab_loop's iteration, contract and
     result triple (x_adv, robust, norm), with the hyperplane of every iteration the closest one - in the dual norm - among the linearised
     boundaries z_k - z_y = 0 of all classes k != y (ties to the lower class; a class whose df or gradient norm is not finite, or whose
     gradient is zero, is skipped; a sample with every class skipped stays where it is).  An iteration costs one forward with autograd, K
-    backward passes off its retained graph and one more forward; K = nclass, or the width of one clean forward's logits.  Deterministic.
+    backward passes off its retained graph and one more forward; K = nclass, or the width of one clean forward's logits.  Deterministic
+    with n_restarts = 1; n_restarts, seed and noise as in fab_loop (the keys are fabstart.seed_of(seed, 0, r)).
     Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of ONE iteration under a key of its own ("fab_u"); both give
     the same bits.  On a model that redraws at every forward, all K hyperplanes of an iteration belong to the one draw of its forward."""
     _fab_ops(norm)
     return _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, "fab_u",
-                        lambda m, x, K: _FabURun(x, y, n_iter, eps, K, path, norm), norm)
+                        lambda m, x, K: _FabURun(x, y, n_iter, eps, K, path, norm), (n_restarts, seed, noise), norm)
 
 
-def fab_u_l1_loop(model, x0, y, n_iter, eps, use_graph=None, path="auto", nclass=None):
+def fab_u_l1_loop(model, x0, y, n_iter, eps, use_graph=None, path="auto", nclass=None, n_restarts=1, seed=None, noise=None):
     """fab_u_loop in the L1 threat model: the projections of fab_l1_loop, the distance to a hyperplane measured in max |g_i|, eps the L1
     radius.  A graph key of its own ("fab_u_l1")."""
     return _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, "fab_u_l1",
-                        lambda m, x, K: _FabUL1Run(x, y, n_iter, eps, K, path))
+                        lambda m, x, K: _FabUL1Run(x, y, n_iter, eps, K, path), (n_restarts, seed, noise))

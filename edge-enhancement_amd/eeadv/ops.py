@@ -728,6 +728,23 @@ def fab_select(g, logits, labels, k, metric, best, best_k, w, df, first=None):
     return best_k
 
 
+def fab_start_(x, x0, res, eps, metric, seed=0, noise=None, path="auto"):
+    """The random start of a FAB restart, written into x [B, ...]: x = clamp(x0 + ((m t) / n) / 2, 0, 1) with
+    m = min(res[b], eps), t the row of `noise` [B, ...] - or, with noise None, the draw of csrc/ee_fab.hip keyed by `seed` (eeadv.fabstart.draw
+    restates it) - and n its norm in `metric` ('Linf', 'L2', 'L1').  res [B] is read on the device; a row whose n is 0 or not finite is x0."""
+    B = x.shape[0]
+    if metric not in FAB_METRICS:
+        raise ValueError("FAB metric must be one of %s, got %r" % (sorted(FAB_METRICS), metric))
+    px = _chk(x, torch.float32, "x")
+    p0 = _chk(x0, torch.float32, "x0", x.shape)
+    if B and x.data_ptr() == x0.data_ptr():
+        raise ValueError("fab_start_ writes x while it reads x0: they must be two tensors")
+    N.check(N.lib.ee_fab_start_f32(px, p0, _chk(res, torch.float32, "res", (B,)), _opt(noise, torch.float32, "noise", x.shape), B,
+                                   x.numel() // B if B else 1, eps, FAB_METRICS[metric], int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                   _sample_path(path, "the FAB start's"), _stream()), "ee_fab_start_f32")
+    return x
+
+
 def _fab_proj(fn, name, x, x0, w, df, path, out, rows=3):
     B = x.shape[0]
     px = _chk(x, torch.float32, "x")

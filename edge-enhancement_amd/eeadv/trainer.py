@@ -679,6 +679,22 @@ def eot_iter_for(args):
     return 1
 
 
+def fab_restarts_for(args):
+    """{} or {'n_restarts': N}: what args.fab_restarts (--fab_restarts; None / absent: 1) adds to the FAB calls of args.attack_method
+    (DESIGN.md section 23).  One restart adds nothing - the calls stay the ones made before the option existed.  A method that runs no FAB
+    stops here on N != 1 instead of ignoring it, as eot_iter_for does."""
+    n = getattr(args, 'fab_restarts', None)
+    n = 1 if n is None else int(n)
+    if n < 1:
+        raise ValueError("--fab_restarts must be at least 1, got %d" % n)
+    if n == 1:
+        return {}
+    if args.attack_method not in FAB_RESTART_METHODS:
+        raise NotImplementedError("--fab_restarts %d with --attack_method %s: restarts are built for FAB only - %s - not for APGD, Square or the "
+                                  "reference's own attacks" % (n, args.attack_method, ", ".join(FAB_RESTART_METHODS)))
+    return {'n_restarts': n}
+
+
 L2_MESSAGE = ("the L2 threat model is built for APGD-CE, APGD-T, APGD, APGD-DLR, Rand and Cascade-Rand only - L2 Square and L2 FAB are different "
               "algorithms and are not built, so Square, APGD+Square, FAB-T, APGD+FAB+Square and Cascade have no L2, and the reference's own "
               "attacks (PGD, FGSM, CW) are Linf")
@@ -710,6 +726,7 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
     targeted = "tar" in args.method_name
     eot_iter = eot_iter_for(args)
     nkw = A._norm_kw(norm_for(args))  # empty for Linf: the calls below are then the ones made before --norm existed
+    rkw = fab_restarts_for(args)  # empty for one restart, likewise
     if args.attack_method == 'PGD':
         if targeted:
             return A.targeted_PGD(model, args, input, target, num_steps, step_size, n_class, device)[0]
@@ -754,17 +771,17 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             fab_iters = int(getattr(args, 'fab_iters', 100))
             return A._first_fooling(input.detach(), (A.APGD_L1(model, args, input, target, num_steps, 'ce'),
                                                      A.APGD_T_L1(model, args, input, target, num_steps, n_class),
-                                                     A.FAB_T_L1(model, args, input, target, n_class, fab_iters)[:2],
+                                                     A.FAB_T_L1(model, args, input, target, n_class, fab_iters, **rkw)[:2],
                                                      A.Square_L1(model, args, input, target, queries)[:2]))[0]
         if args.attack_method in L1_FAB_METHODS:
             # FAB-T in the L1 threat model, args.fab_iters iterations per target class, thresholded at args.epsilon:
             # alone, or after APGD-L1-CE and APGD-L1-T - the L1 ensemble minus Square, flags ANDed, the first fooling point kept
             fab_iters = int(getattr(args, 'fab_iters', 100))
             if args.attack_method == 'FAB-L1-T':
-                return A.FAB_T_L1(model, args, input, target, n_class, fab_iters)[0]
+                return A.FAB_T_L1(model, args, input, target, n_class, fab_iters, **rkw)[0]
             return A._first_fooling(input.detach(), (A.APGD_L1(model, args, input, target, num_steps, 'ce'),
                                                      A.APGD_T_L1(model, args, input, target, num_steps, n_class),
-                                                     A.FAB_T_L1(model, args, input, target, n_class, fab_iters)[:2]))[0]
+                                                     A.FAB_T_L1(model, args, input, target, n_class, fab_iters, **rkw)[:2]))[0]
         x_adv, robust = None, None
         if args.attack_method in ('APGD-L1-CE', 'APGD-L1'):
             x_adv, robust = A.APGD_L1(model, args, input, target, num_steps, 'ce')
@@ -781,8 +798,8 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
         fab_iters = int(getattr(args, 'fab_iters', 100))
         if args.attack_method in L1_FAB_U_METHODS:
-            return A.FAB_L1(model, args, input, target, fab_iters)[0]
-        return A.FAB(model, args, input, target, fab_iters)[0]
+            return A.FAB_L1(model, args, input, target, fab_iters, **rkw)[0]
+        return A.FAB(model, args, input, target, fab_iters, **rkw)[0]
     if args.attack_method in SQUARE_METHODS:
         # Square (black-box, args.square_queries forwards per sample at most), alone or after APGD-CE and APGD-T: flags ANDed, the first
         # fooling point kept
@@ -807,12 +824,12 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         shape = (-1,) + (1,) * (input.dim() - 1)
         fab_iters = int(getattr(args, 'fab_iters', 100))
         if args.attack_method == 'FAB-T':
-            return A.FAB_T(model, args, input, target, n_class, fab_iters)[0]
+            return A.FAB_T(model, args, input, target, n_class, fab_iters, **rkw)[0]
         x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce')
         xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class)
         x_adv = torch.where((robust & ~rt).view(shape), xt, x_adv)
         robust = robust & rt
-        xf, rf, _ = A.FAB_T(model, args, input, target, n_class, fab_iters)
+        xf, rf, _ = A.FAB_T(model, args, input, target, n_class, fab_iters, **rkw)
         x_adv = torch.where((robust & ~rf).view(shape), xf, x_adv)
         robust = robust & rf
         xs, rs, _ = A.Square(model, args, input, target, int(getattr(args, 'square_queries', 5000)))
@@ -850,6 +867,8 @@ L1_METHODS = ('APGD-L1-CE', 'APGD-L1-T', 'APGD-L1') + L1_FAB_METHODS + L1_SQUARE
 # untargeted FAB in tuples of their own: FAB_METHODS and L1_METHODS keep their members
 FAB_U_METHODS = ('FAB-U',)
 L1_FAB_U_METHODS = ('FAB-L1-U',)  # L1 by its name, like L1_METHODS: the ' [norm L1]' tag, --norm refused
+# what honours --fab_restarts: every method that runs a FAB
+FAB_RESTART_METHODS = ('FAB-T', 'FAB-U', 'FAB-L1-T', 'FAB-L1-U', 'APGD+FAB+Square', 'APGD-L1+FAB', 'APGD-L1+FAB+Square', CASCADE_METHOD)
 EVAL_METHODS = APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS + L1_METHODS + FAB_U_METHODS + L1_FAB_U_METHODS
 
 

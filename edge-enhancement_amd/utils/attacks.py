@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from eeadv import _native  # noqa: F401  (fails loudly at import when libeeadv.so is missing)
-from eeadv import engine, functional as EF, ops, runtime
+from eeadv import engine, fabstart, functional as EF, ops, runtime
 
 _INF = float("inf")
 
@@ -818,7 +818,8 @@ def Square_L1(model, args, inputs, targets, n_queries=5000, seed=None):
 # decision boundaries instead of ascending a loss.  Built from the published algorithm with the constants `standard`
 # runs it with (eta = 1.05, beta = 0.9, alpha_max = 0.1, 9 target classes, one run from the clean point: deterministic).  norm="L2" is
 # the same iteration in the other metric; L1 comes through FAB_T_L1 below (section 20), untargeted FAB through
-# FAB / FAB_L1 (section 22).  Restarts with the random start, the final line search and EOT for FAB are NOT here.
+# FAB / FAB_L1 (section 22), restarts with the random start through n_restarts (section 23).  The final line search and EOT for FAB are
+# NOT here.
 # ---------------------------------------------------------------------------------------------------------
 _FAB_ETA, _FAB_BETA, _FAB_ALPHA_MAX = 1.05, 0.9, 0.1
 
@@ -958,21 +959,30 @@ def _fab_iteration(model, x, x0, y, t, adv, res, project, delta, dist, dual=None
     return x_new, adv, res, info
 
 
-def _fab_host(model, x0, y, t, n_iter, trace=None, norm="Linf"):
+def _fab_host(model, x0, y, t, n_iter, trace=None, norm="Linf", n_restarts=1, seed=None, noise=None, eps=None, target_index=0):
     """Plumbing path for CPU tensors (opt-in), the counterpart of _host_loop: the iteration of engine.fab_loop in plain torch ops, in the
-    input's dtype.  Returns (adv, res).  `trace`, a list, receives one dict of clones per iteration."""
+    input's dtype.  Returns (adv, res).  `trace`, a list, receives one dict of clones per iteration.  n_restarts, seed, noise, eps and
+    target_index: the restarts of _fab_u_run."""
     _check_fab_norm(norm)
-    x, adv = x0.clone(), x0.clone()
-    res = torch.full((x0.shape[0],), _INF, dtype=x0.dtype, device=x0.device)
-    for _ in range(int(n_iter)):
-        x, adv, res, info = _fab_host_iteration(model, x, x0, y, t, adv, res, norm)
-        if trace is not None:
-            info.update(x=x, adv=adv, res=res)
-            trace.append({k: v.clone() for k, v in info.items()})
-    return adv, res
+    return _fab_u_run(lambda x, adv, res: _fab_host_iteration(model, x, x0, y, t, adv, res, norm), x0, n_iter, trace, norm, n_restarts, seed,
+                      noise, eps, target_index)
 
 
-def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, order=None, norm="Linf"):
+def _fab_restart_kw(x0, n_restarts, seed):
+    """What the FAB doors add to their engine / host calls: nothing for one restart (the calls stay the ones they always were), else
+    n_restarts and the seed - the caller's, or one drawn here, once for all target classes (on the device a ticket from torch's generator,
+    as Square takes it)."""
+    n_restarts = int(n_restarts)
+    if n_restarts < 1:
+        raise ValueError("FAB needs n_restarts >= 1, got %d" % n_restarts)
+    if n_restarts == 1:
+        return {}
+    if seed is None:
+        seed = engine._drawn_seed(x0.device) if x0.is_cuda else int(torch.randint(0, 2 ** 62, (1,)).item())
+    return dict(n_restarts=n_restarts, seed=int(seed))
+
+
+def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, order=None, norm="Linf", n_restarts=1, seed=None):
     """Targeted FAB (norm: 'Linf', or 'L2' - every ||.||_inf below is then ||.||_2 and args.epsilon the L2 radius): one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most nclass - 1 of
     them, taken as APGD_T takes them), each on the whole batch from the clean point.  Returns (x_adv, robust, norm): norm [B] is the smallest
     ||adv - x0||_inf over all runs (+inf if no run found an adversarial point, 0 for a sample the clean forward already misclassifies),
@@ -980,18 +990,28 @@ def FAB_T(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, 
     (the first one, among equals).  eps only thresholds the result - the search is not confined to the ball.  Deterministic.  The model runs in
     the mode the caller left it in.  On the device c2 = df + sum w_i (x0_i - x_i) is summed in double (csrc/ee_fab.hip); the host path
     below forms the same sum of differences in the input's dtype - the public code's <w, x0> - (<w, x> - df) cancels in fp32.  `order`
-    [B, n_t + 1]: the class order of the clean logits if the caller has it already - the clean forward is then skipped."""
+    [B, n_t + 1]: the class order of the clean logits if the caller has it already - the clean forward is then skipped.  n_restarts > 1
+    (DESIGN.md section 23): every target class runs its restarts, restart r >= 1 of the j-th class from the random start keyed by
+    eeadv.fabstart.seed_of(seed, j, r), on the whole batch, the best norm kept across them; seed None draws one."""
     x0 = inputs.detach()
     eps = float(args.epsilon)
     kw = {} if _check_fab_norm(norm) == "Linf" else {"norm": norm}  # the Linf call is the call it always was
+    rkw = _fab_restart_kw(x0, n_restarts, seed)
     return _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, "FAB_T",
-                        lambda t: engine.fab_loop(model, x0, targets, t, n_iter, eps, **kw)[::2],
-                        lambda t: _fab_host(model, x0, targets, t, n_iter, **kw))
+                        lambda t, j: engine.fab_loop(model, x0, targets, t, n_iter, eps, **kw, **_of_class(rkw, j))[::2],
+                        lambda t, j: _fab_host(model, x0, targets, t, n_iter, **kw, **_of_class(rkw, j, eps)))
+
+
+def _of_class(rkw, j, eps=None):
+    """The restart arguments of the run towards the j-th target class: its index keys the draws; the host paths also take eps."""
+    if not rkw:
+        return {}
+    return dict(rkw, target_index=j) if eps is None else dict(rkw, target_index=j, eps=eps)
 
 
 def _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, what, device_run, host_run):
-    """The runs of FAB_T / FAB_T_L1 over the target classes and their combination; device_run(t) / host_run(t) -> (adv, norm) of one run
-    towards the classes t [B]."""
+    """The runs of FAB_T / FAB_T_L1 over the target classes and their combination; device_run(t, j) / host_run(t, j) -> (adv, norm) of the
+    run towards the classes t [B], the j-th of the order."""
     n_t = min(int(n_target_classes), int(nclass) - 1)
     on_dev = runtime.require_device(x0, what)
     order = _class_order(model, x0, n_t, what, order)
@@ -1001,7 +1021,7 @@ def _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, what,
     norm = torch.where(order[:, 0] != targets, torch.zeros_like(inf), inf)
     for j in range(1, n_t + 1):
         t = order[:, j].contiguous()
-        xa, nj = device_run(t) if on_dev else host_run(t)
+        xa, nj = device_run(t, j) if on_dev else host_run(t, j)
         closer = (nj < norm) & (nj <= eps)
         x_adv = torch.where(closer.view(shape), xa, x_adv)
         norm = torch.minimum(norm, nj)
@@ -1011,7 +1031,7 @@ def _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, what,
 # ---------------------------------------------------------------------------------------------------------
 # FAB-T in the L1 threat model: doors of their own - FAB_T(norm="L1") and _fab_host(norm="L1") stay refused.  The
 # iteration is FAB-T's; the projection is the least-||.||_1 one, a fill by descending |w_i| in which every coordinate tied at the
-# threshold takes the same fraction of its room.  Restarts, the final line search and L1 inside Cascade are NOT here.
+# threshold takes the same fraction of its room.  The final line search and L1 inside Cascade are NOT here.
 # ---------------------------------------------------------------------------------------------------------
 def _l1_norms(v):
     """sum_i |v_i| per row, summed in float64 and rounded to v's dtype once (as the commit kernel does)."""
@@ -1067,37 +1087,33 @@ def _fab_l1_host_iteration(model, x, x0, y, t, adv, res):
     return _fab_iteration(model, x, x0, y, t, adv, res, _fab_projection_l1, _fab_delta_l1, _l1_norms)
 
 
-def _fab_l1_host(model, x0, y, t, n_iter, trace=None):
+def _fab_l1_host(model, x0, y, t, n_iter, trace=None, n_restarts=1, seed=None, noise=None, eps=None, target_index=0):
     """_fab_host in the L1 threat model: the iteration of engine.fab_l1_loop in plain torch ops, in the input's dtype.  Returns (adv, res)."""
-    x, adv = x0.clone(), x0.clone()
-    res = torch.full((x0.shape[0],), _INF, dtype=x0.dtype, device=x0.device)
-    for _ in range(int(n_iter)):
-        x, adv, res, info = _fab_l1_host_iteration(model, x, x0, y, t, adv, res)
-        if trace is not None:
-            info.update(x=x, adv=adv, res=res)
-            trace.append({k: v.clone() for k, v in info.items()})
-    return adv, res
+    return _fab_u_run(lambda x, adv, res: _fab_l1_host_iteration(model, x, x0, y, t, adv, res), x0, n_iter, trace, "L1", n_restarts, seed,
+                      noise, eps, target_index)
 
 
-def FAB_T_L1(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, order=None):
+def FAB_T_L1(model, args, inputs, targets, nclass, n_iter=100, n_target_classes=9, order=None, n_restarts=1, seed=None):
     """FAB_T in the L1 threat model (args.epsilon is the L1 radius): one run per target class as FAB_T takes them, each on the whole batch
     from the clean point.  Returns (x_adv, robust, norm): norm [B] is the smallest ||adv - x0||_1 over all runs (+inf if none found an
     adversarial point, 0 for a sample the clean forward already misclassifies), robust = not (norm <= args.epsilon), and x_adv is the
     inputs with every non-robust sample replaced by the point that attains its norm.  Deterministic.  Two departures from the public
     projection_l1: coordinates of equal |w_i| at the threshold all take the same fraction of their room (the public
-    code fills them in the order its argsort returns - the L1 length is the same), and a coordinate takes part exactly when w_i != 0."""
+    code fills them in the order its argsort returns - the L1 length is the same), and a coordinate takes part exactly when w_i != 0.
+    n_restarts and seed as in FAB_T."""
     x0 = inputs.detach()
     eps = float(args.epsilon)
+    rkw = _fab_restart_kw(x0, n_restarts, seed)
     return _fab_targets(model, x0, targets, nclass, n_target_classes, order, eps, "FAB_T_L1",
-                        lambda t: engine.fab_l1_loop(model, x0, targets, t, n_iter, eps)[::2],
-                        lambda t: _fab_l1_host(model, x0, targets, t, n_iter))
+                        lambda t, j: engine.fab_l1_loop(model, x0, targets, t, n_iter, eps, **_of_class(rkw, j))[::2],
+                        lambda t, j: _fab_l1_host(model, x0, targets, t, n_iter, **_of_class(rkw, j, eps)))
 
 
 # ---------------------------------------------------------------------------------------------------------
 # Untargeted FAB (DESIGN.md section 22; the `fab` of the public ensemble's `plus` version and of a `custom` ['apgd-ce', 'fab'] run): the
 # iteration of FAB-T, its hyperplane the closest one - in the dual norm - among the linearised boundaries z_k - z_y = 0 of ALL classes
-# k != y: K backward passes per iteration.  One run from the clean point, deterministic; restarts with the random start, the final search
-# and EOT are NOT here.
+# k != y: K backward passes per iteration.  One run from the clean point, deterministic, unless n_restarts asks for more (section 23); the
+# final search and EOT are NOT here.
 # ---------------------------------------------------------------------------------------------------------
 def _dual_of_linf(g):
     """sum_i |g_i| per row, summed in float64 and rounded to g's dtype once (as ee_fab_select_f32 does)."""
@@ -1147,27 +1163,50 @@ def _fab_u_l1_host_iteration(model, x, x0, y, adv, res):
     return _fab_iteration(model, x, x0, y, None, adv, res, *_FAB_U_L1_METRIC)
 
 
-def _fab_u_run(iteration, x0, n_iter, trace):
+def _fab_u_run(iteration, x0, n_iter, trace, metric="Linf", n_restarts=1, seed=None, noise=None, eps=None, target_index=0):
+    """The chain of every FAB host path (targeted ones included): restart 0 from the clean point with res = +inf, then - DESIGN.md section
+    23 - restart r = 1 .. n_restarts - 1 from eeadv.fabstart.start(x0, res, eps, t, metric), t being noise[r - 1] of the injected `noise`
+    [n_restarts - 1, B, ...] or the host restatement of the kernel's draw under fabstart.seed_of(seed, target_index, r); adv and res are
+    carried across restarts.  `trace` receives, before the iterations of a restart r >= 1, one entry {"restart", "x_start", "res_in"}."""
+    n_restarts = int(n_restarts)
+    if n_restarts < 1:
+        raise ValueError("FAB needs n_restarts >= 1, got %d" % n_restarts)
+    if n_restarts > 1 and eps is None:
+        raise ValueError("a FAB restart starts at distance min(norm so far, eps) / 2: eps is needed")
+    if n_restarts > 1 and noise is None and seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    B = x0.shape[0]
     x, adv = x0.clone(), x0.clone()
-    res = torch.full((x0.shape[0],), _INF, dtype=x0.dtype, device=x0.device)
-    for _ in range(int(n_iter)):
-        x, adv, res, info = iteration(x, adv, res)
-        if trace is not None:
-            info.update(x=x, adv=adv, res=res)
-            trace.append({k: v.clone() for k, v in info.items()})
+    res = torch.full((B,), _INF, dtype=x0.dtype, device=x0.device)
+    for r in range(n_restarts):
+        if r:
+            if noise is not None:
+                t = noise[r - 1]
+            else:
+                t = torch.from_numpy(fabstart.draw(fabstart.seed_of(seed, target_index, r), B, x0[0].numel() if B else 0, metric))
+            x = fabstart.start(x0, res, eps, t.to(device=x0.device).reshape(x0.shape), metric)
+            if trace is not None:
+                trace.append(dict(restart=torch.tensor(r), x_start=x.clone(), res_in=res.clone()))
+        for _ in range(int(n_iter)):
+            x, adv, res, info = iteration(x, adv, res)
+            if trace is not None:
+                info.update(x=x, adv=adv, res=res)
+                trace.append({k: v.clone() for k, v in info.items()})
     return adv, res
 
 
-def _fab_u_host(model, x0, y, n_iter, trace=None, norm="Linf"):
+def _fab_u_host(model, x0, y, n_iter, trace=None, norm="Linf", n_restarts=1, seed=None, noise=None, eps=None):
     """Plumbing path for CPU tensors (opt-in): the iteration of engine.fab_u_loop in plain torch ops, in the input's dtype, the Jacobian
     taken row by row off one retained forward.  Returns (adv, res).  `trace`, a list, receives one dict of clones per iteration."""
     _check_fab_norm(norm)
-    return _fab_u_run(lambda x, adv, res: _fab_u_host_iteration(model, x, x0, y, adv, res, norm), x0, n_iter, trace)
+    return _fab_u_run(lambda x, adv, res: _fab_u_host_iteration(model, x, x0, y, adv, res, norm), x0, n_iter, trace, norm, n_restarts, seed,
+                      noise, eps)
 
 
-def _fab_u_l1_host(model, x0, y, n_iter, trace=None):
+def _fab_u_l1_host(model, x0, y, n_iter, trace=None, n_restarts=1, seed=None, noise=None, eps=None):
     """_fab_u_host in the L1 threat model."""
-    return _fab_u_run(lambda x, adv, res: _fab_u_l1_host_iteration(model, x, x0, y, adv, res), x0, n_iter, trace)
+    return _fab_u_run(lambda x, adv, res: _fab_u_l1_host_iteration(model, x, x0, y, adv, res), x0, n_iter, trace, "L1", n_restarts, seed,
+                      noise, eps)
 
 
 def _fab_untargeted(model, x0, targets, eps, what, device_run, host_run):
@@ -1188,30 +1227,33 @@ def _fab_untargeted(model, x0, targets, eps, what, device_run, host_run):
     return x_adv, ~(norm <= eps), norm
 
 
-def FAB(model, args, inputs, targets, n_iter=100, eps=None, norm="Linf"):
+def FAB(model, args, inputs, targets, n_iter=100, eps=None, norm="Linf", n_restarts=1, seed=None):
     """Untargeted FAB (norm: 'Linf' or 'L2'; eps, default args.epsilon, is the radius in that metric): one run of n_iter iterations on the
     whole batch from the clean point, every iteration walking towards the closest linearised decision boundary among all classes k != y -
     K backward passes per iteration, K the width of the clean logits.  Returns what FAB_T returns: (x_adv, robust, norm), norm [B] the
     smallest ||adv - x0|| over the adversarial iterates (+inf if there was none, 0 for a sample the clean forward already misclassifies),
     robust = not (norm <= eps), x_adv the inputs with every non-robust sample replaced by the point that attains its norm.  eps only
     thresholds the result.  Deterministic.  The model runs in the mode the caller left it in; on a model that redraws at every forward one
-    iteration linearises one draw (no EOT)."""
+    iteration linearises one draw (no EOT).  n_restarts > 1: restart r >= 1 runs the same iterations from the
+    random start keyed by eeadv.fabstart.seed_of(seed, 0, r), on the whole batch, the best norm kept across them; seed None draws one."""
     x0 = inputs.detach()
     eps = float(args.epsilon if eps is None else eps)
     kw = {} if _check_fab_norm(norm) == "Linf" else {"norm": norm}
+    rkw = _fab_restart_kw(x0, n_restarts, seed)
     return _fab_untargeted(model, x0, targets, eps, "FAB",
-                           lambda K: engine.fab_u_loop(model, x0, targets, n_iter, eps, nclass=K, **kw)[::2],
-                           lambda: _fab_u_host(model, x0, targets, n_iter, **kw))
+                           lambda K: engine.fab_u_loop(model, x0, targets, n_iter, eps, nclass=K, **kw, **rkw)[::2],
+                           lambda: _fab_u_host(model, x0, targets, n_iter, **kw, **(dict(rkw, eps=eps) if rkw else {})))
 
 
-def FAB_L1(model, args, inputs, targets, n_iter=100, eps=None):
+def FAB_L1(model, args, inputs, targets, n_iter=100, eps=None, n_restarts=1, seed=None):
     """FAB in the L1 threat model (eps, default args.epsilon, is the L1 radius): the projections of FAB_T_L1, the distance to a hyperplane
-    measured in max_i |g_i|.  Returns what FAB_T_L1 returns."""
+    measured in max_i |g_i|.  Returns what FAB_T_L1 returns.  n_restarts and seed as in FAB."""
     x0 = inputs.detach()
     eps = float(args.epsilon if eps is None else eps)
+    rkw = _fab_restart_kw(x0, n_restarts, seed)
     return _fab_untargeted(model, x0, targets, eps, "FAB_L1",
-                           lambda K: engine.fab_u_l1_loop(model, x0, targets, n_iter, eps, nclass=K)[::2],
-                           lambda: _fab_u_l1_host(model, x0, targets, n_iter))
+                           lambda K: engine.fab_u_l1_loop(model, x0, targets, n_iter, eps, nclass=K, **rkw)[::2],
+                           lambda: _fab_u_l1_host(model, x0, targets, n_iter, **(dict(rkw, eps=eps) if rkw else {})))
 
 
 class LabelSmoothLoss(torch.nn.Module):

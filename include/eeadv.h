@@ -32,7 +32,7 @@ extern "C" {
 #define EE_ERR_UNSUPPORTED (-3) /* valid request this build has no kernel for (e.g. C > 4) */
 #define EE_ERR_ALIGN (-4)       /* pointer not aligned to the element size */
 
-/* `path` of the launches that give a sample (or a projection problem) one workgroup of 512 threads: ee_fab_proj_*, ee_apgd_step_l2_f32,
+/* `path` of the launches that give a sample (or a projection problem) one workgroup of 512 threads: ee_fab_proj_*, ee_fab_start_f32, ee_apgd_step_l2_f32,
  * ee_l1_proj_f32, ee_apgd_step_l1_f32, ee_sqatk_*_l2_f32, ee_sqatk_*_l1_f32.  The two paths return the same bits; a value outside the three: EE_ERR_SHAPE.
  * EE_FAB_PATH_*, EE_APGD_L2_PATH_*, EE_APGD_L1_PATH_* and EE_SQATK_L2_PATH_* below are these. */
 #define EE_PATH_AUTO 0      /* resident when a sample has at most 12288 elements, else streaming */
@@ -602,6 +602,21 @@ int ee_fab_commit_l1_f32(const float *logits, const int64_t *labels, int B, int 
 int ee_fab_select_f32(const float *g, const float *logits, const int64_t *labels, int k, int metric, int first, int64_t B, int K,
                       int64_t per_sample, float *best, int *best_k, float *w, float *df, void *stream);
 
+/* ---- FAB restarts: the random start of restart r >= 1, one workgroup of 512 threads per sample.  For sample b with
+ * the clean row x0[b], the best norm so far res[b] and a draw t of per_sample elements:
+ *     m = min(res[b], eps) in float (res = +inf: eps);   n = max_i |t_i| (EE_FAB_METRIC_LINF), (float) sqrt(sum_i t_i^2) (_L2) or
+ *     (float) sum_i |t_i| (_L1) - the sums in double in the order of ee_fab_select_f32, rounded to float once;
+ *     x_i = clamp(x0_i + ((m * t_i) / n) * 0.5f, 0, 1), every operation one f32 rounding, in this order.
+ * n == 0 or not finite: the row is written as x0.  noise [B, per_sample] not NULL: t = noise.  noise NULL: t is drawn from Philox4x32-10
+ * keyed by `seed` on stream 15, one call per group of four elements under the counter (b << 32) | (element >> 2) - row b's draw depends
+ * on (seed, b, element) alone - t = 2 u - 1 with u the 24-bit uniform (Linf), or the two Box-Muller pairs of ee_pgd_init_rng_f32 with scale 1
+ * (L2, L1).  Reads res, writes x (x must not alias x0); `path` as for the projections (EE_PATH_*; the resident path keeps the draw in
+ * registers between the norm pass and the write pass, the streaming one reads or draws it again), 128-bit accesses when per_sample % 4 == 0
+ * and x, x0, noise are 16-byte aligned: the same bits from all four.  per_sample >= 1; eps < 0 or NaN, a metric or path outside its three
+ * values: EE_ERR_SHAPE; B == 0 launches nothing.  Records under EE_K_FAB_STEP. */
+int ee_fab_start_f32(float *x, const float *x0, const float *res, const float *noise, int64_t B, int64_t per_sample, float eps, int metric,
+                     uint64_t seed, int path, void *stream);
+
 /* CannyFilter_BPDA (utils/core.py:386-505; AWP configs): no alpha mask, NMS by multiplication, thresholds through
  * To_compare (core.py:329-358), hysteresis through To_eq (core.py:361-382).  thresholds given, hysteresis=True.
  *   forward: edge, thin (the thinned magnitude), t2 (the {0, .5, 1} threshold map) [B,1,H,W]; thin / t2 feed the backward.
@@ -1121,7 +1136,7 @@ int ee_cascade_resolve_f32(const uint8_t *robust, const int64_t *id, const float
 #define EE_K_SQATK_STEP 25   /* ee_sqatk_step_f32 */
 #define EE_K_FAB_DIFF 26     /* ee_fab_diff_f32, ee_fab_select_f32 */
 #define EE_K_FAB_PROJ 27     /* ee_fab_proj_linf_f32, ee_fab_proj_l2_f32, ee_fab_proj_l1_f32 */
-#define EE_K_FAB_STEP 28     /* ee_fab_step_f32, ee_fab_step_l2_f32, ee_fab_step_l1_f32 */
+#define EE_K_FAB_STEP 28     /* ee_fab_step_f32, ee_fab_step_l2_f32, ee_fab_step_l1_f32, ee_fab_start_f32 */
 #define EE_K_FAB_COMMIT 29   /* ee_fab_commit_f32, ee_fab_commit_l2_f32, ee_fab_commit_l1_f32 */
 #define EE_K_COUNT 30
 int ee_prof_enable(int on);

@@ -13,7 +13,11 @@ untrained: labels are their own clean predictions.
 run, the three attacks alternating.  --norm L1 times the L1 iteration (engine.fab_l1_loop, eps = 12) and the L1 projection launch beside
 the Linf and the L2 ones, in the same run, the four attacks alternating.
 
-    python scripts/fab_probe.py [reps] [--norm Linf|L2|L1]   -> a few text lines, then one JSON line per model
+--restarts adds, on `resnet18`, a FAB-T run of 2 restarts beside the others - its time per iteration is
+(t100 - t20) / 160, the same graph replayed twice as often - and the start launch of a restart alone (100 rows of 12288 elements, the
+kernel's own uniform draw, res = +inf), per launch, on both paths.
+
+    python scripts/fab_probe.py [reps] [--norm Linf|L2|L1] [--restarts]   -> a few text lines, then one JSON line per model
 """
 import json
 import os
@@ -40,6 +44,9 @@ def main():
             raise SystemExit("fab_probe: --norm takes one of %s" % (list(engine.FAB_NORMS) + ["L1"],))
         norm = argv[k + 1]
         del argv[k:k + 2]
+    restarts = "--restarts" in argv
+    if restarts:
+        argv.remove("--restarts")
     l1 = norm == "L1"
     l2 = norm == "L2" or l1  # the L1 run is measured beside both
     reps = int(argv[0]) if argv else 7
@@ -60,7 +67,7 @@ def main():
     def median(v):
         return sorted(v)[len(v) // 2]
 
-    for name in ("resnet18", "resnet18_EE_square"):
+    for name in ("resnet18",) if restarts else ("resnet18", "resnet18_EE_square"):
         torch.manual_seed(0)
         if name == "resnet18":
             m = M.make_resnet(18, "tiny")
@@ -78,6 +85,9 @@ def main():
             runs["fab_t_l2"] = lambda k: engine.fab_loop(m, x, y, t, k, 0.5, norm="L2")
         if l1:
             runs["fab_t_l1"] = lambda k: engine.fab_l1_loop(m, x, y, t, k, 12.0)
+        r2 = restarts and name == "resnet18"
+        if r2:
+            runs["fab_t_r2"] = lambda k: engine.fab_loop(m, x, y, t, k, eps, n_restarts=2, seed=1)
         for fn in runs.values():  # captures and warm-up of both lengths
             for k in (100, 20, 100, 20):
                 fn(k)
@@ -91,7 +101,7 @@ def main():
         for n in runs:
             t100, t20 = median(ms[(n, 100)]), median(ms[(n, 20)])
             out[n + "_ms_100"], out[n + "_ms_20"] = round(t100, 3), round(t20, 3)
-            out[n + "_iter_ms"] = round((t100 - t20) / 80, 4)
+            out[n + "_iter_ms"] = round((t100 - t20) / (160 if n == "fab_t_r2" else 80), 4)
         # the eval forward, replayed from a graph of 16
         xs = x.clone()
 
@@ -167,6 +177,20 @@ def main():
             print("%s: L1 FAB-T %.4f ms/iter (x%.3f of the Linf iteration, %+.1f us; x%.3f of the L2 one); L1 projection launch %.1f us resident, "
                   "%.1f us streaming" % (name, out["fab_t_l1_iter_ms"], out["fab_l1_over_linf"], out["fab_l1_minus_linf_us_per_iter"],
                                          out["fab_l1_over_l2"], out["proj_l1_resident_us"], out["proj_l1_streaming_us"]), flush=True)
+        if r2:
+            xs_, res_ = torch.empty_like(x), torch.full((100,), float("inf"), device=dev)
+            for path in ("resident", "streaming"):
+                launch = lambda: [ops.fab_start_(xs_, x, res_, eps, "Linf", seed=1, path=path) for _ in range(50)]
+                launch()
+                torch.cuda.synchronize()
+                out["start_%s_us" % path] = round(1e3 * median([timed(launch) for _ in range(reps)]) / 50, 2)
+            out["fab_r2_over_r1_iter"] = round(out["fab_t_r2_iter_ms"] / out["fab_t_iter_ms"], 4)
+            out["fab_r2_once_ms"] = round(out["fab_t_r2_ms_100"] - 200 * out["fab_t_r2_iter_ms"], 3)  # what a 2-restart run pays once
+            out["fab_r1_once_ms"] = round(out["fab_t_ms_100"] - 100 * out["fab_t_iter_ms"], 3)
+            print("%s: FAB-T with 2 restarts %.4f ms/iter (x%.3f of one run's %.4f); start launch %.1f us resident, %.1f us streaming; "
+                  "paid once per call: %.3f ms with 2 restarts, %.3f ms with one"
+                  % (name, out["fab_t_r2_iter_ms"], out["fab_r2_over_r1_iter"], out["fab_t_iter_ms"], out["start_resident_us"],
+                     out["start_streaming_us"], out["fab_r2_once_ms"], out["fab_r1_once_ms"]), flush=True)
         print(json.dumps(out), flush=True)
 
 
