@@ -136,6 +136,7 @@ def main(argv=None):
     driver.data_source(args.data, SPEC)  # an unusable --data fails here, before a model is built
     trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
     trainer.fab_restarts_for(args)  # and a --fab_restarts on a method that runs no FAB
+    trainer.apgd_restarts_for(args)  # and an --apgd_restarts on a method that runs no APGD
     trainer.norm_for(args)  # and a --norm it has no L2 for
     args.setdefault("cize", 64)
     args.num_classes = SPEC["num_classes"]

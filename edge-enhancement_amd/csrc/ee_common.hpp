@@ -129,6 +129,7 @@ __device__ __forceinline__ void normal4(const uint4 &r, float (&z)[4]) {
     z[3] = r1 * sinf(6.28318530717958647692f * u3);
 }
 // Philox stream ids: 0 (the default), 7 (ee_net2.hip) and 11 - 14 (ee_sqatk.hpp) are taken
-constexpr uint32_t kStreamFabStart = 15u;  // the random start of a FAB restart (ee_fab.hip)
+constexpr uint32_t kStreamFabStart = 15u;   // the random start of a FAB restart (ee_fab.hip)
+constexpr uint32_t kStreamApgdStart = 16u;  // the random start of an APGD restart (ee_apgd_start.hip)
 
 }  // namespace ee

@@ -710,33 +710,10 @@ __global__ __launch_bounds__(kSampleBlock) void select_kernel(const float *__res
 // ---- the random start of a restart ---------------------------------------------------------------------------------
 // x = clamp(x0 + ((m t) / n) / 2, 0, 1) with m = min(res[b], eps), t a draw of D elements and n its norm in the threat model's own metric
 // (M = kLinf: max |t_i|, kL2: sqrt(sum t_i^2), kL1: sum |t_i|; the sums in double in the one order of ee_sample.hpp, rounded to float once).
-// DRAW: t comes from Philox, one call per group of four elements under the counter (b << 32) | (e >> 2) - a row's draw depends on (seed, b,
+// DRAW (start_draw4 of ee_sample.hpp, under kStreamFabStart): t comes from Philox, one call per group of four elements under the counter (b << 32) | (e >> 2) - a row's draw depends on (seed, b,
 // element) alone - uniform on [-1, 1) for Linf, standard normal otherwise; else t is the row of `noise`.  RES keeps t in registers between
 // the norm pass and the write pass, the streaming path reads or draws it again.  A row whose n is 0 or not finite is written as x0.  The
 // launch reads res and writes x: no scalar crosses workgroups.
-template <int M, bool DRAW, bool VEC>
-__device__ __forceinline__ void start_fetch(const Philox &ph, const float *noise_row, int b, int64_t e, int64_t D, float (&t)[4]) {
-    if (!DRAW) {
-        load4<VEC>(noise_row, e, D, t);
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) t[j] = 0.0f;
-    if (e >= D) return;  // a group past the row: nothing to draw (e is fixed by the thread and the group, not by data)
-    const uint4 r = ph((static_cast<uint64_t>(static_cast<uint32_t>(b)) << 32) | static_cast<uint64_t>(e >> 2), kStreamFabStart);
-    if (M == kLinf) {
-        t[0] = 2.0f * u01(r.x) - 1.0f;  // exact: u01 is a multiple of 2^-24 in [0, 1)
-        t[1] = 2.0f * u01(r.y) - 1.0f;
-        t[2] = 2.0f * u01(r.z) - 1.0f;
-        t[3] = 2.0f * u01(r.w) - 1.0f;
-    } else {
-        normal4(r, t);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (e + j >= D) t[j] = 0.0f;  // elements at or past D read as 0, as load4's do
-}
-
 template <bool RES, bool VEC, int M, bool DRAW>
 __global__ __launch_bounds__(kSampleBlock) void start_kernel(float *__restrict__ x, const float *__restrict__ x0, const float *__restrict__ res,
                                                            const float *__restrict__ noise, int64_t D, float eps, uint64_t seed) {
@@ -754,7 +731,7 @@ __global__ __launch_bounds__(kSampleBlock) void start_kernel(float *__restrict__
     double acc = 0.0;
     auto first = [&](int g) {
         float t[4];
-        start_fetch<M, DRAW, VEC>(ph, nr, b, group_element(g), D, t);
+        start_draw4<kStreamFabStart, M == kLinf, DRAW, VEC>(ph, nr, b, group_element(g), D, t);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float a = fabsf(t[j]);
@@ -791,7 +768,7 @@ __global__ __launch_bounds__(kSampleBlock) void start_kernel(float *__restrict__
 #pragma unroll
             for (int j = 0; j < 4; ++j) t[j] = keep[g * 4 + j];
         } else {
-            start_fetch<M, DRAW, VEC>(ph, nr, b, e, D, t);
+            start_draw4<kStreamFabStart, M == kLinf, DRAW, VEC>(ph, nr, b, e, D, t);
         }
         load4<VEC>(x0r, e, D, ov);
 #pragma unroll

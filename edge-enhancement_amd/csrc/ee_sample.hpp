@@ -51,6 +51,33 @@ __device__ __forceinline__ void store4(float *row, int64_t e, int64_t D, const f
     }
 }
 
+// ---- the draw of a random start (ee_fab_start_f32 under kStreamFabStart, ee_apgd_start_f32 under kStreamApgdStart) ------------------------
+// Four consecutive elements of sample b's draw from element e on.  DRAW: one Philox call per group of four elements under the counter
+// (b << 32) | (e >> 2) and the stream id STREAM - a row's draw depends on (seed, b, element) alone - UNIFORM: 2 u01 - 1 on [-1, 1), else
+// the standard normals of normal4.  !DRAW: the row of injected noise.  Elements at or past D read as 0 either way, as load4's do.
+template <uint32_t STREAM, bool UNIFORM, bool DRAW, bool VEC>
+__device__ __forceinline__ void start_draw4(const Philox &ph, const float *noise_row, int b, int64_t e, int64_t D, float (&t)[4]) {
+    if (!DRAW) {
+        load4<VEC>(noise_row, e, D, t);
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) t[j] = 0.0f;
+    if (e >= D) return;  // a group past the row: nothing to draw (e is fixed by the thread and the group, not by data)
+    const uint4 r = ph((static_cast<uint64_t>(static_cast<uint32_t>(b)) << 32) | static_cast<uint64_t>(e >> 2), STREAM);
+    if (UNIFORM) {
+        t[0] = 2.0f * u01(r.x) - 1.0f;  // exact: u01 is a multiple of 2^-24 in [0, 1)
+        t[1] = 2.0f * u01(r.y) - 1.0f;
+        t[2] = 2.0f * u01(r.z) - 1.0f;
+        t[3] = 2.0f * u01(r.w) - 1.0f;
+    } else {
+        normal4(r, t);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (e + j >= D) t[j] = 0.0f;  // elements at or past D read as 0, as load4's do
+}
+
 // the int butterfly (a name of its own: a wave_sum overload declared in a file's own namespace hides ee::wave_sum(double) from it, and
 // ee_rows.hpp keeps that name for the double sum alone)
 __device__ __forceinline__ int wave_count(int v) {

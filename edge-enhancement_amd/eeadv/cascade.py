@@ -33,6 +33,14 @@ def _fab_restarts_kw(args):
     return {} if n == 1 else {"n_restarts": n}
 
 
+def _apgd_restarts_kw(args):
+    """What args.apgd_restarts (default 1) adds to the APGD stages' calls: nothing for one restart."""
+    n = int(getattr(args, "apgd_restarts", 1) or 1)
+    if n < 1:
+        raise ValueError("apgd_restarts must be at least 1, got %d" % n)
+    return {} if n == 1 else {"n_restarts": n}
+
+
 def default_stages(args, num_steps, n_class, n_target_classes=9, norm="Linf"):
     """[(name, fn)] of AutoAttack's `standard` order; fn(model, args, x, y, order) -> (x_adv, robust) runs one stage on one full batch, `order`
     being the class order of the clean logits [B, n_t + 1] (the targets of APGD-T and FAB-T: no clean forward of their own).  norm: 'Linf'
@@ -42,9 +50,10 @@ def default_stages(args, num_steps, n_class, n_target_classes=9, norm="Linf"):
     queries = int(getattr(args, "square_queries", 5000))
     kw = A._norm_kw(norm)  # empty for Linf
     rkw = _fab_restarts_kw(args)  # empty for one restart
+    akw = _apgd_restarts_kw(args)  # likewise
     return [
-        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", **kw)),
-        ("APGD-T", lambda model, a, x, y, order: A.APGD_T(model, a, x, y, num_steps, n_class, n_target_classes, order=order, **kw)),
+        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", **kw, **akw)),
+        ("APGD-T", lambda model, a, x, y, order: A.APGD_T(model, a, x, y, num_steps, n_class, n_target_classes, order=order, **kw, **akw)),
         ("FAB-T", lambda model, a, x, y, order: A.FAB_T(model, a, x, y, n_class, fab_iters, n_target_classes, order=order, **kw, **rkw)[:2]),
         ("Square", lambda model, a, x, y, order: A.Square(model, a, x, y, queries, **kw)[:2]),
     ]
@@ -57,9 +66,10 @@ def l1_stages(args, num_steps, n_class, n_target_classes=9):
     fab_iters = int(getattr(args, "fab_iters", 100))
     queries = int(getattr(args, "square_queries", 5000))
     rkw = _fab_restarts_kw(args)  # empty for one restart
+    akw = _apgd_restarts_kw(args)  # likewise
     return [
-        ("APGD-L1-CE", lambda model, a, x, y, order: A.APGD_L1(model, a, x, y, num_steps, "ce")),
-        ("APGD-T-L1", lambda model, a, x, y, order: A.APGD_T_L1(model, a, x, y, num_steps, n_class, n_target_classes, order=order)),
+        ("APGD-L1-CE", lambda model, a, x, y, order: A.APGD_L1(model, a, x, y, num_steps, "ce", **akw)),
+        ("APGD-T-L1", lambda model, a, x, y, order: A.APGD_T_L1(model, a, x, y, num_steps, n_class, n_target_classes, order=order, **akw)),
         ("FAB-T-L1", lambda model, a, x, y, order: A.FAB_T_L1(model, a, x, y, n_class, fab_iters, n_target_classes, order=order, **rkw)[:2]),
         ("Square-L1", lambda model, a, x, y, order: A.Square_L1(model, a, x, y, queries)[:2]),
     ]
@@ -74,9 +84,10 @@ def rand_stages(args, num_steps, eot_iter=None, norm="Linf"):
     E = 20 if E is None else int(E)
     if E < 1:
         raise ValueError("the rand stages need eot_iter >= 1, got %d" % E)
+    akw = _apgd_restarts_kw(args)  # empty for one restart
     return [
-        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", eot_iter=E, **kw)),
-        ("APGD-DLR", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "dlr", eot_iter=E, **kw)),
+        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", eot_iter=E, **kw, **akw)),
+        ("APGD-DLR", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "dlr", eot_iter=E, **kw, **akw)),
     ]
 
 

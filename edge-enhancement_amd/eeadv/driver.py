@@ -38,12 +38,13 @@ def make_parser(description, default_data="synthetic", with_local_rank=False):
     parser.add_argument('--pretrained', dest='pretrained', action='store_true', help='use pre-trained model')
     parser.add_argument('--resume', default='', type=str, metavar='PATH', help='path to latest checkpoint, (default: None)')
     parser.add_argument('-e', '--evaluate', dest='evaluate', action='store_true', help='evaluate model on validation set')
-    parser.add_argument('--attack_method', default='PGD', type=str, metavar='PATH', help='attack method in validation: PGD, FGSM, CW, APGD-CE, APGD-T, APGD (CE then T), Square, APGD+Square (CE, T, then Square), FAB-T, APGD+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch) Cascade (the same four, each on the samples still robust, over the whole split), APGD-DLR, Rand (APGD-CE then APGD-DLR, every gradient averaged over --eot_iter forwards: for defences that redraw at every forward) or Cascade-Rand (the same two, APGD-DLR on the survivors only), APGD-L1-CE, APGD-L1-T or APGD-L1 (CE then T): APGD in the L1 threat model, radius --epsilon, FAB-U (untargeted FAB: one backward pass per class and iteration), FAB-L1-T or APGD-L1+FAB (CE, T, then FAB-T): FAB-T in the L1 threat model, FAB-L1-U (untargeted FAB in L1), Square-L1 or APGD-L1+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch: the full L1 ensemble): Square in the L1 threat model (default: PGD)')
+    parser.add_argument('--attack_method', default='PGD', type=str, metavar='PATH', help='attack method in validation: PGD, FGSM, CW, APGD-CE, APGD-T, APGD (CE then T), Square, APGD+Square (CE, T, then Square), FAB-T, APGD+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch) Cascade (the same four, each on the samples still robust, over the whole split), APGD-DLR, Rand (APGD-CE then APGD-DLR, every gradient averaged over --eot_iter forwards: for defences that redraw at every forward) or Cascade-Rand (the same two, APGD-DLR on the survivors only), APGD-L1-CE, APGD-L1-T or APGD-L1 (CE then T): APGD in the L1 threat model, radius --epsilon, FAB-U (untargeted FAB: one backward pass per class and iteration), FAB-L1-T or APGD-L1+FAB (CE, T, then FAB-T): FAB-T in the L1 threat model, FAB-L1-U (untargeted FAB in L1), Square-L1 or APGD-L1+FAB+Square (CE, T, FAB-T, then Square, each on the whole batch: the full L1 ensemble): Square in the L1 threat model, Custom (the reference\'s `custom` AutoAttack version: APGD-CE then untargeted FAB, each on the whole batch; with --apgd_restarts 2 --fab_restarts 2 the setting of its utils/aa.py) (default: PGD)')
     parser.add_argument('--eot_iter', default=None, type=int, help='forwards every APGD gradient is averaged over (EOT); default: 20 for Rand and Cascade-Rand, 1 for APGD-CE and APGD-DLR; the other attacks have no EOT and refuse a value above 1')
     parser.add_argument('--norm', default='Linf', type=str, help='threat model of the evaluation attack, radius --epsilon of the config: Linf (default) or L2; L2 exists for APGD-CE, APGD-T, APGD, APGD-DLR, Rand and Cascade-Rand and every other method refuses it')
     parser.add_argument('--square_queries', default=5000, type=int, help='forwards per sample of the Square attack at most (default: 5000); not the defence\'s n_queries')
     parser.add_argument('--fab_iters', default=100, type=int, help='iterations of FAB-T per target class, and of the one run of FAB-U / FAB-L1-U (default: 100)')
     parser.add_argument('--fab_restarts', default=1, type=int, help='runs of every FAB (FAB-T per target class, FAB-U, their L1 forms, the FAB stage of APGD+FAB+Square, APGD-L1+FAB, APGD-L1+FAB+Square and Cascade): the first from the clean point, every later one from a random point at distance min(best norm so far, epsilon) / 2, the best norm kept (default: 1); any other method refuses a value other than 1')
+    parser.add_argument('--apgd_restarts', default=1, type=int, help='runs of every APGD (APGD-CE, APGD-DLR, APGD-T per target class, their L1 forms, the APGD stages of the composites, of Rand, Custom, Cascade and Cascade-Rand): the first from the start drawn as before, every later one on the whole batch from a fresh draw of the same distribution made on the device; a sample counts as fooled if any run fooled it (default: 1); any other method refuses a value other than 1')
     parser.add_argument('--no-cuda', action='store_true', default=False, help='disables CUDA training')
     parser.add_argument('--max-epochs', type=int, default=None, help='stop after this many epochs (smoke runs)')
     parser.add_argument('--output-root', default=None, help='where checkpoint_<DS>/ is created (default: cwd, as the reference)')
@@ -227,6 +228,8 @@ def validate_cascade(val_loader, model, args, device, num_steps, n_class, log):
     model.eval()
     start = time.time()
     eot_iter, stages, tag = trainer.eot_iter_for(args), None, trainer.norm_tag(args)
+    if trainer.apgd_restarts_for(args):
+        log(' * APGD: {0} restarts per run, each on the whole batch of its stage'.format(int(args.apgd_restarts)))
     if trainer.fab_restarts_for(args):
         log(' * FAB-T: {0} restarts per target class, {1} iterations each'.format(int(args.fab_restarts), int(getattr(args, 'fab_iters', 100))))
     if args.attack_method == trainer.CASCADE_RAND_METHOD:
@@ -262,7 +265,9 @@ def validate(val_loader, model, criterion, args, device, num_steps, step_size, l
     if "pre_square" in args.method_name:
         from utils.core import Add_Square
         add_square = Add_Square(channels=spec["shape"][0], size=args.cize, epsilon=args.epsilon, n_queries=args.n_queries)
-    if args.attack_method in trainer.FAB_U_METHODS + trainer.L1_FAB_U_METHODS:
+    if trainer.apgd_restarts_for(args):
+        _log(' * {0}: APGD, {1} restarts per run, each on the whole batch'.format(args.attack_method, int(args.apgd_restarts)), log_dir)
+    if args.attack_method in trainer.FAB_U_METHODS + trainer.L1_FAB_U_METHODS + (trainer.CUSTOM_METHOD,):
         # untargeted FAB takes one backward pass per class and iteration: say so before the first batch
         _log(' * {0}: K = {1} classes, {1} backward passes per iteration, {2} iterations'.format(
             args.attack_method, spec["num_classes"], int(getattr(args, 'fab_iters', 100))) + _restarts_tag(args), log_dir)
@@ -303,6 +308,7 @@ def run(spec, build_model, argv=None):
     trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
     trainer.norm_for(args)  # and a --norm it has no L2 for
     trainer.fab_restarts_for(args)  # and a --fab_restarts on a method that runs no FAB
+    trainer.apgd_restarts_for(args)  # and an --apgd_restarts on a method that runs no APGD
     for key, default in (("type_canny", None), ("step_size_3", args.get("step_size_2")), ("num_steps_3", args.get("num_steps_2")),
                          ("n_queries", 1), ("cize", spec["shape"][-1]), ("beta", 1.0)):
         if key not in args:

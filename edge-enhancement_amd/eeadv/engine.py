@@ -256,8 +256,8 @@ def _prepare(model, key, make_run, inputs, chunk):
 def _drive(model, key, make_run, inputs, n_iter, chunk, use_graph, n_restarts=1):
     """One attack of n_iter iterations on a run object (load(*inputs), start(model), body(model, n, last=False): n consecutive
     iterations, result()): eager - one body call, told that none follows - or n_iter // chunk replays of the graph cached under `key`.
-    load, start and result stay outside the graph ("The attack loops' driver").  n_restarts > 1 (FAB, section 23):
-    the same iterations once more behind run.restart(model, r) for r = 1 .. n_restarts - 1 - the same graph, whatever the count."""
+    load, start and result stay outside the graph (DESIGN.md section 4, "The attack loops' driver").  n_restarts > 1 (FAB, section 23;
+    APGD, section 24): the same iterations once more behind run.restart(model, r) for r = 1 .. n_restarts - 1 - the same graph, whatever the count."""
     if not use_graph:
         run = make_run()
         run.load(*inputs)
@@ -360,6 +360,13 @@ def _apgd_args(loss, targets, trace, use_graph):
     return use_graph
 
 
+def _apgd_restarts(x0, n_restarts, seed, noise, target_index):
+    """(n_restarts, what the count adds to the run's load arguments): () for one restart - the load call, like every other, is then the
+    one made before restarts existed and no ticket is taken - else (seeds, noise) as _fab_restarts forms them."""
+    n_restarts, seeds, noise = _fab_restarts(x0, n_restarts, seed, noise, target_index, "APGD")
+    return n_restarts, (() if n_restarts == 1 else (seeds, noise))
+
+
 class _ApgdSpec:
     """The loss-gradient step of `_body_input_grad` for an APGD run: the row losses, their logit gradient and `pred` in one launch, then -
     once the run is past its start point - the run's per-sample bookkeeping (run.book()).  The kind is none of the CE kinds, so the route
@@ -397,14 +404,38 @@ class _ApgdState:
         self.loss_rows = self.pred = None
         self.started = False
         self.spec = _ApgdSpec(self)
+        self.n_restarts, self.seeds, self.noise = 1, (), None
+        self.adv_all = self.robust_all = self.loss_all = None  # the union across restarts: they exist once a call asks for more than one
 
-    def load(self, x_init, x0, y, targets):
+    def load(self, x_init, x0, y, targets, seeds=(), noise=None):
+        """seeds: the Philox keys of restarts 1 .. n_restarts - 1 (their count sets n_restarts); noise [n_restarts - 1, B, ...]: their draws,
+        injected in place of the kernel's own.  Neither is seen by the graph."""
+        self.seeds, self.noise, self.n_restarts = tuple(seeds), noise, 1 + len(seeds)
+        if self.n_restarts > 1 and self.adv_all is None:
+            B, dev = self.x0.shape[0], self.x0.device
+            self.adv_all = torch.empty_like(self.x0)
+            self.robust_all = torch.empty(B, dtype=torch.int32, device=dev)
+            self.loss_all = torch.empty(B, dtype=torch.float32, device=dev)
         with torch.no_grad():
             self.x.detach().copy_(x_init)
             self.x0.copy_(x0)
             self.y.copy_(y)
             if self.t is not None:
                 self.t.copy_(targets)
+
+    def _merge(self, first):
+        ops.apgd_merge_(self.adv_all, self.robust_all, self.loss_all, self.x_best_adv, self.istate[ops.APGD_I_ROBUST],
+                        self.fstate[ops.APGD_F_LOSS_BEST], first)
+
+    def restart(self, model, r):
+        """Restart r >= 1: the finished restart goes into the union, x <- a fresh draw of the run's own start
+        distribution around x0, then `start` - the forward/backward at the new point and the state reset of restart 0, an L1 run's
+        projection and an EOT run's E draws included."""
+        noise = None if self.noise is None else self.noise[r - 1]
+        with torch.no_grad():
+            self._merge(r == 1)
+            ops.apgd_start_(self.x.detach(), self.x0, self.eps, self.norm, self.seeds[r - 1], noise, self.path)
+        self.start(model)
 
     def body(self, model, n, last=False):
         """n consecutive iterations.  The gradient enters through self.g and - unless this is the last body of the attack - leaves through
@@ -418,6 +449,10 @@ class _ApgdState:
 
     def result(self):
         with torch.no_grad():
+            if self.n_restarts > 1:  # the last restart joins the union: fooled by any restart, the point of the first that fooled
+                self._merge(False)
+                robust = self.robust_all != 0
+                return _adv_where_fooled(robust, self.x0, self.adv_all), robust, self.loss_all.clone()
             robust = self.istate[ops.APGD_I_ROBUST] != 0
             return _adv_where_fooled(robust, self.x0, self.x_best_adv), robust, self.fstate[ops.APGD_F_LOSS_BEST].clone()
 
@@ -431,6 +466,7 @@ class _ApgdRun(_ApgdState):
     the place of ee_apgd_step_f32 - nothing else knows the norm.  `trace` (a list, eager runs only) receives one dict per gradient
     evaluation."""
     KIND = "apgd_"
+    path = "auto"  # of the restarts' start launch
 
     def __init__(self, x0, y, n_iter, eps, loss, eot_iter=1, norm="Linf", trace=None):
         self.norm, self.eot_iter = _check_norm(norm, APGD_NORMS, "APGD"), int(eot_iter)
@@ -521,7 +557,8 @@ class _ApgdRun(_ApgdState):
         return g_new
 
 
-def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, eot_iter=1, trace=None, norm="Linf"):
+def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, eot_iter=1, trace=None, norm="Linf", n_restarts=1,
+              seed=None, noise=None, target_index=0):
     """One APGD run of n_iter iterations from x_init inside the eps-ball around x0, on loss 'ce', 'dlr' or 'dlr_t' (which takes `targets`).
     norm: 'Linf' (the default: exactly what ran before the parameter existed) or 'L2' - the ball is then the L2 ball of radius eps and the
     step ee_apgd_step_l2_f32; start, losses, bookkeeping, copies, EOT, the initial step 2 eps and the schedule are
@@ -535,7 +572,14 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
     iterate on the mean of the E row losses (summed in double) and on the LAST draw's pred.  A replay then covers _eot_chunk(n_iter, E)
     iterations.  E = 1 launches exactly what the loop launched before EOT existed.  `trace` (a list, eager only) receives, per gradient
     evaluation (the start's first), {"draws": [{"loss", "pred", "g"} per draw], "book_loss", "book_pred", "g_mean", "counter", "flags"}
-    (the last two None at the start point) and, before each step, {"step_g"}: the gradient that step reads."""
+    (the last two None at the start point) and, before each step, {"step_g"}: the gradient that step reads.
+
+    n_restarts = 1 (the default) is the one run from x_init - the launches, buffers and bits of the loop before restarts existed, no ticket
+    taken.  n_restarts > 1: restart 0 is that run; restart r >= 1 runs the same n_iter iterations - the same graph -
+    on the WHOLE batch from a fresh draw of the run's own start distribution (ee_apgd_start_f32: Linf clamp(x0 + eps U(-1, 1), 0, 1),
+    L2 clamp(x0 + eps n / ||n||_2, 0, 1)), drawn on the device under fabstart.seed_of(seed, target_index, r) (seed None: one ticket from
+    torch's generator) or taken from noise[r - 1] (`noise` [n_restarts - 1, B, ...], injected).  robust is then "no restart fooled it",
+    x_adv holds the point of the first restart that did (ee_apgd_merge_f32) and loss_best the largest over the restarts."""
     use_graph = _apgd_args(loss, targets, trace, use_graph)
     eot_iter = int(eot_iter)
     if eot_iter < 1:
@@ -547,12 +591,13 @@ def apgd_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=N
     n_iter = _n_iter(n_iter)
     chunk = _eot_chunk(n_iter, eot_iter)
     key = ("apgd", id(model), model.training, tuple(x0.shape), loss, norm, n_iter, float(eps), x0.device.index, chunk, eot_iter)
-    return _drive(model, key, lambda: _ApgdRun(x0, y, n_iter, eps, loss, eot_iter, norm, trace), (x_init, x0, y, targets), n_iter, chunk,
-                  use_graph)
+    n_restarts, more = _apgd_restarts(x0, n_restarts, seed, noise, target_index)
+    return _drive(model, key, lambda: _ApgdRun(x0, y, n_iter, eps, loss, eot_iter, norm, trace), (x_init, x0, y, targets) + more, n_iter,
+                  chunk, use_graph, n_restarts)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
-# APGD in the L1 threat model (Croce & Hein 2021; one run, no momentum, no EOT, no restarts, no large-radius warm-up): a door of its own
+# APGD in the L1 threat model (Croce & Hein 2021; no momentum, no EOT, no large-radius warm-up; restarts: section 24): a door of its own
 # next to apgd_loop, which keeps refusing norm = "L1" 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def apgd_l1_schedule(n_iter):
@@ -569,6 +614,7 @@ class _ApgdL1Run(_ApgdState):
     backward, copies: what a captured graph replays).  `trace` (a list, eager runs only) receives one dict for the start and one per
     iteration."""
     KIND = "apgd_l1_"
+    norm = "L1"
 
     def __init__(self, x0, y, n_iter, eps, loss, path="auto", trace=None):
         B, dev = x0.shape[0], x0.device
@@ -634,7 +680,8 @@ class _ApgdL1Run(_ApgdState):
         return g_new
 
 
-def apgd_l1_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, trace=None, path="auto"):
+def apgd_l1_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_graph=None, trace=None, path="auto", n_restarts=1, seed=None,
+                 noise=None, target_index=0):
     """One L1-APGD run of n_iter iterations inside {z : ||z - x0||_1 <= eps} n [0,1]^D, on loss 'ce', 'dlr' or 'dlr_t' (which takes
     `targets`).  x_init is the unprojected start x0 + n: the run starts at P(x_init), the exact projection (ee_l1_proj_f32).  An
     iteration is ee_apgd_step_l1_f32 -> forward -> ee_apgd_loss_f32 -> ee_apgd_book_l1_f32 -> backward -> ee_apgd_select_f32 on the
@@ -644,7 +691,9 @@ def apgd_l1_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_grap
     kernels' path ('auto', 'resident', 'streaming'; the same bits).  `trace` (a list, eager only) receives the start's dict {"start", "u",
     "scal", "x", "loss", "pred", "g", "step", "topk", "sp_old"} and, per iteration, {"step_g", "x_in", "counter", "step_in", "topk_in",
     "sp_old_in", "scal", "x", "loss", "pred", "g", "flags", "sp", "loss_best", "step", "topk", "sp_old", "x_out", "g_out", "x_best",
-    "x_best_adv"}: what the step read and wrote, what the bookkeeping decided, and the state after the copies."""
+    "x_best_adv"}: what the step read and wrote, what the bookkeeping decided, and the state after the copies.  n_restarts, seed, noise
+    and target_index as in apgd_loop: restart r >= 1 starts at P(x0 + n), n a fresh standard normal draw (the trace then holds one start
+    dict per restart)."""
     use_graph = _apgd_args(loss, targets, trace, use_graph)
     ops._sample_path(path, "the L1 kernels'")
     if not float(eps) >= 0.0:
@@ -657,7 +706,9 @@ def apgd_l1_loop(model, x0, x_init, y, n_iter, eps, loss, targets=None, use_grap
         return _empty_result(x0, torch.float32)
     chunk = _chunk(n_iter)
     key = ("apgd_l1", id(model), model.training, tuple(x0.shape), loss, n_iter, float(eps), x0.device.index, chunk, path)
-    return _drive(model, key, lambda: _ApgdL1Run(x0, y, n_iter, eps, loss, path, trace), (x_init, x0, y, targets), n_iter, chunk, use_graph)
+    n_restarts, more = _apgd_restarts(x0, n_restarts, seed, noise, target_index)
+    return _drive(model, key, lambda: _ApgdL1Run(x0, y, n_iter, eps, loss, path, trace), (x_init, x0, y, targets) + more, n_iter, chunk,
+                  use_graph, n_restarts)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -929,14 +980,14 @@ def _fab_ops(norm):
     return ops.fab_proj_linf, ops.fab_step_, ops.fab_commit_
 
 
-def _fab_restarts(x0, n_restarts, seed, noise, target_index=0):
+def _fab_restarts(x0, n_restarts, seed, noise, target_index=0, what="FAB"):
     """(n_restarts, seeds, noise) as _FabRun.load takes them.  One restart - the default - draws nothing and takes no ticket: the calls
     are the ones made before restarts existed.  Otherwise restart r = 1 .. n_restarts - 1 draws under fabstart.seed_of(seed, target_index,
     r) (seed None: a ticket from torch's generator of the device, as square_loop takes it), or takes noise[r - 1] of the injected
     `noise` [n_restarts - 1, B, ...]."""
     n_restarts = int(n_restarts)
     if n_restarts < 1:
-        raise ValueError("FAB needs n_restarts >= 1, got %d" % n_restarts)
+        raise ValueError("%s needs n_restarts >= 1, got %d" % (what, n_restarts))
     if n_restarts == 1:
         return 1, (), None
     if noise is not None:

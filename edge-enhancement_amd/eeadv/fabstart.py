@@ -23,9 +23,9 @@ def seed_of(seed, target_index, restart):
     return z ^ (z >> 31)
 
 
-def draw(seed, B, D, metric):
+def draw(seed, B, D, metric, stream=STREAM_FAB_START):
     """t, float32 [B, D]: the draw ee_fab_start_f32 makes for rows 0 .. B-1 under the key `seed` - one Philox call per group of four
-    elements, counter (b << 32) | (element >> 2), stream 15.  'Linf': t = 2 u - 1 with u = (word >> 8) 2^-24, exact, so bit-identical to
+    elements, counter (b << 32) | (element >> 2), stream 15 (`stream`: the id of another start launch that draws the same way).  'Linf': t = 2 u - 1 with u = (word >> 8) 2^-24, exact, so bit-identical to
     the kernel.  'L2' / 'L1': the Box-Muller pairs (words 0, 1) and (words 2, 3), sqrt(-2 log(1 - u_a)) cos / sin(a) with the angle
     a = float32(2 pi) * u_b rounded to float32 as the kernel rounds it, everything else in float64 and cast once: the kernel's value up to
     the rounding of its float logf, sqrtf, cosf / sinf and product."""
@@ -34,7 +34,7 @@ def draw(seed, B, D, metric):
     B, D = int(B), int(D)
     G = (D + 3) // 4
     ctr = ((np.arange(B, dtype=np.uint64)[:, None] << np.uint64(32)) | np.arange(G, dtype=np.uint64)[None, :]).reshape(-1)
-    r = philox4x32(seed, ctr, STREAM_FAB_START).reshape(B, G, 4)
+    r = philox4x32(seed, ctr, int(stream)).reshape(B, G, 4)
     u = (r >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)  # exact
     if metric == "Linf":
         t = np.float32(2.0) * u - np.float32(1.0)

@@ -500,6 +500,39 @@ def apgd_select_(x, g, x_best, g_best, x_best_adv, flags, counter):
     return x
 
 
+def apgd_start_(x, x0, eps, metric, seed=0, noise=None, path="auto"):
+    """The start point of an APGD restart, written into x [B, ...]: 'Linf' clamp(x0 + eps t, 0, 1) with t uniform
+    on [-1, 1); 'L2' clamp(x0 + t * (eps / (||t||_2 + 1e-12)), 0, 1) with t standard normal (a row whose norm is not finite is x0); 'L1'
+    x0 + t, unclamped - the run's own projection follows.  t is the row of `noise` [B, ...] or, with noise None, the draw of
+    csrc/ee_apgd_start.hip keyed by `seed` (eeadv.fabstart.draw with stream STREAM_APGD_START restates it)."""
+    B = x.shape[0]
+    if metric not in FAB_METRICS:
+        raise ValueError("APGD metric must be one of %s, got %r" % (sorted(FAB_METRICS), metric))
+    px = _chk(x, torch.float32, "x")
+    p0 = _chk(x0, torch.float32, "x0", x.shape)
+    if B and x.data_ptr() == x0.data_ptr():
+        raise ValueError("apgd_start_ writes x while it reads x0: they must be two tensors")
+    N.check(N.lib.ee_apgd_start_f32(px, p0, _opt(noise, torch.float32, "noise", x.shape), B, x.numel() // B if B else 1, eps,
+                                    FAB_METRICS[metric], int(seed) & 0xFFFFFFFFFFFFFFFF, _sample_path(path, "the APGD start's"), _stream()),
+            "ee_apgd_start_f32")
+    return x
+
+
+def apgd_merge_(adv_all, robust_all, loss_all, x_best_adv, robust_run, loss_best_run, first):
+    """The union across restarts, in place on adv_all [B, ...] float32, robust_all [B] int32 and loss_all [B]
+    float32, from the finished run's x_best_adv, robust row [B] int32 and best losses [B]: a sample this run fooled and no earlier one had
+    takes this run's point and loses its flag, loss_all keeps the larger loss; `first` (restart 0) overwrites flags and losses instead."""
+    B = adv_all.shape[0]
+    pa = _chk(adv_all, torch.float32, "adv_all")
+    pb = _chk(x_best_adv, torch.float32, "x_best_adv", adv_all.shape)
+    if B and adv_all.data_ptr() == x_best_adv.data_ptr():
+        raise ValueError("apgd_merge_ writes adv_all while it reads x_best_adv: they must be two tensors")
+    N.check(N.lib.ee_apgd_merge_f32(pa, _chk(robust_all, torch.int32, "robust_all", (B,)), _chk(loss_all, torch.float32, "loss_all", (B,)), pb,
+                                    _chk(robust_run, torch.int32, "robust_run", (B,)), _chk(loss_best_run, torch.float32, "loss_best_run", (B,)),
+                                    B, adv_all.numel() // B if B else 1, 1 if first else 0, _stream()), "ee_apgd_merge_f32")
+    return adv_all
+
+
 # ---- APGD in the L1 threat model (ee_apgd_l1.hip) --------------------------------------------------------------------
 L1_S_LAMBDA, L1_S_H0, L1_S_ACTIVE, L1_S_DIST, L1_S_TAU, L1_S_M, L1_S_J = range(7)  # rows of scal
 L1_SCAL_ROWS = 7

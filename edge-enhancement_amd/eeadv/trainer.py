@@ -695,6 +695,22 @@ def fab_restarts_for(args):
     return {'n_restarts': n}
 
 
+def apgd_restarts_for(args):
+    """{} or {'n_restarts': N}: what args.apgd_restarts (--apgd_restarts; None / absent: 1) adds to the APGD calls of args.attack_method
+    (DESIGN.md section 24).  One restart adds nothing - the calls stay the ones made before the option existed.  A method that runs no
+    APGD stops here on N != 1 instead of ignoring it, as fab_restarts_for does."""
+    n = getattr(args, 'apgd_restarts', None)
+    n = 1 if n is None else int(n)
+    if n < 1:
+        raise ValueError("--apgd_restarts must be at least 1, got %d" % n)
+    if n == 1:
+        return {}
+    if args.attack_method not in APGD_RESTART_METHODS:
+        raise NotImplementedError("--apgd_restarts %d with --attack_method %s: restarts are built for APGD only - %s - not for Square, for FAB "
+                                  "(--fab_restarts) or the reference's own attacks" % (n, args.attack_method, ", ".join(APGD_RESTART_METHODS)))
+    return {'n_restarts': n}
+
+
 L2_MESSAGE = ("the L2 threat model is built for APGD-CE, APGD-T, APGD, APGD-DLR, Rand and Cascade-Rand only - L2 Square and L2 FAB are different "
               "algorithms and are not built, so Square, APGD+Square, FAB-T, APGD+FAB+Square and Cascade have no L2, and the reference's own "
               "attacks (PGD, FGSM, CW) are Linf")
@@ -727,6 +743,7 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
     eot_iter = eot_iter_for(args)
     nkw = A._norm_kw(norm_for(args))  # empty for Linf: the calls below are then the ones made before --norm existed
     rkw = fab_restarts_for(args)  # empty for one restart, likewise
+    akw = apgd_restarts_for(args)  # and so is this one, for the APGD calls
     if args.attack_method == 'PGD':
         if targeted:
             return A.targeted_PGD(model, args, input, target, num_steps, step_size, n_class, device)[0]
@@ -750,9 +767,9 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
         x_adv, robust = None, None
         if args.attack_method in ('APGD-CE', 'APGD'):
-            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', eot_iter=eot_iter, **nkw)
+            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', eot_iter=eot_iter, **nkw, **akw)
         if args.attack_method in ('APGD-T', 'APGD'):
-            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class, **nkw)
+            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class, **nkw, **akw)
             if x_adv is None:
                 return xt
             x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
@@ -769,8 +786,8 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             if args.attack_method == 'Square-L1':
                 return A.Square_L1(model, args, input, target, queries)[0]
             fab_iters = int(getattr(args, 'fab_iters', 100))
-            return A._first_fooling(input.detach(), (A.APGD_L1(model, args, input, target, num_steps, 'ce'),
-                                                     A.APGD_T_L1(model, args, input, target, num_steps, n_class),
+            return A._first_fooling(input.detach(), (A.APGD_L1(model, args, input, target, num_steps, 'ce', **akw),
+                                                     A.APGD_T_L1(model, args, input, target, num_steps, n_class, **akw),
                                                      A.FAB_T_L1(model, args, input, target, n_class, fab_iters, **rkw)[:2],
                                                      A.Square_L1(model, args, input, target, queries)[:2]))[0]
         if args.attack_method in L1_FAB_METHODS:
@@ -779,14 +796,14 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             fab_iters = int(getattr(args, 'fab_iters', 100))
             if args.attack_method == 'FAB-L1-T':
                 return A.FAB_T_L1(model, args, input, target, n_class, fab_iters, **rkw)[0]
-            return A._first_fooling(input.detach(), (A.APGD_L1(model, args, input, target, num_steps, 'ce'),
-                                                     A.APGD_T_L1(model, args, input, target, num_steps, n_class),
+            return A._first_fooling(input.detach(), (A.APGD_L1(model, args, input, target, num_steps, 'ce', **akw),
+                                                     A.APGD_T_L1(model, args, input, target, num_steps, n_class, **akw),
                                                      A.FAB_T_L1(model, args, input, target, n_class, fab_iters, **rkw)[:2]))[0]
         x_adv, robust = None, None
         if args.attack_method in ('APGD-L1-CE', 'APGD-L1'):
-            x_adv, robust = A.APGD_L1(model, args, input, target, num_steps, 'ce')
+            x_adv, robust = A.APGD_L1(model, args, input, target, num_steps, 'ce', **akw)
         if args.attack_method in ('APGD-L1-T', 'APGD-L1'):
-            xt, rt = A.APGD_T_L1(model, args, input, target, num_steps, n_class)
+            xt, rt = A.APGD_T_L1(model, args, input, target, num_steps, n_class, **akw)
             if x_adv is None:
                 return xt
             x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
@@ -800,6 +817,14 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         if args.attack_method in L1_FAB_U_METHODS:
             return A.FAB_L1(model, args, input, target, fab_iters, **rkw)[0]
         return A.FAB(model, args, input, target, fab_iters, **rkw)[0]
+    if args.attack_method == CUSTOM_METHOD:
+        # the reference's `custom` version (utils/aa.py: attacks_to_run = ['apgd-ce', 'fab']): APGD-CE, then untargeted FAB - FAB-U's call -
+        # each on the whole batch, flags ANDed, the first fooling point kept.  Linf only: norm_for / eot_iter_for have refused the rest.
+        if targeted:
+            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+        fab_iters = int(getattr(args, 'fab_iters', 100))
+        return A._first_fooling(input.detach(), (A.APGD(model, args, input, target, num_steps, 'ce', **akw),
+                                                 A.FAB(model, args, input, target, fab_iters, **rkw)[:2]))[0]
     if args.attack_method in SQUARE_METHODS:
         # Square (black-box, args.square_queries forwards per sample at most), alone or after APGD-CE and APGD-T: flags ANDed, the first
         # fooling point kept
@@ -808,8 +833,8 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         shape = (-1,) + (1,) * (input.dim() - 1)
         x_adv, robust = None, None
         if args.attack_method == 'APGD+Square':
-            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce')
-            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class)
+            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', **akw)
+            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class, **akw)
             x_adv = torch.where((robust & ~rt).view(shape), xt, x_adv)
             robust = robust & rt
         xs, rs, _ = A.Square(model, args, input, target, int(getattr(args, 'square_queries', 5000)))
@@ -825,8 +850,8 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         fab_iters = int(getattr(args, 'fab_iters', 100))
         if args.attack_method == 'FAB-T':
             return A.FAB_T(model, args, input, target, n_class, fab_iters, **rkw)[0]
-        x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce')
-        xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class)
+        x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', **akw)
+        xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class, **akw)
         x_adv = torch.where((robust & ~rt).view(shape), xt, x_adv)
         robust = robust & rt
         xf, rf, _ = A.FAB_T(model, args, input, target, n_class, fab_iters, **rkw)
@@ -840,8 +865,8 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
         if targeted:
             raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
         if args.attack_method == 'APGD-DLR':
-            return A.APGD(model, args, input, target, num_steps, 'dlr', eot_iter=eot_iter, **nkw)[0]
-        return A.APGD_Rand(model, args, input, target, num_steps, eot_iter, n_class, **nkw)[0]
+            return A.APGD(model, args, input, target, num_steps, 'dlr', eot_iter=eot_iter, **nkw, **akw)[0]
+        return A.APGD_Rand(model, args, input, target, num_steps, eot_iter, n_class, **nkw, **akw)[0]
     if args.attack_method == CASCADE_RAND_METHOD:
         raise NotImplementedError("--attack_method Cascade-Rand regroups the survivors of a whole split: it runs as eeadv.cascade.evaluate over the "
                                   "loader (driver.validate_cascade), not batch by batch")
@@ -868,8 +893,14 @@ L1_METHODS = ('APGD-L1-CE', 'APGD-L1-T', 'APGD-L1') + L1_FAB_METHODS + L1_SQUARE
 FAB_U_METHODS = ('FAB-U',)
 L1_FAB_U_METHODS = ('FAB-L1-U',)  # L1 by its name, like L1_METHODS: the ' [norm L1]' tag, --norm refused
 # what honours --fab_restarts: every method that runs a FAB
-FAB_RESTART_METHODS = ('FAB-T', 'FAB-U', 'FAB-L1-T', 'FAB-L1-U', 'APGD+FAB+Square', 'APGD-L1+FAB', 'APGD-L1+FAB+Square', CASCADE_METHOD)
-EVAL_METHODS = APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS + L1_METHODS + FAB_U_METHODS + L1_FAB_U_METHODS
+CUSTOM_METHOD = 'Custom'  # the reference's `custom` version: APGD-CE then untargeted FAB (utils/aa.py); Linf only
+FAB_RESTART_METHODS = ('FAB-T', 'FAB-U', 'FAB-L1-T', 'FAB-L1-U', 'APGD+FAB+Square', 'APGD-L1+FAB', 'APGD-L1+FAB+Square', CASCADE_METHOD,
+                       CUSTOM_METHOD)
+# what honours --apgd_restarts: every method that runs an APGD
+APGD_RESTART_METHODS = (APGD_METHODS + RAND_METHODS + ('APGD+Square', 'APGD+FAB+Square', 'APGD-L1-CE', 'APGD-L1-T', 'APGD-L1', 'APGD-L1+FAB',
+                                                       'APGD-L1+FAB+Square') + CASCADE_METHODS + (CUSTOM_METHOD,))
+EVAL_METHODS = (APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS + L1_METHODS + FAB_U_METHODS + L1_FAB_U_METHODS
+                + (CUSTOM_METHOD,))
 
 
 def validate_batch(model, criterion, args, input, target, device, num_steps, step_size, n_class):

@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from eeadv import _native  # noqa: F401  (fails loudly at import when libeeadv.so is missing)
-from eeadv import engine, fabstart, functional as EF, ops, runtime
+from eeadv import apgdstart, engine, fabstart, functional as EF, ops, runtime
 
 _INF = float("inf")
 
@@ -171,7 +171,55 @@ def _apgd_grad_once(model, xc, y, loss, t):
     return rows.detach(), g.detach(), first == y
 
 
-def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=1, norm="Linf"):
+def _apgd_restart_kw(x0, n_restarts, seed):
+    """What the APGD doors add to their engine / host calls: nothing for one restart (the calls stay the ones they always were, no ticket
+    taken), else n_restarts and the seed - the caller's, or one drawn here, once for all target classes of a targeted attack."""
+    n_restarts = int(n_restarts)
+    if n_restarts < 1:
+        raise ValueError("APGD needs n_restarts >= 1, got %d" % n_restarts)
+    if n_restarts == 1:
+        return {}
+    if seed is None:
+        seed = engine._drawn_seed(x0.device) if x0.is_cuda else int(torch.randint(0, 2 ** 62, (1,)).item())
+    return dict(n_restarts=n_restarts, seed=int(seed))
+
+
+def _apgd_host_restarts(run, x0, x, eps, metric, n_restarts, seed, noise, target_index):
+    """The chain of both APGD host paths: restart 0 is run(x) - with n_restarts = 1 that is all, and no generator
+    is touched - and restart r = 1 .. n_restarts - 1 is run(eeadv.apgdstart.start(x0, eps, t, metric)) on the whole batch, t being
+    noise[r - 1] of the injected `noise` [n_restarts - 1, B, ...] or the host restatement of the kernel's draw under
+    fabstart.seed_of(seed, target_index, r).  The flags are ANDed, the first fooling point is kept, the best loss is the largest."""
+    n_restarts = int(n_restarts)
+    if n_restarts < 1:
+        raise ValueError("APGD needs n_restarts >= 1, got %d" % n_restarts)
+    x_adv, robust, loss_best = run(x)
+    if n_restarts == 1:
+        return x_adv, robust, loss_best
+    if noise is None and seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    B = x0.shape[0]
+    shape = (-1,) + (1,) * (x0.dim() - 1)
+    for r in range(1, n_restarts):
+        if noise is not None:
+            t = noise[r - 1]
+        else:
+            t = torch.from_numpy(apgdstart.draw(apgdstart.seed_of(seed, target_index, r), B, x0[0].numel() if B else 0, metric))
+        xa, rb, lb = run(apgdstart.start(x0, eps, t.to(device=x0.device).reshape(x0.shape), metric))
+        x_adv = torch.where((robust & ~rb).view(shape), xa, x_adv)
+        robust = robust & rb
+        loss_best = torch.where(lb > loss_best, lb, loss_best)
+    return x_adv, robust, loss_best
+
+
+def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=1, norm="Linf", n_restarts=1, seed=None, noise=None,
+               target_index=0):
+    """_apgd_host_run from x and - n_restarts > 1 - from the starts of the later restarts (_apgd_host_restarts), which share `trace`."""
+    _check_norm(norm)
+    return _apgd_host_restarts(lambda xs: _apgd_host_run(model, x0, xs, y, n_iter, eps, loss, t, trace, eot_iter, norm), x0, x, eps, norm,
+                               n_restarts, seed, noise, target_index)
+
+
+def _apgd_host_run(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=1, norm="Linf"):
     """Plumbing path for CPU tensors (opt-in), the counterpart of _host_loop: the iteration of engine.apgd_loop in plain torch ops, in the
     input's dtype.  `trace`, a list, receives one dict of clones per iteration (the start point first).  eot_iter = E > 1: every gradient
     is the sum of E draws' gradients in draw order times 1/E (formed in the input's dtype), the loss the mean of their row losses summed
@@ -269,7 +317,8 @@ def _apgd_host(model, x0, x, y, n_iter, eps, loss, t=None, trace=None, eot_iter=
     return torch.where(robust.view(shape), x0, x_best_adv), robust, loss_best
 
 
-def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None, eot_iter=1, norm="Linf"):
+def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None, eot_iter=1, norm="Linf", n_restarts=1, seed=None,
+         target_index=0):
     """One APGD run (norm 'Linf' or 'L2', radius args.epsilon, num_steps iterations) on loss 'ce', 'dlr' or 'dlr_t' (targeted at `y_target`).  Returns
     (x_adv, robust): the inputs, with every sample that some iterate fooled replaced by such an iterate, and the [B] bool flags of the samples
     that stayed correctly classified throughout.  The start point is the project's uniform start, clamp(x0 + U(-eps, eps), 0, 1) (`noise=`
@@ -281,7 +330,10 @@ def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, nois
     their row losses, and a sample counts as fooled when the last of the E draws of some iterate misclassifies it.
     norm = "L2": the ball is the L2 ball, the step the published L2 step (csrc/ee_apgd_l2.hip; a rescale onto the ball followed by the
     clamp, not the exact projection onto ball and box) and the start the published one, clamp(x0 + eps n / ||n||_2, 0, 1) - `noise=` then
-    injects the standard normal draw n."""
+    injects the standard normal draw n.  n_restarts > 1: restart 0 is the run above; every
+    later restart runs the same iterations on the whole batch from a fresh draw of the same start distribution, made on the device under
+    eeadv.fabstart.seed_of(seed, target_index, r) (seed None draws one); a sample counts as fooled if any restart fooled it and the first
+    restart that did supplies its point.  `noise=` injects restart 0's draw only."""
     eot_iter = int(eot_iter)
     if eot_iter < 1:
         raise ValueError("APGD needs eot_iter >= 1, got %d" % eot_iter)
@@ -290,6 +342,9 @@ def APGD(model, args, inputs, targets, num_steps, loss='ce', y_target=None, nois
     eps = float(args.epsilon)
     x = _uniform_start(x0, eps, noise) if norm == "Linf" else _l2_start(x0, eps, noise)
     kw = {} if norm == "Linf" else {"norm": norm}  # a Linf run makes exactly the calls made before the parameter existed
+    rkw = _apgd_restart_kw(x0, n_restarts, seed)  # and so does a run with one restart
+    if rkw:
+        kw = dict(kw, target_index=int(target_index), **rkw)
     if runtime.require_device(x0, "APGD"):
         x_adv, robust, _ = engine.apgd_loop(model, x0, x, targets, num_steps, eps, loss, y_target, eot_iter=eot_iter, **kw)
     else:
@@ -308,20 +363,28 @@ def _first_fooling(x0, runs):
     return x_adv, robust
 
 
+def _restarts_kw(n_restarts, seed=None):
+    """The keywords the composites hand on to APGD / APGD_L1: none for one restart, as _norm_kw hands on none for Linf."""
+    if int(n_restarts) == 1:
+        return {}
+    return {"n_restarts": int(n_restarts)} if seed is None else {"n_restarts": int(n_restarts), "seed": seed}
+
+
 def _norm_kw(norm):
     """The keyword the composites hand on to APGD: none for Linf, so that a Linf call is the call made before the parameter existed."""
     return {} if _check_norm(norm) == "Linf" else {"norm": norm}
 
 
-def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None, noise=None, norm="Linf"):
+def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None, noise=None, norm="Linf", n_restarts=1, seed=None):
     """The order of the public ensemble's `rand` version, for defences that redraw at every forward: APGD-CE, then APGD-DLR (the untargeted
     DLR loss), each one run of num_steps iterations with every gradient averaged over eot_iter forwards, each on the whole batch.  Returns
     (x_adv, robust) with the flags ANDed and, per sample, the first fooling point - as APGD_T combines its runs.  The DLR loss reads the three
-    largest logits: `nclass` (default: read off one clean forward) must be at least 3.  norm: 'Linf' or 'L2', for both runs."""
+    largest logits: `nclass` (default: read off one clean forward) must be at least 3.  norm: 'Linf' or 'L2', for both runs.  n_restarts and seed as in
+    APGD, for both runs (seed None: each run draws its own)."""
     eot_iter = int(eot_iter)
     if eot_iter < 1:
         raise ValueError("APGD_Rand needs eot_iter >= 1, got %d" % eot_iter)
-    kw = _norm_kw(norm)
+    kw = dict(_norm_kw(norm), **_restarts_kw(n_restarts, seed))
     x0 = inputs.detach()
     if nclass is None:
         with torch.no_grad():
@@ -335,7 +398,7 @@ def APGD_Rand(model, args, inputs, targets, num_steps, eot_iter=20, nclass=None,
 # ---------------------------------------------------------------------------------------------------------
 # APGD in the L1 threat model (Croce & Hein 2021, "Mind the box"): doors of their own - APGD(norm="L1") stays refused.  One run, no
 # momentum, the sparse sign step, the exact projection onto ball and box, the sparsity / step-size checkpoints.
-# The large-radius warm-up, restarts, EOT and L1 inside Cascade / Rand are NOT here (L1 Square: Square_L1 below, section 21).
+# The large-radius warm-up, EOT and L1 inside Cascade / Rand are NOT here; restarts: DESIGN.md section 24 (L1 Square: Square_L1 below, section 21).
 # ---------------------------------------------------------------------------------------------------------
 def _f32c(v, dtype):
     """The float32 constant v in `dtype`: the constants of the L1 run are float32 ones in every dtype."""
@@ -412,7 +475,14 @@ def _l1_step(x, g, x0, step, topk, eps):
     return z, dict(j=j, tau=tau_bits.view(dt).reshape(B), m=m, lam=lam, u=u.reshape(x.shape))
 
 
-def _apgd_l1_host(model, x0, x_init, y, n_iter, eps, loss, t=None, trace=None):
+def _apgd_l1_host(model, x0, x_init, y, n_iter, eps, loss, t=None, trace=None, n_restarts=1, seed=None, noise=None, target_index=0):
+    """_apgd_l1_host_run from x_init and - n_restarts > 1 - from the unprojected starts x0 + n of the later restarts
+    (_apgd_host_restarts), which share `trace`."""
+    return _apgd_host_restarts(lambda xs: _apgd_l1_host_run(model, x0, xs, y, n_iter, eps, loss, t, trace), x0, x_init, eps, "L1",
+                               n_restarts, seed, noise, target_index)
+
+
+def _apgd_l1_host_run(model, x0, x_init, y, n_iter, eps, loss, t=None, trace=None):
     """Plumbing path for CPU tensors (opt-in): the iteration of engine.apgd_l1_loop in plain torch ops, in the input's dtype, with
     sort-based selection and projection.  x_init is the unprojected start x0 + n.  `trace`, a list, receives one dict of clones per
     iteration (the start point first)."""
@@ -466,31 +536,36 @@ def _apgd_l1_host(model, x0, x_init, y, n_iter, eps, loss, t=None, trace=None):
     return torch.where(robust.view(shape), x0, x_best_adv), robust, loss_best
 
 
-def APGD_L1(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None):
+def APGD_L1(model, args, inputs, targets, num_steps, loss='ce', y_target=None, noise=None, n_restarts=1, seed=None, target_index=0):
     """One APGD run in the L1 threat model (radius args.epsilon, num_steps iterations) on loss 'ce', 'dlr' or 'dlr_t' (targeted at
     `y_target`).  Returns (x_adv, robust) as APGD does.  The start is P(x0 + n), n a standard normal draw per element (`noise=` injects n)
     and P the exact projection onto the L1 ball intersected with the box; the step is the sparse sign step followed by P; the
     checkpoints adapt a per-sample sparsity and step size.  The public ensemble's large-radius warm-up
-    (3 eps -> 2 eps -> eps), restarts and EOT are not built."""
+    (3 eps -> 2 eps -> eps) and EOT are not built.  n_restarts, seed and target_index as in APGD: restart r >= 1
+    starts at P(x0 + n) for a fresh n drawn on the device."""
     x0 = inputs.detach()
     eps = float(args.epsilon)
     n = torch.randn_like(x0) if noise is None else noise.to(x0.device, x0.dtype)
     x_init = x0 + n
+    rkw = _apgd_restart_kw(x0, n_restarts, seed)  # empty for one restart: the calls below are then the ones they always were
+    if rkw:
+        rkw = dict(rkw, target_index=int(target_index))
     if runtime.require_device(x0, "APGD_L1"):
-        x_adv, robust, _ = engine.apgd_l1_loop(model, x0, x_init, targets, num_steps, eps, loss, y_target)
+        x_adv, robust, _ = engine.apgd_l1_loop(model, x0, x_init, targets, num_steps, eps, loss, y_target, **rkw)
     else:
-        x_adv, robust, _ = _apgd_l1_host(model, x0, x_init, targets, num_steps, eps, loss, y_target)
+        x_adv, robust, _ = _apgd_l1_host(model, x0, x_init, targets, num_steps, eps, loss, y_target, **rkw)
     return x_adv, robust
 
 
-def APGD_T_L1(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None, order=None):
+def APGD_T_L1(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None, order=None, n_restarts=1, seed=None):
     """Targeted L1-APGD on the DLR loss: one run per target class as APGD_T takes them, each on the whole batch; the flags are ANDed over
-    the runs and, per sample, the first fooling point is kept."""
+    the runs and, per sample, the first fooling point is kept.  n_restarts and seed as in APGD_T."""
     x0 = inputs.detach()
     n_t = min(int(n_target_classes), int(nclass) - 1)
     order = _class_order(model, x0, n_t, "APGD_T_L1", order)
-    return _first_fooling(x0, (APGD_L1(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise)
-                               for j in range(1, n_t + 1)))
+    rkw = _apgd_restart_kw(x0, n_restarts, seed)  # one seed for all target classes; class j keys its draws by target_index = j
+    return _first_fooling(x0, (APGD_L1(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise,
+                                       **(dict(rkw, target_index=j) if rkw else {})) for j in range(1, n_t + 1)))
 
 
 def _class_order(model, x0, n_t, what, order=None):
@@ -508,18 +583,20 @@ def _class_order(model, x0, n_t, what, order=None):
     return torch.sort(z, dim=1, descending=True, stable=True)[1][:, :n_t + 1]
 
 
-def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None, order=None, norm="Linf"):
+def APGD_T(model, args, inputs, targets, num_steps, nclass, n_target_classes=9, noise=None, order=None, norm="Linf", n_restarts=1, seed=None):
     """Targeted APGD on the DLR loss: one run per target class, the 2nd ... (n_target_classes + 1)-th class of the clean logits (at most
     nclass - 1 of them), each on the whole batch - samples fooled by an earlier target are carried along, which keeps one shape (one captured
     graph) for all runs.  Returns (x_adv, robust) with the flags ANDed over the runs and, per sample, the first fooling point.  `order`
     [B, n_t + 1]: the class order of the clean logits if the caller has it already - the clean forward is then skipped.  norm: 'Linf' or
-    'L2', for every run; the class order does not know the norm."""
+    'L2', for every run; the class order does not know the norm.  n_restarts > 1: every target class runs its
+    restarts, restart r >= 1 of the j-th class from the draw keyed by eeadv.fabstart.seed_of(seed, j, r); seed None draws one, once."""
     kw = _norm_kw(norm)
     x0 = inputs.detach()
     n_t = min(int(n_target_classes), int(nclass) - 1)
     order = _class_order(model, x0, n_t, "APGD_T", order)
-    return _first_fooling(x0, (APGD(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise, **kw)
-                               for j in range(1, n_t + 1)))
+    rkw = _apgd_restart_kw(x0, n_restarts, seed)  # one seed for all target classes; class j keys its draws by target_index = j
+    return _first_fooling(x0, (APGD(model, args, inputs, targets, num_steps, 'dlr_t', order[:, j].contiguous(), noise, **kw,
+                                    **(dict(rkw, target_index=j) if rkw else {})) for j in range(1, n_t + 1)))
 
 
 # ---------------------------------------------------------------------------------------------------------

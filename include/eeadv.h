@@ -296,6 +296,36 @@ int ee_apgd_book_f32(const float *loss, const int *pred, float *fstate, int *ist
 int ee_apgd_select_f32(float *x, float *g, float *x_best, float *g_best, float *x_best_adv, const int *flags, int *counter, int B,
                        int64_t per_sample, void *stream);
 
+/* ---- APGD restarts, ee_apgd_start.hip: the two launches a restart adds, both outside the captured iterations, one
+ * workgroup of 512 threads per sample in each.  Both record under EE_K_PGD_STEP.
+ *
+ * The start point of restart r >= 1, written into x (which must not alias x0): the distribution of the run's own restart 0.  With t a draw
+ * of per_sample elements, every operation one f32 rounding in the order written:
+ *     EE_FAB_METRIC_LINF  x_i = clamp(x0_i + eps * t_i, 0, 1),  t = 2 u - 1 with u the 24-bit uniform; one pass, no norm
+ *     EE_FAB_METRIC_L2    n = (float) sqrt(sum_i t_i^2) - the sum in double in the order of ee_apgd_step_l2_f32's, rounded to float once -,
+ *                         s = eps / (n + 1e-12f),  x_i = clamp(x0_i + t_i * s, 0, 1),  t standard normal; n not finite: the row is x0
+ *     EE_FAB_METRIC_L1    x_i = x0_i + t_i, NOT clamped,  t standard normal; one pass (the run's ee_l1_proj_f32 follows)
+ * noise [B, per_sample] not NULL: t = noise.  noise NULL: t is drawn from Philox4x32-10 keyed by `seed` on stream 16, one call per group of
+ * four elements under the counter (b << 32) | (element >> 2) - row b's draw depends on (seed, b, element) alone - the normals being the two
+ * Box-Muller pairs of ee_pgd_init_rng_f32 with scale 1.  `path` (EE_PATH_*): the resident path keeps the L2 draw in registers between the
+ * norm pass and the write pass, the streaming one reads or draws it again; 128-bit accesses when per_sample % 4 == 0 and x, x0, noise are
+ * 16-byte aligned: the same bits from all four.  per_sample >= 1; eps < 0 or NaN, a metric or path outside its three values: EE_ERR_SHAPE;
+ * B == 0 launches nothing. */
+int ee_apgd_start_f32(float *x, const float *x0, const float *noise, int64_t B, int64_t per_sample, float eps, int metric, uint64_t seed,
+                      int path, void *stream);
+
+/* The union across restarts, after restart r's iterations (first != 0: r is restart 0).  robust_run [B] / loss_best_run [B] / x_best_adv are
+ * the finished run's (istate row EE_APGD_I_ROBUST, fstate row EE_APGD_F_LOSS_BEST); adv_all [B, per_sample], robust_all [B] (int),
+ * loss_all [B] are cumulative.  Sample b:
+ *     first:  robust_all = robust_run;  loss_all = loss_best_run;  adv_all[b] = x_best_adv[b] if robust_run == 0
+ *     else:   if robust_all != 0 && robust_run == 0: adv_all[b] = x_best_adv[b], robust_all = 0;
+ *             loss_all = loss_best_run > loss_all ? loss_best_run : loss_all                      (a NaN never replaces a number)
+ * A row that is fooled already is never written again - it keeps the point of the FIRST restart that fooled it; a row never fooled is
+ * never written at all.  Rows are copied as bits, 16 bytes at a time where both row starts are 16-byte aligned.  adv_all must not alias
+ * x_best_adv.  B == 0 launches nothing. */
+int ee_apgd_merge_f32(float *adv_all, int *robust_all, float *loss_all, const float *x_best_adv, const int *robust_run,
+                      const float *loss_best_run, int64_t B, int64_t per_sample, int first, void *stream);
+
 /* ---- APGD in the L1 threat model (Croce & Hein 2021, "Mind the box"; one run, no momentum, no EOT), ee_apgd_l1.hip ----
  * State next to the APGD run's (x, x0, g, x_best, g_best, x_best_adv, fstate rows EE_APGD_F_STEP / _LOSS_BEST, istate rows
  * EE_APGD_I_ROBUST / _FLAGS, counter, sched), all in device memory:
@@ -1110,7 +1140,7 @@ int ee_cascade_resolve_f32(const uint8_t *robust, const int64_t *id, const float
  * Optional built-in timing of the last launch of each kernel family (HIP events on `stream`).
  * Off by default; bench.py switches it on outside graph capture to measure kernel durations live.
  * ------------------------------------------------------------------------------------------- */
-#define EE_K_PGD_STEP 0
+#define EE_K_PGD_STEP 0 /* ee_pgd_step_f32; also ee_apgd_start_f32 and ee_apgd_merge_f32 (once per restart, outside every captured loop) */
 #define EE_K_FRONTEND_FWD 1
 #define EE_K_FRONTEND_BWD 2
 #define EE_K_EDGE_FWD 3

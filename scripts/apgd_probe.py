@@ -8,7 +8,12 @@ the initial state).  The APGD-T share: per run j of the targets, the fraction of
 already fooled; its mean over the runs (weighted by each run's time, and unweighted) is the share of APGD-T's time that went to
 samples whose verdict was settled, because every run carries the whole batch (median of three timed runs per target).  The networks are untrained: labels are their own clean predictions, so clean accuracy is 100 %.
 
-    python scripts/apgd_probe.py [reps]      -> a few text lines, then one JSON line per model
+--restarts measures, on `resnet18` only and in place of the APGD-T part, an APGD-CE run of 2 restarts beside the
+others - its time per iteration is (t100 - t20) / 160, the same graph replayed twice as often - and the two launches a restart adds, alone:
+the start launch (100 rows of 12288 elements, the kernel's own draw, Linf and L2, both paths) and the merge launch (every row copied, and
+none).
+
+    python scripts/apgd_probe.py [reps] [--restarts]     -> a few text lines, then one JSON line per model
 """
 import json
 import os
@@ -27,7 +32,11 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("apgd_probe: needs a ROCm device (a time taken on the host says nothing)")
-    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
+    argv = sys.argv[1:]
+    restarts = "--restarts" in argv
+    if restarts:
+        argv.remove("--restarts")
+    reps = int(argv[0]) if argv else 7
     dev = torch.device("cuda", 0)
     eps = 16 / 255
 
@@ -45,7 +54,7 @@ def main():
     def median(v):
         return sorted(v)[len(v) // 2]
 
-    for name in ("resnet18", "resnet18_EE_square"):
+    for name in ("resnet18",) if restarts else ("resnet18", "resnet18_EE_square"):
         torch.manual_seed(0)
         if name == "resnet18":
             m = M.make_resnet(18, "tiny")
@@ -58,6 +67,8 @@ def main():
         with torch.no_grad():
             y = m(x).argmax(1)
         runs = {"pgd": lambda k: A.PGD(m, Args, x, y, k, 2 / 255), "apgd_ce": lambda k: A.APGD(m, Args, x, y, k, "ce")}
+        if restarts:
+            runs["apgd_ce_r2"] = lambda k: A.APGD(m, Args, x, y, k, "ce", n_restarts=2, seed=1)
         for fn in runs.values():  # captures and warm-up of both lengths
             for k in (100, 20, 100, 20):
                 fn(k)
@@ -71,10 +82,38 @@ def main():
         for n in runs:
             t100, t20 = median(ms[(n, 100)]), median(ms[(n, 20)])
             out[n + "_ms_100"], out[n + "_ms_20"] = round(t100, 3), round(t20, 3)
-            out[n + "_iter_ms"] = round((t100 - t20) / 80, 4)
-            out[n + "_iter_ms_spread"] = [round((a - b) / 80, 4) for a, b in zip(sorted(ms[(n, 100)]), sorted(ms[(n, 20)]))][::max(reps - 1, 1)]
+            per = 160 if n == "apgd_ce_r2" else 80
+            out[n + "_iter_ms"] = round((t100 - t20) / per, 4)
+            out[n + "_iter_ms_spread"] = [round((a - b) / per, 4) for a, b in zip(sorted(ms[(n, 100)]), sorted(ms[(n, 20)]))][::max(reps - 1, 1)]
         out["apgd_over_pgd"] = round(out["apgd_ce_iter_ms"] / out["pgd_iter_ms"], 4)
         out["apgd_extra_us_per_iter"] = round(1e3 * (out["apgd_ce_iter_ms"] - out["pgd_iter_ms"]), 1)
+        if restarts:
+            xs_ = torch.empty_like(x)
+            for metric in ("Linf", "L2"):
+                for path in ("resident", "streaming"):
+                    launch = lambda: [ops.apgd_start_(xs_, x, eps, metric, seed=1, path=path) for _ in range(50)]
+                    launch()
+                    torch.cuda.synchronize()
+                    out["start_%s_%s_us" % (metric.lower(), path)] = round(1e3 * median([timed(launch) for _ in range(reps)]) / 50, 2)
+            rob_all, loss_all = torch.ones(100, dtype=torch.int32, device=dev), torch.zeros(100, device=dev)
+            loss_run = torch.ones(100, device=dev)
+            for what, flag in (("copy", 0), ("idle", 1)):  # first = 1 with every row fooled copies every row; with none it copies nothing
+                rob_run = torch.full((100,), flag, dtype=torch.int32, device=dev)
+                launch = lambda: [ops.apgd_merge_(xs_, rob_all, loss_all, x, rob_run, loss_run, True) for _ in range(50)]
+                launch()
+                torch.cuda.synchronize()
+                out["merge_%s_us" % what] = round(1e3 * median([timed(launch) for _ in range(reps)]) / 50, 2)
+            out["apgd_r2_over_r1_iter"] = round(out["apgd_ce_r2_iter_ms"] / out["apgd_ce_iter_ms"], 4)
+            out["apgd_r2_once_ms"] = round(out["apgd_ce_r2_ms_100"] - 200 * out["apgd_ce_r2_iter_ms"], 3)  # what a 2-restart run pays once
+            out["apgd_r1_once_ms"] = round(out["apgd_ce_ms_100"] - 100 * out["apgd_ce_iter_ms"], 3)
+            print("%s: APGD-CE with 2 restarts %.4f ms/iter (x%.4f of one run's %.4f, spread %s); start launch Linf %.1f / %.1f us, L2 %.1f / %.1f us "
+                  "(resident / streaming); merge launch %.1f us copying every row, %.1f us copying none; paid once per call: %.3f ms with 2 "
+                  "restarts, %.3f ms with one" % (name, out["apgd_ce_r2_iter_ms"], out["apgd_r2_over_r1_iter"], out["apgd_ce_iter_ms"],
+                                                  out["apgd_ce_iter_ms_spread"], out["start_linf_resident_us"], out["start_linf_streaming_us"],
+                                                  out["start_l2_resident_us"], out["start_l2_streaming_us"], out["merge_copy_us"],
+                                                  out["merge_idle_us"], out["apgd_r2_once_ms"], out["apgd_r1_once_ms"]), flush=True)
+            print(json.dumps(out), flush=True)
+            continue
         # APGD-T, run by run, as utils.attacks.APGD_T does it (the flags are read on the host here, which the attack itself never does)
         n_t, k = 9, 20
         with torch.no_grad():
