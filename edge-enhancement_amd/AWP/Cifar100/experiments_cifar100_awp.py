@@ -123,7 +123,8 @@ def main(argv=None):
     """experiments_cifar100_awp.py:138-269"""
     args = parse_config_file(make_parser().parse_args(argv))
     if args.attack_method != 'PGD' and args.attack_method not in trainer.EVAL_METHODS:
-        raise NotImplementedError("--attack_method %s: validation runs PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T, APGD+FAB+Square, Cascade, APGD-DLR, Rand or Cascade-Rand" % args.attack_method)  # experiments_cifar100_awp.py:374-380
+        raise NotImplementedError("--attack_method %s: validation runs %s or %s" % (args.attack_method, ", ".join(('PGD',) + trainer.EVAL_METHODS[:-1]),
+                                                                                    trainer.EVAL_METHODS[-1]))  # experiments_cifar100_awp.py:374-380
     driver.data_source(args.data, SPEC)  # an unusable --data fails here, before a model is built
     trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
     trainer.fab_restarts_for(args)  # and a --fab_restarts on a method that runs no FAB

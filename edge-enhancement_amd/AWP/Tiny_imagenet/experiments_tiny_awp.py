@@ -132,7 +132,8 @@ def main(argv=None):
     args = parse_config_file(make_parser().parse_args(argv))
     if args.attack_method != 'PGD' and args.attack_method not in trainer.EVAL_METHODS:
         raise SystemExit("--attack_method %s: %s; validation runs PGD" % (args.attack_method, AA_UNAVAILABLE) if args.attack_method == 'AA'
-                         else "--attack_method %s: the AWP driver validates with PGD, APGD-CE, APGD-T, APGD, Square, APGD+Square, FAB-T, APGD+FAB+Square, Cascade, APGD-DLR, Rand or Cascade-Rand" % args.attack_method)
+                         else "--attack_method %s: the AWP driver validates with %s or %s"
+                         % (args.attack_method, ", ".join(('PGD',) + trainer.EVAL_METHODS[:-1]), trainer.EVAL_METHODS[-1]))
     driver.data_source(args.data, SPEC)  # an unusable --data fails here, before a model is built
     trainer.eot_iter_for(args)  # so does an --eot_iter the chosen attack cannot honour
     trainer.fab_restarts_for(args)  # and a --fab_restarts on a method that runs no FAB

@@ -20,25 +20,22 @@ import torch
 
 import utils.attacks as A
 
-from . import ops, runtime
+from . import methods, ops, runtime
 
-STAGES = ("APGD-CE", "APGD-T", "FAB-T", "Square")
-
-
-def _fab_restarts_kw(args):
-    """What args.fab_restarts (default 1) adds to the FAB-T stage's call: nothing for one restart."""
-    n = int(getattr(args, "fab_restarts", 1) or 1)
-    if n < 1:
-        raise ValueError("fab_restarts must be at least 1, got %d" % n)
-    return {} if n == 1 else {"n_restarts": n}
+STAGES = methods.PLANS["Cascade"].members
 
 
-def _apgd_restarts_kw(args):
-    """What args.apgd_restarts (default 1) adds to the APGD stages' calls: nothing for one restart."""
-    n = int(getattr(args, "apgd_restarts", 1) or 1)
-    if n < 1:
-        raise ValueError("apgd_restarts must be at least 1, got %d" % n)
-    return {} if n == 1 else {"n_restarts": n}
+def _stages(members, ctx):
+    """[(name, fn)] of `members` (eeadv.methods), the stage named as its member; fn(model, args, x, y, order) -> (x_adv, robust) runs it on one
+    full batch with `ctx`, which holds what the builder read from ITS args, plus the batch's `order`."""
+    def stage(member):
+        return lambda model, a, x, y, order: methods.MEMBERS[member](model, a, x, y, types.SimpleNamespace(order=order, **vars(ctx)))
+    return [(member, stage(member)) for member in members]
+
+
+def _restarts(args):
+    """The APGD and FAB restart counts of args (default 1; DESIGN.md sections 24, 23) as the context's keywords: nothing for one restart."""
+    return {"akw": methods.restarts_kw(args, "apgd_restarts", "apgd_restarts"), "rkw": methods.restarts_kw(args, "fab_restarts", "fab_restarts")}
 
 
 def default_stages(args, num_steps, n_class, n_target_classes=9, norm="Linf"):
@@ -46,49 +43,28 @@ def default_stages(args, num_steps, n_class, n_target_classes=9, norm="Linf"):
     being the class order of the clean logits [B, n_t + 1] (the targets of APGD-T and FAB-T: no clean forward of their own).  norm: 'Linf'
     (the default: the calls made before the parameter existed) or 'L2' - every stage then runs in the L2 ball of radius args.epsilon
     (DESIGN.md sections 16 - 18), so evaluate(..., stages=default_stages(..., norm="L2")) is the L2 `standard` cascade."""
-    fab_iters = int(getattr(args, "fab_iters", 100))
-    queries = int(getattr(args, "square_queries", 5000))
-    kw = A._norm_kw(norm)  # empty for Linf
-    rkw = _fab_restarts_kw(args)  # empty for one restart
-    akw = _apgd_restarts_kw(args)  # likewise
-    return [
-        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", **kw, **akw)),
-        ("APGD-T", lambda model, a, x, y, order: A.APGD_T(model, a, x, y, num_steps, n_class, n_target_classes, order=order, **kw, **akw)),
-        ("FAB-T", lambda model, a, x, y, order: A.FAB_T(model, a, x, y, n_class, fab_iters, n_target_classes, order=order, **kw, **rkw)[:2]),
-        ("Square", lambda model, a, x, y, order: A.Square(model, a, x, y, queries, **kw)[:2]),
-    ]
+    return _stages(STAGES, methods.context(args, num_steps, n_class, nkw=A._norm_kw(norm), n_target_classes=n_target_classes, **_restarts(args)))
 
 
 def l1_stages(args, num_steps, n_class, n_target_classes=9):
     """[(name, fn)] of the `standard` order in the L1 threat model, radius args.epsilon: APGD-L1-CE, APGD-T-L1, FAB-T-L1, Square-L1 through
     the L1 doors of utils.attacks (DESIGN.md sections 19 to 21), so evaluate(..., stages=l1_stages(...)) is the L1 `standard` cascade.
     default_stages(norm="L1") stays refused."""
-    fab_iters = int(getattr(args, "fab_iters", 100))
-    queries = int(getattr(args, "square_queries", 5000))
-    rkw = _fab_restarts_kw(args)  # empty for one restart
-    akw = _apgd_restarts_kw(args)  # likewise
-    return [
-        ("APGD-L1-CE", lambda model, a, x, y, order: A.APGD_L1(model, a, x, y, num_steps, "ce", **akw)),
-        ("APGD-T-L1", lambda model, a, x, y, order: A.APGD_T_L1(model, a, x, y, num_steps, n_class, n_target_classes, order=order, **akw)),
-        ("FAB-T-L1", lambda model, a, x, y, order: A.FAB_T_L1(model, a, x, y, n_class, fab_iters, n_target_classes, order=order, **rkw)[:2]),
-        ("Square-L1", lambda model, a, x, y, order: A.Square_L1(model, a, x, y, queries)[:2]),
-    ]
+    return _stages(methods.PLANS["APGD-L1+FAB+Square"].members,
+                   methods.context(args, num_steps, n_class, n_target_classes=n_target_classes, **_restarts(args)))
 
 
 def rand_stages(args, num_steps, eot_iter=None, norm="Linf"):
     """[(name, fn)] of the public ensemble's `rand` order for randomised defences: APGD-CE, then APGD-DLR on its survivors, every gradient
     averaged over eot_iter forwards (default args.eot_iter, else 20).  norm: 'Linf' or 'L2', for both stages
     (DESIGN.md section 16)."""
+    plan = methods.PLANS["Cascade-Rand"]
     kw = A._norm_kw(norm)  # empty for Linf
     E = eot_iter if eot_iter is not None else getattr(args, "eot_iter", None)
-    E = 20 if E is None else int(E)
+    E = plan.eot if E is None else int(E)
     if E < 1:
         raise ValueError("the rand stages need eot_iter >= 1, got %d" % E)
-    akw = _apgd_restarts_kw(args)  # empty for one restart
-    return [
-        ("APGD-CE", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "ce", eot_iter=E, **kw, **akw)),
-        ("APGD-DLR", lambda model, a, x, y, order: A.APGD(model, a, x, y, num_steps, "dlr", eot_iter=E, **kw, **akw)),
-    ]
+    return _stages(plan.members, methods.context(args, num_steps, None, E, kw, methods.restarts_kw(args, "apgd_restarts", "apgd_restarts")))
 
 
 class _Rows:

@@ -27,7 +27,7 @@ import torch.optim as optim
 
 from utils.helper import AverageMeter, adjust_learning_rate, adjust_learning_rate_1, parse_config_file, save_checkpoint, set_seed
 
-from . import ddp, runtime, trainer
+from . import ddp, methods, runtime, trainer
 
 
 def make_parser(description, default_data="synthetic", with_local_rank=False):
@@ -267,7 +267,7 @@ def validate(val_loader, model, criterion, args, device, num_steps, step_size, l
         add_square = Add_Square(channels=spec["shape"][0], size=args.cize, epsilon=args.epsilon, n_queries=args.n_queries)
     if trainer.apgd_restarts_for(args):
         _log(' * {0}: APGD, {1} restarts per run, each on the whole batch'.format(args.attack_method, int(args.apgd_restarts)), log_dir)
-    if args.attack_method in trainer.FAB_U_METHODS + trainer.L1_FAB_U_METHODS + (trainer.CUSTOM_METHOD,):
+    if methods.runs(args.attack_method, methods.FAB_U_MEMBERS):
         # untargeted FAB takes one backward pass per class and iteration: say so before the first batch
         _log(' * {0}: K = {1} classes, {1} backward passes per iteration, {2} iterations'.format(
             args.attack_method, spec["num_classes"], int(getattr(args, 'fab_iters', 100))) + _restarts_tag(args), log_dir)

@@ -11,7 +11,7 @@ import weakref
 import torch
 import torch.nn as nn
 
-from eeadv import runtime
+from eeadv import methods, runtime
 from utils import attacks as A
 from utils.helper import accuracy
 
@@ -669,10 +669,9 @@ def eot_iter_for(args):
     e = getattr(args, 'eot_iter', None)
     if e is not None and int(e) < 1:
         raise ValueError("--eot_iter must be at least 1, got %d" % int(e))
-    if args.attack_method in ('Rand', CASCADE_RAND_METHOD):
-        return 20 if e is None else int(e)
-    if args.attack_method in ('APGD-CE', 'APGD-DLR'):
-        return 1 if e is None else int(e)
+    plan = methods.plan_of(args.attack_method)
+    if plan.eot_explicit:
+        return plan.eot if e is None else int(e)
     if e is not None and int(e) > 1:
         raise NotImplementedError("--eot_iter %d with --attack_method %s: EOT is built for APGD-CE, APGD-DLR, Rand and Cascade-Rand only - not for "
                                   "APGD-T, FAB-T, Square, their composites, Cascade or the reference's own attacks" % (int(e), args.attack_method))
@@ -683,32 +682,22 @@ def fab_restarts_for(args):
     """{} or {'n_restarts': N}: what args.fab_restarts (--fab_restarts; None / absent: 1) adds to the FAB calls of args.attack_method
     (DESIGN.md section 23).  One restart adds nothing - the calls stay the ones made before the option existed.  A method that runs no FAB
     stops here on N != 1 instead of ignoring it, as eot_iter_for does."""
-    n = getattr(args, 'fab_restarts', None)
-    n = 1 if n is None else int(n)
-    if n < 1:
-        raise ValueError("--fab_restarts must be at least 1, got %d" % n)
-    if n == 1:
-        return {}
-    if args.attack_method not in FAB_RESTART_METHODS:
+    kw = methods.restarts_kw(args, 'fab_restarts', '--fab_restarts')
+    if kw and not methods.runs(args.attack_method, methods.FAB_MEMBERS):
         raise NotImplementedError("--fab_restarts %d with --attack_method %s: restarts are built for FAB only - %s - not for APGD, Square or the "
-                                  "reference's own attacks" % (n, args.attack_method, ", ".join(FAB_RESTART_METHODS)))
-    return {'n_restarts': n}
+                                  "reference's own attacks" % (kw['n_restarts'], args.attack_method, ", ".join(FAB_RESTART_METHODS)))
+    return kw
 
 
 def apgd_restarts_for(args):
     """{} or {'n_restarts': N}: what args.apgd_restarts (--apgd_restarts; None / absent: 1) adds to the APGD calls of args.attack_method
     (DESIGN.md section 24).  One restart adds nothing - the calls stay the ones made before the option existed.  A method that runs no
     APGD stops here on N != 1 instead of ignoring it, as fab_restarts_for does."""
-    n = getattr(args, 'apgd_restarts', None)
-    n = 1 if n is None else int(n)
-    if n < 1:
-        raise ValueError("--apgd_restarts must be at least 1, got %d" % n)
-    if n == 1:
-        return {}
-    if args.attack_method not in APGD_RESTART_METHODS:
+    kw = methods.restarts_kw(args, 'apgd_restarts', '--apgd_restarts')
+    if kw and not methods.runs(args.attack_method, methods.APGD_MEMBERS):
         raise NotImplementedError("--apgd_restarts %d with --attack_method %s: restarts are built for APGD only - %s - not for Square, for FAB "
-                                  "(--fab_restarts) or the reference's own attacks" % (n, args.attack_method, ", ".join(APGD_RESTART_METHODS)))
-    return {'n_restarts': n}
+                                  "(--fab_restarts) or the reference's own attacks" % (kw['n_restarts'], args.attack_method, ", ".join(APGD_RESTART_METHODS)))
+    return kw
 
 
 L2_MESSAGE = ("the L2 threat model is built for APGD-CE, APGD-T, APGD, APGD-DLR, Rand and Cascade-Rand only - L2 Square and L2 FAB are different "
@@ -724,7 +713,7 @@ def norm_for(args):
         return 'Linf'
     if norm != 'L2':
         raise ValueError("--norm must be Linf or L2, got %r; %s" % (norm, L2_MESSAGE))
-    if args.attack_method not in L2_METHODS:
+    if not methods.plan_of(args.attack_method).l2:
         raise NotImplementedError("--norm L2 with --attack_method %s: %s" % (args.attack_method, L2_MESSAGE))
     return 'L2'
 
@@ -733,7 +722,7 @@ def norm_tag(args):
     """What a validation log line carries after its numbers: nothing for Linf (the lines stay as they were), ' [norm L2]' for L2, and
     ' [norm L1]' for the L1 methods, whose threat model is in their name (--norm stays refused with them, by norm_for)."""
     if norm_for(args) == 'Linf':
-        return ' [norm L1]' if args.attack_method in L1_METHODS + L1_FAB_U_METHODS else ''
+        return ' [norm L1]' if methods.plan_of(args.attack_method).l1 else ''
     return ' [norm L2]'
 
 
@@ -760,147 +749,46 @@ def attack_for_validation(model, args, input, target, device, num_steps, step_si
             tl = torch.fmod(target + off, n_class)
         return A.CWLinfAttack(x=input, y=target, model=model, magnitude=args.epsilon, previous_p=None, max_eps=args.epsilon,
                               max_iters=20, target=tl, n_class=n_class, cur_device=device)[0]
-    if args.attack_method in APGD_METHODS:
-        # not in the reference's drivers (they call the `autoattack` package): APGD-CE, APGD-T on the DLR loss, or CE then T with the
-        # flags ANDed and the first fooling point kept.  num_steps iterations per run; the step size is APGD's own.
-        if targeted:
-            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
-        x_adv, robust = None, None
-        if args.attack_method in ('APGD-CE', 'APGD'):
-            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', eot_iter=eot_iter, **nkw, **akw)
-        if args.attack_method in ('APGD-T', 'APGD'):
-            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class, **nkw, **akw)
-            if x_adv is None:
-                return xt
-            x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
-        return x_adv
-    if args.attack_method in L1_METHODS:
-        # APGD in the L1 threat model, radius args.epsilon: CE, T on the DLR loss, or CE then T with the flags ANDed and
-        # the first fooling point kept; FAB-L1-T and APGD-L1+FAB add the minimum-norm attack (section 20), Square-L1 and APGD-L1+FAB+Square the black-box one (section 21).  The methods carry their norm in the name; eot_iter_for and norm_for have refused --eot_iter / --norm.
-        if targeted:
-            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
-        if args.attack_method in L1_SQUARE_METHODS:
-            # Square in the L1 threat model, args.square_queries forwards per sample at most: alone, or as the last
-            # member of the L1 ensemble (APGD-L1-CE, APGD-L1-T, FAB-L1-T, Square-L1) - whole batch, flags ANDed, the first fooling point kept
-            queries = int(getattr(args, 'square_queries', 5000))
-            if args.attack_method == 'Square-L1':
-                return A.Square_L1(model, args, input, target, queries)[0]
-            fab_iters = int(getattr(args, 'fab_iters', 100))
-            return A._first_fooling(input.detach(), (A.APGD_L1(model, args, input, target, num_steps, 'ce', **akw),
-                                                     A.APGD_T_L1(model, args, input, target, num_steps, n_class, **akw),
-                                                     A.FAB_T_L1(model, args, input, target, n_class, fab_iters, **rkw)[:2],
-                                                     A.Square_L1(model, args, input, target, queries)[:2]))[0]
-        if args.attack_method in L1_FAB_METHODS:
-            # FAB-T in the L1 threat model, args.fab_iters iterations per target class, thresholded at args.epsilon:
-            # alone, or after APGD-L1-CE and APGD-L1-T - the L1 ensemble minus Square, flags ANDed, the first fooling point kept
-            fab_iters = int(getattr(args, 'fab_iters', 100))
-            if args.attack_method == 'FAB-L1-T':
-                return A.FAB_T_L1(model, args, input, target, n_class, fab_iters, **rkw)[0]
-            return A._first_fooling(input.detach(), (A.APGD_L1(model, args, input, target, num_steps, 'ce', **akw),
-                                                     A.APGD_T_L1(model, args, input, target, num_steps, n_class, **akw),
-                                                     A.FAB_T_L1(model, args, input, target, n_class, fab_iters, **rkw)[:2]))[0]
-        x_adv, robust = None, None
-        if args.attack_method in ('APGD-L1-CE', 'APGD-L1'):
-            x_adv, robust = A.APGD_L1(model, args, input, target, num_steps, 'ce', **akw)
-        if args.attack_method in ('APGD-L1-T', 'APGD-L1'):
-            xt, rt = A.APGD_T_L1(model, args, input, target, num_steps, n_class, **akw)
-            if x_adv is None:
-                return xt
-            x_adv = torch.where((robust & ~rt).view((-1,) + (1,) * (input.dim() - 1)), xt, x_adv)
-        return x_adv
-    if args.attack_method in FAB_U_METHODS + L1_FAB_U_METHODS:
-        # untargeted FAB: one run of args.fab_iters iterations towards the closest boundary among all classes, n_class
-        # backward passes per iteration, thresholded at args.epsilon - FAB-U in Linf, FAB-L1-U in L1 (the norm is in the name)
-        if targeted:
-            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
-        fab_iters = int(getattr(args, 'fab_iters', 100))
-        if args.attack_method in L1_FAB_U_METHODS:
-            return A.FAB_L1(model, args, input, target, fab_iters, **rkw)[0]
-        return A.FAB(model, args, input, target, fab_iters, **rkw)[0]
-    if args.attack_method == CUSTOM_METHOD:
-        # the reference's `custom` version (utils/aa.py: attacks_to_run = ['apgd-ce', 'fab']): APGD-CE, then untargeted FAB - FAB-U's call -
-        # each on the whole batch, flags ANDed, the first fooling point kept.  Linf only: norm_for / eot_iter_for have refused the rest.
-        if targeted:
-            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
-        fab_iters = int(getattr(args, 'fab_iters', 100))
-        return A._first_fooling(input.detach(), (A.APGD(model, args, input, target, num_steps, 'ce', **akw),
-                                                 A.FAB(model, args, input, target, fab_iters, **rkw)[:2]))[0]
-    if args.attack_method in SQUARE_METHODS:
-        # Square (black-box, args.square_queries forwards per sample at most), alone or after APGD-CE and APGD-T: flags ANDed, the first
-        # fooling point kept
-        if targeted:
-            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
-        shape = (-1,) + (1,) * (input.dim() - 1)
-        x_adv, robust = None, None
-        if args.attack_method == 'APGD+Square':
-            x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', **akw)
-            xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class, **akw)
-            x_adv = torch.where((robust & ~rt).view(shape), xt, x_adv)
-            robust = robust & rt
-        xs, rs, _ = A.Square(model, args, input, target, int(getattr(args, 'square_queries', 5000)))
-        if x_adv is None:
-            return xs
-        return torch.where((robust & ~rs).view(shape), xs, x_adv)
-    if args.attack_method in FAB_METHODS:
-        # FAB-T (minimum-norm, args.fab_iters iterations per target class, thresholded at args.epsilon), alone or between APGD-T and Square -
-        # the order of AutoAttack's `standard` version: flags ANDed, the first fooling point kept
-        if targeted:
-            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
-        shape = (-1,) + (1,) * (input.dim() - 1)
-        fab_iters = int(getattr(args, 'fab_iters', 100))
-        if args.attack_method == 'FAB-T':
-            return A.FAB_T(model, args, input, target, n_class, fab_iters, **rkw)[0]
-        x_adv, robust = A.APGD(model, args, input, target, num_steps, 'ce', **akw)
-        xt, rt = A.APGD_T(model, args, input, target, num_steps, n_class, **akw)
-        x_adv = torch.where((robust & ~rt).view(shape), xt, x_adv)
-        robust = robust & rt
-        xf, rf, _ = A.FAB_T(model, args, input, target, n_class, fab_iters, **rkw)
-        x_adv = torch.where((robust & ~rf).view(shape), xf, x_adv)
-        robust = robust & rf
-        xs, rs, _ = A.Square(model, args, input, target, int(getattr(args, 'square_queries', 5000)))
-        return torch.where((robust & ~rs).view(shape), xs, x_adv)
-    if args.attack_method in RAND_METHODS:
-        # APGD on the untargeted DLR loss, or the `rand` order for randomised defences: APGD-CE then APGD-DLR, every gradient averaged over
-        # eot_iter forwards
-        if targeted:
-            raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
-        if args.attack_method == 'APGD-DLR':
-            return A.APGD(model, args, input, target, num_steps, 'dlr', eot_iter=eot_iter, **nkw, **akw)[0]
-        return A.APGD_Rand(model, args, input, target, num_steps, eot_iter, n_class, **nkw, **akw)[0]
-    if args.attack_method == CASCADE_RAND_METHOD:
-        raise NotImplementedError("--attack_method Cascade-Rand regroups the survivors of a whole split: it runs as eeadv.cascade.evaluate over the "
-                                  "loader (driver.validate_cascade), not batch by batch")
-    if args.attack_method == CASCADE_METHOD:
-        raise NotImplementedError("--attack_method Cascade regroups the survivors of a whole split: it runs as eeadv.cascade.evaluate over the "
-                                  "loader (driver.validate_cascade), not batch by batch")
-    raise NotImplementedError
+    # everything else is not in the reference's drivers (they call the `autoattack` package): the plan of eeadv.methods names the attacks
+    # the method runs, each on the whole batch.  num_steps iterations per APGD run; the step size is APGD's own.
+    plan = methods.PLANS.get(args.attack_method)
+    if plan is None:
+        raise NotImplementedError
+    if plan.cascade:
+        raise NotImplementedError("--attack_method %s regroups the survivors of a whole split: it runs as eeadv.cascade.evaluate over the "
+                                  "loader (driver.validate_cascade), not batch by batch" % args.attack_method)
+    if targeted:
+        raise NotImplementedError("--attack_method %s evaluates untargeted robustness only" % args.attack_method)
+    ctx = methods.context(args, num_steps, n_class, None if plan.eot is None else eot_iter, nkw, akw, rkw)
+    found = [methods.MEMBERS[member](model, args, input, target, ctx) for member in plan.members]
+    if len(found) == 1:
+        return found[0][0]  # the attack's own tensor: no launch behind a single attack
+    return A._first_fooling(input.detach(), found)[0]  # flags ANDed, the first fooling point kept
 
 
-APGD_METHODS = ('APGD-CE', 'APGD-T', 'APGD')
-SQUARE_METHODS = ('Square', 'APGD+Square')
-FAB_METHODS = ('FAB-T', 'APGD+FAB+Square')
-RAND_METHODS = ('APGD-DLR', 'Rand')  # Rand: APGD-CE then APGD-DLR with EOT, the `rand` order for randomised defences
-CASCADE_RAND_METHOD = 'Cascade-Rand'  # the same two, APGD-DLR on the survivors of APGD-CE only, over the whole split
-CASCADE_METHOD = 'Cascade'  # the same four attacks, each on the samples the ones before it left standing (eeadv.cascade)
-CASCADE_METHODS = (CASCADE_METHOD, CASCADE_RAND_METHOD)
-L2_METHODS = APGD_METHODS + RAND_METHODS + (CASCADE_RAND_METHOD,)  # every attack in them is an APGD run: --norm L2
-# what the AWP drivers validate with next to PGD
-L1_FAB_METHODS = ('FAB-L1-T', 'APGD-L1+FAB')  # FAB-T in L1, alone or after the two L1-APGD runs
-L1_SQUARE_METHODS = ('Square-L1', 'APGD-L1+FAB+Square')  # Square in L1, alone or as the last member of the full L1 ensemble (section 21)
-# the L1 attacks through doors of their own (DESIGN.md sections 19 to 21); not in L2_METHODS
-L1_METHODS = ('APGD-L1-CE', 'APGD-L1-T', 'APGD-L1') + L1_FAB_METHODS + L1_SQUARE_METHODS
+# The method tuples, read off the table in its order (the drivers and the tests read them).
+CASCADE_METHOD, CASCADE_RAND_METHOD, CUSTOM_METHOD = 'Cascade', 'Cascade-Rand', 'Custom'
+APGD_METHODS = methods.select(lambda p: not p.cascade and set(p.members) <= {'APGD-CE', 'APGD-T'})  # APGD-CE, APGD-T, or CE then T
+SQUARE_METHODS = methods.select(lambda p: not p.cascade and p.members[-1] == 'Square' and 'FAB-T' not in p.members)  # Square, alone or after the two
+FAB_METHODS = methods.select(lambda p: not p.cascade and 'FAB-T' in p.members)  # FAB-T, alone or between APGD-T and Square
+RAND_METHODS = methods.select(lambda p: not p.cascade and p.members[-1] in ('APGD-DLR', 'Rand'))  # the untargeted DLR loss
+CASCADE_METHODS = methods.select(lambda p: p.cascade)
+L2_METHODS = methods.select(lambda p: p.l2)  # every attack in them is an APGD run: --norm L2
+L1_FAB_METHODS = methods.select(lambda p: 'FAB-T-L1' in p.members and 'Square-L1' not in p.members)
+L1_SQUARE_METHODS = methods.select(lambda p: 'Square-L1' in p.members)  # section 21
 # untargeted FAB in tuples of their own: FAB_METHODS and L1_METHODS keep their members
-FAB_U_METHODS = ('FAB-U',)
-L1_FAB_U_METHODS = ('FAB-L1-U',)  # L1 by its name, like L1_METHODS: the ' [norm L1]' tag, --norm refused
-# what honours --fab_restarts: every method that runs a FAB
-CUSTOM_METHOD = 'Custom'  # the reference's `custom` version: APGD-CE then untargeted FAB (utils/aa.py); Linf only
+L1_METHODS = methods.select(lambda p: p.l1 and not set(p.members) & set(methods.FAB_U_MEMBERS))
+FAB_U_METHODS = methods.select(lambda p: p.members == ('FAB-U',))
+L1_FAB_U_METHODS = methods.select(lambda p: p.members == ('FAB-L1-U',))
+EVAL_METHODS = tuple(methods.PLANS)  # what the AWP drivers validate with next to PGD
+# what honours --fab_restarts and --apgd_restarts (section 24): every method that runs a FAB, or an APGD.  The two stay
+# written out, in the order their refusals have always listed them; what they hold is checked against the table.
 FAB_RESTART_METHODS = ('FAB-T', 'FAB-U', 'FAB-L1-T', 'FAB-L1-U', 'APGD+FAB+Square', 'APGD-L1+FAB', 'APGD-L1+FAB+Square', CASCADE_METHOD,
                        CUSTOM_METHOD)
-# what honours --apgd_restarts: every method that runs an APGD
 APGD_RESTART_METHODS = (APGD_METHODS + RAND_METHODS + ('APGD+Square', 'APGD+FAB+Square', 'APGD-L1-CE', 'APGD-L1-T', 'APGD-L1', 'APGD-L1+FAB',
                                                        'APGD-L1+FAB+Square') + CASCADE_METHODS + (CUSTOM_METHOD,))
-EVAL_METHODS = (APGD_METHODS + SQUARE_METHODS + FAB_METHODS + RAND_METHODS + CASCADE_METHODS + L1_METHODS + FAB_U_METHODS + L1_FAB_U_METHODS
-                + (CUSTOM_METHOD,))
+assert set(FAB_RESTART_METHODS) == {m for m in EVAL_METHODS if methods.runs(m, methods.FAB_MEMBERS)}
+assert set(APGD_RESTART_METHODS) == {m for m in EVAL_METHODS if methods.runs(m, methods.APGD_MEMBERS)}
 
 
 def validate_batch(model, criterion, args, input, target, device, num_steps, step_size, n_class):
