@@ -14,6 +14,14 @@ ReLU:
                                       statistics gives the mask bit for bit;
   ops.bn_relu_pool_fwd                the one-pass stem: maxpool(relu(z)) == relu(maxpool(z)), so `y > 0` is the ReLU mask at each window's
                                       argmax and the one-byte `code` names its position; the float64 side gathers bn1(conv1 x) there.
+
+The EVAL-mode attack route (Branch(..., eval_route=True)) forms its ReLUs in two more places, inside functional.EvalBasicBlockFn /
+EvalDownBlockFn, where models.bn_act and models.block_tail never run:
+
+  functional._eval_conv_fwd           returns relu(bn(conv x) [+ res]): the mask is `output > 0` (bn1's ReLU, or the block's end);
+  ops.conv3x3s2_pair_bn_eval_fwd      the first output carries bn1's ReLU (`output > 0`); the second, the shortcut's BatchNorm, has none.
+
+Their forward order is the stock path's - one bn_act behind conv1, one block_tail per block - so replay() consumes them unchanged.
 """
 import torch
 import torch.nn.functional as F
@@ -23,15 +31,35 @@ ALL_STOCK = frozenset(("bn", "pool", "head", "conv", "stem", "dense", "conv3", "
 N_RELU = {18: 17, 50: 49}
 
 
-def make_net(models, depth, stock, dt=torch.float32, monkeypatch=None):
-    """make_resnet(depth, 'tiny') from seed 21 in train mode, with models._STOCK = stock from here on: until the test ends when `monkeypatch`
-    is given, otherwise until the caller puts it back"""
+def move_batchnorms(net, seed):
+    """every BatchNorm away from its initial (mean 0, variance 1, weight 1, bias 0), drawn as test_gpu_evalfuse._resnet draws them: eval mode
+    reads the running statistics, and the initial state cannot tell `invstd * gamma` from `gamma` or see a missing beta"""
+    gen = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for mod in net.modules():
+            if isinstance(mod, torch.nn.BatchNorm2d):
+                dev, n = mod.weight.device, mod.num_features
+                mod.running_mean.copy_((torch.randn(n, generator=gen) * 0.1).to(dev))
+                mod.running_var.copy_((torch.rand(n, generator=gen) + 0.5).to(dev))
+                mod.weight.copy_((torch.rand(n, generator=gen) + 0.5).to(dev))
+                mod.bias.copy_((torch.randn(n, generator=gen) * 0.1).to(dev))
+    return net
+
+
+def make_net(models, depth, stock, dt=torch.float32, monkeypatch=None, train=True):
+    """make_resnet(depth, 'tiny') from seed 21 in train mode (train=False: in eval mode, every BatchNorm moved away from its initial state
+    first - move_batchnorms, seed 21), with models._STOCK = stock from here on: until the test ends when `monkeypatch` is given, otherwise
+    until the caller puts it back"""
     if monkeypatch is not None:
         monkeypatch.setattr(models, "_STOCK", stock)
     else:
         models._STOCK = stock
     torch.manual_seed(21)
-    return models.make_resnet(depth, "tiny").to(DEV).to(dt).train()
+    net = models.make_resnet(depth, "tiny").to(DEV)
+    if not train:
+        move_batchnorms(net, 21)
+    net = net.to(dt)
+    return net.train() if train else net.eval()
 
 
 def body_run(models, depth, x, dl, stock, dt=torch.float32, monkeypatch=None):
@@ -62,14 +90,18 @@ def train_pre_mask(c1, sm, si, gamma, beta):
 
 class Branch:
     """record() during the fp32 run, replay() during the float64 run, restore() afterwards.  `masks` holds, in forward order, one entry per
-    ReLU: an activation or a boolean mask, or ("stem", y > 0, argmax index) for the one-pass stem.  `calls` counts what the recorders saw."""
+    ReLU: an activation or a boolean mask, or ("stem", y > 0, argmax index) for the one-pass stem.  `calls` counts what the recorders saw.
+    eval_route: also record the two places where the eval-mode attack route forms a ReLU (`calls` then has "eval_conv" and "eval_pair")."""
 
-    def __init__(self, monkeypatch, models):
-        from eeadv import ops
-        self.mp, self.models, self.ops = monkeypatch, models, ops
+    def __init__(self, monkeypatch, models, eval_route=False):
+        from eeadv import functional, ops
+        self.mp, self.models, self.ops, self.fn, self.eval_route = monkeypatch, models, ops, functional, eval_route
         self.orig = {"bn_act": models.bn_act, "block_tail": models.block_tail, "stem_pool": models.stem_pool, "stem_bn_pool": models.stem_bn_pool,
                      "train_pre": ops.wino3x3_bn_train_pre, "pool_fwd": ops.bn_relu_pool_fwd, "ce_head": ops.ce_pool_linear_bwd}
         self.masks, self.calls = [], {"train_pre": 0, "pool_fwd": 0, "pool_fwd_xa": 0, "ce_head": 0}
+        if eval_route:
+            self.orig.update(eval_conv=functional._eval_conv_fwd, eval_pair=ops.conv3x3s2_pair_bn_eval_fwd)
+            self.calls.update(eval_conv=0, eval_pair=0)
 
     def record(self):
         masks, calls, nested, o = self.masks, self.calls, [0], self.orig
@@ -106,6 +138,21 @@ class Branch:
         def rec_ce_head(*a, **k):
             calls["ce_head"] += 1
             return o["ce_head"](*a, **k)
+
+        def rec_eval_conv(x, w, bn, res):  # relu(bn(conv x) [+ res]): bn1's ReLU, or the block's end
+            out = o["eval_conv"](x, w, bn, res)
+            masks.append(out.detach().clone())
+            calls["eval_conv"] += 1
+            return out
+
+        def rec_eval_pair(*a, **k):  # (relu(bn1(conv3x3s2 x)), bn_ds(conv1x1s2 x)): the second output has no ReLU
+            out = o["eval_pair"](*a, **k)
+            masks.append(out[0].detach().clone())
+            calls["eval_pair"] += 1
+            return out
+        if self.eval_route:
+            self.mp.setattr(self.fn, "_eval_conv_fwd", rec_eval_conv)
+            self.mp.setattr(self.ops, "conv3x3s2_pair_bn_eval_fwd", rec_eval_pair)
         self.mp.setattr(self.models, "bn_act", rec_bn_act)
         self.mp.setattr(self.models, "block_tail", rec_tail)
         self.mp.setattr(self.ops, "wino3x3_bn_train_pre", rec_train_pre)
@@ -119,6 +166,9 @@ class Branch:
         self.mp.setattr(self.ops, "wino3x3_bn_train_pre", self.orig["train_pre"])
         self.mp.setattr(self.ops, "bn_relu_pool_fwd", self.orig["pool_fwd"])
         self.mp.setattr(self.ops, "ce_pool_linear_bwd", self.orig["ce_head"])
+        if self.eval_route:
+            self.mp.setattr(self.fn, "_eval_conv_fwd", self.orig["eval_conv"])
+            self.mp.setattr(self.ops, "conv3x3s2_pair_bn_eval_fwd", self.orig["eval_pair"])
 
     def replay(self):
         """-> the list of masks still to be consumed (empty after a float64 run that met every ReLU of the fp32 one)"""
@@ -177,19 +227,37 @@ def replayed_body_gradients(monkeypatch, depth, B, seed, fp32_stock=frozenset(("
     return names, logits32, g32, logits64, g64
 
 
-def replayed_attack_gradient(monkeypatch, B, seed, kind="ce_sum", fp32_stock=frozenset(), affine_seed=None):
+class LogitCotangent:
+    """an engine loss spec whose d loss / d logits is a given tensor: its `kind` is no cross-entropy kind, so engine._body_input_grad takes
+    the branch APGD's DLR loss and FAB's logit differences take - model(x) under attack_forward(), then PoolLinearFn's backward"""
+    kind, payload = "cotangent", None
+
+    def __init__(self, dl):
+        self.dl = dl
+
+    def dlogits(self, logits):
+        assert logits.shape == self.dl.shape
+        return self.dl
+
+
+def replayed_attack_gradient(monkeypatch, B, seed, kind="ce_sum", fp32_stock=frozenset(), affine_seed=None, mode="train", cotangent=None):
     """ResNet-18's INPUT gradient on the route the attack loop takes - engine.input_gradient in train mode, i.e. body_pre under
     functional.attack_forward() and ResNet.head_grad - and the float64 stock modules on the branch that run took, differentiating
     F.cross_entropy(logits64, y, reduction = sum | mean) with respect to the input.  affine_seed: every BatchNorm's weight drawn from
     U(0.5, 1.5) and its bias from N(0, 0.2^2) first - a freshly initialised model has bias 0, where `invstd * gamma` in a ReLU mask
     (x - mean) * (invstd * gamma) + beta > 0 could be any positive number without a test noticing.
+    mode="eval": the model in eval mode (make_net(train=False): every BatchNorm moved away from its initial state), the recorders of the
+    eval route on.  cotangent: dl [B, 200] - the gradient of <logits, dl> instead of the cross-entropy's, through LogitCotangent on the fp32
+    side and torch.autograd.grad(logits64, x64, dl.double()) on the float64 side (`kind` is then unused).
     models._STOCK is left at fp32_stock until the test ends (monkeypatch restores it).
-    -> dict(x, y, net32 (after its one forward), twin (a deep copy of net32 from before it), net64, g32, g64, logits64, calls, n_relu)"""
+    -> dict(x, y, net32 (after its one forward), twin (a deep copy of net32 from before it), net64, g32, g64, logits64, calls, n_relu, spec)"""
     import copy
     from eeadv import engine, models
+    assert mode in ("train", "eval")
+    train = mode == "train"
     g = torch.Generator(device="cpu").manual_seed(seed)
     x, y = torch.rand(B, 3, 64, 64, generator=g).to(DEV), torch.randint(0, 200, (B,), generator=g).to(DEV)
-    net32 = make_net(models, 18, fp32_stock, monkeypatch=monkeypatch)
+    net32 = make_net(models, 18, fp32_stock, monkeypatch=monkeypatch, train=train)
     if affine_seed is not None:
         ga = torch.Generator(device="cpu").manual_seed(affine_seed)
         with torch.no_grad():
@@ -198,17 +266,21 @@ def replayed_attack_gradient(monkeypatch, B, seed, kind="ce_sum", fp32_stock=fro
                     m.weight.copy_(torch.rand(m.weight.shape, generator=ga) + 0.5)
                     m.bias.copy_(torch.randn(m.bias.shape, generator=ga) * 0.2)
     twin = copy.deepcopy(net32)
-    br = Branch(monkeypatch, models)
+    spec = engine.LossSpec(kind, y) if cotangent is None else LogitCotangent(cotangent)
+    br = Branch(monkeypatch, models, eval_route=not train)
     br.record()
-    g32 = engine.input_gradient(net32, x.clone(), engine.LossSpec(kind, y)).detach()
+    g32 = engine.input_gradient(net32, x.clone(), spec).detach()
     n_relu = len(br.masks)
     todo = br.replay()
-    net64 = make_net(models, 18, ALL_STOCK, torch.float64, monkeypatch)
+    net64 = make_net(models, 18, ALL_STOCK, torch.float64, monkeypatch, train=train)
     net64.load_state_dict(twin.state_dict())
     x64 = x.double().requires_grad_(True)
     logits64 = net64(x64)
-    (g64,) = torch.autograd.grad(F.cross_entropy(logits64, y, reduction="sum" if kind == "ce_sum" else "mean"), x64)
+    if cotangent is None:
+        (g64,) = torch.autograd.grad(F.cross_entropy(logits64, y, reduction="sum" if kind == "ce_sum" else "mean"), x64)
+    else:
+        (g64,) = torch.autograd.grad(logits64, x64, cotangent.double())
     assert not todo and n_relu == N_RELU[18], (len(todo), n_relu)
     br.restore()
     monkeypatch.setattr(models, "_STOCK", fp32_stock)  # what net32 and its twin run under; monkeypatch puts the session's value back
-    return dict(x=x, y=y, net32=net32, twin=twin, net64=net64, g32=g32, g64=g64, logits64=logits64.detach(), calls=br.calls, n_relu=n_relu)
+    return dict(x=x, y=y, net32=net32, twin=twin, net64=net64, g32=g32, g64=g64, logits64=logits64.detach(), calls=br.calls, n_relu=n_relu, spec=spec)
