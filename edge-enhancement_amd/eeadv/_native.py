@@ -74,6 +74,8 @@ SIGNATURES = {
     "ee_apgd_start_f32": [c_p, c_p, c_p, c_l, c_l, c_f, c_i, c_u64, c_i, c_p],
     # the union across restarts: adv_all, robust_all, loss_all, x_best_adv, robust_run, loss_best_run, B, per_sample, first, stream
     "ee_apgd_merge_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_l, c_i, c_p],
+    # the perturbation check: x_adv, x0, B, per_sample, norms, range, n_nan, path, stream
+    "ee_pert_check_f32": [c_p, c_p, c_l, c_l, c_p, c_p, c_p, c_i, c_p],
     # g_acc, g, loss_acc, loss, loss_mean, k, E, B, per_sample, stream
     "ee_apgd_eot_acc_f32": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_l, c_l, c_p],
     # x_best, x_new, x0, seed, B, C, H, W, eps, stream

@@ -14,6 +14,7 @@ Host reads: the host decides when to pop, so it reads a pool's count once per ap
 compaction="hip" (the default on a ROCm device) runs the pools as HIP kernels (csrc/ee_cascade.hip); compaction="torch" (the default for
 CPU tensors, what --no-cuda takes) states the same staging with index_select, and feeds identical batches to identical loops.
 """
+import collections
 import types
 
 import torch
@@ -24,13 +25,25 @@ from . import methods, ops, runtime
 
 STAGES = methods.PLANS["Cascade"].members
 
+# A stage description: a member of eeadv.methods and, optionally, the restart count of that stage alone (DESIGN.md section 26).  A bare
+# member name is Stage(name): no count of its own, the stage takes what _restarts(args) gave the whole list.
+Stage = collections.namedtuple("Stage", "member restarts", defaults=(None,))
+
 
 def _stages(members, ctx):
-    """[(name, fn)] of `members` (eeadv.methods), the stage named as its member; fn(model, args, x, y, order) -> (x_adv, robust) runs it on one
-    full batch with `ctx`, which holds what the builder read from ITS args, plus the batch's `order`."""
-    def stage(member):
-        return lambda model, a, x, y, order: methods.MEMBERS[member](model, a, x, y, types.SimpleNamespace(order=order, **vars(ctx)))
-    return [(member, stage(member)) for member in members]
+    """[(name, fn)] of `members` (eeadv.methods; names or Stage tuples), the stage named as its member; fn(model, args, x, y, order) ->
+    (x_adv, robust) runs it on one full batch with `ctx`, which holds what the builder read from ITS args, plus the batch's `order`.  A
+    Stage with a restart count runs with that count in the place of ctx's APGD and FAB counts (one restart: no keyword, as everywhere)."""
+    def stage(member, restarts):
+        own = vars(ctx)
+        if restarts is not None:
+            if int(restarts) < 1:
+                raise ValueError("stage %s: restarts must be at least 1, got %d" % (member, int(restarts)))
+            kw = {} if int(restarts) == 1 else {"n_restarts": int(restarts)}
+            own = dict(own, akw=kw, rkw=kw)
+        return lambda model, a, x, y, order: methods.MEMBERS[member](model, a, x, y, types.SimpleNamespace(order=order, **own))
+    members = [Stage(m) if isinstance(m, str) else Stage(*m) for m in members]
+    return [(s.member, stage(s.member, s.restarts)) for s in members]
 
 
 def _restarts(args):
@@ -65,6 +78,73 @@ def rand_stages(args, num_steps, eot_iter=None, norm="Linf"):
     if E < 1:
         raise ValueError("the rand stages need eot_iter >= 1, got %d" % E)
     return _stages(plan.members, methods.context(args, num_steps, None, E, kw, methods.restarts_kw(args, "apgd_restarts", "apgd_restarts")))
+
+
+# ---- the four versions of the reference's utils/aa.py as stage lists (DESIGN.md section 26) -------------------------------------------------
+# version -> norms it exists for.  `plus`: the six attacks of the public ensemble's plus order, the untargeted ones with 5 restarts;
+# `custom`: the reference's own setting (attacks_to_run = ['apgd-ce', 'fab'], 2 restarts each), here on the survivors.
+AA_VERSIONS = {"standard": ("Linf", "L2", "L1"), "plus": ("Linf", "L2"), "rand": ("Linf", "L2"), "custom": ("Linf", "L2")}
+AA_PLUS = (Stage("APGD-CE", 5), Stage("APGD-DLR", 5), Stage("FAB-U", 5), Stage("Square"), Stage("APGD-T", 1), Stage("FAB-T", 1))
+AA_CUSTOM = (Stage("APGD-CE", 2), Stage("FAB-U", 2))
+AA_DLR_CLASSES = 4  # the class count `plus` and `rand` ask for: the DLR loss reads the third and fourth largest logit
+
+
+def aa_stages(args, num_steps, n_class, version, norm="Linf"):
+    """[(name, fn)] of `version` ('standard', 'plus', 'rand', 'custom') of the reference's utils/aa.py under `norm`, radius args.epsilon:
+        standard  default_stages (Linf, L2) / l1_stages (L1), unchanged - args.apgd_restarts / args.fab_restarts as there
+        plus      APGD-CE (5 restarts), APGD-DLR (5), FAB-U (5), Square, APGD-T (1), FAB-T (1); Linf, L2
+        rand      rand_stages: APGD-CE, APGD-DLR, every gradient over args.eot_iter forwards (default 20); Linf, L2
+        custom    APGD-CE (2), FAB-U (2); Linf, L2
+    with args.n_target_classes (default 9) targets at most.  A combination outside the table stops with the nearest one that exists; `plus`
+    and `rand` stop below four classes."""
+    if version not in AA_VERSIONS:
+        raise ValueError("version must be one of %s, got %r" % (", ".join(AA_VERSIONS), version))
+    if norm not in AA_VERSIONS["standard"]:
+        raise ValueError("norm must be one of %s, got %r" % (", ".join(AA_VERSIONS["standard"]), norm))
+    if norm not in AA_VERSIONS[version]:
+        raise NotImplementedError("version %s exists under %s, not under %s; the nearest supported combination is version standard under %s"
+                                  % (version, " and ".join(AA_VERSIONS[version]), norm, norm))
+    if version in ("plus", "rand") and int(n_class) < AA_DLR_CLASSES:
+        raise ValueError("version %s runs APGD-DLR, whose loss reads the third and fourth largest logit: it needs at least %d classes and this "
+                         "model has %d" % (version, AA_DLR_CLASSES, int(n_class)))
+    n_t = min(int(getattr(args, "n_target_classes", 9)), int(n_class) - 1)
+    if version == "standard":
+        return l1_stages(args, num_steps, n_class, n_t) if norm == "L1" else default_stages(args, num_steps, n_class, n_t, norm)
+    if version == "rand":
+        return rand_stages(args, num_steps, None, norm)
+    return _stages(AA_PLUS if version == "plus" else AA_CUSTOM,
+                   methods.context(args, num_steps, n_class, nkw=A._norm_kw(norm), n_target_classes=n_t, **_restarts(args)))
+
+
+def individual(model, args, batches, n_class, stages, device=None, before_member=None):
+    """Every stage of `stages` on ALL samples of `batches`, one member after the other (the --individual mode of utils/aa.py): {name:
+    (adv [n, ...], robust [n] bool)}, adv being what the member's door returns for each whole batch.  before_member(name), if given, runs
+    before a member's first batch (the script reseeds there, so that each entry can be reproduced on its own).  The class order of the
+    clean logits is taken once per batch, as the cascade takes it; the model is expected in eval mode."""
+    if iter(batches) is batches:
+        batches = list(batches)
+    K = min(int(getattr(args, "n_target_classes", 9)), int(n_class) - 1) + 1
+    rows = []
+    for x, y in batches:
+        if device is not None:
+            x, y = x.to(device), y.to(device)
+        x, y = x.detach(), y.contiguous()
+        with torch.no_grad():
+            z = model(x)
+        if runtime.require_device(x, "cascade"):
+            order = ops.topk(z.detach().float().contiguous(), None, K)[0]
+        else:
+            order = torch.sort(z, dim=1, descending=True, stable=True)[1][:, :K].contiguous()
+        rows.append((x, y, order))
+    if not rows:
+        raise ValueError("the evaluation needs at least one sample")
+    out = {}
+    for name, fn in stages:
+        if before_member is not None:
+            before_member(name)
+        res = [fn(model, args, x, y, order) for x, y, order in rows]
+        out[name] = (torch.cat([xa.detach() for xa, _ in res]), torch.cat([rb for _, rb in res]))
+    return out
 
 
 class _Rows:
@@ -222,7 +302,8 @@ class _Run:
             self.run_stage(s)
 
 
-def evaluate(model, args, batches, n_class, keep_adv=False, compaction=None, stages=None, num_steps=None, n=None, device=None, batch_size=None):
+def evaluate(model, args, batches, n_class, keep_adv=False, compaction=None, stages=None, num_steps=None, n=None, device=None, batch_size=None,
+             per_stage_adv=False):
     """Runs the cascade over `batches`, a re-iterable of (x [b, ...], y [b] int64) with b <= B = `batch_size` (default: the size of the first
     batch), the one shape the attack loops capture; the model is expected in eval mode.  `n`: the number of samples if known (else the batches are counted
     in a pass of their own); `device`: where the batches are moved to (default: where they are); `num_steps`: APGD's iterations
@@ -233,7 +314,11 @@ def evaluate(model, args, batches, n_class, keep_adv=False, compaction=None, sta
     iteration order; stage 0 = misclassified clean, k = broken by stage k, len(stages) + 1 = survived), stage_names,
     robust_after [per stage: samples still robust after it], rows_attacked [per stage: rows it ran on, padding excluded],
     batches_attacked [per stage] and adv [n, ...] (keep_adv: the clean sample where robust or misclassified clean, else the point that
-    broke it; None otherwise)."""
+    broke it; None otherwise).  per_stage_adv (needs keep_adv): also stage_adv, per stage a namespace (name, ids [k] int64 ascending, adv
+    [k, ...]) of the samples that stage broke and the points that broke them - rows of adv, which is resolved by sample id already: no launch
+    of its own."""
+    if per_stage_adv and not keep_adv:
+        raise ValueError("per_stage_adv reads the kept points: it needs keep_adv=True")
     if iter(batches) is batches:
         batches = list(batches)
     N = int(n) if n is not None else _count_samples(batches)
@@ -264,6 +349,12 @@ def evaluate(model, args, batches, n_class, keep_adv=False, compaction=None, sta
     for s in range(S):
         left -= counts[s + 1]
         robust_after.append(left)
-    return types.SimpleNamespace(n=N, clean_correct=clean_correct, robust=run.robust, stage=run.stage, stage_names=[name for name, _ in stages],
-                                 robust_after=robust_after, rows_attacked=run.rows, batches_attacked=run.runs,
-                                 adv=None if run.adv is None else run.adv.view((N,) + run.shape))
+    res = types.SimpleNamespace(n=N, clean_correct=clean_correct, robust=run.robust, stage=run.stage, stage_names=[name for name, _ in stages],
+                                robust_after=robust_after, rows_attacked=run.rows, batches_attacked=run.runs,
+                                adv=None if run.adv is None else run.adv.view((N,) + run.shape))
+    if per_stage_adv:
+        res.stage_adv = []
+        for s, (name, _) in enumerate(stages):
+            ids = torch.nonzero(run.stage == s + 1).view(-1)
+            res.stage_adv.append(types.SimpleNamespace(name=name, ids=ids, adv=res.adv.index_select(0, ids)))
+    return res

@@ -218,6 +218,13 @@ def with_module_prefix(state):
     return {("module." + k if not k.startswith("module.") else k): v for k, v in state.items()}
 
 
+def load_model_checkpoint(model, path, device):
+    """The weights of a checkpoint file into `model`: (the checkpoint dict, load_state_dict's report).  `module.`-prefixed keys are read as
+    bare ones, and keys the model does not have are ignored - reference EE checkpoints carry dead sobel.* / u2netp.* keys."""
+    ckpt = torch.load(path, map_location=device, weights_only=True)
+    return ckpt, model.load_state_dict(strip_module_prefix(ckpt['state_dict']), strict=False)
+
+
 def validate_cascade(val_loader, model, args, device, num_steps, n_class, log):
     """--attack_method Cascade / Cascade-Rand: eeadv.cascade.evaluate over the whole loader in place of the per-batch loop.  log(line) receives the clean
     accuracy and one `robust accuracy after <stage>` line per stage (percent of this rank's samples).  Returns the final robust accuracy
@@ -347,9 +354,8 @@ def run(spec, build_model, argv=None):
     if args.resume:
         if os.path.isfile(args.resume):
             print("=> loading checkpoint '{}'".format(args.resume))
-            ckpt = torch.load(args.resume, map_location=device, weights_only=True)
+            ckpt, missing = load_model_checkpoint(model, args.resume, device)
             args.start_epoch, best_prec1 = ckpt['epoch'], ckpt['best_prec1']
-            missing = model.load_state_dict(strip_module_prefix(ckpt['state_dict']), strict=False)  # reference EE checkpoints carry dead sobel.* / u2netp.* keys
             print("=> loaded checkpoint '{}' (epoch {}); ignored keys: {}".format(args.resume, ckpt['epoch'], len(missing.unexpected_keys)))
             optimizer.load_state_dict(ckpt['optimizer'])
         else:

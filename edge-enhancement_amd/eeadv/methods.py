@@ -65,7 +65,7 @@ def _fab_t(model, args, x, y, ctx):
 
 
 def _fab_u(model, args, x, y, ctx):
-    return A.FAB(model, args, x, y, ctx.fab_iters, **ctx.rkw)[:2]
+    return A.FAB(model, args, x, y, ctx.fab_iters, **ctx.nkw, **ctx.rkw)[:2]  # the norm reaches it from cascade.aa_stages only (section 26)
 
 
 def _square(model, args, x, y, ctx):

@@ -533,6 +533,54 @@ def apgd_merge_(adv_all, robust_all, loss_all, x_best_adv, robust_run, loss_best
     return adv_all
 
 
+# ---- the perturbation check of an evaluation (ee_pert.hip) ---------------------------------------
+def _pert_check_host(x_adv, x0):
+    """ee_pert_check_f32 restated in numpy float64 for [B, ...] arrays or CPU tensors: (norms [B, 3] float32, range [B, 2] float32,
+    n_nan [B] int32).  d = x_adv - x0 is formed in float32, as the kernel forms it; the sums are numpy's float64 ones (pairwise: not the
+    kernel's order, the same value to within the last bit of the float32 result).  A NaN in d makes the row's three norms NaN; NaN
+    entries of x_adv are skipped by the range, (+inf, -inf) for a row of NaN entries only."""
+    a = np.ascontiguousarray(x_adv.detach().cpu().numpy() if isinstance(x_adv, torch.Tensor) else x_adv, dtype=np.float32)
+    o = np.ascontiguousarray(x0.detach().cpu().numpy() if isinstance(x0, torch.Tensor) else x0, dtype=np.float32)
+    if a.shape != o.shape:
+        raise ValueError("x0 has shape %s, expected %s" % (o.shape, a.shape))
+    B = a.shape[0]
+    a, o = a.reshape(B, -1), o.reshape(B, -1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.abs((a - o).astype(np.float32)).astype(np.float64)
+        bad = np.isnan(d).any(axis=1)
+        norms = np.stack([d.max(axis=1, initial=0.0), np.sqrt((d * d).sum(axis=1)), d.sum(axis=1)], axis=1).astype(np.float32)
+    norms[bad] = np.nan
+    nan = np.isnan(a)
+    rng = np.stack([np.where(nan, np.inf, a).min(axis=1, initial=np.inf), np.where(nan, -np.inf, a).max(axis=1, initial=-np.inf)],
+                   axis=1).astype(np.float32)
+    return norms, rng, nan.sum(axis=1).astype(np.int32)
+
+
+def pert_check(x_adv, x0, path="auto"):
+    """(norms [B, 3], range [B, 2], n_nan [B]) of the points x_adv [B, ...] around the clean samples x0: per sample
+    the Linf, L2 and L1 norm of x_adv - x0 (all NaN if the difference holds a NaN), the minimum and maximum of x_adv over its entries that
+    are no NaN, and the number of those that are.  Device tensors: one launch of ee_pert_check_f32, float32 / float32 / int32 tensors, no
+    host read; path: 'auto', 'resident' (per-sample size <= 12288) or 'streaming', the same bits.  CPU tensors are refused, as everywhere,
+    unless the caller opted into the host plumbing (eeadv.runtime.allow_cpu_plumbing, what --no-cuda does): then _pert_check_host, the same
+    three as tensors."""
+    from . import runtime
+    if tuple(x_adv.shape) != tuple(x0.shape):
+        raise ValueError("x0 has shape %s, expected %s" % (tuple(x0.shape), tuple(x_adv.shape)))
+    if not x_adv.is_cuda and not x0.is_cuda and not runtime.require_device(x_adv, "pert_check"):
+        _sample_path(path, "the perturbation check's")
+        return tuple(torch.from_numpy(v) for v in _pert_check_host(x_adv, x0))
+    B = x_adv.shape[0]
+    pa = _chk(x_adv, torch.float32, "x_adv")
+    p0 = _chk(x0, torch.float32, "x0", x_adv.shape)
+    norms = torch.empty((B, 3), dtype=torch.float32, device=x_adv.device)
+    rng = torch.empty((B, 2), dtype=torch.float32, device=x_adv.device)
+    n_nan = torch.empty(B, dtype=torch.int32, device=x_adv.device)
+    N.check(N.lib.ee_pert_check_f32(pa, p0, B, x_adv.numel() // B if B else 1, _chk(norms, torch.float32, "norms"), _chk(rng, torch.float32, "range"),
+                                    _chk(n_nan, torch.int32, "n_nan"), _sample_path(path, "the perturbation check's"), _stream()),
+            "ee_pert_check_f32")
+    return norms, rng, n_nan
+
+
 # ---- APGD in the L1 threat model (ee_apgd_l1.hip) --------------------------------------------------------------------
 L1_S_LAMBDA, L1_S_H0, L1_S_ACTIVE, L1_S_DIST, L1_S_TAU, L1_S_M, L1_S_J = range(7)  # rows of scal
 L1_SCAL_ROWS = 7

@@ -326,6 +326,18 @@ int ee_apgd_start_f32(float *x, const float *x0, const float *noise, int64_t B, 
 int ee_apgd_merge_f32(float *adv_all, int *robust_all, float *loss_all, const float *x_best_adv, const int *robust_run,
                       const float *loss_best_run, int64_t B, int64_t per_sample, int first, void *stream);
 
+/* ---- The perturbation check of an evaluation, ee_pert.hip: one workgroup of 512 threads per sample, one pass over
+ * x_adv and x0 [B, per_sample].  Records under EE_K_PGD_STEP.  With d_i = x_adv_i - x0_i, rounded once in f32, sample b gets
+ *     norms [B, 3]  max_i |d_i|,  (float) sqrt(sum_i d_i^2),  (float) sum_i |d_i| - both sums in double in the order of
+ *                   ee_apgd_step_l2_f32's; a NaN in d (a NaN in either row, or inf - inf) makes all three NaN
+ *     range [B, 2]  min_i x_adv_i, max_i x_adv_i with the NaN entries skipped; a row of NaN entries only: (+inf, -inf)
+ *     n_nan [B]     the number of NaN entries of x_adv (int)
+ * `path` (EE_PATH_*): the resident path loads the sample into registers before it reduces, the streaming one reduces as it reads;
+ * 128-bit loads when per_sample % 4 == 0 and x_adv, x0 are 16-byte aligned, word by word otherwise: the same bits from all four.
+ * per_sample >= 1; a path outside its three values: EE_ERR_SHAPE; B == 0 launches nothing. */
+int ee_pert_check_f32(const float *x_adv, const float *x0, int64_t B, int64_t per_sample, float *norms, float *range, int *n_nan, int path,
+                      void *stream);
+
 /* ---- APGD in the L1 threat model (Croce & Hein 2021, "Mind the box"; one run, no momentum, no EOT), ee_apgd_l1.hip ----
  * State next to the APGD run's (x, x0, g, x_best, g_best, x_best_adv, fstate rows EE_APGD_F_STEP / _LOSS_BEST, istate rows
  * EE_APGD_I_ROBUST / _FLAGS, counter, sched), all in device memory:
@@ -1140,7 +1152,7 @@ int ee_cascade_resolve_f32(const uint8_t *robust, const int64_t *id, const float
  * Optional built-in timing of the last launch of each kernel family (HIP events on `stream`).
  * Off by default; bench.py switches it on outside graph capture to measure kernel durations live.
  * ------------------------------------------------------------------------------------------- */
-#define EE_K_PGD_STEP 0 /* ee_pgd_step_f32; also ee_apgd_start_f32 and ee_apgd_merge_f32 (once per restart, outside every captured loop) */
+#define EE_K_PGD_STEP 0 /* ee_pgd_step_f32; also ee_apgd_start_f32 and ee_apgd_merge_f32 (once per restart, outside every captured loop) and ee_pert_check_f32 (once per evaluation) */
 #define EE_K_FRONTEND_FWD 1
 #define EE_K_FRONTEND_BWD 2
 #define EE_K_EDGE_FWD 3
