@@ -7,8 +7,11 @@
 // convolution, bias, dropout scale, 2x2 pool (ATen's scan: first maximum wins, a NaN always wins) and ReLU fused, the pooled map and a
 // 2-bit argmax code the only things written; the backward gathers through the codes, applies ATen's threshold rule (the gradient passes
 // unless the output is <= 0, so a NaN output passes it) and runs the transposed convolution.  Exact-f32 fma chains in a fixed order;
-// parity is "logits within 1e-4" through the model tests plus per-kernel tests against ATen.  Only the attack loop (input gradient)
-// runs through those; the parameter gradients of a training step: net2_conv*_wrw_kernel below (round 3).
+// parity is "logits within 1e-4" through the model tests plus per-kernel tests: against ATen on random images (tests/test_gpu_kernels.py),
+// and against float64 on the branch the kernels took on MNIST-like images, where most windows tie exactly (tests/test_gpu_net2.py with
+// tests/net2_reference.py: codes on every decided and exact-tie window, values within a derived fp32 bound, all six gradients, the whole
+// model on the attack loop's route).  The attack loop (input gradient) runs through the forward and backward-data kernels only; the
+// parameter gradients of a training step: net2_conv*_wrw_kernel below (round 3).
 //
 // CNN-body glue, not a row of SURVEY.md section 8.
 #include "ee_bn_math.hpp"

@@ -833,6 +833,32 @@ def gen_awp():
     save("awp", **out)
 
 
+# --------------------------------------------------------------------------
+# 13. Net_2 on MNIST-like images (tests/net2_reference.py: exact 0 background, exact 1.0 strokes): where the
+#     pools tie.  Logits, the input gradient of the CE sum and the winners of both pools (ATen's flat indices)
+# --------------------------------------------------------------------------
+def gen_net2_mnist_like():
+    sys.path.insert(0, os.path.dirname(OUT))
+    from net2_reference import mnist_like
+    from models_mnist.Net2 import Net_2
+    torch.manual_seed(7)
+    net = Net_2().eval()
+    out = {"checksum": state_checksum(net)}
+    x = torch.from_numpy(mnist_like(6, 106)).requires_grad_(True)
+    torch.manual_seed(2)
+    y = torch.randint(0, 10, (6,))
+    logits = net(x)
+    (g,) = torch.autograd.grad(nn.CrossEntropyLoss(reduction="sum")(logits, y), x)
+    with torch.no_grad():
+        p1, i1 = F.max_pool2d(net.conv1(x), 2, return_indices=True)
+        p2, i2 = F.max_pool2d(net.conv2(F.relu(p1)), 2, return_indices=True)
+        again = net.fc2(F.relu(net.fc1(F.relu(p2).view(-1, 4 * 4 * 64))))
+    assert torch.equal(again, logits)  # the recorded winners are the ones the model's own forward took
+    out["x"], out["y"], out["logits"], out["grad"] = x.detach().numpy(), y.numpy(), logits.detach().numpy(), g.numpy()
+    out["pool1_idx"], out["pool2_idx"] = i1.numpy().astype(np.int16), i2.numpy().astype(np.int16)
+    save("net2_mnist_like", **out)
+
+
 if __name__ == "__main__":
     torch.set_num_threads(1)
     gen_kernels()
@@ -847,3 +873,4 @@ if __name__ == "__main__":
     gen_add_square()
     gen_free_at()
     gen_awp()
+    gen_net2_mnist_like()
