@@ -77,10 +77,12 @@ __global__ __launch_bounds__(256) void conv1x1s2_kernel(const float *__restrict_
                 // every load is issued (clamped index, valid address) and masked afterwards: a predicated load becomes a
                 // branch around it, and sixteen branches serialise what should be sixteen loads in flight
                 const int tc = (t0 + u < steps) ? t0 + u : steps - 1;
-                const float keep = (t0 + u < steps) ? 1.0f : 0.0f;
+                const bool live = t0 + u < steps;
                 const float a = ap[static_cast<size_t>(tc) * astride], b = bp[static_cast<size_t>(tc) * bstride];
-                av[u] = cv ? a * keep : 0.0f;
-                bv[u] = pv ? b : 0.0f;
+                // past the last step BOTH operands are zero, by select: a clamped operand that is inf or NaN times a masked 0 would put NaN
+                // (0 * inf) into a whole row or column of the tile, where a direct convolution has none
+                av[u] = (cv && live) ? a : 0.0f;
+                bv[u] = (pv && live) ? b : 0.0f;
             }
         };
         auto fma16 = [&](const float (&av)[16], const float (&bv)[16]) {
