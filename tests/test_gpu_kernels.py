@@ -330,7 +330,8 @@ def test_canny_full_fwd_bwd_vs_oracle_UNPINNED(ops, shape, alpha, low, high):
     wts = ops.EdgeWeights(1.0)
     e = ops.canny_fwd(dev(x), wts, alpha, low, high)
     oe = O.canny_fwd(x, alpha, low, high)
-    # orientation uses atanf (device libm != host libm): a pixel exactly on a 22.5-degree boundary could differ; none may here
+    # orientation uses atanf (device libm != host libm): a pixel within rounding of a 22.5-degree boundary could differ; none does here.
+    # Which pixels are decided, and by what margin, is checked in tests/test_gpu_edge_exact.py (edge_reference: |ori / 45 - rint| + bound < 0.5)
     assert_bitexact(e.cpu().numpy(), oe, "canny edge")
     u = rng.randn(shape[0], 1, shape[2], shape[3]).astype(np.float32)
     g = ops.canny_bwd(dev(x), dev(u), wts, alpha, low, high)
