@@ -11,25 +11,24 @@
 // writes a per-sample scalar that another workgroup of the same launch reads: a projection problem and a commit sample each belong to one
 // workgroup, step only reads the scalars, and commit is the one place that advances the counter (nothing reads it there).
 //
-// The projection.  For v = s w (s the sign of c), c' = |c| and rooms r_i (the distance of p_i to the bound v_i pushes it to),
-// g(lambda) = sum_i |v_i| min(lambda, r_i) is continuous, piecewise linear and non-decreasing; lambda is the smallest value with
-// g(lambda) = c'.  The kernel finds T, the largest float with g(T) < c', by 31 steps over the bit pattern of non-negative floats (one
-// workgroup-wide sum each), and then solves the segment that contains lambda in closed form: lambda = (c' - sum_{r_i <= T} |v_i| r_i) /
-// sum_{r_i > T} |v_i|.  No breakpoint lies strictly between T and lambda, so this IS the segment solve of the sort-based formulation - not a
-// bisection stopped at a tolerance - and every loop has a trip count fixed by D and the launch shape.  All sums are double (products of two
-// floats are exact there) in the one order of ee_sample.hpp, which the resident path (a problem's |w_i| and r_i stay in registers across
-// all passes) and the streaming path (re-read through L2) share, so the two return the same bits.
+// The threat model (Linf; L2; L1, section 20) enters at three launches and nothing else - the projection, the step
+// that rebuilds its deltas, and the commit's distance ||x - x0|| (in double in the same order for L2 and L1): ee_fab_proj_{linf,l2,l1}_f32,
+// ee_fab_step{,_l2,_l1}_f32, ee_fab_commit{,_l2,_l1}_f32, each one template on the Metric.  ee_fab_diff_f32 is shared.
 //
-// The L2 threat model changes the metric at three points and nothing else: ee_fab_proj_l2_f32 (the least-||.||_2
-// delta: delta_i = -sign(v_i) min(mu |v_i|, r_i), g(mu) = sum_i |v_i| min(mu |v_i|, r_i), breakpoints t_i = r_i / |v_i| - the same 31-step
-// search and exact segment solve, mu = (c' - sum_{t_i <= T} |v_i| r_i) / sum_{t_i > T} v_i^2), ee_fab_step_l2_f32 (rebuilds those deltas)
-// and ee_fab_commit_l2_f32 (||x - x0||_2 in double in the same order).  ee_fab_diff_f32 is shared.
-//
-// The L1 threat model enters at the same three points: ee_fab_proj_l1_f32 (the least-||.||_1 delta is a fractional-
-// knapsack fill by descending |v_i|: F(T) = sum_{|v_i| >= T} |v_i| r_i is a non-increasing step function, theta the largest float with
-// F(theta) >= c' - the same 31-step search, no sort - coordinates above theta go to their bounds and those AT theta all take the same
-// fraction phi = (c' - sum_{|v_i| > theta} |v_i| r_i) / sum_{|v_i| = theta} |v_i| r_i of their rooms), ee_fab_step_l1_f32 (rebuilds those
-// deltas from theta and phi) and ee_fab_commit_l1_f32 (||x - x0||_1 in double in the same order).
+// The projection.  For v = s w (s the sign of c), c' = |c| and rooms r_i (the distance of p_i to the bound v_i pushes it to), the least-norm
+// delta onto the hyperplane inside the box is fixed by one scalar, the root of a monotone piecewise function of it:
+//     Linf  delta_i = -sign(v_i) min(lambda, r_i)      g(lambda) = sum_i |v_i| min(lambda, r_i) = c',        breakpoints r_i
+//     L2    delta_i = -sign(v_i) min(mu |v_i|, r_i)    g(mu) = sum_i |v_i| min(mu |v_i|, r_i) = c',          breakpoints t_i = r_i / |v_i|
+//     L1    a fractional-knapsack fill by descending |v_i|: F(T) = sum_{|v_i| >= T} |v_i| r_i is a non-increasing step function, theta the
+//           largest float with F(theta) >= c'; coordinates above theta go to their bounds, those AT theta all take the same fraction
+//           phi = (c' - sum_{|v_i| > theta} |v_i| r_i) / sum_{|v_i| = theta} |v_i| r_i of their rooms
+// Each kernel finds T, the largest float on the near side of the root, by 31 steps over the bit pattern of non-negative floats (one
+// workgroup-wide sum each, no sort), and then solves the segment that contains the root in closed form - lambda = (c' - sum_{r_i <= T}
+// |v_i| r_i) / sum_{r_i > T} |v_i|, mu = (c' - sum_{t_i <= T} |v_i| r_i) / sum_{t_i > T} v_i^2, phi as above.  No breakpoint lies strictly
+// between T and the root, so this IS the segment solve of the sort-based formulation - not a bisection stopped at a tolerance - and every
+// loop has a trip count fixed by D and the launch shape.  All sums are double (products of two floats are exact there) in the one order of
+// ee_sample.hpp, which the resident path (a problem's |w_i| and r_i stay in registers across all passes) and the streaming path (re-read
+// through L2) share, so the two return the same bits.
 //
 // Untargeted FAB keeps all of the above and changes where w and df come from: per iteration one forward, then per
 // class k one backward pass (the logit gradient from ee_fab_diff_f32 with targets = k) and one ee_fab_select_f32 - the dual norm of that
@@ -48,6 +47,7 @@ using namespace ee;
 
 constexpr float kEta = 1.05f, kBeta = 0.9f, kAlphaMax = 0.1f;
 
+enum Metric : int { kLinf = 0, kL2 = 1, kL1 = 2 };  // EE_FAB_METRIC_*: the instances of every kernel and launch below that has an M
 
 // the room of a coordinate at p that v pushes down (v > 0: to 0) or up (v < 0: to 1); 0 where v is 0 or NaN.  Never negative.
 __device__ __forceinline__ float room(float v, float p) { return fmaxf(v > 0.0f ? p : (v < 0.0f ? 1.0f - p : 0.0f), 0.0f); }
@@ -73,176 +73,40 @@ __global__ __launch_bounds__(kBlock) void diff_kernel(const float *__restrict__ 
 }
 
 // ---- the projection ------------------------------------------------------------------------------------------------------------------
-// RES: groups 0 .. kSampleVecs-1 of this thread live in a[] / r[] (zeros past D); otherwise every pass re-reads w and p.
-// The body sees (|w|, room) of every element of the thread in the same order on both paths.
-template <bool RES, bool VEC, class F>
-__device__ __forceinline__ void each_element(const float *__restrict__ w, const float *__restrict__ p, int64_t D, int groups, float s,
-                                             const float (&a)[kSampleElems], const float (&r)[kSampleElems], F body) {
-    if (RES) {
-#pragma unroll
-        for (int k = 0; k < kSampleElems; ++k) body(a[k], r[k]);
-    } else {
-        for (int g = 0; g < groups; ++g) {
-            const int64_t e = group_element(g);
-            float wv[4], pv[4];
-            load4<VEC>(w, e, D, wv);
-            load4<VEC>(p, e, D, pv);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) body(fabsf(wv[j]), room(s * wv[j], pv[j]));
-        }
-    }
-}
+// One workgroup per problem: problem b projects x[b] with c = df[b], problem B + b projects x0[b] with c = df[b] + <w[b], x0[b] - x[b]>.
+// proj_begin and each_element are what the three metrics share - the indexing, pass 1, the two degenerate exits and (|w|, room) of every
+// element in the one order of ee_sample.hpp - and solve_linf / solve_l2 / solve_l1 below are what they do not.
 
-template <bool RES, bool VEC>
-__global__ __launch_bounds__(kSampleBlock) void proj_kernel(const float *__restrict__ x, const float *__restrict__ x0, const float *__restrict__ w,
-                                                          const float *__restrict__ df, int B, int64_t D, float *__restrict__ out) {
-    __shared__ double sh[2 * kSampleWaves];
-    SampleReducer red{sh};
-    const int q = blockIdx.x, b = q < B ? q : q - B;
-    const bool second = q >= B;  // problem B + b projects x0, problem b projects x
-    const float *xr = x + static_cast<int64_t>(b) * D, *x0r = x0 + static_cast<int64_t>(b) * D, *wr = w + static_cast<int64_t>(b) * D;
-    const float *pr = second ? x0r : xr;
-    const int groups = groups_of(D);
-    float *lam_out = out + q, *sgn_out = out + 2 * static_cast<int64_t>(B) + q, *nrm_out = out + 4 * static_cast<int64_t>(B) + q;
-
-    // pass 1: sum |w_i| and sum w_i (x0_i - x_i); the resident path keeps w in a[] and the point in r[]
-    float a[kSampleElems], r[kSampleElems];
-    double sabs = 0.0, dot = 0.0;
-    if (RES) {
-#pragma unroll
-        for (int g = 0; g < kSampleVecs; ++g) {
-            const int64_t e = group_element(g);
-            float wv[4], xv[4], ov[4];
-            load4<VEC>(wr, e, D, wv);
-            load4<VEC>(xr, e, D, xv);
-            load4<VEC>(x0r, e, D, ov);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                sabs += static_cast<double>(fabsf(wv[j]));
-                dot = fma(static_cast<double>(wv[j]), static_cast<double>(ov[j] - xv[j]), dot);
-                a[g * 4 + j] = wv[j];
-                r[g * 4 + j] = second ? ov[j] : xv[j];
-            }
-        }
-    } else {
-        for (int g = 0; g < groups; ++g) {
-            const int64_t e = group_element(g);
-            float wv[4], xv[4], ov[4];
-            load4<VEC>(wr, e, D, wv);
-            load4<VEC>(xr, e, D, xv);
-            load4<VEC>(x0r, e, D, ov);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                sabs += static_cast<double>(fabsf(wv[j]));
-                dot = fma(static_cast<double>(wv[j]), static_cast<double>(ov[j] - xv[j]), dot);
-            }
-        }
-    }
-    sabs = red.sum(sabs);
-    dot = red.sum(dot);
-    const float d = df[b];
-    // every decision below is taken on values all threads of the workgroup hold alike: the early exits are uniform
-    if (!(isfinite(d) && d != 0.0f && isfinite(sabs) && sabs > 0.0)) {  // no hyperplane to project onto: both problems of the sample rest
-        if (threadIdx.x == 0) *lam_out = 0.0f, *sgn_out = 0.0f, *nrm_out = 0.0f;
-        return;
-    }
-    const float c = second ? static_cast<float>(static_cast<double>(d) + dot) : d;
-    const float s = c >= 0.0f ? 1.0f : -1.0f;  // NaN cannot come here: d and dot are finite
-    const float cp = fabsf(c);
-    if (!isfinite(c) || cp == 0.0f) {  // c = 0: the point lies on the hyperplane
-        if (threadIdx.x == 0) *lam_out = 0.0f, *sgn_out = 1.0f, *nrm_out = 0.0f;
-        return;
-    }
-    if (RES) {
-#pragma unroll
-        for (int k = 0; k < kSampleElems; ++k) {
-            const float wv = a[k];
-            r[k] = room(s * wv, r[k]);
-            a[k] = fabsf(wv);
-        }
-    }
-    // g(inf) and the largest room among the coordinates that move
-    double ginf = 0.0, rm = 0.0;
-    each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
-        ginf = fma(static_cast<double>(av), static_cast<double>(rv), ginf);
-        if (av != 0.0f) rm = fmax(rm, static_cast<double>(rv));
-    });
-    ginf = red.sum(ginf);
-    const float rmax = static_cast<float>(red.max(rm));
-    const double cpd = static_cast<double>(cp);
-    if (cpd >= ginf) {  // infeasible inside the box: every coordinate that can move goes to its bound
-        if (threadIdx.x == 0) *lam_out = INFINITY, *sgn_out = s, *nrm_out = rmax;
-        return;
-    }
-    // T: the largest non-negative float with g(T) < c' (g(0) = 0 < c' holds, g(inf) < c' does not)
-    uint32_t T = 0u;
-    for (int bit = 30; bit >= 0; --bit) {
-        const uint32_t cand = T | (1u << bit);
-        const float tf = __uint_as_float(cand);
-        double part = 0.0;
-        each_element<RES, VEC>(wr, pr, D, groups, s, a, r,
-                               [&](float av, float rv) { part = fma(static_cast<double>(av), static_cast<double>(fminf(tf, rv)), part); });
-        if (red.sum(part) < cpd) T = cand;
-    }
-    // the segment (T, next breakpoint]: g(lambda) = S + lambda A there
-    const float tl = __uint_as_float(T);
-    double S = 0.0, A = 0.0;
-    each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
-        if (rv <= tl)
-            S = fma(static_cast<double>(av), static_cast<double>(rv), S);
-        else
-            A += static_cast<double>(av);
-    });
-    S = red.sum(S);
-    A = red.sum(A);
-    const float lam = A > 0.0 ? static_cast<float>((cpd - S) / A) : INFINITY;
-    if (threadIdx.x == 0) *lam_out = lam, *sgn_out = s, *nrm_out = fminf(lam, rmax);
-}
-
-// ---- the L2 projection -----------------------------------------------------------------------------------------------------------------
-// The breakpoint of a coordinate: the f32 quotient, rounded once - the one definition both paths (and the host path) classify by.  A
+// The L2 breakpoint of a coordinate: the f32 quotient, rounded once - the one definition both paths (and the host path) classify by.  A
 // denormal |v_i| overflows it to +inf: that coordinate never saturates.  |v_i| = 0 (its room is 0 too) gives 0: the coordinate counts as
 // saturated from the start and adds exact zeros, so no pass ever forms inf * 0.
 __device__ __forceinline__ float ratio(float a, float r) { return a != 0.0f ? r / a : 0.0f; }
 
-// each_element with the breakpoint: the resident path keeps t[] next to a[] / r[], the streaming path recomputes it from what it re-reads
-template <bool RES, bool VEC, class F>
-__device__ __forceinline__ void each_element_l2(const float *__restrict__ w, const float *__restrict__ p, int64_t D, int groups, float s,
-                                                const float (&a)[kSampleElems], const float (&r)[kSampleElems],
-                                                const float (&t)[kSampleElems], F body) {
-    if (RES) {
-#pragma unroll
-        for (int k = 0; k < kSampleElems; ++k) body(a[k], r[k], t[k]);
-    } else {
-        for (int g = 0; g < groups; ++g) {
-            const int64_t e = group_element(g);
-            float wv[4], pv[4];
-            load4<VEC>(w, e, D, wv);
-            load4<VEC>(p, e, D, pv);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float av = fabsf(wv[j]), rv = room(s * wv[j], pv[j]);
-                body(av, rv, ratio(av, rv));
-            }
-        }
-    }
-}
+struct Problem {
+    const float *wr, *pr;  // the rows of w and of the point this problem projects
+    int64_t D;
+    int groups;
+    float s, cp;  // of a live problem: the sign of c and c' = |c|; v = s w
+};
 
-template <bool RES, bool VEC>
-__global__ __launch_bounds__(kSampleBlock) void proj_l2_kernel(const float *__restrict__ x, const float *__restrict__ x0,
-                                                             const float *__restrict__ w, const float *__restrict__ df, int B, int64_t D,
-                                                             float *__restrict__ out) {
-    __shared__ double sh[2 * kSampleWaves];
-    SampleReducer red{sh};
+// RES: groups 0 .. kSampleVecs-1 of this thread live in a[] / r[] (zeros past D); otherwise every pass re-reads w and p.  BRK (L2): the
+// breakpoint goes with them - the resident path keeps t[] next to a[] / r[] (no division in the 33 passes), the streaming path recomputes
+// it from what it re-reads; without BRK t[] has one element that nothing touches.
+template <bool BRK>
+using Breaks = float[BRK ? kSampleElems : 1];
+
+// False: the problem is degenerate and rest(on_the_hyperplane) has written its rows.  Every thread of the workgroup returns the same, so
+// the caller's early exit is uniform.
+template <bool RES, bool VEC, bool BRK, class Rest>
+__device__ __forceinline__ bool proj_begin(const float *__restrict__ x, const float *__restrict__ x0, const float *__restrict__ w,
+                                                const float *__restrict__ df, int B, int64_t D, SampleReducer &red, Problem &p,
+                                                float (&a)[kSampleElems], float (&r)[kSampleElems], Breaks<BRK> &t, Rest rest) {
     const int q = blockIdx.x, b = q < B ? q : q - B;
     const bool second = q >= B;  // problem B + b projects x0, problem b projects x
     const float *xr = x + static_cast<int64_t>(b) * D, *x0r = x0 + static_cast<int64_t>(b) * D, *wr = w + static_cast<int64_t>(b) * D;
-    const float *pr = second ? x0r : xr;
-    const int groups = groups_of(D);
-    float *mu_out = out + q, *sgn_out = out + 2 * static_cast<int64_t>(B) + q, *nrm_out = out + 4 * static_cast<int64_t>(B) + q;
+    p.wr = wr, p.pr = second ? x0r : xr, p.D = D, p.groups = groups_of(D);
 
-    // pass 1, as in proj_kernel: sum |w_i| and sum w_i (x0_i - x_i); the resident path keeps w in a[] and the point in r[]
-    float a[kSampleElems], r[kSampleElems], t[kSampleElems];
+    // pass 1: sum |w_i| and sum w_i (x0_i - x_i); the resident path keeps w in a[] and the point in r[]
     double sabs = 0.0, dot = 0.0;
     auto first = [&](int g) {
         const int64_t e = group_element(g);
@@ -264,22 +128,22 @@ __global__ __launch_bounds__(kSampleBlock) void proj_l2_kernel(const float *__re
 #pragma unroll
         for (int g = 0; g < kSampleVecs; ++g) first(g);
     } else {
-        for (int g = 0; g < groups; ++g) first(g);
+        for (int g = 0; g < p.groups; ++g) first(g);
     }
     sabs = red.sum(sabs);
     dot = red.sum(dot);
     const float d = df[b];
-    // every decision below is taken on values all threads of the workgroup hold alike: the early exits are uniform
+    // every decision below is taken on values all threads of the workgroup hold alike
     if (!(isfinite(d) && d != 0.0f && isfinite(sabs) && sabs > 0.0)) {  // no hyperplane to project onto: both problems of the sample rest
-        if (threadIdx.x == 0) *mu_out = 0.0f, *sgn_out = 0.0f, *nrm_out = 0.0f;
-        return;
+        rest(false);
+        return false;
     }
     const float c = second ? static_cast<float>(static_cast<double>(d) + dot) : d;
     const float s = c >= 0.0f ? 1.0f : -1.0f;  // NaN cannot come here: d and dot are finite
-    const float cp = fabsf(c);
-    if (!isfinite(c) || cp == 0.0f) {  // c = 0: the point lies on the hyperplane
-        if (threadIdx.x == 0) *mu_out = 0.0f, *sgn_out = 1.0f, *nrm_out = 0.0f;
-        return;
+    p.s = s, p.cp = fabsf(c);
+    if (!isfinite(c) || p.cp == 0.0f) {  // c = 0: the point lies on the hyperplane
+        rest(true);
+        return false;
     }
     if (RES) {
 #pragma unroll
@@ -287,22 +151,97 @@ __global__ __launch_bounds__(kSampleBlock) void proj_l2_kernel(const float *__re
             const float wv = a[k];
             r[k] = room(s * wv, r[k]);
             a[k] = fabsf(wv);
-            t[k] = ratio(a[k], r[k]);
+            if (BRK) t[k] = ratio(a[k], r[k]);
         }
     }
+    return true;
+}
+
+// body(|w|, room) - with BRK body(|w|, room, breakpoint) - of every element of the thread, in the same order on both paths
+template <bool RES, bool VEC, bool BRK, class F>
+__device__ __forceinline__ void each_element(const Problem &p, const float (&a)[kSampleElems], const float (&r)[kSampleElems],
+                                             const Breaks<BRK> &t, F body) {
+    if (RES) {
+#pragma unroll
+        for (int k = 0; k < kSampleElems; ++k) {
+            if constexpr (BRK)
+                body(a[k], r[k], t[k]);
+            else
+                body(a[k], r[k]);
+        }
+    } else {
+        for (int g = 0; g < p.groups; ++g) {
+            const int64_t e = group_element(g);
+            float wv[4], pv[4];
+            load4<VEC>(p.wr, e, p.D, wv);
+            load4<VEC>(p.pr, e, p.D, pv);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float av = fabsf(wv[j]), rv = room(p.s * wv[j], pv[j]);
+                if constexpr (BRK)
+                    body(av, rv, ratio(av, rv));
+                else
+                    body(av, rv);
+            }
+        }
+    }
+}
+
+// ---- Linf: lambda, the smallest value with g(lambda) = sum_i |v_i| min(lambda, r_i) = c' ---------------------------------------------------
+template <class Each>
+__device__ __forceinline__ void solve_linf(Each each, const Problem &p, SampleReducer &red, float *lam_out, float *sgn_out, float *nrm_out) {
+    // g(inf) and the largest room among the coordinates that move
+    double ginf = 0.0, rm = 0.0;
+    each([&](float av, float rv) {
+        ginf = fma(static_cast<double>(av), static_cast<double>(rv), ginf);
+        if (av != 0.0f) rm = fmax(rm, static_cast<double>(rv));
+    });
+    ginf = red.sum(ginf);
+    const float rmax = static_cast<float>(red.max(rm));
+    const double cpd = static_cast<double>(p.cp);
+    if (cpd >= ginf) {  // infeasible inside the box: every coordinate that can move goes to its bound
+        if (threadIdx.x == 0) *lam_out = INFINITY, *sgn_out = p.s, *nrm_out = rmax;
+        return;
+    }
+    // T: the largest non-negative float with g(T) < c' (g(0) = 0 < c' holds, g(inf) < c' does not)
+    uint32_t T = 0u;
+    for (int bit = 30; bit >= 0; --bit) {
+        const uint32_t cand = T | (1u << bit);
+        const float tf = __uint_as_float(cand);
+        double part = 0.0;
+        each([&](float av, float rv) { part = fma(static_cast<double>(av), static_cast<double>(fminf(tf, rv)), part); });
+        if (red.sum(part) < cpd) T = cand;
+    }
+    // the segment (T, next breakpoint]: g(lambda) = S + lambda A there
+    const float tl = __uint_as_float(T);
+    double S = 0.0, A = 0.0;
+    each([&](float av, float rv) {
+        if (rv <= tl)
+            S = fma(static_cast<double>(av), static_cast<double>(rv), S);
+        else
+            A += static_cast<double>(av);
+    });
+    S = red.sum(S);
+    A = red.sum(A);
+    const float lam = A > 0.0 ? static_cast<float>((cpd - S) / A) : INFINITY;
+    if (threadIdx.x == 0) *lam_out = lam, *sgn_out = p.s, *nrm_out = fminf(lam, rmax);
+}
+
+// ---- L2: mu, with g(mu) = sum_i |v_i| min(mu |v_i|, r_i) and the breakpoints t_i = ratio(|v_i|, r_i) ---------------------------------------
+template <class Each>
+__device__ __forceinline__ void solve_l2(Each each, const Problem &p, SampleReducer &red, float *mu_out, float *sgn_out, float *nrm_out) {
     // g(inf) = sum |v_i| r_i
     double ginf = 0.0;
-    each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t,
-                              [&](float av, float rv, float) { ginf = fma(static_cast<double>(av), static_cast<double>(rv), ginf); });
+    each([&](float av, float rv, float) { ginf = fma(static_cast<double>(av), static_cast<double>(rv), ginf); });
     ginf = red.sum(ginf);
-    const double cpd = static_cast<double>(cp);
+    const double cpd = static_cast<double>(p.cp);
     if (cpd >= ginf) {  // infeasible inside the box: every coordinate that can move goes to its bound
         double rs = 0.0;
-        each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t, [&](float av, float rv, float) {
+        each([&](float av, float rv, float) {
             if (av != 0.0f) rs = fma(static_cast<double>(rv), static_cast<double>(rv), rs);
         });
         rs = red.sum(rs);
-        if (threadIdx.x == 0) *mu_out = INFINITY, *sgn_out = s, *nrm_out = static_cast<float>(sqrt(rs));
+        if (threadIdx.x == 0) *mu_out = INFINITY, *sgn_out = p.s, *nrm_out = static_cast<float>(sqrt(rs));
         return;
     }
     // g(T) = sum_{t_i <= T} |v_i| r_i + T sum_{t_i > T} v_i^2 (v_i^2 is exact in double).  T: the largest non-negative float with
@@ -314,7 +253,7 @@ __global__ __launch_bounds__(kSampleBlock) void proj_l2_kernel(const float *__re
         const float tf = __uint_as_float(cand);
         const double td = static_cast<double>(tf);
         double part = 0.0;
-        each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t, [&](float av, float rv, float tv) {
+        each([&](float av, float rv, float tv) {
             const double ad = static_cast<double>(av);
             const bool sat = tv <= tf;
             part = fma(sat ? ad : ad * ad, sat ? static_cast<double>(rv) : td, part);
@@ -324,7 +263,7 @@ __global__ __launch_bounds__(kSampleBlock) void proj_l2_kernel(const float *__re
     // the segment (T, next breakpoint]: g(mu) = S + mu A there
     const float tl = __uint_as_float(T);
     double S = 0.0, A = 0.0;
-    each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t, [&](float av, float rv, float tv) {
+    each([&](float av, float rv, float tv) {
         const double ad = static_cast<double>(av);
         if (tv <= tl)
             S = fma(ad, static_cast<double>(rv), S);
@@ -336,93 +275,30 @@ __global__ __launch_bounds__(kSampleBlock) void proj_l2_kernel(const float *__re
     const double mud = A > 0.0 ? (cpd - S) / A : static_cast<double>(INFINITY);
     // ||delta||_2 from the solution before its rounding to float: the emitted norm is the correctly rounded one (or its neighbour)
     double n2 = 0.0;
-    each_element_l2<RES, VEC>(wr, pr, D, groups, s, a, r, t, [&](float av, float rv, float) {
+    each([&](float av, float rv, float) {
         const double m = av != 0.0f ? fmin(mud * static_cast<double>(av), static_cast<double>(rv)) : 0.0;  // never inf * 0
         n2 = fma(m, m, n2);
     });
     n2 = red.sum(n2);
-    if (threadIdx.x == 0) *mu_out = static_cast<float>(mud), *sgn_out = s, *nrm_out = static_cast<float>(sqrt(n2));
+    if (threadIdx.x == 0) *mu_out = static_cast<float>(mud), *sgn_out = p.s, *nrm_out = static_cast<float>(sqrt(n2));
 }
 
-// ---- the L1 projection -----------------------------------------------------------------------------------------------------------------
+// ---- L1: the knapsack fill by descending |v_i| ---------------------------------------------------------------------------------------------
 // F(T) = sum_{a_i >= T} a_i r_i in double (the products are exact there), in the one order of ee_sample.hpp: a sum of non-negative terms in
 // a fixed order is monotone in every term, so the computed F is non-increasing in T like the real one and the bit search below is sound.
 // A coordinate with a_i == 0 has the room 0 and adds an exact zero wherever it is counted.
-template <bool RES, bool VEC>
-__global__ __launch_bounds__(kSampleBlock) void proj_l1_kernel(const float *__restrict__ x, const float *__restrict__ x0,
-                                                             const float *__restrict__ w, const float *__restrict__ df, int B, int64_t D,
-                                                             float *__restrict__ out) {
-    __shared__ double sh[2 * kSampleWaves];
-    SampleReducer red{sh};
-    const int q = blockIdx.x, b = q < B ? q : q - B;
-    const bool second = q >= B;  // problem B + b projects x0, problem b projects x
-    const float *xr = x + static_cast<int64_t>(b) * D, *x0r = x0 + static_cast<int64_t>(b) * D, *wr = w + static_cast<int64_t>(b) * D;
-    const float *pr = second ? x0r : xr;
-    const int groups = groups_of(D);
-    const int64_t Q = 2 * static_cast<int64_t>(B);
-    float *theta_out = out + q, *sgn_out = out + Q + q, *nrm_out = out + 2 * Q + q, *phi_out = out + 3 * Q + q;
-
-    // pass 1, as in proj_kernel: sum |w_i| and sum w_i (x0_i - x_i); the resident path keeps w in a[] and the point in r[]
-    float a[kSampleElems], r[kSampleElems];
-    double sabs = 0.0, dot = 0.0;
-    auto first = [&](int g) {
-        const int64_t e = group_element(g);
-        float wv[4], xv[4], ov[4];
-        load4<VEC>(wr, e, D, wv);
-        load4<VEC>(xr, e, D, xv);
-        load4<VEC>(x0r, e, D, ov);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            sabs += static_cast<double>(fabsf(wv[j]));
-            dot = fma(static_cast<double>(wv[j]), static_cast<double>(ov[j] - xv[j]), dot);
-            if (RES) {
-                a[g * 4 + j] = wv[j];
-                r[g * 4 + j] = second ? ov[j] : xv[j];
-            }
-        }
-    };
-    if (RES) {
-#pragma unroll
-        for (int g = 0; g < kSampleVecs; ++g) first(g);
-    } else {
-        for (int g = 0; g < groups; ++g) first(g);
-    }
-    sabs = red.sum(sabs);
-    dot = red.sum(dot);
-    const float d = df[b];
-    // every decision below is taken on values all threads of the workgroup hold alike: the early exits are uniform
-    if (!(isfinite(d) && d != 0.0f && isfinite(sabs) && sabs > 0.0)) {  // no hyperplane to project onto: both problems of the sample rest
-        if (threadIdx.x == 0) *theta_out = 0.0f, *sgn_out = 0.0f, *nrm_out = 0.0f, *phi_out = 0.0f;
-        return;
-    }
-    const float c = second ? static_cast<float>(static_cast<double>(d) + dot) : d;
-    const float s = c >= 0.0f ? 1.0f : -1.0f;  // NaN cannot come here: d and dot are finite
-    const float cp = fabsf(c);
-    if (!isfinite(c) || cp == 0.0f) {  // c = 0: the point lies on the hyperplane; no |v_i| is above theta = +inf, so nothing moves
-        if (threadIdx.x == 0) *theta_out = INFINITY, *sgn_out = 1.0f, *nrm_out = 0.0f, *phi_out = 0.0f;
-        return;
-    }
-    if (RES) {
-#pragma unroll
-        for (int k = 0; k < kSampleElems; ++k) {
-            const float wv = a[k];
-            r[k] = room(s * wv, r[k]);
-            a[k] = fabsf(wv);
-        }
-    }
+template <class Each>
+__device__ __forceinline__ void solve_l1(Each each, const Problem &p, SampleReducer &red, float *theta_out, float *sgn_out, float *nrm_out, float *phi_out) {
     // F at the smallest positive float: every moving coordinate at its bound
     double full = 0.0;
-    each_element<RES, VEC>(wr, pr, D, groups, s, a, r,
-                           [&](float av, float rv) { full = fma(static_cast<double>(av), static_cast<double>(rv), full); });
+    each([&](float av, float rv) { full = fma(static_cast<double>(av), static_cast<double>(rv), full); });
     full = red.sum(full);
-    const double cpd = static_cast<double>(cp);
+    const double cpd = static_cast<double>(p.cp);
     if (cpd > full) {  // infeasible inside the box: every coordinate that can move goes to its bound (all |v_i| != 0 are above theta = 0)
         double rs = 0.0;
-        each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
-            rs += av != 0.0f ? static_cast<double>(rv) : 0.0;
-        });
+        each([&](float av, float rv) { rs += av != 0.0f ? static_cast<double>(rv) : 0.0; });
         rs = red.sum(rs);
-        if (threadIdx.x == 0) *theta_out = 0.0f, *sgn_out = s, *nrm_out = static_cast<float>(rs), *phi_out = 1.0f;
+        if (threadIdx.x == 0) *theta_out = 0.0f, *sgn_out = p.s, *nrm_out = static_cast<float>(rs), *phi_out = 1.0f;
         return;
     }
     // theta: the largest positive float with F(theta) >= c'.  F(2^-149) = full >= c' holds, so bit 0 at the latest is taken and theta > 0;
@@ -432,7 +308,7 @@ __global__ __launch_bounds__(kSampleBlock) void proj_l1_kernel(const float *__re
         const uint32_t cand = T | (1u << bit);
         const float tf = __uint_as_float(cand);
         double part = 0.0;
-        each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
+        each([&](float av, float rv) {
             part = fma(static_cast<double>(av), av >= tf ? static_cast<double>(rv) : 0.0, part);  // an exact zero below T
         });
         if (red.sum(part) >= cpd) T = cand;
@@ -440,7 +316,7 @@ __global__ __launch_bounds__(kSampleBlock) void proj_l1_kernel(const float *__re
     // the fill: S and N above theta (at their bounds), P and R at theta (they share what is left of c')
     const float theta = __uint_as_float(T);
     double S = 0.0, N = 0.0, P = 0.0, R = 0.0;
-    each_element<RES, VEC>(wr, pr, D, groups, s, a, r, [&](float av, float rv) {
+    each([&](float av, float rv) {
         const double ad = static_cast<double>(av), rd = static_cast<double>(rv);
         const double above = av > theta ? rd : 0.0, at = av == theta ? rd : 0.0;  // adding an exact zero changes no sum
         S = fma(ad, above, S);
@@ -454,11 +330,39 @@ __global__ __launch_bounds__(kSampleBlock) void proj_l1_kernel(const float *__re
     R = red.sum(R);
     const double phid = P > 0.0 ? fmin(fmax((cpd - S) / P, 0.0), 1.0) : 0.0;
     // ||delta||_1 from the fraction before its rounding to float: the emitted norm is rounded once
-    if (threadIdx.x == 0) *theta_out = theta, *sgn_out = s, *nrm_out = static_cast<float>(fma(phid, R, N)), *phi_out = static_cast<float>(phid);
+    if (threadIdx.x == 0) *theta_out = theta, *sgn_out = p.s, *nrm_out = static_cast<float>(fma(phid, R, N)), *phi_out = static_cast<float>(phid);
+}
+
+// out [3, 2B] - L1: [4, 2B] - rows head (lambda, mu or theta), sign, ||delta||, and in L1 phi
+template <bool RES, bool VEC, int M>
+__global__ __launch_bounds__(kSampleBlock) void proj_kernel(const float *__restrict__ x, const float *__restrict__ x0, const float *__restrict__ w,
+                                                          const float *__restrict__ df, int B, int64_t D, float *__restrict__ out) {
+    __shared__ double sh[2 * kSampleWaves];
+    SampleReducer red{sh};
+    const int64_t Q = 2 * static_cast<int64_t>(B), q = blockIdx.x;
+    float *head_out = out + q, *sgn_out = out + Q + q, *nrm_out = out + 2 * Q + q, *phi_out = M == kL1 ? out + 3 * Q + q : nullptr;
+    constexpr bool BRK = M == kL2;
+    Problem p;
+    float a[kSampleElems], r[kSampleElems];
+    Breaks<BRK> t;
+    // a degenerate problem moves nothing.  No hyperplane: sign 0, and step leaves the sample where it is.  On it: sign 1 and a head under
+    // which no coordinate moves - lambda = mu = 0, and theta = +inf (no |v_i| is above it)
+    const auto rest = [&](bool on) {
+        if (threadIdx.x != 0) return;
+        *head_out = M == kL1 && on ? INFINITY : 0.0f, *sgn_out = on ? 1.0f : 0.0f, *nrm_out = 0.0f;
+        if (M == kL1) *phi_out = 0.0f;
+    };
+    if (!proj_begin<RES, VEC, BRK>(x, x0, w, df, B, D, red, p, a, r, t, rest)) return;
+    const auto each = [&](auto body) { each_element<RES, VEC, BRK>(p, a, r, t, body); };
+    if constexpr (M == kL2)
+        solve_l2(each, p, red, head_out, sgn_out, nrm_out);
+    else if constexpr (M == kL1)
+        solve_l1(each, p, red, head_out, sgn_out, nrm_out, phi_out);
+    else
+        solve_linf(each, p, red, head_out, sgn_out, nrm_out);
 }
 
 // ---- the step ------------------------------------------------------------------------------------------------------------------------
-enum Metric : int { kLinf = 0, kL2 = 1, kL1 = 2 };  // the three instances of step, commit and the launches
 
 struct StepSample {
     float l1, s1, l2, s2, alpha;
@@ -801,12 +705,7 @@ int launch_proj(const float *x, const float *x0, const float *w, const float *df
     const int nb = static_cast<int>(B);
     ProfScope prof(EE_K_FAB_PROJ, as_stream(stream));
     sample_launch(res, sample_vec(per_sample, x, x0, w), [&](auto RES, auto VEC) {
-        if constexpr (M == kL2)
-            EE_LAUNCH((proj_l2_kernel<RES, VEC>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-        else if constexpr (M == kL1)
-            EE_LAUNCH((proj_l1_kernel<RES, VEC>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
-        else
-            EE_LAUNCH((proj_kernel<RES, VEC>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
+        EE_LAUNCH((proj_kernel<RES, VEC, M>), grid, block, 0, as_stream(stream), x, x0, w, df, nb, per_sample, out);
     });
     return launch_status();
 }

@@ -973,11 +973,11 @@ def square_l1_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trac
 FAB_NORMS = ("Linf", "L2")
 
 
-def _fab_ops(norm):
-    """(projection, step, commit) of a FAB run in the threat model `norm`: the metric enters FAB at these three launches only."""
-    if _check_norm(norm, FAB_NORMS, "FAB") == "L2":
-        return ops.fab_proj_l2, ops.fab_step_l2_, ops.fab_commit_l2_
-    return ops.fab_proj_linf, ops.fab_step_, ops.fab_commit_
+# norm -> (projection, step, commit - names in `ops`, looked up when a run is made -, rows of the projection scalars): the metric enters
+# FAB at these three launches only.  L1 has doors of its own (fab_l1_loop, fab_u_l1_loop): a run class names the norms its door accepts
+_FAB_METRIC = {"Linf": ("fab_proj_linf", "fab_step_", "fab_commit_", 3),
+               "L2": ("fab_proj_l2", "fab_step_l2_", "fab_commit_l2_", 3),
+               "L1": ("fab_proj_l1", "fab_step_l1_", "fab_commit_l1_", ops.FAB_L1_ROWS)}
 
 
 def _fab_restarts(x0, n_restarts, seed, noise, target_index=0, what="FAB"):
@@ -1018,19 +1018,19 @@ class _FabRun:
     run) and `iteration` (forward, diff, backward, projection, step, forward, commit: what a captured graph replays).  No host read anywhere.
     `eps` only thresholds `result`: the graph does not know it, so a cached run takes the caller's through `load`."""
 
-    SCAL_ROWS = 3  # rows of the projection scalars [SCAL_ROWS, 2B]
-    metric_ops = staticmethod(_fab_ops)  # norm -> (projection, step, commit)
+    NORMS = FAB_NORMS  # the norms this door accepts; the rest of _FAB_METRIC is refused here
 
     def __init__(self, x0, y, n_iter, eps, path="auto", norm="Linf"):
         B, dev = x0.shape[0], x0.device
         self.n_iter, self.eps, self.path, self.norm = int(n_iter), float(eps), path, norm
-        self.proj, self.step_, self.commit_ = self.metric_ops(norm)
+        *launches, rows = _FAB_METRIC[_check_norm(norm, self.NORMS, "FAB")]
+        self.proj, self.step_, self.commit_ = (getattr(ops, name) for name in launches)
         self.x = torch.empty_like(x0).requires_grad_(True)
         self.x0, self.adv = torch.empty_like(x0), torch.empty_like(x0)
         self.y = torch.empty(B, dtype=torch.int64, device=dev)
         self.t = torch.empty(B, dtype=torch.int64, device=dev)
         self.res = torch.empty(B, dtype=torch.float32, device=dev)
-        self.scal = torch.zeros((self.SCAL_ROWS, 2 * B), dtype=torch.float32, device=dev)
+        self.scal = torch.zeros((rows, 2 * B), dtype=torch.float32, device=dev)
         self.pred = torch.zeros(B, dtype=torch.int32, device=dev)
         self.flags = torch.zeros(B, dtype=torch.int32, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1068,8 +1068,12 @@ class _FabRun:
 
     def iteration(self, model):
         w = input_gradient(model, self.x, self.spec).contiguous()
+        self.advance(model, w, self.df)  # the spec has set df by now
+
+    def advance(self, model, w, df):
+        """What follows the hyperplane (w, df), however it was found: projection, step, second forward, commit."""
         x = self.x.detach()
-        self.proj(x, self.x0, w, self.df, self.path, self.scal)
+        self.proj(x, self.x0, w, df, self.path, self.scal)
         self.step_(x, self.x0, w, self.scal)
         with torch.no_grad():
             z = model(self.x)
@@ -1085,6 +1089,34 @@ class _FabRun:
             return _adv_where_fooled(robust, self.x0, self.adv), robust, self.res.clone()
 
 
+def _fab_drive(model, x0, n_iter, use_graph, path, restarts, name, size_of, make_run, load, chunk=None, norm=None):
+    """What fab_loop, fab_l1_loop, fab_u_loop and fab_u_l1_loop share: the argument checks, the empty batch, the graph key, the restarts'
+    keys and _drive.  restarts: the arguments of _fab_restarts behind x0.  size_of(model, x0, n_iter): what the key holds behind the
+    device and make_run(x0, size) gets - the iterations per graph of a targeted door, K of an untargeted one.  load: the run's load tuple
+    between x0 and (seeds, noise).  chunk: the iterations per graph, where they are not `size` - 1 for the untargeted doors: a replay's
+    bubble is nothing against K backward passes, and MAX_ITERS_PER_GRAPH iterations of K passes each would be a graph of thousands of
+    nodes.  norm: that of a door that takes one (it ends the key)."""
+    model = _unwrap(model)
+    x0 = x0.detach().contiguous()
+    n_iter = int(n_iter)
+    if n_iter < 1:
+        raise ValueError("FAB needs n_iter >= 1")
+    ops._sample_path(path, "FAB projection")
+    if norm is not None:
+        _check_norm(norm, FAB_NORMS, "FAB")
+    if int(restarts[0]) < 1:
+        raise ValueError("FAB needs n_restarts >= 1, got %d" % int(restarts[0]))
+    if x0.shape[0] == 0:
+        return _empty_result(x0, torch.float32)
+    if use_graph is None:
+        use_graph = graphs_enabled()
+    size = size_of(model, x0, n_iter)
+    key = (name, id(model), model.training, tuple(x0.shape), path, x0.device.index, size) + (() if norm is None else (norm,))
+    n_restarts, seeds, noise = _fab_restarts(x0, *restarts)
+    return _drive(model, key, lambda: make_run(x0, size), (x0,) + load + (seeds, noise), n_iter, size if chunk is None else chunk, use_graph,
+                  n_restarts)
+
+
 def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", norm="Linf", n_restarts=1, seed=None, noise=None, target_index=0):
     """One FAB-T run of n_iter iterations from x0 towards the classes `targets` [B] in the threat model `norm` ('Linf' or 'L2': the metric of
     the projections, of alpha and of the result).  Returns (x_adv, robust, norm): norm [B] is the smallest ||adv - x0|| in that metric
@@ -1097,25 +1129,8 @@ def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", no
     over all of them.  The graph does not know the count: one cached graph serves any number of restarts.  The model's mode is left as the
     caller set it.  Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of up to MAX_ITERS_PER_GRAPH iterations; both
     give the same bits.  `path` picks the projection kernel's path ('auto', 'resident', 'streaming'; the same bits)."""
-    model = _unwrap(model)
-    x0 = x0.detach().contiguous()
-    n_iter = int(n_iter)
-    if n_iter < 1:
-        raise ValueError("FAB needs n_iter >= 1")
-    ops._sample_path(path, "FAB projection")
-    _fab_ops(norm)
-    n_restarts = int(n_restarts)
-    if n_restarts < 1:
-        raise ValueError("FAB needs n_restarts >= 1, got %d" % n_restarts)
-    if x0.shape[0] == 0:
-        return _empty_result(x0, torch.float32)
-    if use_graph is None:
-        use_graph = graphs_enabled()
-    chunk = _chunk(n_iter)
-    key = ("fab", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk, norm)
-    n_restarts, seeds, noise = _fab_restarts(x0, n_restarts, seed, noise, target_index)
-    return _drive(model, key, lambda: _FabRun(x0, y, n_iter, eps, path, norm), (x0, y, targets, eps, seeds, noise), n_iter, chunk, use_graph,
-                  n_restarts)
+    return _fab_drive(model, x0, n_iter, use_graph, path, (n_restarts, seed, noise, target_index), "fab",
+                      lambda m, x, n: _chunk(n), lambda x, _: _FabRun(x, y, n_iter, eps, path, norm), (y, targets, eps), norm=norm)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -1124,11 +1139,7 @@ def fab_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto", no
 class _FabL1Run(_FabRun):
     """_FabRun with the three L1 launches and their [4, 2B] scalars (theta, sign, ||delta||_1, phi); state, start, iteration and result
     are _FabRun's, and `res` holds L1 distances."""
-    SCAL_ROWS = ops.FAB_L1_ROWS
-
-    @staticmethod
-    def metric_ops(norm):
-        return ops.fab_proj_l1, ops.fab_step_l1_, ops.fab_commit_l1_
+    NORMS = ("L1",)
 
     def __init__(self, x0, y, n_iter, eps, path="auto"):
         super().__init__(x0, y, n_iter, eps, path, "L1")
@@ -1142,24 +1153,8 @@ def fab_l1_loop(model, x0, y, targets, n_iter, eps, use_graph=None, path="auto",
     under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of its own (the key shares nothing with fab_loop's, so Linf, L2 and
     L1 graphs of one shape coexist); both give the same bits, and so do the paths ('auto', 'resident', 'streaming').  n_restarts, seed,
     noise and target_index as in fab_loop; the start of a restart lies at L1 distance min(norm so far, eps) / 2."""
-    model = _unwrap(model)
-    x0 = x0.detach().contiguous()
-    n_iter = int(n_iter)
-    if n_iter < 1:
-        raise ValueError("FAB needs n_iter >= 1")
-    ops._sample_path(path, "FAB projection")
-    n_restarts = int(n_restarts)
-    if n_restarts < 1:
-        raise ValueError("FAB needs n_restarts >= 1, got %d" % n_restarts)
-    if x0.shape[0] == 0:
-        return _empty_result(x0, torch.float32)
-    if use_graph is None:
-        use_graph = graphs_enabled()
-    chunk = _chunk(n_iter)
-    key = ("fab_l1", id(model), model.training, tuple(x0.shape), path, x0.device.index, chunk)
-    n_restarts, seeds, noise = _fab_restarts(x0, n_restarts, seed, noise, target_index)
-    return _drive(model, key, lambda: _FabL1Run(x0, y, n_iter, eps, path), (x0, y, targets, eps, seeds, noise), n_iter, chunk, use_graph,
-                  n_restarts)
+    return _fab_drive(model, x0, n_iter, use_graph, path, (n_restarts, seed, noise, target_index), "fab_l1",
+                      lambda m, x, n: _chunk(n), lambda x, _: _FabL1Run(x, y, n_iter, eps, path), (y, targets, eps))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -1211,43 +1206,15 @@ class _FabURun(_FabRun):
         return self.w, self.df
 
     def iteration(self, model):
-        w, df = self.hyperplane(model)
-        x = self.x.detach()
-        self.proj(x, self.x0, w, df, self.path, self.scal)
-        self.step_(x, self.x0, w, self.scal)
-        with torch.no_grad():
-            z = model(self.x)
-        self.commit_(z.detach().float().contiguous(), self.y, x, self.x0, self.adv, self.res, self.pred, self.flags, self.counter)
+        self.advance(model, *self.hyperplane(model))
 
 
 class _FabUL1Run(_FabURun):
-    """_FabURun with the three L1 launches and their [4, 2B] scalars, through the hook _FabL1Run uses; the arg-min measures in max |g_i|."""
-    SCAL_ROWS = ops.FAB_L1_ROWS
-    metric_ops = staticmethod(_FabL1Run.metric_ops)
+    """_FabURun with the three L1 launches and their [4, 2B] scalars; the arg-min measures in max |g_i|."""
+    NORMS = ("L1",)
 
     def __init__(self, x0, y, n_iter, eps, nclass, path="auto"):
         super().__init__(x0, y, n_iter, eps, nclass, path, "L1")
-
-
-def _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, name, make_run, restarts, *key_tail):
-    model = _unwrap(model)
-    x0 = x0.detach().contiguous()
-    n_iter = int(n_iter)
-    if n_iter < 1:
-        raise ValueError("FAB needs n_iter >= 1")
-    ops._sample_path(path, "FAB projection")
-    if int(restarts[0]) < 1:
-        raise ValueError("FAB needs n_restarts >= 1, got %d" % int(restarts[0]))
-    if x0.shape[0] == 0:
-        return _empty_result(x0, torch.float32)
-    if use_graph is None:
-        use_graph = graphs_enabled()
-    K = _n_classes(model, x0, nclass)
-    n_restarts, seeds, noise = _fab_restarts(x0, *restarts)
-    # one iteration per graph: a replay's bubble is nothing against K backward passes, and MAX_ITERS_PER_GRAPH iterations of K passes each
-    # would be a graph of thousands of nodes
-    key = (name, id(model), model.training, tuple(x0.shape), path, x0.device.index, K) + key_tail
-    return _drive(model, key, lambda: make_run(model, x0, K), (x0, y, eps, seeds, noise), n_iter, 1, use_graph, n_restarts)
 
 
 def fab_u_loop(model, x0, y, n_iter, eps, use_graph=None, path="auto", norm="Linf", nclass=None, n_restarts=1, seed=None, noise=None):
@@ -1259,13 +1226,13 @@ def fab_u_loop(model, x0, y, n_iter, eps, use_graph=None, path="auto", norm="Lin
     with n_restarts = 1; n_restarts, seed and noise as in fab_loop (the keys are fabstart.seed_of(seed, 0, r)).
     Eager, or - under EEADV_GRAPH=1 / use_graph - replayed from a captured graph of ONE iteration under a key of its own ("fab_u"); both give
     the same bits.  On a model that redraws at every forward, all K hyperplanes of an iteration belong to the one draw of its forward."""
-    _fab_ops(norm)
-    return _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, "fab_u",
-                        lambda m, x, K: _FabURun(x, y, n_iter, eps, K, path, norm), (n_restarts, seed, noise), norm)
+    _check_norm(norm, FAB_NORMS, "FAB")
+    return _fab_drive(model, x0, n_iter, use_graph, path, (n_restarts, seed, noise), "fab_u",
+                      lambda m, x, n: _n_classes(m, x, nclass), lambda x, K: _FabURun(x, y, n_iter, eps, K, path, norm), (y, eps), 1, norm)
 
 
 def fab_u_l1_loop(model, x0, y, n_iter, eps, use_graph=None, path="auto", nclass=None, n_restarts=1, seed=None, noise=None):
     """fab_u_loop in the L1 threat model: the projections of fab_l1_loop, the distance to a hyperplane measured in max |g_i|, eps the L1
     radius.  A graph key of its own ("fab_u_l1")."""
-    return _fab_u_drive(model, x0, y, n_iter, eps, use_graph, path, nclass, "fab_u_l1",
-                        lambda m, x, K: _FabUL1Run(x, y, n_iter, eps, K, path), (n_restarts, seed, noise))
+    return _fab_drive(model, x0, n_iter, use_graph, path, (n_restarts, seed, noise), "fab_u_l1",
+                      lambda m, x, n: _n_classes(m, x, nclass), lambda x, K: _FabUL1Run(x, y, n_iter, eps, K, path), (y, eps), 1)
