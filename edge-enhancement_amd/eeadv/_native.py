@@ -33,6 +33,12 @@ SIGNATURES = {
     "ee_add_clamp_f32": [c_p, c_p, c_p, c_l, c_f, c_f, c_p],
     "ee_freeat_update_f32": [c_p, c_p, c_l, c_f, c_f, c_p],
     "ee_freeat_update_masked_f32": [c_p, c_p, c_p, c_l, c_f, c_f, c_p],
+    # fast adversarial training (ee_fastat.hip): delta, in1, x, noise_or_null, n, eps, seed, step, stream
+    "ee_fastat_start_f32": [c_p, c_p, c_p, c_p, c_l, c_f, c_u64, c_p, c_p],
+    # delta, in1, g, x, n, alpha, eps, step_or_null, stream
+    "ee_fastat_ascend_f32": [c_p, c_p, c_p, c_p, c_l, c_f, c_f, c_p, c_p],
+    # final, x, logits, labels, B, K, per_sample, first, stream
+    "ee_fastat_keep_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_l, c_i, c_p],
     "ee_avmix_f32": [c_p, c_p, c_p, c_p, c_l, c_l, c_f, c_p],
     "ee_avmix_labels_f64": [c_p, c_p, c_p, c_l, c_l, c_f, c_f, c_p],
     "ee_edge125_fwd_f32": [c_p, c_i, c_i, c_i, c_i, c_p, c_f, c_f, c_p, c_p, c_p],

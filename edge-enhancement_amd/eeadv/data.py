@@ -390,13 +390,30 @@ def resized_size(w, h, short):
     return int(short * w / h), short
 
 
+def center_crop_u8(a, S):
+    """torchvision's CenterCrop(S) (transforms.functional.center_crop) on a uint8 [H, W, C] array: an image smaller than S along an axis
+    is first padded with zeros there, (S - n) // 2 before and (S - n + 1) // 2 after - the odd pixel goes to the right / bottom -, then the
+    window starts at int(round((n - S) / 2.0)) along each axis (Python's round: halves go to the even number)."""
+    h, w = a.shape[:2]
+    if S > w or S > h:
+        pl, pt = ((S - w) // 2 if S > w else 0), ((S - h) // 2 if S > h else 0)
+        pr, pb = ((S - w + 1) // 2 if S > w else 0), ((S - h + 1) // 2 if S > h else 0)
+        a = np.pad(a, ((pt, pb), (pl, pr), (0, 0)))
+        h, w = a.shape[:2]
+    top, left = int(round((h - S) / 2.0)), int(round((w - S) / 2.0))
+    return a[top:top + S, left:left + S]
+
+
 def _decode_ragged(job):
     from PIL import Image
-    paths, short = job
+    paths, short = job[:2]
+    img_size = job[2] if len(job) > 2 else 0
     out = []
     for p in paths:
         with open(p, "rb") as f:
             img = Image.open(f).convert("RGB")
+        if img_size and min(img.size) != img_size:  # Resize(img_size): up and down
+            img = img.resize(resized_size(img.size[0], img.size[1], img_size), Image.BILINEAR)
         if short and min(img.size) > short:
             img = img.resize(resized_size(img.size[0], img.size[1], short), Image.BILINEAR)
         out.append(np.asarray(img, dtype=np.uint8).reshape(img.size[1], img.size[0], 3))
@@ -406,11 +423,16 @@ def _decode_ragged(job):
 
 def _decode_val(job):
     from PIL import Image
-    paths, S, resize = job
+    paths, S, resize = job[:3]
     out = np.empty((len(paths), S, S, 3), dtype=np.uint8)
     for i, p in enumerate(paths):
         with open(p, "rb") as f:
             img = Image.open(f).convert("RGB")
+        if len(job) > 3:  # the fast-AT pipeline: [Resize(img_size)] + CenterCrop(S), which pads what is smaller than S
+            if job[3] and min(img.size) != job[3]:
+                img = img.resize(resized_size(img.size[0], img.size[1], job[3]), Image.BILINEAR)
+            out[i] = center_crop_u8(np.asarray(img, dtype=np.uint8).reshape(img.size[1], img.size[0], 3), S)
+            continue
         size = resized_size(img.size[0], img.size[1], resize)
         if size != img.size:
             img = img.resize(size, Image.BILINEAR)
@@ -428,11 +450,16 @@ def _pool_map(fn, jobs):
         return list(pool.imap(fn, jobs))
 
 
-def load_imagenet(root, split, shape=(3, 224, 224), num_classes=1000, resize=256):
+def load_imagenet(root, split, shape=(3, 224, 224), num_classes=1000, resize=256, img_size=None):
     """ImageNet `train` as the ragged (pixels uint8 [sum H*W*3], offsets int64 [N], sizes int32 [N,2] = (H, W), labels int64 [N]),
-    `val` as (uint8 [N,S,S,3], int64 [N]) after Resize(resize) + CenterCrop(S); decoded once, then read from the cache."""
+    `val` as (uint8 [N,S,S,3], int64 [N]) after Resize(resize) + CenterCrop(S); decoded once, then read from the cache.
+    img_size (an int, the fast-AT pipeline of fgsm_imagenet/main_fast.py:136-160; `resize` is then unused): > 0 is Resize(img_size) at
+    decode in both splits - the shorter side to img_size, PIL BILINEAR, up and down -, `val` is CenterCrop(S) of that or, with 0, of the
+    file as it is (center_crop_u8: zero padding where the image is smaller).  img_size is part of the cache key."""
     C, S, S2 = shape
-    if C != 3 or S != S2 or resize < S:
+    if img_size is not None and (int(img_size) != img_size or img_size < 0):
+        raise DataError("img_size must be an integer >= 0, got %r" % (img_size,))
+    if C != 3 or S != S2 or (img_size is None and resize < S):
         raise DataError("ImageNet batches are 3 x S x S with S <= the resize size, got shape %s and resize %d" % (tuple(shape), resize))
     classes, samples = imagenet_listing(root, split, num_classes)
     if not samples:
@@ -440,19 +467,21 @@ def load_imagenet(root, split, shape=(3, 224, 224), num_classes=1000, resize=256
     paths = [p for p, _ in samples]
     labels = np.array([lab for _, lab in samples], dtype=np.int64)
     if split == "val":
-        key = cache_key(root, ["imagenet", "val", list(shape), resize, classes], paths)
+        key = cache_key(root, ["imagenet", "val", list(shape), resize, classes] if img_size is None else
+                        ["imagenet", "val", list(shape), "img_size", int(img_size), classes], paths)
+        tail = () if img_size is None else (int(img_size),)
 
         def build_val():
             print("eeadv.data: decoding %d images of %s/val" % (len(paths), root))
-            parts = _pool_map(_decode_val, [(paths[i:i + _CHUNK], S, resize) for i in range(0, len(paths), _CHUNK)])
+            parts = _pool_map(_decode_val, [(paths[i:i + _CHUNK], S, resize) + tail for i in range(0, len(paths), _CHUNK)])
             return np.concatenate(parts), labels
         return cached(root, "imagenet-val-%s.npz" % key, build_val)
     short = imagenet_short()
-    key = cache_key(root, ["imagenet", "train", short, classes], paths)
+    key = cache_key(root, ["imagenet", "train", short, classes] + (["img_size", int(img_size)] if img_size else []), paths)
 
     def build():
         print("eeadv.data: decoding %d images of %s/train%s" % (len(paths), root, " (shorter side <= %d)" % short if short else ""))
-        parts = _pool_map(_decode_ragged, [(paths[i:i + _CHUNK], short) for i in range(0, len(paths), _CHUNK)])
+        parts = _pool_map(_decode_ragged, [(paths[i:i + _CHUNK], short, int(img_size or 0)) for i in range(0, len(paths), _CHUNK)])
         sizes = np.concatenate([s for _, s in parts])
         nbytes = sizes[:, 0].astype(np.int64) * sizes[:, 1] * 3
         offsets = np.concatenate([np.zeros(1, np.int64), np.cumsum(nbytes)[:-1]])
@@ -751,10 +780,11 @@ def make_loaders(kind, root, spec, device, batch_size, seed):
         return (DeviceLoader(lambda: load_mnist(root, "train", shape, k), batch_size, device, seed, shuffle=True, flip=False),
                 DeviceLoader(lambda: load_mnist(root, "test", shape, k), batch_size, device, seed, shuffle=True, flip=False))
     if kind == "imagenet":
-        resize = int(spec.get("resize", 256))
-        return (RaggedDeviceLoader(lambda: load_imagenet(root, "train", shape, k, resize), shape[-1], batch_size, device, seed,
+        resize, img_size = int(spec.get("resize", 256)), spec.get("img_size")  # img_size: the fast-AT pipeline (load_imagenet)
+        return (RaggedDeviceLoader(lambda: load_imagenet(root, "train", shape, k, resize, img_size), shape[-1], batch_size, device, seed,
                                    what="the train split of %s" % root),
-                DeviceLoader(lambda: load_imagenet(root, "val", shape, k, resize), batch_size, device, seed, shuffle=False, flip=False))
+                DeviceLoader(lambda: load_imagenet(root, "val", shape, k, resize, img_size), batch_size, device, seed, shuffle=False,
+                             flip=False))
     if kind == "cifar100":
         return (AugDeviceLoader(lambda: load_cifar100(root, "train", shape, k), batch_size, device, seed, pad=int(spec.get("pad", 4)),
                                 degrees=float(spec.get("degrees", 15.0))),

@@ -162,6 +162,108 @@ def freeat_update_masked_(delta, g_in1, x, alpha, eps):
     return delta
 
 
+# ---- fast adversarial training (ee_fastat.hip) --------------------------------------------------
+def _host_plumbing(what, *tensors):
+    """True when every tensor is on the CPU and the caller opted into the host plumbing (eeadv.runtime.allow_cpu_plumbing, what --no-cuda
+    does); a CPU tensor without the opt-in raises, a mix of devices falls through to _chk, which refuses it."""
+    from . import runtime
+    live = [t for t in tensors if t is not None]
+    return bool(live) and not any(t.is_cuda for t in live) and not runtime.require_device(live[0], what)
+
+
+def fastat_draw_host(n, eps, seed, step):
+    """The U(-eps, eps) draw of ee_fastat_start_f32 for elements 0 .. n-1 in numpy float32, bit for bit: one Philox call (stream 0) per
+    group of four elements at counter (step << 32) + (i >> 2), u = (word >> 8) 2^-24, then u * (eps - (-eps)) + (-eps), 0 + that, and
+    the clamp to [-eps, eps], each rounded to float32 once."""
+    from .sqatk import philox4x32
+    n, e = int(n), np.float32(eps)
+    ctr = (np.uint64((int(step) << 32) & 0xFFFFFFFFFFFFFFFF) + np.arange((n + 3) // 4, dtype=np.uint64))
+    u = (philox4x32(seed, ctr, 0) >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    z = np.float32(0.0) + (u * (e - (-e)) + (-e))
+    return np.ascontiguousarray(np.clip(z, -e, e).reshape(-1)[:n], dtype=np.float32)
+
+
+def fastat_start_(delta, in1, x, eps, seed=0, step=None, noise=None):
+    """The start of a fast-AT batch (main_fast.py:224-225, 233-235), n = x.numel(): delta[:n] = noise (as bits) or, with noise None, the
+    U(-eps, eps) draw keyed by (seed, step[0]) - `step` a device int64 [1] tensor read as the uint64 counter, which this launch never
+    writes; in1 = clamp(x + delta[:n], 0, 1).  delta is the flat persistent buffer (>= n elements), in1 has x's shape.  CPU tensors under
+    the host plumbing: the same bits from fastat_draw_host and torch ops."""
+    n = x.numel()
+    if delta.numel() < n:
+        raise ValueError("batch has more elements than the noise buffer")
+    if noise is None and step is None:
+        raise ValueError("fastat_start_ draws its noise from (seed, step): give the step counter, or the noise")
+    if not float(eps) >= 0.0:
+        raise ValueError("eps must be >= 0, got %r" % (eps,))
+    if _host_plumbing("fastat_start_", delta, in1, x, noise, step):
+        d = delta.view(-1)[:n]
+        if noise is not None:
+            d.copy_(noise.reshape(-1))
+        else:
+            d.copy_(torch.from_numpy(fastat_draw_host(n, eps, seed, int(step.view(-1)[0]))))
+        in1.copy_(torch.clamp(x + d.view(x.shape), 0.0, 1.0))
+        return in1
+    px = _chk(x, torch.float32, "x")
+    pd = _chk(delta, torch.float32, "delta")
+    pi = _chk(in1, torch.float32, "in1", x.shape)
+    N.check(N.lib.ee_fastat_start_f32(pd, pi, px, _opt(noise, torch.float32, "noise", x.shape), n, eps, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                      None if noise is not None else _chk(step, torch.int64, "step", (1,)), _stream()), "ee_fastat_start_f32")
+    return in1
+
+
+def fastat_ascend_(delta, in1, g, x, alpha, eps, step=None):
+    """The noise update and the descend pass's input in one launch (main_fast.py:246-253): freeat_update_masked_(delta, g, x, alpha, eps)
+    then in1 = add_clamp(x, delta[:n]), bit for bit; afterwards step[0] += 1 (`step`: device int64 [1] or None).  in1 may be g."""
+    n = x.numel()
+    if delta.numel() < n:
+        raise ValueError("batch has more elements than the noise buffer")
+    if _host_plumbing("fastat_ascend_", delta, in1, g, x, step):
+        d = delta.view(-1)[:n].view(x.shape)
+        s = x + d
+        gd = torch.where((s >= 0) & (s <= 1), g, torch.zeros_like(g))
+        d.copy_(torch.clamp(d + alpha * torch.sign(gd), -eps, eps))
+        in1.copy_(torch.clamp(x + d, 0.0, 1.0))
+        if step is not None:
+            step += 1
+        return in1
+    px = _chk(x, torch.float32, "x")
+    pd = _chk(delta, torch.float32, "delta")
+    pi = _chk(in1, torch.float32, "in1", x.shape)
+    pg = _chk(g, torch.float32, "g", x.shape)
+    N.check(N.lib.ee_fastat_ascend_f32(pd, pi, pg, px, n, alpha, eps, _opt(step, torch.int64, "step", (1,)), _stream()), "ee_fastat_ascend_f32")
+    return in1
+
+
+def fastat_keep_(final, x, logits=None, labels=None, first=False):
+    """The union across PGD restarts (lib/validation.py:51-57), in place on final [B, ...]: `first` copies every row of x; otherwise the rows
+    whose arg-max logit (torch.max(1)[1]'s: lowest index among equal maxima, the first NaN of a row that holds one) differs from the label."""
+    B = final.shape[0]
+    if tuple(x.shape) != tuple(final.shape):
+        raise ValueError("x has shape %s, expected %s" % (tuple(x.shape), tuple(final.shape)))
+    if B and final.data_ptr() == x.data_ptr():
+        raise ValueError("fastat_keep_ writes final while it reads x: they must be two tensors")
+    if not first and (logits is None or labels is None):
+        raise ValueError("fastat_keep_ needs logits and labels unless first")
+    if _host_plumbing("fastat_keep_", final, x, logits, labels):
+        if first:
+            final.copy_(x)
+        else:
+            I = logits.max(1)[1] != labels
+            final[I] = x[I]
+        return final
+    pf = _chk(final, torch.float32, "final")
+    px = _chk(x, torch.float32, "x")
+    K = 1
+    if not first:
+        if logits.dim() != 2 or logits.shape[0] != B:
+            raise ValueError("logits has shape %s, expected [%d, K]" % (tuple(logits.shape), B))
+        K = logits.shape[1]
+    N.check(N.lib.ee_fastat_keep_f32(pf, px, None if first else _chk(logits, torch.float32, "logits"),
+                                     None if first else _chk(labels, torch.int64, "labels", (B,)), B, K, final.numel() // B if B else 1,
+                                     1 if first else 0, _stream()), "ee_fastat_keep_f32")
+    return final
+
+
 def avmix(x, x0, wgt, gamma):
     B = x.shape[0]
     px = _chk(x, torch.float32, "x")

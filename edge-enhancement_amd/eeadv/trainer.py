@@ -663,6 +663,189 @@ class FreeAtStep:
         return self.loss.clone(), self.output.clone()
 
 
+# ---- fast adversarial training: FGSM from a random start (ImageNet/fgsm_imagenet/main_fast.py) ------------------
+def make_fast_sgd(model, lr, momentum=0.0, weight_decay=0.0):
+    """The optimiser of main_fast.py:99-112: two groups, the parameters that belong to a *BatchNorm* module with weight_decay = 0 and the
+    rest with `weight_decay`.  Built like make_sgd: torch's fused SGD on the device (as _FusedSGD, which tells the weight-derived filter
+    caches about every eager step), the default one otherwise."""
+    decay, no_decay = [], []
+    for m in model.modules():
+        for p in m.parameters(recurse=False):
+            (no_decay if 'BatchNorm' in type(m).__name__ else decay).append(p)
+    groups = [dict(params=decay), dict(params=no_decay, weight_decay=0)]
+    params = decay + no_decay
+    if _FUSED_SGD and params and all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        try:
+            return _FusedSGD(groups, lr=lr, momentum=momentum, weight_decay=weight_decay, fused=True)
+        except (TypeError, RuntimeError):
+            pass
+    return torch.optim.SGD(groups, lr=lr, momentum=momentum, weight_decay=weight_decay)
+
+
+def fast_at_step(model, criterion, optimizer, input, target, noise, fgsm_step, clip_eps, random_init, step_ctr, seed, injected_noise=None,
+                 j=0):
+    """Repeat `j` of one batch of fast adversarial training (main_fast.py:226-266), eager.  `noise` is the persistent buffer, its first
+    len(input) rows are read and updated in place; `step_ctr` the device int64 [1] counter of the drawn starts.  Returns (loss, output) of
+    the descend pass, detached, still on the device.
+
+        j == 0 and random_init: noise[:n] = U(-eps, eps) - or injected_noise -, in1 = clamp(input + noise[:n], 0, 1)
+                                                                              ee_fastat_start_f32   (:224-225, :233-235)
+        otherwise:              in1 = clamp(input + noise[:n], 0, 1)          ee_add_clamp_f32      (:233-235, as free-AT)
+        g = d loss / d in1 of a train-mode forward                            torch.autograd.grad   (:237-243)
+        noise[:n] = clamp(noise[:n] + step * sign(g masked by the clamp), +-eps); in1 = clamp(input + noise[:n], 0, 1); step_ctr += 1
+                                                                              ee_fastat_ascend_f32  (:246-253)
+        second train-mode forward, zero_grad, backward, optimizer.step()                            (:255-266)
+    The reference's ascend pass calls loss.backward(), which also accumulates weight gradients; zero_grad() at :259 discards them
+    before anything reads them, so asking autograd for the input gradient alone gives the same noise and the same update.  Both
+    forwards run in train mode: BatchNorm's running statistics advance twice per step, as in the reference."""
+    from eeadv import ops
+    from eeadv.functional import input_grad_only
+    n = input.size(0)
+    x = input.contiguous()
+    in1 = torch.empty_like(x)
+    if random_init and j == 0:
+        ops.fastat_start_(noise.view(-1), in1, x, float(clip_eps), seed, step_ctr, noise=injected_noise)
+    elif x.is_cuda:
+        in1 = ops.add_clamp(x, noise[0:n], 0.0, 1.0)
+    else:
+        ops.fastat_start_(noise.view(-1), in1, x, float(clip_eps), noise=noise[0:n])  # the host plumbing's add_clamp: delta is its own noise
+    in1.requires_grad_(True)
+    loss = criterion(model(in1), target)
+    with input_grad_only():
+        (g,) = torch.autograd.grad(loss, [in1])
+    in1 = in1.detach()  # write-only from here: the buffer the ascend forward read
+    ops.fastat_ascend_(noise.view(-1), in1, g.contiguous(), x, float(fgsm_step), float(clip_eps), step_ctr)
+    output = model(in1)
+    loss = criterion(output, target)
+    optimizer.zero_grad()
+    loss.backward()
+    optimizer.step()
+    return loss.detach(), output.detach()
+
+
+class FastAtStep:
+    """fast_at_step behind one captured HIP graph per batch shape, modelled on FreeAtStep: with graphs enabled, one rank, plain BatchNorm
+    and an SGD optimiser the first two steps run eagerly (they create the momentum buffers and let MIOpen pick its algorithms), the
+    third is captured - start, two forwards, the input-gradient pass, ascend, zero_grad, backward, the fused SGD step and the rebuild
+    of the weight-derived filter buffers - and every later one replays it.  Two things a replay must not freeze live in device memory:
+    the counter the start draws from (ee_fastat_ascend_f32 advances it) and the LEARNING RATE, a 0-dim float32 tensor handed to the
+    fused SGD as its `lr`; set_lr() fills it, outside the graph, before every step (main_fast.py:228-230) and nothing is re-captured.
+    `captures` counts the graphs taken.  Anything else (CPU tensors, graphs off, SyncBatchNorm, a wrapped model) runs fast_at_step."""
+
+    def __init__(self, model, criterion, optimizer, noise, fgsm_step, clip_eps, random_init=True, seed=0):
+        self.model, self.criterion, self.optimizer, self.noise = model, criterion, optimizer, noise
+        self.fgsm_step, self.clip_eps, self.random_init, self.seed = float(fgsm_step), float(clip_eps), bool(random_init), int(seed)
+        self.step_ctr = torch.zeros(1, dtype=torch.int64, device=noise.device)
+        self.lr_t = torch.zeros((), dtype=torch.float32, device=noise.device) if noise.is_cuda else None
+        self.graphs, self.captures, self.eager_left = {}, 0, EAGER_UPDATES_BEFORE_CAPTURE
+
+    def set_lr(self, v):
+        """The learning rate of the next step: on the device, filled into the tensor every group reads (a captured graph reads it too)"""
+        if self.lr_t is None:
+            for g in self.optimizer.param_groups:
+                g['lr'] = float(v)
+            return
+        self.lr_t.fill_(float(v))
+        for g in self.optimizer.param_groups:
+            if g['lr'] is not self.lr_t:  # at first use, and after optimizer.load_state_dict put a copy there
+                g['lr'] = self.lr_t
+
+    def state_dict(self):
+        """optimizer.state_dict() with the learning rates as plain numbers: what a checkpoint carries (main_fast.py:189)"""
+        sd = self.optimizer.state_dict()
+        sd['param_groups'] = [dict(g, lr=float(g['lr'])) for g in sd['param_groups']]
+        return sd
+
+    def _graphable(self, x):
+        from eeadv import engine
+        m = self.model
+        return (engine.graphs_enabled() and x.is_cuda and isinstance(self.optimizer, torch.optim.SGD) and m.training
+                and not isinstance(m, (nn.parallel.DistributedDataParallel, nn.DataParallel))
+                and not any(isinstance(k, nn.SyncBatchNorm) for k in m.modules()))
+
+    def _step(self, x, y, j, injected):
+        return fast_at_step(self.model, self.criterion, self.optimizer, x, y, self.noise, self.fgsm_step, self.clip_eps, self.random_init,
+                            self.step_ctr, self.seed, injected_noise=injected, j=j)
+
+    def __call__(self, x, y, j=0, injected_noise=None):
+        if not self._graphable(x):
+            return self._step(x, y, j, injected_noise)
+        key = (tuple(x.shape), tuple(y.shape), y.dtype, self.random_init and j == 0, injected_noise is not None)
+        slot = self.graphs.get(key)
+        if slot is None:  # a new batch shape runs eagerly once more: MIOpen must not search inside a capture
+            slot = self.graphs[key] = {"graph": None, "eager": max(self.eager_left, 1 if self.graphs else 0), "x": torch.empty_like(x),
+                                       "y": torch.empty_like(y), "inj": None if injected_noise is None else torch.empty_like(injected_noise)}
+        slot["x"].copy_(x)
+        slot["y"].copy_(y)
+        if injected_noise is not None:
+            slot["inj"].copy_(injected_noise)
+        if slot["eager"] > 0:
+            slot["eager"] -= 1
+            self.eager_left = max(self.eager_left - 1, 0)
+            return self._step(slot["x"], slot["y"], j, slot["inj"])
+        from eeadv.functional import rebuild_dense_weights, refresh_dense_weights
+        refresh_dense_weights()
+        if slot["graph"] is None:
+            runtime.draw_state(x.device)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph, capture_error_mode=runtime.capture_mode()):
+                slot["loss"], slot["output"] = self._step(slot["x"], slot["y"], j, slot["inj"])
+                slot["rebuilt"] = rebuild_dense_weights(self.model)
+            slot["graph"] = graph
+            self.captures += 1
+            self._param_ids = {id(p) for p in self.model.parameters()}
+        slot["graph"].replay()
+        self._rebuilt = slot["rebuilt"]
+        _mark_stale(self)
+        return slot["loss"].clone(), slot["output"].clone()
+
+
+def pgd_restarts(model, x, y, eps, K, step, restarts, seed, noises=None, use_graph=None):
+    """PGD with restarts as lib/validation.py:29-57 runs it on one batch, the model in eval mode: every restart starts at
+    clamp(x + U(-eps, eps), 0, 1) (:32-34; `noises`: one tensor of x's shape per restart instead of the draw keyed by (seed, restart)),
+    takes K steps of x = clamp(min(max(x + step * sign(g), x0 - eps), x0 + eps), 0, 1) on the mean cross-entropy (:35-48) through the
+    engine's captured loop, and the union keeps, per row, the point of the LAST restart that fools the model - restart 0 fills every
+    row and needs no forward (:51-57, ee_fastat_keep_f32).  Returns (final, output): the kept points and the logits of the final forward
+    (:59-63), both detached."""
+    if model.training:
+        raise ValueError("pgd_restarts attacks the model in eval mode (lib/validation.py:21)")
+    x0 = x.detach().contiguous()
+    if noises is not None and len(noises) != restarts:
+        raise ValueError("noises holds %d starts for %d restarts" % (len(noises), restarts))
+    final = torch.empty_like(x0)
+    for r in range(restarts):
+        if x0.is_cuda:
+            from eeadv import engine, ops
+            if noises is not None:
+                x_adv = ops.pgd_init(x0, noises[r].contiguous(), 0.0, 1.0)
+            else:
+                x_adv = ops.pgd_init_rng(x0, float(eps), 0, int(seed) & 0xFFFFFFFFFFFFFFFF, r << 32, 0.0, 1.0)
+            x_adv = engine.pgd_loop(model, x0, x_adv, engine.LossSpec(engine.CE_MEAN, y), K, step, eps, use_graph=use_graph)
+            with torch.no_grad():
+                if r == 0:
+                    ops.fastat_keep_(final, x_adv, first=True)
+                else:
+                    ops.fastat_keep_(final, x_adv, model(x_adv).contiguous(), y)
+        else:
+            runtime.require_device(x0, "pgd_restarts")
+            from eeadv import ops
+            nz = noises[r] if noises is not None else torch.from_numpy(ops.fastat_draw_host(x0.numel(), eps, seed, r)).view(x0.shape)
+            x_adv = torch.clamp(x0 + nz, 0.0, 1.0)
+            for _ in range(K):
+                xv = x_adv.clone().requires_grad_(True)
+                (g,) = torch.autograd.grad(nn.functional.cross_entropy(model(xv), y), [xv])
+                x_adv = torch.clamp(torch.min(torch.max(x_adv + step * torch.sign(g), x0 - eps), x0 + eps), 0.0, 1.0)
+            with torch.no_grad():
+                if r == 0:
+                    ops.fastat_keep_(final, x_adv, first=True)
+                else:
+                    ops.fastat_keep_(final, x_adv, model(x_adv), y)
+    with torch.no_grad():
+        output = model(final)
+    return final, output.detach()
+
+
 def eot_iter_for(args):
     """The EOT count of args.attack_method from args.eot_iter (--eot_iter; None / absent: 20 for Rand and Cascade-Rand, 1 for APGD-CE and
     APGD-DLR, which honour an explicit value).  Every other method has no EOT: a value above 1 stops here instead of being ignored."""

@@ -95,6 +95,49 @@ int ee_freeat_update_f32(float *delta, const float *g, int64_t n, float alpha, f
  * the clamp's gradient mask (0 <= x + delta <= 1) is applied in the kernel, dL/d(delta) never exists as a tensor. */
 int ee_freeat_update_masked_f32(float *delta, const float *g_in1, const float *x, int64_t n, float alpha, float eps, void *stream);
 
+/* ---- Fast adversarial training (FGSM from a random start), ee_fastat.hip; ImageNet/fgsm_imagenet/main_fast.py, DESIGN.md section 28 ----
+ * Three launches, each one grid-strided sweep: 128-bit accesses when n (per_sample for the third) % 4 == 0 and every float pointer is
+ * 16-byte aligned, word by word otherwise - the same bits from both.  Every operation is one f32 rounding in the order written.
+ *
+ * main_fast.py:224-225, 233-235 - the start of a batch, for i < n:
+ *     noise != NULL:  delta[i] = noise[i], copied as bits
+ *     noise == NULL:  delta[i] = clamp(0 + (u * (eps - (-eps)) + (-eps)), -eps, eps), u = (word >> 8) * 2^-24 with word = word (i & 3) of the
+ *                     Philox4x32-10 call keyed by `seed`, stream 0, counter (step[0] << 32) + (i >> 2): the bits ee_pgd_init_rng_f32(x0 = 0,
+ *                     scale = eps, dist 0, seed, offset = step[0] << 32, lo = -eps, hi = eps) writes
+ *     in1[i] = clamp(x[i] + delta[i], 0, 1): the bits of ee_add_clamp_f32; a NaN in x or delta gives NaN
+ * step is a device uint64[1] (8-byte aligned) that this launch READS and never writes - ee_fastat_ascend_f32 advances it - so a replayed
+ * graph draws fresh noise every time; it is not read when noise != NULL and may then be NULL.  The reference redraws its whole persistent
+ * buffer (:225); rows of delta beyond n are NOT drawn here: with random_init every step starts by drawing the n live elements, so the
+ * rest is never read before it is drawn.  delta may alias noise (the launch is then ee_add_clamp_f32 on the kept noise); delta and in1
+ * must not alias x or each other.  n/4 >= 2^32 (group indices (i >> 2) <= (n - 1) / 4 < 2^32 then stay in the counter's low word), eps < 0 or NaN: EE_ERR_SHAPE; a float pointer off 4 bytes, step
+ * off 8: EE_ERR_ALIGN; n == 0 launches nothing. */
+int ee_fastat_start_f32(float *delta, float *in1, const float *x, const float *noise, int64_t n, float eps, uint64_t seed,
+                        const uint64_t *step, void *stream);
+
+/* main_fast.py:246-253 - the noise update and the descend pass's input in one sweep, for i < n, with g = dL/d(in1) of the ascend pass:
+ *     s = x[i] + delta[i];  gd = (0 <= s && s <= 1) ? g[i] : 0          the gradient mask of the in-place clamp of :235 (a NaN s masks)
+ *     delta[i] = clamp(delta[i] + alpha * sign(gd), -eps, eps)          sign(+-0) = sign(NaN) = 0, sign(+-inf) = +-1
+ *     in1[i]   = clamp(x[i] + delta[i], 0, 1)                           with the NEW delta
+ * which is ee_freeat_update_masked_f32(delta, g, x, n, alpha, eps) followed by ee_add_clamp_f32(in1, x, delta, n, 0, 1), bit for bit, at
+ * 20 B of HBM traffic per element instead of 28.  Afterwards one thread writes step[0] += 1 (a vector store; nothing in this launch
+ * reads it); step == NULL: no counter.  in1 is write-only and may alias g (each element is read before it is written); delta and in1
+ * must not alias x or each other.  As the free-AT update, only the n live elements of the persistent buffer are touched (:248 clamps all
+ * of it; the rest is inside the box already).  n < 0: EE_ERR_SHAPE; a float pointer off 4 bytes, step off 8: EE_ERR_ALIGN; n == 0
+ * launches nothing and leaves the counter. */
+int ee_fastat_ascend_f32(float *delta, float *in1, const float *g, const float *x, int64_t n, float alpha, float eps, uint64_t *step,
+                         void *stream);
+
+/* lib/validation.py:51-57 - the union across PGD restarts, final and x [B, per_sample], logits [B, K], labels [B] (int64):
+ *     first != 0:  final[b] = x[b] for every row (:53; logits and labels are not read and may be NULL)
+ *     first == 0:  final[b] = x[b] where argmax_k logits[b, k] != labels[b] (:55-57), other rows of final are not written
+ * The arg-max is output.max(1)[1]'s: the LOWEST index among equal maxima (+0 and -0 are equal), and a row that holds a NaN gives the index
+ * of its FIRST NaN (torch 2.10 on the CPU: torch.tensor([[1., 3., 3.], [0., nan, nan]]).max(1)[1] is [1, 1]; -inf everywhere gives 0).
+ * A label outside [0, K) equals no index: the row is copied.  Rows are copied as bits.  One launch: workgroup (b, chunk) finds row b's
+ * arg-max for itself and copies its chunk.  final must not alias x (final == x: EE_ERR_SHAPE).  B < 0, per_sample < 1, K < 1 with
+ * first == 0: EE_ERR_SHAPE; labels off 8 bytes: EE_ERR_ALIGN; B == 0 launches nothing. */
+int ee_fastat_keep_f32(float *final_, const float *x, const float *logits, const int64_t *labels, int64_t B, int64_t K, int64_t per_sample,
+                       int first, void *stream);
+
 /* attacks.py:469-479 AVmixup vertex + per-sample mix.  wgt = float64[B] (numpy Beta(1,1) weights):
  *     v = clamp(x0 + (x - x0)*gamma, 0, 1);   out = float(double(x0)*w_b + double(v)*(1 - w_b)) */
 int ee_avmix_f32(float *out, const float *x, const float *x0, const double *wgt, int64_t B, int64_t per_sample,

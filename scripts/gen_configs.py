@@ -113,7 +113,67 @@ FILES = {
                                                         epsilon=E255[8], step_size_2=E255[2], num_steps_3=100, step_size_3=E255[2]),
 }
 
+
+# ---- ImageNet/fgsm_imagenet: the sixteen phase configs of fast adversarial training (sections TRAIN / ADV / DATA, main_fast.py) --------
+# (crop_size, batch_size, start_epoch, epochs, lr_epochs, lr_values, workers, r) per phase; eps -> (clip_eps, fgsm_step of the phases)
+FAST_PHASES = {
+    "phase1": (128, 512, 0, 6, [0, 1, 6], [0, 0.4, 0.04], 16, 12),
+    "phase2": (224, 224, 6, 12, [6, 12], [0.04, 0.004], 16, 16),
+    "phase3": (288, 128, 12, 15, [12, 15], [0.004, 0.0004], 4, 18),
+    "evaluate": (288, 128, 12, 15, [12, 15], [0.004, 0.0004], 4, 18),
+}
+FAST_EPS = {"2px": (2.0, 2.5), "4px": (4.0, 5.0)}
+
+
+def fast(eps, phase, ee):
+    crop, batch, start, epochs, lr_epochs, lr_values, workers, r = FAST_PHASES[phase]
+    clip, step = FAST_EPS[eps]
+    if phase == "evaluate" and eps == "2px":
+        step = 2.0  # configs_fast_2px_evaluate.yml:47 (unused by --evaluate)
+    attacks = [[50, 0.00392156862]] if phase == "evaluate" else [[10, 0.00392156862], [50, 0.00392156862]]
+    data = dict(workers=workers, max_color_value=255.0, img_size=0, batch_size=batch, crop_size=crop)
+    if ee:
+        data.update(r=r, w=1.0, low=38.0, high=76.0)
+    return dict(TRAIN=dict(arch="resnet50_EE" if ee else "resnet50", lr=0.1, momentum=0.9, weight_decay=0.0001, print_freq=10,
+                           mean=[0.485, 0.456, 0.406], std=[0.229, 0.224, 0.225], start_epoch=start, epochs=epochs, lr_epochs=lr_epochs,
+                           lr_values=lr_values, half=True, random_init=True),
+                ADV=dict(clip_eps=clip, fgsm_step=step, n_repeats=1, pgd_attack=attacks), DATA=data)
+
+
+def _scalar(v):
+    if isinstance(v, bool):
+        return "true" if v else "false"
+    if isinstance(v, str):
+        return "'%s'" % v
+    if isinstance(v, list):
+        return "[%s]" % ", ".join(_scalar(e) for e in v)
+    return str(v)
+
+
+def emit_sections(path, header, d):
+    """Two-level YAML: sections of scalars and plain lists (the reference writes its sequences as !!python/tuple)"""
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        f.write("# %s\n" % header)
+        for sec, body in d.items():
+            f.write("%s:\n" % sec)
+            for k, v in body.items():
+                if k == "pgd_attack":
+                    f.write("    %s:\n%s" % (k, "".join("    - %s\n" % _scalar(e) for e in v)))
+                else:
+                    f.write("    %s: %s\n" % (k, _scalar(v)))
+
+
+FAST_FILES = {}
+for _eps in FAST_EPS:
+    for _phase in FAST_PHASES:
+        FAST_FILES["ImageNet/fgsm_imagenet/configs/configs_fast_%s_%s.yml" % (_eps, _phase)] = fast(_eps, _phase, False)
+        FAST_FILES["ImageNet/fgsm_imagenet/configs_ee/configs_fast_%s_%s_ee.yml" % (_eps, _phase)] = fast(_eps, _phase, True)
+
 if __name__ == "__main__":
     for rel, d in FILES.items():
         emit(os.path.join(ROOT, rel), "effective values of the reference's %s (scripts/gen_configs.py)" % rel, d)
-    print("wrote %d configs" % len(FILES))
+    for rel, d in FAST_FILES.items():
+        emit_sections(os.path.join(ROOT, rel), "effective values of the reference's %s (scripts/gen_configs.py); arch: DESIGN.md section 28"
+                      % rel, d)
+    print("wrote %d configs" % (len(FILES) + len(FAST_FILES)))
