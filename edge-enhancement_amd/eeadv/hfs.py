@@ -136,10 +136,44 @@ def band_tables(H, W, r):
     return np.ascontiguousarray(np.concatenate(t1 + t2 + t3 + t4), dtype=np.float32), NUp
 
 
+def wide_tables(H, W, r):
+    """Fragment-ordered constant operands of ee_hfs_wide_f32 (planes up to 320 x 320, at most 48 kept row and 32 kept column
+    frequencies: ImageNet/fgsm_imagenet phase 3, 288 x 288, r = 18; csrc/ee_hfs_mfma.hip).  Layout = scripts/chain_emulate.py
+    wide_tables: t1 [Wp/4][NT][64] | t2 [Hp/16][MT2][4][64] | t3 [Hp/16][MT2][4][64] | t4 [Wp/16][NT][4][64] with MT2 = 2 NUp / 16,
+    NT = 2 NVp / 16; cos / sin blocks padded to NUp = 16, 32 or 48 row and NVp = 16 or 32 column frequencies.
+    Returns (float32 array, NUp, NVp)."""
+    us = np.array([u if u < H / 2 else u - H for u in keep_set(H, r)], dtype=np.float64)
+    vs = np.array([v for v in keep_set(W, r) if v <= W // 2], dtype=np.float64)
+    kap = np.array([1.0 if (v == 0 or (W % 2 == 0 and v == W // 2)) else 2.0 for v in vs])
+    NU, NV = len(us), len(vs)
+    if NU > 48 or NV > 32 or H > 320 or W > 320:
+        raise ValueError("wide_tables: %dx%d r=%d is outside ee_hfs_wide_f32's shape class" % (H, W, r))
+    NUp, NVp = (NU + 15) // 16 * 16, (NV + 15) // 16 * 16
+    MT2, NT = 2 * NUp // 16, 2 * NVp // 16
+    Hp, Wp = (H + 15) // 16 * 16, (W + 15) // 16 * 16
+    lanes = np.arange(64)
+    li, lg = lanes & 15, lanes >> 4
+    h, w = np.arange(H)[:, None], np.arange(W)[:, None]
+    Ch, Sh, Cw, Sw = np.zeros((Hp, NUp)), np.zeros((Hp, NUp)), np.zeros((Wp, NVp)), np.zeros((Wp, NVp))
+    Ch[:H, :NU], Sh[:H, :NU] = np.cos(2 * np.pi * h * us[None, :] / H), np.sin(2 * np.pi * h * us[None, :] / H)
+    Cw[:W, :NV], Sw[:W, :NV] = np.cos(2 * np.pi * w * vs[None, :] / W), np.sin(2 * np.pi * w * vs[None, :] / W)
+    dv = np.zeros(NVp)
+    dv[:NV] = kap / W
+    T1 = np.concatenate([Cw * dv, Sw * dv], 1)   # [Wp, 2 NVp]
+    CS = np.concatenate([Ch, Sh], 1)             # [Hp, 2 NUp]
+    T4 = np.concatenate([Cw.T, Sw.T], 0)         # [2 NVp, Wp]
+    t1 = [T1[4 * s + lg, 16 * nt + li] for s in range(Wp // 4) for nt in range(NT)]
+    t2 = [CS[16 * t + 4 * lg + rr, 16 * mt + li] for t in range(Hp // 16) for mt in range(MT2) for rr in range(4)]
+    t3 = [CS[16 * ht + li, 16 * kt + 4 * lg + rr] / H for ht in range(Hp // 16) for kt in range(MT2) for rr in range(4)]
+    t4 = [T4[16 * nt + 4 * lg + rr, 16 * wt + li] for wt in range(Wp // 16) for nt in range(NT) for rr in range(4)]
+    return np.ascontiguousarray(np.concatenate(t1 + t2 + t3 + t4), dtype=np.float32), NUp, NVp
+
+
 class HFSOperator:
     """Device-resident factors of the operator (which equals its own adjoint).  ROCm planes up to 64x64 go through the
     single-launch LDS kernel ee_hfs_f32, planes up to 256x256 (ImageNet 224x224, r = 16) through the matrix-core kernel
-    ee_hfs_mfma_f32; anything larger and the CPU plumbing path use the dense form."""
+    ee_hfs_mfma_f32, and what neither takes, up to 320x320 (fast-AT phase 3: 288x288, r = 18), through its two-bands-per-wavefront
+    sibling ee_hfs_wide_f32 (`self.wide`); anything larger and the CPU plumbing path use the dense form."""
 
     def __init__(self, H, W, r, device):
         Ar, Ai, B1, B2 = hfs_matrices(H, W, r)
@@ -156,6 +190,13 @@ class HFSOperator:
             try:
                 flat, nu_pad = band_tables(H, W, r)
                 self.mfma = (torch.from_numpy(flat).to(device), nu_pad)
+            except ValueError:
+                pass
+        self.wide = None   # ... and of the wide kernel for what neither of the two takes (two bands per wavefront, same file)
+        if torch.device(device).type == "cuda" and self.kernel is None and self.mfma is None:
+            try:
+                flat, nu_pad, nv_pad = wide_tables(H, W, r)
+                self.wide = (torch.from_numpy(flat).to(device), nu_pad, nv_pad)
             except ValueError:
                 pass
         f = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=torch.float32)
@@ -185,7 +226,7 @@ class HFSOperator:
     @property
     def fused_square(self):
         """True when Add_Square can be fused into the low-pass kernel's load / store (one launch each way)."""
-        return self.kernel is not None or self.mfma is not None
+        return self.kernel is not None or self.mfma is not None or self.wide is not None
 
     def forward(self, x):
         if x.is_cuda and self._use_lds_kernel:
@@ -194,6 +235,9 @@ class HFSOperator:
         if x.is_cuda and self.mfma is not None:
             from . import ops
             return ops.hfs_mfma(x.contiguous(), *self.mfma)
+        if x.is_cuda and self.wide is not None:
+            from . import ops
+            return ops.hfs_wide(x.contiguous(), *self.wide)
         return self._apply(x, self.Bcat, self.Ar, self.Ai)
 
     def adjoint(self, g):
@@ -203,6 +247,9 @@ class HFSOperator:
         if g.is_cuda and self.mfma is not None:
             from . import ops
             return ops.hfs_mfma(g.contiguous(), *self.mfma)
+        if g.is_cuda and self.wide is not None:
+            from . import ops
+            return ops.hfs_wide(g.contiguous(), *self.wide)
         return self._apply(g, self.BcatT, self.ArT, self.AiT)
 
     def forward_square(self, x, eps, draws):
@@ -211,6 +258,9 @@ class HFSOperator:
         if self._use_lds_kernel:
             t, NU, NV = self.kernel
             return ops.hfs(x.contiguous(), t, NU, NV, 1, None, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
+        if self.mfma is None:
+            t, nu_pad, nv_pad = self.wide
+            return ops.hfs_wide(x.contiguous(), t, nu_pad, nv_pad, 1, None, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
         t, nu_pad = self.mfma
         return ops.hfs_mfma(x.contiguous(), t, nu_pad, 1, None, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
 
@@ -220,6 +270,9 @@ class HFSOperator:
         if self._use_lds_kernel:
             t, NU, NV = self.kernel
             return ops.hfs(g.contiguous(), t, NU, NV, 2, x, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
+        if self.mfma is None:
+            t, nu_pad, nv_pad = self.wide
+            return ops.hfs_wide(g.contiguous(), t, nu_pad, nv_pad, 2, x, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
         t, nu_pad = self.mfma
         return ops.hfs_mfma(g.contiguous(), t, nu_pad, 2, x, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
 

@@ -1076,6 +1076,19 @@ int ee_hfs_mfma_table_floats(int H, int W, int nu_pad);
 int ee_hfs_mfma_f32(const float *in, float *out, int B, int C, int H, int W, const float *tables, int nu_pad, int sq_mode,
                     const float *sq_x, float eps, const float *stripe, const float *sq_sign, const int64_t *sq_pos, const int32_t *sq_size,
                     int nq, void *stream);
+/* ... and for planes past that class, up to 320 x 320 with at most 48 kept row and 32 kept column frequencies (ImageNet/fgsm_imagenet
+ * phase 3: 288 x 288, r = 18 keeps 36 and 18): the same chain with two consecutive 16-row bands per wavefront and [P | Q] up to 64
+ * columns wide (hfs_wide_kernel, same file).  nu_pad = 16, 32 or 48 and nv_pad = 16 or 32 = the kept row / column frequencies rounded
+ * up.  `tables`: ee_hfs_wide_table_floats(H, W, nu_pad, nv_pad) floats in MFMA fragment order (eeadv/hfs.py: wide_tables;
+ * scripts/chain_emulate.py wide_tables is the layout's specification), with Hp / Wp = H / W rounded up to 16, MT2 = 2 nu_pad / 16,
+ * NT = 2 nv_pad / 16 and lane l <-> (l & 15, l >> 4):
+ *   t1 [Wp/4][NT][64] | t2 [Hp/16][MT2][4][64] | t3 [Hp/16][MT2][4][64] | t4 [Wp/16][NT][4][64],   16-byte aligned.
+ * A size < 1 or a pad outside its set: EE_ERR_SHAPE; H or W > 320: EE_ERR_UNSUPPORTED (both also from ee_hfs_wide_table_floats);
+ * B == 0 launches nothing.  Same traffic, same sq_mode fusions, bit-reproducible (the bands are added in band order). */
+int ee_hfs_wide_table_floats(int H, int W, int nu_pad, int nv_pad);
+int ee_hfs_wide_f32(const float *in, float *out, int B, int C, int H, int W, const float *tables, int nu_pad, int nv_pad, int sq_mode,
+                    const float *sq_x, float eps, const float *stripe, const float *sq_sign, const int64_t *sq_pos, const int32_t *sq_size,
+                    int nq, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The whole EE front end of one PGD iteration in two launches (csrc/ee_chain.hip): one workgroup per image.

@@ -195,3 +195,96 @@ if __name__ == "__main__":
         got = big_apply(x, big_tables(H, W, r))
         print("band variant %dx%d r=%d: f64 err %.2e" % (H, W, r, np.abs(got - want).max()))
         assert np.abs(got - want).max() < 1e-11
+
+
+# ---- the wide variant past the band kernel's class: two bands per wavefront, [P | Q] up to 64 columns (hfs_wide_kernel) -----------------
+BPW = 2  # bands per wavefront
+
+
+def wide_tables(H, W, r, dtype=np.float64):
+    from eeadv.hfs import keep_set
+    us = np.array([u if u < H / 2 else u - H for u in keep_set(H, r)], dtype=np.float64)
+    vs = np.array([v for v in keep_set(W, r) if v <= W // 2], dtype=np.float64)
+    kap = np.array([1.0 if (v == 0 or (W % 2 == 0 and v == W // 2)) else 2.0 for v in vs])
+    NU, NV = len(us), len(vs)
+    assert NU <= 48 and NV <= 32 and H <= 320 and W <= 320
+    NUp, NVp = (NU + 15) // 16 * 16, (NV + 15) // 16 * 16
+    MT2, NT = 2 * NUp // 16, 2 * NVp // 16
+    Hp, Wp = (H + 15) // 16 * 16, (W + 15) // 16 * 16
+    h, w = np.arange(H)[:, None], np.arange(W)[:, None]
+    Ch = np.zeros((Hp, NUp)); Sh = np.zeros((Hp, NUp)); Cw = np.zeros((Wp, NVp)); Sw = np.zeros((Wp, NVp))
+    Ch[:H, :NU] = np.cos(2 * np.pi * h * us[None, :] / H)
+    Sh[:H, :NU] = np.sin(2 * np.pi * h * us[None, :] / H)
+    Cw[:W, :NV] = np.cos(2 * np.pi * w * vs[None, :] / W)
+    Sw[:W, :NV] = np.sin(2 * np.pi * w * vs[None, :] / W)
+    dv = np.zeros(NVp); dv[:NV] = kap / W
+    T1m = np.concatenate([Cw * dv, Sw * dv], 1)   # [Wp, 2 NVp]: P tiles nt < NT / 2, Q tiles above
+    CS = np.concatenate([Ch, Sh], 1)              # [Hp, 2 NUp]
+    T4m = np.concatenate([Cw.T, Sw.T], 0)         # [2 NVp, Wp]
+    t1 = np.stack([T1m[4 * s + LG, 16 * nt + LI] for s in range(Wp // 4) for nt in range(NT)])
+    t2 = np.stack([CS[16 * t + 4 * LG + rr, 16 * mt + LI] for t in range(Hp // 16) for mt in range(MT2) for rr in range(4)])
+    t3 = np.stack([CS[16 * ht + LI, 16 * kt + 4 * LG + rr] / H for ht in range(Hp // 16) for kt in range(MT2) for rr in range(4)])
+    t4 = np.stack([T4m[16 * nt + 4 * LG + rr, 16 * wt + LI] for wt in range(Wp // 16) for nt in range(NT) for rr in range(4)])
+    return {"t1": t1.astype(dtype), "t2": t2.astype(dtype), "t3": t3.astype(dtype), "t4": t4.astype(dtype), "Hp": Hp, "Wp": Wp, "MT2": MT2,
+            "NT": NT}
+
+
+def wide_apply(x, T):
+    H, W = x.shape
+    Hp, Wp, MT2, NT = T["Hp"], T["Wp"], T["MT2"], T["NT"]
+    dt = T["t1"].dtype
+    xp = np.zeros((Hp, Wp), dt)
+    xp[:H, :W] = x
+    NB, WT, half, nh = Hp // 16, Wp // 16, MT2 // 2, NT // 2
+    NW = (NB + BPW - 1) // BPW
+    Rsum = [[np.zeros((64, 4), dt) for _ in range(NT)] for _ in range(MT2)]
+    for wv in range(NW):  # one wavefront per BPW consecutive bands (the last one may own fewer)
+        bands = [b for b in range(wv * BPW, wv * BPW + BPW) if b < NB]
+        pq = {}
+        for b in bands:
+            pq[b] = [np.zeros((64, 4), dt) for _ in range(NT)]
+            for s in range(Wp // 4):
+                for nt in range(NT):
+                    pq[b][nt] = mfma(xp[16 * b + LI, 4 * s + LG], T["t1"][s * NT + nt], pq[b][nt])
+        rc = [[np.zeros((64, 4), dt) for _ in range(NT)] for _ in range(MT2)]
+        for b in bands:  # the wave's bands accumulate into the same tiles
+            for mt in range(MT2):
+                for rr in range(4):
+                    for nt in range(NT):
+                        rc[mt][nt] = mfma(T["t2"][(b * MT2 + mt) * 4 + rr], pq[b][nt][:, rr], rc[mt][nt])
+        for mt in range(MT2):
+            for nt in range(NT):
+                Rsum[mt][nt] = Rsum[mt][nt] + rc[mt][nt]  # the reduction over the waves, in wave order (through LDS on the device)
+    EF = [[None] * NT for _ in range(MT2)]
+    for j in range(half):
+        for p in range(nh):
+            a, c, bb, d = Rsum[j][p], Rsum[j][nh + p], Rsum[half + j][p], Rsum[half + j][nh + p]
+            EF[j][p], EF[j][nh + p] = a - d, c + bb
+            EF[half + j][p], EF[half + j][nh + p] = bb + c, d - a
+    y = np.zeros((Hp, Wp), dt)
+    for b in range(NB):
+        uvT = [np.zeros((64, 4), dt) for _ in range(NT)]
+        for kt in range(MT2):
+            for rr in range(4):
+                for nt in range(NT):
+                    uvT[nt] = mfma(EF[kt][nt][:, rr], T["t3"][(b * MT2 + kt) * 4 + rr], uvT[nt])
+        for wt in range(WT):
+            acc = np.zeros((64, 4), dt)
+            for nt in range(NT):
+                for rr in range(4):
+                    acc = mfma(uvT[nt][:, rr], T["t4"][(wt * NT + nt) * 4 + rr], acc)
+            for rr in range(4):
+                y[16 * b + 4 * LG + rr, 16 * wt + LI] = acc[:, rr]
+    return y[:H, :W]
+
+
+if __name__ == "__main__":
+    from eeadv.hfs import hfs_matrices
+    rng = np.random.RandomState(2)
+    for (H, W, r) in [(288, 288, 18), (260, 40, 3), (33, 262, 5), (289, 291, 18), (272, 304, 20), (320, 320, 24)]:
+        x = rng.rand(H, W)
+        Ar, Ai, B1, B2 = hfs_matrices(H, W, r)
+        want = Ar @ x @ B1 + Ai @ x @ B2
+        got = wide_apply(x, wide_tables(H, W, r))
+        print("wide variant %dx%d r=%d: f64 err %.2e" % (H, W, r, np.abs(got - want).max()))
+        assert np.abs(got - want).max() < 1e-11

@@ -28,14 +28,36 @@ def timeit(fn, iters=20, reps=3):
     return 1e3 * a.elapsed_time(b) / (iters * reps)
 
 
+def report(name, shape, us, nbytes):
+    print("%-34s %4dx%dx%dx%d  %9.2f us  %8.1f GB/s (%.2f of 8 TB/s)" % ((name,) + shape + (us, nbytes / us / 1e3, nbytes / us / 1e3 / 8000)))
+
+
 for (B, C, n, r) in [(32, 3, 224, 16), (256, 3, 224, 16), (100, 3, 64, 8), (1600, 3, 64, 8), (50, 1, 28, 4)]:
     x = torch.rand(B, C, n, n, device="cuda:0")
     op = HF.HFSOperator(n, n, r, "cuda:0")
-    nbytes = 8 * x.numel()
     rows = [("mfma band kernel", lambda: ops.hfs_mfma(x, *op.mfma))]
     if op.kernel is not None:
         rows.append(("LDS kernel (VALU)", lambda: ops.hfs(x, *op.kernel)))
     rows.append(("dense rocBLAS x3", lambda: op._apply(x, op.Bcat, op.Ar, op.Ai)))
     for name, fn in rows:
-        us = timeit(fn)
-        print("%-20s %4dx%dx%dx%d  %9.2f us  %8.1f GB/s (%.2f of 8 TB/s)" % (name, B, C, n, n, us, nbytes / us / 1e3, nbytes / us / 1e3 / 8000))
+        report(name, (B, C, n, n), timeit(fn), 8 * x.numel())
+
+# fast-AT phase 3 (crop 288, r = 18): the wide kernel against the dense form it replaces, plain and with Add_Square - fused into the
+# kernel (sq_mode 1 forward, 2 backward) against a launch of its own around the three rocBLAS calls.  Median of five timings.
+import utils.core as core  # noqa: E402
+
+for (B, C, n, r) in [(128, 3, 288, 18), (32, 3, 288, 18)]:
+    x, g = torch.rand(B, C, n, n, device="cuda:0"), torch.randn(B, C, n, n, device="cuda:0")
+    op = HF.HFSOperator(n, n, r, "cuda:0")
+    eps = 16 / 255
+    d = core.Add_Square(C, n, eps, n_queries=1).prepare(x)
+    sq = (eps, d["stripe"], d["sq_sign"], d["sq_pos"], d["sq_size"])
+    tab, nu_pad, nv_pad = op.wide
+    rows = [("wide kernel", 8, lambda: ops.hfs_wide(x, tab, nu_pad, nv_pad)),
+            ("dense rocBLAS x3", 8, lambda: op._apply(x, op.Bcat, op.Ar, op.Ai)),
+            ("wide kernel, Add_Square fwd", 8, lambda: ops.hfs_wide(x, tab, nu_pad, nv_pad, 1, None, *sq)),
+            ("add_square_fwd + dense", 8, lambda: op._apply(ops.add_square_fwd(x, *sq), op.Bcat, op.Ar, op.Ai)),
+            ("wide kernel, Add_Square bwd", 12, lambda: ops.hfs_wide(g, tab, nu_pad, nv_pad, 2, x, *sq)),
+            ("dense adjoint + add_square_bwd", 12, lambda: ops.add_square_bwd(op._apply(g, op.BcatT, op.ArT, op.AiT), x, *sq))]
+    for name, bpe, fn in rows:
+        report(name, (B, C, n, n), sorted(timeit(fn) for _ in range(5))[2], bpe * x.numel())
