@@ -100,6 +100,36 @@ __device__ __forceinline__ float propose(float xb, float x0, const Sample &sm, i
     return proj_linf(xb + delta, x0, eps);
 }
 
+// what a step launch knows apart from the element it is at
+struct Step {
+    float *x_best, *x_new;
+    const float *x0;
+    const int *flags;
+    const float *margin_min;
+    Philox ph;
+    int it, s, H, W, HW;
+    int64_t per_sample;
+    float eps;
+};
+
+// one element's turn: its sample's decision, the commit, the proposal
+__device__ __forceinline__ void element_turn(const Step &k, int64_t e) {
+    const int64_t b = e / k.per_sample;
+    const int r = static_cast<int>(e - b * k.per_sample);
+    const Sample sm = sample_of(b, k.flags, k.margin_min, k.ph, k.it, k.s, k.H, k.W);
+    if (!sm.commit && !sm.propose) return;
+    float xb;
+    if (sm.commit) {
+        xb = k.x_new[e];
+        k.x_best[e] = xb;
+    } else {
+        xb = k.x_best[e];
+    }
+    if (!sm.propose) return;
+    const int c = r / k.HW, h = (r - c * k.HW) / k.W, w = r - c * k.HW - h * k.W;
+    k.x_new[e] = propose(xb, k.x0[e], sm, c, h, w, k.s, k.eps);
+}
+
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void step_kernel(float *x_best, float *x_new, const float *__restrict__ x0, const int *__restrict__ flags,
                                                       const float *__restrict__ margin_min, const int *__restrict__ counter,
@@ -108,9 +138,9 @@ __global__ __launch_bounds__(kBlock) void step_kernel(float *x_best, float *x_ne
     const int it = counter[0];
     int s = (it >= 0 && it < n_sizes) ? sizes[it] : 0;  // 0: no proposal in this launch (commit only)
     if (s < 1 || s > H || s > W) s = 0;                 // a size the window arithmetic cannot take is no proposal either
-    const Philox ph(static_cast<uint64_t>(seed[0]));
     const int HW = H * W;
     const int64_t per_sample = static_cast<int64_t>(C) * HW;
+    const Step k{x_best, x_new, x0, flags, margin_min, Philox(static_cast<uint64_t>(seed[0])), it, s, H, W, HW, per_sample, eps};
     const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     const int64_t nv = VEC == 4 ? (n >> 2) : 0;
@@ -118,77 +148,46 @@ __global__ __launch_bounds__(kBlock) void step_kernel(float *x_best, float *x_ne
         const int64_t base = v << 2;
         const int64_t b = base / per_sample;
         const int r = static_cast<int>(base - b * per_sample);
-        if (r + 4 <= per_sample) {  // the four elements belong to one sample (they may straddle rows and channels)
-            const Sample sm = sample_of(b, flags, margin_min, ph, it, s, H, W);
-            if (!sm.commit && !sm.propose) continue;
-            float4 xb;
-            if (sm.commit) {
-                xb = reinterpret_cast<const float4 *>(x_new)[v];
-                reinterpret_cast<float4 *>(x_best)[v] = xb;
-            } else {
-                xb = reinterpret_cast<const float4 *>(x_best)[v];
-            }
-            if (!sm.propose) continue;
-            const float4 v0 = reinterpret_cast<const float4 *>(x0)[v];
-            int c = r / HW, h = (r - c * HW) / W, w = r - c * HW - h * W;
-            const float in[4] = {xb.x, xb.y, xb.z, xb.w}, o0[4] = {v0.x, v0.y, v0.z, v0.w};
-            float out[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                out[k] = propose(in[k], o0[k], sm, c, h, w, s, eps);
-                if (++w == W) {
-                    w = 0;
-                    if (++h == H) h = 0, ++c;
-                }
-            }
-            reinterpret_cast<float4 *>(x_new)[v] = make_float4(out[0], out[1], out[2], out[3]);
-        } else {  // a vector across two (or more) samples: element by element
-            for (int k = 0; k < 4; ++k) {
-                const int64_t e = base + k;
-                const int64_t be = e / per_sample;
-                const int re = static_cast<int>(e - be * per_sample);
-                const Sample sm = sample_of(be, flags, margin_min, ph, it, s, H, W);
-                if (!sm.commit && !sm.propose) continue;
-                float xb;
-                if (sm.commit) {
-                    xb = x_new[e];
-                    x_best[e] = xb;
-                } else {
-                    xb = x_best[e];
-                }
-                if (!sm.propose) continue;
-                const int c = re / HW, h = (re - c * HW) / W, w = re - c * HW - h * W;
-                x_new[e] = propose(xb, x0[e], sm, c, h, w, s, eps);
-            }
+        if (r + 4 > per_sample) {  // a vector across two (or more) samples: element by element
+            for (int j = 0; j < 4; ++j) element_turn(k, base + j);
+            continue;
         }
-    }
-    for (int64_t e = (nv << 2) + i; e < n; e += stride) {
-        const int64_t be = e / per_sample;
-        const int re = static_cast<int>(e - be * per_sample);
-        const Sample sm = sample_of(be, flags, margin_min, ph, it, s, H, W);
+        // the four elements belong to one sample (they may straddle rows and channels): element_turn's lines on float4 accesses
+        const Sample sm = sample_of(b, flags, margin_min, k.ph, it, s, H, W);
         if (!sm.commit && !sm.propose) continue;
-        float xb;
+        float4 xb;
         if (sm.commit) {
-            xb = x_new[e];
-            x_best[e] = xb;
+            xb = reinterpret_cast<const float4 *>(x_new)[v];
+            reinterpret_cast<float4 *>(x_best)[v] = xb;
         } else {
-            xb = x_best[e];
+            xb = reinterpret_cast<const float4 *>(x_best)[v];
         }
         if (!sm.propose) continue;
-        const int c = re / HW, h = (re - c * HW) / W, w = re - c * HW - h * W;
-        x_new[e] = propose(xb, x0[e], sm, c, h, w, s, eps);
+        const float4 v0 = reinterpret_cast<const float4 *>(x0)[v];
+        int c = r / HW, h = (r - c * HW) / W, w = r - c * HW - h * W;
+        const float in[4] = {xb.x, xb.y, xb.z, xb.w}, o0[4] = {v0.x, v0.y, v0.z, v0.w};
+        float out[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            out[j] = propose(in[j], o0[j], sm, c, h, w, s, eps);
+            if (++w == W) {
+                w = 0;
+                if (++h == H) h = 0, ++c;
+            }
+        }
+        reinterpret_cast<float4 *>(x_new)[v] = make_float4(out[0], out[1], out[2], out[3]);
     }
+    for (int64_t e = (nv << 2) + i; e < n; e += stride) element_turn(k, e);
 }
 
 }  // namespace
 
 EE_API int ee_sqatk_init_f32(float *x_best, float *x_new, const float *x0, const int64_t *seed, int B, int C, int H, int W, float eps,
                              void *stream) {
-    const int rc = sqatk_check_shape(B, C, H, W);
+    int rc = sqatk_check_shape(B, C, H, W);
     if (rc != EE_OK) return rc;
     if (B == 0) return EE_OK;
-    if (!x_best || !x_new || !x0 || !seed) return EE_ERR_NULL;
-    if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || (reinterpret_cast<uintptr_t>(seed) & 7u)) return EE_ERR_ALIGN;
+    if ((rc = sqatk_check_ptrs(seed, {x_best, x_new, x0})) != EE_OK) return rc;
     const int64_t n = static_cast<int64_t>(B) * C * H * W;
     ProfScope prof(EE_K_SQATK_INIT, as_stream(stream));
     EE_LAUNCH(init_kernel, dim3(grid_for(n)), dim3(kBlock), 0, as_stream(stream), x_best, x_new, x0, seed, n, C, H, W, eps);
@@ -211,14 +210,11 @@ EE_API int ee_sqatk_margin_f32(const float *logits, const int64_t *labels, int B
 
 EE_API int ee_sqatk_step_f32(float *x_best, float *x_new, const float *x0, const int *flags, const float *margin_min, const int *counter,
                              const int *sizes, int n_sizes, const int64_t *seed, int B, int C, int H, int W, float eps, void *stream) {
-    const int rc = sqatk_check_shape(B, C, H, W);
+    int rc = sqatk_check_shape(B, C, H, W);
     if (rc != EE_OK) return rc;
     if (n_sizes < 0) return EE_ERR_SHAPE;
     if (B == 0) return EE_OK;
-    if (!x_best || !x_new || !x0 || !flags || !margin_min || !counter || !seed || (n_sizes > 0 && !sizes)) return EE_ERR_NULL;
-    if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || !aligned4(flags) || !aligned4(margin_min) || !aligned4(counter) ||
-        !aligned4(sizes) || (reinterpret_cast<uintptr_t>(seed) & 7u))
-        return EE_ERR_ALIGN;
+    if ((rc = sqatk_check_ptrs(seed, {x_best, x_new, x0, flags, margin_min, counter}, n_sizes > 0, {sizes})) != EE_OK) return rc;
     const int64_t n = static_cast<int64_t>(B) * C * H * W;
     const bool vec = aligned16(x_best) && aligned16(x_new) && aligned16(x0);
     ProfScope prof(EE_K_SQATK_STEP, as_stream(stream));

@@ -1,6 +1,9 @@
-// ee_sqatk.hpp - what the two Square attacks (ee_sqatk.hip: Linf; ee_sqatk_l2.hip: L2) share: the Philox stream ids, the window draw of
-// proposal i and sample b, and the shape check.  One definition each, so that a window of an L2 run is the window a Linf run would draw.
+// ee_sqatk.hpp - what the three Square attacks (ee_sqatk.hip: Linf; ee_sqatk_l2.hip: L2; ee_sqatk_l1.hip: L1) share: the Philox stream
+// ids, the window draw of proposal i and sample b, and the entry points' shape and pointer checks.  One definition each, so that a window
+// of an L2 run is the window a Linf run would draw.
 #pragma once
+
+#include <initializer_list>
 
 #include "ee_common.hpp"
 
@@ -34,6 +37,17 @@ static inline int sqatk_check_shape(int B, int C, int H, int W) {
     if (static_cast<int64_t>(C) * H * W > INT32_MAX) return EE_ERR_SHAPE;
     if (C > 32) return EE_ERR_UNSUPPORTED;  // one sign bit per channel in a 32-bit draw
     return EE_OK;
+}
+
+// The pointers of an init or step launch, whatever the norm: EE_ERR_NULL, then EE_ERR_ALIGN.  `need` (the images and the launch's own
+// extras) must be there; `tables` (sizes, eta_off, eta of a step) only when the launch reads them, n_sizes > 0.  All are 4-byte aligned,
+// the seed 8-byte.
+static inline int sqatk_check_ptrs(const int64_t *seed, std::initializer_list<const void *> need, bool read_tables = false,
+                                   std::initializer_list<const void *> tables = {}) {
+    bool null = !seed, skew = (reinterpret_cast<uintptr_t>(seed) & 7u) != 0;
+    for (const void *p : need) null |= !p, skew |= !aligned4(p);
+    for (const void *p : tables) null |= read_tables && !p, skew |= !aligned4(p);
+    return null ? EE_ERR_NULL : skew ? EE_ERR_ALIGN : EE_OK;
 }
 
 }  // namespace ee

@@ -1,7 +1,7 @@
 // ee_sqatk_l1.hip - the Square attack in the L1 threat model (Croce & Hein 2021, "Mind the box"): the two launches
 // that stand in the place of ee_sqatk_init_f32 and ee_sqatk_step_f32 in an L1 run.  The margin launch, the counter, the flags and the
-// query count do not know the norm (ee_sqatk.hip); pattern, windows, draws and the window-1 update are the L2 run's (ee_sqatk_prop.hpp);
-// the projection is ee_l1_proj_f32's (ee_l1_proj.hpp).
+// query count do not know the norm (ee_sqatk.hip); pattern, windows, draws and the window-1 update are the L2 run's by construction - the
+// step is propose_window (ee_sqatk_prop.hpp) under the policy below, then the projection, which is ee_l1_proj_f32's (ee_l1_proj.hpp).
 //
 // eps is the L1 radius, eps_p <= eps the radius every projection uses (the host forms it).  P_r(u) is the Euclidean projection onto
 // {z : ||z - x0||_1 <= r} n [0,1]^D.  tiny = 1e-12f - every operation rounded once in f32:
@@ -32,7 +32,15 @@ namespace {
 
 using namespace ee;
 
-__device__ __forceinline__ double mag(float v) { return fabs(static_cast<double>(v)); }
+// the L1 norm of propose_window
+struct NormL1 {
+    static constexpr int kHead = 2;  // n_img, n_un
+    static __device__ __forceinline__ double term(float v) { return fabs(static_cast<double>(v)); }
+    static __device__ __forceinline__ float fin(double s) { return static_cast<float>(s); }
+    static __device__ __forceinline__ float scale(float eps, float n_img, float n_un, int C) {
+        return tmax(eps - n_img, 0.0f) / static_cast<float>(C) + n_un;
+    }
+};
 
 // (w, lo) of u = x0 + v, four at a time
 __device__ __forceinline__ void coords4(const float (&cv)[4], const float (&vv)[4], float (&wv)[4], float (&lv)[4]) {
@@ -56,18 +64,11 @@ __global__ __launch_bounds__(kSampleBlock) void init_l1_kernel(float *__restrict
     const float *cr = x0 + b * D;
     float *br = x_best + b * D, *nr = x_new + b * D;
     const int groups = groups_of(D);
-    const Philox ph(static_cast<uint64_t>(seed[0]));
-    Tiling tl;
-    tl.s0 = s0, tl.nh = H / s0, tl.nw = W / s0, tl.oh = (H - tl.nh * s0) / 2, tl.ow = (W - tl.nw * s0) / 2, tl.id = b, tl.eta = eta;
-    // an element's d travels in Info::idx as its bits
-    const auto one = [&](int c, int h, int w) { return Info{0u, __float_as_int(tl.value(ph, c, h, w))}; };
+    const Tiling tl(seed, eta, s0, H, W, b);
     const auto group = [&](int64_t e, float (&cv)[4], float (&wv)[4], float (&lv)[4]) {
         float dv[4];
-        Info in[4];
         load4<VEC>(cr, e, D, cv);
-        infos4(e, geo, in, one);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dv[j] = __int_as_float(in[j].idx);
+        tl.d4(e, geo, dv);
         coords4(cv, dv, wv, lv);
     };
 
@@ -115,129 +116,18 @@ __global__ __launch_bounds__(kSampleBlock) void step_l1_kernel(float *x_best, fl
     __shared__ int shi[2 * kSampleWaves];
     Reducer rnd{part};
     SampleReducer red{shd, shi};
-    const Geo geo{C, H, W, H * W, static_cast<int64_t>(C) * H * W};
-    const int64_t b = blockIdx.x, D = geo.D;
-    const int it = counter[0];
-    int s = (it >= 0 && it < n_sizes) ? sizes[it] : 0;  // 0: no proposal in this launch (commit only)
-    if (s < 1 || s > H || s > W) s = 0;                 // a size the window arithmetic cannot take is no proposal either
-    const int off = s ? eta_off[it] : 0;
-    if (off < 0) s = 0;
-    const bool commit = flags[b] != 0, propose = s > 0 && !(margin_min[b] <= 0.0f);  // uniform over the workgroup
-    if (!propose) {
-        const int t = static_cast<int>(threadIdx.x);
-        if (t < 2 + 2 * C) norms[static_cast<int64_t>(t) * B + b] = 0.0f;
-        if (t < 4) scal[static_cast<int64_t>(t) * B + b] = 0.0f;
-    }
-    if (!commit && !propose) return;
-    const float *cr = x0 + b * D;
-    float *br = x_best + b * D, *nr = x_new + b * D;
-    const int groups = groups_of(D);
-    if (!propose) {  // the commit alone
-        for (int k = 0; k < groups; ++k) {
-            float v[4];
-            load4<VEC>(nr, group_element(k), D, v);
-            store4<VEC>(br, group_element(k), D, v);
-        }
-        return;
-    }
-    const Philox ph(static_cast<uint64_t>(seed[0]));
-    const WindowDraw w1 = draw_window(ph, it, b, s, H, W, kStreamWindow), w2 = draw_window(ph, it, b, s, H, W, kStreamWindow2);
     Proposal p;
-    p.s = s, p.vh = w1.vh, p.vw = w1.vw, p.vh2 = w2.vh, p.vw2 = w2.vw, p.signs = w1.z, p.transpose = (w1.w & 1u) != 0;
-    p.eta = eta + off, p.n_w = sn1 + 2, p.n_new = sn2, p.scale = 0.0f;
-    const auto one = [&](int c, int h, int w) { return p.info(c, h, w); };
-
-    // round 1: n_img, n_un over the whole sample - the pass that commits, and that takes the sample into registers on the resident path
+    Stream<VEC> stream;
     float rc[kSampleElems], rv[kSampleElems], rl[kSampleElems];  // rv: delta, then new, then w = u - x0; rl: lo, the projection's alone
     Info ri[kSampleElems];                                       // the proposal's alone
-    double a_img = 0.0, a_un = 0.0;
-    const auto first = [&](int64_t e, float (&cv)[4], float (&dv)[4], Info (&in)[4]) {
-        float xv[4];
-        load4<VEC>(commit ? nr : br, e, D, xv);
-        if (commit) store4<VEC>(br, e, D, xv);
-        load4<VEC>(cr, e, D, cv);
-        infos4(e, geo, in, one);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            dv[j] = xv[j] - cv[j];
-            const double q = mag(dv[j]);
-            a_img += q;
-            a_un += (in[j].f & (kIn1 | kIn2)) ? q : 0.0;
-        }
-    };
-    if (RES) {
-#pragma unroll
-        for (int k = 0; k < kSampleVecs; ++k) {
-            float cv[4], dv[4];
-            Info in[4];
-            first(group_element(k), cv, dv, in);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rc[k * 4 + j] = cv[j], rv[k * 4 + j] = dv[j], ri[k * 4 + j] = in[j];
-        }
-    } else {
-        for (int k = 0; k < groups; ++k) {
-            float cv[4], dv[4];
-            Info in[4];
-            first(group_element(k), cv, dv, in);
-        }
+    const StepArgs a{x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off, eta, n_sizes, seed, norms, B, C, H, W, eps};
+    const int64_t b = blockIdx.x, D = static_cast<int64_t>(C) * H * W;
+    if (!propose_window<NormL1, RES, VEC>(a, rnd, sn1, sn2, p, stream, rc, rv, ri)) {  // no proposal, no projection: its rows are zeros
+        if (threadIdx.x < 4) scal[static_cast<int64_t>(threadIdx.x) * B + b] = 0.0f;
+        return;
     }
-    rnd.put(0, a_img);
-    rnd.put(1, a_un);
-    // the streaming path from here on: (x0, delta, info) of a group, skipped when `want` says the pass has no use for it
-    const auto stream = [&](int k, auto want, auto body) {
-        const int64_t e = group_element(k);
-        Info in[4];
-        infos4(e, geo, in, one);
-        if (!want(in)) return;
-        float xv[4], cv[4], dv[4];
-        load4<VEC>(br, e, D, xv);
-        load4<VEC>(cr, e, D, cv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dv[j] = xv[j] - cv[j];
-        body(e, cv, dv, in);
-    };
-    // n_w[c]: window 1 of channel c
-    for (int c = 0; c < C; ++c) {
-        double acc = 0.0;
-        if (RES) {
-#pragma unroll
-            for (int k = 0; k < kSampleElems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? mag(rv[k]) : 0.0;
-        } else {
-            for (int k = 0; k < groups; ++k)
-                stream(k, [&](const Info(&in)[4]) { return any_in1(in, c); },
-                       [&](int64_t, const float(&)[4], const float(&dv)[4], const Info(&in)[4]) {
-#pragma unroll
-                           for (int j = 0; j < 4; ++j) acc += ((in[j].f & kIn1) && channel_of(in[j]) == c) ? mag(dv[j]) : 0.0;
-                       });
-        }
-        rnd.put(2 + c, acc);
-    }
-    const auto as_float = [](double r) { return static_cast<float>(r); };
-    rnd.sums(2 + C, sn1, norms, B, b, [](int k) { return k; }, as_float);
-    p.scale = tmax(eps - sn1[0], 0.0f) / static_cast<float>(C) + sn1[1];
-
-    // round 2: n_new[c]
-    if (RES) {
-#pragma unroll
-        for (int k = 0; k < kSampleElems; ++k) rv[k] = p.stage1(rv[k], ri[k]);
-    }
-    for (int c = 0; c < C; ++c) {
-        double acc = 0.0;
-        if (RES) {
-#pragma unroll
-            for (int k = 0; k < kSampleElems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? mag(rv[k]) : 0.0;
-        } else {
-            for (int k = 0; k < groups; ++k)
-                stream(k, [&](const Info(&in)[4]) { return any_in1(in, c); },
-                       [&](int64_t, const float(&)[4], const float(&dv)[4], const Info(&in)[4]) {
-#pragma unroll
-                           for (int j = 0; j < 4; ++j)
-                               acc += ((in[j].f & kIn1) && channel_of(in[j]) == c) ? mag(p.stage1(dv[j], in[j])) : 0.0;
-                       });
-        }
-        rnd.put(c, acc);
-    }
-    rnd.sums(C, sn2, norms, B, b, [C](int k) { return 2 + C + k; }, as_float);
+    float *nr = x_new + b * D;
+    const int groups = groups_of(D);
 
     // u = x0 + delta and its projection: from here on the resident path holds (x0, w, lo) and what is known of an element is dead
     if (RES) {
@@ -282,13 +172,11 @@ int check_sq_l1(int B, int C, int H, int W, float eps, float eps_p, int path, bo
 EE_API int ee_sqatk_init_l1_f32(float *x_best, float *x_new, const float *x0, const int64_t *seed, const float *eta, int s0, float *scal,
                                 int B, int C, int H, int W, float eps, float eps_p, int path, void *stream) {
     bool res = false;
-    const int rc = check_sq_l1(B, C, H, W, eps, eps_p, path, &res);
+    int rc = check_sq_l1(B, C, H, W, eps, eps_p, path, &res);
     if (rc != EE_OK) return rc;
     if (s0 < 1 || s0 > H || s0 > W) return EE_ERR_SHAPE;
     if (B == 0) return EE_OK;
-    if (!x_best || !x_new || !x0 || !seed || !eta || !scal) return EE_ERR_NULL;
-    if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || !aligned4(eta) || !aligned4(scal) || (reinterpret_cast<uintptr_t>(seed) & 7u))
-        return EE_ERR_ALIGN;
+    if ((rc = sqatk_check_ptrs(seed, {x_best, x_new, x0, eta, scal})) != EE_OK) return rc;
     const int64_t Bl = B;
     ProfScope prof(EE_K_SQATK_INIT, as_stream(stream));
     sample_launch(res, sample_vec(static_cast<int64_t>(C) * H * W, x_best, x_new, x0), [&](auto RES, auto VEC) {
@@ -302,17 +190,12 @@ EE_API int ee_sqatk_step_l1_f32(float *x_best, float *x_new, const float *x0, co
                                 const int *sizes, const int *eta_off, const float *eta, int n_sizes, const int64_t *seed, float *norms,
                                 float *scal, int B, int C, int H, int W, float eps, float eps_p, int path, void *stream) {
     bool res = false;
-    const int rc = check_sq_l1(B, C, H, W, eps, eps_p, path, &res);
+    int rc = check_sq_l1(B, C, H, W, eps, eps_p, path, &res);
     if (rc != EE_OK) return rc;
     if (n_sizes < 0) return EE_ERR_SHAPE;
     if (B == 0) return EE_OK;
-    if (!x_best || !x_new || !x0 || !flags || !margin_min || !counter || !seed || !norms || !scal ||
-        (n_sizes > 0 && (!sizes || !eta_off || !eta)))
-        return EE_ERR_NULL;
-    if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || !aligned4(flags) || !aligned4(margin_min) || !aligned4(counter) ||
-        !aligned4(sizes) || !aligned4(eta_off) || !aligned4(eta) || !aligned4(norms) || !aligned4(scal) ||
-        (reinterpret_cast<uintptr_t>(seed) & 7u))
-        return EE_ERR_ALIGN;
+    if ((rc = sqatk_check_ptrs(seed, {x_best, x_new, x0, flags, margin_min, counter, norms, scal}, n_sizes > 0, {sizes, eta_off, eta})) != EE_OK)
+        return rc;
     const int64_t Bl = B;
     ProfScope prof(EE_K_SQATK_STEP, as_stream(stream));
     sample_launch(res, sample_vec(static_cast<int64_t>(C) * H * W, x_best, x_new, x0), [&](auto RES, auto VEC) {

@@ -13,8 +13,9 @@
 //     x_new    = clamp(x0 + delta / (tiny + n_d) * eps, 0, 1)
 //
 // One workgroup per sample: the norms depend on each other in three rounds ({n_img, n_un, n_w}, {n_new}, {n_d}) and never cross a
-// workgroup.  A norm is (float) sqrt(S), S the sum of the squares in double (the square of a float is exact there) in the one order of
-// ee_sample.hpp; the Reducer below takes a round's sums together and adds each one's eight partials in that index order.  An element
+// workgroup.  The first two rounds are propose_window's (ee_sqatk_prop.hpp) under the policy below; this file adds round 3 and the last
+// pass.  A norm is (float) sqrt(S), S the sum of the squares in double (the square of a float is exact there) in the one order of
+// ee_sample.hpp; the Reducer takes a round's sums together and adds each one's eight partials in that index order.  An element
 // outside a window adds an exact zero to that window's sum (or is skipped, which is the same number), so the order depends on the shape
 // only and the resident path (x0, the difference and what is known of each element stay in registers across the rounds), the streaming
 // path (every pass re-reads x_best and x0 and recomputes from the scalars already known) and the vector / element-wise accesses all
@@ -29,10 +30,19 @@ namespace {
 
 using namespace ee;
 
-__device__ __forceinline__ double square(float v) {
-    const double d = static_cast<double>(v);
-    return d * d;
-}
+// the L2 norm of propose_window
+struct NormL2 {
+    static constexpr int kHead = 3;  // n_img, n_un, n_d
+    static __device__ __forceinline__ double term(float v) {
+        const double d = static_cast<double>(v);
+        return d * d;
+    }
+    static __device__ __forceinline__ float fin(double s) { return static_cast<float>(sqrt(s)); }
+    static __device__ __forceinline__ float scale(float eps, float n_img, float n_un, int C) {
+        const float room = tmax(eps * eps - n_img * n_img, 0.0f);
+        return static_cast<float>(sqrt(static_cast<double>(room / static_cast<float>(C) + n_un * n_un)));  // the f32 root, rounded once
+    }
+};
 
 // ---- start ---------------------------------------------------------------------------------------------------------------------------
 template <bool RES, bool VEC>
@@ -47,11 +57,7 @@ __global__ __launch_bounds__(kSampleBlock) void init_l2_kernel(float *__restrict
     const float *cr = x0 + b * D;
     float *br = x_best + b * D, *nr = x_new + b * D;
     const int groups = groups_of(D);
-    const Philox ph(static_cast<uint64_t>(seed[0]));
-    Tiling tl;
-    tl.s0 = s0, tl.nh = H / s0, tl.nw = W / s0, tl.oh = (H - tl.nh * s0) / 2, tl.ow = (W - tl.nw * s0) / 2, tl.id = b, tl.eta = eta;
-    // an element's d travels in Info::idx as its bits
-    const auto one = [&](int c, int h, int w) { return Info{0u, __float_as_int(tl.value(ph, c, h, w))}; };
+    const Tiling tl(seed, eta, s0, H, W, b);
 
     float rc[kSampleElems], rd[kSampleElems];
     double acc = 0.0;
@@ -59,26 +65,25 @@ __global__ __launch_bounds__(kSampleBlock) void init_l2_kernel(float *__restrict
 #pragma unroll
         for (int k = 0; k < kSampleVecs; ++k) {
             const int64_t e = group_element(k);
-            float cv[4];
-            Info in[4];
+            float cv[4], dv[4];
             load4<VEC>(cr, e, D, cv);
-            infos4(e, geo, in, one);
+            tl.d4(e, geo, dv);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                rc[k * 4 + j] = cv[j], rd[k * 4 + j] = __int_as_float(in[j].idx);
-                acc += square(rd[k * 4 + j]);
+                rc[k * 4 + j] = cv[j], rd[k * 4 + j] = dv[j];
+                acc += NormL2::term(rd[k * 4 + j]);
             }
         }
     } else {
         for (int k = 0; k < groups; ++k) {
-            Info in[4];
-            infos4(group_element(k), geo, in, one);
+            float dv[4];
+            tl.d4(group_element(k), geo, dv);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc += square(__int_as_float(in[j].idx));
+            for (int j = 0; j < 4; ++j) acc += NormL2::term(dv[j]);
         }
     }
     red.put(0, acc);
-    red.norms(1, sn, nullptr, 0, 0, [](int k) { return k; });
+    red.sums(1, sn, nullptr, 0, 0, [](int k) { return k; }, NormL2::fin);
     const float q = eps / (sn[0] + kTiny);
     if (RES) {
 #pragma unroll
@@ -92,12 +97,11 @@ __global__ __launch_bounds__(kSampleBlock) void init_l2_kernel(float *__restrict
     } else {
         for (int k = 0; k < groups; ++k) {
             const int64_t e = group_element(k);
-            float cv[4], o[4];
-            Info in[4];
+            float cv[4], dv[4], o[4];
             load4<VEC>(cr, e, D, cv);
-            infos4(e, geo, in, one);
+            tl.d4(e, geo, dv);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = tclamp(cv[j] + __int_as_float(in[j].idx) * q, 0.0f, 1.0f);
+            for (int j = 0; j < 4; ++j) o[j] = tclamp(cv[j] + dv[j] * q, 0.0f, 1.0f);
             store4<VEC>(br, e, D, o);
             store4<VEC>(nr, e, D, o);
         }
@@ -105,12 +109,6 @@ __global__ __launch_bounds__(kSampleBlock) void init_l2_kernel(float *__restrict
 }
 
 // ---- commit and proposal -------------------------------------------------------------------------------------------------------------
-// the proposal of ee_sqatk_prop.hpp and the L2 run's last line: the whole delta rescaled to the sphere
-struct ProposalL2 : Proposal {
-    float n_d, eps;
-    __device__ __forceinline__ float next(float x0, float v) const { return tclamp(x0 + v / (kTiny + n_d) * eps, 0.0f, 1.0f); }
-};
-
 template <bool RES, bool VEC>
 __global__ __launch_bounds__(kSampleBlock) void step_l2_kernel(float *x_best, float *x_new, const float *__restrict__ x0, const int *__restrict__ flags,
                                                            const float *__restrict__ margin_min, const int *__restrict__ counter,
@@ -120,128 +118,16 @@ __global__ __launch_bounds__(kSampleBlock) void step_l2_kernel(float *x_best, fl
     __shared__ double part[(2 + kMaxC) * kSampleWaves];
     __shared__ float sn1[2 + kMaxC], sn2[kMaxC], sn3[1];
     Reducer red{part};
-    const Geo geo{C, H, W, H * W, static_cast<int64_t>(C) * H * W};
-    const int64_t b = blockIdx.x, D = geo.D;
-    const int it = counter[0];
-    int s = (it >= 0 && it < n_sizes) ? sizes[it] : 0;  // 0: no proposal in this launch (commit only)
-    if (s < 1 || s > H || s > W) s = 0;                 // a size the window arithmetic cannot take is no proposal either
-    const int off = s ? eta_off[it] : 0;
-    if (off < 0) s = 0;
-    const bool commit = flags[b] != 0, propose = s > 0 && !(margin_min[b] <= 0.0f);  // uniform over the workgroup
-    if (!propose && static_cast<int>(threadIdx.x) < 3 + 2 * C) norms[static_cast<int64_t>(threadIdx.x) * B + b] = 0.0f;
-    if (!commit && !propose) return;
-    const float *cr = x0 + b * D;
-    float *br = x_best + b * D, *nr = x_new + b * D;
-    const int groups = groups_of(D);
-    if (!propose) {  // the commit alone
-        for (int k = 0; k < groups; ++k) {
-            float v[4];
-            load4<VEC>(nr, group_element(k), D, v);
-            store4<VEC>(br, group_element(k), D, v);
-        }
-        return;
-    }
-    const Philox ph(static_cast<uint64_t>(seed[0]));
-    const WindowDraw w1 = draw_window(ph, it, b, s, H, W, kStreamWindow), w2 = draw_window(ph, it, b, s, H, W, kStreamWindow2);
-    ProposalL2 p;
-    p.s = s, p.vh = w1.vh, p.vw = w1.vw, p.vh2 = w2.vh, p.vw2 = w2.vw, p.signs = w1.z, p.transpose = (w1.w & 1u) != 0;
-    p.eta = eta + off, p.n_w = sn1 + 2, p.n_new = sn2, p.scale = 0.0f, p.n_d = 0.0f, p.eps = eps;
-    const auto one = [&](int c, int h, int w) { return p.info(c, h, w); };
-
-    // round 1: n_img, n_un over the whole sample - the pass that commits, and that takes the sample into registers on the resident path
+    Proposal p;
+    Stream<VEC> stream;
     float rc[kSampleElems], rv[kSampleElems];
     Info ri[kSampleElems];
-    double a_img = 0.0, a_un = 0.0;
-    const auto first = [&](int64_t e, float (&cv)[4], float (&dv)[4], Info (&in)[4]) {
-        float xv[4];
-        load4<VEC>(commit ? nr : br, e, D, xv);
-        if (commit) store4<VEC>(br, e, D, xv);
-        load4<VEC>(cr, e, D, cv);
-        infos4(e, geo, in, one);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            dv[j] = xv[j] - cv[j];
-            const double q = square(dv[j]);
-            a_img += q;
-            a_un += (in[j].f & (kIn1 | kIn2)) ? q : 0.0;
-        }
-    };
-    if (RES) {
-#pragma unroll
-        for (int k = 0; k < kSampleVecs; ++k) {
-            float cv[4], dv[4];
-            Info in[4];
-            first(group_element(k), cv, dv, in);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) rc[k * 4 + j] = cv[j], rv[k * 4 + j] = dv[j], ri[k * 4 + j] = in[j];
-        }
-    } else {
-        for (int k = 0; k < groups; ++k) {
-            float cv[4], dv[4];
-            Info in[4];
-            first(group_element(k), cv, dv, in);
-        }
-    }
-    red.put(0, a_img);
-    red.put(1, a_un);
-    // the streaming path from here on: (x0, delta, info) of a group, skipped when `want` says the pass has no use for it
-    const auto stream = [&](int k, auto want, auto body) {
-        const int64_t e = group_element(k);
-        Info in[4];
-        infos4(e, geo, in, one);
-        if (!want(in)) return;
-        float xv[4], cv[4], dv[4];
-        load4<VEC>(br, e, D, xv);
-        load4<VEC>(cr, e, D, cv);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dv[j] = xv[j] - cv[j];
-        body(e, cv, dv, in);
-    };
-    // n_w[c]: window 1 of channel c
-    for (int c = 0; c < C; ++c) {
-        double acc = 0.0;
-        if (RES) {
-#pragma unroll
-            for (int k = 0; k < kSampleElems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? square(rv[k]) : 0.0;
-        } else {
-            for (int k = 0; k < groups; ++k)
-                stream(k, [&](const Info(&in)[4]) { return any_in1(in, c); },
-                       [&](int64_t, const float(&)[4], const float(&dv)[4], const Info(&in)[4]) {
-#pragma unroll
-                           for (int j = 0; j < 4; ++j) acc += ((in[j].f & kIn1) && channel_of(in[j]) == c) ? square(dv[j]) : 0.0;
-                       });
-        }
-        red.put(2 + c, acc);
-    }
-    red.norms(2 + C, sn1, norms, B, b, [](int k) { return k < 2 ? k : k + 1; });
-    {
-        const float n_img = sn1[0], n_un = sn1[1];
-        const float room = tmax(eps * eps - n_img * n_img, 0.0f);
-        p.scale = static_cast<float>(sqrt(static_cast<double>(room / static_cast<float>(C) + n_un * n_un)));  // the f32 root, rounded once
-    }
-
-    // round 2: n_new[c]
-    if (RES) {
-#pragma unroll
-        for (int k = 0; k < kSampleElems; ++k) rv[k] = p.stage1(rv[k], ri[k]);
-    }
-    for (int c = 0; c < C; ++c) {
-        double acc = 0.0;
-        if (RES) {
-#pragma unroll
-            for (int k = 0; k < kSampleElems; ++k) acc += ((ri[k].f & kIn1) && channel_of(ri[k]) == c) ? square(rv[k]) : 0.0;
-        } else {
-            for (int k = 0; k < groups; ++k)
-                stream(k, [&](const Info(&in)[4]) { return any_in1(in, c); },
-                       [&](int64_t, const float(&)[4], const float(&dv)[4], const Info(&in)[4]) {
-#pragma unroll
-                           for (int j = 0; j < 4; ++j)
-                               acc += ((in[j].f & kIn1) && channel_of(in[j]) == c) ? square(p.stage1(dv[j], in[j])) : 0.0;
-                       });
-        }
-        red.put(c, acc);
-    }
-    red.norms(C, sn2, norms, B, b, [C](int k) { return 3 + C + k; });
+    const StepArgs a{x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off, eta, n_sizes, seed, norms, B, C, H, W, eps};
+    if (!propose_window<NormL2, RES, VEC>(a, red, sn1, sn2, p, stream, rc, rv, ri)) return;
+    const int64_t b = blockIdx.x, D = stream.geo.D;
+    float *nr = x_new + b * D;
+    const int groups = groups_of(D);
+    const auto all = [](const Info(&)[4]) { return true; };
 
     // round 3: n_d over the whole sample
     double a_d = 0.0;
@@ -249,18 +135,20 @@ __global__ __launch_bounds__(kSampleBlock) void step_l2_kernel(float *x_best, fl
 #pragma unroll
         for (int k = 0; k < kSampleElems; ++k) {
             rv[k] = p.stage2(rv[k], ri[k]);
-            a_d += square(rv[k]);
+            a_d += NormL2::term(rv[k]);
         }
     } else {
         for (int k = 0; k < groups; ++k)
-            stream(k, [](const Info(&)[4]) { return true; }, [&](int64_t, const float(&)[4], const float(&dv)[4], const Info(&in)[4]) {
+            stream(k, all, [&](int64_t, const float(&)[4], const float(&dv)[4], const Info(&in)[4]) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) a_d += square(p.stage2(p.stage1(dv[j], in[j]), in[j]));
+                for (int j = 0; j < 4; ++j) a_d += NormL2::term(p.stage2(p.stage1(dv[j], in[j]), in[j]));
             });
     }
     red.put(0, a_d);
-    red.norms(1, sn3, norms, B, b, [](int) { return 2; });
-    p.n_d = sn3[0];
+    red.sums(1, sn3, norms, B, b, [](int) { return 2; }, NormL2::fin);
+    const float n_d = sn3[0];
+    // the L2 run's last line: the whole delta rescaled to the sphere
+    const auto next = [&](float x0v, float v) { return tclamp(x0v + v / (kTiny + n_d) * eps, 0.0f, 1.0f); };
 
     // final pass: the one place x_new is written
     if (RES) {
@@ -268,15 +156,15 @@ __global__ __launch_bounds__(kSampleBlock) void step_l2_kernel(float *x_best, fl
         for (int k = 0; k < kSampleVecs; ++k) {
             float o[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = p.next(rc[k * 4 + j], rv[k * 4 + j]);
+            for (int j = 0; j < 4; ++j) o[j] = next(rc[k * 4 + j], rv[k * 4 + j]);
             store4<VEC>(nr, group_element(k), D, o);
         }
     } else {
         for (int k = 0; k < groups; ++k)
-            stream(k, [](const Info(&)[4]) { return true; }, [&](int64_t e, const float(&cv)[4], const float(&dv)[4], const Info(&in)[4]) {
+            stream(k, all, [&](int64_t e, const float(&cv)[4], const float(&dv)[4], const Info(&in)[4]) {
                 float o[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = p.next(cv[j], p.stage2(p.stage1(dv[j], in[j]), in[j]));
+                for (int j = 0; j < 4; ++j) o[j] = next(cv[j], p.stage2(p.stage1(dv[j], in[j]), in[j]));
                 store4<VEC>(nr, e, D, o);
             });
     }
@@ -295,12 +183,11 @@ int check_l2(int B, int C, int H, int W, float eps, int path, bool *res) {
 EE_API int ee_sqatk_init_l2_f32(float *x_best, float *x_new, const float *x0, const int64_t *seed, const float *eta, int s0, int B, int C, int H,
                                 int W, float eps, int path, void *stream) {
     bool res = false;
-    const int rc = check_l2(B, C, H, W, eps, path, &res);
+    int rc = check_l2(B, C, H, W, eps, path, &res);
     if (rc != EE_OK) return rc;
     if (s0 < 1 || s0 > H || s0 > W) return EE_ERR_SHAPE;
     if (B == 0) return EE_OK;
-    if (!x_best || !x_new || !x0 || !seed || !eta) return EE_ERR_NULL;
-    if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || !aligned4(eta) || (reinterpret_cast<uintptr_t>(seed) & 7u)) return EE_ERR_ALIGN;
+    if ((rc = sqatk_check_ptrs(seed, {x_best, x_new, x0, eta})) != EE_OK) return rc;
     ProfScope prof(EE_K_SQATK_INIT, as_stream(stream));
     sample_launch(res, sample_vec(static_cast<int64_t>(C) * H * W, x_best, x_new, x0), [&](auto RES, auto VEC) {
         EE_LAUNCH((init_l2_kernel<RES, VEC>), dim3(static_cast<unsigned>(B)), dim3(kSampleBlock), 0, as_stream(stream), x_best, x_new, x0, seed,
@@ -313,15 +200,11 @@ EE_API int ee_sqatk_step_l2_f32(float *x_best, float *x_new, const float *x0, co
                                 const int *sizes, const int *eta_off, const float *eta, int n_sizes, const int64_t *seed, float *norms, int B,
                                 int C, int H, int W, float eps, int path, void *stream) {
     bool res = false;
-    const int rc = check_l2(B, C, H, W, eps, path, &res);
+    int rc = check_l2(B, C, H, W, eps, path, &res);
     if (rc != EE_OK) return rc;
     if (n_sizes < 0) return EE_ERR_SHAPE;
     if (B == 0) return EE_OK;
-    if (!x_best || !x_new || !x0 || !flags || !margin_min || !counter || !seed || !norms || (n_sizes > 0 && (!sizes || !eta_off || !eta)))
-        return EE_ERR_NULL;
-    if (!aligned4(x_best) || !aligned4(x_new) || !aligned4(x0) || !aligned4(flags) || !aligned4(margin_min) || !aligned4(counter) ||
-        !aligned4(sizes) || !aligned4(eta_off) || !aligned4(eta) || !aligned4(norms) || (reinterpret_cast<uintptr_t>(seed) & 7u))
-        return EE_ERR_ALIGN;
+    if ((rc = sqatk_check_ptrs(seed, {x_best, x_new, x0, flags, margin_min, counter, norms}, n_sizes > 0, {sizes, eta_off, eta})) != EE_OK) return rc;
     const int64_t Bl = B;
     ProfScope prof(EE_K_SQATK_STEP, as_stream(stream));
     sample_launch(res, sample_vec(static_cast<int64_t>(C) * H * W, x_best, x_new, x0), [&](auto RES, auto VEC) {

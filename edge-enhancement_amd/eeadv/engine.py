@@ -730,22 +730,40 @@ def _signed64(seed):
     return seed - (1 << 64) if seed >= (1 << 63) else seed
 
 
+# norm -> (init, step - names in `ops`, looked up when a run is made -, rows of `norms` for C channels, and the attributes of the run that
+# init and step take behind eps): the norm enters a Square run at these two launches only.  No rows (Linf): the launches take no pattern
+# tables either, and the schedule is the Linf one.  L1 has a door of its own (square_l1_loop): a run class names the norms its door accepts
+_SQUARE_NORM = {"Linf": ("sqatk_init_", "sqatk_step_", None, (), ()),
+                "L2": ("sqatk_init_l2_", "sqatk_step_l2_", lambda C: 3 + 2 * C, ("path",), ("norms", "path")),
+                "L1": ("sqatk_init_l1_", "sqatk_step_l1_", lambda C: 2 + 2 * C, ("eps_p", "scal", "path"), ("eps_p", "norms", "scal", "path"))}
+_SQUARE_WRITTEN = ("norms", "scal")  # those of the attributes above that a launch writes: what a trace keeps of it
+
+
 class _SquareRun:
-    """The device state of one Square attack (include/eeadv.h, "Square attack") and its pieces: `start` (the striped start and its forward,
-    once per attack), `iteration` (step, eval forward under no_grad, margin: what a captured graph replays) and `finish` (the commit of the
-    last accepted proposal).  No host read anywhere.  norm = "L2": the run owns `norms` [3 + 2C, B], the pattern tables `eta` with `eta_off`
-    and the L2 schedule, and init / step are the launches of ee_sqatk_l2.hip (`path` picks their path) - nothing else knows the norm."""
+    """The device state of one Square attack (include/eeadv.h, "Square attack") and its pieces: `start` (the start and its forward, once
+    per attack), `iteration` (step, eval forward under no_grad, margin: what a captured graph replays) and `finish` (the commit of the
+    last accepted proposal).  No host read anywhere.  Init and step are the launches _SQUARE_NORM names for the norm (`path` picks their
+    path) - nothing else knows it; an L2 or L1 run owns `norms`, the pattern tables `eta` with `eta_off` and the L2 schedule, an L1 run
+    also `scal` [4, B] (the projection's rows) and eps_p, the radius of every projection (sqatk.l1_eps_p: formed once, here)."""
+
+    NORMS = SQUARE_NORMS  # the norms this door accepts; the rest of _SQUARE_NORM is refused here
 
     def __init__(self, x0, y, n_queries, eps, norm="Linf", path="auto"):
-        _check_norm(norm, SQUARE_NORMS, "Square")
+        init, step, rows, self.init_more, self.step_more = _SQUARE_NORM[_check_norm(norm, self.NORMS, "Square")]
+        self.init_, self.step_ = getattr(ops, init), getattr(ops, step)
+        if rows is not None:
+            ops._sample_path(path, "the %s Square kernels'" % norm)
         self._state(x0, n_queries, eps)
+        B, C, dev = x0.shape[0], x0.shape[1], x0.device
         self.norm, self.path, self.norms = norm, path, None
-        if norm == "L2":
-            ops._sample_path(path, "the L2 Square kernels'")
+        if "scal" in self.step_more:  # the run projects
+            self.eps_p = sqatk.l1_eps_p(eps)
+            self.scal = torch.zeros((ops.SQATK_L1_SCAL_ROWS, B), dtype=torch.float32, device=dev)
+        if rows is not None:
             self._tables(x0, n_queries)
-            self.norms = torch.zeros((3 + 2 * x0.shape[1], x0.shape[0]), dtype=torch.float32, device=x0.device)
+            self.norms = torch.zeros((rows(C), B), dtype=torch.float32, device=dev)
         else:
-            self.sizes = torch.tensor(square_schedule(n_queries, x0.shape[2], x0.shape[3]), dtype=torch.int32).to(x0.device)
+            self.sizes = torch.tensor(square_schedule(n_queries, x0.shape[2], x0.shape[3]), dtype=torch.int32).to(dev)
 
     def _state(self, x0, n_queries, eps):
         """What no launch of the norm's own sees: images, margins, flags, counter, query count, seed."""
@@ -801,22 +819,24 @@ class _SquareRun:
         self._query(model)
 
     def _init(self):
-        if self.norms is None:
-            ops.sqatk_init_(self.x_best, self.x_new, self.x0, self.seed, self.eps)
-        else:
-            ops.sqatk_init_l2_(self.x_best, self.x_new, self.x0, self.seed, self.eta0, self.eps, self.path)
+        tables = () if self.norms is None else (self.eta0,)
+        self.init_(self.x_best, self.x_new, self.x0, self.seed, *tables, self.eps, *(getattr(self, name) for name in self.init_more))
+        self._record({}, self.init_more)  # an L1 run: the start's forward carries its projection
 
     def _step(self, sizes):
-        if self.norms is None:
-            ops.sqatk_step_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, sizes, self.seed, self.eps)
-            return
         entry = None
-        if self.trace is not None:
+        if self.trace is not None and self.norms is not None:
             entry = dict(x_best_in=self.x_best.clone(), x_new_in=self.x_new.clone(), counter=int(self.counter.item()))
-        ops.sqatk_step_l2_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, sizes, self.eta_off, self.eta, self.seed,
-                           self.eps, self.norms, self.path)
-        if entry is not None:
-            entry.update(norms=self.norms.clone(), x_new=self.x_new.clone())
+        tables = () if self.norms is None else (self.eta_off, self.eta)
+        self.step_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, sizes, *tables, self.seed, self.eps,
+                   *(getattr(self, name) for name in self.step_more))
+        self._record(entry, self.step_more)
+
+    def _record(self, entry, more):
+        """Under a trace, a launch that wrote some of `more` leaves `entry`, those and x_new for the forward that follows it."""
+        written = [name for name in more if name in _SQUARE_WRITTEN]
+        if self.trace is not None and written:
+            entry.update({name: getattr(self, name).clone() for name in written}, x_new=self.x_new.clone())
             self.step_entry = entry
 
     def iteration(self, model):
@@ -918,33 +938,11 @@ def _drawn_seed(device):
 # _SquareRun(norm="L1") stay refused
 # ---------------------------------------------------------------------------------------------------------------------------------------
 class _SquareL1Run(_SquareRun):
-    """_SquareRun with the two launches of ee_sqatk_l1.hip: margin, flags, counter, queries, `finish`, `any_active` and `result` are
-    _SquareRun's; the run owns `norms` [2 + 2C, B], `scal` [4, B] (the projection's rows), the L2 schedule and tables, and eps_p, the
-    radius of every projection (sqatk.l1_eps_p: formed once, here)."""
+    """_SquareRun with the two launches of ee_sqatk_l1.hip, `norms` [2 + 2C, B], `scal` and eps_p; everything else is _SquareRun's."""
+    NORMS = ("L1",)
 
     def __init__(self, x0, y, n_queries, eps, path="auto"):
-        ops._sample_path(path, "the L1 Square kernels'")
-        self._state(x0, n_queries, eps)
-        self.norm, self.path, self.eps_p = "L1", path, sqatk.l1_eps_p(eps)
-        self._tables(x0, n_queries)
-        B, C, dev = x0.shape[0], x0.shape[1], x0.device
-        self.norms = torch.zeros((2 + 2 * C, B), dtype=torch.float32, device=dev)
-        self.scal = torch.zeros((ops.SQATK_L1_SCAL_ROWS, B), dtype=torch.float32, device=dev)
-
-    def _init(self):
-        ops.sqatk_init_l1_(self.x_best, self.x_new, self.x0, self.seed, self.eta0, self.eps, self.eps_p, self.scal, self.path)
-        if self.trace is not None:
-            self.step_entry = dict(scal=self.scal.clone(), x_new=self.x_new.clone())  # the start's forward carries its projection
-
-    def _step(self, sizes):
-        entry = None
-        if self.trace is not None:
-            entry = dict(x_best_in=self.x_best.clone(), x_new_in=self.x_new.clone(), counter=int(self.counter.item()))
-        ops.sqatk_step_l1_(self.x_best, self.x_new, self.x0, self.flags, self.margin_min, self.counter, sizes, self.eta_off, self.eta, self.seed,
-                           self.eps, self.eps_p, self.norms, self.scal, self.path)
-        if entry is not None:
-            entry.update(norms=self.norms.clone(), scal=self.scal.clone(), x_new=self.x_new.clone())
-            self.step_entry = entry
+        super().__init__(x0, y, n_queries, eps, "L1", path)
 
 
 def square_l1_loop(model, x0, y, n_queries, eps, seed=None, use_graph=None, trace=None, early_exit=True, path="auto"):

@@ -788,15 +788,38 @@ def sqatk_step_(x_best, x_new, x0, flags, margin_min, counter, sizes, seed, eps)
     return x_new
 
 
-# ---- Square attack in the L2 threat model (ee_sqatk_l2.hip) -----------------------------------------------------------
+# ---- Square attack in the L2 and L1 threat models (ee_sqatk_l2.hip, ee_sqatk_l1.hip) ----------------------------------
+SQATK_L1_SCAL_ROWS = 4  # rows L1_S_LAMBDA .. L1_S_DIST of the launch's projection
+
+
+def _sqatk_eta0(eta0):
+    """The side s0 of the start's table."""
+    if eta0.dim() != 2 or eta0.shape[0] != eta0.shape[1]:
+        raise ValueError("eta0 must be a square table [s0, s0], got shape %s" % (tuple(eta0.shape),))
+    return int(eta0.shape[0])
+
+
+def _sqatk_tables(sizes, eta_off, eta):
+    """(sizes, eta_off, eta, n_sizes) as a step launch takes them: sizes None or empty is a commit-only launch, which reads none of them."""
+    n_sizes = 0 if sizes is None else int(sizes.numel())
+    if not n_sizes:
+        return None, None, None, 0
+    return _chk(sizes, torch.int32, "sizes", (n_sizes,)), _chk(eta_off, torch.int32, "eta_off", (n_sizes,)), _chk(eta, torch.float32, "eta"), n_sizes
+
+
+def _sqatk_l1_scal(scal, x_best):
+    B = x_best.shape[0]
+    scal = torch.zeros((SQATK_L1_SCAL_ROWS, B), dtype=torch.float32, device=x_best.device) if scal is None else scal
+    return scal, _chk(scal, torch.float32, "scal", (SQATK_L1_SCAL_ROWS, B))
+
+
 def sqatk_init_l2_(x_best, x_new, x0, seed, eta0, eps, path="auto"):
     """The tiled start of an L2 run into x_best and x_new [B,C,H,W]; eta0 float32 [s0, s0] on the device (eeadv.sqatk.eta), seed int64 [1]."""
     B, C, H, W = x_best.shape
     pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
-    if eta0.dim() != 2 or eta0.shape[0] != eta0.shape[1]:
-        raise ValueError("eta0 must be a square table [s0, s0], got shape %s" % (tuple(eta0.shape),))
+    s0 = _sqatk_eta0(eta0)
     path = _sample_path(path, "the L2 Square kernels'")
-    N.check(N.lib.ee_sqatk_init_l2_f32(pb, pn, p0, _chk(seed, torch.int64, "seed", (1,)), _chk(eta0, torch.float32, "eta0"), int(eta0.shape[0]),
+    N.check(N.lib.ee_sqatk_init_l2_f32(pb, pn, p0, _chk(seed, torch.int64, "seed", (1,)), _chk(eta0, torch.float32, "eta0"), s0,
                                        B, C, H, W, eps, path, _stream()), "ee_sqatk_init_l2_f32")
     return x_best
 
@@ -808,12 +831,7 @@ def sqatk_step_l2_(x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off
     same bits."""
     B, C, H, W = x_best.shape
     pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
-    n_sizes = 0 if sizes is None else int(sizes.numel())
-    ps = po = pe = None
-    if n_sizes:
-        ps = _chk(sizes, torch.int32, "sizes", (n_sizes,))
-        po = _chk(eta_off, torch.int32, "eta_off", (n_sizes,))
-        pe = _chk(eta, torch.float32, "eta")
+    ps, po, pe, n_sizes = _sqatk_tables(sizes, eta_off, eta)
     norms = torch.zeros((3 + 2 * C, B), dtype=torch.float32, device=x_best.device) if norms is None else norms
     path = _sample_path(path, "the L2 Square kernels'")
     N.check(N.lib.ee_sqatk_step_l2_f32(pb, pn, p0, _chk(flags, torch.int32, "flags", (B,)), _chk(margin_min, torch.float32, "margin_min", (B,)),
@@ -823,27 +841,16 @@ def sqatk_step_l2_(x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off
     return norms
 
 
-# ---- Square attack in the L1 threat model (ee_sqatk_l1.hip) -----------------------------------------------------------
-SQATK_L1_SCAL_ROWS = 4  # rows L1_S_LAMBDA .. L1_S_DIST of the launch's projection
-
-
-def _sqatk_l1_scal(scal, x_best):
-    B = x_best.shape[0]
-    scal = torch.zeros((SQATK_L1_SCAL_ROWS, B), dtype=torch.float32, device=x_best.device) if scal is None else scal
-    return scal, _chk(scal, torch.float32, "scal", (SQATK_L1_SCAL_ROWS, B))
-
-
 def sqatk_init_l1_(x_best, x_new, x0, seed, eta0, eps, eps_p, scal=None, path="auto"):
     """The start of an L1 run into x_best and x_new [B,C,H,W]: P_{eps_p}(x0 + d), d the tiled pattern of the L2 start; eta0 float32
     [s0, s0] on the device (eeadv.sqatk.eta), seed int64 [1].  Returns scal [4, B] (rows L1_S_LAMBDA .. _DIST), written into `scal` when
     given."""
     B, C, H, W = x_best.shape
     pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
-    if eta0.dim() != 2 or eta0.shape[0] != eta0.shape[1]:
-        raise ValueError("eta0 must be a square table [s0, s0], got shape %s" % (tuple(eta0.shape),))
+    s0 = _sqatk_eta0(eta0)
     scal, ps = _sqatk_l1_scal(scal, x_best)
     path = _sample_path(path, "the L1 Square kernels'")
-    N.check(N.lib.ee_sqatk_init_l1_f32(pb, pn, p0, _chk(seed, torch.int64, "seed", (1,)), _chk(eta0, torch.float32, "eta0"), int(eta0.shape[0]),
+    N.check(N.lib.ee_sqatk_init_l1_f32(pb, pn, p0, _chk(seed, torch.int64, "seed", (1,)), _chk(eta0, torch.float32, "eta0"), s0,
                                        ps, B, C, H, W, eps, eps_p, path, _stream()), "ee_sqatk_init_l1_f32")
     return scal
 
@@ -855,12 +862,7 @@ def sqatk_step_l1_(x_best, x_new, x0, flags, margin_min, counter, sizes, eta_off
     proposal - written into `norms` / `scal` when given.  path: 'auto', 'resident' (C*H*W <= 12288) or 'streaming'; the same bits."""
     B, C, H, W = x_best.shape
     pb, pn, p0 = _sqatk_images(x_best, x_new, x0)
-    n_sizes = 0 if sizes is None else int(sizes.numel())
-    ps = po = pe = None
-    if n_sizes:
-        ps = _chk(sizes, torch.int32, "sizes", (n_sizes,))
-        po = _chk(eta_off, torch.int32, "eta_off", (n_sizes,))
-        pe = _chk(eta, torch.float32, "eta")
+    ps, po, pe, n_sizes = _sqatk_tables(sizes, eta_off, eta)
     norms = torch.zeros((2 + 2 * C, B), dtype=torch.float32, device=x_best.device) if norms is None else norms
     scal, pscal = _sqatk_l1_scal(scal, x_best)
     path = _sample_path(path, "the L1 Square kernels'")

@@ -619,24 +619,28 @@ def _check_square_norm(norm):
     return engine._check_norm(norm, engine.SQUARE_NORMS, "Square")
 
 
-def _square_l2_norms(v, planes=False):
-    """||v[b]||_2 [B] (planes: ||v[b, c]||_2 [B, C]) in v's dtype for the L2 Square host path: the root, rounded once, of the squares summed in
-    float64.  The squares of float32 (and narrower) values are exact there and torch's sum is then far inside the last bit of the result;
-    float64 values are split into halves whose products are exact and summed without error (math.fsum), so that a float64 run - what the
-    tests compare bit for bit - has norms rounded once as well."""
+def _square_norms(v, planes, power):
+    """||v[b]||_power [B] (planes: ||v[b, c]||_power [B, C]), power 1 or 2, in v's dtype for the L1 / L2 Square host paths: the |values| or
+    the squares summed in float64 - then the root, for 2 - rounded once.  Those terms of float32 (and narrower) values are exact there and
+    torch's sum is then far inside the last bit of the result; float64 values are summed without error (math.fsum) - their squares as
+    the products of halves, which are exact - so that a float64 run, what the tests compare bit for bit, has norms rounded once as well."""
     import math
     rows = v.reshape(v.shape[0] * v.shape[1] if planes else v.shape[0], -1).detach().cpu()
     if v.dtype == torch.float64:
         a = rows.numpy()
-        c = a * 134217729.0  # Veltkamp: hi holds the upper 26 bits
-        hi = c - (c - a)
-        lo = a - hi
-        terms = np.concatenate([hi * hi, 2.0 * hi * lo, lo * lo], axis=1)
+        terms = np.abs(a)
+        if power == 2:
+            c = a * 134217729.0  # Veltkamp: hi holds the upper 26 bits
+            hi = c - (c - a)
+            lo = a - hi
+            terms = np.concatenate([hi * hi, 2.0 * hi * lo, lo * lo], axis=1)
         sums = np.array([math.fsum(r) for r in terms.tolist()], dtype=np.float64)
     else:
-        sums = (rows.to(torch.float64) ** 2).sum(dim=1).numpy()
-    out = torch.from_numpy(np.sqrt(sums)).to(v.dtype).to(v.device)
+        rows = rows.to(torch.float64)
+        sums = (rows ** 2 if power == 2 else rows.abs()).sum(dim=1).numpy()
+    out = torch.from_numpy(np.sqrt(sums) if power == 2 else sums).to(v.dtype).to(v.device)
     return out.view(v.shape[0], v.shape[1]) if planes else out
+
 
 
 def _square_tiles(x0, seed, ids):
@@ -666,7 +670,7 @@ def _square_l2_start(x0, eps, seed, ids):
     B = x0.shape[0]
     d = _square_tiles(x0, seed, ids)
     tiny = torch.tensor(1e-12, dtype=torch.float32).to(x0.dtype)  # the constant is a float32 one in every dtype
-    n0 = _square_l2_norms(d)
+    n0 = _square_norms(d, False, 2)
     q = torch.tensor(eps, dtype=x0.dtype) / (n0 + tiny)
     return torch.clamp(x0 + d * q.view(B, 1, 1, 1), 0, 1), n0
 
@@ -694,27 +698,58 @@ def _square_windows(x0, seed, i, ids, s):
     return inside(vh, vw), inside(vh2, vw2), pattern.to(x0.device).view(B, 1, H, W) * sign
 
 
-def _square_l2_propose(x_best, x0, eps, seed, i, ids, s):
-    """Proposal i of an L2 run for every sample (DESIGN.md section 18): (x_new, norms [3 + 2C, B])."""
+def _square_propose(x_best, x0, seed, i, ids, s, power, scale, tail):
+    """Proposal i of an L2 or L1 run for every sample (DESIGN.md sections 18 and 21), written once up to the rescaled window 1: the norms
+    are _square_norms' of `power`, scale(n_img, n_un) [B] is the threat model's rule, and tail(delta) = (x_new, the rows of norms that
+    follow n_img and n_un, whatever else the caller returns) takes the proposed difference to a point.  Returns (x_new, norms [.. + 2C, B])
+    and the tail's extras."""
     B, C, H, W = x0.shape
     dt = x0.dtype
     in1, in2, signed = _square_windows(x0, seed, i, ids, s)
     zero = torch.zeros((), dtype=dt)
     tiny = torch.tensor(1e-12, dtype=torch.float32).to(dt)  # the constant is a float32 one in every dtype
-    e = torch.tensor(eps, dtype=dt)
     delta = x_best - x0
-    n_img = _square_l2_norms(delta)
-    n_un = _square_l2_norms(torch.where(in1 | in2, delta, zero))
-    n_w = _square_l2_norms(torch.where(in1, delta, zero), planes=True)
+    n_img = _square_norms(delta, False, power)
+    n_un = _square_norms(torch.where(in1 | in2, delta, zero), False, power)
+    n_w = _square_norms(torch.where(in1, delta, zero), True, power)
     new = torch.where(in1, signed + delta / (tiny + n_w).view(B, C, 1, 1), zero)
-    n_new = _square_l2_norms(new, planes=True)
-    room = torch.clamp(e * e - n_img * n_img, min=0) / C + n_un * n_un
-    scale = torch.from_numpy(np.sqrt(room.cpu().numpy())).to(x0.device)  # the root rounded once: torch's vectorised CPU sqrt may miss the last bit
-    new = new / (tiny + n_new).view(B, C, 1, 1) * scale.view(B, 1, 1, 1)
+    n_new = _square_norms(new, True, power)
+    new = new / (tiny + n_new).view(B, C, 1, 1) * scale(n_img, n_un).view(B, 1, 1, 1)
     delta = torch.where(in1, new, torch.where(in2, zero, delta))
-    n_d = _square_l2_norms(delta)
-    x_new = torch.clamp(x0 + delta / (tiny + n_d).view(B, 1, 1, 1) * e, 0, 1)
-    return x_new, torch.cat([torch.stack([n_img, n_un, n_d]), n_w.t(), n_new.t()])
+    x_new, head, *more = tail(delta)
+    return (x_new, torch.cat([torch.stack([n_img, n_un] + head), n_w.t(), n_new.t()]), *more)
+
+
+def _square_l2_propose(x_best, x0, eps, seed, i, ids, s):
+    """Proposal i of an L2 run for every sample (DESIGN.md section 18): (x_new, norms [3 + 2C, B])."""
+    B, C = x0.shape[:2]
+    e = torch.tensor(eps, dtype=x0.dtype)
+    tiny = torch.tensor(1e-12, dtype=torch.float32).to(x0.dtype)
+
+    def scale(n_img, n_un):
+        room = torch.clamp(e * e - n_img * n_img, min=0) / C + n_un * n_un
+        return torch.from_numpy(np.sqrt(room.cpu().numpy())).to(x0.device)  # the root rounded once: torch's vectorised CPU sqrt may miss the last bit
+
+    def tail(delta):  # the whole delta rescaled to the sphere
+        n_d = _square_norms(delta, False, 2)
+        return torch.clamp(x0 + delta / (tiny + n_d).view(B, 1, 1, 1) * e, 0, 1), [n_d]
+
+    return _square_propose(x_best, x0, seed, i, ids, s, 2, scale, tail)
+
+
+def _square_l1_propose(x_best, x0, eps, eps_p, seed, i, ids, s):
+    """Proposal i of an L1 run for every sample (DESIGN.md section 21): (x_new, norms [2 + 2C, B], lam [B])."""
+    C = x0.shape[1]
+    e = torch.tensor(eps, dtype=x0.dtype)
+
+    def scale(n_img, n_un):
+        return torch.clamp(e - n_img, min=0) / torch.tensor(C, dtype=x0.dtype) + n_un
+
+    def tail(delta):  # the exact projection onto the eps_p ball and the box
+        x_new, lam = _l1_project(x0 + delta, x0, eps_p)
+        return x_new, [], lam
+
+    return _square_propose(x_best, x0, seed, i, ids, s, 1, scale, tail)
 
 
 class _SquareQueries:
@@ -742,6 +777,21 @@ class _SquareQueries:
             self.trace.append(dict(extra or {}, margin=m.clone(), flags=accept.clone()))
         return torch.where(accept.view(-1, 1, 1, 1), x_new, x_best)
 
+    def run(self, x_start, kept, sizes, propose, early_exit):
+        """The host loop of a tiled-start run: the forward on x_start, then proposal i = 0, 1, ... of edge sizes[i] while a sample is active.
+        propose(x_best, i, s) = (the proposal of every sample, {name: per-sample rows [.., B]}); the trace keeps x_new and those rows -
+        zeros for a sample that made no proposal and kept x_new = x_best - as it keeps `kept` of the start.  Returns x_best."""
+        x_best = self.query(x_start, x_start, dict({"x_new": x_start.clone()}, **kept))
+        for i, s in enumerate(sizes):
+            active = self.active()
+            if early_exit and not bool(active.any()):
+                break
+            prop, rows = propose(x_best, i, s)
+            x_new = torch.where(active.view(-1, 1, 1, 1), prop, x_best)
+            rows = {k: torch.where(active, v, torch.zeros((), dtype=v.dtype)) for k, v in rows.items()}
+            x_best = self.query(x_new, x_best, dict({"x_new": x_new.clone()}, **rows))
+        return x_best
+
 
 def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early_exit=True, norm="Linf"):
     """Plumbing path for CPU tensors (opt-in): the iteration of engine.square_loop in plain torch ops, in the input's dtype, with the
@@ -754,28 +804,23 @@ def _square_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early
     _check_square_norm(norm)
     B, C, H, W = x0.shape
     ids = np.arange(B) if ids is None else np.asarray(ids)
-    l2 = norm == "L2"
-    sizes = sqatk.square_schedule_l2(n_queries, H, W) if l2 else engine.square_schedule(n_queries, H, W)
     st = _SquareQueries(model, x0, y, trace)
-    extra = None
-    if l2:
+    if norm == "L2":
         x_best, n0 = _square_l2_start(x0, eps, seed, ids)
-        extra = {"x_new": x_best.clone(), "norms": n0.view(1, B).clone()}
-    else:
-        stripe = torch.from_numpy(sqatk.stripes(seed, ids, C, W)).to(x0.dtype).to(x0.device)
-        x_best = torch.clamp(x0 + eps * stripe.view(B, C, 1, W), 0, 1)
-    x_best = st.query(x_best, x_best, extra)
+
+        def propose(x_best, i, s):
+            prop, norms = _square_l2_propose(x_best, x0, eps, seed, i, ids, s)
+            return prop, {"norms": norms}
+        x_best = st.run(x_best, {"norms": n0.view(1, B).clone()}, sqatk.square_schedule_l2(n_queries, H, W), propose, early_exit)
+        return x_best, st.margin_min, st.queries
+    stripe = torch.from_numpy(sqatk.stripes(seed, ids, C, W)).to(x0.dtype).to(x0.device)
+    x_best = torch.clamp(x0 + eps * stripe.view(B, C, 1, W), 0, 1)
+    x_best = st.query(x_best, x_best)
     hh, ww, cc = torch.arange(H).view(1, H), torch.arange(W).view(1, W), torch.arange(C).view(1, C)
-    for i, s in enumerate(sizes):
+    for i, s in enumerate(engine.square_schedule(n_queries, H, W)):
         active = st.active()
         if early_exit and not bool(active.any()):
             break
-        if l2:
-            prop, norms = _square_l2_propose(x_best, x0, eps, seed, i, ids, s)
-            x_new = torch.where(active.view(-1, 1, 1, 1), prop, x_best)
-            extra = {"x_new": x_new.clone(), "norms": torch.where(active.view(1, B), norms, torch.zeros((), dtype=norms.dtype))}
-            x_best = st.query(x_new, x_best, extra)
-            continue
         vh, vw, bits = (torch.from_numpy(a).view(B, 1) for a in sqatk.windows(seed, i, ids, H, W, s))
         inside = ((hh >= vh) & (hh < vh + s)).view(B, 1, H, 1) & ((ww >= vw) & (ww < vw + s)).view(B, 1, 1, W)
         up = torch.tensor(2.0 * eps, dtype=x0.dtype)  # a 0-dim tensor of the input's dtype: two Python scalars would make float32 of it
@@ -811,41 +856,6 @@ def Square(model, args, inputs, targets, n_queries=5000, seed=None, norm="Linf")
 # every point is the exact projection (_l1_project) of x0 + delta onto the ball of radius eps_p = float32(eps * (1 - 1e-6)) and the box.
 # Restarts, EOT and L1 inside Cascade / Rand at the command line are NOT here.
 # ---------------------------------------------------------------------------------------------------------
-def _square_l1_norms(v, planes=False):
-    """||v[b]||_1 [B] (planes: ||v[b, c]||_1 [B, C]) in v's dtype for the L1 Square host path: the |values| summed in float64 and rounded
-    once.  float32 (and narrower) values are exact there and torch's sum is far inside the last bit of the result; float64 values are
-    summed without error (math.fsum), so that a float64 run has norms rounded once as well."""
-    import math
-    rows = v.reshape(v.shape[0] * v.shape[1] if planes else v.shape[0], -1).detach().abs().cpu()
-    if v.dtype == torch.float64:
-        sums = torch.tensor([math.fsum(r) for r in rows.tolist()], dtype=torch.float64)
-    else:
-        sums = rows.to(torch.float64).sum(dim=1)
-    out = sums.to(v.dtype).to(v.device)
-    return out.view(v.shape[0], v.shape[1]) if planes else out
-
-
-def _square_l1_propose(x_best, x0, eps, eps_p, seed, i, ids, s):
-    """Proposal i of an L1 run for every sample (DESIGN.md section 21): (x_new, norms [2 + 2C, B], lam [B])."""
-    B, C, H, W = x0.shape
-    dt = x0.dtype
-    in1, in2, signed = _square_windows(x0, seed, i, ids, s)
-    zero = torch.zeros((), dtype=dt)
-    tiny = torch.tensor(1e-12, dtype=torch.float32).to(dt)  # the constant is a float32 one in every dtype
-    e = torch.tensor(eps, dtype=dt)
-    delta = x_best - x0
-    n_img = _square_l1_norms(delta)
-    n_un = _square_l1_norms(torch.where(in1 | in2, delta, zero))
-    n_w = _square_l1_norms(torch.where(in1, delta, zero), planes=True)
-    new = torch.where(in1, signed + delta / (tiny + n_w).view(B, C, 1, 1), zero)
-    n_new = _square_l1_norms(new, planes=True)
-    scale = torch.clamp(e - n_img, min=0) / torch.tensor(C, dtype=dt) + n_un
-    new = new / (tiny + n_new).view(B, C, 1, 1) * scale.view(B, 1, 1, 1)
-    delta = torch.where(in1, new, torch.where(in2, zero, delta))
-    x_new, lam = _l1_project(x0 + delta, x0, eps_p)
-    return x_new, torch.cat([torch.stack([n_img, n_un]), n_w.t(), n_new.t()]), lam
-
-
 def _square_l1_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, early_exit=True):
     """Plumbing path for CPU tensors (opt-in): the iteration of engine.square_l1_loop in plain torch ops, in the input's dtype, with the
     kernels' draws (eeadv.sqatk: windows_l2, windows2, tiles).  Each norm is the |values| summed in float64 and rounded once; the
@@ -858,20 +868,16 @@ def _square_l1_host(model, x0, y, n_queries, eps, seed, trace=None, ids=None, ea
     B, C, H, W = x0.shape
     ids = np.arange(B) if ids is None else np.asarray(ids)
     eps_p = sqatk.l1_eps_p(eps)
-    sizes = sqatk.square_schedule_l2(n_queries, H, W)
     st = _SquareQueries(model, x0, y, trace)
     x_best, lam = _l1_project(x0 + _square_tiles(x0, seed, ids), x0, eps_p)
-    x_best = st.query(x_best, x_best, {"x_new": x_best.clone(), "lam": lam.clone()})
-    for i, s in enumerate(sizes):
-        active = st.active()
-        if early_exit and not bool(active.any()):
-            break
+
+    def propose(x_best, i, s):
         prop, norms, lam = _square_l1_propose(x_best, x0, eps, eps_p, seed, i, ids, s)
-        x_new = torch.where(active.view(-1, 1, 1, 1), prop, x_best)
-        zero = torch.zeros((), dtype=norms.dtype)
-        x_best = st.query(x_new, x_best, {"x_new": x_new.clone(), "norms": torch.where(active.view(1, B), norms, zero),
-                                          "lam": torch.where(active, lam, zero)})
+        return prop, {"norms": norms, "lam": lam}
+    x_best = st.run(x_best, {"lam": lam.clone()}, sqatk.square_schedule_l2(n_queries, H, W), propose, early_exit)
     return x_best, st.margin_min, st.queries
+
+
 
 
 def Square_L1(model, args, inputs, targets, n_queries=5000, seed=None):
