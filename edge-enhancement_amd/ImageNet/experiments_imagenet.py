@@ -38,6 +38,8 @@ def _build(args, **size):
     arch = args.arch
     if arch in ('resnet18', 'resnet34', 'resnet50', 'resnet101', 'resnet152'):
         return getattr(zoo, arch)(pretrained=args.pretrained, **size)
+    if arch in ('resnet18_fd', 'resnet34_fd', 'resnet50_fd', 'resnet101_fd', 'resnet152_fd'):  # experiments_imagenet.py:110-119
+        return getattr(zoo, arch)(pretrained=args.pretrained, size=args.crop_size, **size)
     ee = dict(pretrained=args.pretrained, cize=args.cize, r=args.r, w=args.w, with_gf=args.gf, low=args.low, high=args.high,
               alpha=args.alpha, sigma=args.sigma, type_canny=args.type_canny if args.type_canny not in (None, "None") else 'CannyFilter', **size)
     if arch.endswith('_EE_square'):

@@ -166,6 +166,11 @@ SIGNATURES = {
     "ee_dense2x2_bn_eval_fwd_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_i, c_p, c_i, c_i, c_i, c_p],
     # dy, dy2, y, w2t, var, gamma, eps, dres, dx_add, dx, B, Cin, Cout, stream
     "ee_dense2x2_bn_eval_bwd_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_f, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    # the feature-denoising product (ee_fd.hip): C, P / N, C, P / x, f, gram, scratch, N, C, P, scale, stream / x, df, gram, dx, scratch, N, C, P, scale, stream
+    "ee_fd_supported": [c_i, c_i],
+    "ee_fd_scratch_floats": [c_i, c_i, c_i],
+    "ee_fd_fwd_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p],
+    "ee_fd_bwd_f32": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p],
     # dc, u_b, x, save_mean, save_invstd, gamma, beta, dy, sums, B, Cin, Cout, H, stream
     "ee_wino3x3_bwd_sums_f32": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     # dy, x, sums, S, cnt, save_mean, save_invstd, gamma, beta, u_b, dx, B, Cin, Cout, H, stream
@@ -222,7 +227,7 @@ SIGNATURES = {
     "ee_prof_read_work": [c_i, c_p],
     "ee_prof_reset": [],
 }
-_RESTYPE = {"ee_strerror": ctypes.c_char_p, "ee_device_name": ctypes.c_char_p, "ee_mse_num_partials": c_l, "ee_wrw3x3_workspace_floats": c_l, "ee_wrw3x3s2_workspace_floats": c_l, "ee_wrw_stem7x7s2_workspace_floats": c_l, "ee_wrw1x1_workspace_floats": c_l, "ee_net2_conv_wrw_workspace_floats": c_l}
+_RESTYPE = {"ee_strerror": ctypes.c_char_p, "ee_device_name": ctypes.c_char_p, "ee_mse_num_partials": c_l, "ee_wrw3x3_workspace_floats": c_l, "ee_wrw3x3s2_workspace_floats": c_l, "ee_wrw_stem7x7s2_workspace_floats": c_l, "ee_wrw1x1_workspace_floats": c_l, "ee_net2_conv_wrw_workspace_floats": c_l, "ee_fd_scratch_floats": c_l}
 
 # kernel-family ids of include/eeadv.h (ee_prof_*)
 (K_PGD_STEP, K_FRONTEND_FWD, K_FRONTEND_BWD, K_EDGE_FWD, K_EDGE_BWD, K_CE, K_PGD_STEP_BCAST, K_EMPTY, K_HFS, K_CHAIN_FWD, K_CHAIN_BWD,

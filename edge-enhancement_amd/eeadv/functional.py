@@ -864,6 +864,29 @@ class Conv3x3Map2Fn(torch.autograd.Function):
         return dx, dw
 
 
+class FeatureDenoiseFn(torch.autograd.Function):
+    """f = scale * X X^T X per sample, X the [C, H * W] matrix of the map: the dot-product non-local product of the feature-denoising block
+    (resnet_fd.py:133-148 with embed=False, softmax=False) through ops.fd_fwd / ops.fd_bwd (ee_fd.hip).  The forward keeps x and the Gram
+    matrix; the backward is one fd_bwd.  No parameters: input_grad_only() changes nothing here."""
+
+    @staticmethod
+    def forward(ctx, x, scale):
+        n, C = x.shape[0], x.shape[1]
+        f, gram = ops.fd_fwd(x.reshape(n, C, -1), scale)
+        ctx.save_for_backward(x, gram)
+        ctx.scale = scale
+        ctx.set_materialize_grads(False)
+        return f.view_as(x)
+
+    @staticmethod
+    def backward(ctx, df):
+        x, gram = ctx.saved_tensors
+        if df is None or not ctx.needs_input_grad[0]:
+            return None, None
+        n, C = x.shape[0], x.shape[1]
+        return ops.fd_bwd(x.reshape(n, C, -1), df.contiguous().reshape(n, C, -1), gram, ctx.scale).view_as(x), None
+
+
 class Net2ConvFn(torch.autograd.Function):
     """relu(max_pool2d(conv2_drop(conv2(relu(max_pool2d(conv1(x), 2)))), 2)) of Net_2 (MNIST/models_mnist/Net2.py:13-14) in two launches
     each way (ee_net2.hip): the gradient w.r.t. the image - what the attack loop asks for, 40 times per training step - and, for a backward

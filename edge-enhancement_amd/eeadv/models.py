@@ -739,6 +739,107 @@ class ResNet_EE(_EEFrontMixin, ResNet):
         return self.body(self.front(x, draws))
 
 
+# ---- feature-denoising ResNets (ImageNet/models_imagenet/resnet_fd.py) ------------------------------------------------------------
+def _fd_routed(C, P):
+    """The maps whose product runs on ee_fd.hip: those of the kernel class where forward + backward beat the matmul composite on MI355X at
+    batch 32 (scripts/fd_probe.py, profiles/fd_probe.txt): every ResNet-18/34 block (1.5 - 4.1 x), 256 x 3136 (1.05 x)
+    and 2048 x 49 (1.34 x).  Wide channels on a mid-size map stay with the composite: 1024 x 196 measured 0.97 x."""
+    return ops.fd_supported(C, P) and (C <= 512 or P <= 64)
+
+
+def fd_product(x, scale, spatial):
+    """scale * X X^T X per sample of a [N, C, H, W] map (resnet_fd.py:133-148 with embed=False, softmax=False): one Function over ee_fd.hip
+    where the kernel takes the shape and picks the association the caller asks for (spatial: X (X^T X), the reference's n_in > H * W), else
+    - CPU plumbing, other dtypes, unsupported sizes, EEADV_STOCK_GLUE=fd - the matmul composite in that association under autograd."""
+    n, C, P = x.shape[0], x.shape[1], x.shape[2] * x.shape[3]
+    if "fd" not in _STOCK and _dense_f32(x) and spatial == (C > P) and _fd_routed(C, P):
+        return _fn.FeatureDenoiseFn.apply(x, scale)
+    m = x.reshape(n, C, P)
+    mt = m.transpose(1, 2)
+    f = torch.matmul(m, torch.matmul(mt, m)) if spatial else torch.matmul(torch.matmul(m, mt), m)
+    return (f * scale).reshape(x.shape)
+
+
+class Denoising(nn.Module):
+    """The dot-product non-local block (resnet_fd.py:105-153) as the reference always builds it - embed=False, softmax=False:
+    y = x + bn(conv3(X X^T X / (H * W))).  conv1 / conv2 (the embeddings) are created and never called, like there: they belong to the
+    state_dict and to the initialisation's random stream."""
+
+    def __init__(self, n_in=64, H=56, W=56):
+        super(Denoising, self).__init__()
+        self.n_in, self.H, self.W = n_in, H, W
+        self.conv1 = nn.Conv2d(n_in, int(n_in / 2), kernel_size=1, stride=1)
+        self.conv2 = nn.Conv2d(n_in, int(n_in / 2), kernel_size=1, stride=1)
+        self.conv3 = nn.Conv2d(n_in, n_in, kernel_size=1, stride=1)
+        self.bn = BatchNorm2d(n_in)
+
+    def forward(self, x, fork=False):
+        """x: a tensor or the two tensors of a forked block output (the product reads one, the residual the other)"""
+        xm, xs = _pair(x)
+        f = fd_product(xm, 1.0 / (self.H * self.W), self.n_in > self.H * self.W)
+        return bn_act(self.bn, _route(self.conv3, "miopen")(f), residual=xs, relu=False, fork=fork)
+
+
+class ResNet_fd(ResNet):
+    """resnet_fd.py:156-222: a Denoising block after each of the four stages.  Modules are created in the reference's order (same seed, same
+    initial weights; same state_dict keys).  The denoise blocks are built with n_in = 64 .. 512 for every depth, as there: behind the
+    Bottleneck stages (256 .. 2048 channels) conv3 then refuses its input, in the reference's forward as in this one - the `_fd` depths
+    that run are 18 and 34.  size: the input's side; the blocks get H = W = size / 4, / 8, / 16, / 32 (the reference's 56 .. 7 at 224)."""
+
+    def __init__(self, block, layers, num_classes=1000, size=224):
+        nn.Module.__init__(self)
+        self.inplanes = 64
+        self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        for k, (planes, stride) in enumerate(((64, 1), (128, 2), (256, 2), (512, 2))):
+            setattr(self, "layer%d" % (k + 1), self._make_layer(block, planes, layers[k], stride=stride))
+            setattr(self, "denoise%d" % (k + 1), Denoising(n_in=planes, H=size // (4 << k), W=size // (4 << k)))
+        self.avgpool = nn.AvgPool2d(7, stride=1)
+        self.fc = nn.Linear(512 * block.expansion, num_classes)
+        self._init_weights()
+
+    def _stages(self):
+        return [(self.layer1, self.denoise1), (self.layer2, self.denoise2), (self.layer3, self.denoise3), (self.layer4, self.denoise4)]
+
+    @staticmethod
+    def _run(x, stages, to_head):
+        """every block output feeds two consumers (forked) but the last denoise block's, which feeds the head"""
+        for k, (layer, denoise) in enumerate(stages):
+            for blk in layer:
+                x = blk(x, fork=True)
+            x = denoise(x, fork=not (to_head and k + 1 == len(stages)))
+        return x
+
+    def body_pre(self, x):
+        x, moments = stem_conv(self.conv1, x, want_stats=True)
+        x = stem_bn_pool(self.bn1, self.maxpool, x, fork=True, conv_stats=moments)
+        x = self._run(x, self._stages(), True)
+        _bump_bn_counters(self)
+        return x
+
+    def segment_fns(self):
+        def first(x):
+            x, moments = stem_conv(self.conv1, x, want_stats=True)
+            x = stem_bn_pool(self.bn1, self.maxpool, x, fork=True, conv_stats=moments)
+            return self._run(x, self._stages()[:2], False)
+
+        def middle(x):
+            return self._run(x, self._stages()[2:3], False)
+
+        def last(x):
+            x = self._run(x, self._stages()[3:], True)
+            _bump_bn_counters(self)
+            return self.head_from_pre(x)
+        return [first, middle, last]
+
+    def grad_segments(self):
+        own = lambda *mods: [p for m in mods for p in m.parameters()]
+        return [own(self.layer4, self.denoise4, self.fc), own(self.layer3, self.denoise3),
+                own(self.conv1, self.bn1, self.layer1, self.denoise1, self.layer2, self.denoise2)]
+
+
 _LAYERS = {18: (BasicBlock, [2, 2, 2, 2]), 34: (BasicBlock, [3, 4, 6, 3]), 50: (Bottleneck, [3, 4, 6, 3]),
            101: (Bottleneck, [3, 4, 23, 3]), 152: (Bottleneck, [3, 8, 36, 3])}
 
@@ -749,6 +850,16 @@ def make_resnet(depth, dataset="tiny", pretrained=False, **kwargs):
     block, layers = _LAYERS[depth]
     kwargs.setdefault("num_classes", 1000 if dataset == "imagenet" else 200)
     return ResNet(block, layers, dataset=dataset, **kwargs)
+
+
+def make_resnet_fd(depth, size=224, pretrained=False, **kwargs):
+    """resnet{18,34,50,101,152}_fd of ImageNet/models_imagenet/resnet_fd.py:225-287; size: the crop the model will see (a multiple of 32)"""
+    if pretrained:
+        raise NotImplementedError("pretrained weights are read from ~/.torch/models in the reference; none ship offline")
+    if size % 32 != 0 or size < 32:
+        raise ValueError("size %d: the ImageNet ResNets need a multiple of 32" % size)
+    block, layers = _LAYERS[depth]
+    return ResNet_fd(block, layers, size=size, **kwargs)
 
 
 def make_resnet_ee(depth, dataset="tiny", square=False, pretrained=False, **kwargs):

@@ -1701,6 +1701,63 @@ def dense2x2_bn_eval_bwd(dy, dy2, y, w2t, bn, want_dres, dx_add=None):
     return dx, dres
 
 
+def fd_supported(C, P):
+    """ee_fd.hip takes the map: C % 64 == 0, C <= 2048, 1 <= P <= 4096, min(C, P) <= 256"""
+    return bool(N.lib.ee_fd_supported(int(C), int(P)))
+
+
+def _fd_on_kernel(x):
+    return x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[0] <= 65535 and fd_supported(x.shape[1], x.shape[2])
+
+
+def _fd_check(x, name):
+    if not isinstance(x, torch.Tensor) or x.dim() != 3 or not x.is_floating_point():
+        raise ValueError("%s must be a floating-point [N, C, P] tensor" % name)
+
+
+def fd_fwd(x, scale):
+    """The feature-denoising product per sample (resnet_fd.py:133-148 with embed=False, softmax=False): x [N, C, P] -> (f, gram) with
+    f = scale * X X^T X and gram [N, d, d], d = min(C, P), the unscaled X X^T (C <= P) or X^T X (C > P) that fd_bwd reuses.  Dense fp32 ROCm
+    tensors of a supported shape (fd_supported) run on ee_fd.hip; CPU tensors, other dtypes and other shapes take plain matmuls in the
+    reference's association (the host fallback: the block exists at every size, the kernel only where it was built)."""
+    _fd_check(x, "x")
+    n, C, P = x.shape
+    if not _fd_on_kernel(x):
+        xt = x.transpose(1, 2)
+        if C > P:
+            gram = torch.matmul(xt, x)
+            return torch.matmul(x, gram) * scale, gram
+        gram = torch.matmul(x, xt)
+        return torch.matmul(gram, x) * scale, gram
+    d = min(C, P)
+    f = torch.empty_like(x)
+    gram = torch.empty((n, d, d), dtype=torch.float32, device=x.device)
+    ws = torch.empty(max(int(N.lib.ee_fd_scratch_floats(n, C, P)), 4), dtype=torch.float32, device=x.device)
+    N.check(N.lib.ee_fd_fwd_f32(_chk(x, torch.float32, "x"), f.data_ptr(), gram.data_ptr(), ws.data_ptr(), n, C, P, float(scale), _stream()), "ee_fd_fwd_f32")
+    return f, gram
+
+
+def fd_bwd(x, df, gram, scale):
+    """d fd_fwd / d x for the upstream gradient df [N, C, P]: scale * [(M + M^T) X + G D], M = D X^T (C <= P) or scale * [D A + X (B + B^T)],
+    B = D^T X (C > P), with G / A = fd_fwd's gram; the same routing as fd_fwd."""
+    _fd_check(x, "x")
+    n, C, P = x.shape
+    d = min(C, P)
+    if tuple(df.shape) != (n, C, P) or tuple(gram.shape) != (n, d, d):
+        raise ValueError("df %s / gram %s do not match x %s" % (tuple(df.shape), tuple(gram.shape), tuple(x.shape)))
+    if not _fd_on_kernel(x):
+        if C > P:
+            b = torch.matmul(df.transpose(1, 2), x)
+            return (torch.matmul(df, gram) + torch.matmul(x, b + b.transpose(1, 2))) * scale
+        m = torch.matmul(df, x.transpose(1, 2))
+        return (torch.matmul(m + m.transpose(1, 2), x) + torch.matmul(gram, df)) * scale
+    dx = torch.empty_like(x)
+    ws = torch.empty(max(int(N.lib.ee_fd_scratch_floats(n, C, P)), 4), dtype=torch.float32, device=x.device)
+    N.check(N.lib.ee_fd_bwd_f32(_chk(x, torch.float32, "x"), _chk(df, torch.float32, "df"), _chk(gram, torch.float32, "gram"), dx.data_ptr(), ws.data_ptr(),
+                                n, C, P, float(scale), _stream()), "ee_fd_bwd_f32")
+    return dx
+
+
 def wrw3x3_supported(x, dy):
     """ee_wrw.hip: weight gradient of a 3x3 / stride 1 / padding 1 convolution on 2x2, 4x4, 8x8 or 16x16 maps"""
     return (x.dim() == 4 and dy.dim() == 4 and x.shape[2] == x.shape[3] and x.shape[2] in (2, 4, 8, 16) and x.shape[2:] == dy.shape[2:]

@@ -940,6 +940,23 @@ int ee_dense2x2_bn_eval_fwd_f32(const float *x, const float *w2, const float *me
 int ee_dense2x2_bn_eval_bwd_f32(const float *dy, const float *dy2, const float *y, const float *w2t, const float *var, const float *gamma, float eps,
                                 float *dres, const float *dx_add, float *dx, int B, int Cin, int Cout, void *stream);
 
+/* The dot-product non-local product of the feature-denoising block (ImageNet/models_imagenet/resnet_fd.py:126-148 with embed=False,
+ * softmax=False) on the f32 matrix cores (ee_fd.hip).  Per sample, X = x[n] as a C x P matrix (P = H * W, rows contiguous):
+ *   ee_fd_fwd_f32   f  = scale * X X^T X;  gram [N,d,d], d = min(C, P), receives X X^T (C <= P, the channel form) or X^T X (C > P, the spatial
+ *                   form - the reference's rule n_in > H * W), unscaled, for the backward;
+ *   ee_fd_bwd_f32   dx = scale * [(M + M^T) X + G D], M = D X^T (channel form) or scale * [D A + X (B + B^T)], B = D^T X (spatial form), D = df,
+ *                   G / A = the forward's gram.
+ * The long contraction is split over workgroups whose partial d x d tiles meet in `scratch` (ee_fd_scratch_floats(N, C, P) floats, contents
+ * undefined on entry and exit) and are added in a fixed order: bit-identical run to run, no atomics; scale multiplies each finished sum once.
+ * Up to three launches each; no allocation, no host read.  Shapes: ee_fd_supported(C, P) != 0 - C a multiple of 64, C <= 2048, 1 <= P <= 4096,
+ * min(C, P) <= 256 - others EE_ERR_UNSUPPORTED (the scratch query returns 0); N < 0, N > 65535, N*C*P > INT32_MAX, a NaN scale, f == x or
+ * dx == x or dx == df: EE_ERR_SHAPE; pointers 4-byte aligned (EE_ERR_ALIGN) - every element is loaded on its own, so 16-byte alignment changes
+ * nothing; N == 0 launches nothing. */
+int ee_fd_supported(int C, int P);
+int64_t ee_fd_scratch_floats(int N, int C, int P);
+int ee_fd_fwd_f32(const float *x, float *f, float *gram, float *scratch, int N, int C, int P, float scale, void *stream);
+int ee_fd_bwd_f32(const float *x, const float *df, const float *gram, float *dx, float *scratch, int N, int C, int P, float scale, void *stream);
+
 /* The WEIGHT gradient of the same convolution (`loss.backward()` of the training step, experiments_tinyimagenet.py:304-306; resnet.py:26-31) on
  * H x H maps, H = 2, 4, 8 or 16, as Winograd F(3x3, 2x2) around the f32 matrix cores: x [B,Cin,H,H] (the layer's input), dy [B,Cout,H,H] (the
  * gradient of its output) -> dw [Cout,Cin,3,3] (overwritten).  The sum over images and tiles is split over ~256 workgroups whose partial results
