@@ -1,26 +1,27 @@
-// ee_hfs_mfma.hip - HighFreqSuppress (utils/core.py:15-55) for planes up to 256 x 256 (ImageNet: 224 x 224, r = 16) on the
-// f32 matrix cores, one workgroup per plane, ONE WAVEFRONT PER 16-ROW BAND - and, second kernel, for planes up to 320 x 320
-// (ImageNet/fgsm_imagenet phase 3: 288 x 288, r = 18) with TWO BANDS PER WAVEFRONT and wider tables.
+// ee_hfs_mfma.hip - HighFreqSuppress (utils/core.py:15-55) for planes past ee_hfs.hip's 64 x 64 on the f32 matrix cores: one
+// workgroup per plane, the plane cut into 16-row bands, BPW consecutive bands per wavefront.  One kernel serves two plane classes:
+//     narrow  ee_hfs_mfma_f32  up to 256 x 256 (ImageNet: 224 x 224, r = 16): BPW = 1, [P | Q] 32 columns (NT = 2), MT2 = 2 or 4
+//     wide    ee_hfs_wide_f32  up to 320 x 320 (ImageNet/fgsm_imagenet phase 3: 288 x 288, r = 18): BPW = 2 (288 rows are 18 bands
+//                              and a workgroup has at most 16 wavefronts), [P | Q] 32 or 64 columns (NT = 2 or 4), MT2 = 2, 4 or 6
 //
 // ee_hfs.hip keeps a whole plane in LDS and is limited to 64 x 64; beyond that the host layer used three rocBLAS launches and a
 // [B,C,H,2W] intermediate in HBM.  The operator is still the rank-(NU x 2NV) one (eeadv/hfs.py), so here it is the same four
 // skinny products as in ee_chain.hip, chained through the v_mfma_f32_16x16x4_f32 accumulators, but split over the bands:
-//     S1  [P | Q]   = X_band  T1                 per band: 16 x W times W x 32      (X staged through a wave-private LDS strip)
-//     S2  R_band    = CS_band^T [P | Q]          per band: 2NU x 16 times 16 x 32   -> summed over the bands through LDS
+//     S1  [P | Q]   = X_band  T1                 per band: 16 x W times W x 16 NT   (X staged through a wave-private LDS strip)
+//     S2  R_band    = CS_band^T [P | Q]          per band: 2NU x 16 times 16 x 16 NT -> a wavefront's bands accumulate into the
+//                                                same MT2 x NT tiles; summed over the wavefronts through LDS
 //     EF            = (a - d | c + b ; b + c | d - a)                                   (tile-wise register arithmetic)
 //     S3  [U | V]^T = EF^T CS_band^T / H         per band
-//     S4  y_band    = [U | V] T4                 per band: 16 x 32 times 32 x W
-// scripts/chain_emulate.py (big_tables / big_apply) is the specification of the fragment-ordered tables and checks the index
-// algebra against the dense operator in float64.  HBM traffic = the algorithmic minimum, read x + write y (8 B per element;
-// 12 with sq_mode 2).  The band reduction adds in band order: results are bit-reproducible run to run.
-//
-// The wide kernel (hfs_wide_kernel; chain_emulate.py wide_tables / wide_apply) is the same chain with [P | Q] 2 x nv_pad = 32 or
-// 64 columns wide (NT = 2 or 4 tiles) and up to 48 kept row frequencies (MT2 = 6).  288 rows are 18 bands and a workgroup has
-// at most 16 wavefronts, so a wavefront owns BPW = 2 consecutive bands: S1 runs once per band, S2 accumulates both bands into
-// the same R tiles, and the reduction over the wavefronts goes through the strips four tiles at a time, in wavefront order.
+//     S4  y_band    = [U | V] T4                 per band: 16 x 16 NT times 16 NT x W
+// scripts/chain_emulate.py (wide_tables / wide_apply, with the narrow class as its NT = 2, BPW = 1 case) is the specification of
+// the fragment-ordered tables and checks the index algebra against the dense operator in float64.  HBM traffic = the algorithmic
+// minimum, read x + write y (8 B per element; 12 with sq_mode 2).  The reduction over the wavefronts goes through the strips four
+// tiles at a time and adds each element in wavefront order = band order: results are bit-reproducible run to run.
 //
 // sq_mode as in ee_hfs_f32: 1 applies Add_Square (core.py:636-655) while a strip is staged, 2 multiplies the result by
 // d add_square / dx evaluated at sq_x.  Parity: UNPINNED like ee_hfs.hip (torch.rfft is gone); 3e-7 from the float64 operator.
+#include <type_traits>
+
 #include "ee_common.hpp"
 #include "ee_square.hpp"
 
@@ -33,8 +34,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int KC = 64;           // columns per staged strip
 constexpr int SS = KC + 4;       // strip row stride: bank = (4 i + g + 4 s) % 64, conflict-free A-fragment reads
 constexpr int STRIP = 16 * SS;   // floats per wave
-constexpr int BPW = 2;           // wide kernel: bands per wavefront
-constexpr int WIDE_MAX = 320;    // wide kernel: largest H, W (20 bands, 10 wavefronts)
+constexpr int NARROW_MAX = 256;  // narrow class: largest H, W (16 bands, one per wavefront)
+constexpr int WIDE_MAX = 320;    // wide class: largest H, W (20 bands, 10 wavefronts)
+constexpr int WIDE_BPW = 2;      // wide class: bands per wavefront
 
 struct BandDims {
     int H, W, HP, WP, NB, WT;  // NB = HP / 16 bands, WT = WP / 16
@@ -138,138 +140,15 @@ struct BandIO {
     }
 };
 
-template <int SQ, int MT2>
-__global__ __launch_bounds__(1024) void hfs_band_kernel(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ tables,
-                                                        BandDims d, const float *__restrict__ sq_x, SquareArgs sq) {
-    extern __shared__ __align__(16) float lds[];
-    const int tid = threadIdx.x, lane = tid & 63, band = tid >> 6, li = lane & 15, lg = lane >> 4;
-    const int WP = d.WP, NB = d.NB, NT = NB * 64;
-    float *strip = lds + band * STRIP;        // this wave's [16][SS] staging strip (later: partial R tiles, output tiles)
-    float *tab = lds + NB * STRIP;            // T1, later T4: WP * 32 floats
-    float *rsum = tab + WP * 32;              // [MT2][2][4][64] band-summed R
-    const int n1 = WP / 4 * 2, n2 = NB * MT2 * 4, n3 = n2;  // fragments of T1, T2, T3
-    const float *g1 = tables, *g2 = g1 + n1 * 64, *g3 = g2 + n2 * 64, *g4 = g3 + n3 * 64;
-    const BandIO<SQ> io(in, out, sq_x, sq, blockIdx.x, d.C, d.H, d.W, strip, lane);
-
-    // ---- T1 -> LDS ----------------------------------------------------------------------------------------------------------
-    for (int i = tid; i < WP * 8; i += NT) reinterpret_cast<float4 *>(tab)[i] = reinterpret_cast<const float4 *>(g1)[i];
-    __syncthreads();
-
-    // ---- S1: [P | Q] of this band, strips of KC columns staged through the wave's private LDS strip ------------------------------
-    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-    f32x4 pq[2] = {zero, zero};
-    const int row0 = 16 * band;
-    float4 cur[4], nxt[4];
-    io.load(row0, 0, cur);
-    for (int col0 = 0; col0 < WP; col0 += KC) {
-        if (col0 + KC < WP) io.load(row0, col0 + KC, nxt);  // in flight while this strip is multiplied
-        io.stage(row0, col0, cur);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const int ksteps = (WP - col0 < KC ? WP - col0 : KC) / 4;
-        for (int s = 0; s < ksteps; ++s) {
-            const float a = strip[li * SS + 4 * s + lg];
-            const int f = ((col0 >> 2) + s) * 2;
-            pq[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, tab[(f + 0) * 64 + lane], pq[0], 0, 0, 0);
-            pq[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, tab[(f + 1) * 64 + lane], pq[1], 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();  // every lane has read the strip before it is overwritten
-#pragma unroll
-        for (int q = 0; q < 4; ++q) cur[q] = nxt[q];
-    }
-
-    // ---- S2: this band's share of R = CS^T [P | Q] (the PQ accumulators are the B operands as they lie) --------------------------
-    f32x4 rc[MT2][2];
-#pragma unroll
-    for (int mt = 0; mt < MT2; ++mt) {
-        rc[mt][0] = zero;
-        rc[mt][1] = zero;
-    }
-    {
-        const float *t2 = g2 + static_cast<size_t>(band) * MT2 * 4 * 64 + lane;
-#pragma unroll
-        for (int mt = 0; mt < MT2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float a = t2[(mt * 4 + r) * 64];
-                rc[mt][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, pq[0][r], rc[mt][0], 0, 0, 0);
-                rc[mt][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, pq[1][r], rc[mt][1], 0, 0, 0);
-            }
-    }
-    __syncthreads();  // every band is done with T1 and with its strip
-
-    // ---- band reduction of R through the strips (two rounds: the tiles of P, then those of Q), T4 takes T1's place meanwhile ----------
-    for (int i = tid; i < WP * 8; i += NT) reinterpret_cast<float4 *>(tab)[i] = reinterpret_cast<const float4 *>(g4)[i];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-#pragma unroll
-        for (int mt = 0; mt < MT2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) strip[(mt * 4 + r) * 64 + lane] = rc[mt][nt][r];
-        __syncthreads();
-        for (int e = tid; e < MT2 * 256; e += NT) {
-            float acc = 0.0f;
-            for (int b = 0; b < NB; ++b) acc += lds[b * STRIP + e];  // band order: reproducible
-            const int mt = e >> 8, rl = e & 255;
-            rsum[(mt * 2 + nt) * 256 + rl] = acc;
-        }
-        __syncthreads();
-    }
-
-    // ---- EF (tile-wise), S3: [U | V]^T of this band, S4: y_band, written out through the strip in 64-column groups --------------------
-    constexpr int HALF = MT2 / 2;
-    f32x4 ef[MT2][2];
-#pragma unroll
-    for (int j = 0; j < HALF; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float a = rsum[((j * 2 + 0) * 4 + r) * 64 + lane], cq = rsum[((j * 2 + 1) * 4 + r) * 64 + lane];
-            const float b = rsum[(((HALF + j) * 2 + 0) * 4 + r) * 64 + lane], dq = rsum[(((HALF + j) * 2 + 1) * 4 + r) * 64 + lane];
-            ef[j][0][r] = a - dq;
-            ef[j][1][r] = cq + b;
-            ef[HALF + j][0][r] = b + cq;
-            ef[HALF + j][1][r] = dq - a;
-        }
-    f32x4 uv[2] = {zero, zero};
-    {
-        const float *t3 = g3 + static_cast<size_t>(band) * MT2 * 4 * 64 + lane;
-#pragma unroll
-        for (int kt = 0; kt < MT2; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float b = t3[(kt * 4 + r) * 64];
-                uv[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ef[kt][0][r], b, uv[0], 0, 0, 0);
-                uv[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ef[kt][1][r], b, uv[1], 0, 0, 0);
-            }
-    }
-    for (int wt0 = 0; wt0 < d.WT; wt0 += 4) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int wt = wt0 + q;
-            if (wt < d.WT) {
-                f32x4 y = zero;
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) y = __builtin_amdgcn_mfma_f32_16x16x4f32(uv[nt][r], tab[((wt * 2 + nt) * 4 + r) * 64 + lane], y, 0, 0, 0);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) strip[(4 * lg + r) * SS + 16 * q + li] = y[r];
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        io.store(row0, 16 * wt0);
-        __builtin_amdgcn_wave_barrier();
-    }
-}
-
-// The wide kernel: blockDim.x = 64 * ceil(NB / BPW), wavefront w owns bands BPW w .. BPW w + BPW - 1 (the last wavefront may own
-// fewer).  NT = 2 nv_pad / 16 column tiles of [P | Q]; the tiles of R, EF are indexed [mt][nt], flat mt * NT + nt.
-// LDS: strips NW * STRIP | T1, later T4: WP * NT * 16 | rsum: MT2 * NT * 256 floats (320 x 320, MT2 = 6, NT = 4: 150016 B).
-template <int SQ, int MT2, int NT>
-__global__ __launch_bounds__(64 * (WIDE_MAX / 16 / BPW)) void hfs_wide_kernel(const float *__restrict__ in, float *__restrict__ out,
-                                                                              const float *__restrict__ tables, BandDims d,
-                                                                              const float *__restrict__ sq_x, SquareArgs sq) {
+// blockDim.x = 64 * ceil(NB / BPW), wavefront w owns bands BPW w .. BPW w + BPW - 1 (the last wavefront may own fewer).
+// MT2 = 2 nu_pad / 16 row tiles of R, NT = 2 nv_pad / 16 column tiles of [P | Q]; the tiles of R, EF are indexed [mt][nt], flat
+// mt * NT + nt.  LDS: strips NW * STRIP | T1, later T4: WP * NT * 16 | rsum: MT2 * NT * 256 floats (256 x 256, MT2 = 4, NT = 2:
+// 110592 B; 320 x 320, MT2 = 6, NT = 4: 150016 B).
+template <int SQ, int MT2, int NT, int BPW>
+__global__ __launch_bounds__(BPW == 1 ? 1024 : 64 * (WIDE_MAX / 16 / BPW)) void hfs_band_kernel(const float *__restrict__ in, float *__restrict__ out,
+                                                                                                const float *__restrict__ tables, BandDims d,
+                                                                                                const float *__restrict__ sq_x, SquareArgs sq) {
+    static_assert(BPW != 1 || NT == 2, "one band per wavefront is the 256 x 256 class: [P | Q] 32 columns wide");
     extern __shared__ __align__(16) float lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
     const int WP = d.WP, NB = d.NB, NW = (NB + BPW - 1) / BPW, NTHR = NW * 64;
@@ -279,6 +158,7 @@ __global__ __launch_bounds__(64 * (WIDE_MAX / 16 / BPW)) void hfs_wide_kernel(co
     const int n1 = WP / 4 * NT, n2 = NB * MT2 * 4, n3 = n2;  // fragments of T1, T2, T3
     const float *g1 = tables, *g2 = g1 + n1 * 64, *g3 = g2 + n2 * 64, *g4 = g3 + n3 * 64;
     const BandIO<SQ> io(in, out, sq_x, sq, blockIdx.x, d.C, d.H, d.W, strip, lane);
+    const auto mine = [NB](int band) { return BPW == 1 || band < NB; };  // wave-uniform; one band per wavefront: every wavefront has its band
 
     // ---- T1 -> LDS ----------------------------------------------------------------------------------------------------------
     for (int i = tid; i < WP * NT * 4; i += NTHR) reinterpret_cast<float4 *>(tab)[i] = reinterpret_cast<const float4 *>(g1)[i];
@@ -292,7 +172,7 @@ __global__ __launch_bounds__(64 * (WIDE_MAX / 16 / BPW)) void hfs_wide_kernel(co
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) pq[k][nt] = zero;
         const int band = wave * BPW + k, row0 = 16 * band;
-        if (band < NB) {  // wave-uniform
+        if (mine(band)) {
             float4 cur[4], nxt[4];
             io.load(row0, 0, cur);
             for (int col0 = 0; col0 < WP; col0 += KC) {
@@ -323,7 +203,7 @@ __global__ __launch_bounds__(64 * (WIDE_MAX / 16 / BPW)) void hfs_wide_kernel(co
 #pragma unroll
     for (int k = 0; k < BPW; ++k) {
         const int band = wave * BPW + k;
-        if (band < NB) {
+        if (mine(band)) {
             const float *t2 = g2 + static_cast<size_t>(band) * MT2 * 4 * 64 + lane;
 #pragma unroll
             for (int mt = 0; mt < MT2; ++mt)
@@ -374,7 +254,7 @@ __global__ __launch_bounds__(64 * (WIDE_MAX / 16 / BPW)) void hfs_wide_kernel(co
 #pragma unroll
     for (int k = 0; k < BPW; ++k) {
         const int band = wave * BPW + k, row0 = 16 * band;
-        if (band >= NB) break;
+        if (!mine(band)) break;
         f32x4 uv[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) uv[nt] = zero;
@@ -415,68 +295,24 @@ int table_floats(int H, int W, int nu_pad, int nv_pad) {
     return (wp / 4 * nt + 2 * (hp / 16) * mt2 * 4 + (wp / 16) * nt * 4) * 64;
 }
 
+bool narrow_pads(int nu_pad) { return nu_pad == 16 || nu_pad == 32; }
 bool wide_pads(int nu_pad, int nv_pad) { return (nu_pad == 16 || nu_pad == 32 || nu_pad == 48) && (nv_pad == 16 || nv_pad == 32); }
 
-}  // namespace
-
-EE_API int ee_hfs_mfma_table_floats(int H, int W, int nu_pad) {
-    if (H < 1 || W < 1 || H > 256 || W > 256 || (nu_pad != 16 && nu_pad != 32)) return EE_ERR_SHAPE;
-    return table_floats(H, W, nu_pad, 16);
+// f(V) with the one of V... that equals v as a constant: in a generic lambda, `kernel<decltype(V)::value>` names the instantiation
+template <int... V, class F>
+void with_constant(int v, F f) {
+    (void)((v == V && (f(std::integral_constant<int, V>{}), true)) || ...);
 }
 
-EE_API int ee_hfs_mfma_f32(const float *in, float *out, int B, int C, int H, int W, const float *tables, int nu_pad, int sq_mode,
-                           const float *sq_x, float eps, const float *stripe, const float *sq_sign, const int64_t *sq_pos, const int32_t *sq_size,
-                           int nq, void *stream) {
-    if (B < 0 || C < 1 || H < 1 || W < 1 || sq_mode < 0 || sq_mode > 2 || nq < 0) return EE_ERR_SHAPE;
-    if (H > 256 || W > 256 || (nu_pad != 16 && nu_pad != 32)) return EE_ERR_UNSUPPORTED;
-    if (B == 0) return EE_OK;
-    if (!in || !out || !tables) return EE_ERR_NULL;
-    if (sq_mode != 0 && (!stripe || (nq > 0 && (!sq_sign || !sq_pos || !sq_size)))) return EE_ERR_NULL;
-    if (sq_mode == 2 && !sq_x) return EE_ERR_NULL;
-    if (reinterpret_cast<uintptr_t>(tables) & 15u) return EE_ERR_ALIGN;
-    BandDims d{H, W, (H + 15) / 16 * 16, (W + 15) / 16 * 16, 0, 0, C};
-    d.NB = d.HP / 16;
-    d.WT = d.WP / 16;
-    const int mt2 = 2 * nu_pad / 16;
-    const size_t lds_bytes = sizeof(float) * (static_cast<size_t>(d.NB) * STRIP + static_cast<size_t>(d.WP) * 32 + static_cast<size_t>(mt2) * 512);
-    SquareArgs sq{stripe, sq_sign, sq_pos, sq_size, nq, C, H, W, eps, static_cast<float>(2.0 * static_cast<double>(eps))};
-    const dim3 grid(static_cast<unsigned>(static_cast<int64_t>(B) * C)), block(static_cast<unsigned>(d.NB * 64));
-    hipStream_t st = as_stream(stream);
-    ProfScope prof(sq_mode == 0 ? EE_K_HFS : (sq_mode == 1 ? EE_K_HFS_SQ_FWD : EE_K_HFS_SQ_BWD), st);
-#define EE_BAND_LAUNCH(KERNEL_)                                                                                                \
-    do {                                                                                                                       \
-        static bool opted = false;                                                                                             \
-        if (!opted && lds_bytes > 64 * 1024) {                                                                                 \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(KERNEL_), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != \
-                hipSuccess)                                                                                                    \
-                (void)hipGetLastError();                                                                                       \
-            opted = true;                                                                                                      \
-        }                                                                                                                      \
-        EE_LAUNCH((KERNEL_), grid, block, lds_bytes, st, in, out, tables, d, sq_x, sq);                                        \
-    } while (0)
-    if (mt2 == 2) {
-        if (sq_mode == 0) EE_BAND_LAUNCH((hfs_band_kernel<0, 2>));
-        else if (sq_mode == 1) EE_BAND_LAUNCH((hfs_band_kernel<1, 2>));
-        else EE_BAND_LAUNCH((hfs_band_kernel<2, 2>));
-    } else {
-        if (sq_mode == 0) EE_BAND_LAUNCH((hfs_band_kernel<0, 4>));
-        else if (sq_mode == 1) EE_BAND_LAUNCH((hfs_band_kernel<1, 4>));
-        else EE_BAND_LAUNCH((hfs_band_kernel<2, 4>));
-    }
-    return launch_status();
-}
-
-EE_API int ee_hfs_wide_table_floats(int H, int W, int nu_pad, int nv_pad) {
-    if (H < 1 || W < 1 || !wide_pads(nu_pad, nv_pad)) return EE_ERR_SHAPE;
-    if (H > WIDE_MAX || W > WIDE_MAX) return EE_ERR_UNSUPPORTED;
-    return table_floats(H, W, nu_pad, nv_pad);
-}
-
-EE_API int ee_hfs_wide_f32(const float *in, float *out, int B, int C, int H, int W, const float *tables, int nu_pad, int nv_pad, int sq_mode,
-                           const float *sq_x, float eps, const float *stripe, const float *sq_sign, const int64_t *sq_pos, const int32_t *sq_size,
-                           int nq, void *stream) {
-    if (B < 0 || C < 1 || H < 1 || W < 1 || sq_mode < 0 || sq_mode > 2 || nq < 0 || !wide_pads(nu_pad, nv_pad)) return EE_ERR_SHAPE;
-    if (H > WIDE_MAX || W > WIDE_MAX) return EE_ERR_UNSUPPORTED;
+// One plane class: sides up to `limit`, BPW bands per wavefront, pads_ok = (nu_pad, nv_pad) is one of the class's table widths.  The
+// two entry points differ in how they report a pad outside the set: the wide one as a shape error, ahead of the size limit, the
+// narrow one as unsupported, along with it.
+template <int BPW>
+int launch(const float *in, float *out, int B, int C, int H, int W, const float *tables, int limit, bool pads_ok, int nu_pad, int nv_pad,
+           int sq_mode, const float *sq_x, float eps, const float *stripe, const float *sq_sign, const int64_t *sq_pos, const int32_t *sq_size,
+           int nq, void *stream) {
+    if (B < 0 || C < 1 || H < 1 || W < 1 || sq_mode < 0 || sq_mode > 2 || nq < 0 || (BPW != 1 && !pads_ok)) return EE_ERR_SHAPE;
+    if (H > limit || W > limit || !pads_ok) return EE_ERR_UNSUPPORTED;
     if (B == 0) return EE_OK;
     if (!in || !out || !tables) return EE_ERR_NULL;
     if (sq_mode != 0 && (!stripe || (nq > 0 && (!sq_sign || !sq_pos || !sq_size)))) return EE_ERR_NULL;
@@ -492,22 +328,51 @@ EE_API int ee_hfs_wide_f32(const float *in, float *out, int B, int C, int H, int
     const dim3 grid(static_cast<unsigned>(static_cast<int64_t>(B) * C)), block(static_cast<unsigned>(nw * 64));
     hipStream_t st = as_stream(stream);
     ProfScope prof(sq_mode == 0 ? EE_K_HFS : (sq_mode == 1 ? EE_K_HFS_SQ_FWD : EE_K_HFS_SQ_BWD), st);
-#define EE_WIDE_SQ(MT2_, NT_)                                                                                                  \
-    do {                                                                                                                       \
-        if (sq_mode == 0) EE_BAND_LAUNCH((hfs_wide_kernel<0, MT2_, NT_>));                                                     \
-        else if (sq_mode == 1) EE_BAND_LAUNCH((hfs_wide_kernel<1, MT2_, NT_>));                                                \
-        else EE_BAND_LAUNCH((hfs_wide_kernel<2, MT2_, NT_>));                                                                  \
-    } while (0)
-    if (nt == 2) {
-        if (mt2 == 2) EE_WIDE_SQ(2, 2);
-        else if (mt2 == 4) EE_WIDE_SQ(4, 2);
-        else EE_WIDE_SQ(6, 2);
-    } else {
-        if (mt2 == 2) EE_WIDE_SQ(2, 4);
-        else if (mt2 == 4) EE_WIDE_SQ(4, 4);
-        else EE_WIDE_SQ(6, 4);
-    }
-#undef EE_WIDE_SQ
-#undef EE_BAND_LAUNCH
+    with_constant<0, 1, 2>(sq_mode, [&](auto SQ) {
+        with_constant<2, 4, 6>(mt2, [&](auto MT2) {
+            with_constant<2, 4>(nt, [&](auto NT) {
+                constexpr int sq_c = decltype(SQ)::value, mt2_c = decltype(MT2)::value, nt_c = decltype(NT)::value;
+                if constexpr (BPW != 1 || (mt2_c <= 4 && nt_c == 2)) {  // the narrow class has no wider tables
+                    const auto kernel = hfs_band_kernel<sq_c, mt2_c, nt_c, BPW>;
+                    static bool opted = false;  // per instantiation
+                    if (!opted && lds_bytes > 64 * 1024) {
+                        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) !=
+                            hipSuccess)
+                            (void)hipGetLastError();
+                        opted = true;
+                    }
+                    EE_LAUNCH(kernel, grid, block, lds_bytes, st, in, out, tables, d, sq_x, sq);
+                }
+            });
+        });
+    });
     return launch_status();
 }
+
+}  // namespace
+
+EE_API int ee_hfs_mfma_table_floats(int H, int W, int nu_pad) {
+    if (H < 1 || W < 1 || H > NARROW_MAX || W > NARROW_MAX || !narrow_pads(nu_pad)) return EE_ERR_SHAPE;
+    return table_floats(H, W, nu_pad, 16);
+}
+
+EE_API int ee_hfs_mfma_f32(const float *in, float *out, int B, int C, int H, int W, const float *tables, int nu_pad, int sq_mode,
+                           const float *sq_x, float eps, const float *stripe, const float *sq_sign, const int64_t *sq_pos, const int32_t *sq_size,
+                           int nq, void *stream) {
+    return launch<1>(in, out, B, C, H, W, tables, NARROW_MAX, narrow_pads(nu_pad), nu_pad, 16, sq_mode, sq_x, eps, stripe, sq_sign, sq_pos,
+                     sq_size, nq, stream);
+}
+
+EE_API int ee_hfs_wide_table_floats(int H, int W, int nu_pad, int nv_pad) {
+    if (H < 1 || W < 1 || !wide_pads(nu_pad, nv_pad)) return EE_ERR_SHAPE;
+    if (H > WIDE_MAX || W > WIDE_MAX) return EE_ERR_UNSUPPORTED;
+    return table_floats(H, W, nu_pad, nv_pad);
+}
+
+EE_API int ee_hfs_wide_f32(const float *in, float *out, int B, int C, int H, int W, const float *tables, int nu_pad, int nv_pad, int sq_mode,
+                           const float *sq_x, float eps, const float *stripe, const float *sq_sign, const int64_t *sq_pos, const int32_t *sq_size,
+                           int nq, void *stream) {
+    return launch<WIDE_BPW>(in, out, B, C, H, W, tables, WIDE_MAX, wide_pads(nu_pad, nv_pad), nu_pad, nv_pad, sq_mode, sq_x, eps, stripe, sq_sign,
+                            sq_pos, sq_size, nq, stream);
+}
+

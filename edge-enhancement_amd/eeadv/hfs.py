@@ -51,12 +51,19 @@ def hfs_matrices(H, W, r):
     return Ar, Ai, B1, B2
 
 
-def lowrank_tables(H, W, r):
-    """The device table of ee_hfs_f32 (layout documented in include/eeadv.h): cos / sin factors of the operator's
-    exact low-rank form  y = U Cw^T + V Sw^T  (csrc/ee_hfs.hip).  Returns (float32 array, NU, NV)."""
+def _kept(H, W, r):
+    """float64 (us, vs, kap): the signed kept row frequencies (indices >= H/2 are negative frequencies), the kept column
+    frequencies of the half spectrum v <= W/2, and their weights k_v."""
     us = np.array([u if u < H / 2 else u - H for u in keep_set(H, r)], dtype=np.float64)
     vs = np.array([v for v in keep_set(W, r) if v <= W // 2], dtype=np.float64)
     kap = np.array([1.0 if (v == 0 or (W % 2 == 0 and v == W // 2)) else 2.0 for v in vs])
+    return us, vs, kap
+
+
+def lowrank_tables(H, W, r):
+    """The device table of ee_hfs_f32 (layout documented in include/eeadv.h): cos / sin factors of the operator's
+    exact low-rank form  y = U Cw^T + V Sw^T  (csrc/ee_hfs.hip).  Returns (float32 array, NU, NV)."""
+    us, vs, kap = _kept(H, W, r)
     NU, NV = len(us), len(vs)
     up, vp, Hp, Wp = (NU + 3) & ~3, (NV + 3) & ~3, (H + 3) & ~3, (W + 3) & ~3
     hs = Hp + 4
@@ -80,9 +87,7 @@ def chain_tables(H, W, r):
     kernels (csrc/ee_chain.hip).  Layout = scripts/chain_emulate.py (which checks the index algebra against hfs_matrices):
     t1 [Wp/4][64] | t2 [2][Hp/16][4][64] | t3 [Hp/16][2][4][64] | t4 [Wp/16][4][64], lane l <-> (l & 15, l >> 4).
     cos / sin column blocks are padded to 8 (v) and 16 (u) entries with zeros, Hp / Wp = H / W rounded up to 16."""
-    us = np.array([u if u < H / 2 else u - H for u in keep_set(H, r)], dtype=np.float64)
-    vs = np.array([v for v in keep_set(W, r) if v <= W // 2], dtype=np.float64)
-    kap = np.array([1.0 if (v == 0 or (W % 2 == 0 and v == W // 2)) else 2.0 for v in vs])
+    us, vs, kap = _kept(H, W, r)
     NU, NV = len(us), len(vs)
     if NU > 16 or NV > 8 or H > 64 or W > 64:
         raise ValueError("chain_tables: %dx%d r=%d is outside the fused kernels' shape class" % (H, W, r))
@@ -105,50 +110,16 @@ def chain_tables(H, W, r):
     return np.ascontiguousarray(np.concatenate(t1 + t2 + t3 + t4), dtype=np.float32)
 
 
-def band_tables(H, W, r):
-    """Fragment-ordered constant operands of ee_hfs_mfma_f32 (planes up to 256 x 256; csrc/ee_hfs_mfma.hip).  Layout =
-    scripts/chain_emulate.py big_tables: t1 [Wp/4][2][64] | t2 [Hp/16][MT2][4][64] | t3 [Hp/16][MT2][4][64] | t4 [Wp/16][2][4][64];
-    cos / sin blocks padded to 16 column frequencies and NUp = 16 or 32 row frequencies.  Returns (float32 array, NUp)."""
-    us = np.array([u if u < H / 2 else u - H for u in keep_set(H, r)], dtype=np.float64)
-    vs = np.array([v for v in keep_set(W, r) if v <= W // 2], dtype=np.float64)
-    kap = np.array([1.0 if (v == 0 or (W % 2 == 0 and v == W // 2)) else 2.0 for v in vs])
+def _fragment_tables(name, entry, H, W, r, limit, nu_pads, nv_pads):
+    """Fragment-ordered constant operands of the band kernel (csrc/ee_hfs_mfma.hip) for one of its plane classes: sides up to
+    `limit`, cos / sin blocks padded to the smallest of `nu_pads` row and of `nv_pads` column frequencies that holds the kept ones.
+    Layout = scripts/chain_emulate.py wide_tables: t1 [Wp/4][NT][64] | t2 [Hp/16][MT2][4][64] | t3 [Hp/16][MT2][4][64] |
+    t4 [Wp/16][NT][4][64] with MT2 = 2 NUp / 16, NT = 2 NVp / 16.  Returns (float32 array, NUp, NVp)."""
+    us, vs, kap = _kept(H, W, r)
     NU, NV = len(us), len(vs)
-    if NU > 32 or NV > 16 or H > 256 or W > 256:
-        raise ValueError("band_tables: %dx%d r=%d is outside ee_hfs_mfma_f32's shape class" % (H, W, r))
-    NUp = 16 if NU <= 16 else 32
-    MT2 = 2 * NUp // 16
-    Hp, Wp = (H + 15) // 16 * 16, (W + 15) // 16 * 16
-    lanes = np.arange(64)
-    li, lg = lanes & 15, lanes >> 4
-    h, w = np.arange(H)[:, None], np.arange(W)[:, None]
-    Ch, Sh, Cw, Sw = np.zeros((Hp, NUp)), np.zeros((Hp, NUp)), np.zeros((Wp, 16)), np.zeros((Wp, 16))
-    Ch[:H, :NU], Sh[:H, :NU] = np.cos(2 * np.pi * h * us[None, :] / H), np.sin(2 * np.pi * h * us[None, :] / H)
-    Cw[:W, :NV], Sw[:W, :NV] = np.cos(2 * np.pi * w * vs[None, :] / W), np.sin(2 * np.pi * w * vs[None, :] / W)
-    dv = np.zeros(16)
-    dv[:NV] = kap / W
-    T1 = np.concatenate([Cw * dv, Sw * dv], 1)   # [Wp, 32]
-    CS = np.concatenate([Ch, Sh], 1)             # [Hp, 2 NUp]
-    T4 = np.concatenate([Cw.T, Sw.T], 0)         # [32, Wp]
-    t1 = [T1[4 * s + lg, 16 * nt + li] for s in range(Wp // 4) for nt in range(2)]
-    t2 = [CS[16 * t + 4 * lg + rr, 16 * mt + li] for t in range(Hp // 16) for mt in range(MT2) for rr in range(4)]
-    t3 = [CS[16 * ht + li, 16 * kt + 4 * lg + rr] / H for ht in range(Hp // 16) for kt in range(MT2) for rr in range(4)]
-    t4 = [T4[16 * nt + 4 * lg + rr, 16 * wt + li] for wt in range(Wp // 16) for nt in range(2) for rr in range(4)]
-    return np.ascontiguousarray(np.concatenate(t1 + t2 + t3 + t4), dtype=np.float32), NUp
-
-
-def wide_tables(H, W, r):
-    """Fragment-ordered constant operands of ee_hfs_wide_f32 (planes up to 320 x 320, at most 48 kept row and 32 kept column
-    frequencies: ImageNet/fgsm_imagenet phase 3, 288 x 288, r = 18; csrc/ee_hfs_mfma.hip).  Layout = scripts/chain_emulate.py
-    wide_tables: t1 [Wp/4][NT][64] | t2 [Hp/16][MT2][4][64] | t3 [Hp/16][MT2][4][64] | t4 [Wp/16][NT][4][64] with MT2 = 2 NUp / 16,
-    NT = 2 NVp / 16; cos / sin blocks padded to NUp = 16, 32 or 48 row and NVp = 16 or 32 column frequencies.
-    Returns (float32 array, NUp, NVp)."""
-    us = np.array([u if u < H / 2 else u - H for u in keep_set(H, r)], dtype=np.float64)
-    vs = np.array([v for v in keep_set(W, r) if v <= W // 2], dtype=np.float64)
-    kap = np.array([1.0 if (v == 0 or (W % 2 == 0 and v == W // 2)) else 2.0 for v in vs])
-    NU, NV = len(us), len(vs)
-    if NU > 48 or NV > 32 or H > 320 or W > 320:
-        raise ValueError("wide_tables: %dx%d r=%d is outside ee_hfs_wide_f32's shape class" % (H, W, r))
-    NUp, NVp = (NU + 15) // 16 * 16, (NV + 15) // 16 * 16
+    if NU > nu_pads[-1] or NV > nv_pads[-1] or H > limit or W > limit:
+        raise ValueError("%s: %dx%d r=%d is outside %s's shape class" % (name, H, W, r, entry))
+    NUp, NVp = min(p for p in nu_pads if p >= NU), min(p for p in nv_pads if p >= NV)
     MT2, NT = 2 * NUp // 16, 2 * NVp // 16
     Hp, Wp = (H + 15) // 16 * 16, (W + 15) // 16 * 16
     lanes = np.arange(64)
@@ -169,11 +140,22 @@ def wide_tables(H, W, r):
     return np.ascontiguousarray(np.concatenate(t1 + t2 + t3 + t4), dtype=np.float32), NUp, NVp
 
 
+def band_tables(H, W, r):
+    """The tables of ee_hfs_mfma_f32: planes up to 256 x 256, NUp = 16 or 32, 16 column frequencies.  Returns (float32 array, NUp)."""
+    return _fragment_tables("band_tables", "ee_hfs_mfma_f32", H, W, r, 256, (16, 32), (16,))[:2]
+
+
+def wide_tables(H, W, r):
+    """The tables of ee_hfs_wide_f32: planes up to 320 x 320, NUp = 16, 32 or 48, NVp = 16 or 32 (ImageNet/fgsm_imagenet phase 3,
+    288 x 288, r = 18: 48 and 32).  Returns (float32 array, NUp, NVp)."""
+    return _fragment_tables("wide_tables", "ee_hfs_wide_f32", H, W, r, 320, (16, 32, 48), (16, 32))
+
+
 class HFSOperator:
     """Device-resident factors of the operator (which equals its own adjoint).  ROCm planes up to 64x64 go through the
-    single-launch LDS kernel ee_hfs_f32, planes up to 256x256 (ImageNet 224x224, r = 16) through the matrix-core kernel
-    ee_hfs_mfma_f32, and what neither takes, up to 320x320 (fast-AT phase 3: 288x288, r = 18), through its two-bands-per-wavefront
-    sibling ee_hfs_wide_f32 (`self.wide`); anything larger and the CPU plumbing path use the dense form."""
+    single-launch LDS kernel ee_hfs_f32, larger ones through the matrix-core band kernel: ee_hfs_mfma_f32 up to 256x256 (ImageNet
+    224x224, r = 16), ee_hfs_wide_f32 (`self.wide`) for what neither takes, up to 320x320 (fast-AT phase 3: 288x288, r = 18);
+    anything larger and the CPU plumbing path use the dense form."""
 
     def __init__(self, H, W, r, device):
         Ar, Ai, B1, B2 = hfs_matrices(H, W, r)
@@ -192,7 +174,7 @@ class HFSOperator:
                 self.mfma = (torch.from_numpy(flat).to(device), nu_pad)
             except ValueError:
                 pass
-        self.wide = None   # ... and of the wide kernel for what neither of the two takes (two bands per wavefront, same file)
+        self.wide = None   # ... and of its wide class for what neither of the two takes (two bands per wavefront)
         if torch.device(device).type == "cuda" and self.kernel is None and self.mfma is None:
             try:
                 flat, nu_pad, nv_pad = wide_tables(H, W, r)
@@ -201,6 +183,13 @@ class HFSOperator:
                 pass
         f = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device=device, dtype=torch.float32)
         self.H, self.W = H, W
+        self._route = None  # (name of the ops function, its arguments after x) of the kernel a device plane goes through
+        if self._use_lds_kernel:
+            self._route = ("hfs", self.kernel)
+        elif self.mfma is not None:
+            self._route = ("hfs_mfma", self.mfma)
+        elif self.wide is not None:
+            self._route = ("hfs_wide", self.wide)
         self.Bcat = f(np.concatenate([B1, B2], axis=1))      # [W, 2W]   x @ Bcat = [x B1 | x B2]
         self.Ar, self.Ai = f(Ar), f(Ai)                      # [H, H]
         # adjoint: g_x = Ar^T g B1^T + Ai^T g B2^T
@@ -226,55 +215,32 @@ class HFSOperator:
     @property
     def fused_square(self):
         """True when Add_Square can be fused into the low-pass kernel's load / store (one launch each way)."""
-        return self.kernel is not None or self.mfma is not None or self.wide is not None
+        return self._route is not None
+
+    def _run(self, x, sq_mode, sq_x, eps, draws):
+        """One launch of this plane's kernel; the ops function is looked up by name at call time."""
+        from . import ops
+        name, lead = self._route
+        sq = () if draws is None else (draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
+        return getattr(ops, name)(x.contiguous(), *lead, sq_mode, sq_x, eps, *sq)
 
     def forward(self, x):
-        if x.is_cuda and self._use_lds_kernel:
-            from . import ops
-            return ops.hfs(x.contiguous(), *self.kernel)
-        if x.is_cuda and self.mfma is not None:
-            from . import ops
-            return ops.hfs_mfma(x.contiguous(), *self.mfma)
-        if x.is_cuda and self.wide is not None:
-            from . import ops
-            return ops.hfs_wide(x.contiguous(), *self.wide)
+        if x.is_cuda and self._route is not None:
+            return self._run(x, 0, None, 0.0, None)
         return self._apply(x, self.Bcat, self.Ar, self.Ai)
 
     def adjoint(self, g):
-        if g.is_cuda and self._use_lds_kernel:
-            from . import ops
-            return ops.hfs(g.contiguous(), *self.kernel)  # self-adjoint
-        if g.is_cuda and self.mfma is not None:
-            from . import ops
-            return ops.hfs_mfma(g.contiguous(), *self.mfma)
-        if g.is_cuda and self.wide is not None:
-            from . import ops
-            return ops.hfs_wide(g.contiguous(), *self.wide)
+        if g.is_cuda and self._route is not None:
+            return self._run(g, 0, None, 0.0, None)  # self-adjoint
         return self._apply(g, self.BcatT, self.ArT, self.AiT)
 
     def forward_square(self, x, eps, draws):
         """F(add_square(x)) in one launch."""
-        from . import ops
-        if self._use_lds_kernel:
-            t, NU, NV = self.kernel
-            return ops.hfs(x.contiguous(), t, NU, NV, 1, None, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
-        if self.mfma is None:
-            t, nu_pad, nv_pad = self.wide
-            return ops.hfs_wide(x.contiguous(), t, nu_pad, nv_pad, 1, None, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
-        t, nu_pad = self.mfma
-        return ops.hfs_mfma(x.contiguous(), t, nu_pad, 1, None, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
+        return self._run(x, 1, None, eps, draws)
 
     def backward_square(self, g, x, eps, draws):
         """F(g) * d add_square/dx (x): the backward of forward_square, one launch."""
-        from . import ops
-        if self._use_lds_kernel:
-            t, NU, NV = self.kernel
-            return ops.hfs(g.contiguous(), t, NU, NV, 2, x, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
-        if self.mfma is None:
-            t, nu_pad, nv_pad = self.wide
-            return ops.hfs_wide(g.contiguous(), t, nu_pad, nv_pad, 2, x, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
-        t, nu_pad = self.mfma
-        return ops.hfs_mfma(g.contiguous(), t, nu_pad, 2, x, eps, draws["stripe"], draws["sq_sign"], draws["sq_pos"], draws["sq_size"])
+        return self._run(g, 2, x, eps, draws)
 
 
 class _HFSFn(torch.autograd.Function):

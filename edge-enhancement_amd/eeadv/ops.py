@@ -1061,25 +1061,37 @@ def cascade_resolve_(robust, ids, x_adv, n_valid, stage, robust_out, stage_out, 
 
 
 # ---- Add_Square ------------------------------------------------------------------------------------------------------
-def add_square_fwd(x, eps, stripe, sq_sign, sq_pos, sq_size):
+def _square_ptrs(sq_mode, x, sq_x, stripe, sq_sign, sq_pos, sq_size):
+    """The Add_Square arguments of a native call, checked against x [B,C,H,W]: (stripe, sq_sign, sq_pos, sq_size, sq_x, nq).
+    All empty at sq_mode 0; sq_x only at sq_mode 2."""
+    if not sq_mode:
+        return None, None, None, None, None, 0
     B, C, H, W = x.shape
     nq = int(sq_size.numel())
+    ps = _chk(stripe, torch.float32, "stripe", (B, C, 1, W))
+    pg = _chk(sq_sign, torch.float32, "sq_sign", (nq, C))
+    pp = _chk(sq_pos, torch.int64, "sq_pos", (nq,))
+    pz = _chk(sq_size, torch.int32, "sq_size", (nq,))
+    pxo = _chk(sq_x, torch.float32, "sq_x", x.shape) if sq_mode == 2 else None
+    return ps, pg, pp, pz, pxo, nq
+
+
+def add_square_fwd(x, eps, stripe, sq_sign, sq_pos, sq_size):
+    B, C, H, W = x.shape
     out = torch.empty_like(x)
-    N.check(N.lib.ee_add_square_fwd_f32(_chk(x, torch.float32, "x"), B, C, H, W, eps, _chk(stripe, torch.float32, "stripe", (B, C, 1, W)),
-                                        _chk(sq_sign, torch.float32, "sq_sign", (nq, C)), _chk(sq_pos, torch.int64, "sq_pos", (nq,)),
-                                        _chk(sq_size, torch.int32, "sq_size", (nq,)), nq, _chk(out, torch.float32, "out"), _stream()),
+    px = _chk(x, torch.float32, "x")
+    ps, pg, pp, pz, _, nq = _square_ptrs(1, x, None, stripe, sq_sign, sq_pos, sq_size)
+    N.check(N.lib.ee_add_square_fwd_f32(px, B, C, H, W, eps, ps, pg, pp, pz, nq, _chk(out, torch.float32, "out"), _stream()),
             "ee_add_square_fwd_f32")
     return out
 
 
 def add_square_bwd(g_out, x, eps, stripe, sq_sign, sq_pos, sq_size):
     B, C, H, W = x.shape
-    nq = int(sq_size.numel())
     g_x = torch.empty_like(x)
-    N.check(N.lib.ee_add_square_bwd_f32(_chk(g_out, torch.float32, "g_out", x.shape), _chk(x, torch.float32, "x"), B, C, H, W, eps,
-                                        _chk(stripe, torch.float32, "stripe", (B, C, 1, W)),
-                                        _chk(sq_sign, torch.float32, "sq_sign", (nq, C)), _chk(sq_pos, torch.int64, "sq_pos", (nq,)),
-                                        _chk(sq_size, torch.int32, "sq_size", (nq,)), nq, _chk(g_x, torch.float32, "g_x"), _stream()),
+    pgo, px = _chk(g_out, torch.float32, "g_out", x.shape), _chk(x, torch.float32, "x")
+    ps, pg, pp, pz, _, nq = _square_ptrs(1, x, None, stripe, sq_sign, sq_pos, sq_size)
+    N.check(N.lib.ee_add_square_bwd_f32(pgo, px, B, C, H, W, eps, ps, pg, pp, pz, nq, _chk(g_x, torch.float32, "g_x"), _stream()),
             "ee_add_square_bwd_f32")
     return g_x
 
@@ -1099,68 +1111,38 @@ def square_draw(batch, C, h, sq_size, state):
     return stripe, sq_pos, sq_sign
 
 
-def hfs(x, tables, NU, NV, sq_mode=0, sq_x=None, eps=0.0, stripe=None, sq_sign=None, sq_pos=None, sq_size=None):
-    """y = F(x) (sq_mode 0), F(add_square(x)) (1) or F(x) * d add_square/dx at sq_x (2); F = the low-pass operator."""
+def _hfs(entry, need, lead, x, tables, sq_mode, sq_x, eps, stripe, sq_sign, sq_pos, sq_size):
+    """The shared body of the three low-pass wrappers: `entry` is the native function, `need` its table-size query's answer for
+    x's plane, `lead` the arguments between the table and sq_mode."""
     B, C, H, W = x.shape
     px = _chk(x, torch.float32, "x")
-    need = N.lib.ee_hfs_table_floats(H, W, NU, NV)
     pt = _chk(tables, torch.float32, "tables", (need,))
     out = torch.empty_like(x)
-    nq = 0
-    ps = pg = pp = pz = pxo = None
-    if sq_mode:
-        nq = int(sq_size.numel())
-        ps = _chk(stripe, torch.float32, "stripe", (B, C, 1, W))
-        pg = _chk(sq_sign, torch.float32, "sq_sign", (nq, C))
-        pp = _chk(sq_pos, torch.int64, "sq_pos", (nq,))
-        pz = _chk(sq_size, torch.int32, "sq_size", (nq,))
-        if sq_mode == 2:
-            pxo = _chk(sq_x, torch.float32, "sq_x", x.shape)
-    N.check(N.lib.ee_hfs_f32(px, _chk(out, torch.float32, "out"), B, C, H, W, pt, NU, NV, 1.0 / H, sq_mode, pxo, eps, ps, pg, pp, pz, nq,
-                             _stream()), "ee_hfs_f32")
+    ps, pg, pp, pz, pxo, nq = _square_ptrs(sq_mode, x, sq_x, stripe, sq_sign, sq_pos, sq_size)
+    N.check(getattr(N.lib, entry)(px, _chk(out, torch.float32, "out"), B, C, H, W, pt, *lead, sq_mode, pxo, eps, ps, pg, pp, pz, nq, _stream()),
+            entry)
     return out
+
+
+def hfs(x, tables, NU, NV, sq_mode=0, sq_x=None, eps=0.0, stripe=None, sq_sign=None, sq_pos=None, sq_size=None):
+    """y = F(x) (sq_mode 0), F(add_square(x)) (1) or F(x) * d add_square/dx at sq_x (2); F = the low-pass operator."""
+    H, W = x.shape[2:]
+    return _hfs("ee_hfs_f32", N.lib.ee_hfs_table_floats(H, W, NU, NV), (NU, NV, 1.0 / H), x, tables, sq_mode, sq_x, eps, stripe, sq_sign,
+                sq_pos, sq_size)
 
 
 def hfs_mfma(x, tables, nu_pad, sq_mode=0, sq_x=None, eps=0.0, stripe=None, sq_sign=None, sq_pos=None, sq_size=None):
     """The same operator as `hfs` for planes up to 256 x 256, on the matrix cores (ee_hfs_mfma.hip)."""
-    B, C, H, W = x.shape
-    px = _chk(x, torch.float32, "x")
-    pt = _chk(tables, torch.float32, "tables", (N.lib.ee_hfs_mfma_table_floats(H, W, nu_pad),))
-    out = torch.empty_like(x)
-    nq = 0
-    ps = pg = pp = pz = pxo = None
-    if sq_mode:
-        nq = int(sq_size.numel())
-        ps = _chk(stripe, torch.float32, "stripe", (B, C, 1, W))
-        pg = _chk(sq_sign, torch.float32, "sq_sign", (nq, C))
-        pp = _chk(sq_pos, torch.int64, "sq_pos", (nq,))
-        pz = _chk(sq_size, torch.int32, "sq_size", (nq,))
-        if sq_mode == 2:
-            pxo = _chk(sq_x, torch.float32, "sq_x", x.shape)
-    N.check(N.lib.ee_hfs_mfma_f32(px, _chk(out, torch.float32, "out"), B, C, H, W, pt, nu_pad, sq_mode, pxo, eps, ps, pg, pp, pz, nq, _stream()),
-            "ee_hfs_mfma_f32")
-    return out
+    H, W = x.shape[2:]
+    return _hfs("ee_hfs_mfma_f32", N.lib.ee_hfs_mfma_table_floats(H, W, nu_pad), (nu_pad,), x, tables, sq_mode, sq_x, eps, stripe, sq_sign,
+                sq_pos, sq_size)
 
 
 def hfs_wide(x, tables, nu_pad, nv_pad, sq_mode=0, sq_x=None, eps=0.0, stripe=None, sq_sign=None, sq_pos=None, sq_size=None):
     """The same operator for planes up to 320 x 320 with up to 48 kept row and 32 kept column frequencies (ee_hfs_wide_f32)."""
-    B, C, H, W = x.shape
-    px = _chk(x, torch.float32, "x")
-    pt = _chk(tables, torch.float32, "tables", (N.lib.ee_hfs_wide_table_floats(H, W, nu_pad, nv_pad),))
-    out = torch.empty_like(x)
-    nq = 0
-    ps = pg = pp = pz = pxo = None
-    if sq_mode:
-        nq = int(sq_size.numel())
-        ps = _chk(stripe, torch.float32, "stripe", (B, C, 1, W))
-        pg = _chk(sq_sign, torch.float32, "sq_sign", (nq, C))
-        pp = _chk(sq_pos, torch.int64, "sq_pos", (nq,))
-        pz = _chk(sq_size, torch.int32, "sq_size", (nq,))
-        if sq_mode == 2:
-            pxo = _chk(sq_x, torch.float32, "sq_x", x.shape)
-    N.check(N.lib.ee_hfs_wide_f32(px, _chk(out, torch.float32, "out"), B, C, H, W, pt, nu_pad, nv_pad, sq_mode, pxo, eps, ps, pg, pp, pz, nq,
-                                  _stream()), "ee_hfs_wide_f32")
-    return out
+    H, W = x.shape[2:]
+    return _hfs("ee_hfs_wide_f32", N.lib.ee_hfs_wide_table_floats(H, W, nu_pad, nv_pad), (nu_pad, nv_pad), x, tables, sq_mode, sq_x, eps,
+                stripe, sq_sign, sq_pos, sq_size)
 
 
 # ---- the fused front end of one PGD iteration (ee_chain.hip) ------------------------------------------------------------------------

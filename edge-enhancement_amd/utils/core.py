@@ -23,7 +23,7 @@ from eeadv import functional as EF, hfs as _hfs, ops, runtime, sqatk
 # function to suppress high freqency components (core.py:15-55)
 class HighFreqSuppress(torch.nn.Module):
     """On a ROCm device one HIP launch per call (eeadv.hfs.HFSOperator): the LDS kernel for planes up to 64 x 64, the matrix-core band
-    kernel up to 256 x 256 (224, r = 16), its two-bands-per-wavefront sibling up to 320 x 320 (288, r = 18); past that, and on the CPU,
+    kernel up to 256 x 256 (224, r = 16) and, two bands per wavefront, up to 320 x 320 (288, r = 18); past that, and on the CPU,
     the dense form of the same operator."""
 
     def __init__(self, w, h, r):

@@ -1087,15 +1087,15 @@ int ee_ce_pool_linear_bwd_f32(const float *logits, const int64_t *labels, float 
 /* HighFreqSuppress for planes up to 256 x 256 (ImageNet 224 x 224, r = 16: utils/core.py:15-55 with cize 224) on the f32 matrix
  * cores, one workgroup per plane, one wavefront per 16-row band (csrc/ee_hfs_mfma.hip).  Same operator, same sq_mode fusions and
  * draw arrays as ee_hfs_f32.  `tables`: ee_hfs_mfma_table_floats(H, W, nu_pad) floats in MFMA fragment order (eeadv/hfs.py:
- * band_tables; scripts/chain_emulate.py big_tables is the layout's specification); nu_pad = 16 or 32 = the kept row frequencies
- * rounded up.  8 B of HBM traffic per element (12 with sq_mode 2). */
+ * band_tables; the layout is ee_hfs_wide_f32's below at nv_pad = 16); nu_pad = 16 or 32 = the kept row frequencies rounded up.
+ * 8 B of HBM traffic per element (12 with sq_mode 2). */
 int ee_hfs_mfma_table_floats(int H, int W, int nu_pad);
 int ee_hfs_mfma_f32(const float *in, float *out, int B, int C, int H, int W, const float *tables, int nu_pad, int sq_mode,
                     const float *sq_x, float eps, const float *stripe, const float *sq_sign, const int64_t *sq_pos, const int32_t *sq_size,
                     int nq, void *stream);
 /* ... and for planes past that class, up to 320 x 320 with at most 48 kept row and 32 kept column frequencies (ImageNet/fgsm_imagenet
- * phase 3: 288 x 288, r = 18 keeps 36 and 18): the same chain with two consecutive 16-row bands per wavefront and [P | Q] up to 64
- * columns wide (hfs_wide_kernel, same file).  nu_pad = 16, 32 or 48 and nv_pad = 16 or 32 = the kept row / column frequencies rounded
+ * phase 3: 288 x 288, r = 18 keeps 36 and 18): the same kernel with two consecutive 16-row bands per wavefront and [P | Q] up to 64
+ * columns wide.  nu_pad = 16, 32 or 48 and nv_pad = 16 or 32 = the kept row / column frequencies rounded
  * up.  `tables`: ee_hfs_wide_table_floats(H, W, nu_pad, nv_pad) floats in MFMA fragment order (eeadv/hfs.py: wide_tables;
  * scripts/chain_emulate.py wide_tables is the layout's specification), with Hp / Wp = H / W rounded up to 16, MT2 = 2 nu_pad / 16,
  * NT = 2 nv_pad / 16 and lane l <-> (l & 15, l >> 4):

@@ -117,98 +117,20 @@ if __name__ == "__main__":
 
 
 # ---- the band-parallel variant for planes that do not fit one wavefront's registers / the LDS (csrc/ee_hfs_mfma.hip) --------------
-def big_tables(H, W, r, dtype=np.float64):
+# One chain, two plane classes: narrow (up to 256 x 256, [P | Q] 32 columns, one band per wavefront) and wide (up to 320 x 320,
+# [P | Q] up to 64 columns, two bands per wavefront).
+NARROW = {"limit": 256, "nu_pads": (16, 32), "nv_pads": (16,), "bpw": 1}
+WIDE = {"limit": 320, "nu_pads": (16, 32, 48), "nv_pads": (16, 32), "bpw": 2}
+
+
+def wide_tables(H, W, r, dtype=np.float64, cls=WIDE):
     from eeadv.hfs import keep_set
     us = np.array([u if u < H / 2 else u - H for u in keep_set(H, r)], dtype=np.float64)
     vs = np.array([v for v in keep_set(W, r) if v <= W // 2], dtype=np.float64)
     kap = np.array([1.0 if (v == 0 or (W % 2 == 0 and v == W // 2)) else 2.0 for v in vs])
     NU, NV = len(us), len(vs)
-    assert NU <= 32 and NV <= 16
-    NUp = 16 if NU <= 16 else 32
-    MT2 = 2 * NUp // 16
-    Hp, Wp = (H + 15) // 16 * 16, (W + 15) // 16 * 16
-    h, w = np.arange(H)[:, None], np.arange(W)[:, None]
-    Ch = np.zeros((Hp, NUp)); Sh = np.zeros((Hp, NUp)); Cw = np.zeros((Wp, 16)); Sw = np.zeros((Wp, 16))
-    Ch[:H, :NU] = np.cos(2 * np.pi * h * us[None, :] / H)
-    Sh[:H, :NU] = np.sin(2 * np.pi * h * us[None, :] / H)
-    Cw[:W, :NV] = np.cos(2 * np.pi * w * vs[None, :] / W)
-    Sw[:W, :NV] = np.sin(2 * np.pi * w * vs[None, :] / W)
-    dv = np.zeros(16); dv[:NV] = kap / W
-    T1m = np.concatenate([Cw * dv, Sw * dv], 1)   # [Wp, 32]
-    CS = np.concatenate([Ch, Sh], 1)              # [Hp, 2 NUp]
-    T4m = np.concatenate([Cw.T, Sw.T], 0)         # [32, Wp]
-    t1 = np.stack([T1m[4 * s + LG, 16 * nt + LI] for s in range(Wp // 4) for nt in range(2)])
-    t2 = np.stack([CS[16 * t + 4 * LG + rr, 16 * mt + LI] for t in range(Hp // 16) for mt in range(MT2) for rr in range(4)])
-    t3 = np.stack([CS[16 * ht + LI, 16 * kt + 4 * LG + rr] / H for ht in range(Hp // 16) for kt in range(MT2) for rr in range(4)])
-    t4 = np.stack([T4m[16 * nt + 4 * LG + rr, 16 * wt + LI] for wt in range(Wp // 16) for nt in range(2) for rr in range(4)])
-    return {"t1": t1.astype(dtype), "t2": t2.astype(dtype), "t3": t3.astype(dtype), "t4": t4.astype(dtype), "Hp": Hp, "Wp": Wp, "MT2": MT2}
-
-
-def big_apply(x, T):
-    H, W = x.shape
-    Hp, Wp, MT2 = T["Hp"], T["Wp"], T["MT2"]
-    dt = T["t1"].dtype
-    xp = np.zeros((Hp, Wp), dt)
-    xp[:H, :W] = x
-    NB, WT, half = Hp // 16, Wp // 16, MT2 // 2
-    Rsum = [[np.zeros((64, 4), dt) for _ in range(2)] for _ in range(MT2)]
-    for b in range(NB):  # one wavefront per 16-row band
-        pq = [np.zeros((64, 4), dt) for _ in range(2)]
-        for s in range(Wp // 4):
-            for nt in range(2):
-                pq[nt] = mfma(xp[16 * b + LI, 4 * s + LG], T["t1"][s * 2 + nt], pq[nt])
-        for mt in range(MT2):
-            for nt in range(2):
-                acc = np.zeros((64, 4), dt)
-                for rr in range(4):
-                    acc = mfma(T["t2"][(b * MT2 + mt) * 4 + rr], pq[nt][:, rr], acc)
-                Rsum[mt][nt] += acc  # the cross-band reduction (through LDS on the device)
-    EF = [[None, None] for _ in range(MT2)]
-    for j in range(half):
-        a, c, bb, d = Rsum[j][0], Rsum[j][1], Rsum[half + j][0], Rsum[half + j][1]
-        EF[j][0], EF[j][1] = a - d, c + bb
-        EF[half + j][0], EF[half + j][1] = bb + c, d - a
-    y = np.zeros((Hp, Wp), dt)
-    for b in range(NB):
-        uvT = [np.zeros((64, 4), dt) for _ in range(2)]
-        for nt in range(2):
-            for kt in range(MT2):
-                for rr in range(4):
-                    uvT[nt] = mfma(EF[kt][nt][:, rr], T["t3"][(b * MT2 + kt) * 4 + rr], uvT[nt])
-        for wt in range(WT):
-            acc = np.zeros((64, 4), dt)
-            for nt in range(2):
-                for rr in range(4):
-                    acc = mfma(uvT[nt][:, rr], T["t4"][(wt * 2 + nt) * 4 + rr], acc)
-            for rr in range(4):
-                y[16 * b + 4 * LG + rr, 16 * wt + LI] = acc[:, rr]
-    return y[:H, :W]
-
-
-if __name__ == "__main__":
-    from eeadv.hfs import hfs_matrices
-    rng = np.random.RandomState(1)
-    for (H, W, r) in [(224, 224, 16), (64, 64, 8), (7, 9, 2), (96, 128, 12), (28, 28, 4)]:
-        x = rng.rand(H, W)
-        Ar, Ai, B1, B2 = hfs_matrices(H, W, r)
-        want = Ar @ x @ B1 + Ai @ x @ B2
-        got = big_apply(x, big_tables(H, W, r))
-        print("band variant %dx%d r=%d: f64 err %.2e" % (H, W, r, np.abs(got - want).max()))
-        assert np.abs(got - want).max() < 1e-11
-
-
-# ---- the wide variant past the band kernel's class: two bands per wavefront, [P | Q] up to 64 columns (hfs_wide_kernel) -----------------
-BPW = 2  # bands per wavefront
-
-
-def wide_tables(H, W, r, dtype=np.float64):
-    from eeadv.hfs import keep_set
-    us = np.array([u if u < H / 2 else u - H for u in keep_set(H, r)], dtype=np.float64)
-    vs = np.array([v for v in keep_set(W, r) if v <= W // 2], dtype=np.float64)
-    kap = np.array([1.0 if (v == 0 or (W % 2 == 0 and v == W // 2)) else 2.0 for v in vs])
-    NU, NV = len(us), len(vs)
-    assert NU <= 48 and NV <= 32 and H <= 320 and W <= 320
-    NUp, NVp = (NU + 15) // 16 * 16, (NV + 15) // 16 * 16
+    assert NU <= cls["nu_pads"][-1] and NV <= cls["nv_pads"][-1] and H <= cls["limit"] and W <= cls["limit"]
+    NUp, NVp = min(p for p in cls["nu_pads"] if p >= NU), min(p for p in cls["nv_pads"] if p >= NV)
     MT2, NT = 2 * NUp // 16, 2 * NVp // 16
     Hp, Wp = (H + 15) // 16 * 16, (W + 15) // 16 * 16
     h, w = np.arange(H)[:, None], np.arange(W)[:, None]
@@ -226,18 +148,18 @@ def wide_tables(H, W, r, dtype=np.float64):
     t3 = np.stack([CS[16 * ht + LI, 16 * kt + 4 * LG + rr] / H for ht in range(Hp // 16) for kt in range(MT2) for rr in range(4)])
     t4 = np.stack([T4m[16 * nt + 4 * LG + rr, 16 * wt + LI] for wt in range(Wp // 16) for nt in range(NT) for rr in range(4)])
     return {"t1": t1.astype(dtype), "t2": t2.astype(dtype), "t3": t3.astype(dtype), "t4": t4.astype(dtype), "Hp": Hp, "Wp": Wp, "MT2": MT2,
-            "NT": NT}
+            "NT": NT, "BPW": cls["bpw"]}
 
 
 def wide_apply(x, T):
     H, W = x.shape
-    Hp, Wp, MT2, NT = T["Hp"], T["Wp"], T["MT2"], T["NT"]
+    Hp, Wp, MT2, NT, BPW = T["Hp"], T["Wp"], T["MT2"], T["NT"], T["BPW"]
     dt = T["t1"].dtype
     xp = np.zeros((Hp, Wp), dt)
     xp[:H, :W] = x
     NB, WT, half, nh = Hp // 16, Wp // 16, MT2 // 2, NT // 2
     NW = (NB + BPW - 1) // BPW
-    Rsum = [[np.zeros((64, 4), dt) for _ in range(NT)] for _ in range(MT2)]
+    part = []  # per wavefront: its MT2 * NT partial R tiles, flat mt * NT + nt
     for wv in range(NW):  # one wavefront per BPW consecutive bands (the last one may own fewer)
         bands = [b for b in range(wv * BPW, wv * BPW + BPW) if b < NB]
         pq = {}
@@ -246,15 +168,23 @@ def wide_apply(x, T):
             for s in range(Wp // 4):
                 for nt in range(NT):
                     pq[b][nt] = mfma(xp[16 * b + LI, 4 * s + LG], T["t1"][s * NT + nt], pq[b][nt])
-        rc = [[np.zeros((64, 4), dt) for _ in range(NT)] for _ in range(MT2)]
+        rc = [np.zeros((64, 4), dt) for _ in range(MT2 * NT)]
         for b in bands:  # the wave's bands accumulate into the same tiles
             for mt in range(MT2):
                 for rr in range(4):
                     for nt in range(NT):
-                        rc[mt][nt] = mfma(T["t2"][(b * MT2 + mt) * 4 + rr], pq[b][nt][:, rr], rc[mt][nt])
-        for mt in range(MT2):
-            for nt in range(NT):
-                Rsum[mt][nt] = Rsum[mt][nt] + rc[mt][nt]  # the reduction over the waves, in wave order (through LDS on the device)
+                        rc[mt * NT + nt] = mfma(T["t2"][(b * MT2 + mt) * 4 + rr], pq[b][nt][:, rr], rc[mt * NT + nt])
+        part.append(rc)
+    # the reduction over the waves (through the LDS strips on the device): four tiles a round, each element in wave order
+    assert (MT2 * NT) % 4 == 0
+    Rflat = [None] * (MT2 * NT)
+    for q in range(MT2 * NT // 4):
+        for k in range(4 * q, 4 * q + 4):
+            acc = np.zeros((64, 4), dt)
+            for wv in range(NW):
+                acc = acc + part[wv][k]
+            Rflat[k] = acc
+    Rsum = [[Rflat[mt * NT + nt] for nt in range(NT)] for mt in range(MT2)]
     EF = [[None] * NT for _ in range(MT2)]
     for j in range(half):
         for p in range(nh):
@@ -280,11 +210,14 @@ def wide_apply(x, T):
 
 if __name__ == "__main__":
     from eeadv.hfs import hfs_matrices
-    rng = np.random.RandomState(2)
-    for (H, W, r) in [(288, 288, 18), (260, 40, 3), (33, 262, 5), (289, 291, 18), (272, 304, 20), (320, 320, 24)]:
-        x = rng.rand(H, W)
-        Ar, Ai, B1, B2 = hfs_matrices(H, W, r)
-        want = Ar @ x @ B1 + Ai @ x @ B2
-        got = wide_apply(x, wide_tables(H, W, r))
-        print("wide variant %dx%d r=%d: f64 err %.2e" % (H, W, r, np.abs(got - want).max()))
-        assert np.abs(got - want).max() < 1e-11
+    CASES = [("band", NARROW, 1, [(224, 224, 16), (64, 64, 8), (7, 9, 2), (96, 128, 12), (28, 28, 4)]),
+             ("wide", WIDE, 2, [(288, 288, 18), (260, 40, 3), (33, 262, 5), (289, 291, 18), (272, 304, 20), (320, 320, 24)])]
+    for label, cls, seed, shapes in CASES:
+        rng = np.random.RandomState(seed)
+        for (H, W, r) in shapes:
+            x = rng.rand(H, W)
+            Ar, Ai, B1, B2 = hfs_matrices(H, W, r)
+            want = Ar @ x @ B1 + Ai @ x @ B2
+            got = wide_apply(x, wide_tables(H, W, r, cls=cls))
+            print("%s variant %dx%d r=%d: f64 err %.2e" % (label, H, W, r, np.abs(got - want).max()))
+            assert np.abs(got - want).max() < 1e-11
