@@ -84,36 +84,19 @@ __device__ __forceinline__ void magnitude_group(const float *xs, const Weights &
 // =====================================================================================================
 template <int C, int TH, int TW, bool FUSED>
 __global__ __launch_bounds__(kBlock) void canny_fwd_kernel(CannyParams cp, Weights wt, CannyDirs cd) {
-    constexpr int FH = TH + 8, FW = TW + 8, PL = FH * FW, LX = TW / 4;
+    constexpr int FH = TH + 8, FW = TW + 8, PL = FH * FW;
     constexpr int MG_GX = (TW + 4 + 3) / 4, MG_ROWS = TH + 4;
     __shared__ __align__(16) float lds[(C + 3) * PL];
     __shared__ int dirs[16];
     const EdgeParams &p = cp.e;
     float *xs = lds, *magAs = lds + C * PL, *kdirs = magAs + PL, *t2s = kdirs + PL;
     const int H = p.H, W = p.W;
-    int n, i0, j0;
-    tile_origin(p, TH, TW, n, i0, j0);
-    const int oi = i0 - 4, oj = j0 - 4;
-    const bool vec = p.vec != 0;
-    const int lx = threadIdx.x % LX, ly = threadIdx.x / LX;
-    const int ti = i0 + ly, tjb = j0 + 4 * lx;
-    const bool live = (ly < TH) && (ti < H) && (tjb < W);
+    const Lane l = lane_of<TH, TW>(p);
+    const int n = l.n, i0 = l.i0, j0 = l.j0, ti = l.ti, tjb = l.tjb, oi = i0 - 4, oj = j0 - 4;
+    const bool vec = p.vec != 0, live = l.live;
 
     float4 xh[C];
-    if (FUSED && live) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const float *src = p.x_hfs + ((static_cast<size_t>(n) * C + c) * H + ti) * W + tjb;
-            if (vec) {
-                xh[c] = *reinterpret_cast<const float4 *>(src);
-            } else {
-                xh[c].x = src[0];
-                xh[c].y = (tjb + 1 < W) ? src[1] : 0.0f;
-                xh[c].z = (tjb + 2 < W) ? src[2] : 0.0f;
-                xh[c].w = (tjb + 3 < W) ? src[3] : 0.0f;
-            }
-        }
-    }
+    if (FUSED) load_px4<C, false, false>(p.x_hfs, nullptr, n, H, W, ti, tjb, live, vec, xh, nullptr);
     if (threadIdx.x < 8) {
         dirs[threadIdx.x] = cd.dr[threadIdx.x];
         dirs[8 + threadIdx.x] = cd.dc[threadIdx.x];
@@ -124,11 +107,8 @@ __global__ __launch_bounds__(kBlock) void canny_fwd_kernel(CannyParams cp, Weigh
 
     // ---- magnitude / direction on rows [i0-2, i0+TH+2) x cols [j0-2, j0+TW+2) ------------------------------------------
     for (int gidx = threadIdx.x; gidx < MG_ROWS * MG_GX; gidx += kBlock) {
-        const int r = gidx / MG_GX, g = gidx - r * MG_GX;
-        const int fr = r + 2, fc = 2 + 4 * g;
-        const int i = oi + fr, jb = oj + fc;
-        if (i >= 0 && i < H && jb < W && jb + 3 >= 0)
-            magnitude_group<C, FH, FW>(xs, wt, fr, fc, i, jb, H, W, p.alpha, nullptr, nullptr, magAs, kdirs);
+        const Group q = group_of<MG_GX, 2, 2>(gidx, oi, oj, H, W);
+        if (q.in) magnitude_group<C, FH, FW>(xs, wt, q.fr, q.fc, q.i, q.jb, H, W, p.alpha, nullptr, nullptr, magAs, kdirs);
     }
     __syncthreads();
 
@@ -181,38 +161,11 @@ __global__ __launch_bounds__(kBlock) void canny_fwd_kernel(CannyParams cp, Weigh
             e[k] = highb + ((acc > 1.0f && t2 == 0.5f) ? 1.0f : 0.0f);
         }
     }
-    const size_t pix = (static_cast<size_t>(n) * H + ti) * W + tjb;
-    if (p.edge) {
-        if (vec) {
-            *reinterpret_cast<float4 *>(p.edge + pix) = make_float4(e[0], e[1], e[2], e[3]);
-        } else {
-            for (int k = 0; k < 4 && tjb + k < W; ++k) p.edge[pix + k] = e[k];
-        }
-    }
-    if (FUSED) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const size_t o = ((static_cast<size_t>(n) * C + c) * H + ti) * W + tjb;
-            const float sv[4] = {xh[c].x + p.w * e[0], xh[c].y + p.w * e[1], xh[c].z + p.w * e[2], xh[c].w + p.w * e[3]};
-            if (vec) {
-                *reinterpret_cast<float4 *>(p.x_in + o) =
-                    make_float4(tclamp(sv[0], 0.0f, 1.0f), tclamp(sv[1], 0.0f, 1.0f), tclamp(sv[2], 0.0f, 1.0f), tclamp(sv[3], 0.0f, 1.0f));
-                if (p.gate) {
-                    uchar4 gt;
-                    gt.x = (sv[0] >= 0.0f && sv[0] <= 1.0f);
-                    gt.y = (sv[1] >= 0.0f && sv[1] <= 1.0f);
-                    gt.z = (sv[2] >= 0.0f && sv[2] <= 1.0f);
-                    gt.w = (sv[3] >= 0.0f && sv[3] <= 1.0f);
-                    *reinterpret_cast<uchar4 *>(p.gate + o) = gt;
-                }
-            } else {
-                for (int k = 0; k < 4 && tjb + k < W; ++k) {
-                    p.x_in[o + k] = tclamp(sv[k], 0.0f, 1.0f);
-                    if (p.gate) p.gate[o + k] = (sv[k] >= 0.0f && sv[k] <= 1.0f);
-                }
-            }
-        }
-    }
+    by_vec(vec, [&](auto v) {
+        constexpr bool VEC = decltype(v)::value;
+        if (p.edge) store_px4<VEC>(p.edge, plane_at(n, 1, 0, H, W, ti, tjb), tjb, W, e);
+        if (FUSED) store_combine<C, VEC>(p.x_in, p.gate, n, H, W, ti, tjb, xh, e, p.w);
+    });
 }
 
 // =====================================================================================================
@@ -221,7 +174,7 @@ __global__ __launch_bounds__(kBlock) void canny_fwd_kernel(CannyParams cp, Weigh
 template <int C, int TH, int TW, bool FUSED>
 __global__ __launch_bounds__(kBlock) void canny_bwd_kernel(CannyParams cp, Weights wt, CannyDirs cd) {
     constexpr int RH_ = 5, CH_ = 8;  // row halo 5, column halo 8 (keeps every frame row 16-B aligned)
-    constexpr int FH = TH + 2 * RH_, FW = TW + 2 * CH_, PL = FH * FW, LX = TW / 4;
+    constexpr int FH = TH + 2 * RH_, FW = TW + 2 * CH_, PL = FH * FW;
     constexpr int MG_GX = (TW + 8 + 3) / 4, MG_ROWS = TH + 6;  // magnitude region: rows [i0-3, i0+TH+3), cols [j0-4, j0+TW+4)
     constexpr int NA = C > 3 ? C : 3;
     __shared__ __align__(16) float lds[(NA + 5) * PL];
@@ -231,39 +184,13 @@ __global__ __launch_bounds__(kBlock) void canny_bwd_kernel(CannyParams cp, Weigh
     float *us = lds + NA * PL, *gx1s = us + PL, *gy1s = gx1s + PL, *magAs = gy1s + PL, *kdirs = magAs + PL;
     float *ggx = xs, *ggy = xs + PL, *gb = xs + 2 * PL;
     const int H = p.H, W = p.W;
-    int n, i0, j0;
-    tile_origin(p, TH, TW, n, i0, j0);
-    const int oi = i0 - RH_, oj = j0 - CH_;
-    const bool vec = p.vec != 0;
-    const int lx = threadIdx.x % LX, ly = threadIdx.x / LX;
-    const int ti = i0 + ly, tjb = j0 + 4 * lx;
-    const bool live = (ly < TH) && (ti < H) && (tjb < W);
+    const Lane l = lane_of<TH, TW>(p);
+    const int n = l.n, i0 = l.i0, j0 = l.j0, ti = l.ti, tjb = l.tjb, oi = i0 - RH_, oj = j0 - CH_;
+    const bool vec = p.vec != 0, live = l.live;
 
     float4 gin[FUSED ? C : 1];
     uchar4 gtv[FUSED ? C : 1];
-    if (FUSED && vec) {  // unconditional on clamped (always valid) addresses: the loads batch with the frame's; dead lanes never store
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const size_t o = ((static_cast<size_t>(n) * C + c) * H + (ti < H ? ti : H - 1)) * W + clamp_col4(tjb, W);
-            gin[c] = *reinterpret_cast<const float4 *>(p.g_in + o);
-            gtv[c] = *reinterpret_cast<const uchar4 *>(p.gate_in + o);
-        }
-    } else if (FUSED && live) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const size_t o = ((static_cast<size_t>(n) * C + c) * H + ti) * W + tjb;
-            {
-                float gv[4] = {0, 0, 0, 0};
-                unsigned char tv[4] = {0, 0, 0, 0};
-                for (int k = 0; k < 4 && tjb + k < W; ++k) {
-                    gv[k] = p.g_in[o + k];
-                    tv[k] = p.gate_in[o + k];
-                }
-                gin[c] = make_float4(gv[0], gv[1], gv[2], gv[3]);
-                gtv[c] = make_uchar4(tv[0], tv[1], tv[2], tv[3]);
-            }
-        }
-    }
+    if (FUSED) load_px4<C, true>(p.g_in, p.gate_in, n, H, W, ti, tjb, live, vec, gin, gtv);
     if (threadIdx.x < 8) {
         dirs[threadIdx.x] = cd.dr[threadIdx.x];
         dirs[8 + threadIdx.x] = cd.dc[threadIdx.x];
@@ -278,11 +205,8 @@ __global__ __launch_bounds__(kBlock) void canny_bwd_kernel(CannyParams cp, Weigh
 
     // ---- magnitude maps on rows [i0-3, i0+TH+3) x cols [j0-4, j0+TW+4) ---------------------------------------------------
     for (int gidx = threadIdx.x; gidx < MG_ROWS * MG_GX; gidx += kBlock) {
-        const int r = gidx / MG_GX, g = gidx - r * MG_GX;
-        const int fr = r + 2, fc = 4 + 4 * g;
-        const int i = oi + fr, jb = oj + fc;
-        if (i >= 0 && i < H && jb < W && jb + 3 >= 0)
-            magnitude_group<C, FH, FW>(xs, wt, fr, fc, i, jb, H, W, p.alpha, gx1s, gy1s, magAs, kdirs);
+        const Group q = group_of<MG_GX, 2, 4>(gidx, oi, oj, H, W);
+        if (q.in) magnitude_group<C, FH, FW>(xs, wt, q.fr, q.fc, q.i, q.jb, H, W, p.alpha, gx1s, gy1s, magAs, kdirs);
     }
     __syncthreads();  // the input frame is dead from here on: its planes become ggx / ggy / gb
     for (int idx = threadIdx.x; idx < 3 * PL / 4; idx += kBlock) reinterpret_cast<float4 *>(xs)[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -298,8 +222,7 @@ __global__ __launch_bounds__(kBlock) void canny_bwd_kernel(CannyParams cp, Weigh
                 const int fr = i - oi, fc = j - oj, o = fr * FW + fc;
                 const bool removed = nms_removed<FW>(magAs, kdirs, dirs, fr, fc);
                 const float gx1 = gx1s[o], gy1 = gy1s[o];
-                const float s2 = gx1 * gx1 + gy1 * gy1;
-                const float mag = sqrtf(s2);
+                const float mag = sqrtf(gx1 * gx1 + gy1 * gy1);
                 const float t = removed ? 0.0f : magAs[o];
                 float gm;
                 if (cp.thin_grad) {                                   // CannyFilter_BPDA: us already holds d loss / d thin
@@ -311,10 +234,7 @@ __global__ __launch_bounds__(kBlock) void canny_bwd_kernel(CannyParams cp, Weigh
                     if (removed) gm = 0.0f;                           // thin_edges[to_remove] = 0.0, core.py:290
                     if (mag < p.alpha) gm = 0.0f;                     // where() backward core.py:264
                 }
-                const float rs = 1.0f / sqrtf(s2);
-                const float gs = gm * (0.5f * rs);
-                ggx[o] = (gs * (2.0f * gx1)) / static_cast<float>(C);
-                ggy[o] = (gs * (2.0f * gy1)) / static_cast<float>(C);
+                mag_grad<C>(gx1, gy1, gm, ggx[o], ggy[o]);
             }
         }
     }
@@ -323,81 +243,11 @@ __global__ __launch_bounds__(kBlock) void canny_bwd_kernel(CannyParams cp, Weigh
     float o4[4];
     adjoint_tail<TH, TW, FW>(ggx, ggy, gb, wt, H, W, i0, j0, oi, oj, live, ti, tjb, o4);
     if (!live) return;
-    const size_t pix = (static_cast<size_t>(n) * H + ti) * W + tjb;
-    if (vec) {
-        *reinterpret_cast<float4 *>(p.g_img + pix) = make_float4(o4[0], o4[1], o4[2], o4[3]);
-    } else {
-        for (int k = 0; k < 4 && tjb + k < W; ++k) p.g_img[pix + k] = o4[k];
-    }
-    if (FUSED) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const size_t o = ((static_cast<size_t>(n) * C + c) * H + ti) * W + tjb;
-            const float4 g = gin[c];
-            const uchar4 gt = gtv[c];
-            const float r4[4] = {gt.x ? g.x : 0.0f, gt.y ? g.y : 0.0f, gt.z ? g.z : 0.0f, gt.w ? g.w : 0.0f};
-            if (vec) {
-                *reinterpret_cast<float4 *>(p.g_hfs + o) = make_float4(r4[0], r4[1], r4[2], r4[3]);
-            } else {
-                for (int k = 0; k < 4 && tjb + k < W; ++k) p.g_hfs[o + k] = r4[k];
-            }
-        }
-    }
-}
-
-// ---- host side --------------------------------------------------------------------------------------
-constexpr int kFwdTH64 = 11, kFwdTH32 = 24, kBwdTH64 = 8, kBwdTH32 = 16;
-
-int check_dims(int B, int C, int H, int W) {
-    if (B < 0 || C < 1 || H < 1 || W < 1) return EE_ERR_SHAPE;
-    if (C > 4) return EE_ERR_UNSUPPORTED;
-    if (static_cast<int64_t>(B) * ((H + 7) / 8) * ((W + 31) / 32) > 0x7fffffffLL) return EE_ERR_SHAPE;
-    return EE_OK;
-}
-
-template <int C, bool FUSED, bool BWD>
-void launch_c(CannyParams &cp, const Weights &wt, const CannyDirs &cd, int B, hipStream_t s) {
-    EdgeParams &p = cp.e;
-    const bool wide = p.W > 32;
-    const int tw = wide ? 64 : 32;
-    const int th = wide ? (BWD ? kBwdTH64 : kFwdTH64) : (BWD ? kBwdTH32 : kFwdTH32);
-    p.tiles_x = (p.W + tw - 1) / tw;
-    p.tiles_y = (p.H + th - 1) / th;
-    const unsigned grid = static_cast<unsigned>(static_cast<int64_t>(B) * p.tiles_x * p.tiles_y);
-    if (BWD) {
-        if (wide)
-            EE_LAUNCH((canny_bwd_kernel<C, kBwdTH64, 64, FUSED>), dim3(grid), dim3(kBlock), 0, s, cp, wt, cd);
-        else
-            EE_LAUNCH((canny_bwd_kernel<C, kBwdTH32, 32, FUSED>), dim3(grid), dim3(kBlock), 0, s, cp, wt, cd);
-    } else {
-        if (wide)
-            EE_LAUNCH((canny_fwd_kernel<C, kFwdTH64, 64, FUSED>), dim3(grid), dim3(kBlock), 0, s, cp, wt, cd);
-        else
-            EE_LAUNCH((canny_fwd_kernel<C, kFwdTH32, 32, FUSED>), dim3(grid), dim3(kBlock), 0, s, cp, wt, cd);
-    }
-}
-
-template <bool FUSED, bool BWD>
-int launch(CannyParams cp, const float *w27, const int *dirs16, int B, int C, hipStream_t s) {
-    Weights wt;
-    for (int k = 0; k < 9; ++k) {
-        wt.g[k] = w27[k];
-        wt.sx[k] = w27[9 + k];
-        wt.sy[k] = w27[18 + k];
-    }
-    CannyDirs cd;
-    for (int k = 0; k < 8; ++k) {
-        cd.dr[k] = dirs16[2 * k];
-        cd.dc[k] = dirs16[2 * k + 1];
-        if (cd.dr[k] < -1 || cd.dr[k] > 1 || cd.dc[k] < -1 || cd.dc[k] > 1) return EE_ERR_SHAPE;  // 3x3 neighbourhood only
-    }
-    switch (C) {
-        case 1: launch_c<1, FUSED, BWD>(cp, wt, cd, B, s); break;
-        case 2: launch_c<2, FUSED, BWD>(cp, wt, cd, B, s); break;
-        case 3: launch_c<3, FUSED, BWD>(cp, wt, cd, B, s); break;
-        default: launch_c<4, FUSED, BWD>(cp, wt, cd, B, s); break;
-    }
-    return launch_status();
+    by_vec(vec, [&](auto v) {
+        constexpr bool VEC = decltype(v)::value;
+        store_px4<VEC>(p.g_img, plane_at(n, 1, 0, H, W, ti, tjb), tjb, W, o4);
+        if (FUSED) store_gated<C, VEC>(p.g_hfs, n, H, W, ti, tjb, gin, gtv);
+    });
 }
 
 // CannyFilter_BPDA backward, threshold / hysteresis part (core.py:482-504): d loss / d thin from u = d loss / d edge,
@@ -450,38 +300,69 @@ __global__ __launch_bounds__(256) void bpda_threshold_bwd_kernel(const float *__
     g_thin[idx] = g_low + g_high;
 }
 
-inline bool al16(const void *q) { return !q || aligned16(q); }
-inline bool al4(const void *q) { return !q || (reinterpret_cast<uintptr_t>(q) & 3u) == 0; }
+// ---- host side --------------------------------------------------------------------------------------
+constexpr int kFwdTH64 = 11, kFwdTH32 = 24, kBwdTH64 = 8, kBwdTH32 = 16;
+
+template <int C, bool FUSED, bool BWD>
+void launch_c(const CannyParams &cp, const Weights &wt, const CannyDirs &cd, const TilePlan &l, hipStream_t s) {
+    const dim3 grid(l.grid), block(kBlock);
+    if (BWD) {
+        if (l.tw == 64)
+            EE_LAUNCH((canny_bwd_kernel<C, kBwdTH64, 64, FUSED>), grid, block, 0, s, cp, wt, cd);
+        else
+            EE_LAUNCH((canny_bwd_kernel<C, kBwdTH32, 32, FUSED>), grid, block, 0, s, cp, wt, cd);
+    } else {
+        if (l.tw == 64)
+            EE_LAUNCH((canny_fwd_kernel<C, kFwdTH64, 64, FUSED>), grid, block, 0, s, cp, wt, cd);
+        else
+            EE_LAUNCH((canny_fwd_kernel<C, kFwdTH32, 32, FUSED>), grid, block, 0, s, cp, wt, cd);
+    }
+}
+
+// what every entry point does once its pointers are in cp: the opening checks, the remaining fields, the direction table
+template <bool FUSED, bool BWD>
+int launch(CannyParams cp, bool missing, int B, int C, int H, int W, const float *weights27, const int *dirs16, float alpha, float low,
+           float high, float w, void *stream) {
+    int rc;
+    if (ends_early(rc, B, C, H, W, kBwdTH64, missing || !weights27 || !dirs16)) return rc;
+    finish_params(cp.e, H, W, alpha, high, w);
+    cp.low = low;
+    const Weights wt = load_weights(weights27);
+    CannyDirs cd;
+    for (int k = 0; k < 8; ++k) {
+        cd.dr[k] = dirs16[2 * k];
+        cd.dc[k] = dirs16[2 * k + 1];
+        if (cd.dr[k] < -1 || cd.dr[k] > 1 || cd.dc[k] < -1 || cd.dc[k] > 1) return EE_ERR_SHAPE;  // 3x3 neighbourhood only
+    }
+    const TilePlan l = tile_plan(cp.e, B, BWD ? kBwdTH64 : kFwdTH64, BWD ? kBwdTH32 : kFwdTH32);
+    switch (C) {
+        case 1: launch_c<1, FUSED, BWD>(cp, wt, cd, l, as_stream(stream)); break;
+        case 2: launch_c<2, FUSED, BWD>(cp, wt, cd, l, as_stream(stream)); break;
+        case 3: launch_c<3, FUSED, BWD>(cp, wt, cd, l, as_stream(stream)); break;
+        default: launch_c<4, FUSED, BWD>(cp, wt, cd, l, as_stream(stream)); break;
+    }
+    return launch_status();
+}
 
 }  // namespace
 
 EE_API int ee_canny_fwd_f32(const float *x, const float *x_hfs, int B, int C, int H, int W, const float *weights27, const int *dirs16,
                             float alpha, float low, float high, float w, float *edge, float *x_in, uint8_t *gate, void *stream) {
-    if (int rc = check_dims(B, C, H, W)) return rc;
-    if (B == 0) return EE_OK;
-    if (!x || !weights27 || !dirs16 || (!edge && !x_in)) return EE_ERR_NULL;
-    if (x_in && !x_hfs) return EE_ERR_NULL;
     CannyParams cp{};
     cp.e.x = x;
     cp.e.x_hfs = x_hfs;
     cp.e.edge = edge;
     cp.e.x_in = x_in;
     cp.e.gate = gate;
-    cp.e.H = H; cp.e.W = W;
-    cp.e.alpha = alpha; cp.e.high = high; cp.e.w = w;
-    cp.low = low;
-    cp.e.vec = (W % 4 == 0) && al16(x) && al16(x_hfs) && al16(edge) && al16(x_in) && al4(gate);
-    return x_in ? launch<true, false>(cp, weights27, dirs16, B, C, as_stream(stream))
-                : launch<false, false>(cp, weights27, dirs16, B, C, as_stream(stream));
+    const bool missing = !x || (!edge && !x_in) || (x_in && !x_hfs);
+    return x_in ? launch<true, false>(cp, missing, B, C, H, W, weights27, dirs16, alpha, low, high, w, stream)
+                : launch<false, false>(cp, missing, B, C, H, W, weights27, dirs16, alpha, low, high, w, stream);
 }
 
 EE_API int ee_canny_bwd_f32(const float *x, const float *u, const float *g_in, const uint8_t *gate, int B, int C, int H, int W,
                             const float *weights27, const int *dirs16, float alpha, float low, float high, float w, float *g_img,
                             float *g_hfs, void *stream) {
-    if (int rc = check_dims(B, C, H, W)) return rc;
-    if (B == 0) return EE_OK;
     const bool fused = g_in != nullptr;
-    if (!x || !weights27 || !dirs16 || !g_img || (!fused && !u) || (fused && (!gate || !g_hfs))) return EE_ERR_NULL;
     CannyParams cp{};
     cp.e.x = x;
     cp.e.u = u;
@@ -489,52 +370,37 @@ EE_API int ee_canny_bwd_f32(const float *x, const float *u, const float *g_in, c
     cp.e.gate_in = gate;
     cp.e.g_img = g_img;
     cp.e.g_hfs = g_hfs;
-    cp.e.H = H; cp.e.W = W;
-    cp.e.alpha = alpha; cp.e.high = high; cp.e.w = w;
-    cp.low = low;
-    cp.e.vec = (W % 4 == 0) && al16(x) && al16(u) && al16(g_in) && al16(g_img) && al16(g_hfs) && al4(gate);
-    return fused ? launch<true, true>(cp, weights27, dirs16, B, C, as_stream(stream))
-                 : launch<false, true>(cp, weights27, dirs16, B, C, as_stream(stream));
+    const bool missing = !x || !g_img || (!fused && !u) || (fused && (!gate || !g_hfs));
+    return fused ? launch<true, true>(cp, missing, B, C, H, W, weights27, dirs16, alpha, low, high, w, stream)
+                 : launch<false, true>(cp, missing, B, C, H, W, weights27, dirs16, alpha, low, high, w, stream);
 }
 
 // CannyFilter_BPDA (utils/core.py:386-505): the forward is the CannyFilter pipeline without the alpha mask; thin / t2 are kept
 // for the backward.  NaN pixels (NaN input only) are not reproduced: To_compare keeps them, the sign-based forward does not.
 EE_API int ee_canny_bpda_fwd_f32(const float *x, int B, int C, int H, int W, const float *weights27, const int *dirs16, float low, float high,
                                  float *edge, float *thin, float *t2, void *stream) {
-    if (int rc = check_dims(B, C, H, W)) return rc;
-    if (B == 0) return EE_OK;
-    if (!x || !weights27 || !dirs16 || !edge || !thin || !t2) return EE_ERR_NULL;
     CannyParams cp{};
     cp.e.x = x;
     cp.e.edge = edge;
-    cp.e.H = H; cp.e.W = W;
-    cp.e.alpha = 0.0f; cp.e.high = high; cp.e.w = 0.0f;
-    cp.low = low;
     cp.thin_out = thin;
     cp.t2_out = t2;
-    cp.e.vec = (W % 4 == 0) && al16(x) && al16(edge);
-    return launch<false, false>(cp, weights27, dirs16, B, C, as_stream(stream));
+    return launch<false, false>(cp, !x || !edge || !thin || !t2, B, C, H, W, weights27, dirs16, 0.0f, low, high, 0.0f, stream);
 }
 
 EE_API int ee_canny_bpda_bwd_f32(const float *x, const float *u, const float *thin, const float *t2, int B, int C, int H, int W,
                                  const float *weights27, const int *dirs16, float low, float high, float *g_thin, float *g_img,
                                  void *stream) {
-    if (int rc = check_dims(B, C, H, W)) return rc;
-    if (B == 0) return EE_OK;
-    if (!x || !u || !thin || !t2 || !weights27 || !dirs16 || !g_thin || !g_img) return EE_ERR_NULL;
+    int rc;
+    if (ends_early(rc, B, C, H, W, kBwdTH64, !x || !u || !thin || !t2 || !weights27 || !dirs16 || !g_thin || !g_img)) return rc;
     const int64_t total = static_cast<int64_t>(B) * H * W;
     if ((total + 255) / 256 > 0x7fffffffLL) return EE_ERR_SHAPE;
     EE_LAUNCH(bpda_threshold_bwd_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, as_stream(stream), u, thin, t2, g_thin, H,
               W, low, high, total);
-    if (int rc = launch_status()) return rc;
+    if ((rc = launch_status())) return rc;
     CannyParams cp{};
     cp.e.x = x;
     cp.e.u = g_thin;
     cp.e.g_img = g_img;
-    cp.e.H = H; cp.e.W = W;
-    cp.e.alpha = 0.0f; cp.e.high = high; cp.e.w = 0.0f;
-    cp.low = low;
     cp.thin_grad = 1;
-    cp.e.vec = (W % 4 == 0) && al16(x) && al16(g_thin) && al16(g_img);
-    return launch<false, true>(cp, weights27, dirs16, B, C, as_stream(stream));
+    return launch<false, true>(cp, false, B, C, H, W, weights27, dirs16, 0.0f, low, high, 0.0f, stream);
 }

@@ -437,6 +437,7 @@ __global__ __launch_bounds__((kSW + C) * kWave) void chain_bwd_kernel(BwdParams 
                 float ox[4], oy[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
+                    // mirrors step125_mask + mag_grad of ee_stencil.hpp (calling them moves instructions in two instantiations)
                     const float gx1 = gxa[k], gy1 = gya[k];
                     const float s2 = gx1 * gx1 + gy1 * gy1;
                     const float mag = sqrtf(s2);
@@ -571,16 +572,6 @@ __global__ __launch_bounds__((kSW + C) * kWave) void chain_bwd_kernel(BwdParams 
     }
 }
 
-Weights load_weights(const float *w27) {
-    Weights wt;
-    for (int k = 0; k < 9; ++k) {
-        wt.g[k] = w27[k];
-        wt.sx[k] = w27[9 + k];
-        wt.sy[k] = w27[18 + k];
-    }
-    return wt;
-}
-
 template <int H, int W>
 size_t fwd_lds_bytes(int C) {
     using D = Dims<H, W>;
@@ -637,8 +628,6 @@ Shape shape_of(int C, int H, int W) {
     if (C == 1 && H == 64 && W == 64) return S_1_64;
     return S_NONE;
 }
-
-inline bool al16(const void *q) { return !q || aligned16(q); }
 
 }  // namespace
 

@@ -4,6 +4,8 @@
 #pragma once
 #include <math.h>
 
+#include <type_traits>
+
 #include "ee_common.hpp"
 
 namespace ee {
@@ -45,8 +47,26 @@ __device__ __forceinline__ void edge_from_sums(float ax, float ay, float alpha, 
     e = (mag_a > high) ? 1.0f : ((mag_a <= high) ? 0.0f : mag_a);
 }
 
-// frame[c][r][s] = src(c, clamp(i0 - hr + r), clamp(j0 - COLH + s)),  r < FH, s < FW (FW % 4 == 0); planes of `src`
-// are H*W apart.  16-B loads wherever a whole float4 lies inside the image.
+// backward of that decision: the gradient gm of the magnitude at a pixel with channel-mean responses (gx1, gy1), masked
+// as the step125 filter masks it (ee_chain.hip and both backwards of ee_edge.hip; s2 / mag / mag_a as in edge_from_sums)
+__device__ __forceinline__ float step125_mask(float gm, float gx1, float gy1, float alpha, float high) {
+    const float mag = sqrtf(gx1 * gx1 + gy1 * gy1);
+    const float mag_a = (mag < alpha) ? 0.0f : mag;
+    if (mag_a <= high) gm = 0.0f;  // To_compare.backward core.py:356
+    if (mag_a > 1.001f) gm = 0.0f;  // core.py:357
+    if (mag < alpha) gm = 0.0f;     // where() backward core.py:575
+    return gm;
+}
+
+// the magnitude-stage gradient, the one place it is written: d loss / d (channel-summed gx, gy) from d loss / d mag
+template <int C>
+__device__ __forceinline__ void mag_grad(float gx1, float gy1, float gm, float &ggx, float &ggy) {
+    const float rs = 1.0f / sqrtf(gx1 * gx1 + gy1 * gy1);  // pow(s2, -0.5): 0 -> inf
+    const float gs = gm * (0.5f * rs);                     // 0*inf = NaN kept
+    ggx = (gs * (2.0f * gx1)) / static_cast<float>(C);
+    ggy = (gs * (2.0f * gy1)) / static_cast<float>(C);
+}
+
 // replicate-padded float4 at columns gj .. gj+3 of a row whose width is a multiple of 4 (gj a multiple of 4): ONE aligned,
 // always in-bounds 16-B load plus selects - a whole float4 left of the image is row[0] four times, right of it row[W-1]
 __device__ __forceinline__ int clamp_col4(int gj, int W) { return gj < 0 ? 0 : (gj > W - 4 ? W - 4 : gj); }
@@ -56,6 +76,99 @@ __device__ __forceinline__ float4 replicate4(float4 v, int gj, int W) {
     return v;
 }
 
+// ---- the lane's own four pixels (i, jb .. jb+3) of the planes [n, c], c < C --------------------------------------------------
+__device__ __forceinline__ size_t plane_at(int n, int C, int c, int H, int W, int i, int j) {
+    return ((static_cast<size_t>(n) * C + c) * H + i) * W + j;
+}
+
+// read, with the gate bytes alongside when GATE.  vec: unconditional loads on clamped (always valid) addresses -
+// no branch, so they batch with the frame's loads issued next to them; dead lanes never store.  Otherwise live lanes read
+// what lies inside the row and the rest is 0.  !ALL_LANES: the 16-B loads too are for live lanes only (for them the clamped
+// address is their own) - canny_fwd_kernel, whose 11-row tiles leave whole dead rows that would read x_hfs for nothing.
+template <int C, bool GATE, bool ALL_LANES = true>
+__device__ __forceinline__ void load_px4(const float *__restrict__ src, const uint8_t *__restrict__ gate, int n, int H, int W, int i, int jb,
+                                         bool live, bool vec, float4 *v, uchar4 *t) {
+    if (vec && (ALL_LANES || live)) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const size_t o = plane_at(n, C, c, H, W, i < H ? i : H - 1, clamp_col4(jb, W));
+            v[c] = *reinterpret_cast<const float4 *>(src + o);
+            if constexpr (GATE) t[c] = *reinterpret_cast<const uchar4 *>(gate + o);
+        }
+    } else if (live) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const size_t o = plane_at(n, C, c, H, W, i, jb);
+            float gv[4] = {0, 0, 0, 0};
+            unsigned char tv[4] = {0, 0, 0, 0};
+            for (int k = 0; k < 4 && jb + k < W; ++k) {
+                gv[k] = src[o + k];
+                if constexpr (GATE) tv[k] = gate[o + k];
+            }
+            v[c] = make_float4(gv[0], gv[1], gv[2], gv[3]);
+            if constexpr (GATE) t[c] = make_uchar4(tv[0], tv[1], tv[2], tv[3]);
+        }
+    }
+}
+
+// write (live lanes only): VEC one 16-B / 4-B store, else the pixels inside the row one by one.  by_vec runs a kernel's stores
+// as f(true_type) or f(false_type): ONE test of `vec` in front of all of them, so the stores of the taken side issue back to back
+template <class F>
+__device__ __forceinline__ void by_vec(bool vec, F f) {
+    if (vec) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <bool VEC>
+__device__ __forceinline__ void store_px4(float *dst, size_t o, int jb, int W, const float (&v)[4]) {
+    if (VEC) {
+        *reinterpret_cast<float4 *>(dst + o) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int k = 0; k < 4 && jb + k < W; ++k) dst[o + k] = v[k];
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ void store_px4(uint8_t *dst, size_t o, int jb, int W, const uint8_t (&v)[4]) {
+    if (VEC) {
+        *reinterpret_cast<uchar4 *>(dst + o) = make_uchar4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (int k = 0; k < 4 && jb + k < W; ++k) dst[o + k] = v[k];
+    }
+}
+
+// the front-end combine: s = x_hfs + w * e, x_in = clamp(s, 0, 1), gate (optional) = 0 <= s <= 1
+template <int C, bool VEC>
+__device__ __forceinline__ void store_combine(float *x_in, uint8_t *gate, int n, int H, int W, int i, int jb, const float4 *xh,
+                                              const float (&e)[4], float w) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float s[4] = {xh[c].x + w * e[0], xh[c].y + w * e[1], xh[c].z + w * e[2], xh[c].w + w * e[3]};
+        float xi[4];
+        uint8_t gt[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            xi[k] = tclamp(s[k], 0.0f, 1.0f);
+            gt[k] = (s[k] >= 0.0f && s[k] <= 1.0f);
+        }
+        const size_t o = plane_at(n, C, c, H, W, i, jb);
+        store_px4<VEC>(x_in, o, jb, W, xi);
+        if (gate) store_px4<VEC>(gate, o, jb, W, gt);
+    }
+}
+
+// the gated pass-through of the front-end backward: g_hfs = gate ? g_in : 0
+template <int C, bool VEC>
+__device__ __forceinline__ void store_gated(float *g_hfs, int n, int H, int W, int i, int jb, const float4 *gin, const uchar4 *gtv) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float4 g = gin[c];
+        const uchar4 gt = gtv[c];
+        const float r4[4] = {gt.x ? g.x : 0.0f, gt.y ? g.y : 0.0f, gt.z ? g.z : 0.0f, gt.w ? g.w : 0.0f};
+        store_px4<VEC>(g_hfs, plane_at(n, C, c, H, W, i, jb), jb, W, r4);
+    }
+}
+
+// frame[c][r][s] = src(c, clamp(i0 - hr + r), clamp(j0 - COLH + s)),  r < FH, s < FW (FW % 4 == 0); planes of `src`
+// are H*W apart.  16-B loads wherever a whole float4 lies inside the image.
 template <int FH, int FW, int COLH = kColHalo, int PLANES = 0>
 __device__ __forceinline__ void load_frame(float *frame, const float *__restrict__ src, int planes, int H, int W, int i0, int j0,
                                            int hr, bool vec) {
@@ -244,6 +357,39 @@ __device__ __forceinline__ void tile_origin(const EdgeParams &p, int TH, int TW,
     j0 = tx * TW;
 }
 
+// this workgroup's tile of image n, and this lane's four pixels (ti, tjb .. tjb+3) of it
+struct Lane {
+    int n, i0, j0, ti, tjb;
+    bool live;
+};
+template <int TH, int TW>
+__device__ __forceinline__ Lane lane_of(const EdgeParams &p) {
+    Lane l;
+    tile_origin(p, TH, TW, l.n, l.i0, l.j0);
+    const int lx = threadIdx.x % (TW / 4), ly = threadIdx.x / (TW / 4);
+    l.ti = l.i0 + ly;
+    l.tjb = l.j0 + 4 * lx;
+    l.live = (ly < TH) && (l.ti < p.H) && (l.tjb < p.W);
+    return l;
+}
+
+// 4-pixel group number gidx (GX groups to a row) of a halo region that starts at frame (FR0, FC0): frame and image coordinates of
+// its first pixel, and whether any of it can lie inside the image (row inside, some column inside)
+struct Group {
+    int fr, fc, i, jb;
+    bool in;
+};
+template <int GX, int FR0, int FC0>
+__device__ __forceinline__ Group group_of(int gidx, int oi, int oj, int H, int W) {
+    const int r = gidx / GX;
+    Group q;
+    q.fr = FR0 + r;
+    q.fc = FC0 + 4 * (gidx - r * GX);
+    q.i = oi + q.fr;
+    q.jb = oj + q.fc;
+    q.in = q.i >= 0 && q.i < H && q.jb < W && q.jb + 3 >= 0;
+    return q;
+}
 
 // Transposed 3x3 correlation, register-blocked.  cell[q] += fmaf-chain over (di, dj) row-major of
 // w[di][dj] * src(P - di, Q0 + q - dj), q < 6, where src(i, j) is the plane value at IMAGE pixel (i, j) read from a frame
@@ -333,6 +479,63 @@ __device__ __forceinline__ void adjoint_tail(const float *ggx, const float *ggy,
         if (need) cells_row<FW>(gb, wt.g, ti + a, tjb, oi, oj, cells[a]);
     }
     fold4(cells, ti, tjb, H, W, o4);
+}
+
+// ---- host side of ee_edge.hip and ee_canny.hip ---------------------------------------------------------------------------
+// min_tile_rows: the lowest tile of the file's kernels, which bounds its largest grid
+inline int check_dims(int B, int C, int H, int W, int min_tile_rows) {
+    if (B < 0 || C < 1 || H < 1 || W < 1) return EE_ERR_SHAPE;
+    if (C > 4) return EE_ERR_UNSUPPORTED;
+    if (static_cast<int64_t>(B) * ((H + min_tile_rows - 1) / min_tile_rows) * ((W + 31) / 32) > 0x7fffffffLL) return EE_ERR_SHAPE;
+    return EE_OK;
+}
+
+// the checks every entry point opens with, in the ABI's order: the shape, the empty batch (EE_OK, nothing to do), the
+// pointers it needs.  True when the call ends here, with its status in rc.
+inline bool ends_early(int &rc, int B, int C, int H, int W, int min_tile_rows, bool missing) {
+    rc = check_dims(B, C, H, W, min_tile_rows);
+    if (rc == EE_OK && B > 0 && missing) rc = EE_ERR_NULL;
+    return rc != EE_OK || B == 0;
+}
+
+inline Weights load_weights(const float *w27) {
+    Weights wt;
+    for (int k = 0; k < 9; ++k) {
+        wt.g[k] = w27[k];
+        wt.sx[k] = w27[9 + k];
+        wt.sy[k] = w27[18 + k];
+    }
+    return wt;
+}
+
+// p with everything but the pointers filled in.  vec: 16-B accesses need W % 4 == 0 and every plane the call was given on
+// a 16-B boundary (the gates, one byte a pixel, on 4 B); a pointer that is not given does not count.  Planes that a kernel only
+// ever writes one float at a time (CannyParams::thin_out / t2_out) are not in EdgeParams and must stay out of this test
+inline bool al16(const void *q) { return !q || aligned16(q); }
+inline bool al4(const void *q) { return !q || aligned4(q); }
+inline void finish_params(EdgeParams &p, int H, int W, float alpha, float high, float w) {
+    p.H = H;
+    p.W = W;
+    p.alpha = alpha;
+    p.high = high;
+    p.w = w;
+    p.vec = (W % 4 == 0) && al16(p.x) && al16(p.x_hfs) && al16(p.u) && al16(p.g_in) && al4(p.gate_in) && al16(p.edge) && al16(p.mag) &&
+            al16(p.x_in) && al4(p.gate) && al16(p.g_hfs) && al16(p.g_img) && al16(p.gx_out) && al16(p.gy_out) && al16(p.gx_in) && al16(p.gy_in);
+}
+
+// th x tw tiles (tw = 64 when W > 32, else 32) over B images: sets p's tile counts
+struct TilePlan {
+    int th, tw;
+    unsigned grid;
+};
+inline TilePlan tile_plan(EdgeParams &p, int B, int th64, int th32) {
+    TilePlan l;
+    l.tw = (p.W > 32) ? 64 : 32;
+    l.th = (p.W > 32) ? th64 : th32;
+    p.tiles_x = (p.W + l.tw - 1) / l.tw;
+    p.tiles_y = (p.H + l.th - 1) / l.th;
+    l.grid = static_cast<unsigned>(static_cast<int64_t>(B) * p.tiles_x * p.tiles_y);
+    return l;
 }
 
 }  // namespace ee

@@ -26,7 +26,7 @@ def _match(pat, name):
 
 FAMILIES = {  # bench.py family -> substring of the kernel symbol (every template instance of the bench shape)
     "ee_chain_fwd": "chain_fwd_kernel", "ee_chain_bwd": "chain_bwd_kernel", "ee_frontend_fwd": "edge_fwd_kernel",
-    "ee_frontend_bwd": "edge_bwd_saved_kernel", "ee_hfs": "hfs_*kernel<0", "ee_hfs_square_fwd": "hfs_*kernel<1", "ee_hfs_square_bwd": "hfs_*kernel<2",
+    "ee_frontend_bwd": "edge_bwd_kernel<*true, true>", "ee_hfs": "hfs_*kernel<0", "ee_hfs_square_fwd": "hfs_*kernel<1", "ee_hfs_square_bwd": "hfs_*kernel<2",
     "ee_pgd_step": "map3_kernel*PgdStepOp", "ee_pgd_step_bcast": "pgd_step_bcast_kernel", "ee_square_draw": "square_draw_kernel",
     "ee_wino3x3": "wino3x3_*PLAIN", "ee_wino3x3_fused": "wino3x3_*FUSED", "ee_conv3x3s2_small_fwd": "conv3s2_fwd_mfma_kernel", "ee_conv3x3s2_small_bwd_data": "conv3s2_bwd_mfma_kernel", "ee_ce": "ce_kernel",
 }

@@ -45,5 +45,5 @@ px, C = B * 224 * 224, 3
 print("front end of one PGD iteration at %d x 3 x 224 x 224: %.1f us per iteration (eager launches, torch events)" % (B, 1e3 * a.elapsed_time(b) / n))
 print("algorithmic bytes per launch (SURVEY 8(d)):")
 for name, nbytes in (("square_draw_kernel", 4 * B * C * 224), ("hfs_band_kernel<1 (Add_Square on load)", 8 * C * px), ("edge_fwd_kernel (+ combine, gate, saved responses)", (12 * C + C + 8) * px),
-                     ("edge_bwd_saved_kernel", (9 * C + 12) * px), ("hfs_band_kernel<2 (d Add_Square on store)", 12 * C * px), ("pgd_step_bcast_kernel", (16 * C + 4) * px)):
+                     ("edge_bwd_kernel<C, TH, TW, true, true> (saved)", (9 * C + 12) * px), ("hfs_band_kernel<2 (d Add_Square on store)", 12 * C * px), ("pgd_step_bcast_kernel", (16 * C + 4) * px)):
     print("  %-52s %8.2f MB" % (name, nbytes / 1e6))

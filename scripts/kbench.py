@@ -45,6 +45,8 @@ def main():
         _, _, _, sgx, sgy = ops.frontend_fwd_save(x, xh, wts, 0.0, 76 / 255, 1.0)
         u = torch.randn(B, 1, H, W, device=dev)
         gl, ge = ops.frontend_bwd(g, gate, x, wts, 0.0, 76 / 255, 1.0)
+        low = 25 / 255
+        _, thin, t2 = ops.canny_bpda_fwd(x, wts, low, 76 / 255)
         y = torch.randint(0, 200, (B,), device=dev)
         z = torch.randn(B, 200, device=dev)
         from eeadv import hfs as HF
@@ -71,6 +73,12 @@ def main():
             ("frontend_bwd_saved", lambda: ops.frontend_bwd_saved(g, gate, sgx, sgy, wts, 0.0, 76 / 255, 1.0), 16 * C * px),
             ("edge125_fwd", lambda: ops.edge125_fwd(x, wts, 0.0, 76 / 255), (C + 1) * 4 * px),
             ("edge125_bwd", lambda: ops.edge125_bwd(x, u, wts, 0.0, 76 / 255), (C + 2) * 4 * px),
+            ("canny_fwd", lambda: ops.canny_fwd(x, wts, 0.0, low, 76 / 255), (C + 1) * 4 * px),
+            ("canny_bwd", lambda: ops.canny_bwd(x, u, wts, 0.0, low, 76 / 255), (C + 2) * 4 * px),
+            ("canny_frontend_fwd", lambda: ops.canny_frontend_fwd(x, xh, wts, 0.0, low, 76 / 255, 1.0), 12 * C * px),
+            ("canny_frontend_bwd", lambda: ops.canny_frontend_bwd(g, gate, x, wts, 0.0, low, 76 / 255, 1.0), 16 * C * px),
+            ("canny_bpda_fwd", lambda: ops.canny_bpda_fwd(x, wts, low, 76 / 255), (C + 3) * 4 * px),
+            ("canny_bpda_bwd", lambda: ops.canny_bpda_bwd(x, u, thin, t2, wts, low, 76 / 255), (C + 6) * 4 * px),
             ("ce_grad", lambda: ops.ce(z, y, "sum", 0.0, False, True), 2 * B * 200 * 4),
         ]
         for name, fn, nbytes in rows:
